@@ -107,7 +107,13 @@ def parse():
                     help="also time candidate_verify + SearchLoop on the device (reported beside, never inside, value)")
     ap.add_argument("--boundary", choices=["on", "off"], default="on",
                     help="also time the per-frame host-pointer adapter path (reported beside value)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of `value` computed as DIR/<name>.npy (float64): the candidate tables of "
+                         "every query and the match lists of a fixed, seeded sample of them, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -363,6 +369,42 @@ def run_steps(step, sync, steps):
         step()
     sync()
     return time.perf_counter() - t0
+
+
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together, at most
+DUMP_SEED = 0               # the order in which queries are drawn for the sample of match lists
+DUMP_MAX_QUERIES = 64
+
+
+def dump_outputs(out_dir, arrays, pairs_of=None):
+    """--dump-outputs: `arrays` (name -> integer array, each value below 2^53 and so exact in float64) go whole to
+    out_dir/<name>.npy as float64.  With pairs_of(q) -> (q_idx, db_entry), the ordered match lists of query q, it also
+    writes the lists of a sample of the queries: drawn in a fixed, seeded order, each taken if its lists fit in what
+    DUMP_BYTES leaves, up to DUMP_MAX_QUERIES of them.  The sample's lists are concatenated in match_q_idx and
+    match_db_entry; sample_queries names the queries and sample_pair_off is where each one's pairs start."""
+    out = {k: np.asarray(v).astype(np.float64) for k, v in arrays.items()}
+    if pairs_of is not None:
+        cn = out["pair_off"].shape[1] - 1
+        n_pairs = out["pair_off"][:, cn].astype(np.int64)
+        room = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 16 * (DUMP_MAX_QUERIES + 1) - 8 * 128      # (npy headers)
+        picked, off = [], [0]
+        for q in np.random.default_rng(DUMP_SEED).permutation(len(n_pairs)):
+            if len(picked) == DUMP_MAX_QUERIES:
+                break
+            if 16 * (off[-1] + n_pairs[q]) <= room:
+                picked.append(int(q))
+                off.append(off[-1] + int(n_pairs[q]))
+        lists = [pairs_of(q) for q in picked]
+        out["sample_queries"] = np.array(picked, np.float64)
+        out["sample_pair_off"] = np.array(off, np.float64)
+        out["match_q_idx"] = np.concatenate([np.zeros(0)] + [qi for qi, _ in lists]).astype(np.float64)
+        out["match_db_entry"] = np.concatenate([np.zeros(0)] + [de for _, de in lists]).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    total = sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in out)
+    assert total <= DUMP_BYTES, total
+    return {"dir": out_dir, "bytes": total, "arrays": {k: list(a.shape) for k, a in out.items()}}
 
 
 def claim_stdout():
@@ -747,8 +789,7 @@ def rccl_one_leg(args):
     """runs rccl_one_child in a process of its own (a hung communicator set-up must not cost the measured line): a rendezvous
     on 127.0.0.1, WORLD_SIZE = 1"""
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()),
-               HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"),
-               GPU_MAX_HW_QUEUES=os.environ.get("GPU_MAX_HW_QUEUES", "8"))      # (as the ranks of an N > 1 run set it: main())
+               HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, os.path.abspath(__file__), "--rccl-one-child", "--frames", str(args.frames), "--keypoints", str(args.keypoints),
            "--queries", str(args.queries), "--steps", str(args.steps), "--rccl-one-shape", args.rccl_one_shape]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -780,13 +821,8 @@ def main():
             sys.stderr.write(p.stdout)
         sys.exit(p.returncode if (p.returncode or line is not None) else 1)
     world = int(env_world or "1")
-    if world > 1 and os.environ.get("SGTD_BENCH_SHARE_GPU") != "1":
-        # main stream, side stream and RCCL's own stream of every engine in flight: with the runtime's default of four
-        # hardware queues some of them share one and the exchange queues up behind the list pass (measured with a group of
-        # one: 0.13 ms of the step exposed at 4 queues, 0.04 at 8 — DESIGN.md §4); read by the HIP runtime when it starts.
-        # One process per GPU only: two processes with eight queues each on ONE device (the gloo test mode) are
-        # time-sliced against each other and run at half the rate (165 k -> 85 k frames/s, gpurun_out/r05an_*).
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+    # The number of hardware queues per process is left to the HIP runtime and the machine: GPUs shared between users
+    # cap it, and more queues than the card has slots can reset the device for everyone on it.
     if world != args.gpus:
         sys.exit("bench.py: --gpus %d but the launcher started WORLD_SIZE=%d ranks" % (args.gpus, world))
     result_out = claim_stdout()
@@ -1064,6 +1100,19 @@ def main():
         timed_info = {}
         elapsed = timed(fstep_, flight, info=timed_info)
         timed_info["batches_in_flight"] = args.in_flight
+    # --dump-outputs: the results of the region's last step (batch (K - 1) % n_rot), before any later step can overwrite
+    # them: the candidate tables and match lists of the handle that ran it or, with several ranks, the merged tables
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if m2 is None:
+            last = flight.h[(flight.k - 1) % len(flight.h)] if flight is not None else mgr
+            res_last = last.results()
+            dumped = dump_outputs(args.dump_outputs, {"n_cand": res_last.n_cand, "cand_frame": res_last.cand_frame,
+                                                      "cand_votes": res_last.cand_votes, "pair_off": res_last.pair_off},
+                                  lambda q: last.result_pairs(q, res_last))
+        else:
+            torch.cuda.synchronize()
+            dumped = dump_outputs(args.dump_outputs, {"cand_frame": merged["out"][0].cpu(), "cand_votes": merged["out"][1].cpu()})
     cur_step, cur_mgr = (fstep_, flight) if flight is not None else (step, mgr if m2 is None else mgr_all)
     # the headline region four more times (each with its own warm-up, barrier and overflow check): `value` stays the FIRST
     # region's — the contract's K steps — the spread of the five is reported beside it
@@ -1771,6 +1820,8 @@ def main():
             out["incremental_insert"] = incremental
         if rccl_one is not None:
             out["rccl_group_of_one"] = rccl_one
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if table_sharded is not None:
             out["table_sharded"] = table_sharded
         if fixed_total is not None:

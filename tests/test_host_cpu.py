@@ -157,6 +157,39 @@ def test_bench_finds_the_committed_traffic_row_of_its_default_workload():
     assert os.path.exists(os.path.join(ROOT, "profiles", "%s_kernel_stats.csv" % row["profile_tag"]))
 
 
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: every array as float64, the match lists of a seeded sample of the queries (the same
+    sample on every run, each query's pairs where sample_pair_off says), nothing beyond DUMP_BYTES"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    nq, cn = 300, 8
+    pair_off = np.concatenate([np.zeros((nq, 1), np.int64), np.cumsum(rng.integers(0, 400, (nq, cn)), axis=1)], axis=1)
+    arrays = {"n_cand": rng.integers(0, cn + 1, nq).astype(np.int32), "cand_frame": rng.integers(0, 1000, (nq, cn)).astype(np.int32),
+              "pair_off": pair_off}
+
+    def pairs_of(q):
+        n = int(pair_off[q, cn])
+        return (np.arange(n, dtype=np.int32) + q) % 97, np.arange(n, dtype=np.int64) * 1000003 + q
+    bench.DUMP_BYTES = 1 << 20
+    runs = [bench.dump_outputs(str(tmp_path / d), arrays, pairs_of) for d in ("a", "b")]
+    assert runs[0]["arrays"] == runs[1]["arrays"] and 0 < runs[0]["bytes"] <= bench.DUMP_BYTES
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted([k + ".npy" for k in arrays] + ["sample_queries.npy", "sample_pair_off.npy", "match_q_idx.npy", "match_db_entry.npy"])
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f[:-4]].dtype == np.float64 and np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f))
+    for k, v in arrays.items():
+        assert np.array_equal(got[k], v)
+    sample, off = got["sample_queries"].astype(np.int64), got["sample_pair_off"].astype(np.int64)
+    assert 0 < len(sample) < nq and len(set(sample.tolist())) == len(sample) and off[-1] == len(got["match_db_entry"])
+    for i, q in enumerate(sample):
+        qi, de = pairs_of(q)
+        assert np.array_equal(got["match_q_idx"][off[i]:off[i + 1]], qi) and np.array_equal(got["match_db_entry"][off[i]:off[i + 1]], de)
+
+
 def test_committed_traffic_row_describes_the_kernels_the_bench_launches():
     """bench.py refuses a PMC row that was taken on other kernels than the ones the run launches: the row committed
     under profiles/ for the default workload must carry the kernels of the per-query form (sgtd_stats.select_form 2),
