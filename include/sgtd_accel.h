@@ -214,6 +214,30 @@ int sgtd_attach_table(sgtd_handle view, sgtd_handle owner);
 int sgtd_query_frames(sgtd_handle h, const float *xyz, const uint32_t *label,
                       const int64_t *kp_off, int n_queries, int device_ptrs);
 
+/* Sequence loop detection: the reference's per-frame loop build -> SearchLoop -> AddSTDescs
+ * (STDesc.cpp:174-315, :84-147, :149-172) over n_frames frames in one batch.  Frames
+ * k = 0..n_frames-1 (keypoints kp_off[k]..kp_off[k+1]) are built and added to the table as
+ * sgtd_add_frames adds them: frame id c+k, where c = current_frame_id_ on entry, and
+ * current_frame_id_ += n_frames.  Each frame is then queried as a batch query q = k.  Its
+ * descriptors carry frame id c+k, and only table entries with frame id e such that
+ * e + skip_near < c+k count.  skip_near = 0 is the reference's result for build -> SearchLoop ->
+ * AddSTDescs run frame after frame (STDesc.cpp:373 under that call order); skip_near > 0 also
+ * leaves out the skip_near frames just before the query (upstream STD's skip_near_num_).
+ * Results are read as for sgtd_query_frames: sgtd_result_*, sgtd_verify, sgtd_search_loop,
+ * sgtd_result_rough.
+ * Chunking composes exactly: calls on frames 0..B-1, then B..2B-1, and so on give every frame
+ * the result one call on all frames gives — each chunk is added before it is queried, and each
+ * query sees only older frames.  That is how a caller stays under sgtd_max_batch, and how an
+ * online system calls it every B frames.  Entries already in the table (a map, an earlier
+ * session) are searched as the reference's sequential loop would search them.
+ * skip_near < 0 and the usual bad arguments: SGTD_ERR_INVALID; a view (sgtd_attach_table) cannot
+ * add frames: SGTD_ERR_STATE; a multi-device handle (sgtd_create_multi): SGTD_ERR_UNSUPPORTED
+ * (its round-robin frame blocks make the local frame index non-monotonic in the frame id);
+ * SGTD_ERR_FRAME_LIMIT as for sgtd_add_frames.  xyz/label are host pointers unless
+ * device_ptrs != 0 and must stay valid until the first sgtd_result_* call returns. */
+int sgtd_loop_frames(sgtd_handle h, const float *xyz, const uint32_t *label, const int64_t *kp_off,
+                     int n_frames, int32_t skip_near, int device_ptrs);
+
 /* candidate_selector on caller-provided descriptors (one query frame). */
 int sgtd_query_descs(sgtd_handle h, const sgtd_desc_soa *q, int64_t nq);
 

@@ -132,7 +132,7 @@ static_assert(sizeof(BucketDir) == 32 && SGTD_YSLICES == 2 && SGTD_ZSLICES == 3,
 struct __attribute__((aligned(64))) QueryRec {
   double q0, q1, q2;  // side_length_ (scaled)
   double thr2;        // exact squared match threshold (sq_threshold)
-  u32 qframe;         // frame_id_
+  u32 qframe;         // frame_id_ (a loop batch: the bound below which entries count, loop_bound_kernel)
   u32 gate;           // 27-bit mask of the probe cells that pass the 1.5 gate (gate_mask)
   u32 gid;            // key-major: group (home cell) of the descriptor
   u32 d;              // key-major: descriptor slot

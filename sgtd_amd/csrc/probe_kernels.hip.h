@@ -686,7 +686,7 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
                    q2 = __hiloint2double((int)b.y, (int)b.x);
       hq[k][0] = __float_as_uint((float)q0); hq[k][1] = __float_as_uint((float)q1); hq[k][2] = __float_as_uint((float)q2);
       hq[k][3] = e.x; hq[k][4] = e.y;
-      const u32 ql = c.x - T.map.frame_lo;
+      const u32 ql = c.x - T.map.frame_lo;      // (a loop batch: local_limit, loop_bound_kernel)
       qfr[k] = ql < T.frame_span ? ql : 0xFFFFFFFFu;
       gate[k] = c.y;
       const float t_up = __uint_as_float(e.z);
@@ -957,10 +957,14 @@ __device__ __forceinline__ u32 in_vgpr(u32 x) {
 // FRAMES = false: no descriptor of the batch carries a frame id the table holds (the reference
 // stamps every query descriptor with current_frame_id_, one beyond the map's last frame, quirk 1
 // of SURVEY §8a), so the frame test of :373 is true for every entry and is not evaluated.
+// BOUND (a loop batch, sgtd_loop_frames; FRAMES is set too): the header's frame word is the query's
+// local_limit and an entry counts when its local frame lies below it — the reference's order
+// build -> SearchLoop -> AddSTDescs, under which a frame only sees the frames added before it.
+// One unsigned compare per lane, like the != it replaces.
 // Registers: the loop's scalar state is, per column, the list's base address and its match count;
 // the thresholds and frames are wave-uniform values in VECTOR registers, the query sides scalar
 // pairs (packed operands), the streams' cursors are parked in WaveSlab::state.
-template <bool DIAG, bool WIDE, bool FRAMES, int K>
+template <bool DIAG, bool WIDE, bool FRAMES, bool BOUND, int K>
 __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffers &B, const QueryView &Q, double rough,
                                            const PassView &pv, u64 *bits, WaveSlab &slab, PendingLoads pending) {
   static_assert(!DIAG || K == 1, "the diagnostic sweep takes one descriptor at a time");
@@ -1152,8 +1156,8 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
       u32 id = __float_as_uint(v[u].w);
       // (the replay shares nothing with the first evaluation: no mask of the hot loop stays alive for it)
       if constexpr (PUSH) asm volatile("" : "+v"(id), "+v"(d2));
-      // unsigned (src.frame_id_ - db.frame_id_) > 0  <=>  frame ids differ (:373)
-      const bool other = !(FRAMES || DIAG) || qfv[k] != (id >> id_bits);
+      // unsigned (src.frame_id_ - db.frame_id_) > 0  <=>  frame ids differ (:373); BOUND: an older frame
+      const bool other = BOUND ? (id >> id_bits) < qfv[k] : (!(FRAMES || DIAG) || qfv[k] != (id >> id_bits));
       bool hit, amb = false;
       u64 m;
       double dis = 0.0;
@@ -1368,7 +1372,7 @@ struct TicketQueue {
 // of one wave, the other waves cover the LDS round trips of the locate step
 #define SGTD_SWEEP_WAVES
 #endif
-template <bool DIAG, bool WIDE, bool FRAMES>
+template <bool DIAG, bool WIDE, bool FRAMES, bool BOUND = false>
 __global__ __launch_bounds__(SGTD_PROBE_THREADS) SGTD_SWEEP_WAVES void probe_sorted_kernel(
     TableView T, ProbeBuffers B, QueryView Q, PassPool P, double rough, const u32 *n_valid_p, const u32 *n_groups_p,
     u32 chunk /* 1..SGTD_TICKET_MAX */) {
@@ -1450,7 +1454,7 @@ __global__ __launch_bounds__(SGTD_PROBE_THREADS) SGTD_SWEEP_WAVES void probe_sor
     }
     auto pass = [&](auto k_tag) {
       constexpr int KK = decltype(k_tag)::value;
-      sweep_pass<DIAG, WIDE, FRAMES, KK>(T, B, Q, rough, pv, s_bits[threadIdx.x >> 6], slab, pend);
+      sweep_pass<DIAG, WIDE, FRAMES, BOUND, KK>(T, B, Q, rough, pv, s_bits[threadIdx.x >> 6], slab, pend);
     };
     if constexpr (!DIAG && SGTD_PAIR >= 4) { if (kk == 4) pass(std::integral_constant<int, 4>{}); }
     if constexpr (!DIAG && SGTD_PAIR >= 2) { if (kk == 2) pass(std::integral_constant<int, 2>{}); }

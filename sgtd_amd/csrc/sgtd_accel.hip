@@ -162,6 +162,8 @@ struct sgtd_engine {
   std::vector<long long> last_kp_off;
   int last_max_n = 0;
   u32 last_qframe = 0;  // current_frame_id_ when the batch was enqueued (a re-run stamps the same id)
+  bool loop_batch = false;  // sgtd_loop_frames: query q is stamped last_qframe + q and sees the entries of frames
+  int loop_skip = 0;        // below last_qframe + q - loop_skip only (the sweep's BOUND variant)
   DevBuf totals;        // 3 x u64, zeroed once: batch_totals_kernel's running counts
   DevBuf cursors, list, n_visit, votes, slot_of;   // cursors: the batch's counters, overflow flags and ticket heads (ProbeBuffers::ctr)
   DevBuf q_M, q_P, q_pairs, q_pair_base, blk_count, rec, rec_cell, rec_dis;
@@ -1247,14 +1249,21 @@ int launch_select(sgtd_engine *e) {
       // sgtd_query_frames are stamped with the current frame id (one beyond the newest map frame
       // in the reference's use); descriptors handed in by the caller carry whatever they carry
       const bool frames = e->last_kind != 1 || (e->have_frames && e->last_qframe >= e->frame_lo && e->last_qframe <= e->frame_hi);
-#define SGTD_LAUNCH_SORTED(DG, WD, FR)                                                                          \
-  probe_sorted_kernel<DG, WD, FR><<<sgrid, SGTD_PROBE_THREADS, 0, e->stream>>>(                                 \
+      // a loop batch (sgtd_loop_frames) takes the BOUND variants: an entry counts when its frame lies below the query's bound
+#define SGTD_LAUNCH_SORTED(DG, WD, FR, BD)                                                                      \
+  probe_sorted_kernel<DG, WD, FR, BD><<<sgrid, SGTD_PROBE_THREADS, 0, e->stream>>>(                             \
       vs.T, vs.B, vs.Q, PP, e->dc.rough, e->n_valid.as<u32>(), e->n_groups.as<u32>(), chunk)
-      if (e->diag) SGTD_LAUNCH_SORTED(true, true, true);
-      else if (narrow && frames) SGTD_LAUNCH_SORTED(false, false, true);
-      else if (narrow) SGTD_LAUNCH_SORTED(false, false, false);
-      else if (frames) SGTD_LAUNCH_SORTED(false, true, true);
-      else SGTD_LAUNCH_SORTED(false, true, false);
+      if (e->diag) {
+        if (e->loop_batch) SGTD_LAUNCH_SORTED(true, true, true, true);
+        else SGTD_LAUNCH_SORTED(true, true, true, false);
+      } else if (e->loop_batch) {
+        if (narrow) SGTD_LAUNCH_SORTED(false, false, true, true);
+        else SGTD_LAUNCH_SORTED(false, true, true, true);
+      }
+      else if (narrow && frames) SGTD_LAUNCH_SORTED(false, false, true, false);
+      else if (narrow) SGTD_LAUNCH_SORTED(false, false, false, false);
+      else if (frames) SGTD_LAUNCH_SORTED(false, true, true, false);
+      else SGTD_LAUNCH_SORTED(false, true, false, false);
 #undef SGTD_LAUNCH_SORTED
       HIPCHK(hipGetLastError());
       resolve_undecided_kernel<<<64, 256, 0, e->stream>>>(vs.T, vs.Q, vs.B, e->q_M.as<u32>());
@@ -1392,7 +1401,12 @@ int enqueue_frames(sgtd_engine *e) {
   const int nq = e->nq;
   if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_START], e->stream));
   CHK(launch_build(e, e->last_xyz, e->last_label, e->kp_off_dev.as<long long>(), nq, e->last_max_n,
-                   e->last_qframe, 0, e->qd.view(), e->q_stride, e->q_count.as<u32>()));
+                   e->last_qframe, e->loop_batch ? 1 : 0, e->qd.view(), e->q_stride, e->q_count.as<u32>()));
+  if (e->loop_batch) {
+    loop_bound_kernel<<<grid_for(e->q_stride * nq, 256), 256, 0, e->stream>>>(e->qd.qrec.as<QueryRec>(), e->q_stride, nq, e->last_qframe,
+                                                                             e->loop_skip, e->have_frames ? e->frame_lo : 0);
+    HIPCHK(hipGetLastError());
+  }
   if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_BUILD], e->stream));
   return launch_select(e);
 }
@@ -2030,18 +2044,17 @@ int sgtd_finalize(sgtd_handle e) {
   return do_finalize(e);
 }
 
-int sgtd_query_frames(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
-                      int n_queries, int device_ptrs) {
-  if (e && e->grp) return multi::query_frames(e, xyz, label, kp_off, n_queries, device_ptrs);
-  if (!e || n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
-  HIPCHK(hipSetDevice(e->cfg.device_id));
+// a batch of query frames built on the device: query q is stamped qframe (loop: qframe + q and the sweep's bound)
+static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
+                              int n_queries, int device_ptrs, u32 qframe, bool loop, int32_t skip_near) {
   CHK(settle_tail(e));
   const float *dx; const u32 *dl; int max_n;
   CHK(stage_inputs(e, xyz, label, kp_off, n_queries, device_ptrs, &dx, &dl, &max_n));
   e->nq = n_queries;
   e->q_stride = (long long)std::max(max_n, 1) * e->dc.tpi;
   e->last_kind = 1; e->last_xyz = dx; e->last_label = dl; e->last_max_n = max_n;
-  e->last_qframe = e->current_frame_id;
+  e->last_qframe = qframe;
+  e->loop_batch = loop; e->loop_skip = loop ? skip_near : 0;
   e->diag = false;   // a new batch runs the product sweep; sgtd_result_rough re-runs it in the diagnostic form
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);   // (a cap a re-run needed recovers slowly)
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride * n_queries));
@@ -2065,6 +2078,31 @@ int sgtd_query_frames(sgtd_handle e, const float *xyz, const uint32_t *label, co
   return enqueue_frames(e);
 }
 
+int sgtd_query_frames(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
+                      int n_queries, int device_ptrs) {
+  if (e && e->grp) return multi::query_frames(e, xyz, label, kp_off, n_queries, device_ptrs);
+  if (!e || n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  return query_frames_batch(e, xyz, label, kp_off, n_queries, device_ptrs, e->current_frame_id, false, 0);
+}
+
+int sgtd_loop_frames(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
+                     int n_frames, int32_t skip_near, int device_ptrs) {
+  if (e && e->grp) {
+    // (its round-robin frame blocks make the local frame index non-monotonic in the frame id: a bound on it would be wrong)
+    e->err = "not available on a multi-device handle";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (!e || n_frames <= 0 || !kp_off || !xyz || !label || skip_near < 0) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  if (e->attached_to) { e->err = "the table belongs to another handle (sgtd_attach_table): a view cannot add frames"; return SGTD_ERR_STATE; }
+  const u32 c = e->current_frame_id;
+  // the frames join the table first (sgtd_add_frames' build stamps c + k), then every frame is a query that sees
+  // only what was added before it: the bound c + k - skip_near
+  CHK(sgtd_add_frames(e, xyz, label, kp_off, n_frames, device_ptrs));
+  return query_frames_batch(e, xyz, label, kp_off, n_frames, device_ptrs, c, true, skip_near);
+}
+
 int sgtd_query_descs(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq) {
   if (e && e->grp) return multi::query_descs(e, q, nq);
   if (!e || nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame))) return SGTD_ERR_INVALID;
@@ -2073,6 +2111,7 @@ int sgtd_query_descs(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq) {
   e->nq = 1;
   e->q_stride = std::max<long long>(nq, 1);
   e->last_kind = 2;
+  e->loop_batch = false;
   e->diag = false;
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
@@ -2662,6 +2701,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   e->nq = 1;
   e->q_stride = std::max<long long>(nq, 1);
   e->last_kind = 2;
+  e->loop_batch = false;
   e->diag = false;
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride));

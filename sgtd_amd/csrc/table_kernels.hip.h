@@ -371,6 +371,17 @@ __global__ __launch_bounds__(256) void slice_partition_kernel(const u32 *bucket_
   }
 }
 
+// a loop batch (sgtd_loop_frames): the sweep record of every descriptor slot of query q carries, instead
+// of its frame, the frame below which table entries count — max(frame0 + q - skip_near, frame_lo), so the
+// plan's header word (local frame of the record's frame) is local_limit = c + q - skip_near - frame_lo
+// clamped at 0 (nothing counts).  frame0 + q - skip_near never exceeds the newest added frame.
+__global__ void loop_bound_kernel(QueryRec *qrec, long long stride, int nq, u32 frame0, int skip_near, u32 frame_lo) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= stride * nq) return;
+  const long long lim = (long long)frame0 + i / stride - skip_near;
+  qrec[i].qframe = (u32)(lim < (long long)frame_lo ? (long long)frame_lo : lim);
+}
+
 // squared thresholds for caller-provided query descriptors
 __global__ void thr2_kernel(const double *side, const u32 *frame, QueryRec *qrec, long long n, double rough) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

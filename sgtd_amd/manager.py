@@ -228,6 +228,37 @@ class STDescManager:
         self._check(self._L.sgtd_query_frames(self._h, xp, lp, _p(off), nq, dev))
         return self.results() if fetch else None
 
+    def loop_frames(self, xyz, label, kp_off=None, skip_near=0, batch=None, fetch=True):
+        """sequence loop detection (sgtd_loop_frames): every frame is added to the table and searched against the
+        frames added before it, minus the skip_near frames just before it — the reference's per-frame
+        build -> SearchLoop -> AddSTDescs loop (skip_near = 0).  Runs in chunks of at most `batch` frames (None:
+        sgtd_max_batch); chunking does not change any frame's result.  fetch=True returns the candidates of every frame
+        as one BatchResult (query_frame_id: the frames' ids).  verify(), search_loop() and the result_* calls then
+        refer to the last chunk — a caller that wants them for every frame passes `batch` and one chunk per call."""
+        xp, lp, off, nf, dev = self._frames_args(xyz, label, kp_off)
+        if nf == 0:
+            return None
+        if batch is None:
+            batch = self.max_batch(int(np.max(off[1:] - off[:-1])))
+        batch = max(1, int(batch))
+        c0 = self.current_frame_id_
+        parts = []
+        for f0 in range(0, nf, batch):
+            n = min(batch, nf - f0)
+            st = self._L.sgtd_loop_frames(self._h, xp, lp, _p(np.ascontiguousarray(off[f0:f0 + n + 1])), n, int(skip_near), dev)
+            if st == -6 and self.device_count > 1:
+                raise SgtdError(st, "loop_frames is not available on a multi-device handle (devices=[...]): "
+                                    "use one STDescManager per device")
+            self._check(st)
+            self._nq = n
+            if fetch:
+                parts.append(self.results())
+        if not fetch:
+            return None
+        res = BatchResult(*(np.concatenate([getattr(r, k) for r in parts]) for k in ("n_cand", "cand_frame", "cand_votes", "pair_off")),
+                          c0 + np.arange(nf, dtype=np.int64))
+        return res
+
     def results(self):
         nq, cn = self._nq, self.config_setting_["candidate_num"]
         n_cand = np.zeros(nq, np.int32)
