@@ -409,8 +409,10 @@ __global__ __launch_bounds__(SGTD_VERIFY_THREADS) SGTD_VERIFY_WAVES void verify_
         const float a0 = qp[3 * m], a1 = qp[3 * m + 1], a2 = qp[3 * m + 2];
         const float b0 = ep[3 * m], b1 = ep[3 * m + 1], b2 = ep[3 * m + 2];
         const float s1 = (fabsf(a0) + fabsf(a1)) + fabsf(a2), s2 = (fabsf(b0) + fabsf(b1)) + fabsf(b2);
-        vmax = !(s1 <= vmax) ? s1 : vmax;                           // max that keeps a NaN
-        wmax = !(s2 <= wmax) ? s2 : wmax;
+        // max that keeps a NaN, wherever it comes: a NaN maximum stays (`!(s <= max)` alone would let a later finite
+        // vertex replace it, and the NaN vertex's distance, which fmaxf drops below, would let the pair vote for sure)
+        vmax = (s1 <= vmax || vmax != vmax) ? vmax : s1;
+        wmax = (s2 <= wmax || wmax != wmax) ? wmax : s2;
         if (u == 0) { v[m][0].x = a0; v[m][1].x = a1; v[m][2].x = a2; w[m][0].x = b0; w[m][1].x = b1; w[m][2].x = b2; }
         else { v[m][0].y = a0; v[m][1].y = a1; v[m][2].y = a2; w[m][0].y = b0; w[m][1].y = b1; w[m][2].y = b2; }
       }
