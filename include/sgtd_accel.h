@@ -193,12 +193,26 @@ int sgtd_add_frames(sgtd_handle h, const float *xyz, const uint32_t *label,
  * .ms_finalize). */
 int sgtd_finalize(sgtd_handle h);
 
+/* Takes sessions out of a built table (the reference only appends, STDesc.cpp:149-172).  Every entry whose frame id is
+ * in frame_ids[0..n) is removed; duplicates and ids without entries are ignored.  Afterwards the handle answers every
+ * query and inspection call as a handle would to which those frames were never added: the surviving entries keep
+ * their insertion order and their insertion indices are renumbered densely (db_entry, sgtd_fetch_entries,
+ * sgtd_table_dump, sgtd_save_table); frame_lo / frame_hi and the entry and bucket counts of sgtd_stats describe the
+ * survivors, and n_frames loses one for every removed frame that had entries.  current_frame_id_ does not change and
+ * removed ids are not reused; a table left empty behaves as a fresh handle's.  The pending batch is dropped and the
+ * table version changes: views (sgtd_attach_table) return SGTD_ERR_STATE until attached again.  The next finalize
+ * builds one segment over the whole table.  A call that removes nothing changes nothing.  *n_removed (may be NULL):
+ * the number of entries removed.  h == NULL, n < 0 or frame_ids == NULL with n > 0: SGTD_ERR_INVALID; a view:
+ * SGTD_ERR_STATE.  A multi-device handle forwards each id to the shard that owns it; group entry ids keep their form.
+ * Device memory: 36 B per surviving entry beyond the table, for the duration of the call. */
+int sgtd_remove_frames(sgtd_handle h, const uint32_t *frame_ids, int64_t n, int64_t *n_removed);
+
 /* Two (or more) batches in flight over ONE map: `view` — a handle of the same configuration on the same device,
  * without a table of its own — borrows the finalized table of `owner` (cold entries, probe layout, entry ids) and keeps
  * its own work buffers, results and stream.  Batches enqueued alternately on the two handles' streams overlap on the
  * device: the descriptor build, home-cell sort and plan of one run beside the passes over the other's match records.
  * The owner must outlive its views (sgtd_destroy of an owner with views is SGTD_ERR_STATE); after anything that changes
- * the owner's table (sgtd_add*, sgtd_load_table, a finalize that merges a tail — the owner's own fifth batch on a tail
+ * the owner's table (sgtd_add*, sgtd_remove_frames, sgtd_load_table, a finalize that merges a tail — the owner's own fifth batch on a tail
  * does) every call of a view that would touch the table again returns SGTD_ERR_STATE until it is attached again: the next
  * query, and for a batch still pending sgtd_sync / sgtd_verify* / sgtd_search_loop / the result calls that gather entries
  * (the view's batch is dropped; nothing reads the owner's freed buffers).  A view cannot add, load or rebuild (SGTD_ERR_STATE).  Neither handle

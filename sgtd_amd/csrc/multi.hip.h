@@ -42,6 +42,7 @@ int build(sgtd_engine *e, const float *xyz, const uint32_t *label, int n, sgtd_d
 int add(sgtd_engine *e, const sgtd_desc_soa *d, int64_t n);
 int add_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_frames, int device_ptrs);
 int finalize(sgtd_engine *e);
+int remove_frames(sgtd_engine *e, const uint32_t *frame_ids, int64_t n, int64_t *n_removed);
 int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_queries, int device_ptrs);
 int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq);
 int result_candidates(sgtd_engine *e, int32_t *n_cand, int32_t *cand_frame, int32_t *cand_votes, int64_t *pair_off);

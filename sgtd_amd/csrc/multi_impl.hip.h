@@ -109,6 +109,26 @@ int finalize(sgtd_engine *e) {
   return SGTD_OK;
 }
 
+// every global id goes to its owner as the owner's local id; entry ids keep their shard << 40 form (each shard's
+// insertion indices are renumbered densely on the shard)
+int remove_frames(sgtd_engine *e, const uint32_t *frame_ids, int64_t n, int64_t *n_removed) {
+  if (n < 0 || (n > 0 && !frame_ids)) return SGTD_ERR_INVALID;
+  Group *g = G(e);
+  std::vector<std::vector<uint32_t>> loc(g->n);
+  for (int64_t i = 0; i < n; i++) loc[shard_of(frame_ids[i], g->n)].push_back(local_of(frame_ids[i], g->n));
+  int64_t total = 0;
+  for (int s = 0; s < g->n; s++) {
+    if (loc[s].empty()) continue;
+    sgtd_engine *c = g->dev[s];
+    int64_t r = 0;
+    MCHK(sgtd_remove_frames(c, loc[s].data(), (int64_t)loc[s].size(), &r));
+    total += r;
+  }
+  if (total > 0) g->batch_valid = false;
+  if (n_removed) *n_removed = total;
+  return SGTD_OK;
+}
+
 int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_queries, int device_ptrs) {
   if (n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
   Group *g = G(e);

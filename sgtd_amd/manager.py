@@ -190,6 +190,18 @@ class STDescManager:
     def finalize(self):
         self._check(self._L.sgtd_finalize(self._h))
 
+    def remove_frames(self, frame_ids):
+        """take the entries of the given frames out of the table (sgtd_remove_frames): afterwards every query and
+        inspection call answers as if those frames had never been added; entry ids are renumbered densely and
+        current_frame_id_ does not change.  Duplicates and ids without entries are ignored.  -> entries removed"""
+        ids = np.ascontiguousarray(np.asarray(frame_ids, dtype=np.int64).reshape(-1))
+        if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+            raise ValueError("frame ids must lie in [0, 2^32)")
+        ids = ids.astype(np.uint32)
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_remove_frames(self._h, _p(ids) if ids.size else None, ids.size, C.byref(n)))
+        return n.value
+
     def attach_table(self, owner):
         """borrow the finalized table of `owner` (another manager on the same device): this manager then queries the
         same map with its own work buffers and stream — two batches in flight (include/sgtd_accel.h)"""
