@@ -207,6 +207,22 @@ int sgtd_finalize(sgtd_handle h);
  * Device memory: 36 B per surviving entry beyond the table, for the duration of the call. */
 int sgtd_remove_frames(sgtd_handle h, const uint32_t *frame_ids, int64_t n, int64_t *n_removed);
 
+/* Restrict later queries to a set of frames.  Row r holds ceil(n_frames / 64) words; bit (f - frame_lo)
+ * (word (f - frame_lo) >> 6, bit (f - frame_lo) & 63) set means frame f is allowed.  Frames outside
+ * [frame_lo, frame_lo + n_frames) are never allowed.  n_rows == 1: one row for every query of a batch;
+ * n_rows > 1: row q for query q.  rows == NULL with n_rows == 0 clears the filter. */
+/* The rows are copied at the call and hold for every later sgtd_query_frames, sgtd_query_descs and sgtd_search_frame
+ * until replaced or cleared (a batch keeps the rows it was enqueued with, re-runs included).  Each query is answered as
+ * by a handle that holds only its allowed frames (same ids, order and current_frame_id_): candidates, votes (0 for
+ * frames not allowed), match lists, per-query match count M, verification, SearchLoop's choice, the rough list.  Only
+ * the visit counters (P, n_visit) still count the whole map.  Frame ids are global: sgtd_add*, sgtd_remove_frames and
+ * sgtd_load_table leave the filter alone, and frames added later are outside it unless the range covers them.  A view
+ * (sgtd_attach_table) has a filter of its own; a multi-device handle slices the rows into each shard's frames.  A
+ * query call whose batch size differs from n_rows > 1 (sgtd_query_descs and sgtd_search_frame are batches of one):
+ * SGTD_ERR_INVALID; sgtd_loop_frames with a filter set: SGTD_ERR_STATE.  h == NULL, n_rows < 0, rows == NULL with
+ * n_rows > 0 or n_frames == 0 with n_rows > 0: SGTD_ERR_INVALID, before the device is touched. */
+int sgtd_set_frame_filter(sgtd_handle h, uint32_t frame_lo, uint32_t n_frames, const uint64_t *rows, int n_rows);
+
 /* Two (or more) batches in flight over ONE map: `view` — a handle of the same configuration on the same device,
  * without a table of its own — borrows the finalized table of `owner` (cold entries, probe layout, entry ids) and keeps
  * its own work buffers, results and stream.  Batches enqueued alternately on the two handles' streams overlap on the

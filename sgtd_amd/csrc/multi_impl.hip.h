@@ -129,8 +129,55 @@ int remove_frames(sgtd_engine *e, const uint32_t *frame_ids, int64_t n, int64_t 
   return SGTD_OK;
 }
 
+// every shard gets the rows sliced to its own frames in its local ids.  A shard holds whole blocks of SGTD_SHARD_BLOCK
+// (64) frames, global block b as its local block b / n: each of its blocks is one word of its rows, read from the global
+// row at bit b * 64 - frame_lo.  A shard without a frame in [frame_lo, frame_lo + n_frames) allows nothing.
+int set_frame_filter(sgtd_engine *e, uint32_t frame_lo, uint32_t n_frames, const uint64_t *rows, int n_rows) {
+  Group *g = G(e);
+  if (n_rows == 0) {
+    for (sgtd_engine *c : g->dev) MCHK(sgtd_set_frame_filter(c, 0, 0, nullptr, 0));
+    e->filt.reset();
+    return SGTD_OK;
+  }
+  auto F = std::make_shared<FrameFilter>();
+  F->lo = frame_lo; F->n = n_frames; F->n_rows = n_rows;      // (the group's own copy: the row count for filter_fits)
+  e->filt = std::move(F);
+  static_assert(SGTD_SHARD_BLOCK == 64, "a shard's block is one word of its rows");
+  const size_t words = ((size_t)n_frames + 63) / 64;
+  const u64 b_first = frame_lo / SGTD_SHARD_BLOCK, b_last = ((u64)frame_lo + n_frames - 1) / SGTD_SHARD_BLOCK;
+  std::vector<uint64_t> loc;
+  std::vector<u64> clean((size_t)n_rows * words);      // the caller's rows with the bits beyond n_frames cleared
+  for (int r = 0; r < n_rows; r++)
+    for (size_t w = 0; w < words; w++) {
+      u64 v = rows[(size_t)r * words + w];
+      if (w == words - 1 && n_frames % 64) v &= (1ull << (n_frames % 64)) - 1ull;
+      clean[(size_t)r * words + w] = v;
+    }
+  for (int s = 0; s < g->n; s++) {
+    sgtd_engine *c = g->dev[s];
+    // the shard's first and last block inside the range
+    u64 b0 = b_first + ((u64)s + g->n - b_first % g->n) % g->n;
+    if (b0 > b_last) {
+      const std::vector<uint64_t> none((size_t)n_rows, 0u);
+      MCHK(sgtd_set_frame_filter(c, 0, 1, none.data(), n_rows));
+      continue;
+    }
+    const u64 b1 = b_last - ((b_last + g->n - s) % g->n);
+    const u64 lb0 = b0 / g->n, n_blocks = b1 / g->n - lb0 + 1;
+    loc.assign((size_t)n_rows * n_blocks, 0u);
+    for (int r = 0; r < n_rows; r++)
+      for (u64 k = 0; k < n_blocks; k++) {
+        const u64 b = (lb0 + k) * g->n + s;
+        loc[(size_t)r * n_blocks + k] = row_bits_at(clean.data() + (size_t)r * words, words, (long long)(b * SGTD_SHARD_BLOCK) - (long long)frame_lo);
+      }
+    MCHK(sgtd_set_frame_filter(c, (uint32_t)(lb0 * SGTD_SHARD_BLOCK), (uint32_t)(n_blocks * SGTD_SHARD_BLOCK), loc.data(), n_rows));
+  }
+  return SGTD_OK;
+}
+
 int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_queries, int device_ptrs) {
   if (n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
+  CHK(filter_fits(e, n_queries));
   Group *g = G(e);
   if (device_ptrs) { e->err = "multi-device tables take host pointers"; return SGTD_ERR_UNSUPPORTED; }
   // every device builds the query descriptors itself and sweeps its shard; the calls only
@@ -142,6 +189,7 @@ int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const 
 
 int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq) {
   if (nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame))) return SGTD_ERR_INVALID;
+  CHK(filter_fits(e, 1));
   Group *g = G(e);
   std::vector<uint32_t> lf((size_t)std::max<int64_t>(nq, 1));
   for (int s = 0; s < g->n; s++) {

@@ -6,9 +6,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -21,6 +23,7 @@
 #include "verify_mfma.hip.h"
 #include "exchange_kernels.hip.h"
 #include "remove_kernels.hip.h"
+#include "filter_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -46,6 +49,25 @@ struct DescStore {
     return a;
   }
 };
+
+// sgtd_set_frame_filter's rows as the caller gave them: bit f - lo of row r (word (f - lo) >> 6) set = frame f allowed
+// to query r (every query when n_rows == 1); the bits beyond n of a row's last word are cleared
+struct FrameFilter {
+  u32 lo = 0, n = 0;
+  int n_rows = 0;
+  size_t words = 0;          // per row
+  std::vector<u64> rows;
+  u64 serial = 0;            // distinct for every filter a process makes
+  const u64 *row(int r) const { return rows.data() + (size_t)(n_rows == 1 ? 0 : r) * words; }
+};
+
+// bits s .. s + 63 of a bit row of `words` 64-bit words (bit i: word i >> 6, bit i & 63); bits outside the row read 0
+static u64 row_bits_at(const u64 *row, size_t words, long long s) {
+  const long long w = s >= 0 ? s / 64 : -((-s + 63) / 64);
+  const int sh = (int)(s - w * 64);
+  auto word = [&](long long i) -> u64 { return i >= 0 && i < (long long)words ? row[i] : 0ull; };
+  return sh == 0 ? word(w) : (word(w) >> sh) | (word(w + 1) << (64 - sh));
+}
 
 // A host array in page-locked memory (grow-only): the per-batch result tables land here by direct DMA — a copy into
 // pageable memory goes through the runtime's staging at about a third of the rate (and ~150 us each on this runtime).
@@ -141,6 +163,14 @@ struct sgtd_engine {
   // sgtd_remove_frames: the removed set and the frames that have entries (bitmaps over the frame span), keep masks,
   // survivor counts per tile, and the out-of-place scratch of one field (freed when the call returns)
   DevBuf rm_bits, rm_present, rm_mask, rm_count, rm_scratch;
+  // sgtd_set_frame_filter: the caller's rows (global frame ids; replaced as a whole, never changed), and the rows the
+  // pending batch was enqueued with — a re-run filters with these whatever was set since.  filt_rows: the batch rows
+  // re-based to the table's frame span on the device (filter_kernels.hip.h), made for (filt_rows_serial, _lo, _span)
+  std::shared_ptr<const FrameFilter> filt, batch_filt;
+  DevBuf filt_rows;
+  std::vector<u64> filt_host;      // (the source of their upload)
+  u64 filt_rows_serial = 0;
+  u32 filt_rows_lo = 0, filt_rows_span = 0;
   // sort scratch
   DevBuf keyA, keyB, valA, valB, hist, digit_tot, flags, bad_flag;
   std::vector<DevBuf> scan_lvl;
@@ -1044,6 +1074,53 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
   return SGTD_OK;
 }
 
+// The batch's filter rows re-based to the table's frame span: bit f of device row r = frame frame_lo + f allowed.  Made
+// again only when the rows or the span change (a batch of the same filter on the same table reuses them).
+int prepare_filter(sgtd_engine *e, u32 frame_lo, u32 span) {
+  const FrameFilter &F = *e->batch_filt;
+  if (e->filt_rows.p && F.serial == e->filt_rows_serial && frame_lo == e->filt_rows_lo && span == e->filt_rows_span) return SGTD_OK;
+  const int n_rows = F.n_rows == 1 ? 1 : e->nq;
+  const size_t words = ((size_t)span + 63) / 64;
+  e->filt_host.assign((size_t)n_rows * words, 0ull);
+  const long long shift = (long long)frame_lo - (long long)F.lo;
+  const u64 last = span % 64 ? (1ull << (span % 64)) - 1ull : ~0ull;
+  for (int r = 0; r < n_rows; r++) {
+    u64 *dst = e->filt_host.data() + (size_t)r * words;
+    for (size_t w = 0; w < words; w++) dst[w] = row_bits_at(F.row(r), F.words, shift + (long long)w * 64);
+    dst[words - 1] &= last;
+  }
+  CHK(ensure(e, e->filt_rows, e->filt_host.size() * sizeof(u64)));
+  CHK(h2d(e, e->filt_rows.p, e->filt_host.data(), e->filt_host.size() * sizeof(u64)));
+  e->filt_rows_serial = F.serial; e->filt_rows_lo = frame_lo; e->filt_rows_span = span;
+  return SGTD_OK;
+}
+
+// filter_kernels.hip.h, right after the sweep's undecided records are resolved: the records of frames a query may not
+// see die (the diagnostic build: leave their lists)
+int launch_filter(sgtd_engine *e, const Views &v) {
+  const int nq = e->nq, n_rows = e->batch_filt->n_rows == 1 ? 1 : nq;
+  const u32 words = (v.span + 63) / 64;
+  // workgroups per query: one once the batch fills the chip (8 per CU), more for small batches (one frame per call:
+  // its ~4 500 lists over 18 workgroups), never more than its 64-list chunks need
+  const long long chunks = (e->q_stride + SGTD_WAVE - 1) / SGTD_WAVE;
+  const int want = (int)std::max<long long>(1, ((long long)e->n_cus * 8 + nq - 1) / nq);
+  const int wg_per_q = (int)std::max<long long>(1, std::min<long long>(want, (chunks + SGTD_FILT_WAVES - 1) / SGTD_FILT_WAVES));
+  const int grid = nq * wg_per_q;
+  const size_t lds = (size_t)words * sizeof(u64);
+  const u64 *rows = e->filt_rows.as<u64>();
+  if (e->diag) {
+    if (lds <= 65536) filter_compact_kernel<true><<<grid, SGTD_FILT_THREADS, lds, e->stream>>>(v.Q, v.B, rows, n_rows, words, v.span, wg_per_q);
+    else filter_compact_kernel<false><<<grid, SGTD_FILT_THREADS, 0, e->stream>>>(v.Q, v.B, rows, n_rows, words, v.span, wg_per_q);
+  } else {
+    if (lds <= 65536)
+      filter_records_kernel<true><<<grid, SGTD_FILT_THREADS, lds, e->stream>>>(v.Q, v.B, rows, n_rows, words, v.span, wg_per_q, e->q_M.as<u32>());
+    else
+      filter_records_kernel<false><<<grid, SGTD_FILT_THREADS, 0, e->stream>>>(v.Q, v.B, rows, n_rows, words, v.span, wg_per_q, e->q_M.as<u32>());
+  }
+  HIPCHK(hipGetLastError());
+  return SGTD_OK;
+}
+
 int launch_select(sgtd_engine *e) {
   const int nq = e->nq;
   const long long n_slots = (long long)nq * e->q_stride;
@@ -1069,6 +1146,7 @@ int launch_select(sgtd_engine *e) {
   CHK(ensure(e, e->cand_frame, (size_t)nq * cn * sizeof(int)));
   CHK(ensure(e, e->cand_votes, (size_t)nq * cn * sizeof(int)));
   CHK(ensure(e, e->pair_off, (size_t)nq * (cn + 1) * sizeof(long long)));
+  if (e->batch_filt) CHK(prepare_filter(e, e->have_frames ? e->frame_lo : 0, span));
 
   // Which passes over the match records (STDesc.cpp:404-453): one workgroup per query (select_kernels.hip.h) when
   // the batch has a query for every CU — votes + top-k in one launch while the query's vote histogram fits LDS,
@@ -1272,6 +1350,7 @@ int launch_select(sgtd_engine *e) {
       HIPCHK(hipGetLastError());
       resolve_undecided_kernel<<<64, 256, 0, e->stream>>>(vs.T, vs.Q, vs.B, e->q_M.as<u32>());
       HIPCHK(hipGetLastError());
+      if (e->batch_filt) CHK(launch_filter(e, vs));
     }
     HIPCHK(hipGetLastError());
 #ifdef SGTD_EXP_PHASE
@@ -1886,7 +1965,7 @@ int sgtd_destroy(sgtd_handle e) {
                     // (the entry-id map: missing from this list until the engine's host code ran under the sanitizers — every destroyed
                     // handle kept them, 8 bytes per map frame and, with frame ids out of insertion order, 8 bytes per entry)
                     &e->frame_first, &e->by_frame, &e->id_of_g, &e->longest,
-                    &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch};
+                    &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows};
   for (DevBuf *b : bufs) free_buf(*b);
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
@@ -2152,6 +2231,15 @@ int sgtd_finalize(sgtd_handle e) {
 }
 
 // a batch of query frames built on the device: query q is stamped qframe (loop: qframe + q and the sweep's bound)
+// a batch of n_queries against the filter's rows: one row for all, or one per query
+static int filter_fits(sgtd_engine *e, int n_queries) {
+  if (e->filt && e->filt->n_rows > 1 && e->filt->n_rows != n_queries) {
+    e->err = "the frame filter has " + std::to_string(e->filt->n_rows) + " rows for a batch of " + std::to_string(n_queries) + " queries";
+    return SGTD_ERR_INVALID;
+  }
+  return SGTD_OK;
+}
+
 static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
                               int n_queries, int device_ptrs, u32 qframe, bool loop, int32_t skip_near) {
   CHK(settle_tail(e));
@@ -2162,6 +2250,7 @@ static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *l
   e->last_kind = 1; e->last_xyz = dx; e->last_label = dl; e->last_max_n = max_n;
   e->last_qframe = qframe;
   e->loop_batch = loop; e->loop_skip = loop ? skip_near : 0;
+  e->batch_filt = loop ? nullptr : e->filt;
   e->diag = false;   // a new batch runs the product sweep; sgtd_result_rough re-runs it in the diagnostic form
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);   // (a cap a re-run needed recovers slowly)
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride * n_queries));
@@ -2189,6 +2278,7 @@ int sgtd_query_frames(sgtd_handle e, const float *xyz, const uint32_t *label, co
                       int n_queries, int device_ptrs) {
   if (e && e->grp) return multi::query_frames(e, xyz, label, kp_off, n_queries, device_ptrs);
   if (!e || n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
+  CHK(filter_fits(e, n_queries));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   return query_frames_batch(e, xyz, label, kp_off, n_queries, device_ptrs, e->current_frame_id, false, 0);
 }
@@ -2201,6 +2291,7 @@ int sgtd_loop_frames(sgtd_handle e, const float *xyz, const uint32_t *label, con
     return SGTD_ERR_UNSUPPORTED;
   }
   if (!e || n_frames <= 0 || !kp_off || !xyz || !label || skip_near < 0) return SGTD_ERR_INVALID;
+  if (e->filt) { e->err = "a frame filter is set (sgtd_set_frame_filter): clear it before sgtd_loop_frames"; return SGTD_ERR_STATE; }
   HIPCHK(hipSetDevice(e->cfg.device_id));
   if (e->attached_to) { e->err = "the table belongs to another handle (sgtd_attach_table): a view cannot add frames"; return SGTD_ERR_STATE; }
   const u32 c = e->current_frame_id;
@@ -2213,12 +2304,14 @@ int sgtd_loop_frames(sgtd_handle e, const float *xyz, const uint32_t *label, con
 int sgtd_query_descs(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq) {
   if (e && e->grp) return multi::query_descs(e, q, nq);
   if (!e || nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame))) return SGTD_ERR_INVALID;
+  CHK(filter_fits(e, 1));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   CHK(settle_tail(e));
   e->nq = 1;
   e->q_stride = std::max<long long>(nq, 1);
   e->last_kind = 2;
   e->loop_batch = false;
+  e->batch_filt = e->filt;
   e->diag = false;
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
@@ -2788,6 +2881,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   PinScope pin_scope(e && !e->grp ? e : nullptr);
   if (e && e->grp) { e->err = "not available on a multi-device handle"; return SGTD_ERR_UNSUPPORTED; }
   if (!e || !io || nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame)) || io->capacity < 0) return SGTD_ERR_INVALID;
+  CHK(filter_fits(e, 1));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   const int cn = e->dc.cand_num;
   const bool lists_only = (io->flags & SGTD_FRAME_LISTS_ONLY) != 0;     // candidate_selector alone: no verification, every pair of every list
@@ -2809,6 +2903,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   e->q_stride = std::max<long long>(nq, 1);
   e->last_kind = 2;
   e->loop_batch = false;
+  e->batch_filt = e->filt;
   e->diag = false;
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
@@ -3083,6 +3178,22 @@ int sgtd_remove_frames(sgtd_handle e, const uint32_t *frame_ids, int64_t n, int6
   int64_t r = 0;
   CHK(remove_entries(e, bits, (u32)span, &r));
   if (n_removed) *n_removed = r;
+  return SGTD_OK;
+}
+
+int sgtd_set_frame_filter(sgtd_handle e, uint32_t frame_lo, uint32_t n_frames, const uint64_t *rows, int n_rows) {
+  if (!e || n_rows < 0 || (n_rows > 0 && (!rows || n_frames == 0))) return SGTD_ERR_INVALID;
+  if (e->grp) return multi::set_frame_filter(e, frame_lo, n_frames, rows, n_rows);
+  if (n_rows == 0) { e->filt.reset(); return SGTD_OK; }
+  static std::atomic<u64> serial{0};
+  auto F = std::make_shared<FrameFilter>();
+  F->lo = frame_lo; F->n = n_frames; F->n_rows = n_rows;
+  F->words = ((size_t)n_frames + 63) / 64;
+  F->rows.assign(rows, rows + (size_t)n_rows * F->words);
+  if (n_frames % 64)
+    for (int r = 0; r < n_rows; r++) F->rows[(size_t)r * F->words + F->words - 1] &= (1ull << (n_frames % 64)) - 1ull;
+  F->serial = ++serial;
+  e->filt = std::move(F);
   return SGTD_OK;
 }
 

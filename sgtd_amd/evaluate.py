@@ -94,12 +94,22 @@ def account(metrics, gt_pose4, map_pose4, search_frame, loop_rot, loop_t, cand_f
     return t_err, r_err
 
 
-def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None):
+def frames_near(map_xy, prior_xy, radius):
+    """the map frames within `radius` of each position prior: bool [n_priors, n_map_frames], column f = map frame f
+    (a row of STDescManager.set_frame_filter's boolean form)"""
+    m = np.asarray(map_xy, np.float64).reshape(-1, 2)
+    p = np.asarray(prior_xy, np.float64).reshape(-1, 2)
+    d2 = ((p[:, None, :] - m[None, :, :]) ** 2).sum(axis=2)
+    return d2 <= float(radius) ** 2
+
+
+def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None):
     """SearchLoop for a batch of query frames on the device + the node's accounting.
-    map_pose4[f] = 4x4 pose of map frame f; query_pose4[q] = ground truth of query q."""
+    map_pose4[f] = 4x4 pose of map frame f; query_pose4[q] = ground truth of query q.
+    allowed: a frame filter for the batch (STDescManager.set_frame_filter; e.g. frames_near of position priors)."""
     if metrics is None:
         metrics = LoopMetrics(mgr.config_setting_["candidate_num"])
-    res = mgr.query_frames(query_xyz, query_label, kp_off)
+    res = mgr.query_frames(query_xyz, query_label, kp_off, allowed=allowed)
     mgr.verify()
     bc, bf, bs = mgr.search_loop()
     for q in range(len(bf)):

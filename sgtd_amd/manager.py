@@ -61,6 +61,47 @@ class Descs:
         return out
 
 
+def pack_frame_rows(allowed, frame_lo=None, n_frames=None):
+    """the rows of sgtd_set_frame_filter from `allowed` -> (frame_lo, n_frames, rows: uint64 [n_rows, ceil(n_frames / 64)]).
+    `allowed`: a 1-D array of frame ids shared by the batch; a list of such arrays, one per query; or a boolean matrix
+    [n_queries, n_frames] whose column c is frame frame_lo + c (frame_lo defaults to 0).  Bit f - frame_lo of a row
+    (word (f - frame_lo) >> 6, bit (f - frame_lo) & 63, little-endian bit order) is set for an allowed frame f.  For ids,
+    frame_lo / n_frames default to the span of the ids given; ids outside [frame_lo, frame_lo + n_frames) are dropped.
+    An empty set allows nothing.  ValueError: ids outside [0, 2^32)."""
+    a = np.asarray(allowed) if not isinstance(allowed, (list, tuple)) else None
+    if a is not None and a.dtype == np.bool_ and a.ndim == 2:
+        lo = 0 if frame_lo is None else int(frame_lo)
+        n = a.shape[1] if n_frames is None else int(n_frames)
+        bits = np.zeros((a.shape[0], max(n, 1)), np.bool_)
+        k = min(n, a.shape[1])
+        bits[:, :k] = a[:, :k]
+    else:
+        if a is not None:
+            sets = [a]
+        elif len(allowed) > 0 and any(np.ndim(x) >= 1 for x in allowed):
+            sets = list(allowed)
+        else:
+            sets = [np.asarray(allowed)]
+        sets = [np.asarray(x, dtype=np.int64).reshape(-1) for x in sets]
+        ids = np.concatenate(sets) if sets else np.zeros(0, np.int64)
+        if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+            raise ValueError("frame ids must lie in [0, 2^32)")
+        lo = (int(ids.min()) if ids.size else 0) if frame_lo is None else int(frame_lo)
+        n = (int(ids.max()) - lo + 1 if ids.size else 1) if n_frames is None else int(n_frames)
+        n = max(n, 1)
+        bits = np.zeros((len(sets), n), np.bool_)
+        for r, x in enumerate(sets):
+            d = x - lo
+            bits[r, d[(d >= 0) & (d < n)]] = True
+    if not (0 <= lo <= 0xFFFFFFFF and 1 <= n <= 0xFFFFFFFF):
+        raise ValueError("frame_lo and n_frames must lie in [0, 2^32)")
+    words = (n + 63) // 64
+    packed = np.packbits(bits, axis=1, bitorder="little")
+    out = np.zeros((bits.shape[0], words * 8), np.uint8)
+    out[:, :packed.shape[1]] = packed
+    return lo, n, np.ascontiguousarray(out.view("<u8").astype(np.uint64))
+
+
 class STDMatchList:
     """STDMatchList (STDesc.h:120-124): match_id_ = (query frame id, map frame id);
     match_list_ as (query descriptor index, table entry index) pairs in order"""
@@ -202,6 +243,30 @@ class STDescManager:
         self._check(self._L.sgtd_remove_frames(self._h, _p(ids) if ids.size else None, ids.size, C.byref(n)))
         return n.value
 
+    def set_frame_filter(self, allowed, frame_lo=None, n_frames=None):
+        """restrict the following queries to a set of map frames (sgtd_set_frame_filter): each query is answered as by a
+        handle that holds only its allowed frames (only the visit counters still count the whole map).  `allowed`: None
+        clears the filter; otherwise as pack_frame_rows takes it — frame ids shared by the batch, one id array per query,
+        or a boolean matrix [n_queries, n_frames].  A batch of per-query rows must match the next batch's size."""
+        if allowed is None:
+            self._check(self._L.sgtd_set_frame_filter(self._h, 0, 0, None, 0))
+            self._filter = None
+            return
+        lo, n, rows = pack_frame_rows(allowed, frame_lo, n_frames)
+        self._check(self._L.sgtd_set_frame_filter(self._h, lo, n, _p(rows), rows.shape[0]))
+        self._filter = (allowed, frame_lo, n_frames)
+
+    def _with_filter(self, allowed, call):
+        """call() under the filter `allowed`, then the filter set before it again"""
+        if allowed is None:
+            return call()
+        before = getattr(self, "_filter", None)
+        self.set_frame_filter(allowed)
+        try:
+            return call()
+        finally:
+            self.set_frame_filter(*before) if before is not None else self.set_frame_filter(None)
+
     def attach_table(self, owner):
         """borrow the finalized table of `owner` (another manager on the same device): this manager then queries the
         same map with its own work buffers and stream — two batches in flight (include/sgtd_accel.h)"""
@@ -231,13 +296,13 @@ class STDescManager:
         return xp, lp, off, nf, dev
 
     # ---- candidate_selector -------------------------------------------------
-    def query_frames(self, xyz, label, kp_off=None, fetch=True):
+    def query_frames(self, xyz, label, kp_off=None, fetch=True, allowed=None):
         """fused BuildSingleScanSTD + candidate_selector for a batch of query frames
         (semantic_graph_localization.cpp:592,601 -> STDesc.cpp:98).  Asynchronous when
-        fetch=False (results via .results())."""
+        fetch=False (results via .results()).  allowed: a frame filter for this batch only (set_frame_filter)."""
         xp, lp, off, nq, dev = self._frames_args(xyz, label, kp_off)
         self._nq = nq
-        self._check(self._L.sgtd_query_frames(self._h, xp, lp, _p(off), nq, dev))
+        self._with_filter(allowed, lambda: self._check(self._L.sgtd_query_frames(self._h, xp, lp, _p(off), nq, dev)))
         return self.results() if fetch else None
 
     def loop_frames(self, xyz, label, kp_off=None, skip_near=0, batch=None, fetch=True):
@@ -432,14 +497,17 @@ class STDescManager:
         self._check(self._L.sgtd_search_loop(self._h, float(icp_threshold), _p(bc), _p(bf), _p(bs)))
         return bc, bf, bs
 
-    def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False):
+    def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None):
         """sgtd_search_frame: candidate_selector + candidate_verify + the inlier pairs of every candidate with their table
         entries for ONE query frame given as descriptors, in one call -> dict(n_cand, cand_frame, cand_votes, pair_off,
         score, rot, t, inlier_off, inlier_q_idx, entries (Descs), n_inliers, status).  page_locked: the arrays the inlier
         pairs arrive in come from sgtd_host_alloc, as adapter/STDesc_shim.hpp keeps them — the device then writes them in
         place and the call has one wait (ordinary arrays are filled from the handle's own page-locked block).
         lists_only (SGTD_FRAME_LISTS_ONLY): candidate_selector alone — no verification, inlier_off = pair_off and the pairs
-        handed back are all pairs of every candidate's match list"""
+        handed back are all pairs of every candidate's match list.  allowed: a frame filter for this call only
+        (set_frame_filter)"""
+        if allowed is not None:
+            return self._with_filter(allowed, lambda: self.search_frame(stds_vec, capacity, page_locked, lists_only))
         from ._lib import FrameSearch
         cn = self.config_setting_["candidate_num"]
         cap = max(int(capacity), 1)
