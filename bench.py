@@ -36,13 +36,22 @@ caller uses; and, at N = 8, `cfg4`: BASELINE configs[3]'s 100 000-frame map.
 N = 1 also carries `scaling_prediction`: what rank 0 of an 8-rank job does, measured
 here part by part, for both forms.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what `value` needs: it sets up, warms up, times the `--steps` steps, writes `--dump-outputs`
+and prints the line.  Everything else named above and below — the other map sizes, batch sizes and workloads, one
+batch in flight, the repeated regions, the delivered steps, the roofline's per-kernel timing, verification, the
+adapter boundary, the CPU baseline and parity, recall, the multi-rank legs — runs only with `--full`; the options that
+switch those legs on or off matter only there.
 """
 import argparse
+import atexit
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -98,7 +107,7 @@ def parse():
                          "other settings; full = the protocol at every setting (slow); bounded = a bounded sample everywhere")
     ap.add_argument("--in-flight", type=int, default=3,
                     help="N=1: batches in flight over the one table (handles attached with sgtd_attach_table, one stream each); "
-                         "1 = every batch behind the one before (reported beside the headline either way)")
+                         "1 = every batch behind the one before (with --full reported beside the headline either way)")
     ap.add_argument("--repeat-region", type=int, default=5, help="how many times the headline's timed region is measured (median, min, max reported; value = the first)")
     ap.add_argument("--rotate", type=int, default=4,
                     help="distinct query batches the timed region rotates through (all different from the warm-up batch)")
@@ -110,6 +119,9 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step of `value` computed as DIR/<name>.npy (float64): the candidate tables of "
                          "every query and the match lists of a fixed, seeded sample of them, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside `value` (the legs the options above switch, one batch in flight, "
+                         "repeated regions, delivered steps, roofline, recall, CPU baseline); without it only `value` is measured")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -331,7 +343,7 @@ def flatten_evidence(out):
                 return None
             d = d[k]
         return d
-    c, r = out["config"], out["roofline"]
+    c, r = out["config"], out.get("roofline")
     tr = out.get("timed_region") or {}
     c["delivered_frames_per_s"] = get(out, "delivered", "frames_per_s")
     c["one_in_flight_ms_per_step"] = get(out, "one_batch_in_flight", "ms_per_step")
@@ -351,6 +363,8 @@ def flatten_evidence(out):
         c["cfg4_frames_per_s"] = get(out, "cfg4", "value")
         c["cfg4_leg_wall_s"] = get(out, "cfg4", "leg_wall_s")
         c["exchange_exposed_ms"] = get(out, "scaling_parts", "exchange_exposed_ms")
+    if r is None:       # (a plain run: no roofline)
+        return out
     # the sweep's USEFUL fraction of the HBM roof: the probe layout once + every 4-byte match record once, over the sweep's
     # live time; and the whole step's compulsory I/O over the step's time
     comp = r.get("compulsory") or {}
@@ -804,6 +818,12 @@ T_PROCESS_START = time.perf_counter()
 
 def main():
     args = parse()
+    if "SGTD_SYNTH_CACHE" not in os.environ:
+        # every run generates its synthetic world itself (nothing is read that an earlier run left in synth's shared
+        # cache); the ranks and child processes of THIS run share it through a directory of the run's own
+        run_cache = tempfile.mkdtemp(prefix="sgtd_bench_synth_")
+        os.environ["SGTD_SYNTH_CACHE"] = run_cache
+        atexit.register(shutil.rmtree, run_cache, True)
     if args.rccl_one_child:
         return rccl_one_child(args)
     env_world = os.environ.get("WORLD_SIZE")
@@ -1034,11 +1054,12 @@ def main():
             mgr.query_frames(x, l, fetch=False)
         # cold start: the very first batch of a fresh handle (work buffers sized from the table
         # statistics; re-run if they were too small)
-        t0 = time.perf_counter()
-        step(); mgr.sync(); torch.cuda.synchronize()
-        cold["first_batch_ms"] = 1000.0 * (time.perf_counter() - t0)
-        cold["first_batch_overflowed"] = int(mgr.stats()["overflowed"])
-        cold["bucket_len_sq_over_E"] = mgr.stats()["bucket_len_sq_over_E"]
+        if args.full:
+            t0 = time.perf_counter()
+            step(); mgr.sync(); torch.cuda.synchronize()
+            cold["first_batch_ms"] = 1000.0 * (time.perf_counter() - t0)
+            cold["first_batch_overflowed"] = int(mgr.stats()["overflowed"])
+            cold["bucket_len_sq_over_E"] = mgr.stats()["bucket_len_sq_over_E"]
     else:
         m2 = Map2D(F, rank, world, r_t=r_t, device_id=local_rank, lists=args.lists, max_frame_n=max(20000, F + 1))
         mgr = m2.mgr
@@ -1080,15 +1101,18 @@ def main():
         for _ in range(2 * len(m2s)):       # every engine's work buffers reach their size
             step(-1)
         mgr_all.sync(); torch.cuda.synchronize()
-    elapsed = timed(step, mgr if m2 is None else mgr_all, info=timed_info)
-    if m2 is not None:
-        timed_info["batches_in_flight"] = len(m2s)
     one_in_flight = None
-    if mode == "single" and args.in_flight > 1:
-        # The headline: `--in-flight` batches in flight over the one table.  The measurement above (ONE batch in flight,
-        # every kernel of a batch behind the one before) stays beside it.
-        one_in_flight = {"frames_per_s": n_q_value * args.steps / elapsed, "ms_per_step": 1000.0 * elapsed / args.steps,
-                         "timed_region": dict(timed_info)}
+    if mode == "single" and args.in_flight > 1 and args.full:
+        # ONE batch in flight (every kernel of a batch behind the one before), measured first and reported beside the headline
+        info1 = {}
+        el1 = timed(step, mgr, info=info1)
+        one_in_flight = {"frames_per_s": n_q_value * args.steps / el1, "ms_per_step": 1000.0 * el1 / args.steps, "timed_region": info1}
+    if mode != "single" or args.in_flight <= 1:
+        elapsed = timed(step, mgr if m2 is None else mgr_all, info=timed_info)
+        if m2 is not None:
+            timed_info["batches_in_flight"] = len(m2s)
+    else:
+        # The headline: `--in-flight` batches in flight over the one table
         flight = InFlight(mgr, args.in_flight)
 
         def fstep_(i=-1):
@@ -1097,7 +1121,6 @@ def main():
         for _ in range(2 * args.in_flight):      # every handle's work buffers reach their size
             fstep_(-1)
         flight.sync()
-        timed_info = {}
         elapsed = timed(fstep_, flight, info=timed_info)
         timed_info["batches_in_flight"] = args.in_flight
     # --dump-outputs: the results of the region's last step (batch (K - 1) % n_rot), before any later step can overwrite
@@ -1113,6 +1136,86 @@ def main():
         else:
             torch.cuda.synchronize()
             dumped = dump_outputs(args.dump_outputs, {"cand_frame": merged["out"][0].cpu(), "cand_votes": merged["out"][1].cpu()})
+    backend_ran = dist.get_backend() if world > 1 else None
+    collective = {"nccl": "RCCL (torch.distributed backend nccl)", "gloo": "gloo (NOT RCCL: test fallback)"}.get(backend_ran, backend_ran)
+
+    def entries_of(m):
+        ent = torch.tensor([m.stats()["n_entries"]], dtype=torch.int64, device=dev)
+        ents = [torch.zeros_like(ent) for _ in range(world)]
+        dist.all_gather(ents, ent)
+        return [int(e.item()) for e in ents]
+
+    def headline_line(st, delivered=None, roofline=None):
+        """the line as far as `value` goes: what ran, its timed region, the outputs written (on rank 0; None on the others,
+        and every rank must call it: the ranks count themselves)"""
+        ranks_seen = 1
+        entries_per_rank = [int(st["n_entries"])]
+        if world > 1:
+            one = torch.ones(1, dtype=torch.int64, device=dev)
+            dist.all_reduce(one)
+            ranks_seen = int(one.item())
+            entries_per_rank = entries_of(mgr)
+        if rank != 0:
+            return None
+        value = n_q_value * args.steps / elapsed
+        if mode == "single":
+            sharding = "none"
+        else:
+            sharding = ("%d table shards (map frames by range) x %d query groups over %d GPUs: every rank sweeps its shard with its group's %d query frames; "
+                        "per group one all_gather of the packed top-50 tables + the merge kernel on a side stream, one all_gather of the groups' "
+                        "result tables; collectives over %s" % (r_t, r_q, world, Q, collective))
+        out = {
+            "metric": "query frames/sec vs map size (descriptor build + candidate selection)",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed / args.steps,
+            "higher_is_better": True, "scaling": "weak" if (world == 1 or r_q > 1) else "strong", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "arithmetic": "every decision equals the reference's f64 result: the sweep pre-tests in f32 against two "
+                          "conservative thresholds and decides the few entries between them on the exact f64 sides",
+            "config": {"workload": "synthetic %d keypoints/frame, %d-frame map, descriptor build+match (BASELINE north-star point: 10k-frame map, 1 GPU)" % (N, F)
+                       if F == 10000 else "synthetic %d keypoints/frame, %d-frame map, descriptor build+match" % (N, F),
+                       "map_frames": F, "keypoints_per_frame": N, "queries_per_step": n_q_value, "queries_per_query_group": Q,
+                       "table_shards_R_t": r_t, "query_groups_R_q": r_q, "lists": args.lists if world > 1 else None,
+                       "sharding": sharding, "mode": mode, "collective_backend": backend_ran, "queries_this_rank": q_hi - q_lo,
+                       "ranks_in_collective": ranks_seen, "table_entries_per_rank": entries_per_rank,
+                       "table_entries_this_rank": st["n_entries"], "table_buckets_this_rank": st["n_buckets"],
+                       # (under `config` so that a parser that keeps only the contract's keys still carries them)
+                       "timed_region": dict(timed_info, warmup_batch="a batch of its own: no timed step repeats it",
+                                            note="the timed steps rotate through %d distinct synthetic batches; a region in which a batch outgrew a work "
+                                                 "buffer is discarded and timed again (timed_region_attempts); moved match lists are counted; "
+                                                 "same_batch_ms_per_step = rounds 1-3's measurement (one batch over and over) in the same run" % n_rot),
+                       "delivered": delivered},
+        }
+        if roofline is not None:
+            out["roofline"] = roofline
+        out["timed_region"] = out["config"]["timed_region"]
+        if flight is not None:
+            out["config"]["batches_in_flight"] = args.in_flight
+        return out
+
+    def print_line(out):
+        """rank 0 prints the line (the only thing on stdout); the ranks leave together"""
+        if rank == 0:
+            out["config"]["wall_s_of_this_rank_until_the_line"] = time.perf_counter() - T_PROCESS_START
+            flatten_evidence(out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            result_out.write(json.dumps(out) + "\n")
+            result_out.flush()
+
+    if not args.full:
+        # a plain run ends here: `value` is measured and the outputs are written
+        out = headline_line(mgr.stats())
+        if out is not None:
+            if cold:
+                out["cold_start"] = cold
+            if dumped is not None:
+                out["dump_outputs"] = dumped
+        print_line(out)
+        return
+
     cur_step, cur_mgr = (fstep_, flight) if flight is not None else (step, mgr if m2 is None else mgr_all)
     # the headline region four more times (each with its own warm-up, barrier and overflow check): `value` stays the FIRST
     # region's — the contract's K steps — the spread of the five is reported beside it
@@ -1172,8 +1275,6 @@ def main():
         mgr_all.sync()
         turn["pin"] = True          # (everything below works on the rank's first engine)
     step(-1); mgr.sync(); torch.cuda.synchronize()          # leave the handle on the warm-up batch: the parity, recall and profile legs read its results
-    backend_ran = dist.get_backend() if world > 1 else None
-    collective = {"nccl": "RCCL (torch.distributed backend nccl)", "gloo": "gloo (NOT RCCL: test fallback)"}.get(backend_ran, backend_ran)
     st = mgr.stats()
 
     # ---- per-kernel timing for the roofline (HIP events on the handle's stream), on the rotating batches
@@ -1424,12 +1525,6 @@ def main():
             boundary["cpp_adapter_error"] = "%s: %s" % (type(exc).__name__, exc)
         step(); mgr.sync()   # leave the handle on the headline batch
         res = mgr.results()
-
-    def entries_of(m):
-        ent = torch.tensor([m.stats()["n_entries"]], dtype=torch.int64, device=dev)
-        ents = [torch.zeros_like(ent) for _ in range(world)]
-        dist.all_gather(ents, ent)
-        return [int(e.item()) for e in ents]
 
     # ---- N > 1: the pure table-sharded form of the same map beside a headline of another form (north_star's wording), with
     # its own scaling parts, and the check that its merged list IS the list of a rank that holds the whole table
@@ -1754,47 +1849,8 @@ def main():
         except Exception as exc:
             rccl_one = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
-    ranks_seen = 1
-    entries_per_rank = [int(st["n_entries"])]
-    if world > 1:
-        one = torch.ones(1, dtype=torch.int64, device=dev)
-        dist.all_reduce(one)
-        ranks_seen = int(one.item())
-        entries_per_rank = entries_of(mgr)
-
-    out = None
+    out = headline_line(st, delivered, roofline)
     if rank == 0:
-        value = n_q_value * args.steps / elapsed
-        if mode == "single":
-            sharding = "none"
-        else:
-            sharding = ("%d table shards (map frames by range) x %d query groups over %d GPUs: every rank sweeps its shard with its group's %d query frames; "
-                        "per group one all_gather of the packed top-50 tables + the merge kernel on a side stream, one all_gather of the groups' "
-                        "result tables; collectives over %s" % (r_t, r_q, world, Q, collective))
-        out = {
-            "metric": "query frames/sec vs map size (descriptor build + candidate selection)",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak" if (world == 1 or r_q > 1) else "strong", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "arithmetic": "every decision equals the reference's f64 result: the sweep pre-tests in f32 against two "
-                          "conservative thresholds and decides the few entries between them on the exact f64 sides",
-            "config": {"workload": "synthetic %d keypoints/frame, %d-frame map, descriptor build+match (BASELINE north-star point: 10k-frame map, 1 GPU)" % (N, F)
-                       if F == 10000 else "synthetic %d keypoints/frame, %d-frame map, descriptor build+match" % (N, F),
-                       "map_frames": F, "keypoints_per_frame": N, "queries_per_step": n_q_value, "queries_per_query_group": Q,
-                       "table_shards_R_t": r_t, "query_groups_R_q": r_q, "lists": args.lists if world > 1 else None,
-                       "sharding": sharding, "mode": mode, "collective_backend": backend_ran, "queries_this_rank": q_hi - q_lo,
-                       "ranks_in_collective": ranks_seen, "table_entries_per_rank": entries_per_rank,
-                       "table_entries_this_rank": st["n_entries"], "table_buckets_this_rank": st["n_buckets"],
-                       # (under `config` so that a parser that keeps only the contract's keys still carries them)
-                       "timed_region": dict(timed_info, warmup_batch="a batch of its own: no timed step repeats it",
-                                            note="the timed steps rotate through %d distinct synthetic batches; a region in which a batch outgrew a work "
-                                                 "buffer is discarded and timed again (timed_region_attempts); moved match lists are counted; "
-                                                 "same_batch_ms_per_step = rounds 1-3's measurement (one batch over and over) in the same run" % n_rot),
-                       "delivered": delivered},
-            "roofline": roofline,
-        }
-        out["timed_region"] = out["config"]["timed_region"]
         if scaling_parts is not None:
             out["scaling_parts"] = scaling_parts
         if prediction is not None:
@@ -1803,7 +1859,6 @@ def main():
             out["delivered"] = delivered
         if one_in_flight is not None:
             out["one_batch_in_flight"] = one_in_flight
-            out["config"]["batches_in_flight"] = args.in_flight
         if cold:
             out["cold_start"] = cold
         if sweep is not None:
@@ -1842,22 +1897,14 @@ def main():
                 cb, par = cpu_baseline(smap, queries, res, mgr, args.cpu_seconds, args.cpu_protocol)
                 out["cpu_baseline"] = cb
                 out["parity"] = par
-                out["speedup_vs_cpu_baseline"] = value / cb["value"]
-                out["speedup_vs_best_cpu_setting"] = value / cb["best_setting_frames_per_s"]
+                out["speedup_vs_cpu_baseline"] = out["value"] / cb["value"]
+                out["speedup_vs_best_cpu_setting"] = out["value"] / cb["best_setting_frames_per_s"]
             except Exception as exc:   # a broken checker must not cost the measured line
                 out["cpu_baseline"] = None
                 out["cpu_baseline_error"] = "%s: %s" % (type(exc).__name__, exc)
         else:
             out["cpu_baseline"] = None
-    if rank == 0:
-        out["config"]["wall_s_of_this_rank_until_the_line"] = time.perf_counter() - T_PROCESS_START
-        flatten_evidence(out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        result_out.write(json.dumps(out) + "\n")
-        result_out.flush()
+    print_line(out)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,7 @@
 set -u
 TAG=${1:-r04a}
 COMMIT=${2:-unknown}
-ARGS=${3:-"--steps 6 --warmup 2 --cpu-baseline off --verify off --boundary off --sweep none"}
+ARGS=${3:-"--full --steps 6 --warmup 2 --cpu-baseline off --verify off --boundary off --sweep none"}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT

@@ -7,7 +7,7 @@
 set -u
 TAG=${1:-r05a}
 COMMIT=${2:-unknown}
-ARGS=${3:-"--steps 6 --warmup 2 --cpu-baseline off --verify off --boundary off --sweep none --in-flight 1 --predict-world 0"}
+ARGS=${3:-"--full --steps 6 --warmup 2 --cpu-baseline off --verify off --boundary off --sweep none --in-flight 1 --predict-world 0"}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT

@@ -8,7 +8,7 @@ set -u
 TAG=${1:-r06a}
 COMMIT=${2:-unknown}
 VSTAT_LIB=${3:-}
-ARGS=${VERIFY_ARGS:-"--steps 2 --warmup 1 --cpu-baseline off --verify on --boundary off --sweep none --in-flight 1 --predict-world 0 --skew off --cfg1 off --rccl-one off --profile-steps 1"}
+ARGS=${VERIFY_ARGS:-"--full --steps 2 --warmup 1 --cpu-baseline off --verify on --boundary off --sweep none --in-flight 1 --predict-world 0 --skew off --cfg1 off --rccl-one off --profile-steps 1"}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT

@@ -8,10 +8,10 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for F in 1000 10000; do
-  timeout 1500 python3 bench.py --frames $F --queries 256 --steps 5 --cpu-baseline on --cpu-protocol full --sweep none --verify off --boundary off \
+  timeout 1500 python3 bench.py --full --frames $F --queries 256 --steps 5 --cpu-baseline on --cpu-protocol full --sweep none --verify off --boundary off \
     > $OUT/cpu_protocol_F$F.json 2> $OUT/cpu_protocol_F$F.err
   echo "F=$F rc=$?"
 done
-SGTD_BENCH_BACKEND=gloo SGTD_BENCH_SHARE_GPU=1 timeout 600 python3 bench.py --gpus 2 --steps 5 --cpu-baseline off --sweep none --verify off --boundary off \
+SGTD_BENCH_BACKEND=gloo SGTD_BENCH_SHARE_GPU=1 timeout 600 python3 bench.py --full --gpus 2 --steps 5 --cpu-baseline off --sweep none --verify off --boundary off \
   > $OUT/bench_2rank_one_gpu_gloo.json 2> $OUT/bench_2rank_one_gpu_gloo.err
 echo "2rank rc=$?"

@@ -12,13 +12,14 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--frames", "400", "--queries", "24", "--steps", "2", "--warmup", "1", "--cpu-baseline", "off",
-        "--sweep", "none", "--verify", "off", "--boundary", "off"]
+ARGS = ["--frames", "400", "--queries", "24", "--steps", "2", "--warmup", "1"]
+# (the legs beside `value` run only with --full; of them these tests want the multi-rank ones)
+FULL = ["--full", "--cpu-baseline", "off", "--sweep", "none", "--verify", "off", "--boundary", "off"]
 
 
-def _bench(extra, env):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + ARGS + extra, capture_output=True, text=True,
-                         timeout=1200, env=env)
+def _bench(extra, env, full=True):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + ARGS + (FULL if full else []) + extra, capture_output=True,
+                         text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 1, "stdout must carry exactly one line, got %d: %r" % (len(lines), [l[:80] for l in lines])
@@ -95,6 +96,27 @@ def test_four_rank_two_by_two_grid():
     # the four-shard form of the same map gives the lists of query group 0 (two shards): both are the single table's
     assert g["table_sharded"]["merged_list_equals_headline_list"] is True
     assert g["recall"]["top1_pose_within_5m"] > 0.9
+
+
+@pytest.mark.gpu
+def test_plain_bench_measures_value_only(tmp_path):
+    """without --full a run sets up, warms up, times its steps, writes --dump-outputs and prints the line: the headline keys
+    say what they say with --full, and none of the legs beside `value` ran — on one rank and on two"""
+    one = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path / "one")], dict(os.environ), full=False)
+    two = _bench(["--gpus", "2"], _env(2), full=False)
+    for line, n in ((one, 1), (two, 2)):
+        assert line["n_gpus"] == n and line["steps"] == 2 and line["warmup"] == 1
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        assert abs(line["value"] - line["config"]["queries_per_step"] * 1000.0 / line["ms_per_step"]) < 1e-9 * line["value"]
+        tr = line["config"]["timed_region"]
+        assert tr["batch_launches_in_timed_region"] >= 2 and tr["launches_that_overflowed_a_work_buffer"] == 0
+        assert "regions_timed" not in tr and "same_batch_ms_per_step" not in tr
+        for key in ("roofline", "recall", "cpu_baseline", "delivered", "one_batch_in_flight", "scaling_parts", "scaling_prediction",
+                    "map_size_sweep", "workload_skew", "verify", "boundary", "table_sharded", "fixed_total_batch"):
+            assert key not in line, key
+    assert one["config"]["batches_in_flight"] == 3 and two["config"]["ranks_in_collective"] == 2
+    written = sorted(os.listdir(tmp_path / "one"))
+    assert written == sorted(name + ".npy" for name in one["dump_outputs"]["arrays"]) and "cand_frame.npy" in written
 
 
 def _search_loop(n, r_t, lists, extra_env=None, backend=None):

@@ -190,6 +190,27 @@ def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path):
         assert np.array_equal(got["match_q_idx"][off[i]:off[i + 1]], qi) and np.array_equal(got["match_db_entry"][off[i]:off[i + 1]], de)
 
 
+def test_bench_legs_beside_value_wait_for_full():
+    """a plain bench.py run measures `value` only: --full is off unless asked for, and the line of a plain run (no
+    roofline) still gets its scalar evidence keys"""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        assert bench.parse().full is False
+        sys.argv = ["bench.py", "--full"]
+        assert bench.parse().full is True
+    finally:
+        sys.argv = argv
+    plain = bench.flatten_evidence({"n_gpus": 1, "config": {}, "timed_region": {"launches_that_overflowed_a_work_buffer": 0}})
+    assert "roofline" not in plain and plain["config"]["overflowed_launches_in_timed_region"] == 0
+    assert all(k in plain["config"] for k in bench.FLAT_CONFIG_KEYS)
+
+
 def test_committed_traffic_row_describes_the_kernels_the_bench_launches():
     """bench.py refuses a PMC row that was taken on other kernels than the ones the run launches: the row committed
     under profiles/ for the default workload must carry the kernels of the per-query form (sgtd_stats.select_form 2),

@@ -1,7 +1,7 @@
 #!/bin/bash
 # times the sweep of kernel variants under test (variants/lib_*.so, built with -DSGTD_EXP_*) and of launch
 # knobs with a short bench run each; prints ms per kernel stage.   bash tools/exp_variants.sh [knob=value ...]
-ARGS="--steps 4 --warmup 1 --cpu-baseline off --verify off --boundary off --sweep none --profile-steps 2"
+ARGS="--full --steps 4 --warmup 1 --cpu-baseline off --verify off --boundary off --sweep none --profile-steps 2"
 run() {  # label, env...
   local label=$1; shift
   env "$@" python3 bench.py $ARGS 2>gpurun_out/exp_err_$label.log | python3 -c "
