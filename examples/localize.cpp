@@ -3,7 +3,10 @@
 // on the C ABI alone: graph-JSON directories in, localization statistics out.  No ROS, no PCL,
 // no GICP (enable_gicp = false); BASE2OUSTER = identity.
 //
-//   localize <map_dir | map.cache> <query_dir | query.cache> [batch=256] [icp_threshold=0.4]
+//   localize <map_dir | map.cache> <query_dir | query.cache> [batch=256] [icp_threshold=0.4] [prior_radius]
+//   prior_radius: restrict every query to the map frames within that many metres (x, y) of its ground-truth position
+//   (sgtd_set_frame_poses + sgtd_set_position_prior), as a localizer with odometry would, and report how many map
+//   frames a query was allowed on average (the LOCALIZE_PER_FRAME calls below run without it)
 //   LOCALIZE_DEFAULT_MALLOC=1: do not tune glibc's allocator (see main)
 //   LOCALIZE_PER_FRAME=n: additionally run the first n queries the way the reference node does —
 //   one BuildSingleScanSTD + SearchLoop call per frame through the STDescManager adapter
@@ -117,7 +120,7 @@ static int load_any(const char *path, Graphs &g) {
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold] [prior_radius]\n", argv[0]);
     return 2;
   }
   // SearchLoop hands back ~130 MB of std::pair<STDesc, STDesc> per frame (the reference's own result
@@ -133,6 +136,8 @@ int main(int argc, char **argv) {
   }
   const int batch = argc > 3 ? std::atoi(argv[3]) : 256;
   const double icp_threshold = argc > 4 ? std::atof(argv[4]) : 0.4;   // SG_localization.yaml:89
+  const bool use_prior = argc > 5;
+  const double prior_radius = use_prior ? std::atof(argv[5]) : 0.0;
   auto t0 = std::chrono::steady_clock::now();
   Graphs map, qs;
   OK(load_any(argv[1], map));
@@ -151,6 +156,13 @@ int main(int argc, char **argv) {
   OK(sgtd_create_multi(&cfg, devices.data(), (int)devices.size(), &h));
   OK(sgtd_add_frames(h, map.xyz, map.label, map.off, map.n, 0));   // :419-458
   OK(sgtd_finalize(h));
+  if (use_prior) {                                           // map frame i has global id i (first_frame_id 0)
+    std::vector<uint32_t> ids(map.n);
+    for (int i = 0; i < map.n; i++) ids[i] = (uint32_t)i;
+    OK(sgtd_set_frame_poses(h, ids.data(), map.poses, map.n));
+  }
+  long allowed_sum = 0;                                      // (query, map frame) pairs the priors allowed
+  std::vector<double> prior_c, prior_r;
   auto t2 = std::chrono::steady_clock::now();
 
   const int cn = cfg.candidate_num;
@@ -163,6 +175,21 @@ int main(int argc, char **argv) {
     const int nb = std::min(batch, qs.n - q0);
     std::vector<int64_t> off(nb + 1);
     for (int i = 0; i <= nb; i++) off[i] = qs.off[q0 + i] - qs.off[q0];
+    if (use_prior) {                                         // each query's ground-truth (x, y), one row per query
+      prior_c.assign((size_t)nb * 2, 0.0);
+      prior_r.assign(nb, prior_radius);
+      for (int i = 0; i < nb; i++) {
+        const float *qp = qs.poses + (size_t)(q0 + i) * 12;
+        prior_c[(size_t)i * 2] = qp[3];
+        prior_c[(size_t)i * 2 + 1] = qp[7];
+        for (int f = 0; f < map.n; f++) {                    // (the rule of sgtd_set_position_prior, dims 2)
+          const float *mp = map.poses + (size_t)f * 12;
+          const double dx = (double)mp[3] - prior_c[(size_t)i * 2], dy = (double)mp[7] - prior_c[(size_t)i * 2 + 1];
+          allowed_sum += std::isfinite(mp[3]) && std::isfinite(mp[7]) && dx * dx + dy * dy <= prior_radius * prior_radius;
+        }
+      }
+      OK(sgtd_set_position_prior(h, prior_c.data(), prior_r.data(), nb, 2));
+    }
     auto tb0 = std::chrono::steady_clock::now();
     OK(sgtd_query_frames(h, qs.xyz + 3 * qs.off[q0], qs.label + qs.off[q0], off.data(), nb, 0));
     OK(sgtd_sync(h));
@@ -204,6 +231,9 @@ int main(int argc, char **argv) {
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   std::printf("map frames %d, queries %ld: loops %ld, success(5m,10deg) %ld (%.4f), candidate<10m %ld, top-1 hit %ld\n", map.n,
               total_num, detected, score_num, total_num ? (double)score_num / total_num : 0.0, test_10, STD_num[0]);
+  if (use_prior)
+    std::printf("position prior %.2f m: %.1f map frames allowed per query (%ld in all)\n", prior_radius,
+                total_num ? (double)allowed_sum / total_num : 0.0, allowed_sum);
   std::printf("mean errors of the successes: %.4f m, %.4f deg\n", score_num ? err_t / score_num : 0.0, score_num ? err_r / score_num : 0.0);
   std::printf("time: load %.1f ms, map build %.1f ms, queries %.1f ms (%.3f ms per query incl. verification), %d device(s)\n", ms(t0, t1), ms(t1, t2),
               ms(t2, t3), total_num ? ms(t2, t3) / total_num : 0.0, sgtd_device_count(h));

@@ -223,6 +223,33 @@ int sgtd_remove_frames(sgtd_handle h, const uint32_t *frame_ids, int64_t n, int6
  * n_rows > 0 or n_frames == 0 with n_rows > 0: SGTD_ERR_INVALID, before the device is touched. */
 int sgtd_set_frame_filter(sgtd_handle h, uint32_t frame_lo, uint32_t n_frames, const uint64_t *rows, int n_rows);
 
+/* Poses of map frames, keyed by global frame id: row-major 3x4 [R | t], the 12 floats of a graph file's "poses"
+ * (sgtd_graphs_view hands them out in this form).  Later calls overwrite.  pose12 == NULL with n > 0 forgets the
+ * poses of those ids; frame_ids == NULL with n == 0 forgets all.  Ids may name frames not (yet) added. */
+/* The poses are copied at the call and are settings of the handle, like a frame filter: sgtd_add*, sgtd_remove_frames
+ * and sgtd_load_table leave them alone, the table file does not hold them, and a view (sgtd_attach_table) has poses of
+ * its own.  A multi-device handle hands each pose to the shard that owns its frame.  h == NULL, n < 0 or
+ * frame_ids == NULL with n > 0: SGTD_ERR_INVALID; an id >= max_frame_n: SGTD_ERR_FRAME_LIMIT (nothing is stored). */
+int sgtd_set_frame_poses(sgtd_handle h, const uint32_t *frame_ids, const float *pose12, int64_t n);
+
+/* Restrict later queries to the map frames within radius[r] of center[r]: dims 2 tests (x, y) = (t[0], t[1]),
+ * dims 3 tests (x, y, z).  n_rows == 1: one prior for every query of a batch; n_rows > 1: row q for query q.
+ * center == NULL with n_rows == 0 clears the prior. */
+/* center[r * dims + i], radius[r].  Frame f is allowed by row r iff it has a pose (sgtd_set_frame_poses), the tested
+ * coordinates of its translation t are finite, and d2 <= rr, where dx = (double)t[0] - cx (dy, dz alike),
+ * d2 = (dx*dx + dy*dy) + dz*dz (dims 2: no dz term) and rr = radius * radius, all in f64 without contraction.  (This is
+ * evaluate.frames_near's rule for dims 2, which writes radius ** 2.)  A NaN or infinite translation is never allowed,
+ * whatever the radius; radius +inf allows every frame with a pose.  The rows are built on the device, once per prior,
+ * poses, filter and table span, and work as sgtd_set_frame_filter's rows do: each query is answered as under a filter
+ * of the same rows, in everything that call lists.  A prior and a frame filter may be set together: a frame is then
+ * allowed only if both allow it, and setting or clearing one leaves the other alone.  The prior is a setting of the
+ * handle as the filter is (a batch keeps the prior it was enqueued with, re-runs included; a view has its own; a
+ * multi-device handle gives it to every shard).  A query call whose batch size differs from n_rows > 1: SGTD_ERR_INVALID;
+ * sgtd_loop_frames with a prior set: SGTD_ERR_STATE.  h == NULL, n_rows < 0, and with n_rows > 0: center or radius
+ * NULL, dims not 2 or 3, a non-finite center coordinate, a NaN or negative radius (+inf is allowed): SGTD_ERR_INVALID,
+ * before the device is touched. */
+int sgtd_set_position_prior(sgtd_handle h, const double *center, const double *radius, int n_rows, int dims);
+
 /* Two (or more) batches in flight over ONE map: `view` — a handle of the same configuration on the same device,
  * without a table of its own — borrows the finalized table of `owner` (cold entries, probe layout, entry ids) and keeps
  * its own work buffers, results and stream.  Batches enqueued alternately on the two handles' streams overlap on the
@@ -361,6 +388,16 @@ int sgtd_verify(sgtd_handle h);
  * of query q: score[candidate_num], pose[candidate_num*12] = rot row-major (9) then t (3);
  * entries past the query's candidate count hold -1 / zeros.  Either pointer may be NULL. */
 int sgtd_result_verify(sgtd_handle h, int q, double *score, double *pose);
+/* World pose of every candidate of query q after sgtd_verify: world[k*12 .. k*12+11] = map pose of the candidate's
+ * frame composed with its relative pose (3x4 row-major f32); 12 NaNs where the candidate is past n_cand, was
+ * rejected (score -1), or its frame has no pose. */
+/* world holds candidate_num * 12 floats.  With M the stored pose (sgtd_set_frame_poses) and R, t the relative pose of
+ * sgtd_result_verify cast to f32, every operation an f32 rounding (the node's Global_SG[match].pose * loop_transform):
+ *   w[i][j] = (M[i][0]*R[0][j] + M[i][1]*R[1][j]) + M[i][2]*R[2][j]
+ *   w[i][3] = ((M[i][0]*t[0] + M[i][1]*t[1]) + M[i][2]*t[2]) + M[i][3]
+ * Computed in the library's host code; a multi-device handle gives the single-device values bit for bit.  h == NULL,
+ * world == NULL, q outside the batch or no verification yet: SGTD_ERR_INVALID. */
+int sgtd_result_world_poses(sgtd_handle h, int q, float *world);
 /* asynchronous device-to-device export of the verification results of the whole batch into
  * caller device buffers (score f64 [n_queries*candidate_num], pose f64 [n_queries*candidate_num*12]),
  * enqueued on the handle's stream without synchronising: the table-sharded multi-GPU path

@@ -30,6 +30,7 @@ SYMBOLS = [
     "sgtd_candidate_export_ints", "sgtd_set_candidate_export", "sgtd_export_wait", "sgtd_export_release", "sgtd_merge_candidates_dev",
     "sgtd_gather_verified_dev", "sgtd_set_deferred_lists", "sgtd_finish_lists", "sgtd_verify_masked", "sgtd_attach_table", "sgtd_search_frame",
     "sgtd_loop_frames", "sgtd_remove_frames", "sgtd_set_frame_filter",
+    "sgtd_set_frame_poses", "sgtd_set_position_prior", "sgtd_result_world_poses",
 ]
 
 
@@ -145,6 +146,9 @@ def lib():
     L.sgtd_finalize.argtypes = [vp]
     L.sgtd_remove_frames.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.sgtd_set_frame_filter.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_int]
+    L.sgtd_set_frame_poses.argtypes = [vp, vp, vp, i64]
+    L.sgtd_set_position_prior.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+    L.sgtd_result_world_poses.argtypes = [vp, C.c_int, vp]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

@@ -44,6 +44,9 @@ int add_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const in
 int finalize(sgtd_engine *e);
 int remove_frames(sgtd_engine *e, const uint32_t *frame_ids, int64_t n, int64_t *n_removed);
 int set_frame_filter(sgtd_engine *e, uint32_t frame_lo, uint32_t n_frames, const uint64_t *rows, int n_rows);
+int set_frame_poses(sgtd_engine *e, const uint32_t *frame_ids, const float *pose12, int64_t n);
+int set_position_prior(sgtd_engine *e, const double *center, const double *radius, int n_rows, int dims);
+int candidates_of(sgtd_engine *e, int q, int *n_cand, int *cand_frame);
 int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_queries, int device_ptrs);
 int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq);
 int result_candidates(sgtd_engine *e, int32_t *n_cand, int32_t *cand_frame, int32_t *cand_votes, int64_t *pair_off);

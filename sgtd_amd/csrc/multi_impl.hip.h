@@ -175,9 +175,39 @@ int set_frame_filter(sgtd_engine *e, uint32_t frame_lo, uint32_t n_frames, const
   return SGTD_OK;
 }
 
+// every shard keeps the poses of its own frames under their local ids (the group keeps them under the global ids for
+// sgtd_result_world_poses); the checks ran in sgtd_set_frame_poses
+int set_frame_poses(sgtd_engine *e, const uint32_t *frame_ids, const float *pose12, int64_t n) {
+  Group *g = G(e);
+  if (n == 0) {
+    for (sgtd_engine *c : g->dev) MCHK(sgtd_set_frame_poses(c, frame_ids, pose12, 0));
+    return SGTD_OK;
+  }
+  std::vector<std::vector<uint32_t>> loc(g->n);
+  std::vector<std::vector<float>> rows(g->n);
+  for (int64_t i = 0; i < n; i++) {
+    const int s = shard_of(frame_ids[i], g->n);
+    loc[s].push_back(local_of(frame_ids[i], g->n));
+    if (pose12) rows[s].insert(rows[s].end(), pose12 + (size_t)i * 12, pose12 + (size_t)i * 12 + 12);
+  }
+  for (int s = 0; s < g->n; s++) {
+    if (loc[s].empty()) continue;
+    sgtd_engine *c = g->dev[s];
+    MCHK(sgtd_set_frame_poses(c, loc[s].data(), pose12 ? rows[s].data() : nullptr, (int64_t)loc[s].size()));
+  }
+  return SGTD_OK;
+}
+
+// the prior goes to every shard as it is (it tests each shard's own positions); the group keeps it for prior_fits
+int set_position_prior(sgtd_engine *e, const double *center, const double *radius, int n_rows, int dims) {
+  for (sgtd_engine *c : G(e)->dev) MCHK(sgtd_set_position_prior(c, center, radius, n_rows, dims));
+  return SGTD_OK;
+}
+
 int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_queries, int device_ptrs) {
   if (n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
   CHK(filter_fits(e, n_queries));
+  CHK(prior_fits(e, n_queries));
   Group *g = G(e);
   if (device_ptrs) { e->err = "multi-device tables take host pointers"; return SGTD_ERR_UNSUPPORTED; }
   // every device builds the query descriptors itself and sweeps its shard; the calls only
@@ -190,6 +220,7 @@ int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const 
 int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq) {
   if (nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame))) return SGTD_ERR_INVALID;
   CHK(filter_fits(e, 1));
+  CHK(prior_fits(e, 1));
   Group *g = G(e);
   std::vector<uint32_t> lf((size_t)std::max<int64_t>(nq, 1));
   for (int s = 0; s < g->n; s++) {
@@ -263,6 +294,17 @@ int result_candidates(sgtd_engine *e, int32_t *n_cand, int32_t *cand_frame, int3
   if (cand_votes) std::memcpy(cand_votes, g->cand_votes.data(), (size_t)nq * cn * sizeof(int));
   if (pair_off)
     for (size_t i = 0; i < (size_t)nq * (cn + 1); i++) pair_off[i] = g->pair_off[i];
+  return SGTD_OK;
+}
+
+// query q's merged candidate count and global frame ids
+int candidates_of(sgtd_engine *e, int q, int *n_cand, int *cand_frame) {
+  CHK(merge(e));
+  Group *g = G(e);
+  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  *n_cand = g->n_cand[(size_t)q];
+  std::memcpy(cand_frame, g->cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
   return SGTD_OK;
 }
 

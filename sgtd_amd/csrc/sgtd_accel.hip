@@ -8,8 +8,10 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -24,6 +26,7 @@
 #include "exchange_kernels.hip.h"
 #include "remove_kernels.hip.h"
 #include "filter_kernels.hip.h"
+#include "prior_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -59,6 +62,14 @@ struct FrameFilter {
   std::vector<u64> rows;
   u64 serial = 0;            // distinct for every filter a process makes
   const u64 *row(int r) const { return rows.data() + (size_t)(n_rows == 1 ? 0 : r) * words; }
+};
+
+// sgtd_set_position_prior's rows: (cx, cy, cz, r*r) per row in f64 (cz = 0 for dims 2); one for every query when
+// n_rows == 1
+struct PositionPrior {
+  int n_rows = 0, dims = 2;
+  std::vector<double4> prm;
+  u64 serial = 0;            // distinct for every prior a process makes
 };
 
 // bits s .. s + 63 of a bit row of `words` 64-bit words (bit i: word i >> 6, bit i & 63); bits outside the row read 0
@@ -171,6 +182,28 @@ struct sgtd_engine {
   std::vector<u64> filt_host;      // (the source of their upload)
   u64 filt_rows_serial = 0;
   u32 filt_rows_lo = 0, filt_rows_span = 0;
+  // sgtd_set_frame_poses / sgtd_set_position_prior (prior_kernels.hip.h): the poses by global frame id (12 f32 each;
+  // has_pose[id] != 0 where set; both grown to the largest id given), the prior, and the prior the pending batch was
+  // enqueued with.  pos_dev: (t0, t1, t2, has pose) per local frame of the table's span, made for (pos_serial, _lo,
+  // _span); prior_dev: the batch prior's rows; filt_base: the batch filter's rows re-based (when both are set), made
+  // for (serial, lo, span) as filt_rows are.  The rows the kernel last wrote into filt_rows were made for prior_key.
+  std::vector<float> poses;
+  std::vector<unsigned char> has_pose;
+  u64 poses_serial = 0;
+  std::shared_ptr<const PositionPrior> prior, batch_prior;
+  DevBuf pos_dev, prior_dev, filt_base;
+  std::vector<float4> pos_host;      // (the source of pos_dev's upload)
+  u64 pos_serial = 0;
+  u32 pos_lo = 0, pos_span = 0;
+  u64 filt_base_serial = 0;
+  u32 filt_base_lo = 0, filt_base_span = 0;
+  struct PriorKey {
+    u64 prior = 0, poses = 0, filt = 0;
+    u32 lo = 0, span = 0;
+    int n_rows = 0;
+    bool operator==(const PriorKey &o) const { return prior == o.prior && poses == o.poses && filt == o.filt && lo == o.lo && span == o.span && n_rows == o.n_rows; }
+  } prior_key;
+  bool prior_rows_valid = false;
   // sort scratch
   DevBuf keyA, keyB, valA, valB, hist, digit_tot, flags, bad_flag;
   std::vector<DevBuf> scan_lvl;
@@ -1074,12 +1107,10 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
   return SGTD_OK;
 }
 
-// The batch's filter rows re-based to the table's frame span: bit f of device row r = frame frame_lo + f allowed.  Made
-// again only when the rows or the span change (a batch of the same filter on the same table reuses them).
-int prepare_filter(sgtd_engine *e, u32 frame_lo, u32 span) {
+// The batch's filter rows re-based to the table's frame span: bit f of device row r = frame frame_lo + f allowed, into
+// `dst` (n_rows rows of ceil(span / 64) words).
+int rebase_filter(sgtd_engine *e, u32 frame_lo, u32 span, int n_rows, DevBuf &dst) {
   const FrameFilter &F = *e->batch_filt;
-  if (e->filt_rows.p && F.serial == e->filt_rows_serial && frame_lo == e->filt_rows_lo && span == e->filt_rows_span) return SGTD_OK;
-  const int n_rows = F.n_rows == 1 ? 1 : e->nq;
   const size_t words = ((size_t)span + 63) / 64;
   e->filt_host.assign((size_t)n_rows * words, 0ull);
   const long long shift = (long long)frame_lo - (long long)F.lo;
@@ -1089,16 +1120,79 @@ int prepare_filter(sgtd_engine *e, u32 frame_lo, u32 span) {
     for (size_t w = 0; w < words; w++) dst[w] = row_bits_at(F.row(r), F.words, shift + (long long)w * 64);
     dst[words - 1] &= last;
   }
-  CHK(ensure(e, e->filt_rows, e->filt_host.size() * sizeof(u64)));
-  CHK(h2d(e, e->filt_rows.p, e->filt_host.data(), e->filt_host.size() * sizeof(u64)));
+  CHK(ensure(e, dst, e->filt_host.size() * sizeof(u64)));
+  CHK(h2d(e, dst.p, e->filt_host.data(), e->filt_host.size() * sizeof(u64)));
+  return SGTD_OK;
+}
+
+// Made again only when the rows or the span change (a batch of the same filter on the same table reuses them).
+int prepare_filter(sgtd_engine *e, u32 frame_lo, u32 span) {
+  const FrameFilter &F = *e->batch_filt;
+  if (e->filt_rows.p && F.serial == e->filt_rows_serial && frame_lo == e->filt_rows_lo && span == e->filt_rows_span) return SGTD_OK;
+  CHK(rebase_filter(e, frame_lo, span, F.n_rows == 1 ? 1 : e->nq, e->filt_rows));
   e->filt_rows_serial = F.serial; e->filt_rows_lo = frame_lo; e->filt_rows_span = span;
+  e->prior_rows_valid = false;      // (filt_rows no longer hold a prior's rows)
+  return SGTD_OK;
+}
+
+// rows of the batch's filter pass: one for every query when every row source (filter, prior) has one, else one per query
+static int batch_row_count(const sgtd_engine *e) {
+  const bool per_q = (e->batch_filt && e->batch_filt->n_rows > 1) || (e->batch_prior && e->batch_prior->n_rows > 1);
+  return per_q ? e->nq : 1;
+}
+
+// The batch's rows from its position prior (prior_kernels.hip.h), ANDed with its filter's when one is set, written into
+// filt_rows on the device.  The span's positions are uploaded again only when the poses or the span change; the rows
+// are made again only when the prior, the poses, the filter, frame_lo or the span change.
+int prepare_prior(sgtd_engine *e, u32 frame_lo, u32 span) {
+  const PositionPrior &P = *e->batch_prior;
+  const int n_rows = batch_row_count(e);
+  const sgtd_engine::PriorKey key{P.serial, e->poses_serial, e->batch_filt ? e->batch_filt->serial : 0ull, frame_lo, span, n_rows};
+  if (e->filt_rows.p && e->prior_rows_valid && key == e->prior_key) return SGTD_OK;
+  if (!e->pos_dev.p || e->pos_serial != e->poses_serial || e->pos_lo != frame_lo || e->pos_span != span) {
+    e->pos_host.assign(span, make_float4(0.f, 0.f, 0.f, 0.f));
+    const size_t n_ids = e->has_pose.size();
+    for (u32 f = 0; f < span; f++) {
+      const size_t id = (size_t)frame_lo + f;
+      if (id >= n_ids) break;
+      if (e->has_pose[id]) {
+        const float *m = e->poses.data() + id * 12;
+        e->pos_host[f] = make_float4(m[3], m[7], m[11], 1.f);
+      }
+    }
+    CHK(ensure(e, e->pos_dev, (size_t)span * sizeof(float4)));
+    CHK(h2d(e, e->pos_dev.p, e->pos_host.data(), (size_t)span * sizeof(float4)));
+    e->pos_serial = e->poses_serial; e->pos_lo = frame_lo; e->pos_span = span;
+  }
+  CHK(ensure(e, e->prior_dev, P.prm.size() * sizeof(double4)));
+  CHK(h2d(e, e->prior_dev.p, P.prm.data(), P.prm.size() * sizeof(double4)));
+  const u64 *base = nullptr;
+  int base_rows = 1;
+  if (e->batch_filt) {
+    const FrameFilter &F = *e->batch_filt;
+    base_rows = F.n_rows == 1 ? 1 : e->nq;
+    if (!e->filt_base.p || F.serial != e->filt_base_serial || frame_lo != e->filt_base_lo || span != e->filt_base_span) {
+      CHK(rebase_filter(e, frame_lo, span, base_rows, e->filt_base));
+      e->filt_base_serial = F.serial; e->filt_base_lo = frame_lo; e->filt_base_span = span;
+    }
+    base = e->filt_base.as<u64>();
+  }
+  const u32 words = (span + 63) / 64;
+  CHK(ensure(e, e->filt_rows, (size_t)n_rows * words * sizeof(u64)));
+  const long long waves = (long long)n_rows * words;
+  const int grid = (int)((waves + SGTD_PRIOR_THREADS / SGTD_WAVE - 1) / (SGTD_PRIOR_THREADS / SGTD_WAVE));
+  prior_rows_kernel<<<grid, SGTD_PRIOR_THREADS, 0, e->stream>>>(e->pos_dev.as<float4>(), span, words, e->prior_dev.as<double4>(),
+                                                               P.n_rows == 1 ? 1 : n_rows, P.dims, base, base_rows, n_rows, e->filt_rows.as<u64>());
+  HIPCHK(hipGetLastError());
+  e->prior_key = key; e->prior_rows_valid = true;
+  e->filt_rows_serial = 0;          // (filt_rows no longer hold a filter's own rows)
   return SGTD_OK;
 }
 
 // filter_kernels.hip.h, right after the sweep's undecided records are resolved: the records of frames a query may not
 // see die (the diagnostic build: leave their lists)
 int launch_filter(sgtd_engine *e, const Views &v) {
-  const int nq = e->nq, n_rows = e->batch_filt->n_rows == 1 ? 1 : nq;
+  const int nq = e->nq, n_rows = batch_row_count(e);
   const u32 words = (v.span + 63) / 64;
   // workgroups per query: one once the batch fills the chip (8 per CU), more for small batches (one frame per call:
   // its ~4 500 lists over 18 workgroups), never more than its 64-list chunks need
@@ -1146,7 +1240,8 @@ int launch_select(sgtd_engine *e) {
   CHK(ensure(e, e->cand_frame, (size_t)nq * cn * sizeof(int)));
   CHK(ensure(e, e->cand_votes, (size_t)nq * cn * sizeof(int)));
   CHK(ensure(e, e->pair_off, (size_t)nq * (cn + 1) * sizeof(long long)));
-  if (e->batch_filt) CHK(prepare_filter(e, e->have_frames ? e->frame_lo : 0, span));
+  if (e->batch_prior) CHK(prepare_prior(e, e->have_frames ? e->frame_lo : 0, span));
+  else if (e->batch_filt) CHK(prepare_filter(e, e->have_frames ? e->frame_lo : 0, span));
 
   // Which passes over the match records (STDesc.cpp:404-453): one workgroup per query (select_kernels.hip.h) when
   // the batch has a query for every CU — votes + top-k in one launch while the query's vote histogram fits LDS,
@@ -1350,7 +1445,7 @@ int launch_select(sgtd_engine *e) {
       HIPCHK(hipGetLastError());
       resolve_undecided_kernel<<<64, 256, 0, e->stream>>>(vs.T, vs.Q, vs.B, e->q_M.as<u32>());
       HIPCHK(hipGetLastError());
-      if (e->batch_filt) CHK(launch_filter(e, vs));
+      if (e->batch_filt || e->batch_prior) CHK(launch_filter(e, vs));
     }
     HIPCHK(hipGetLastError());
 #ifdef SGTD_EXP_PHASE
@@ -1965,7 +2060,8 @@ int sgtd_destroy(sgtd_handle e) {
                     // (the entry-id map: missing from this list until the engine's host code ran under the sanitizers — every destroyed
                     // handle kept them, 8 bytes per map frame and, with frame ids out of insertion order, 8 bytes per entry)
                     &e->frame_first, &e->by_frame, &e->id_of_g, &e->longest,
-                    &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows};
+                    &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows,
+                    &e->pos_dev, &e->prior_dev, &e->filt_base};
   for (DevBuf *b : bufs) free_buf(*b);
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
@@ -2240,6 +2336,15 @@ static int filter_fits(sgtd_engine *e, int n_queries) {
   return SGTD_OK;
 }
 
+// a batch of n_queries against the position prior's rows: one row for all, or one per query
+static int prior_fits(sgtd_engine *e, int n_queries) {
+  if (e->prior && e->prior->n_rows > 1 && e->prior->n_rows != n_queries) {
+    e->err = "the position prior has " + std::to_string(e->prior->n_rows) + " rows for a batch of " + std::to_string(n_queries) + " queries";
+    return SGTD_ERR_INVALID;
+  }
+  return SGTD_OK;
+}
+
 static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
                               int n_queries, int device_ptrs, u32 qframe, bool loop, int32_t skip_near) {
   CHK(settle_tail(e));
@@ -2251,6 +2356,7 @@ static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *l
   e->last_qframe = qframe;
   e->loop_batch = loop; e->loop_skip = loop ? skip_near : 0;
   e->batch_filt = loop ? nullptr : e->filt;
+  e->batch_prior = loop ? nullptr : e->prior;
   e->diag = false;   // a new batch runs the product sweep; sgtd_result_rough re-runs it in the diagnostic form
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);   // (a cap a re-run needed recovers slowly)
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride * n_queries));
@@ -2279,6 +2385,7 @@ int sgtd_query_frames(sgtd_handle e, const float *xyz, const uint32_t *label, co
   if (e && e->grp) return multi::query_frames(e, xyz, label, kp_off, n_queries, device_ptrs);
   if (!e || n_queries <= 0 || !kp_off || !xyz || !label) return SGTD_ERR_INVALID;
   CHK(filter_fits(e, n_queries));
+  CHK(prior_fits(e, n_queries));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   return query_frames_batch(e, xyz, label, kp_off, n_queries, device_ptrs, e->current_frame_id, false, 0);
 }
@@ -2292,6 +2399,7 @@ int sgtd_loop_frames(sgtd_handle e, const float *xyz, const uint32_t *label, con
   }
   if (!e || n_frames <= 0 || !kp_off || !xyz || !label || skip_near < 0) return SGTD_ERR_INVALID;
   if (e->filt) { e->err = "a frame filter is set (sgtd_set_frame_filter): clear it before sgtd_loop_frames"; return SGTD_ERR_STATE; }
+  if (e->prior) { e->err = "a position prior is set (sgtd_set_position_prior): clear it before sgtd_loop_frames"; return SGTD_ERR_STATE; }
   HIPCHK(hipSetDevice(e->cfg.device_id));
   if (e->attached_to) { e->err = "the table belongs to another handle (sgtd_attach_table): a view cannot add frames"; return SGTD_ERR_STATE; }
   const u32 c = e->current_frame_id;
@@ -2305,6 +2413,7 @@ int sgtd_query_descs(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq) {
   if (e && e->grp) return multi::query_descs(e, q, nq);
   if (!e || nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame))) return SGTD_ERR_INVALID;
   CHK(filter_fits(e, 1));
+  CHK(prior_fits(e, 1));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   CHK(settle_tail(e));
   e->nq = 1;
@@ -2312,6 +2421,7 @@ int sgtd_query_descs(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq) {
   e->last_kind = 2;
   e->loop_batch = false;
   e->batch_filt = e->filt;
+  e->batch_prior = e->prior;
   e->diag = false;
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
@@ -2882,6 +2992,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   if (e && e->grp) { e->err = "not available on a multi-device handle"; return SGTD_ERR_UNSUPPORTED; }
   if (!e || !io || nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame)) || io->capacity < 0) return SGTD_ERR_INVALID;
   CHK(filter_fits(e, 1));
+  CHK(prior_fits(e, 1));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   const int cn = e->dc.cand_num;
   const bool lists_only = (io->flags & SGTD_FRAME_LISTS_ONLY) != 0;     // candidate_selector alone: no verification, every pair of every list
@@ -2904,6 +3015,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   e->last_kind = 2;
   e->loop_batch = false;
   e->batch_filt = e->filt;
+  e->batch_prior = e->prior;
   e->diag = false;
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
   CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
@@ -3194,6 +3306,110 @@ int sgtd_set_frame_filter(sgtd_handle e, uint32_t frame_lo, uint32_t n_frames, c
     for (int r = 0; r < n_rows; r++) F->rows[(size_t)r * F->words + F->words - 1] &= (1ull << (n_frames % 64)) - 1ull;
   F->serial = ++serial;
   e->filt = std::move(F);
+  return SGTD_OK;
+}
+
+// the poses of `n` frames kept on a handle (global ids: sgtd_set_frame_poses has checked them); pose12 == nullptr forgets
+static void store_poses(sgtd_engine *e, const uint32_t *frame_ids, const float *pose12, int64_t n) {
+  for (int64_t i = 0; i < n; i++) {
+    const size_t id = frame_ids[i];
+    if (id >= e->has_pose.size()) {
+      if (!pose12) continue;
+      e->has_pose.resize(id + 1, 0);
+      e->poses.resize((id + 1) * 12, 0.f);
+    }
+    e->has_pose[id] = pose12 ? 1 : 0;
+    if (pose12) std::memcpy(e->poses.data() + id * 12, pose12 + (size_t)i * 12, 12 * sizeof(float));
+  }
+}
+
+static u64 next_pose_serial() {
+  static std::atomic<u64> serial{0};
+  return ++serial;
+}
+
+int sgtd_set_frame_poses(sgtd_handle e, const uint32_t *frame_ids, const float *pose12, int64_t n) {
+  if (!e || n < 0 || (n > 0 && !frame_ids)) return SGTD_ERR_INVALID;
+  for (int64_t i = 0; i < n; i++)
+    if (frame_ids[i] >= (uint32_t)e->cfg.max_frame_n) return SGTD_ERR_FRAME_LIMIT;
+  if (e->grp) CHK(multi::set_frame_poses(e, frame_ids, pose12, n));
+  if (n == 0) {
+    if (frame_ids) return SGTD_OK;
+    e->poses.clear(); e->has_pose.clear();
+  } else {
+    store_poses(e, frame_ids, pose12, n);
+  }
+  e->poses_serial = next_pose_serial();
+  return SGTD_OK;
+}
+
+int sgtd_set_position_prior(sgtd_handle e, const double *center, const double *radius, int n_rows, int dims) {
+  if (!e || n_rows < 0) return SGTD_ERR_INVALID;
+  if (n_rows > 0) {
+    if (!center || !radius || (dims != 2 && dims != 3)) return SGTD_ERR_INVALID;
+    for (int r = 0; r < n_rows; r++) {
+      for (int i = 0; i < dims; i++)
+        if (!std::isfinite(center[(size_t)r * dims + i])) return SGTD_ERR_INVALID;
+      if (std::isnan(radius[r]) || radius[r] < 0.0) return SGTD_ERR_INVALID;
+    }
+  }
+  if (e->grp) CHK(multi::set_position_prior(e, center, radius, n_rows, dims));
+  if (n_rows == 0) { e->prior.reset(); return SGTD_OK; }
+  static std::atomic<u64> serial{0};
+  auto P = std::make_shared<PositionPrior>();
+  P->n_rows = n_rows; P->dims = dims;
+  P->prm.resize((size_t)n_rows);
+  for (int r = 0; r < n_rows; r++) {
+    const double *c = center + (size_t)r * dims;
+    P->prm[(size_t)r] = make_double4(c[0], c[1], dims == 3 ? c[2] : 0.0, radius[r] * radius[r]);
+  }
+  P->serial = ++serial;
+  e->prior = std::move(P);
+  return SGTD_OK;
+}
+
+// world[k * 12 ..] = the stored pose M of candidate k's frame composed with its relative pose (R, t cast to f32), each
+// operation an f32 rounding in the order include/sgtd_accel.h states; NaNs past n_cand, for rejected candidates and for
+// frames without a pose
+static void world_poses_of(const sgtd_engine *e, int n_cand, const int *cand_frame, const double *score, const double *pose,
+                           float *world) {
+  const int cn = e->cfg.candidate_num;
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  for (int k = 0; k < cn; k++) {
+    float *w = world + (size_t)k * 12;
+    std::fill(w, w + 12, nan);
+    if (k >= n_cand || score[k] < 0.0) continue;
+    const size_t id = (size_t)(u32)cand_frame[k];
+    if (id >= e->has_pose.size() || !e->has_pose[id]) continue;
+    const float *M = e->poses.data() + id * 12;
+    const double *rel = pose + (size_t)k * 12;
+    float R[9], t[3];
+    for (int i = 0; i < 9; i++) R[i] = (float)rel[i];
+    for (int i = 0; i < 3; i++) t[i] = (float)rel[9 + i];
+    for (int i = 0; i < 3; i++) {
+      const float *m = M + i * 4;
+      for (int j = 0; j < 3; j++) w[i * 4 + j] = (m[0] * R[j] + m[1] * R[3 + j]) + m[2] * R[6 + j];
+      w[i * 4 + 3] = ((m[0] * t[0] + m[1] * t[1]) + m[2] * t[2]) + m[3];
+    }
+  }
+}
+
+int sgtd_result_world_poses(sgtd_handle e, int q, float *world) {
+  if (!e || !world) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  std::vector<double> score((size_t)cn), pose((size_t)cn * 12);
+  std::vector<int> frames((size_t)cn);
+  int n_cand = 0;
+  if (e->grp) {
+    CHK(multi::result_verify(e, q, score.data(), pose.data()));
+    CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
+  } else {
+    CHK(sgtd_result_verify(e, q, score.data(), pose.data()));
+    CHK(sync_batch(e));
+    n_cand = e->h_n_cand[(size_t)q];
+    std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
+  }
+  world_poses_of(e, n_cand, frames.data(), score.data(), pose.data(), world);
   return SGTD_OK;
 }
 

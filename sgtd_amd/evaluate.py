@@ -103,13 +103,14 @@ def frames_near(map_xy, prior_xy, radius):
     return d2 <= float(radius) ** 2
 
 
-def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None):
+def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None, prior=None):
     """SearchLoop for a batch of query frames on the device + the node's accounting.
     map_pose4[f] = 4x4 pose of map frame f; query_pose4[q] = ground truth of query q.
-    allowed: a frame filter for the batch (STDescManager.set_frame_filter; e.g. frames_near of position priors)."""
+    allowed: a frame filter for the batch (STDescManager.set_frame_filter; e.g. frames_near of position priors).
+    prior: (center, radius), a position prior for the batch (STDescManager.set_position_prior; the map poses set)."""
     if metrics is None:
         metrics = LoopMetrics(mgr.config_setting_["candidate_num"])
-    res = mgr.query_frames(query_xyz, query_label, kp_off, allowed=allowed)
+    res = mgr.query_frames(query_xyz, query_label, kp_off, allowed=allowed, prior=prior)
     mgr.verify()
     bc, bf, bs = mgr.search_loop()
     for q in range(len(bf)):

@@ -267,6 +267,73 @@ class STDescManager:
         finally:
             self.set_frame_filter(*before) if before is not None else self.set_frame_filter(None)
 
+    def set_frame_poses(self, frame_ids, poses):
+        """map poses kept on the handle (sgtd_set_frame_poses), keyed by global frame id: `poses` (n, 12) rows of the
+        row-major 3x4 [R | t] (a graph file's "poses") or (n, 4, 4) matrices, stored as f32.  poses=None forgets the
+        poses of those ids; frame_ids=None with poses=None forgets all."""
+        if frame_ids is None:
+            if poses is not None:
+                raise ValueError("poses need their frame ids")
+            self._check(self._L.sgtd_set_frame_poses(self._h, None, None, 0))
+            return
+        ids = np.asarray(frame_ids)
+        if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+            raise ValueError("frame_ids: a 1-D array of integer frame ids")
+        if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+            raise ValueError("frame ids must lie in [0, 2^32)")
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if poses is None:
+            if ids.size:
+                self._check(self._L.sgtd_set_frame_poses(self._h, _p(ids), None, ids.size))
+            return
+        p = np.asarray(poses)
+        if p.ndim == 3 and p.shape[1:] == (4, 4):
+            p = p[:, :3, :].reshape(-1, 12)
+        if p.ndim != 2 or p.shape[1] != 12 or p.shape[0] != ids.size:
+            raise ValueError("poses: (n, 12) rows or (n, 4, 4) matrices, one per frame id")
+        p = np.ascontiguousarray(p, np.float32)
+        if ids.size:
+            self._check(self._L.sgtd_set_frame_poses(self._h, _p(ids), _p(p), ids.size))
+
+    def set_position_prior(self, center, radius=None):
+        """restrict the following queries to the map frames whose pose lies within `radius` of `center`
+        (sgtd_set_position_prior; the poses come from set_frame_poses).  center: (dims,) for one prior shared by the
+        batch or (n_queries, dims), dims 2 (x, y) or 3 (x, y, z); radius: a scalar or one per row (+inf allowed).
+        None clears the prior."""
+        if center is None:
+            self._check(self._L.sgtd_set_position_prior(self._h, None, None, 0, 2))
+            self._prior = None
+            return
+        c = np.asarray(center, np.float64)
+        if c.ndim == 1:
+            c = c[None, :]
+        if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] not in (2, 3):
+            raise ValueError("center: (dims,) or (n_rows, dims) with dims 2 or 3")
+        if not np.isfinite(c).all():
+            raise ValueError("center: finite coordinates")
+        if radius is None:
+            raise ValueError("a prior needs a radius")
+        r = np.asarray(radius, np.float64)
+        r = np.full(c.shape[0], float(r)) if r.ndim == 0 else r.reshape(-1)
+        if r.size != c.shape[0]:
+            raise ValueError("radius: a scalar or one per prior row")
+        if np.isnan(r).any() or (r < 0).any():
+            raise ValueError("radius: not NaN, not negative")
+        c, r = np.ascontiguousarray(c), np.ascontiguousarray(r)
+        self._check(self._L.sgtd_set_position_prior(self._h, _p(c), _p(r), c.shape[0], c.shape[1]))
+        self._prior = (center, radius)
+
+    def _with_prior(self, prior, call):
+        """call() under the prior `prior` = (center, radius), then the prior set before it again"""
+        if prior is None:
+            return call()
+        before = getattr(self, "_prior", None)
+        self.set_position_prior(*prior)
+        try:
+            return call()
+        finally:
+            self.set_position_prior(*before) if before is not None else self.set_position_prior(None)
+
     def attach_table(self, owner):
         """borrow the finalized table of `owner` (another manager on the same device): this manager then queries the
         same map with its own work buffers and stream — two batches in flight (include/sgtd_accel.h)"""
@@ -296,13 +363,15 @@ class STDescManager:
         return xp, lp, off, nf, dev
 
     # ---- candidate_selector -------------------------------------------------
-    def query_frames(self, xyz, label, kp_off=None, fetch=True, allowed=None):
+    def query_frames(self, xyz, label, kp_off=None, fetch=True, allowed=None, prior=None):
         """fused BuildSingleScanSTD + candidate_selector for a batch of query frames
         (semantic_graph_localization.cpp:592,601 -> STDesc.cpp:98).  Asynchronous when
-        fetch=False (results via .results()).  allowed: a frame filter for this batch only (set_frame_filter)."""
+        fetch=False (results via .results()).  allowed: a frame filter for this batch only (set_frame_filter);
+        prior: (center, radius), a position prior for this batch only (set_position_prior)."""
         xp, lp, off, nq, dev = self._frames_args(xyz, label, kp_off)
         self._nq = nq
-        self._with_filter(allowed, lambda: self._check(self._L.sgtd_query_frames(self._h, xp, lp, _p(off), nq, dev)))
+        self._with_prior(prior, lambda: self._with_filter(
+            allowed, lambda: self._check(self._L.sgtd_query_frames(self._h, xp, lp, _p(off), nq, dev))))
         return self.results() if fetch else None
 
     def loop_frames(self, xyz, label, kp_off=None, skip_near=0, batch=None, fetch=True):
@@ -465,6 +534,15 @@ class STDescManager:
         self._check(self._L.sgtd_result_verify(self._h, q, _p(score), _p(pose)))
         return score, pose[:, :9].reshape(cn, 3, 3).copy(), pose[:, 9:].copy()
 
+    def result_world_poses(self, q):
+        """sgtd_result_world_poses after verify(): (candidate_num, 12) f32, row k = the map pose of candidate k's frame
+        composed with its relative pose (row-major 3x4); NaN rows past the candidates, for rejected ones and for frames
+        without a pose"""
+        cn = self.config_setting_["candidate_num"]
+        w = np.zeros((cn, 12), np.float32)
+        self._check(self._L.sgtd_result_world_poses(self._h, int(q), _p(w)))
+        return w
+
     def result_inliers(self, q, cand, n_pairs):
         """sucess_match_vec of one candidate as positions into its match_list_"""
         idx = np.zeros(max(int(n_pairs), 1), np.int32)
@@ -497,7 +575,7 @@ class STDescManager:
         self._check(self._L.sgtd_search_loop(self._h, float(icp_threshold), _p(bc), _p(bf), _p(bs)))
         return bc, bf, bs
 
-    def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None):
+    def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None, prior=None):
         """sgtd_search_frame: candidate_selector + candidate_verify + the inlier pairs of every candidate with their table
         entries for ONE query frame given as descriptors, in one call -> dict(n_cand, cand_frame, cand_votes, pair_off,
         score, rot, t, inlier_off, inlier_q_idx, entries (Descs), n_inliers, status).  page_locked: the arrays the inlier
@@ -505,7 +583,9 @@ class STDescManager:
         place and the call has one wait (ordinary arrays are filled from the handle's own page-locked block).
         lists_only (SGTD_FRAME_LISTS_ONLY): candidate_selector alone — no verification, inlier_off = pair_off and the pairs
         handed back are all pairs of every candidate's match list.  allowed: a frame filter for this call only
-        (set_frame_filter)"""
+        (set_frame_filter); prior: (center, radius), a position prior for this call only (set_position_prior)"""
+        if prior is not None:
+            return self._with_prior(prior, lambda: self.search_frame(stds_vec, capacity, page_locked, lists_only, allowed))
         if allowed is not None:
             return self._with_filter(allowed, lambda: self.search_frame(stds_vec, capacity, page_locked, lists_only))
         from ._lib import FrameSearch
