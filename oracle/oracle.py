@@ -242,6 +242,14 @@ class OracleManager:
         L.orc_audit_select.restype = None
         L.orc_audit_select(self._h, C.byref(acc))
 
+    def audit_select_query(self, acc):
+        """the loop of the last select (its query descriptors), audited (accumulates into `acc`; min_cell_margin from the
+        query's sides)"""
+        L = lib()
+        L.orc_audit_select_query.argtypes = [C.c_void_p, C.POINTER(OrcAudit)]
+        L.orc_audit_select_query.restype = None
+        L.orc_audit_select_query(self._h, C.byref(acc))
+
     def verify_hyp_inputs(self, cand):
         """per hypothesis of candidate `cand` of the last select: covariance matrix (:558), query centre, table centre"""
         L = lib()

@@ -871,9 +871,8 @@ void orc_audit_build(orc_manager *mg, const float *xyz, const uint32_t *label, i
   }
 }
 
-void orc_audit_select(orc_manager *mg, orc_audit *A) {
+static void audit_select(orc_manager *mg, const std::vector<Desc> &q, orc_audit *A) {
   using namespace audit;
-  const std::vector<Desc> &q = mg->last;
   const double rough = mg->cfg.rough_dis_threshold;
   auto &db = mg->data_base_;
   omp_set_num_threads(mg->cfg.num_threads > 0 ? mg->cfg.num_threads : 1);
@@ -931,6 +930,22 @@ void orc_audit_select(orc_manager *mg, orc_audit *A) {
     if (p.min_margin < A->min_margin) { A->min_margin = p.min_margin; A->min_margin_ulps = p.min_margin_ulps; }
     lower(A->min_gate_margin, p.min_gate_margin);
   }
+}
+
+void orc_audit_select(orc_manager *mg, orc_audit *A) { audit_select(mg, mg->last, A); }
+
+// the same for the descriptors of the last orc_select (its query given as descriptors or not); also lowers
+// min_cell_margin with every query side's distance to an integer (the probe's truncation) and every visited entry's
+// distance to k + 0.5 (the insert's rounding)
+void orc_audit_select_query(orc_manager *mg, orc_audit *A) {
+  using audit::lower;
+  audit_select(mg, mg->last_query, A);
+  for (const Desc &d : mg->last_query)
+    for (int k = 0; k < 3; k++) {
+      const double fr = d.side_length_[k] - std::floor(d.side_length_[k]);
+      lower(A->min_cell_margin, std::min(fr, 1.0 - fr));
+      lower(A->min_cell_margin, std::fabs(fr - 0.5));
+    }
 }
 
 }  // extern "C"

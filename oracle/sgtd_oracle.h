@@ -166,6 +166,8 @@ typedef struct orc_audit {
 void orc_audit_build(orc_manager *m, const float *xyz, const uint32_t *label, int n, orc_audit *acc);
 /* audits candidate_selector's loop for the last built frame against the table (results are not kept) */
 void orc_audit_select(orc_manager *m, orc_audit *acc);
+/* the same for the query of the last orc_select; min_cell_margin from its sides */
+void orc_audit_select_query(orc_manager *m, orc_audit *acc);
 
 /* ---- the same for candidate_verify (STDesc.cpp:462-547): Eigen::JacobiSVD is the third inferred piece (this restatement
  * solves the 3x3 problem with a one-sided Jacobi SVD).  The caller hands in the hypotheses (R row-major, t: 12 doubles each)

@@ -203,6 +203,14 @@ __global__ __launch_bounds__(256) void query_prefix_kernel(const u32 *count, u32
   if (threadIdx.x == 0) *n_valid = carry;
 }
 
+// cell coordinate of a home key: (int)side, or the all-ones marker where that does not fit cbits - 1 bits or where the
+// side's probe cells are not those of the other descriptors of its home cell.  In cell 0 a side whose side - 1
+// truncates below 0 (a side below about 2^-54, +-0, or a negative side) probes cell -1 (STDesc.cpp:359) where a side
+// in [2^-54, 1) probes cell 0 a second time: group_resolve_kernel resolves a group from its first member's sides.
+__device__ __forceinline__ u64 home_coord(double s, u64 cmask) {
+  return (int)(s - 1.0) < 0 ? cmask : min((u64)(u32)(int)s, cmask);
+}
+
 // Below the cell, the home key carries `sub_bits` bits (0..6) of where in the cell's second and third
 // interval the descriptor lies (2^(sub_bits / 2) x 2^(sub_bits - sub_bits / 2) classes), so that the
 // descriptors of a pass (up to four consecutive positions of one home cell) reach about the same slices of
@@ -220,10 +228,10 @@ __global__ void home_keys_kernel(QueryView Q, const u32 *q_prefix, KeyT *keys, u
   if (i >= Q.count[q]) return;
   const u64 code = label_code(Q.label[d * 3 + 0], Q.label[d * 3 + 1], Q.label[d * 3 + 2]);
   const u64 cmask = (1ull << cbits) - 1ull;
-  // a coordinate that does not fit cbits-1 bits becomes the all-ones marker: such a
-  // descriptor never shares a group (group_heads_kernel), so aliasing cannot merge cells
-  const u64 x = min((u64)(u32)(int)Q.side[d * 3 + 0], cmask), y = min((u64)(u32)(int)Q.side[d * 3 + 1], cmask),
-            z = min((u64)(u32)(int)Q.side[d * 3 + 2], cmask);
+  // a coordinate that does not fit cbits-1 bits (or probes cell -1, home_coord) becomes the all-ones
+  // marker: such a descriptor never shares a group (group_heads_kernel), so aliasing cannot merge cells
+  const u64 x = home_coord(Q.side[d * 3 + 0], cmask), y = home_coord(Q.side[d * 3 + 1], cmask),
+            z = home_coord(Q.side[d * 3 + 2], cmask);
   const u32 idx = q_prefix[q] + i;
   const int ny = 1 << (sub_bits >> 1), nz = 1 << (sub_bits - (sub_bits >> 1));
   const double f1 = Q.side[d * 3 + 1] - (double)(int)Q.side[d * 3 + 1], f2 = Q.side[d * 3 + 2] - (double)(int)Q.side[d * 3 + 2];
@@ -290,8 +298,8 @@ __global__ __launch_bounds__(256) void group_resolve_kernel(TableView T, QueryVi
     // differs only for a side that is the largest double below a power of two (side + 1 rounds up
     // across the integer): such a descriptor's own gate mask, computed with the float form like
     // the reference, excludes that cell on both sides.
-    // (a descriptor with a negative side — outside the envelope — is a group of its own,
-    // home_keys_kernel, and keeps the float form)
+    // (a descriptor with a negative side — outside the envelope — or a side below 2^-54 is a group of
+    // its own, home_coord, and keeps the float form where the side is negative)
     const bool nonneg = q0 >= 0.0 && q1 >= 0.0 && q2 >= 0.0;
     const int x = nonneg ? max((int)q0 + ix, 0) : (int)(q0 + (double)ix);
     const int y = nonneg ? max((int)q1 + iy, 0) : (int)(q1 + (double)iy);
@@ -451,8 +459,8 @@ __global__ __launch_bounds__(SGTD_SMALL_THREADS) void small_order_kernel(QueryVi
     u64 k = ~0ull;
     if (d < nv) {
       const u64 code = label_code(Q.label[d * 3 + 0], Q.label[d * 3 + 1], Q.label[d * 3 + 2]);
-      const u64 x = min((u64)(u32)(int)Q.side[d * 3 + 0], cmask), y = min((u64)(u32)(int)Q.side[d * 3 + 1], cmask),
-                z = min((u64)(u32)(int)Q.side[d * 3 + 2], cmask);
+      const u64 x = home_coord(Q.side[d * 3 + 0], cmask), y = home_coord(Q.side[d * 3 + 1], cmask),
+                z = home_coord(Q.side[d * 3 + 2], cmask);
       const double f1 = Q.side[d * 3 + 1] - (double)(int)Q.side[d * 3 + 1], f2 = Q.side[d * 3 + 2] - (double)(int)Q.side[d * 3 + 2];
       const u64 sub = (u64)min(max((int)(f1 * ny), 0), ny - 1) * nz + (u64)min(max((int)(f2 * nz), 0), nz - 1);
       const u32 key = (u32)(((((code << S.cbits | x) << S.cbits | y) << S.cbits) | z) << S.sub_bits | sub);
