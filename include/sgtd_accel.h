@@ -167,7 +167,12 @@ int sgtd_current_frame_id(sgtd_handle h, uint32_t *out);
  * utility.hpp:646-659), host memory.  Descriptors are stamped with the
  * current frame id.  out arrays must hold sgtd_max_descs(h, n) descriptors.
  * A frame with n < K yields 0 descriptors (the reference reads past its k-NN
- * result there). */
+ * result there).  A frame too large for the build kernel's LDS (3638 keypoints
+ * at K = 10) is SGTD_ERR_UNSUPPORTED, more than 65535 SGTD_ERR_INVALID.
+ * Outside the contract: labels >= 2^31 (the reference's (int) of the label as a
+ * double is undefined; labels up to 2^31 - 1 are the reference's), and, with
+ * descriptor_min_len = 0, coordinates so far apart that the f32 squared distance
+ * of the k-NN search overflows. */
 int64_t sgtd_max_descs(sgtd_handle h, int n_keypoints);
 int sgtd_build(sgtd_handle h, const float *xyz, const uint32_t *label, int n,
                sgtd_desc_soa *out, int64_t capacity, int64_t *n_out);

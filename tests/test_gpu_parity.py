@@ -3,8 +3,14 @@
 Bar (BASELINE.json north_star): bit-exact candidate indices, vote counts, match
 lists and table layout; descriptor distances within 1e-5 (asserted bit-equal).
 """
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _build_edges import field_bits_equal  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -12,11 +18,10 @@ DESC_FIELDS = ("side", "angle", "center", "vertex", "label", "frame", "node_id")
 
 
 def assert_descs_equal(g, o):
+    """bit for bit (-0.0 is not +0.0; NaN equals NaN whatever its sign and payload)"""
     assert g.n == o.n
     for f in DESC_FIELDS:
-        a, b = getattr(g, f), getattr(o, f)
-        np.testing.assert_array_equal(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64),
-                                      err_msg=f)
+        assert field_bits_equal(getattr(g, f), getattr(o, f)), f
 
 
 @pytest.fixture(scope="module")
@@ -270,7 +275,7 @@ def test_query_against_empty_table(mods):
 
 @pytest.mark.parametrize("n_kp", [420, 900])
 def test_large_frames_use_the_global_dedup_path(mods, n_kp):
-    """frames whose dedup tables do not fit LDS (N > ~380) take the global-memory variant"""
+    """frames whose dedup tables do not fit LDS (N > 294 at K = 10: _build_edges.lds_switch) take the global-memory variant"""
     _, _, synth = mods
     g, o = _pair(mods)
     m = synth.make_map(3, n_kp, stream=95)
