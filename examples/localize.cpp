@@ -3,7 +3,9 @@
 // on the C ABI alone: graph-JSON directories in, localization statistics out.  No ROS, no PCL,
 // no GICP (enable_gicp = false); BASE2OUSTER = identity.
 //
-//   localize <map_dir | map.cache> <query_dir | query.cache> [batch=256] [icp_threshold=0.4] [prior_radius]
+//   localize <map_dir | map.cache> <query_dir | query.cache> [batch=256] [icp_threshold=0.4] [prior_radius] [--refine N]
+//   --refine N (anywhere on the line): sgtd_refine_poses(h, N) after the verification — the relative pose of SearchLoop's
+//   choice refitted over all its inlier pairs — and a second set of error lines for the refined poses (off by default)
 //   prior_radius: restrict every query to the map frames within that many metres (x, y) of its ground-truth position
 //   (sgtd_set_frame_poses + sgtd_set_position_prior), as a localizer with odometry would, and report how many map
 //   frames a query was allowed on average (the LOCALIZE_PER_FRAME calls below run without it)
@@ -19,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <filesystem>
 #include <malloc.h>
 #include <string>
@@ -119,8 +122,17 @@ static int load_any(const char *path, Graphs &g) {
 }
 
 int main(int argc, char **argv) {
+  int refine = 0;                                            // --refine N, taken out of the positional arguments
+  for (int i = 1; i < argc; i++)
+    if (!std::strcmp(argv[i], "--refine")) {
+      refine = i + 1 < argc ? std::atoi(argv[i + 1]) : 0;
+      if (refine < 1) { std::fprintf(stderr, "--refine needs a number of iterations >= 1\n"); return 2; }
+      for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+      argc -= 2;
+      break;
+    }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold] [prior_radius]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold] [prior_radius] [--refine N]\n", argv[0]);
     return 2;
   }
   // SearchLoop hands back ~130 MB of std::pair<STDesc, STDesc> per frame (the reference's own result
@@ -169,6 +181,9 @@ int main(int argc, char **argv) {
   long total_num = 0, detected = 0, score_num = 0, test_10 = 0;
   std::vector<long> STD_num(cn, 0);
   double err_t = 0, err_r = 0;
+  long ref_score_num = 0;                                    // --refine: the same accounting with the refined poses
+  double ref_err_t = 0, ref_err_r = 0, ref_rmse = 0, ver_rmse = 0;
+  std::vector<double> ref_pose((size_t)cn * 12), ref_rmse_v(cn), ver_rmse_v(cn);
   std::vector<int32_t> n_cand(batch), cand_frame((size_t)batch * cn), best_cand(batch), best_frame(batch);
   std::vector<double> best_score(batch), score(cn), pose((size_t)cn * 12);
   for (int q0 = 0; q0 < qs.n; q0 += batch) {                 // :567-745, `batch` queries per call
@@ -197,6 +212,7 @@ int main(int argc, char **argv) {
     OK(sgtd_verify(h));
     OK(sgtd_search_loop(h, icp_threshold, best_cand.data(), best_frame.data(), best_score.data()));
     OK(sgtd_result_candidates(h, n_cand.data(), cand_frame.data(), nullptr, nullptr));
+    if (refine) OK(sgtd_refine_poses(h, refine));
     auto tb2 = std::chrono::steady_clock::now();
     if (std::getenv("LOCALIZE_VERBOSE"))
       std::printf("  batch at %d: select %.1f ms, verify + choice %.1f ms\n", q0,
@@ -225,6 +241,18 @@ int main(int argc, char **argv) {
       double te, re;
       compute_adj_rpe(gt, mul(from_row(map.poses + (size_t)best_frame[i] * 12), nt), te, re);   // :733-735
       if (te < 5 && re < 10) { score_num++; err_t += te; err_r += re; }
+      if (refine) {                                          // the refined pose of the same candidate in place of loop_transform
+        OK(sgtd_result_refined(h, i, ref_pose.data(), ref_rmse_v.data(), ver_rmse_v.data(), nullptr, nullptr));
+        const double *r = &ref_pose[(size_t)best_cand[i] * 12];
+        for (int a = 0; a < 3; a++) {
+          for (int b = 0; b < 3; b++) nt.m[a][b] = (float)r[a * 3 + b];
+          nt.m[a][3] = (float)r[9 + a];
+        }
+        compute_adj_rpe(gt, mul(from_row(map.poses + (size_t)best_frame[i] * 12), nt), te, re);
+        if (te < 5 && re < 10) { ref_score_num++; ref_err_t += te; ref_err_r += re; }
+        ref_rmse += ref_rmse_v[best_cand[i]];
+        ver_rmse += ver_rmse_v[best_cand[i]];
+      }
     }
   }
   auto t3 = std::chrono::steady_clock::now();
@@ -235,6 +263,14 @@ int main(int argc, char **argv) {
     std::printf("position prior %.2f m: %.1f map frames allowed per query (%ld in all)\n", prior_radius,
                 total_num ? (double)allowed_sum / total_num : 0.0, allowed_sum);
   std::printf("mean errors of the successes: %.4f m, %.4f deg\n", score_num ? err_t / score_num : 0.0, score_num ? err_r / score_num : 0.0);
+  if (refine) {
+    std::printf("refined poses (%d iteration%s): success(5m,10deg) %ld (%.4f)\n", refine, refine == 1 ? "" : "s", ref_score_num,
+                total_num ? (double)ref_score_num / total_num : 0.0);
+    std::printf("mean errors of the successes, refined: %.4f m, %.4f deg\n", ref_score_num ? ref_err_t / ref_score_num : 0.0,
+                ref_score_num ? ref_err_r / ref_score_num : 0.0);
+    std::printf("mean inlier rmse of the chosen candidates: %.4f m refined, %.4f m under the verification's pose\n",
+                detected ? ref_rmse / detected : 0.0, detected ? ver_rmse / detected : 0.0);
+  }
   std::printf("time: load %.1f ms, map build %.1f ms, queries %.1f ms (%.3f ms per query incl. verification), %d device(s)\n", ms(t0, t1), ms(t1, t2),
               ms(t2, t3), total_num ? ms(t2, t3) / total_num : 0.0, sgtd_device_count(h));
   if (const char *pf = std::getenv("LOCALIZE_PER_FRAME")) {

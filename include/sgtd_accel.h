@@ -403,6 +403,54 @@ int sgtd_result_verify(sgtd_handle h, int q, double *score, double *pose);
  * Computed in the library's host code; a multi-device handle gives the single-device values bit for bit.  h == NULL,
  * world == NULL, q outside the batch or no verification yet: SGTD_ERR_INVALID. */
 int sgtd_result_world_poses(sgtd_handle h, int q, float *world);
+
+/* Least-squares refit of every verified candidate's relative pose over ALL its inlier pairs, on the device, after
+ * sgtd_verify (or sgtd_verify_masked, or sgtd_search_frame with flags 0).  sgtd_verify's pose is the motion of one triangle
+ * pair (three points); this one averages over the whole inlier set and reports its RMS residual.  iterations >= 1:
+ * iteration i >= 2 first re-selects the inliers under the pose of iteration i - 1. */
+/* The rule, for candidate k of query q.  All arithmetic is f64, every operation rounded once (no contraction).
+ * Inputs: the pairs j = 0 .. n_list-1 of the candidate's match list in list order (sgtd_result_pairs).  A pair of the
+ * current set contributes three correspondences (p, w) in the order A, B, C: p = the query descriptor's vertex, w = the
+ * table entry's vertex, f32 values widened exactly.  Set 0 is sgtd_verify's inlier set (sgtd_result_inliers).
+ * A sum over the set, written SUM below, has this fixed order: 256 accumulators acc[0..255], each starting at +0.0;
+ * acc[l] takes the pairs at list positions j == l (mod 256) in ascending j, and of a pair its correspondences A, B, C in
+ * that order, one addition each (acc = acc + term); a pair outside the set is skipped, not added as zero.  Then
+ * acc[l] = acc[l] + acc[l + s] for all l < s, for s = 128, 64, 32, 16, 8, 4, 2, 1 in turn; SUM = acc[0].  Sums of vectors
+ * and matrices are taken component by component.
+ * Fit: n = pairs in the set, d = (double)(3 n); cp = SUM(p) / d, cw = SUM(w) / d;
+ *   H[i][j] = SUM((p[i] - cp[i]) * (w[j] - cw[j]));
+ *   R from H exactly as triangle_solver (STDesc.cpp:558-568) obtains rot from its covariance, with sgtd_verify's 3x3
+ *   solver: H = U S V^T (one-sided Jacobi), R = V U^T, and R = V diag(1, 1, -1) U^T when det(V U^T) < 0;
+ *   t[i] = -((R[i][0]*cp[0] + R[i][1]*cp[1]) + R[i][2]*cp[2]) + cw[i]     (:569).
+ * Residual of a correspondence under a pose (R, t): x[i] = ((R[i][0]*p[0] + R[i][1]*p[1]) + R[i][2]*p[2]) + t[i],
+ *   e[i] = x[i] - w[i], r2 = (e[0]*e[0] + e[1]*e[1]) + e[2]*e[2]   (candidate_verify's distance, :488-505, squared).
+ * Iteration i >= 2: the next set = every pair of the list whose three correspondences all have r2 < 9.0 under the pose of
+ * iteration i - 1 (sqrt(r2) < 3.0, sgtd_verify's exact test).  If it has fewer than 4 pairs, or equals the current set,
+ * the loop stops and the result of iteration i - 1 stands; otherwise it becomes the current set and is fitted.
+ * Results: pose = (R, t) of the last fit, n_pairs = n of its set, moments = cp, cw, H of that fit,
+ *   rmse = sqrt(SUM(r2 under (R, t)) / d), rmse_verify = sqrt(SUM(r2 under sgtd_verify's pose) / d), over that same set.
+ * With iterations == 1, n_pairs[k] == score[k] of sgtd_result_verify and rmse <= rmse_verify up to rounding.
+ * The call adds results and changes none: sgtd_result_verify, sgtd_result_inliers, sgtd_result_inlier_*, sgtd_search_loop
+ * and sgtd_result_world_poses return what they returned before (re-selected sets live in a buffer of their own).  A new
+ * batch or a new sgtd_verify* drops the refined results.  A view (sgtd_attach_table) has refined results of its own; a
+ * multi-device handle forwards the call to every shard and fetches each candidate's result from its owner.
+ * h == NULL or iterations < 1: SGTD_ERR_INVALID, before the device is touched; no verification of the pending batch yet:
+ * SGTD_ERR_STATE; a view whose owner's table changed: SGTD_ERR_STATE, as for sgtd_verify. */
+int sgtd_refine_poses(sgtd_handle h, int iterations);
+/* Refined results of every candidate of query q; cn = candidate_num; any pointer may be NULL.  A candidate without a
+ * verification result (past n_cand, score -1, masked out by sgtd_verify_masked) gets 12 zeros, NaN rmse and rmse_verify,
+ * 0 pairs and NaN moments.  h == NULL: SGTD_ERR_INVALID; before sgtd_refine_poses on this batch: SGTD_ERR_STATE; q outside
+ * the batch: SGTD_ERR_INVALID. */
+int sgtd_result_refined(sgtd_handle h, int q,
+                        double *pose,        /* [cn*12] rot row-major (9), t (3)             */
+                        double *rmse,        /* [cn] residual under the refined pose         */
+                        double *rmse_verify, /* [cn] same points, sgtd_verify's pose         */
+                        int32_t *n_pairs,    /* [cn] inlier pairs of the final set           */
+                        double *moments);    /* [cn*15] cp(3), cw(3), H(9): parity output    */
+/* sgtd_result_world_poses with the refined relative pose in place of sgtd_verify's: the same composition rule, in the
+ * library's host code (a multi-device handle gives the single-device values bit for bit); 12 NaNs where the candidate
+ * has no result or its frame has no pose.  world == NULL: SGTD_ERR_INVALID; otherwise as sgtd_result_refined. */
+int sgtd_result_refined_world_poses(sgtd_handle h, int q, float *world);
 /* asynchronous device-to-device export of the verification results of the whole batch into
  * caller device buffers (score f64 [n_queries*candidate_num], pose f64 [n_queries*candidate_num*12]),
  * enqueued on the handle's stream without synchronising: the table-sharded multi-GPU path

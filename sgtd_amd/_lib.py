@@ -31,6 +31,7 @@ SYMBOLS = [
     "sgtd_gather_verified_dev", "sgtd_set_deferred_lists", "sgtd_finish_lists", "sgtd_verify_masked", "sgtd_attach_table", "sgtd_search_frame",
     "sgtd_loop_frames", "sgtd_remove_frames", "sgtd_set_frame_filter",
     "sgtd_set_frame_poses", "sgtd_set_position_prior", "sgtd_result_world_poses",
+    "sgtd_refine_poses", "sgtd_result_refined", "sgtd_result_refined_world_poses",
 ]
 
 
@@ -149,6 +150,9 @@ def lib():
     L.sgtd_set_frame_poses.argtypes = [vp, vp, vp, i64]
     L.sgtd_set_position_prior.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_result_world_poses.argtypes = [vp, C.c_int, vp]
+    L.sgtd_refine_poses.argtypes = [vp, C.c_int]
+    L.sgtd_result_refined.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.sgtd_result_refined_world_poses.argtypes = [vp, C.c_int, vp]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

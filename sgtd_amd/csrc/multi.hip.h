@@ -23,7 +23,7 @@ struct Group {
   int n = 0;
   u32 current_frame_id = 0;              // global
   int nq = 0;
-  bool batch_valid = false, merged = false, verified = false;
+  bool batch_valid = false, merged = false, verified = false, refined = false;
   // merged candidate tables of the last batch
   std::vector<int> n_cand, cand_frame, cand_votes, owner, owner_slot;
   std::vector<long long> pair_off;       // [nq * (cn + 1)] offsets into the query's concatenated lists
@@ -57,6 +57,8 @@ int result_query_descs(sgtd_engine *e, int q, sgtd_desc_soa *out, int64_t capaci
 int result_votes(sgtd_engine *e, int q, uint32_t *votes, int64_t capacity, uint32_t *frame_lo, int64_t *n);
 int verify(sgtd_engine *e);
 int result_verify(sgtd_engine *e, int q, double *score, double *pose);
+int refine_poses(sgtd_engine *e, int iterations);
+int result_refined(sgtd_engine *e, int q, double *pose, double *rmse, double *rmse_verify, int32_t *n_pairs, double *moments);
 int result_inliers(sgtd_engine *e, int q, int cand, int32_t *idx, int64_t capacity, int64_t *n);
 int result_inlier_pairs(sgtd_engine *e, int q, int64_t *cand_off, int32_t *q_idx, int64_t *db_entry, int64_t capacity, int64_t *n_pairs);
 int search_loop(sgtd_engine *e, double icp_threshold, int32_t *best_cand, int32_t *best_frame, double *best_score);

@@ -213,7 +213,7 @@ int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const 
   // every device builds the query descriptors itself and sweeps its shard; the calls only
   // enqueue, so the devices run concurrently
   for (sgtd_engine *c : g->dev) MCHK(sgtd_query_frames(c, xyz, label, kp_off, n_queries, 0));
-  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false;
+  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false;
   return SGTD_OK;
 }
 
@@ -235,7 +235,7 @@ int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq) {
     t.frame = lf.data();
     MCHK(sgtd_query_descs(c, &t, nq));
   }
-  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false;
+  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false;
   return SGTD_OK;
 }
 
@@ -409,6 +409,7 @@ int result_votes(sgtd_engine *e, int q, uint32_t *votes, int64_t capacity, uint3
 int verify(sgtd_engine *e) {
   Group *g = G(e);
   CHK(merge(e));
+  g->refined = false;
   for (sgtd_engine *c : g->dev) MCHK(sgtd_verify(c));   // every owner verifies its local candidates
   g->verified = true;
   return SGTD_OK;
@@ -433,6 +434,50 @@ int result_verify(sgtd_engine *e, int q, double *score, double *pose) {
     }
     if (score) score[k] = ss[s][ks];
     if (pose) std::copy(pp[s].begin() + (size_t)ks * 12, pp[s].begin() + (size_t)ks * 12 + 12, pose + (size_t)k * 12);
+  }
+  return SGTD_OK;
+}
+
+// every owner refits the poses of its local candidates
+int refine_poses(sgtd_engine *e, int iterations) {
+  Group *g = G(e);
+  if (!g->batch_valid || !g->verified) { e->err = "sgtd_refine_poses needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  g->refined = false;
+  for (sgtd_engine *c : g->dev) MCHK(sgtd_refine_poses(c, iterations));
+  g->refined = true;
+  return SGTD_OK;
+}
+
+// the refined results of query q's merged candidates, each from its owner (result_verify's pattern)
+int result_refined(sgtd_engine *e, int q, double *pose, double *rmse, double *rmse_verify, int32_t *n_pairs, double *moments) {
+  Group *g = G(e);
+  if (!g->batch_valid || !g->verified || !g->refined) { e->err = "no refined poses: sgtd_refine_poses comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  struct Owned { std::vector<double> pose, rmse, rmse_v, mom; std::vector<int32_t> np; };
+  std::vector<Owned> own(g->n);
+  for (int k = 0; k < cn; k++) {
+    if (pose) std::fill(pose + (size_t)k * 12, pose + (size_t)k * 12 + 12, 0.0);
+    if (rmse) rmse[k] = nan;
+    if (rmse_verify) rmse_verify[k] = nan;
+    if (n_pairs) n_pairs[k] = 0;
+    if (moments) std::fill(moments + (size_t)k * 15, moments + (size_t)k * 15 + 15, nan);
+  }
+  for (int k = 0; k < g->n_cand[q]; k++) {
+    const size_t i = (size_t)q * cn + k;
+    const int s = g->owner[i], ks = g->owner_slot[i];
+    Owned &o = own[s];
+    if (o.np.empty()) {
+      sgtd_engine *c = g->dev[s];
+      o.pose.resize((size_t)cn * 12); o.rmse.resize(cn); o.rmse_v.resize(cn); o.mom.resize((size_t)cn * 15); o.np.resize(cn);
+      MCHK(sgtd_result_refined(c, q, o.pose.data(), o.rmse.data(), o.rmse_v.data(), o.np.data(), o.mom.data()));
+    }
+    if (pose) std::copy(o.pose.begin() + (size_t)ks * 12, o.pose.begin() + (size_t)ks * 12 + 12, pose + (size_t)k * 12);
+    if (rmse) rmse[k] = o.rmse[ks];
+    if (rmse_verify) rmse_verify[k] = o.rmse_v[ks];
+    if (n_pairs) n_pairs[k] = o.np[ks];
+    if (moments) std::copy(o.mom.begin() + (size_t)ks * 15, o.mom.begin() + (size_t)ks * 15 + 15, moments + (size_t)k * 15);
   }
   return SGTD_OK;
 }

@@ -27,6 +27,7 @@
 #include "remove_kernels.hip.h"
 #include "filter_kernels.hip.h"
 #include "prior_kernels.hip.h"
+#include "refine_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -252,6 +253,10 @@ struct sgtd_engine {
   DevBuf v_hypB, v_tau, v_words;              // the matrix-core vote pass: hypothesis features, |t|^2, vote words
   DevBuf v_okey[2], v_oval[2];                // its dispatch order: (candidate frame, candidate index) sorted
   bool verified = false;
+  // sgtd_refine_poses (refine_kernels.hip.h): the refit poses, residuals, pair counts and moments of the batch, and the
+  // flags of the re-selected sets (two halves; sgtd_verify's v_inlier is only read)
+  DevBuf r_pose, r_rmse, r_rmse_v, r_npairs, r_moments, r_flag;
+  bool refined = false;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -1102,7 +1107,7 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
     HIPCHK(hipGetLastError());
   }
   e->lists_pending = false;
-  e->verified = false;
+  e->verified = false; e->refined = false;
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -1512,7 +1517,7 @@ int launch_select(sgtd_engine *e) {
       batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
       HIPCHK(hipGetLastError());
       e->lists_pending = true;
-      e->verified = false;
+      e->verified = false; e->refined = false;
       e->batch_synced = false;
       return SGTD_OK;
     }
@@ -1569,7 +1574,7 @@ int launch_select(sgtd_engine *e) {
     HIPCHK(hipGetLastError());
   }
   e->batch_valid = true;
-  e->verified = false;
+  e->verified = false; e->refined = false;
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -2052,7 +2057,7 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->seg[1].hot, &e->seg[1].perm, &e->seg[1].hash, &e->seg[1].bucket_start, &e->seg[1].bucket_key, &e->seg[1].dir, &e->slice_of, &e->sq_sum,
                     &e->keyA, &e->keyB, &e->valA, &e->valB, &e->hist, &e->digit_tot, &e->flags, &e->bad_flag,
                     &e->kp_off_dev, &e->xyz_dev, &e->label_dev, &e->b_kp_off_dev, &e->b_xyz_dev, &e->b_label_dev, &e->ws_keys, &e->ws_slots, &e->cnt_scan,
-                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
+                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
                     &e->votes, &e->slot_of, &e->q_M, &e->q_P, &e->q_pairs, &e->q_pair_base,
                     &e->blk_count, &e->c_pair, &e->c_blk, &e->amb_queue, &e->rec, &e->rec_cell, &e->rec_dis, &e->rough_qi,
                     &e->rough_entry, &e->rough_frame, &e->rough_cell, &e->rough_dis, &e->n_cand, &e->cand_frame,
@@ -2811,6 +2816,7 @@ int sgtd_verify(sgtd_handle e) {
   CHK(sync_batch(e));
   if (!e->batch_valid) return SGTD_ERR_INVALID;
   const int cn = e->dc.cand_num, nq = e->nq;
+  e->refined = false;
   if (nq == 0) { e->verified = true; return SGTD_OK; }
   int64_t total = 0;
   for (int q = 0; q < nq; q++) total = std::max<int64_t>(total, (int64_t)e->h_pair_base[q] + e->h_pair_off[(size_t)q * (cn + 1) + cn]);
@@ -3170,7 +3176,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   }
   stage_times(e);
   e->batch_synced = true;
-  e->verified = !lists_only;
+  e->verified = !lists_only; e->refined = false;
   io->n_cand = (int32_t)w[12];
   if (io->cand_frame) std::memcpy(io->cand_frame, cf, (size_t)cn * 4);
   if (io->cand_votes) std::memcpy(io->cand_votes, cv, (size_t)cn * 4);
@@ -3410,6 +3416,95 @@ int sgtd_result_world_poses(sgtd_handle e, int q, float *world) {
     std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
   }
   world_poses_of(e, n_cand, frames.data(), score.data(), pose.data(), world);
+  return SGTD_OK;
+}
+
+// ---- sgtd_refine_poses: the least-squares refit over every candidate's inlier pairs (refine_kernels.hip.h) ----
+int sgtd_refine_poses(sgtd_handle e, int iterations) {
+  if (!e || iterations < 1) return SGTD_ERR_INVALID;
+  if (e->grp) return multi::refine_poses(e, iterations);
+  if (!e->batch_valid || !e->verified) { e->err = "sgtd_refine_poses needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(sync_batch(e));
+  e->refined = false;
+  const int cn = e->dc.cand_num, nq = e->nq;
+  if (nq == 0) { e->refined = true; return SGTD_OK; }
+  int64_t total = 0;
+  for (int q = 0; q < nq; q++) total = std::max<int64_t>(total, (int64_t)e->h_pair_base[q] + e->h_pair_off[(size_t)q * (cn + 1) + cn]);
+  const size_t nb = (size_t)nq * cn, half = (size_t)std::max<int64_t>(total, 1);
+  CHK(ensure(e, e->r_pose, nb * 12 * sizeof(double)));
+  CHK(ensure(e, e->r_rmse, nb * sizeof(double)));
+  CHK(ensure(e, e->r_rmse_v, nb * sizeof(double)));
+  CHK(ensure(e, e->r_npairs, nb * sizeof(int)));
+  CHK(ensure(e, e->r_moments, nb * 15 * sizeof(double)));
+  if (iterations > 1) CHK(ensure(e, e->r_flag, 2 * half));
+  RefineParams P;
+  P.pairs = e->pairs.as<u64>(); P.pair_off = e->pair_off.as<long long>(); P.q_pair_base = e->q_pair_base.as<u32>();
+  P.n_cand = e->n_cand.as<int>(); P.cand_num = cn; P.q_stride = e->q_stride;
+  P.q_vertex = e->qd.vertex.as<float>(); P.t_vertex = e->tab.vertex.as<float>();
+  P.score = e->v_score.as<double>(); P.v_pose = e->v_pose.as<double>(); P.v_inlier = e->v_inlier.as<unsigned char>();
+  P.flag = e->r_flag.as<unsigned char>(); P.flag_half = half;
+  P.thr2 = 9.0;                 // (verify_enqueue's: sqrt_rn(y) < 3.0 <=> y < 9.0)
+  P.iterations = iterations;
+  P.order = nullptr; P.n_blocks = (u32)nb;
+  P.pose = e->r_pose.as<double>(); P.rmse = e->r_rmse.as<double>(); P.rmse_verify = e->r_rmse_v.as<double>();
+  P.n_pairs = e->r_npairs.as<int>(); P.moments = e->r_moments.as<double>();
+  // a batch of many candidates in the order of the candidates' frames, as its verification was dispatched: the table
+  // gathers of one frame stay close
+  if (nb >= 4096 && e->have_frames) {
+    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
+    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
+    const u32 last = e->frame_hi + 1u;
+    verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, (u32)nb, last, kin, vin);
+    HIPCHK(hipGetLastError());
+    int bits = 1;
+    while (bits < 32 && (last >> bits)) bits++;
+    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
+    P.order = vin;
+  }
+  const size_t lds = refine_lds_bytes();
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&refine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device)
+  refine_kernel<<<(int)nb, SGTD_REFINE_THREADS, lds, e->stream>>>(P);
+  HIPCHK(hipGetLastError());
+  e->refined = true;
+  return SGTD_OK;
+}
+
+int sgtd_result_refined(sgtd_handle e, int q, double *pose, double *rmse, double *rmse_verify, int32_t *n_pairs, double *moments) {
+  PinScope pin_scope(e && !e->grp ? e : nullptr);
+  if (!e) return SGTD_ERR_INVALID;
+  if (e->grp) return multi::result_refined(e, q, pose, rmse, rmse_verify, n_pairs, moments);
+  if (!e->batch_valid || !e->verified || !e->refined) { e->err = "no refined poses: sgtd_refine_poses comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(view_current(e));
+  const size_t cn = (size_t)e->dc.cand_num, o = (size_t)q * cn;
+  if (pose) CHK(d2h(e, pose, e->r_pose.as<double>() + o * 12, cn * 12 * sizeof(double)));
+  if (rmse) CHK(d2h(e, rmse, e->r_rmse.as<double>() + o, cn * sizeof(double)));
+  if (rmse_verify) CHK(d2h(e, rmse_verify, e->r_rmse_v.as<double>() + o, cn * sizeof(double)));
+  if (n_pairs) CHK(d2h(e, n_pairs, e->r_npairs.as<int>() + o, cn * sizeof(int)));
+  if (moments) CHK(d2h(e, moments, e->r_moments.as<double>() + o * 15, cn * 15 * sizeof(double)));
+  CHK(xfer_sync(e));
+  return SGTD_OK;
+}
+
+int sgtd_result_refined_world_poses(sgtd_handle e, int q, float *world) {
+  if (!e || !world) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  std::vector<double> has((size_t)cn), pose((size_t)cn * 12);
+  std::vector<int32_t> np((size_t)cn);
+  std::vector<int> frames((size_t)cn);
+  int n_cand = 0;
+  CHK(sgtd_result_refined(e, q, pose.data(), nullptr, nullptr, np.data(), nullptr));
+  if (e->grp) {
+    CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
+  } else {
+    CHK(sync_batch(e));
+    n_cand = e->h_n_cand[(size_t)q];
+    std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
+  }
+  for (int k = 0; k < cn; k++) has[(size_t)k] = np[(size_t)k] > 0 ? 1.0 : -1.0;     // (a candidate without a result has no pairs)
+  world_poses_of(e, n_cand, frames.data(), has.data(), pose.data(), world);
   return SGTD_OK;
 }
 

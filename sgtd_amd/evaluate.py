@@ -103,21 +103,30 @@ def frames_near(map_xy, prior_xy, radius):
     return d2 <= float(radius) ** 2
 
 
-def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None, prior=None):
+def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None, prior=None,
+                   refine=0):
     """SearchLoop for a batch of query frames on the device + the node's accounting.
     map_pose4[f] = 4x4 pose of map frame f; query_pose4[q] = ground truth of query q.
     allowed: a frame filter for the batch (STDescManager.set_frame_filter; e.g. frames_near of position priors).
-    prior: (center, radius), a position prior for the batch (STDescManager.set_position_prior; the map poses set)."""
+    prior: (center, radius), a position prior for the batch (STDescManager.set_position_prior; the map poses set).
+    refine: 0 = the node's accounting with SearchLoop's relative pose; N > 0 = STDescManager.refine_poses(N) after the
+    verification, and the localization error is accounted with the refined pose of the candidate SearchLoop chose (the
+    choice itself and the candidate ranks are not touched)."""
     if metrics is None:
         metrics = LoopMetrics(mgr.config_setting_["candidate_num"])
     res = mgr.query_frames(query_xyz, query_label, kp_off, allowed=allowed, prior=prior)
     mgr.verify()
     bc, bf, bs = mgr.search_loop()
+    if refine:
+        mgr.refine_poses(refine)
     for q in range(len(bf)):
         n_c = int(res.n_cand[q])
         if bf[q] > 0:
             score, rot, t = mgr.result_verify(q)
             k = int(bc[q])
+            if refine:
+                r = mgr.result_refined(q)
+                rot, t = r["rot"], r["t"]
             account(metrics, query_pose4[q], map_pose4, int(bf[q]), rot[k], t[k], res.cand_frame[q, :n_c], score[:n_c])
         else:
             account(metrics, query_pose4[q], map_pose4, int(bf[q]), None, None, (), ())

@@ -543,6 +543,47 @@ class STDescManager:
         self._check(self._L.sgtd_result_world_poses(self._h, int(q), _p(w)))
         return w
 
+    def refine_poses(self, iterations=1):
+        """sgtd_refine_poses after verify(): the least-squares refit of every verified candidate's relative pose over all
+        its inlier pairs, on the device; iterations > 1 re-select the inliers under the last pose before each further fit"""
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)):
+            raise TypeError("iterations: an integer")
+        if iterations < 1:
+            raise ValueError("iterations: at least 1")
+        self._check(self._L.sgtd_refine_poses(self._h, int(iterations)))
+
+    def result_refined(self, q):
+        """sgtd_result_refined of query q after refine_poses(): a dict of rot [candidate_num, 3, 3], t [candidate_num, 3],
+        rmse and rmse_verify [candidate_num] (the residual of the final inlier set under the refined pose and under
+        verify()'s), n_pairs [candidate_num] (int32) and moments [candidate_num, 15] (cp, cw, H).  Candidates without a
+        verification result: zeros, NaN, 0 pairs"""
+        q = self._query_index(q)
+        cn = self.config_setting_["candidate_num"]
+        pose = np.zeros((cn, 12), np.float64)
+        rmse = np.zeros(cn, np.float64)
+        rmse_v = np.zeros(cn, np.float64)
+        n_pairs = np.zeros(cn, np.int32)
+        mom = np.zeros((cn, 15), np.float64)
+        self._check(self._L.sgtd_result_refined(self._h, q, _p(pose), _p(rmse), _p(rmse_v), _p(n_pairs), _p(mom)))
+        return {"rot": pose[:, :9].reshape(cn, 3, 3).copy(), "t": pose[:, 9:].copy(), "rmse": rmse, "rmse_verify": rmse_v,
+                "n_pairs": n_pairs, "moments": mom}
+
+    def result_refined_world_poses(self, q):
+        """sgtd_result_refined_world_poses after refine_poses(): result_world_poses with the refined relative poses"""
+        q = self._query_index(q)
+        cn = self.config_setting_["candidate_num"]
+        w = np.zeros((cn, 12), np.float32)
+        self._check(self._L.sgtd_result_refined_world_poses(self._h, q, _p(w)))
+        return w
+
+    @staticmethod
+    def _query_index(q):
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
+            raise TypeError("q: an integer")
+        if q < 0:
+            raise ValueError("q: not negative")
+        return int(q)
+
     def result_inliers(self, q, cand, n_pairs):
         """sucess_match_vec of one candidate as positions into its match_list_"""
         idx = np.zeros(max(int(n_pairs), 1), np.int32)
