@@ -501,11 +501,16 @@ class STDescManager:
                                               _p(out["dis"]), m, C.byref(n)))
         return out
 
-    def candidate_selector(self, stds_vec):
-        """one query frame given as descriptors -> list of STDMatchList"""
+    def query_descs(self, stds_vec):
+        """enqueue one query frame given as descriptors (sgtd_query_descs); results via .results() / .result_pairs() —
+        with set_deferred_lists(True) the lists after finish_lists()"""
         s = stds_vec.soa()
         self._nq = 1
         self._check(self._L.sgtd_query_descs(self._h, C.byref(s), stds_vec.n))
+
+    def candidate_selector(self, stds_vec):
+        """one query frame given as descriptors -> list of STDMatchList"""
+        self.query_descs(stds_vec)
         res = self.results()
         qi, de = self.result_pairs(0, res)
         out = []

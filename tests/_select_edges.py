@@ -71,14 +71,15 @@ class RefTable:
         return self._arr
 
 
-def ref_select(table, qside, qlabel, qframe, rough, candidate_num=CANDIDATE_NUM, max_frame_n=MAX_FRAME_N):
-    """candidate_selector (:318-460) in f64: the 27 voxel_round cells with C truncation, the norm() < 1.5 gate,
-    dis < side.norm() * rough, the unsigned frame test; votes, the top-k rule, the (i, cell, j) list order"""
+def ref_rough(table, qside, qlabel, qframe, rough, thr_scale=1.0):
+    """the match records of candidate_selector's loop (:318-403) in f64, in the reference's (i, cell, j) order: the 27
+    voxel_round cells with C truncation, the norm() < 1.5 gate, dis < side.norm() * rough, the unsigned frame test
+    -> (descriptor, cell, table entry) per record.  thr_scale != 1 is a mutant's (tests/_record_edges.py)"""
     side, frame, buckets = table.arrays()
     rec_q, rec_cell, rec_e = [], [], []
     for i in range(len(qside)):
         s = [float(v) for v in qside[i]]
-        thr = float(norm3(s)) * rough
+        thr = float(norm3(s)) * rough * thr_scale
         code = label_code(qlabel[i])
         cell = 0
         for x in (-1, 0, 1):
@@ -100,7 +101,14 @@ def ref_select(table, qside, qlabel, qframe, rough, candidate_num=CANDIDATE_NUM,
                     rec_q += [i] * len(hit)
                     rec_cell += [c] * len(hit)
                     rec_e += hit.tolist()
-    rec_q, rec_cell, rec_e = np.array(rec_q, np.int32), np.array(rec_cell, np.int32), np.array(rec_e, np.int64)
+    return np.array(rec_q, np.int32), np.array(rec_cell, np.int32), np.array(rec_e, np.int64)
+
+
+def ref_select(table, qside, qlabel, qframe, rough, candidate_num=CANDIDATE_NUM, max_frame_n=MAX_FRAME_N):
+    """candidate_selector (:318-460) in f64: the records of ref_rough; votes, the top-k rule, the (i, cell, j) list
+    order"""
+    frame = table.arrays()[1]
+    rec_q, rec_cell, rec_e = ref_rough(table, qside, qlabel, qframe, rough)
     rec_f = frame[rec_e] if len(rec_e) else np.zeros(0, np.uint32)
     votes = np.bincount(rec_f[rec_f < max_frame_n].astype(np.int64), minlength=max_frame_n).astype(np.float64)
     work = votes.copy()
