@@ -6,6 +6,10 @@
 //   localize <map_dir | map.cache> <query_dir | query.cache> [batch=256] [icp_threshold=0.4] [prior_radius] [--refine N]
 //   --refine N (anywhere on the line): sgtd_refine_poses(h, N) after the verification — the relative pose of SearchLoop's
 //   choice refitted over all its inlier pairs — and a second set of error lines for the refined poses (off by default)
+//   --overlap RADIUS [--min-overlap X] (anywhere on the line): the map's keypoints are stored on the handle
+//   (sgtd_set_frame_keypoints), sgtd_overlap(h, RADIUS) runs after the verification and the detection is
+//   sgtd_search_loop_overlap's — the best-scored candidate among those whose keypoint overlap reaches X (default 0.4) —
+//   in place of sgtd_search_loop's; one more line counts what the gate accepted, rejected and moved (off by default)
 //   prior_radius: restrict every query to the map frames within that many metres (x, y) of its ground-truth position
 //   (sgtd_set_frame_poses + sgtd_set_position_prior), as a localizer with odometry would, and report how many map
 //   frames a query was allowed on average (the LOCALIZE_PER_FRAME calls below run without it)
@@ -131,8 +135,26 @@ int main(int argc, char **argv) {
       argc -= 2;
       break;
     }
+  double overlap_radius = -1.0, min_overlap = 0.4;           // --overlap RADIUS, --min-overlap X, taken out likewise
+  bool min_overlap_given = false;
+  for (int i = 1; i < argc;) {
+    const bool ov = !std::strcmp(argv[i], "--overlap"), mo = !std::strcmp(argv[i], "--min-overlap");
+    if (!ov && !mo) { i++; continue; }
+    char *end = nullptr;
+    const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : -1.0;
+    if (i + 1 >= argc || end == argv[i + 1] || *end || !(v >= 0.0) || std::isinf(v)) {
+      std::fprintf(stderr, "%s needs a number >= 0\n", argv[i]);
+      return 2;
+    }
+    if (ov) overlap_radius = v; else { min_overlap = v; min_overlap_given = true; }
+    for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+    argc -= 2;
+  }
+  const bool use_overlap = overlap_radius >= 0.0;
+  if (min_overlap_given && !use_overlap) { std::fprintf(stderr, "--min-overlap comes with --overlap RADIUS\n"); return 2; }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold] [prior_radius] [--refine N]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold] [prior_radius] [--refine N] "
+                         "[--overlap RADIUS [--min-overlap X]]\n", argv[0]);
     return 2;
   }
   // SearchLoop hands back ~130 MB of std::pair<STDesc, STDesc> per frame (the reference's own result
@@ -173,6 +195,15 @@ int main(int argc, char **argv) {
     for (int i = 0; i < map.n; i++) ids[i] = (uint32_t)i;
     OK(sgtd_set_frame_poses(h, ids.data(), map.poses, map.n));
   }
+  if (use_overlap) {                                         // the map's keypoints, under the ids the frames were added with
+    std::vector<uint32_t> ids(map.n);
+    for (int i = 0; i < map.n; i++) ids[i] = (uint32_t)i;
+    OK(sgtd_set_frame_keypoints(h, ids.data(), map.off, map.xyz, map.label, map.n));
+  }
+  long ov_accepted = 0, ov_rejected = 0, ov_moved = 0;       // --overlap: the gated choice against sgtd_search_loop's
+  double ov_sum = 0;
+  std::vector<int32_t> plain_cand(batch), plain_frame(batch);
+  std::vector<double> best_overlap(batch);
   long allowed_sum = 0;                                      // (query, map frame) pairs the priors allowed
   std::vector<double> prior_c, prior_r;
   auto t2 = std::chrono::steady_clock::now();
@@ -212,6 +243,16 @@ int main(int argc, char **argv) {
     OK(sgtd_verify(h));
     OK(sgtd_search_loop(h, icp_threshold, best_cand.data(), best_frame.data(), best_score.data()));
     OK(sgtd_result_candidates(h, n_cand.data(), cand_frame.data(), nullptr, nullptr));
+    if (use_overlap) {
+      plain_cand = best_cand; plain_frame = best_frame;
+      OK(sgtd_overlap(h, overlap_radius, 0, nullptr, nullptr, nullptr));
+      OK(sgtd_search_loop_overlap(h, icp_threshold, min_overlap, best_cand.data(), best_frame.data(), best_score.data(), best_overlap.data()));
+      for (int i = 0; i < nb; i++) {
+        if (best_frame[i] > 0) { ov_accepted++; ov_sum += best_overlap[i]; }
+        if (plain_frame[i] > 0 && !(best_frame[i] > 0)) ov_rejected++;
+        if (plain_frame[i] > 0 && best_frame[i] > 0 && plain_cand[i] != best_cand[i]) ov_moved++;
+      }
+    }
     if (refine) OK(sgtd_refine_poses(h, refine));
     auto tb2 = std::chrono::steady_clock::now();
     if (std::getenv("LOCALIZE_VERBOSE"))
@@ -271,6 +312,9 @@ int main(int argc, char **argv) {
     std::printf("mean inlier rmse of the chosen candidates: %.4f m refined, %.4f m under the verification's pose\n",
                 detected ? ref_rmse / detected : 0.0, detected ? ver_rmse / detected : 0.0);
   }
+  if (use_overlap)
+    std::printf("keypoint overlap (radius %.2f m, min %.2f): accepted %ld, rejected %ld, moved to another candidate %ld, mean overlap of the accepted %.4f\n",
+                overlap_radius, min_overlap, ov_accepted, ov_rejected, ov_moved, ov_accepted ? ov_sum / ov_accepted : 0.0);
   std::printf("time: load %.1f ms, map build %.1f ms, queries %.1f ms (%.3f ms per query incl. verification), %d device(s)\n", ms(t0, t1), ms(t1, t2),
               ms(t2, t3), total_num ? ms(t2, t3) / total_num : 0.0, sgtd_device_count(h));
   if (const char *pf = std::getenv("LOCALIZE_PER_FRAME")) {

@@ -451,6 +451,79 @@ int sgtd_result_refined(sgtd_handle h, int q,
  * library's host code (a multi-device handle gives the single-device values bit for bit); 12 NaNs where the candidate
  * has no result or its frame has no pose.  world == NULL: SGTD_ERR_INVALID; otherwise as sgtd_result_refined. */
 int sgtd_result_refined_world_poses(sgtd_handle h, int q, float *world);
+
+/* Keypoints of map frames, keyed by global frame id: frame frame_ids[i] gets the keypoints kp_off[i] .. kp_off[i+1] of
+ * xyz (3 floats each) / label — host arrays, the data sgtd_add_frames takes for that frame.  They feed sgtd_overlap.
+ * The call behaves like sgtd_set_frame_poses: the keypoints are copied at the call and are settings of the handle;
+ * later calls overwrite; xyz == NULL with n > 0 forgets the keypoints of those ids; frame_ids == NULL with n == 0 forgets
+ * all; ids may name frames not (yet) added; sgtd_add*, sgtd_remove_frames and sgtd_load_table leave them alone, the table
+ * file does not hold them, a view (sgtd_attach_table) has keypoints of its own, and a multi-device handle hands each
+ * frame to the shard that owns it.  A frame stored with zero keypoints "has keypoints" (count 0).
+ * Memory: a host copy, and a device copy built before the next sgtd_overlap and rebuilt only after the store changed:
+ * 16 B a keypoint plus an 8-byte offset word per frame id up to the largest id stored.
+ * h == NULL, n < 0, frame_ids == NULL with n > 0, kp_off == NULL or label == NULL with xyz != NULL and n > 0, a frame with
+ * a negative count or more than 65535 keypoints: SGTD_ERR_INVALID; an id >= max_frame_n: SGTD_ERR_FRAME_LIMIT (nothing
+ * is stored).  All before the device is touched. */
+int sgtd_set_frame_keypoints(sgtd_handle h, const uint32_t *frame_ids, const int64_t *kp_off,
+                             const float *xyz, const uint32_t *label, int64_t n);
+
+/* Keypoint overlap of every verified candidate, on the device, after sgtd_verify (or sgtd_verify_masked, or
+ * sgtd_search_frame with flags 0): under the candidate's relative pose, how many of the query's keypoints land within
+ * `radius` of a keypoint of the same label of the candidate's frame (sgtd_set_frame_keypoints) — a scale-free quantity
+ * to accept or reject a loop on, where verify_score is a count.
+ * Pose: sgtd_result_verify's; with SGTD_OVERLAP_REFINED sgtd_result_refined's (SGTD_ERR_STATE when sgtd_refine_poses has
+ * not run on this batch).
+ * Query keypoints: q_xyz == NULL takes the batch's own, as given to sgtd_query_frames / sgtd_loop_frames — if those were
+ * passed with device_ptrs != 0 the caller's arrays must still be valid; a batch of sgtd_query_descs or sgtd_search_frame
+ * has none (SGTD_ERR_STATE).  Otherwise q_xyz, q_label and q_kp_off (n_queries + 1 offsets) are host arrays for every
+ * query of the batch, used in place of the batch's own (copied before the call returns). */
+/* The rule, for candidate k of query q that has a verification result and whose frame has stored keypoints.  All
+ * arithmetic is f64, every operation rounded once (no contraction); f32 inputs are widened exactly.  (R, t) = the pose.
+ * For query keypoint i = 0 .. n_query_kp-1 with position p and label l:
+ *   x[c] = ((R[c][0]*p[0] + R[c][1]*p[1]) + R[c][2]*p[2]) + t[c];
+ *   for every keypoint j of the frame whose label equals l (as u32), with position w:
+ *     e = x - w, r2(i, j) = (e[0]*e[0] + e[1]*e[1]) + e[2]*e[2];
+ *   m_i = the minimum of r2(i, j) over those j, +inf when no j has the label (a NaN r2 never is the minimum).
+ * With rr = radius * radius: query keypoint i is a hit iff m_i <= rr; frame keypoint j is a hit iff some query keypoint
+ * i of its label has r2(i, j) <= rr.  Any NaN makes a comparison false.
+ *   n_hit_query, n_hit_frame = the hits; n_query_kp, n_frame_kp = the set sizes;
+ *   overlap = (double)n_hit_query / (double)n_query_kp, NaN when n_query_kp == 0;
+ *   rms = sqrt(SUM(m_i over the hits i) / (double)n_hit_query), NaN without hits.
+ * SUM has the fixed order of sgtd_refine_poses: 256 accumulators acc[0..255] starting at +0.0; acc[l] takes the query
+ * keypoints i == l (mod 256) in ascending i, one addition each; a keypoint that is no hit is skipped, not added as zero;
+ * then acc[l] = acc[l] + acc[l + s] for all l < s, for s = 128, 64, 32, 16, 8, 4, 2, 1 in turn; SUM = acc[0].
+ * A candidate without a verification result (past n_cand, score -1, masked out by sgtd_verify_masked): all four counts
+ * -1, overlap and rms NaN.  A verified candidate whose frame has no stored keypoints: n_frame_kp = -1, both hit counts
+ * 0, overlap and rms NaN; n_query_kp is still reported.
+ * The call adds results and changes none: sgtd_result_verify, sgtd_result_inlier*, sgtd_result_refined*,
+ * sgtd_result_world_poses and sgtd_search_loop return what they returned before.  A new batch or a new sgtd_verify* drops
+ * the overlap results; a later sgtd_overlap replaces them (another radius, another pose).  A view has results of its
+ * own; a multi-device handle forwards the call to every shard and fetches each candidate's result from its owner (the
+ * single handle's values bit for bit).
+ * h == NULL, radius NaN, negative or infinite, unknown flag bits, q_xyz set while q_label or q_kp_off is NULL, a query
+ * with a negative count or more than 65535 keypoints: SGTD_ERR_INVALID, before the device is touched; no verification of
+ * the pending batch yet: SGTD_ERR_STATE; a view whose owner's table changed: SGTD_ERR_STATE, as for sgtd_verify. */
+#define SGTD_OVERLAP_REFINED 1   /* use sgtd_refine_poses' pose instead of sgtd_verify's */
+int sgtd_overlap(sgtd_handle h, double radius, int flags,
+                 const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off);
+/* Overlap results of every candidate of query q; cn = candidate_num; any pointer may be NULL.  h == NULL:
+ * SGTD_ERR_INVALID; before sgtd_overlap on this batch: SGTD_ERR_STATE; q outside the batch: SGTD_ERR_INVALID. */
+int sgtd_result_overlap(sgtd_handle h, int q,
+                        int32_t *n_query_kp,  /* [cn] */
+                        int32_t *n_frame_kp,  /* [cn] */
+                        int32_t *n_hit_query, /* [cn] */
+                        int32_t *n_hit_frame, /* [cn] */
+                        double *overlap,      /* [cn] n_hit_query / n_query_kp */
+                        double *rms);         /* [cn] */
+/* sgtd_search_loop's rule over the candidates with overlap >= min_overlap (a NaN overlap leaves a candidate out): among
+ * them the first candidate with the strictly largest verify_score, accepted if it exceeds icp_threshold.
+ * min_overlap <= 0 disables the gate: the choice equals sgtd_search_loop's and the call needs no overlap results.  With
+ * min_overlap > 0 it requires sgtd_overlap on the batch (SGTD_ERR_STATE otherwise).  Arrays of n_queries; any may be
+ * NULL.  best_overlap: the chosen candidate's overlap; NaN where nothing was accepted or no overlap results exist.
+ * h == NULL or no verification yet: SGTD_ERR_INVALID. */
+int sgtd_search_loop_overlap(sgtd_handle h, double icp_threshold, double min_overlap,
+                             int32_t *best_cand, int32_t *best_frame,
+                             double *best_score, double *best_overlap);
 /* asynchronous device-to-device export of the verification results of the whole batch into
  * caller device buffers (score f64 [n_queries*candidate_num], pose f64 [n_queries*candidate_num*12]),
  * enqueued on the handle's stream without synchronising: the table-sharded multi-GPU path

@@ -32,6 +32,7 @@ SYMBOLS = [
     "sgtd_loop_frames", "sgtd_remove_frames", "sgtd_set_frame_filter",
     "sgtd_set_frame_poses", "sgtd_set_position_prior", "sgtd_result_world_poses",
     "sgtd_refine_poses", "sgtd_result_refined", "sgtd_result_refined_world_poses",
+    "sgtd_set_frame_keypoints", "sgtd_overlap", "sgtd_result_overlap", "sgtd_search_loop_overlap",
 ]
 
 
@@ -153,6 +154,10 @@ def lib():
     L.sgtd_refine_poses.argtypes = [vp, C.c_int]
     L.sgtd_result_refined.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.sgtd_result_refined_world_poses.argtypes = [vp, C.c_int, vp]
+    L.sgtd_set_frame_keypoints.argtypes = [vp, vp, vp, vp, vp, i64]
+    L.sgtd_overlap.argtypes = [vp, C.c_double, C.c_int, vp, vp, vp]
+    L.sgtd_result_overlap.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.sgtd_search_loop_overlap.argtypes = [vp, C.c_double, C.c_double, vp, vp, vp, vp]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

@@ -23,7 +23,7 @@ struct Group {
   int n = 0;
   u32 current_frame_id = 0;              // global
   int nq = 0;
-  bool batch_valid = false, merged = false, verified = false, refined = false;
+  bool batch_valid = false, merged = false, verified = false, refined = false, overlapped = false;
   // merged candidate tables of the last batch
   std::vector<int> n_cand, cand_frame, cand_votes, owner, owner_slot;
   std::vector<long long> pair_off;       // [nq * (cn + 1)] offsets into the query's concatenated lists
@@ -45,6 +45,7 @@ int finalize(sgtd_engine *e);
 int remove_frames(sgtd_engine *e, const uint32_t *frame_ids, int64_t n, int64_t *n_removed);
 int set_frame_filter(sgtd_engine *e, uint32_t frame_lo, uint32_t n_frames, const uint64_t *rows, int n_rows);
 int set_frame_poses(sgtd_engine *e, const uint32_t *frame_ids, const float *pose12, int64_t n);
+int set_frame_keypoints(sgtd_engine *e, const uint32_t *frame_ids, const int64_t *kp_off, const float *xyz, const uint32_t *label, int64_t n);
 int set_position_prior(sgtd_engine *e, const double *center, const double *radius, int n_rows, int dims);
 int candidates_of(sgtd_engine *e, int q, int *n_cand, int *cand_frame);
 int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const int64_t *kp_off, int n_queries, int device_ptrs);
@@ -59,6 +60,10 @@ int verify(sgtd_engine *e);
 int result_verify(sgtd_engine *e, int q, double *score, double *pose);
 int refine_poses(sgtd_engine *e, int iterations);
 int result_refined(sgtd_engine *e, int q, double *pose, double *rmse, double *rmse_verify, int32_t *n_pairs, double *moments);
+int nq_of(sgtd_engine *e, int *nq);
+int overlap(sgtd_engine *e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off);
+int result_overlap(sgtd_engine *e, int q, int32_t *n_query_kp, int32_t *n_frame_kp, int32_t *n_hit_query, int32_t *n_hit_frame, double *overlap, double *rms);
+int has_overlap(sgtd_engine *e);
 int result_inliers(sgtd_engine *e, int q, int cand, int32_t *idx, int64_t capacity, int64_t *n);
 int result_inlier_pairs(sgtd_engine *e, int q, int64_t *cand_off, int32_t *q_idx, int64_t *db_entry, int64_t capacity, int64_t *n_pairs);
 int search_loop(sgtd_engine *e, double icp_threshold, int32_t *best_cand, int32_t *best_frame, double *best_score);

@@ -198,6 +198,38 @@ int set_frame_poses(sgtd_engine *e, const uint32_t *frame_ids, const float *pose
   return SGTD_OK;
 }
 
+// every shard keeps the keypoints of its own frames under their local ids (the group keeps them under the global ids,
+// as it keeps the poses); the checks ran in sgtd_set_frame_keypoints
+int set_frame_keypoints(sgtd_engine *e, const uint32_t *frame_ids, const int64_t *kp_off, const float *xyz, const uint32_t *label, int64_t n) {
+  Group *g = G(e);
+  if (n == 0) {
+    for (sgtd_engine *c : g->dev) MCHK(sgtd_set_frame_keypoints(c, frame_ids, kp_off, xyz, label, 0));
+    return SGTD_OK;
+  }
+  std::vector<std::vector<uint32_t>> loc(g->n), lab(g->n);
+  std::vector<std::vector<int64_t>> off(g->n);
+  std::vector<std::vector<float>> pts(g->n);
+  for (int s = 0; s < g->n; s++) off[s].push_back(0);
+  for (int64_t i = 0; i < n; i++) {
+    const int s = shard_of(frame_ids[i], g->n);
+    loc[s].push_back(local_of(frame_ids[i], g->n));
+    if (xyz) {
+      pts[s].insert(pts[s].end(), xyz + (size_t)kp_off[i] * 3, xyz + (size_t)kp_off[i + 1] * 3);
+      lab[s].insert(lab[s].end(), label + (size_t)kp_off[i], label + (size_t)kp_off[i + 1]);
+      off[s].push_back((int64_t)lab[s].size());
+    }
+  }
+  static const float no_xyz[3] = {0.f, 0.f, 0.f};      // (a shard whose frames are all empty still stores them: not NULL)
+  static const uint32_t no_label[1] = {0u};
+  for (int s = 0; s < g->n; s++) {
+    if (loc[s].empty()) continue;
+    sgtd_engine *c = g->dev[s];
+    MCHK(sgtd_set_frame_keypoints(c, loc[s].data(), off[s].data(), xyz ? (pts[s].empty() ? no_xyz : pts[s].data()) : nullptr,
+                                  lab[s].empty() ? no_label : lab[s].data(), (int64_t)loc[s].size()));
+  }
+  return SGTD_OK;
+}
+
 // the prior goes to every shard as it is (it tests each shard's own positions); the group keeps it for prior_fits
 int set_position_prior(sgtd_engine *e, const double *center, const double *radius, int n_rows, int dims) {
   for (sgtd_engine *c : G(e)->dev) MCHK(sgtd_set_position_prior(c, center, radius, n_rows, dims));
@@ -213,7 +245,7 @@ int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const 
   // every device builds the query descriptors itself and sweeps its shard; the calls only
   // enqueue, so the devices run concurrently
   for (sgtd_engine *c : g->dev) MCHK(sgtd_query_frames(c, xyz, label, kp_off, n_queries, 0));
-  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false;
+  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false;
   return SGTD_OK;
 }
 
@@ -235,7 +267,7 @@ int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq) {
     t.frame = lf.data();
     MCHK(sgtd_query_descs(c, &t, nq));
   }
-  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false;
+  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false;
   return SGTD_OK;
 }
 
@@ -409,7 +441,7 @@ int result_votes(sgtd_engine *e, int q, uint32_t *votes, int64_t capacity, uint3
 int verify(sgtd_engine *e) {
   Group *g = G(e);
   CHK(merge(e));
-  g->refined = false;
+  g->refined = false; g->overlapped = false;
   for (sgtd_engine *c : g->dev) MCHK(sgtd_verify(c));   // every owner verifies its local candidates
   g->verified = true;
   return SGTD_OK;
@@ -478,6 +510,61 @@ int result_refined(sgtd_engine *e, int q, double *pose, double *rmse, double *rm
     if (rmse_verify) rmse_verify[k] = o.rmse_v[ks];
     if (n_pairs) n_pairs[k] = o.np[ks];
     if (moments) std::copy(o.mom.begin() + (size_t)ks * 15, o.mom.begin() + (size_t)ks * 15 + 15, moments + (size_t)k * 15);
+  }
+  return SGTD_OK;
+}
+
+int nq_of(sgtd_engine *e, int *nq) {
+  Group *g = G(e);
+  if (!g->batch_valid) return SGTD_ERR_STATE;
+  *nq = g->nq;
+  return SGTD_OK;
+}
+
+int has_overlap(sgtd_engine *e) {
+  Group *g = G(e);
+  return g->batch_valid && g->verified && g->overlapped;
+}
+
+// every owner computes the overlap of its local candidates (the checks ran in sgtd_overlap)
+int overlap(sgtd_engine *e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
+  Group *g = G(e);
+  if (!g->batch_valid || !g->verified) { e->err = "sgtd_overlap needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if ((flags & SGTD_OVERLAP_REFINED) && !g->refined) { e->err = "SGTD_OVERLAP_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
+  g->overlapped = false;
+  for (sgtd_engine *c : g->dev) MCHK(sgtd_overlap(c, radius, flags, q_xyz, q_label, q_kp_off));
+  g->overlapped = true;
+  return SGTD_OK;
+}
+
+// the overlap results of query q's merged candidates, each from its owner (result_refined's pattern)
+int result_overlap(sgtd_engine *e, int q, int32_t *n_query_kp, int32_t *n_frame_kp, int32_t *n_hit_query, int32_t *n_hit_frame, double *overlap, double *rms) {
+  Group *g = G(e);
+  if (!has_overlap(e)) { e->err = "no overlap results: sgtd_overlap comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  struct Owned { std::vector<int32_t> c[4]; std::vector<double> ov, rms; };
+  std::vector<Owned> own(g->n);
+  int32_t *out[4] = {n_query_kp, n_frame_kp, n_hit_query, n_hit_frame};
+  for (int k = 0; k < cn; k++) {
+    for (int a = 0; a < 4; a++) if (out[a]) out[a][k] = -1;
+    if (overlap) overlap[k] = nan;
+    if (rms) rms[k] = nan;
+  }
+  for (int k = 0; k < g->n_cand[q]; k++) {
+    const size_t i = (size_t)q * cn + k;
+    const int s = g->owner[i], ks = g->owner_slot[i];
+    Owned &o = own[s];
+    if (o.ov.empty()) {
+      sgtd_engine *c = g->dev[s];
+      for (int a = 0; a < 4; a++) o.c[a].resize(cn);
+      o.ov.resize(cn); o.rms.resize(cn);
+      MCHK(sgtd_result_overlap(c, q, o.c[0].data(), o.c[1].data(), o.c[2].data(), o.c[3].data(), o.ov.data(), o.rms.data()));
+    }
+    for (int a = 0; a < 4; a++) if (out[a]) out[a][k] = o.c[a][ks];
+    if (overlap) overlap[k] = o.ov[ks];
+    if (rms) rms[k] = o.rms[ks];
   }
   return SGTD_OK;
 }

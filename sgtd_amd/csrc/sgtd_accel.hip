@@ -28,6 +28,7 @@
 #include "filter_kernels.hip.h"
 #include "prior_kernels.hip.h"
 #include "refine_kernels.hip.h"
+#include "overlap_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -257,6 +258,18 @@ struct sgtd_engine {
   // flags of the re-selected sets (two halves; sgtd_verify's v_inlier is only read)
   DevBuf r_pose, r_rmse, r_rmse_v, r_npairs, r_moments, r_flag;
   bool refined = false;
+  // sgtd_set_frame_keypoints / sgtd_overlap (overlap_kernels.hip.h): the keypoints by global frame id (x, y, z bits and
+  // the label, 16 B each; has_kps[id] != 0 where set, a frame of zero keypoints included).  kp_dev / kp_word: the device
+  // copy (all stored keypoints back to back; per frame id first << 16 | count, or all ones), made for kp_dev_serial.
+  // o_*: the overlap results of the batch and the caller's query keypoints when they were given to sgtd_overlap.
+  std::vector<std::vector<uint4>> kps;
+  std::vector<unsigned char> has_kps;
+  u64 kps_serial = 0, kp_dev_serial = 0;
+  DevBuf kp_dev, kp_word, o_cnt, o_val, o_qxyz, o_qlabel, o_qoff;
+  std::vector<uint4> kp_host;        // (the sources of their upload)
+  std::vector<u64> kp_word_host;
+  int kp_dev_max = 0;                // keypoints of the longest frame of the device copy
+  bool overlapped = false;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -1107,7 +1120,7 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
     HIPCHK(hipGetLastError());
   }
   e->lists_pending = false;
-  e->verified = false; e->refined = false;
+  e->verified = false; e->refined = false; e->overlapped = false;
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -1517,7 +1530,7 @@ int launch_select(sgtd_engine *e) {
       batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
       HIPCHK(hipGetLastError());
       e->lists_pending = true;
-      e->verified = false; e->refined = false;
+      e->verified = false; e->refined = false; e->overlapped = false;
       e->batch_synced = false;
       return SGTD_OK;
     }
@@ -1574,7 +1587,7 @@ int launch_select(sgtd_engine *e) {
     HIPCHK(hipGetLastError());
   }
   e->batch_valid = true;
-  e->verified = false; e->refined = false;
+  e->verified = false; e->refined = false; e->overlapped = false;
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -2057,7 +2070,7 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->seg[1].hot, &e->seg[1].perm, &e->seg[1].hash, &e->seg[1].bucket_start, &e->seg[1].bucket_key, &e->seg[1].dir, &e->slice_of, &e->sq_sum,
                     &e->keyA, &e->keyB, &e->valA, &e->valB, &e->hist, &e->digit_tot, &e->flags, &e->bad_flag,
                     &e->kp_off_dev, &e->xyz_dev, &e->label_dev, &e->b_kp_off_dev, &e->b_xyz_dev, &e->b_label_dev, &e->ws_keys, &e->ws_slots, &e->cnt_scan,
-                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
+                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->kp_dev, &e->kp_word, &e->o_cnt, &e->o_val, &e->o_qxyz, &e->o_qlabel, &e->o_qoff, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
                     &e->votes, &e->slot_of, &e->q_M, &e->q_P, &e->q_pairs, &e->q_pair_base,
                     &e->blk_count, &e->c_pair, &e->c_blk, &e->amb_queue, &e->rec, &e->rec_cell, &e->rec_dis, &e->rough_qi,
                     &e->rough_entry, &e->rough_frame, &e->rough_cell, &e->rough_dis, &e->n_cand, &e->cand_frame,
@@ -2816,7 +2829,7 @@ int sgtd_verify(sgtd_handle e) {
   CHK(sync_batch(e));
   if (!e->batch_valid) return SGTD_ERR_INVALID;
   const int cn = e->dc.cand_num, nq = e->nq;
-  e->refined = false;
+  e->refined = false; e->overlapped = false;
   if (nq == 0) { e->verified = true; return SGTD_OK; }
   int64_t total = 0;
   for (int q = 0; q < nq; q++) total = std::max<int64_t>(total, (int64_t)e->h_pair_base[q] + e->h_pair_off[(size_t)q * (cn + 1) + cn]);
@@ -3176,7 +3189,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   }
   stage_times(e);
   e->batch_synced = true;
-  e->verified = !lists_only; e->refined = false;
+  e->verified = !lists_only; e->refined = false; e->overlapped = false;
   io->n_cand = (int32_t)w[12];
   if (io->cand_frame) std::memcpy(io->cand_frame, cf, (size_t)cn * 4);
   if (io->cand_votes) std::memcpy(io->cand_votes, cv, (size_t)cn * 4);
@@ -3505,6 +3518,222 @@ int sgtd_result_refined_world_poses(sgtd_handle e, int q, float *world) {
   }
   for (int k = 0; k < cn; k++) has[(size_t)k] = np[(size_t)k] > 0 ? 1.0 : -1.0;     // (a candidate without a result has no pairs)
   world_poses_of(e, n_cand, frames.data(), has.data(), pose.data(), world);
+  return SGTD_OK;
+}
+
+// ---- sgtd_set_frame_keypoints / sgtd_overlap: the keypoint overlap of the verified candidates (overlap_kernels.hip.h) ----
+int sgtd_set_frame_keypoints(sgtd_handle e, const uint32_t *frame_ids, const int64_t *kp_off, const float *xyz, const uint32_t *label, int64_t n) {
+  if (!e || n < 0 || (n > 0 && !frame_ids)) return SGTD_ERR_INVALID;
+  if (n > 0 && xyz && (!kp_off || !label)) return SGTD_ERR_INVALID;
+  if (n > 0 && xyz)
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t cnt = kp_off[i + 1] - kp_off[i];
+      if (cnt < 0 || cnt > 65535) return SGTD_ERR_INVALID;
+    }
+  for (int64_t i = 0; i < n; i++)
+    if (frame_ids[i] >= (uint32_t)e->cfg.max_frame_n) return SGTD_ERR_FRAME_LIMIT;
+  if (e->grp) CHK(multi::set_frame_keypoints(e, frame_ids, kp_off, xyz, label, n));
+  if (n == 0) {
+    if (frame_ids) return SGTD_OK;
+    e->kps.clear(); e->has_kps.clear();
+  } else {
+    for (int64_t i = 0; i < n; i++) {
+      const size_t id = frame_ids[i];
+      if (id >= e->has_kps.size()) {
+        if (!xyz) continue;
+        e->has_kps.resize(id + 1, 0);
+        e->kps.resize(id + 1);
+      }
+      e->has_kps[id] = xyz ? 1 : 0;
+      std::vector<uint4> &v = e->kps[id];
+      v.clear();
+      if (!xyz) { v.shrink_to_fit(); continue; }
+      v.resize((size_t)(kp_off[i + 1] - kp_off[i]));
+      for (size_t j = 0; j < v.size(); j++) {
+        const size_t k = (size_t)kp_off[i] + j;
+        u32 b[3];
+        std::memcpy(b, xyz + k * 3, sizeof(b));
+        v[j] = make_uint4(b[0], b[1], b[2], label[k]);
+      }
+    }
+  }
+  static std::atomic<u64> serial{0};
+  e->kps_serial = ++serial;
+  return SGTD_OK;
+}
+
+// the keypoint store's device copy, made again only when the store changed
+static int prepare_keypoints(sgtd_engine *e) {
+  if (e->kp_word.p && e->kp_dev_serial == e->kps_serial) return SGTD_OK;
+  const size_t n_ids = e->has_kps.size();
+  e->kp_word_host.assign(std::max<size_t>(n_ids, 1), SGTD_OVERLAP_NONE);
+  e->kp_host.clear();
+  int mx = 0;
+  for (size_t id = 0; id < n_ids; id++) {
+    if (!e->has_kps[id]) continue;
+    const std::vector<uint4> &v = e->kps[id];
+    e->kp_word_host[id] = ((u64)e->kp_host.size() << 16) | (u64)v.size();
+    e->kp_host.insert(e->kp_host.end(), v.begin(), v.end());
+    mx = std::max(mx, (int)v.size());
+  }
+  CHK(ensure(e, e->kp_word, e->kp_word_host.size() * sizeof(u64)));
+  CHK(ensure(e, e->kp_dev, std::max<size_t>(e->kp_host.size(), 1) * sizeof(uint4)));
+  CHK(h2d(e, e->kp_word.p, e->kp_word_host.data(), e->kp_word_host.size() * sizeof(u64)));
+  CHK(h2d(e, e->kp_dev.p, e->kp_host.data(), e->kp_host.size() * sizeof(uint4)));
+  e->kp_dev_max = mx;
+  e->kp_dev_serial = e->kps_serial;
+  return SGTD_OK;
+}
+
+int sgtd_overlap(sgtd_handle e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
+  if (!e || !(radius >= 0.0) || std::isinf(radius) || (flags & ~SGTD_OVERLAP_REFINED)) return SGTD_ERR_INVALID;
+  if (q_xyz && (!q_label || !q_kp_off)) return SGTD_ERR_INVALID;
+  int nq = 0;
+  if (e->grp) {
+    if (multi::nq_of(e, &nq) != SGTD_OK) { e->err = "sgtd_overlap needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  } else {
+    if (!e->batch_valid || !e->verified) { e->err = "sgtd_overlap needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+    nq = e->nq;
+  }
+  if (q_xyz)
+    for (int q = 0; q < nq; q++) {
+      const int64_t cnt = q_kp_off[q + 1] - q_kp_off[q];
+      if (cnt < 0 || cnt > 65535) return SGTD_ERR_INVALID;
+    }
+  if (e->grp) return multi::overlap(e, radius, flags, q_xyz, q_label, q_kp_off);
+  if ((flags & SGTD_OVERLAP_REFINED) && !e->refined) { e->err = "SGTD_OVERLAP_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
+  if (!q_xyz && e->last_kind != 1) { e->err = "the batch has no keypoints of its own (sgtd_query_descs, sgtd_search_frame): pass them to sgtd_overlap"; return SGTD_ERR_STATE; }
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(sync_batch(e));
+  e->overlapped = false;
+  const int cn = e->dc.cand_num;
+  if (nq == 0) { e->overlapped = true; return SGTD_OK; }
+  CHK(prepare_keypoints(e));
+  const size_t nb = (size_t)nq * cn;
+  CHK(ensure(e, e->o_cnt, nb * sizeof(int4)));
+  CHK(ensure(e, e->o_val, nb * sizeof(double2)));
+  OverlapParams P;
+  P.n_cand = e->n_cand.as<int>(); P.cand_frame = e->cand_frame.as<int>(); P.cand_num = cn;
+  P.score = e->v_score.as<double>();
+  P.pose = (flags & SGTD_OVERLAP_REFINED) ? e->r_pose.as<double>() : e->v_pose.as<double>();
+  if (q_xyz) {
+    std::vector<long long> off((size_t)nq + 1);
+    for (int q = 0; q <= nq; q++) off[(size_t)q] = q_kp_off[q] - q_kp_off[0];
+    const size_t total = (size_t)off[(size_t)nq];
+    CHK(ensure(e, e->o_qoff, off.size() * sizeof(long long)));
+    CHK(ensure(e, e->o_qxyz, std::max<size_t>(total, 1) * 3 * sizeof(float)));
+    CHK(ensure(e, e->o_qlabel, std::max<size_t>(total, 1) * sizeof(u32)));
+    CHK(h2d(e, e->o_qoff.p, off.data(), off.size() * sizeof(long long)));
+    CHK(h2d(e, e->o_qxyz.p, q_xyz + (size_t)q_kp_off[0] * 3, total * 3 * sizeof(float)));
+    CHK(h2d(e, e->o_qlabel.p, q_label + (size_t)q_kp_off[0], total * sizeof(u32)));
+    CHK(xfer_sync(e));          // (the offsets' staging vector and the caller's arrays are free at return)
+    P.q_xyz = e->o_qxyz.as<float>(); P.q_label = e->o_qlabel.as<u32>(); P.q_off = e->o_qoff.as<long long>();
+  } else {
+    P.q_xyz = e->last_xyz; P.q_label = e->last_label; P.q_off = e->kp_off_dev.as<long long>();
+  }
+  P.kp = e->kp_dev.as<uint4>(); P.f_word = e->kp_word.as<u64>(); P.n_ids = (u32)e->has_kps.size();
+  P.hit_off = (u32)overlap_hit_off(e->kp_dev_max);
+  P.rr = radius * radius;
+  P.order = nullptr; P.n_blocks = (u32)nb;
+  P.cnt = e->o_cnt.as<int4>(); P.val = e->o_val.as<double2>();
+  // a batch of many candidates in the order of the candidates' frames, as sgtd_refine_poses: a frame's keypoints stay in cache
+  if (nb >= 4096 && e->have_frames) {
+    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
+    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
+    const u32 last = e->frame_hi + 1u;
+    verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, (u32)nb, last, kin, vin);
+    HIPCHK(hipGetLastError());
+    int bits = 1;
+    while (bits < 32 && (last >> bits)) bits++;
+    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
+    P.order = vin;
+  }
+  const size_t lds = overlap_lds_bytes(e->kp_dev_max);
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&overlap_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device)
+  overlap_kernel<<<(int)nb, SGTD_OVERLAP_THREADS, lds, e->stream>>>(P);
+  HIPCHK(hipGetLastError());
+  e->overlapped = true;
+  return SGTD_OK;
+}
+
+int sgtd_result_overlap(sgtd_handle e, int q, int32_t *n_query_kp, int32_t *n_frame_kp, int32_t *n_hit_query, int32_t *n_hit_frame,
+                        double *overlap, double *rms) {
+  PinScope pin_scope(e && !e->grp ? e : nullptr);
+  if (!e) return SGTD_ERR_INVALID;
+  if (e->grp) return multi::result_overlap(e, q, n_query_kp, n_frame_kp, n_hit_query, n_hit_frame, overlap, rms);
+  if (!e->batch_valid || !e->verified || !e->overlapped) { e->err = "no overlap results: sgtd_overlap comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(view_current(e));
+  const size_t cn = (size_t)e->dc.cand_num, o = (size_t)q * cn;
+  std::vector<int4> cnt(cn);
+  std::vector<double2> val(cn);
+  CHK(d2h(e, cnt.data(), e->o_cnt.as<int4>() + o, cn * sizeof(int4)));
+  CHK(d2h(e, val.data(), e->o_val.as<double2>() + o, cn * sizeof(double2)));
+  CHK(xfer_sync(e));
+  for (size_t k = 0; k < cn; k++) {
+    if (n_query_kp) n_query_kp[k] = cnt[k].x;
+    if (n_frame_kp) n_frame_kp[k] = cnt[k].y;
+    if (n_hit_query) n_hit_query[k] = cnt[k].z;
+    if (n_hit_frame) n_hit_frame[k] = cnt[k].w;
+    if (overlap) overlap[k] = val[k].x;
+    if (rms) rms[k] = val[k].y;
+  }
+  return SGTD_OK;
+}
+
+// sgtd_search_loop's rule over the candidates whose overlap reaches min_overlap, in host code (one rule for single and
+// multi-device handles)
+int sgtd_search_loop_overlap(sgtd_handle e, double icp_threshold, double min_overlap, int32_t *best_cand, int32_t *best_frame,
+                             double *best_score, double *best_overlap) {
+  PinScope pin_scope(e && !e->grp ? e : nullptr);
+  if (!e) return SGTD_ERR_INVALID;
+  const bool gate = min_overlap > 0.0;
+  const bool have = e->grp ? multi::has_overlap(e) != 0 : (e->batch_valid && e->verified && e->overlapped);
+  if (gate && !have) { e->err = "sgtd_search_loop_overlap with min_overlap > 0 needs sgtd_overlap on the pending batch"; return SGTD_ERR_STATE; }
+  const int cn = e->cfg.candidate_num;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  int nq = 0;
+  std::vector<double> score, ov;
+  std::vector<int> n_cand, frames;
+  if (e->grp) {
+    if (multi::nq_of(e, &nq) != SGTD_OK) return SGTD_ERR_INVALID;
+    score.resize((size_t)nq * cn); ov.assign((size_t)nq * cn, nan); n_cand.resize((size_t)nq); frames.resize((size_t)nq * cn);
+    for (int q = 0; q < nq; q++) {
+      CHK(multi::result_verify(e, q, score.data() + (size_t)q * cn, nullptr));
+      CHK(multi::candidates_of(e, q, &n_cand[(size_t)q], frames.data() + (size_t)q * cn));
+      if (have) CHK(multi::result_overlap(e, q, nullptr, nullptr, nullptr, nullptr, ov.data() + (size_t)q * cn, nullptr));
+    }
+  } else {
+    HIPCHK(hipSetDevice(e->cfg.device_id));
+    if (!e->verified || !e->batch_valid) return SGTD_ERR_INVALID;
+    CHK(sync_batch(e));
+    nq = e->nq;
+    if (nq == 0) return SGTD_OK;
+    const size_t nb = (size_t)nq * cn;
+    score.resize(nb); ov.assign(nb, nan);
+    std::vector<double2> val(have ? nb : 0);
+    CHK(d2h(e, score.data(), e->v_score.p, nb * sizeof(double)));
+    if (have) CHK(d2h(e, val.data(), e->o_val.p, nb * sizeof(double2)));
+    CHK(xfer_sync(e));
+    for (size_t i = 0; i < val.size(); i++) ov[i] = val[i].x;
+    n_cand.assign(e->h_n_cand.data(), e->h_n_cand.data() + nq);
+    frames.assign(e->h_cand_frame.data(), e->h_cand_frame.data() + nb);
+  }
+  for (int q = 0; q < nq; q++) {
+    double bs = 0;
+    int bc = -1;
+    for (int c = 0; c < n_cand[(size_t)q]; c++) {
+      const size_t i = (size_t)q * cn + c;
+      if (gate && !(ov[i] >= min_overlap)) continue;        // (NaN: left out)
+      if (score[i] > bs) { bs = score[i]; bc = c; }
+    }
+    const bool ok = bc >= 0 && bs > icp_threshold;
+    if (best_cand) best_cand[q] = ok ? bc : -1;
+    if (best_frame) best_frame[q] = ok ? frames[(size_t)q * cn + bc] : -1;
+    if (best_score) best_score[q] = ok ? bs : 0.0;
+    if (best_overlap) best_overlap[q] = ok ? ov[(size_t)q * cn + bc] : nan;
+  }
   return SGTD_OK;
 }
 

@@ -104,19 +104,26 @@ def frames_near(map_xy, prior_xy, radius):
 
 
 def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None, prior=None,
-                   refine=0):
+                   refine=0, min_overlap=0.0, overlap_radius=1.0):
     """SearchLoop for a batch of query frames on the device + the node's accounting.
     map_pose4[f] = 4x4 pose of map frame f; query_pose4[q] = ground truth of query q.
     allowed: a frame filter for the batch (STDescManager.set_frame_filter; e.g. frames_near of position priors).
     prior: (center, radius), a position prior for the batch (STDescManager.set_position_prior; the map poses set).
     refine: 0 = the node's accounting with SearchLoop's relative pose; N > 0 = STDescManager.refine_poses(N) after the
     verification, and the localization error is accounted with the refined pose of the candidate SearchLoop chose (the
-    choice itself and the candidate ranks are not touched)."""
+    choice itself and the candidate ranks are not touched).
+    min_overlap: 0 = SearchLoop's choice (today's accounting); > 0 = STDescManager.overlap(overlap_radius) after the
+    verification (the map's keypoints stored: add_frames(keep_keypoints=True) / set_frame_keypoints) and the detection
+    is search_loop_overlap's: the best-scored candidate among those whose keypoint overlap reaches min_overlap."""
     if metrics is None:
         metrics = LoopMetrics(mgr.config_setting_["candidate_num"])
     res = mgr.query_frames(query_xyz, query_label, kp_off, allowed=allowed, prior=prior)
     mgr.verify()
-    bc, bf, bs = mgr.search_loop()
+    if min_overlap > 0:
+        mgr.overlap(overlap_radius)
+        bc, bf, bs, _ = mgr.search_loop_overlap(min_overlap)
+    else:
+        bc, bf, bs = mgr.search_loop()
     if refine:
         mgr.refine_poses(refine)
     for q in range(len(bf)):

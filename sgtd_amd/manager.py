@@ -221,12 +221,68 @@ class STDescManager:
         s = d.soa()
         self._check(self._L.sgtd_add(self._h, C.byref(s), d.n))
 
-    def add_frames(self, xyz, label, kp_off=None):
+    def add_frames(self, xyz, label, kp_off=None, keep_keypoints=False):
         """BuildSingleScanSTD + AddSTDescs for a whole run of frames on the device
         (the caller's map loop, semantic_graph_localization.cpp:419-458).
-        xyz (F,N,3)/(total,3) numpy or torch.cuda tensor; kp_off None => uniform N."""
+        xyz (F,N,3)/(total,3) numpy or torch.cuda tensor; kp_off None => uniform N.
+        keep_keypoints: also store the frames' keypoints under the ids they are added with (set_frame_keypoints), for
+        overlap()."""
         xp, lp, off, nf, dev = self._frames_args(xyz, label, kp_off)
+        c0 = self.current_frame_id_ if keep_keypoints else 0
         self._check(self._L.sgtd_add_frames(self._h, xp, lp, _p(off), nf, dev))
+        if keep_keypoints and nf:
+            if dev:
+                xyz, label = xyz.cpu().numpy(), label.cpu().numpy()
+            self.set_frame_keypoints(np.arange(c0, c0 + nf, dtype=np.int64), xyz, label, off)
+
+    def set_frame_keypoints(self, frame_ids, xyz, label=None, kp_off=None):
+        """map keypoints kept on the handle (sgtd_set_frame_keypoints), keyed by global frame id: frame frame_ids[i] gets
+        the keypoints kp_off[i] .. kp_off[i+1] of xyz (.., 3) / label — what add_frames takes for that frame; kp_off None:
+        xyz (n, N, 3), N keypoints a frame.  xyz=None forgets the keypoints of those ids; frame_ids=None with xyz=None
+        forgets all."""
+        if frame_ids is None:
+            if xyz is not None:
+                raise ValueError("keypoints need their frame ids")
+            self._check(self._L.sgtd_set_frame_keypoints(self._h, None, None, None, None, 0))
+            return
+        ids = np.asarray(frame_ids)
+        if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+            raise ValueError("frame_ids: a 1-D array of integer frame ids")
+        if ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF):
+            raise ValueError("frame ids must lie in [0, 2^32)")
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if xyz is None:
+            if ids.size:
+                self._check(self._L.sgtd_set_frame_keypoints(self._h, _p(ids), None, None, None, ids.size))
+            return
+        if label is None:
+            raise ValueError("keypoints need their labels")
+        x, l, off = self._keypoint_args(xyz, label, kp_off, ids.size, "frame id")
+        if ids.size:
+            self._check(self._L.sgtd_set_frame_keypoints(self._h, _p(ids), _p(off), _p(x), _p(l), ids.size))
+
+    @staticmethod
+    def _keypoint_args(xyz, label, kp_off, n, what):
+        """host keypoint arrays for n frames: xyz (total, 3) f32, label (total,) u32, n + 1 offsets (checked)"""
+        x = np.asarray(xyz)
+        if kp_off is None:
+            if x.ndim != 3 or x.shape[2] != 3 or x.shape[0] != n:
+                raise ValueError("xyz: (n, N, 3), one row of keypoints per %s, or kp_off" % what)
+            off = np.arange(n + 1, dtype=np.int64) * x.shape[1]
+        else:
+            off = np.ascontiguousarray(np.asarray(kp_off).reshape(-1), np.int64)
+            if off.size != n + 1:
+                raise ValueError("kp_off: one offset per %s and a closing one" % what)
+        cnt = off[1:] - off[:-1]
+        if (cnt < 0).any() or (cnt > 65535).any():
+            raise ValueError("a frame has 0 .. 65535 keypoints")
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+        l = np.ascontiguousarray(label, np.uint32).reshape(-1)
+        if x.shape[0] != l.size or off[0] < 0 or off[-1] > l.size:
+            raise ValueError("xyz, label and kp_off do not fit each other")
+        if x.shape[0] == 0:           # (never a NULL pointer for an existing, empty set)
+            x, l = np.zeros((1, 3), np.float32), np.zeros(1, np.uint32)
+        return x, l, off
 
     def finalize(self):
         self._check(self._L.sgtd_finalize(self._h))
@@ -620,6 +676,57 @@ class STDescManager:
         bs = np.zeros(nq, np.float64)
         self._check(self._L.sgtd_search_loop(self._h, float(icp_threshold), _p(bc), _p(bf), _p(bs)))
         return bc, bf, bs
+
+    def overlap(self, radius, refined=False, xyz=None, label=None, kp_off=None):
+        """sgtd_overlap after verify(): under every verified candidate's relative pose (refined=True: refine_poses()'s),
+        how many of the query's keypoints land within `radius` of a keypoint of the same label of the candidate's frame
+        (set_frame_keypoints / add_frames(keep_keypoints=True)).  xyz=None: the batch's own keypoints (query_frames,
+        loop_frames); otherwise xyz / label (and kp_off, or xyz (n_queries, N, 3)) for every query of the batch."""
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+            raise TypeError("radius: a number")
+        radius = float(radius)
+        if not (radius >= 0.0) or np.isinf(radius):
+            raise ValueError("radius: finite, not negative")
+        flags = 1 if refined else 0
+        if xyz is None:
+            if label is not None or kp_off is not None:
+                raise ValueError("label and kp_off come with xyz")
+            self._check(self._L.sgtd_overlap(self._h, radius, flags, None, None, None))
+            return
+        if label is None:
+            raise ValueError("keypoints need their labels")
+        x, l, off = self._keypoint_args(xyz, label, kp_off, self._nq, "query")
+        self._check(self._L.sgtd_overlap(self._h, radius, flags, _p(x), _p(l), _p(off)))
+
+    def result_overlap(self, q):
+        """sgtd_result_overlap of query q after overlap(): a dict of n_query_kp, n_frame_kp, n_hit_query, n_hit_frame
+        [candidate_num] (int32; -1 without a verification result, n_frame_kp -1 for a frame without stored keypoints),
+        overlap (n_hit_query / n_query_kp) and rms [candidate_num] (NaN where undefined)"""
+        q = self._query_index(q)
+        cn = self.config_setting_["candidate_num"]
+        out = {k: np.zeros(cn, np.int32) for k in ("n_query_kp", "n_frame_kp", "n_hit_query", "n_hit_frame")}
+        out["overlap"] = np.zeros(cn, np.float64)
+        out["rms"] = np.zeros(cn, np.float64)
+        self._check(self._L.sgtd_result_overlap(self._h, q, _p(out["n_query_kp"]), _p(out["n_frame_kp"]), _p(out["n_hit_query"]),
+                                                _p(out["n_hit_frame"]), _p(out["overlap"]), _p(out["rms"])))
+        return out
+
+    def search_loop_overlap(self, min_overlap, icp_threshold=None):
+        """sgtd_search_loop_overlap: search_loop()'s rule over the candidates whose overlap reaches min_overlap (after
+        overlap(); min_overlap <= 0: search_loop()'s choice) -> (best_cand, best_frame, best_score, best_overlap)"""
+        if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float, np.integer, np.floating)):
+            raise TypeError("min_overlap: a number")
+        if np.isnan(min_overlap):
+            raise ValueError("min_overlap: not NaN")
+        if icp_threshold is None:
+            icp_threshold = self.icp_threshold_
+        nq = self._nq
+        bc = np.zeros(nq, np.int32)
+        bf = np.zeros(nq, np.int32)
+        bs = np.zeros(nq, np.float64)
+        bo = np.zeros(nq, np.float64)
+        self._check(self._L.sgtd_search_loop_overlap(self._h, float(icp_threshold), float(min_overlap), _p(bc), _p(bf), _p(bs), _p(bo)))
+        return bc, bf, bs, bo
 
     def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None, prior=None):
         """sgtd_search_frame: candidate_selector + candidate_verify + the inlier pairs of every candidate with their table
