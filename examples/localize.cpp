@@ -10,6 +10,10 @@
 //   (sgtd_set_frame_keypoints), sgtd_overlap(h, RADIUS) runs after the verification and the detection is
 //   sgtd_search_loop_overlap's — the best-scored candidate among those whose keypoint overlap reaches X (default 0.4) —
 //   in place of sgtd_search_loop's; one more line counts what the gate accepted, rejected and moved (off by default)
+//   --align RADIUS[,ITER] (anywhere on the line): the map's keypoints are stored on the handle, sgtd_align_keypoints(h,
+//   RADIUS, ITER) (default 10 iterations; from the refined pose with --refine) runs after the verification, and one more
+//   set of lines accounts sgtd_search_loop_aligned's choice (overlap_after >= 0.4, the lowest rms_after) with its aligned
+//   world pose (off by default)
 //   prior_radius: restrict every query to the map frames within that many metres (x, y) of its ground-truth position
 //   (sgtd_set_frame_poses + sgtd_set_position_prior), as a localizer with odometry would, and report how many map
 //   frames a query was allowed on average (the LOCALIZE_PER_FRAME calls below run without it)
@@ -151,10 +155,29 @@ int main(int argc, char **argv) {
     argc -= 2;
   }
   const bool use_overlap = overlap_radius >= 0.0;
+  double align_radius = -1.0;                                // --align RADIUS[,ITER], taken out likewise
+  int align_iter = 10;
+  for (int i = 1; i < argc;) {
+    if (std::strcmp(argv[i], "--align")) { i++; continue; }
+    char *end = nullptr;
+    const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : -1.0;
+    long it = 10;
+    bool ok = i + 1 < argc && end != argv[i + 1] && v >= 0.0 && !std::isinf(v);
+    if (ok && *end == ',') {
+      char *e2 = nullptr;
+      it = std::strtol(end + 1, &e2, 10);
+      ok = e2 != end + 1 && !*e2 && it >= 1 && it <= 1000000;
+    } else if (ok && *end) ok = false;
+    if (!ok) { std::fprintf(stderr, "--align needs RADIUS[,ITER]: a number >= 0 and an iteration count >= 1\n"); return 2; }
+    align_radius = v; align_iter = (int)it;
+    for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+    argc -= 2;
+  }
+  const bool use_align = align_radius >= 0.0;
   if (min_overlap_given && !use_overlap) { std::fprintf(stderr, "--min-overlap comes with --overlap RADIUS\n"); return 2; }
   if (argc < 3) {
     std::fprintf(stderr, "usage: %s <map_dir | map.cache> <query_dir | query.cache> [batch] [icp_threshold] [prior_radius] [--refine N] "
-                         "[--overlap RADIUS [--min-overlap X]]\n", argv[0]);
+                         "[--overlap RADIUS [--min-overlap X]] [--align RADIUS[,ITER]]\n", argv[0]);
     return 2;
   }
   // SearchLoop hands back ~130 MB of std::pair<STDesc, STDesc> per frame (the reference's own result
@@ -195,7 +218,7 @@ int main(int argc, char **argv) {
     for (int i = 0; i < map.n; i++) ids[i] = (uint32_t)i;
     OK(sgtd_set_frame_poses(h, ids.data(), map.poses, map.n));
   }
-  if (use_overlap) {                                         // the map's keypoints, under the ids the frames were added with
+  if (use_overlap || use_align) {                            // the map's keypoints, under the ids the frames were added with
     std::vector<uint32_t> ids(map.n);
     for (int i = 0; i < map.n; i++) ids[i] = (uint32_t)i;
     OK(sgtd_set_frame_keypoints(h, ids.data(), map.off, map.xyz, map.label, map.n));
@@ -204,6 +227,10 @@ int main(int argc, char **argv) {
   double ov_sum = 0;
   std::vector<int32_t> plain_cand(batch), plain_frame(batch);
   std::vector<double> best_overlap(batch);
+  long al_chosen = 0, al_moved = 0, al_score_num = 0;        // --align: sgtd_search_loop_aligned's choice, its aligned pose
+  double al_err_t = 0, al_err_r = 0, al_rms_b = 0, al_rms_a = 0;
+  std::vector<int32_t> al_cand(batch), al_frame(batch);
+  std::vector<double> al_pose((size_t)cfg.candidate_num * 12), al_rb(cfg.candidate_num), al_ra(cfg.candidate_num);
   long allowed_sum = 0;                                      // (query, map frame) pairs the priors allowed
   std::vector<double> prior_c, prior_r;
   auto t2 = std::chrono::steady_clock::now();
@@ -254,6 +281,27 @@ int main(int argc, char **argv) {
       }
     }
     if (refine) OK(sgtd_refine_poses(h, refine));
+    if (use_align) {
+      OK(sgtd_align_keypoints(h, align_radius, align_iter, refine ? SGTD_ALIGN_REFINED : 0, nullptr, nullptr, nullptr));
+      OK(sgtd_search_loop_aligned(h, 0.4, 0.0, al_cand.data(), al_frame.data(), nullptr, nullptr));
+      for (int i = 0; i < nb; i++) {
+        if (!(al_frame[i] > 0)) continue;
+        al_chosen++;
+        if (al_cand[i] != best_cand[i]) al_moved++;
+        OK(sgtd_result_aligned(h, i, al_pose.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, al_rb.data(), nullptr, al_ra.data(), nullptr));
+        const double *r = &al_pose[(size_t)al_cand[i] * 12];
+        Mat4 nt{};
+        for (int a = 0; a < 3; a++) {
+          for (int b = 0; b < 3; b++) nt.m[a][b] = (float)r[a * 3 + b];
+          nt.m[a][3] = (float)r[9 + a];
+        }
+        nt.m[3][3] = 1.f;
+        double te, re;
+        compute_adj_rpe(from_row(qs.poses + (size_t)(q0 + i) * 12), mul(from_row(map.poses + (size_t)al_frame[i] * 12), nt), te, re);
+        if (te < 5 && re < 10) { al_score_num++; al_err_t += te; al_err_r += re; }
+        al_rms_b += al_rb[al_cand[i]]; al_rms_a += al_ra[al_cand[i]];
+      }
+    }
     auto tb2 = std::chrono::steady_clock::now();
     if (std::getenv("LOCALIZE_VERBOSE"))
       std::printf("  batch at %d: select %.1f ms, verify + choice %.1f ms\n", q0,
@@ -315,6 +363,13 @@ int main(int argc, char **argv) {
   if (use_overlap)
     std::printf("keypoint overlap (radius %.2f m, min %.2f): accepted %ld, rejected %ld, moved to another candidate %ld, mean overlap of the accepted %.4f\n",
                 overlap_radius, min_overlap, ov_accepted, ov_rejected, ov_moved, ov_accepted ? ov_sum / ov_accepted : 0.0);
+  if (use_align) {
+    std::printf("keypoint alignment (radius %.2f m, %d iteration%s, overlap >= 0.40): chosen %ld, another candidate than SearchLoop's %ld, success(5m,10deg) %ld (%.4f)\n",
+                align_radius, align_iter, align_iter == 1 ? "" : "s", al_chosen, al_moved, al_score_num, total_num ? (double)al_score_num / total_num : 0.0);
+    std::printf("mean errors of the successes, aligned: %.4f m, %.4f deg; mean keypoint rms of the chosen %.4f m before, %.4f m after\n",
+                al_score_num ? al_err_t / al_score_num : 0.0, al_score_num ? al_err_r / al_score_num : 0.0,
+                al_chosen ? al_rms_b / al_chosen : 0.0, al_chosen ? al_rms_a / al_chosen : 0.0);
+  }
   std::printf("time: load %.1f ms, map build %.1f ms, queries %.1f ms (%.3f ms per query incl. verification), %d device(s)\n", ms(t0, t1), ms(t1, t2),
               ms(t2, t3), total_num ? ms(t2, t3) / total_num : 0.0, sgtd_device_count(h));
   if (const char *pf = std::getenv("LOCALIZE_PER_FRAME")) {

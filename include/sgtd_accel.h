@@ -524,6 +524,87 @@ int sgtd_result_overlap(sgtd_handle h, int q,
 int sgtd_search_loop_overlap(sgtd_handle h, double icp_threshold, double min_overlap,
                              int32_t *best_cand, int32_t *best_frame,
                              double *best_score, double *best_overlap);
+
+/* Label-aware closest-keypoint alignment (ICP over the semantic keypoints) of every verified candidate, on the device,
+ * after sgtd_verify (or sgtd_verify_masked, or sgtd_search_frame with flags 0).  sgtd_refine_poses sees only the vertices
+ * of matched triangles and sgtd_overlap only measures; this call assigns every query keypoint to the nearest keypoint of
+ * its label of the candidate's frame (sgtd_set_frame_keypoints), refits the pose over the assigned pairs and repeats.
+ * It hands out the polished pose, sgtd_overlap's figures before and after (rms_after is the registration fitness to
+ * re-rank candidates on) and the keypoint-to-keypoint assignment under the final pose.
+ * Start pose (R0, t0): sgtd_result_verify's; with SGTD_ALIGN_REFINED sgtd_result_refined's (SGTD_ERR_STATE when
+ * sgtd_refine_poses has not run on this batch).  Query keypoints: as for sgtd_overlap (NULL: the batch's own; a batch of
+ * sgtd_query_descs or sgtd_search_frame has none, SGTD_ERR_STATE; otherwise host arrays, copied before the call returns). */
+/* The rule, for candidate k of query q that has a verification result and whose frame has stored keypoints.  All
+ * arithmetic is f64, every operation rounded once (no contraction); f32 inputs are widened exactly.
+ * Query keypoints i = 0 .. n-1 with position p_i and label l_i; frame keypoints j = 0 .. m-1 with position w_j and a
+ * label; rr = radius * radius; iterations >= 1.
+ * Assignment under a pose (R, t): x_i and r2(i, j) are sgtd_overlap's (x[c] = ((R[c][0]*p[0] + R[c][1]*p[1]) + R[c][2]*p[2])
+ *   + t[c]; e = x - w; r2 = (e[0]*e[0] + e[1]*e[1]) + e[2]*e[2]).  a(i) = the j of label l_i (as u32) with the smallest
+ *   r2(i, j); an equal r2 goes to the lowest j; a NaN r2 is never chosen.  a(i) = -1 when no j has the label (or every
+ *   such r2 is NaN), or when the minimum m_i is not <= rr.
+ * Iteration it = 1 .. iterations, pose 0 being the start pose: A_it = the assignment under the pose of iteration it - 1.
+ *   If fewer than 3 keypoints are assigned, stop: the pose of iteration it - 1 stands.  If it >= 2 and A_it equals
+ *   A_(it-1) element for element, stop (converged).  Otherwise fit, with c = (double)(number assigned):
+ *     cp = SUM(p_i) / c, cw = SUM(w_a(i)) / c, H[r][s] = SUM((p_i[r] - cp[r]) * (w_a(i)[s] - cw[s]));
+ *     R from H exactly as in sgtd_refine_poses (H = U S V^T by sgtd_verify's one-sided Jacobi, R = V U^T, and
+ *     R = V diag(1, 1, -1) U^T when det(V U^T) < 0); t[r] = -((R[r][0]*cp[0] + R[r][1]*cp[1]) + R[r][2]*cp[2]) + cw[r];
+ *   that is the pose of iteration it.
+ * SUM has the fixed order of sgtd_refine_poses and sgtd_overlap: 256 accumulators acc[0..255] starting at +0.0; acc[l]
+ * takes the query keypoints i == l (mod 256) in ascending i, one addition each; an unassigned keypoint is skipped, not
+ * added as zero; then acc[l] = acc[l] + acc[l + s] for all l < s, for s = 128, 64, 32, 16, 8, 4, 2, 1 in turn; SUM = acc[0].
+ * Results: pose = the last pose that stands (the start pose itself when no fit was made); n_fits = fits made;
+ *   n_corr = the assigned count of the last fit (0 with no fit); moments = cp, cw, H of the last fit (NaN with no fit);
+ *   stop = 0 ran out of iterations, 1 fewer than 3 assigned, 2 converged;
+ *   counts_before / overlap_before / rms_before = sgtd_overlap's n_query_kp, n_frame_kp, n_hit_query, n_hit_frame, overlap
+ *   and rms, by sgtd_overlap's rule at this radius, under the start pose; *_after = the same under the final pose;
+ *   assign = the assignment under the final pose, an int32 per query keypoint (sgtd_result_aligned_pairs).
+ * A candidate without a verification result (past n_cand, score -1, masked out by sgtd_verify_masked): pose 12 zeros, the
+ * counts -1, n_fits and n_corr 0, stop -1, every double NaN, every assign entry -1.  A verified candidate whose frame has
+ * no stored keypoints: n_frame_kp = -1 (n_query_kp is reported), the pose is the start pose, n_fits = 0, stop = 1, the hit
+ * counts 0, overlap, rms and moments NaN, every assign entry -1.
+ * The call adds results and changes none: sgtd_result_verify, sgtd_result_inlier*, sgtd_result_refined*,
+ * sgtd_result_overlap, sgtd_result_world_poses and sgtd_search_loop* return what they returned before.  A new batch or a
+ * new sgtd_verify* drops the aligned results; a later sgtd_align_keypoints replaces them.  A view has results of its own;
+ * a multi-device handle forwards the call to every shard and fetches each candidate's result from its owner (the single
+ * handle's values bit for bit).  Memory: candidate_num int32 per query keypoint of the batch for the assignments.
+ * h == NULL, radius NaN, negative or infinite, iterations < 1, unknown flag bits, q_xyz set while q_label or q_kp_off is
+ * NULL, a query with a negative count or more than 65535 keypoints: SGTD_ERR_INVALID, before the device is touched; no
+ * verification of the pending batch yet: SGTD_ERR_STATE; a view whose owner's table changed: SGTD_ERR_STATE. */
+#define SGTD_ALIGN_REFINED 1   /* start from sgtd_refine_poses' pose instead of sgtd_verify's */
+int sgtd_align_keypoints(sgtd_handle h, double radius, int iterations, int flags,
+                         const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off);
+/* Aligned results of every candidate of query q; cn = candidate_num; any pointer may be NULL.  h == NULL:
+ * SGTD_ERR_INVALID; before sgtd_align_keypoints on this batch: SGTD_ERR_STATE; q outside the batch: SGTD_ERR_INVALID. */
+int sgtd_result_aligned(sgtd_handle h, int q,
+                        double *pose,            /* [cn*12] rot row-major (9), t (3) */
+                        int32_t *n_fits,         /* [cn] */
+                        int32_t *n_corr,         /* [cn] */
+                        int32_t *stop,           /* [cn] */
+                        int32_t *counts_before,  /* [cn*4] n_query_kp, n_frame_kp, n_hit_query, n_hit_frame */
+                        int32_t *counts_after,   /* [cn*4] */
+                        double *overlap_before,  /* [cn] */
+                        double *rms_before,      /* [cn] */
+                        double *overlap_after,   /* [cn] */
+                        double *rms_after,       /* [cn] */
+                        double *moments);        /* [cn*15] cp(3), cw(3), H(9): parity output */
+/* The assignment of (query q, candidate cand) under the final pose: frame_kp[i] = the frame keypoint query keypoint i is
+ * assigned to, or -1; capacity in elements, *n = needed = the query's keypoint count.  cand outside the query's
+ * candidates, q outside the batch, n == NULL: SGTD_ERR_INVALID; more than capacity: SGTD_ERR_CAPACITY (the first
+ * `capacity` entries are written); before sgtd_align_keypoints: SGTD_ERR_STATE. */
+int sgtd_result_aligned_pairs(sgtd_handle h, int q, int cand, int32_t *frame_kp, int64_t capacity, int64_t *n);
+/* sgtd_result_world_poses with the aligned relative pose in place of sgtd_verify's: the same composition rule, in the
+ * library's host code; 12 NaNs where the candidate has no result or its frame has no pose.  world == NULL:
+ * SGTD_ERR_INVALID; otherwise as sgtd_result_aligned. */
+int sgtd_result_aligned_world_poses(sgtd_handle h, int q, float *world);
+/* The reference node's choice among registered candidates (the lowest fitness wins), for every query of the batch, in host
+ * code: of the candidates with a verification result, overlap_after >= min_overlap (min_overlap <= 0: no bound) and
+ * rms_after <= max_rms (max_rms <= 0 or +inf: no bound) — a NaN overlap_after under a bound, or a NaN rms_after, leaves a
+ * candidate out — the one with the strictly smallest rms_after; equal rms_after goes to the larger verify_score, then to
+ * the lower candidate index.  best_rms / best_overlap: its rms_after and overlap_after.  Nothing qualifies: -1, -1, NaN,
+ * NaN.  Arrays of n_queries; any may be NULL.  h == NULL, min_overlap or max_rms NaN: SGTD_ERR_INVALID; without
+ * sgtd_align_keypoints on the batch: SGTD_ERR_STATE. */
+int sgtd_search_loop_aligned(sgtd_handle h, double min_overlap, double max_rms,
+                             int32_t *best_cand, int32_t *best_frame, double *best_rms, double *best_overlap);
 /* asynchronous device-to-device export of the verification results of the whole batch into
  * caller device buffers (score f64 [n_queries*candidate_num], pose f64 [n_queries*candidate_num*12]),
  * enqueued on the handle's stream without synchronising: the table-sharded multi-GPU path

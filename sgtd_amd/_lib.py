@@ -33,6 +33,8 @@ SYMBOLS = [
     "sgtd_set_frame_poses", "sgtd_set_position_prior", "sgtd_result_world_poses",
     "sgtd_refine_poses", "sgtd_result_refined", "sgtd_result_refined_world_poses",
     "sgtd_set_frame_keypoints", "sgtd_overlap", "sgtd_result_overlap", "sgtd_search_loop_overlap",
+    "sgtd_align_keypoints", "sgtd_result_aligned", "sgtd_result_aligned_pairs", "sgtd_result_aligned_world_poses",
+    "sgtd_search_loop_aligned",
 ]
 
 
@@ -158,6 +160,11 @@ def lib():
     L.sgtd_overlap.argtypes = [vp, C.c_double, C.c_int, vp, vp, vp]
     L.sgtd_result_overlap.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.sgtd_search_loop_overlap.argtypes = [vp, C.c_double, C.c_double, vp, vp, vp, vp]
+    L.sgtd_align_keypoints.argtypes = [vp, C.c_double, C.c_int, C.c_int, vp, vp, vp]
+    L.sgtd_result_aligned.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgtd_result_aligned_pairs.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp]
+    L.sgtd_result_aligned_world_poses.argtypes = [vp, C.c_int, vp]
+    L.sgtd_search_loop_aligned.argtypes = [vp, C.c_double, C.c_double, vp, vp, vp, vp]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

@@ -23,7 +23,7 @@ struct Group {
   int n = 0;
   u32 current_frame_id = 0;              // global
   int nq = 0;
-  bool batch_valid = false, merged = false, verified = false, refined = false, overlapped = false;
+  bool batch_valid = false, merged = false, verified = false, refined = false, overlapped = false, aligned = false;
   // merged candidate tables of the last batch
   std::vector<int> n_cand, cand_frame, cand_votes, owner, owner_slot;
   std::vector<long long> pair_off;       // [nq * (cn + 1)] offsets into the query's concatenated lists
@@ -64,6 +64,11 @@ int nq_of(sgtd_engine *e, int *nq);
 int overlap(sgtd_engine *e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off);
 int result_overlap(sgtd_engine *e, int q, int32_t *n_query_kp, int32_t *n_frame_kp, int32_t *n_hit_query, int32_t *n_hit_frame, double *overlap, double *rms);
 int has_overlap(sgtd_engine *e);
+int align_keypoints(sgtd_engine *e, double radius, int iterations, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off);
+int result_aligned(sgtd_engine *e, int q, double *pose, int32_t *n_fits, int32_t *n_corr, int32_t *stop, int32_t *counts_before, int32_t *counts_after,
+                   double *overlap_before, double *rms_before, double *overlap_after, double *rms_after, double *moments);
+int result_aligned_pairs(sgtd_engine *e, int q, int cand, int32_t *frame_kp, int64_t capacity, int64_t *n);
+int has_aligned(sgtd_engine *e);
 int result_inliers(sgtd_engine *e, int q, int cand, int32_t *idx, int64_t capacity, int64_t *n);
 int result_inlier_pairs(sgtd_engine *e, int q, int64_t *cand_off, int32_t *q_idx, int64_t *db_entry, int64_t capacity, int64_t *n_pairs);
 int search_loop(sgtd_engine *e, double icp_threshold, int32_t *best_cand, int32_t *best_frame, double *best_score);

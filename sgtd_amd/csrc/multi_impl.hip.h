@@ -245,7 +245,7 @@ int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const 
   // every device builds the query descriptors itself and sweeps its shard; the calls only
   // enqueue, so the devices run concurrently
   for (sgtd_engine *c : g->dev) MCHK(sgtd_query_frames(c, xyz, label, kp_off, n_queries, 0));
-  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false;
+  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false; g->aligned = false;
   return SGTD_OK;
 }
 
@@ -267,7 +267,7 @@ int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq) {
     t.frame = lf.data();
     MCHK(sgtd_query_descs(c, &t, nq));
   }
-  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false;
+  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false; g->aligned = false;
   return SGTD_OK;
 }
 
@@ -441,7 +441,7 @@ int result_votes(sgtd_engine *e, int q, uint32_t *votes, int64_t capacity, uint3
 int verify(sgtd_engine *e) {
   Group *g = G(e);
   CHK(merge(e));
-  g->refined = false; g->overlapped = false;
+  g->refined = false; g->overlapped = false; g->aligned = false;
   for (sgtd_engine *c : g->dev) MCHK(sgtd_verify(c));   // every owner verifies its local candidates
   g->verified = true;
   return SGTD_OK;
@@ -566,6 +566,73 @@ int result_overlap(sgtd_engine *e, int q, int32_t *n_query_kp, int32_t *n_frame_
     if (overlap) overlap[k] = o.ov[ks];
     if (rms) rms[k] = o.rms[ks];
   }
+  return SGTD_OK;
+}
+
+int has_aligned(sgtd_engine *e) {
+  Group *g = G(e);
+  return g->batch_valid && g->verified && g->aligned;
+}
+
+// every owner aligns its local candidates (the checks ran in sgtd_align_keypoints)
+int align_keypoints(sgtd_engine *e, double radius, int iterations, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
+  Group *g = G(e);
+  if (!g->batch_valid || !g->verified) { e->err = "sgtd_align_keypoints needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if ((flags & SGTD_ALIGN_REFINED) && !g->refined) { e->err = "SGTD_ALIGN_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
+  g->aligned = false;
+  for (sgtd_engine *c : g->dev) MCHK(sgtd_align_keypoints(c, radius, iterations, flags, q_xyz, q_label, q_kp_off));
+  g->aligned = true;
+  return SGTD_OK;
+}
+
+// the aligned results of query q's merged candidates, each from its owner (result_refined's pattern)
+int result_aligned(sgtd_engine *e, int q, double *pose, int32_t *n_fits, int32_t *n_corr, int32_t *stop, int32_t *counts_before, int32_t *counts_after,
+                   double *overlap_before, double *rms_before, double *overlap_after, double *rms_after, double *moments) {
+  Group *g = G(e);
+  if (!has_aligned(e)) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  struct Owned { std::vector<double> pose, mom, val[4]; std::vector<int32_t> fit[3], cnt[2]; };
+  std::vector<Owned> own(g->n);
+  int32_t *fit[3] = {n_fits, n_corr, stop}, *cnt[2] = {counts_before, counts_after};
+  double *val[4] = {overlap_before, rms_before, overlap_after, rms_after};
+  for (int k = 0; k < cn; k++) {
+    if (pose) std::fill(pose + (size_t)k * 12, pose + (size_t)k * 12 + 12, 0.0);
+    if (moments) std::fill(moments + (size_t)k * 15, moments + (size_t)k * 15 + 15, nan);
+    for (int a = 0; a < 3; a++) if (fit[a]) fit[a][k] = a == 2 ? -1 : 0;
+    for (int a = 0; a < 2; a++) if (cnt[a]) std::fill(cnt[a] + (size_t)k * 4, cnt[a] + (size_t)k * 4 + 4, -1);
+    for (int a = 0; a < 4; a++) if (val[a]) val[a][k] = nan;
+  }
+  for (int k = 0; k < g->n_cand[q]; k++) {
+    const size_t i = (size_t)q * cn + k;
+    const int s = g->owner[i], ks = g->owner_slot[i];
+    Owned &o = own[s];
+    if (o.pose.empty()) {
+      sgtd_engine *c = g->dev[s];
+      o.pose.resize((size_t)cn * 12); o.mom.resize((size_t)cn * 15);
+      for (int a = 0; a < 4; a++) o.val[a].resize(cn);
+      for (int a = 0; a < 3; a++) o.fit[a].resize(cn);
+      for (int a = 0; a < 2; a++) o.cnt[a].resize((size_t)cn * 4);
+      MCHK(sgtd_result_aligned(c, q, o.pose.data(), o.fit[0].data(), o.fit[1].data(), o.fit[2].data(), o.cnt[0].data(), o.cnt[1].data(),
+                               o.val[0].data(), o.val[1].data(), o.val[2].data(), o.val[3].data(), o.mom.data()));
+    }
+    if (pose) std::copy(o.pose.begin() + (size_t)ks * 12, o.pose.begin() + (size_t)ks * 12 + 12, pose + (size_t)k * 12);
+    if (moments) std::copy(o.mom.begin() + (size_t)ks * 15, o.mom.begin() + (size_t)ks * 15 + 15, moments + (size_t)k * 15);
+    for (int a = 0; a < 3; a++) if (fit[a]) fit[a][k] = o.fit[a][ks];
+    for (int a = 0; a < 2; a++) if (cnt[a]) std::copy(o.cnt[a].begin() + (size_t)ks * 4, o.cnt[a].begin() + (size_t)ks * 4 + 4, cnt[a] + (size_t)k * 4);
+    for (int a = 0; a < 4; a++) if (val[a]) val[a][k] = o.val[a][ks];
+  }
+  return SGTD_OK;
+}
+
+int result_aligned_pairs(sgtd_engine *e, int q, int cand, int32_t *frame_kp, int64_t capacity, int64_t *n) {
+  Group *g = G(e);
+  if (!has_aligned(e)) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= g->nq || cand < 0 || cand >= g->n_cand[q]) return SGTD_ERR_INVALID;
+  const size_t i = (size_t)q * e->cfg.candidate_num + cand;
+  sgtd_engine *c = g->dev[g->owner[i]];
+  MCHK(sgtd_result_aligned_pairs(c, q, g->owner_slot[i], frame_kp, capacity, n));
   return SGTD_OK;
 }
 

@@ -54,6 +54,47 @@ inline size_t overlap_tile_slots(int max_kp) { return (size_t)std::min(std::max(
 inline size_t overlap_hit_off(int max_kp) { return (size_t)SGTD_OVERLAP_HEAD + overlap_tile_slots(max_kp) * sizeof(uint4); }
 inline size_t overlap_lds_bytes(int max_kp) { return overlap_hit_off(max_kp) + (((size_t)std::max(max_kp, 1) + 15) & ~(size_t)15); }
 
+// The walk of one round of 256 query keypoints over a frame's keypoints, tile by tile: this thread's keypoint (x, lab;
+// `active`) against every frame keypoint.  m (+inf at the call) becomes the minimum of r2 over the keypoints of the
+// label, the frame keypoints within reach get their hit byte.  ARG (sgtd_align_keypoints): bj (-1 at the call) becomes
+// the lowest j that attains the minimum, -1 when no keypoint of the label has a non-NaN r2.  `stage` (uniform): stage
+// the first tile too — off when a frame of one tile is still in `tile` from the round before.
+template <bool ARG>
+__device__ __forceinline__ void overlap_walk(const uint4 *kp, int nf, bool stage, uint4 *tile, unsigned char *hit, bool active,
+                                             const double (&x)[3], u32 lab, double rr, double &m, int &bj) {
+  const int tid = threadIdx.x;
+  for (int t0 = 0; t0 < nf; t0 += SGTD_OVERLAP_TILE) {
+    const int nt = min(SGTD_OVERLAP_TILE, nf - t0);
+    if (stage || t0 > 0) {
+      __syncthreads();                                     // the last tile's readers are done; the hit bytes are cleared
+      for (int j = tid; j < nt; j += SGTD_OVERLAP_THREADS) tile[j] = kp[t0 + j];
+      __syncthreads();
+    }
+    if (active) {
+      // the label gates both comparisons; the distance itself is computed for every lane (the wave pays for it as
+      // soon as one lane's label matches, and without a branch around it four keypoints' LDS reads are in flight)
+      auto test = [&](const uint4 k, int j) {
+        const double e0 = x[0] - (double)__uint_as_float(k.x), e1 = x[1] - (double)__uint_as_float(k.y),
+                     e2 = x[2] - (double)__uint_as_float(k.z);
+        const double r2 = (e0 * e0 + e1 * e1) + e2 * e2;
+        const bool same = k.w == lab;
+        if (ARG) {
+          if (same && (r2 < m || (bj < 0 && r2 <= m))) { m = r2; bj = t0 + j; }      // (the first one, +inf included)
+        } else {
+          if (same && r2 < m) m = r2;
+        }
+        if (same && r2 <= rr) hit[t0 + j] = 1;
+      };
+      int j = 0;
+      for (; j + 4 <= nt; j += 4) {
+        const uint4 k0 = tile[j], k1 = tile[j + 1], k2 = tile[j + 2], k3 = tile[j + 3];
+        test(k0, j); test(k1, j + 1); test(k2, j + 2); test(k3, j + 3);
+      }
+      for (; j < nt; j++) test(tile[j], j);
+    }
+  }
+}
+
 __global__ __launch_bounds__(SGTD_OVERLAP_THREADS) void overlap_kernel(OverlapParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char overlap_smem[];
   double *red = reinterpret_cast<double *>(overlap_smem);                       // [128]
@@ -102,32 +143,8 @@ __global__ __launch_bounds__(SGTD_OVERLAP_THREADS) void overlap_kernel(OverlapPa
       for (int a = 0; a < 3; a++) x[a] = ((Rt[a * 3] * p[0] + Rt[a * 3 + 1] * p[1]) + Rt[a * 3 + 2] * p[2]) + Rt[9 + a];
     }
     double m = __builtin_inf();
-    for (int t0 = 0; t0 < nf; t0 += SGTD_OVERLAP_TILE) {
-      const int nt = min(SGTD_OVERLAP_TILE, nf - t0);
-      if (nf > SGTD_OVERLAP_TILE || r == 0) {              // (uniform: a frame of one tile is staged once)
-        __syncthreads();                                   // the last tile's readers are done; the hit bytes are cleared
-        for (int j = tid; j < nt; j += SGTD_OVERLAP_THREADS) tile[j] = kp[t0 + j];
-        __syncthreads();
-      }
-      if (active) {
-        // the label gates both comparisons; the distance itself is computed for every lane (the wave pays for it as
-        // soon as one lane's label matches, and without a branch around it four keypoints' LDS reads are in flight)
-        auto test = [&](const uint4 k, int j) {
-          const double e0 = x[0] - (double)__uint_as_float(k.x), e1 = x[1] - (double)__uint_as_float(k.y),
-                       e2 = x[2] - (double)__uint_as_float(k.z);
-          const double r2 = (e0 * e0 + e1 * e1) + e2 * e2;
-          const bool same = k.w == lab;
-          if (same && r2 < m) m = r2;
-          if (same && r2 <= rr) hit[t0 + j] = 1;
-        };
-        int j = 0;
-        for (; j + 4 <= nt; j += 4) {
-          const uint4 k0 = tile[j], k1 = tile[j + 1], k2 = tile[j + 2], k3 = tile[j + 3];
-          test(k0, j); test(k1, j + 1); test(k2, j + 2); test(k3, j + 3);
-        }
-        for (; j < nt; j++) test(tile[j], j);
-      }
-    }
+    int bj = -1;
+    overlap_walk<false>(kp, nf, nf > SGTD_OVERLAP_TILE || r == 0, tile, hit, active, x, lab, rr, m, bj);   // (a frame of one tile is staged once)
     if (active && m <= rr) { acc += m; n_hit++; }
   }
   __syncthreads();

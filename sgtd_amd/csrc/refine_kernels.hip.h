@@ -93,6 +93,30 @@ __device__ __forceinline__ void refine_tree(double (&v)[N], double *red, double 
   __syncthreads();
 }
 
+// the 3x3 solve (triangle_solver's, :558-569) of a fit with covariance H about the centroids mom = cp, cw:
+// out[0..8] = rot row-major, out[9..11] = t
+__device__ inline void refine_solve(const double (&H)[9], const double *mom, double *out) {
+  double cov[3][3], U[3][3], V[3][3], UT[3][3], rot[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) cov[i][j] = H[i * 3 + j];
+  svd3_dev(cov, U, V);
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) UT[i][j] = U[j][i];
+  mul3(V, UT, rot);
+  const double det = rot[0][0] * (rot[1][1] * rot[2][2] - rot[1][2] * rot[2][1]) -
+                     rot[0][1] * (rot[1][0] * rot[2][2] - rot[1][2] * rot[2][0]) +
+                     rot[0][2] * (rot[1][0] * rot[2][1] - rot[1][1] * rot[2][0]);
+  if (det < 0) {
+    double K[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, -1}}, VK[3][3];
+    mul3(V, K, VK);
+    mul3(VK, UT, rot);
+  }
+  for (int r = 0; r < 3; r++) {
+    for (int k = 0; k < 3; k++) out[r * 3 + k] = rot[r][k];
+    out[9 + r] = -(rot[r][0] * mom[0] + rot[r][1] * mom[1] + rot[r][2] * mom[2]) + mom[3 + r];
+  }
+}
+
 __global__ __launch_bounds__(SGTD_REFINE_THREADS) void refine_kernel(RefineParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char refine_smem[];
   float *rec = reinterpret_cast<float *>(refine_smem);                                        // [18][CAP]
@@ -196,27 +220,7 @@ __global__ __launch_bounds__(SGTD_REFINE_THREADS) void refine_kernel(RefineParam
 #pragma unroll
     for (int i = 0; i < 9; i++) mom[6 + i] = H[i];
     // ---- the 3x3 solve (triangle_solver's, :558-569) by thread 0
-    if (tid == 0) {
-      double cov[3][3], U[3][3], V[3][3], UT[3][3], rot[3][3];
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) cov[i][j] = H[i * 3 + j];
-      svd3_dev(cov, U, V);
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) UT[i][j] = U[j][i];
-      mul3(V, UT, rot);
-      const double det = rot[0][0] * (rot[1][1] * rot[2][2] - rot[1][2] * rot[2][1]) -
-                         rot[0][1] * (rot[1][0] * rot[2][2] - rot[1][2] * rot[2][0]) +
-                         rot[0][2] * (rot[1][0] * rot[2][1] - rot[1][1] * rot[2][0]);
-      if (det < 0) {
-        double K[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, -1}}, VK[3][3];
-        mul3(V, K, VK);
-        mul3(VK, UT, rot);
-      }
-      for (int r = 0; r < 3; r++) {
-        for (int k = 0; k < 3; k++) bc[r * 3 + k] = rot[r][k];
-        bc[9 + r] = -(rot[r][0] * mom[0] + rot[r][1] * mom[1] + rot[r][2] * mom[2]) + mom[3 + r];
-      }
-    }
+    if (tid == 0) refine_solve(H, mom, bc);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 12; k++) Rt[k] = bc[k];

@@ -29,6 +29,7 @@
 #include "prior_kernels.hip.h"
 #include "refine_kernels.hip.h"
 #include "overlap_kernels.hip.h"
+#include "align_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -270,6 +271,11 @@ struct sgtd_engine {
   std::vector<u64> kp_word_host;
   int kp_dev_max = 0;                // keypoints of the longest frame of the device copy
   bool overlapped = false;
+  // sgtd_align_keypoints (align_kernels.hip.h): the aligned results of the batch; a_assign holds candidate_num int32 per
+  // query keypoint of the batch (a_qoff: the queries' keypoint offsets, from 0, as the call had them)
+  DevBuf a_pose, a_fit, a_cnt, a_val, a_mom, a_assign;
+  std::vector<long long> a_qoff;
+  bool aligned = false;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -1120,7 +1126,7 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
     HIPCHK(hipGetLastError());
   }
   e->lists_pending = false;
-  e->verified = false; e->refined = false; e->overlapped = false;
+  e->verified = false; e->refined = false; e->overlapped = false; e->aligned = false;
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -1369,8 +1375,7 @@ int launch_select(sgtd_engine *e) {
       SO.n_slots = (u32)n_slots; SO.max_pass_slots = (u32)max_pass_slots; SO.cbits = cbits; SO.sub_bits = sub_bits; SO.pair = pair ? 1 : 0; SO.key_bits = key_bits;
       SO.qrec = nullptr; SO.n_qrec = 0; SO.rough = e->dc.rough;
       const size_t lds = (size_t)SGTD_SMALL_SLOTS * 16;
-      static const bool lds_set = [&] { return hipFuncSetAttribute(reinterpret_cast<const void *>(&small_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }();
-      if (!lds_set) return SGTD_ERR_HIP;
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&small_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device: before every launch)
       small_order_kernel<<<1, SGTD_SMALL_THREADS, lds, e->stream>>>(v.Q, SO);
       HIPCHK(hipGetLastError());
     } else {
@@ -1530,7 +1535,7 @@ int launch_select(sgtd_engine *e) {
       batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
       HIPCHK(hipGetLastError());
       e->lists_pending = true;
-      e->verified = false; e->refined = false; e->overlapped = false;
+      e->verified = false; e->refined = false; e->overlapped = false; e->aligned = false;
       e->batch_synced = false;
       return SGTD_OK;
     }
@@ -1587,7 +1592,7 @@ int launch_select(sgtd_engine *e) {
     HIPCHK(hipGetLastError());
   }
   e->batch_valid = true;
-  e->verified = false; e->refined = false; e->overlapped = false;
+  e->verified = false; e->refined = false; e->overlapped = false; e->aligned = false;
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -2070,7 +2075,7 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->seg[1].hot, &e->seg[1].perm, &e->seg[1].hash, &e->seg[1].bucket_start, &e->seg[1].bucket_key, &e->seg[1].dir, &e->slice_of, &e->sq_sum,
                     &e->keyA, &e->keyB, &e->valA, &e->valB, &e->hist, &e->digit_tot, &e->flags, &e->bad_flag,
                     &e->kp_off_dev, &e->xyz_dev, &e->label_dev, &e->b_kp_off_dev, &e->b_xyz_dev, &e->b_label_dev, &e->ws_keys, &e->ws_slots, &e->cnt_scan,
-                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->kp_dev, &e->kp_word, &e->o_cnt, &e->o_val, &e->o_qxyz, &e->o_qlabel, &e->o_qoff, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
+                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->kp_dev, &e->kp_word, &e->o_cnt, &e->o_val, &e->o_qxyz, &e->o_qlabel, &e->o_qoff, &e->a_pose, &e->a_fit, &e->a_cnt, &e->a_val, &e->a_mom, &e->a_assign, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
                     &e->votes, &e->slot_of, &e->q_M, &e->q_P, &e->q_pairs, &e->q_pair_base,
                     &e->blk_count, &e->c_pair, &e->c_blk, &e->amb_queue, &e->rec, &e->rec_cell, &e->rec_dis, &e->rough_qi,
                     &e->rough_entry, &e->rough_frame, &e->rough_cell, &e->rough_dis, &e->n_cand, &e->cand_frame,
@@ -2829,7 +2834,7 @@ int sgtd_verify(sgtd_handle e) {
   CHK(sync_batch(e));
   if (!e->batch_valid) return SGTD_ERR_INVALID;
   const int cn = e->dc.cand_num, nq = e->nq;
-  e->refined = false; e->overlapped = false;
+  e->refined = false; e->overlapped = false; e->aligned = false;
   if (nq == 0) { e->verified = true; return SGTD_OK; }
   int64_t total = 0;
   for (int q = 0; q < nq; q++) total = std::max<int64_t>(total, (int64_t)e->h_pair_base[q] + e->h_pair_off[(size_t)q * (cn + 1) + cn]);
@@ -3189,7 +3194,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   }
   stage_times(e);
   e->batch_synced = true;
-  e->verified = !lists_only; e->refined = false; e->overlapped = false;
+  e->verified = !lists_only; e->refined = false; e->overlapped = false; e->aligned = false;
   io->n_cand = (int32_t)w[12];
   if (io->cand_frame) std::memcpy(io->cand_frame, cf, (size_t)cn * 4);
   if (io->cand_votes) std::memcpy(io->cand_votes, cv, (size_t)cn * 4);
@@ -3585,6 +3590,36 @@ static int prepare_keypoints(sgtd_engine *e) {
   return SGTD_OK;
 }
 
+// the query keypoints of an overlap or alignment pass: the caller's host arrays (copied to the handle's o_q* buffers,
+// free at return) or the batch's own.  host_off (or NULL): the nq + 1 offsets, from 0, on the host
+static int stage_query_keypoints(sgtd_engine *e, int nq, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off,
+                                 const float **d_xyz, const u32 **d_label, const long long **d_off, std::vector<long long> *host_off) {
+  if (q_xyz) {
+    std::vector<long long> off((size_t)nq + 1);
+    for (int q = 0; q <= nq; q++) off[(size_t)q] = q_kp_off[q] - q_kp_off[0];
+    const size_t total = (size_t)off[(size_t)nq];
+    CHK(ensure(e, e->o_qoff, off.size() * sizeof(long long)));
+    CHK(ensure(e, e->o_qxyz, std::max<size_t>(total, 1) * 3 * sizeof(float)));
+    CHK(ensure(e, e->o_qlabel, std::max<size_t>(total, 1) * sizeof(u32)));
+    CHK(h2d(e, e->o_qoff.p, off.data(), off.size() * sizeof(long long)));
+    CHK(h2d(e, e->o_qxyz.p, q_xyz + (size_t)q_kp_off[0] * 3, total * 3 * sizeof(float)));
+    CHK(h2d(e, e->o_qlabel.p, q_label + (size_t)q_kp_off[0], total * sizeof(u32)));
+    CHK(xfer_sync(e));          // (the offsets' staging vector and the caller's arrays are free at return)
+    *d_xyz = e->o_qxyz.as<float>(); *d_label = e->o_qlabel.as<u32>(); *d_off = e->o_qoff.as<long long>();
+    if (host_off) host_off->swap(off);
+  } else {
+    *d_xyz = e->last_xyz; *d_label = e->last_label; *d_off = e->kp_off_dev.as<long long>();
+    if (host_off) {
+      host_off->resize((size_t)nq + 1);
+      CHK(d2h(e, host_off->data(), e->kp_off_dev.p, host_off->size() * sizeof(long long)));
+      CHK(xfer_sync(e));
+      const long long o0 = (*host_off)[0];
+      for (long long &o : *host_off) o -= o0;
+    }
+  }
+  return SGTD_OK;
+}
+
 int sgtd_overlap(sgtd_handle e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
   if (!e || !(radius >= 0.0) || std::isinf(radius) || (flags & ~SGTD_OVERLAP_REFINED)) return SGTD_ERR_INVALID;
   if (q_xyz && (!q_label || !q_kp_off)) return SGTD_ERR_INVALID;
@@ -3616,21 +3651,7 @@ int sgtd_overlap(sgtd_handle e, double radius, int flags, const float *q_xyz, co
   P.n_cand = e->n_cand.as<int>(); P.cand_frame = e->cand_frame.as<int>(); P.cand_num = cn;
   P.score = e->v_score.as<double>();
   P.pose = (flags & SGTD_OVERLAP_REFINED) ? e->r_pose.as<double>() : e->v_pose.as<double>();
-  if (q_xyz) {
-    std::vector<long long> off((size_t)nq + 1);
-    for (int q = 0; q <= nq; q++) off[(size_t)q] = q_kp_off[q] - q_kp_off[0];
-    const size_t total = (size_t)off[(size_t)nq];
-    CHK(ensure(e, e->o_qoff, off.size() * sizeof(long long)));
-    CHK(ensure(e, e->o_qxyz, std::max<size_t>(total, 1) * 3 * sizeof(float)));
-    CHK(ensure(e, e->o_qlabel, std::max<size_t>(total, 1) * sizeof(u32)));
-    CHK(h2d(e, e->o_qoff.p, off.data(), off.size() * sizeof(long long)));
-    CHK(h2d(e, e->o_qxyz.p, q_xyz + (size_t)q_kp_off[0] * 3, total * 3 * sizeof(float)));
-    CHK(h2d(e, e->o_qlabel.p, q_label + (size_t)q_kp_off[0], total * sizeof(u32)));
-    CHK(xfer_sync(e));          // (the offsets' staging vector and the caller's arrays are free at return)
-    P.q_xyz = e->o_qxyz.as<float>(); P.q_label = e->o_qlabel.as<u32>(); P.q_off = e->o_qoff.as<long long>();
-  } else {
-    P.q_xyz = e->last_xyz; P.q_label = e->last_label; P.q_off = e->kp_off_dev.as<long long>();
-  }
+  CHK(stage_query_keypoints(e, nq, q_xyz, q_label, q_kp_off, &P.q_xyz, &P.q_label, &P.q_off, nullptr));
   P.kp = e->kp_dev.as<uint4>(); P.f_word = e->kp_word.as<u64>(); P.n_ids = (u32)e->has_kps.size();
   P.hit_off = (u32)overlap_hit_off(e->kp_dev_max);
   P.rr = radius * radius;
@@ -3733,6 +3754,186 @@ int sgtd_search_loop_overlap(sgtd_handle e, double icp_threshold, double min_ove
     if (best_frame) best_frame[q] = ok ? frames[(size_t)q * cn + bc] : -1;
     if (best_score) best_score[q] = ok ? bs : 0.0;
     if (best_overlap) best_overlap[q] = ok ? ov[(size_t)q * cn + bc] : nan;
+  }
+  return SGTD_OK;
+}
+
+// ---- sgtd_align_keypoints: closest-keypoint alignment of the verified candidates (align_kernels.hip.h) ----
+int sgtd_align_keypoints(sgtd_handle e, double radius, int iterations, int flags, const float *q_xyz, const uint32_t *q_label,
+                         const int64_t *q_kp_off) {
+  if (!e || !(radius >= 0.0) || std::isinf(radius) || iterations < 1 || (flags & ~SGTD_ALIGN_REFINED)) return SGTD_ERR_INVALID;
+  if (q_xyz && (!q_label || !q_kp_off)) return SGTD_ERR_INVALID;
+  int nq = 0;
+  if (e->grp) {
+    if (multi::nq_of(e, &nq) != SGTD_OK) { e->err = "sgtd_align_keypoints needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  } else {
+    if (!e->batch_valid || !e->verified) { e->err = "sgtd_align_keypoints needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+    nq = e->nq;
+  }
+  if (q_xyz)
+    for (int q = 0; q < nq; q++) {
+      const int64_t cnt = q_kp_off[q + 1] - q_kp_off[q];
+      if (cnt < 0 || cnt > 65535) return SGTD_ERR_INVALID;
+    }
+  if (e->grp) return multi::align_keypoints(e, radius, iterations, flags, q_xyz, q_label, q_kp_off);
+  if ((flags & SGTD_ALIGN_REFINED) && !e->refined) { e->err = "SGTD_ALIGN_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
+  if (!q_xyz && e->last_kind != 1) { e->err = "the batch has no keypoints of its own (sgtd_query_descs, sgtd_search_frame): pass them to sgtd_align_keypoints"; return SGTD_ERR_STATE; }
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(sync_batch(e));
+  e->aligned = false;
+  const int cn = e->dc.cand_num;
+  if (nq == 0) { e->a_qoff.assign(1, 0); e->aligned = true; return SGTD_OK; }
+  CHK(prepare_keypoints(e));
+  const size_t nb = (size_t)nq * cn;
+  AlignParams P;
+  CHK(stage_query_keypoints(e, nq, q_xyz, q_label, q_kp_off, &P.q_xyz, &P.q_label, &P.q_off, &e->a_qoff));
+  const size_t total = (size_t)e->a_qoff[(size_t)nq];
+  CHK(ensure(e, e->a_pose, nb * 12 * sizeof(double)));
+  CHK(ensure(e, e->a_fit, nb * sizeof(int4)));
+  CHK(ensure(e, e->a_cnt, nb * 2 * sizeof(int4)));
+  CHK(ensure(e, e->a_val, nb * 4 * sizeof(double)));
+  CHK(ensure(e, e->a_mom, nb * 15 * sizeof(double)));
+  CHK(ensure(e, e->a_assign, std::max<size_t>(total * (size_t)cn, 1) * sizeof(int)));
+  P.n_cand = e->n_cand.as<int>(); P.cand_frame = e->cand_frame.as<int>(); P.cand_num = cn;
+  P.score = e->v_score.as<double>();
+  P.pose = (flags & SGTD_ALIGN_REFINED) ? e->r_pose.as<double>() : e->v_pose.as<double>();
+  P.kp = e->kp_dev.as<uint4>(); P.f_word = e->kp_word.as<u64>(); P.n_ids = (u32)e->has_kps.size();
+  P.hit_off = (u32)align_hit_off(e->kp_dev_max); P.asg_off = (u32)align_asg_off(e->kp_dev_max);
+  P.rr = radius * radius;
+  P.iterations = iterations;
+  P.order = nullptr; P.n_blocks = (u32)nb;
+  P.o_pose = e->a_pose.as<double>(); P.fit = e->a_fit.as<int4>(); P.cnt = e->a_cnt.as<int4>(); P.val = e->a_val.as<double>();
+  P.moments = e->a_mom.as<double>(); P.assign = e->a_assign.as<int>();
+  // a batch of many candidates in the order of the candidates' frames, as sgtd_overlap: a frame's keypoints stay in cache
+  if (nb >= 4096 && e->have_frames) {
+    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
+    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
+    const u32 last = e->frame_hi + 1u;
+    verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, (u32)nb, last, kin, vin);
+    HIPCHK(hipGetLastError());
+    int bits = 1;
+    while (bits < 32 && (last >> bits)) bits++;
+    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
+    P.order = vin;
+  }
+  const size_t lds = align_lds_bytes(e->kp_dev_max);
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device)
+  align_kernel<<<(int)nb, SGTD_ALIGN_THREADS, lds, e->stream>>>(P);
+  HIPCHK(hipGetLastError());
+  e->aligned = true;
+  return SGTD_OK;
+}
+
+int sgtd_result_aligned(sgtd_handle e, int q, double *pose, int32_t *n_fits, int32_t *n_corr, int32_t *stop, int32_t *counts_before,
+                        int32_t *counts_after, double *overlap_before, double *rms_before, double *overlap_after, double *rms_after,
+                        double *moments) {
+  PinScope pin_scope(e && !e->grp ? e : nullptr);
+  if (!e) return SGTD_ERR_INVALID;
+  if (e->grp) return multi::result_aligned(e, q, pose, n_fits, n_corr, stop, counts_before, counts_after, overlap_before, rms_before, overlap_after, rms_after, moments);
+  if (!e->batch_valid || !e->verified || !e->aligned) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(view_current(e));
+  const size_t cn = (size_t)e->dc.cand_num, o = (size_t)q * cn;
+  std::vector<int4> fit(cn), cnt(cn * 2);
+  std::vector<double> val(cn * 4);
+  if (pose) CHK(d2h(e, pose, e->a_pose.as<double>() + o * 12, cn * 12 * sizeof(double)));
+  if (moments) CHK(d2h(e, moments, e->a_mom.as<double>() + o * 15, cn * 15 * sizeof(double)));
+  CHK(d2h(e, fit.data(), e->a_fit.as<int4>() + o, cn * sizeof(int4)));
+  CHK(d2h(e, cnt.data(), e->a_cnt.as<int4>() + o * 2, cn * 2 * sizeof(int4)));
+  CHK(d2h(e, val.data(), e->a_val.as<double>() + o * 4, cn * 4 * sizeof(double)));
+  CHK(xfer_sync(e));
+  for (size_t k = 0; k < cn; k++) {
+    if (n_fits) n_fits[k] = fit[k].x;
+    if (n_corr) n_corr[k] = fit[k].y;
+    if (stop) stop[k] = fit[k].z;
+    if (counts_before) std::memcpy(counts_before + k * 4, &cnt[k * 2], sizeof(int4));
+    if (counts_after) std::memcpy(counts_after + k * 4, &cnt[k * 2 + 1], sizeof(int4));
+    if (overlap_before) overlap_before[k] = val[k * 4];
+    if (rms_before) rms_before[k] = val[k * 4 + 1];
+    if (overlap_after) overlap_after[k] = val[k * 4 + 2];
+    if (rms_after) rms_after[k] = val[k * 4 + 3];
+  }
+  return SGTD_OK;
+}
+
+int sgtd_result_aligned_pairs(sgtd_handle e, int q, int cand, int32_t *frame_kp, int64_t capacity, int64_t *n) {
+  PinScope pin_scope(e && !e->grp ? e : nullptr);
+  if (!e || !n) return SGTD_ERR_INVALID;
+  if (e->grp) return multi::result_aligned_pairs(e, q, cand, frame_kp, capacity, n);
+  if (!e->batch_valid || !e->verified || !e->aligned) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(view_current(e));
+  CHK(sync_batch(e));
+  if (cand < 0 || cand >= e->h_n_cand[(size_t)q]) return SGTD_ERR_INVALID;
+  const int64_t nqk = e->a_qoff[(size_t)q + 1] - e->a_qoff[(size_t)q];
+  *n = nqk;
+  const int64_t take = frame_kp ? std::min<int64_t>(nqk, std::max<int64_t>(capacity, 0)) : 0;
+  if (take > 0) {
+    const size_t at = (size_t)e->a_qoff[(size_t)q] * (size_t)e->dc.cand_num + (size_t)cand * (size_t)nqk;
+    CHK(d2h(e, frame_kp, e->a_assign.as<int>() + at, (size_t)take * sizeof(int)));
+    CHK(xfer_sync(e));
+  }
+  return (frame_kp && nqk > capacity) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_aligned_world_poses(sgtd_handle e, int q, float *world) {
+  if (!e || !world) return SGTD_ERR_INVALID;
+  const int cn = e->cfg.candidate_num;
+  std::vector<double> has((size_t)cn), pose((size_t)cn * 12);
+  std::vector<int32_t> stop((size_t)cn);
+  std::vector<int> frames((size_t)cn);
+  int n_cand = 0;
+  CHK(sgtd_result_aligned(e, q, pose.data(), nullptr, nullptr, stop.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  if (e->grp) {
+    CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
+  } else {
+    CHK(sync_batch(e));
+    n_cand = e->h_n_cand[(size_t)q];
+    std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
+  }
+  for (int k = 0; k < cn; k++) has[(size_t)k] = stop[(size_t)k] >= 0 ? 1.0 : -1.0;     // (stop -1: a candidate without a result)
+  world_poses_of(e, n_cand, frames.data(), has.data(), pose.data(), world);
+  return SGTD_OK;
+}
+
+// the lowest registration fitness among the candidates that pass the bounds, in host code over the public results (one
+// rule for single and multi-device handles)
+int sgtd_search_loop_aligned(sgtd_handle e, double min_overlap, double max_rms, int32_t *best_cand, int32_t *best_frame,
+                             double *best_rms, double *best_overlap) {
+  if (!e || std::isnan(min_overlap) || std::isnan(max_rms)) return SGTD_ERR_INVALID;
+  const bool have = e->grp ? multi::has_aligned(e) != 0 : (e->batch_valid && e->verified && e->aligned);
+  if (!have) { e->err = "sgtd_search_loop_aligned needs sgtd_align_keypoints on the pending batch"; return SGTD_ERR_STATE; }
+  const int cn = e->cfg.candidate_num;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const bool gate_ov = min_overlap > 0.0, gate_rms = max_rms > 0.0 && !std::isinf(max_rms);
+  int nq = 0;
+  if (e->grp) CHK(multi::nq_of(e, &nq)); else nq = e->nq;
+  std::vector<double> score((size_t)cn), ov((size_t)cn), rms((size_t)cn);
+  std::vector<int32_t> stop((size_t)cn);
+  std::vector<int> frames((size_t)cn);
+  for (int q = 0; q < nq; q++) {
+    int n_cand = 0;
+    CHK(sgtd_result_verify(e, q, score.data(), nullptr));
+    CHK(sgtd_result_aligned(e, q, nullptr, nullptr, nullptr, stop.data(), nullptr, nullptr, nullptr, nullptr, ov.data(), rms.data(), nullptr));
+    if (e->grp) {
+      CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
+    } else {
+      n_cand = e->h_n_cand[(size_t)q];
+      std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
+    }
+    int bc = -1;
+    for (int c = 0; c < n_cand; c++) {
+      if (stop[(size_t)c] < 0 || std::isnan(rms[(size_t)c])) continue;
+      if (gate_ov && !(ov[(size_t)c] >= min_overlap)) continue;         // (NaN: left out)
+      if (gate_rms && !(rms[(size_t)c] <= max_rms)) continue;
+      if (bc < 0 || rms[(size_t)c] < rms[(size_t)bc] || (rms[(size_t)c] == rms[(size_t)bc] && score[(size_t)c] > score[(size_t)bc])) bc = c;
+    }
+    if (best_cand) best_cand[q] = bc;
+    if (best_frame) best_frame[q] = bc >= 0 ? frames[(size_t)bc] : -1;
+    if (best_rms) best_rms[q] = bc >= 0 ? rms[(size_t)bc] : nan;
+    if (best_overlap) best_overlap[q] = bc >= 0 ? ov[(size_t)bc] : nan;
   }
   return SGTD_OK;
 }

@@ -104,7 +104,7 @@ def frames_near(map_xy, prior_xy, radius):
 
 
 def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=None, kp_off=None, allowed=None, prior=None,
-                   refine=0, min_overlap=0.0, overlap_radius=1.0):
+                   refine=0, min_overlap=0.0, overlap_radius=1.0, align=0.0, align_iterations=10):
     """SearchLoop for a batch of query frames on the device + the node's accounting.
     map_pose4[f] = 4x4 pose of map frame f; query_pose4[q] = ground truth of query q.
     allowed: a frame filter for the batch (STDescManager.set_frame_filter; e.g. frames_near of position priors).
@@ -114,24 +114,37 @@ def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=
     choice itself and the candidate ranks are not touched).
     min_overlap: 0 = SearchLoop's choice (today's accounting); > 0 = STDescManager.overlap(overlap_radius) after the
     verification (the map's keypoints stored: add_frames(keep_keypoints=True) / set_frame_keypoints) and the detection
-    is search_loop_overlap's: the best-scored candidate among those whose keypoint overlap reaches min_overlap."""
+    is search_loop_overlap's: the best-scored candidate among those whose keypoint overlap reaches min_overlap.
+    align: 0 = off (today's accounting); a radius > 0 = STDescManager.align_keypoints(align, align_iterations) after the
+    verification (from the refined pose when refine > 0; the map's keypoints stored), the detection is
+    search_loop_aligned's — the candidate with the lowest rms_after among those whose overlap_after reaches min_overlap —
+    and the localization error is accounted with its aligned pose."""
     if metrics is None:
         metrics = LoopMetrics(mgr.config_setting_["candidate_num"])
     res = mgr.query_frames(query_xyz, query_label, kp_off, allowed=allowed, prior=prior)
     mgr.verify()
-    if min_overlap > 0:
+    if align > 0:
+        bs = None
+        if refine:
+            mgr.refine_poses(refine)
+        mgr.align_keypoints(align, iterations=align_iterations, refined=bool(refine))
+        bc, bf, _, _ = mgr.search_loop_aligned(min_overlap)
+    elif min_overlap > 0:
         mgr.overlap(overlap_radius)
         bc, bf, bs, _ = mgr.search_loop_overlap(min_overlap)
     else:
         bc, bf, bs = mgr.search_loop()
-    if refine:
+    if refine and not align > 0:
         mgr.refine_poses(refine)
     for q in range(len(bf)):
         n_c = int(res.n_cand[q])
         if bf[q] > 0:
             score, rot, t = mgr.result_verify(q)
             k = int(bc[q])
-            if refine:
+            if align > 0:
+                r = mgr.result_aligned(q)
+                rot, t = r["rot"], r["t"]
+            elif refine:
                 r = mgr.result_refined(q)
                 rot, t = r["rot"], r["t"]
             account(metrics, query_pose4[q], map_pose4, int(bf[q]), rot[k], t[k], res.cand_frame[q, :n_c], score[:n_c])

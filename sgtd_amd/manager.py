@@ -728,6 +728,95 @@ class STDescManager:
         self._check(self._L.sgtd_search_loop_overlap(self._h, float(icp_threshold), float(min_overlap), _p(bc), _p(bf), _p(bs), _p(bo)))
         return bc, bf, bs, bo
 
+    def align_keypoints(self, radius, iterations=10, refined=False, xyz=None, label=None, kp_off=None):
+        """sgtd_align_keypoints after verify(): for every verified candidate, assign each query keypoint to the nearest
+        keypoint of its label of the candidate's frame within `radius` (set_frame_keypoints /
+        add_frames(keep_keypoints=True)), refit the pose over the assigned pairs, and repeat up to `iterations` times or
+        until the assignment stays.  refined=True starts from refine_poses()'s pose.  xyz=None: the batch's own keypoints
+        (query_frames, loop_frames); otherwise xyz / label (and kp_off, or xyz (n_queries, N, 3)) for every query."""
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+            raise TypeError("radius: a number")
+        radius = float(radius)
+        if not (radius >= 0.0) or np.isinf(radius):
+            raise ValueError("radius: finite, not negative")
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)):
+            raise TypeError("iterations: an integer")
+        if iterations < 1:
+            raise ValueError("iterations: at least 1")
+        flags = 1 if refined else 0
+        if xyz is None:
+            if label is not None or kp_off is not None:
+                raise ValueError("label and kp_off come with xyz")
+            self._check(self._L.sgtd_align_keypoints(self._h, radius, int(iterations), flags, None, None, None))
+            return
+        if label is None:
+            raise ValueError("keypoints need their labels")
+        x, l, off = self._keypoint_args(xyz, label, kp_off, self._nq, "query")
+        self._check(self._L.sgtd_align_keypoints(self._h, radius, int(iterations), flags, _p(x), _p(l), _p(off)))
+
+    def result_aligned(self, q):
+        """sgtd_result_aligned of query q after align_keypoints(): a dict of rot [candidate_num, 3, 3], t [candidate_num, 3]
+        (the aligned pose), n_fits, n_corr, stop [candidate_num] (int32; stop 0 = out of iterations, 1 = fewer than 3
+        assigned, 2 = converged, -1 = no verification result), counts_before / counts_after [candidate_num, 4] (int32:
+        n_query_kp, n_frame_kp, n_hit_query, n_hit_frame of result_overlap's rule under the start / the aligned pose),
+        overlap_before, rms_before, overlap_after, rms_after [candidate_num] and moments [candidate_num, 15] (cp, cw, H
+        of the last fit)"""
+        q = self._query_index(q)
+        cn = self.config_setting_["candidate_num"]
+        pose = np.zeros((cn, 12), np.float64)
+        out = {k: np.zeros(cn, np.int32) for k in ("n_fits", "n_corr", "stop")}
+        out["counts_before"] = np.zeros((cn, 4), np.int32)
+        out["counts_after"] = np.zeros((cn, 4), np.int32)
+        for k in ("overlap_before", "rms_before", "overlap_after", "rms_after"):
+            out[k] = np.zeros(cn, np.float64)
+        out["moments"] = np.zeros((cn, 15), np.float64)
+        self._check(self._L.sgtd_result_aligned(self._h, q, _p(pose), _p(out["n_fits"]), _p(out["n_corr"]), _p(out["stop"]),
+                                                _p(out["counts_before"]), _p(out["counts_after"]), _p(out["overlap_before"]),
+                                                _p(out["rms_before"]), _p(out["overlap_after"]), _p(out["rms_after"]),
+                                                _p(out["moments"])))
+        out["rot"] = pose[:, :9].reshape(cn, 3, 3).copy()
+        out["t"] = pose[:, 9:].copy()
+        return out
+
+    def result_aligned_pairs(self, q, cand):
+        """sgtd_result_aligned_pairs: the frame keypoint every keypoint of query q is assigned to under candidate cand's
+        aligned pose, -1 where none (int32, one entry per query keypoint)"""
+        q = self._query_index(q)
+        if isinstance(cand, bool) or not isinstance(cand, (int, np.integer)):
+            raise TypeError("cand: an integer")
+        if cand < 0:
+            raise ValueError("cand: not negative")
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_aligned_pairs(self._h, q, int(cand), None, 0, C.byref(n)))
+        a = np.zeros(max(int(n.value), 1), np.int32)
+        self._check(self._L.sgtd_result_aligned_pairs(self._h, q, int(cand), _p(a), len(a), C.byref(n)))
+        return a[:n.value].copy()
+
+    def result_aligned_world_poses(self, q):
+        """sgtd_result_aligned_world_poses after align_keypoints(): result_world_poses with the aligned relative poses"""
+        q = self._query_index(q)
+        cn = self.config_setting_["candidate_num"]
+        w = np.zeros((cn, 12), np.float32)
+        self._check(self._L.sgtd_result_aligned_world_poses(self._h, q, _p(w)))
+        return w
+
+    def search_loop_aligned(self, min_overlap=0.0, max_rms=0.0):
+        """sgtd_search_loop_aligned after align_keypoints(): per query the candidate with the smallest rms_after among
+        those with overlap_after >= min_overlap (<= 0: no bound) and rms_after <= max_rms (<= 0 or inf: no bound) ->
+        (best_cand, best_frame, best_rms, best_overlap); -1, -1, NaN, NaN where nothing qualifies"""
+        for name, v in (("min_overlap", min_overlap), ("max_rms", max_rms)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(name + ": a number")
+            if np.isnan(v):
+                raise ValueError(name + ": not NaN")
+        nq = self._nq
+        bc = np.zeros(nq, np.int32)
+        bf = np.zeros(nq, np.int32)
+        br = np.zeros(nq, np.float64)
+        bo = np.zeros(nq, np.float64)
+        self._check(self._L.sgtd_search_loop_aligned(self._h, float(min_overlap), float(max_rms), _p(bc), _p(bf), _p(br), _p(bo)))
+        return bc, bf, br, bo
+
     def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None, prior=None):
         """sgtd_search_frame: candidate_selector + candidate_verify + the inlier pairs of every candidate with their table
         entries for ONE query frame given as descriptors, in one call -> dict(n_cand, cand_frame, cand_votes, pair_off,
