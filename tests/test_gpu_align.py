@@ -267,6 +267,8 @@ def test_edges_on_constructed_frames(mods, world):
             tally = {}
             _check_query(g, n_cand, cand_frame, 0, radius, iterations, False, q_xyz, lab, lambda f: frames[f], (n, radius, iterations), tally)
             assert tally["fragile"] <= 1, (n, radius, tally["fragile"])
+            n_verified += tally["verified"]
+            n_fragile += tally["fragile"] + tally["collinear"]
             seen_stops |= {(iterations, e["stop"]) for e in tally["results"]}
             fits += [e["n_fits"] for e in tally["results"]]
             if radius == 0.0:
