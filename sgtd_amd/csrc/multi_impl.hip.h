@@ -14,6 +14,52 @@ static inline Group *G(sgtd_engine *e) { return e->grp; }
     }                                  \
   } while (0)
 
+// as sgtd_accel.hip's two, for the group's own flags
+static void stale_stages(Group *g) { g->refined = false; g->overlapped = false; g->aligned = false; }
+static void new_results(Group *g, bool verified) { g->verified = verified; stale_stages(g); }
+
+// A stage on a verified batch, on every owner: the state checks with the texts of the single-device entry points (`stage`:
+// the entry point's name; refined_flag: the name of the flag that asks for the refit's poses, or NULL), the stage's
+// results (*done) gone while the devices run
+template <class Call>
+static int fan_out(sgtd_engine *e, const char *stage, const char *refined_flag, bool *done, Call call) {
+  Group *g = G(e);
+  if (!g->batch_valid || !g->verified) return needs(e, stage, "sgtd_verify");
+  if (refined_flag && !g->refined) return needs(e, refined_flag, "sgtd_refine_poses");
+  *done = false;
+  for (sgtd_engine *c : g->dev) MCHK(call(c));
+  *done = true;
+  return SGTD_OK;
+}
+
+// a stage's getter of query q on a group: the stage has run on the pending batch (`missing` says what has not), q is one
+// of its queries
+static int group_result_ready(sgtd_engine *e, int q, bool done, const char *missing) {
+  Group *g = G(e);
+  if (!g->batch_valid || !g->verified || !done) { e->err = missing; return SGTD_ERR_STATE; }
+  return (q < 0 || q >= g->nq) ? SGTD_ERR_INVALID : SGTD_OK;
+}
+
+// Query q's merged candidates, each from the device that owns it: fetch(c, s) brings what owner s (the engine c) has for
+// the query, once, before copy(s, ks, k) first copies from it: the owner's slot ks to the merged slot k
+template <class Fetch, class Copy>
+static int gather(sgtd_engine *e, int q, Fetch fetch, Copy copy) {
+  Group *g = G(e);
+  const int cn = e->cfg.candidate_num;
+  std::vector<char> have((size_t)g->n, 0);
+  for (int k = 0; k < g->n_cand[q]; k++) {
+    const size_t i = (size_t)q * cn + k;
+    const int s = g->owner[i];
+    if (!have[(size_t)s]) {
+      sgtd_engine *c = g->dev[s];
+      MCHK(fetch(c, s));
+      have[(size_t)s] = 1;
+    }
+    copy(s, g->owner_slot[i], k);
+  }
+  return SGTD_OK;
+}
+
 int create(const sgtd_config *cfg, const int *device_ids, int n_dev, sgtd_handle *out) {
   if (!cfg || !out || !device_ids || n_dev < 1 || n_dev > 64) return SGTD_ERR_INVALID;
   *out = nullptr;
@@ -245,7 +291,7 @@ int query_frames(sgtd_engine *e, const float *xyz, const uint32_t *label, const 
   // every device builds the query descriptors itself and sweeps its shard; the calls only
   // enqueue, so the devices run concurrently
   for (sgtd_engine *c : g->dev) MCHK(sgtd_query_frames(c, xyz, label, kp_off, n_queries, 0));
-  g->nq = n_queries; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false; g->aligned = false;
+  g->nq = n_queries; g->batch_valid = true; g->merged = false; new_results(g, false);
   return SGTD_OK;
 }
 
@@ -267,7 +313,7 @@ int query_descs(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq) {
     t.frame = lf.data();
     MCHK(sgtd_query_descs(c, &t, nq));
   }
-  g->nq = 1; g->batch_valid = true; g->merged = false; g->verified = false; g->refined = false; g->overlapped = false; g->aligned = false;
+  g->nq = 1; g->batch_valid = true; g->merged = false; new_results(g, false);
   return SGTD_OK;
 }
 
@@ -352,28 +398,22 @@ int result_pairs(sgtd_engine *e, int q, int32_t *q_idx, int64_t *db_entry, int64
   if (total > capacity) return SGTD_ERR_CAPACITY;
   std::vector<std::vector<int32_t>> qi(g->n);
   std::vector<std::vector<int64_t>> en(g->n), off(g->n);
-  std::vector<bool> have(g->n, false);
-  for (int k = 0; k < g->n_cand[q]; k++) {
-    const size_t i = (size_t)q * cn + k;
-    const int s = g->owner[i], ks = g->owner_slot[i];
-    sgtd_engine *c = g->dev[s];
-    if (!have[s]) {   // the owner's lists of this query, once
-      off[s].resize((size_t)g->nq * (cn + 1));
-      MCHK(sgtd_result_candidates(c, nullptr, nullptr, nullptr, off[s].data()));
-      const int64_t ts = off[s][(size_t)q * (cn + 1) + cn];
-      qi[s].resize((size_t)std::max<int64_t>(ts, 1)); en[s].resize((size_t)std::max<int64_t>(ts, 1));
-      int64_t got = 0;
-      MCHK(sgtd_result_pairs(c, q, qi[s].data(), en[s].data(), ts, &got));
-      have[s] = true;
-    }
+  return gather(e, q, [&](sgtd_engine *c, int s) {   // the owner's lists of this query
+    off[s].resize((size_t)g->nq * (cn + 1));
+    MCHK(sgtd_result_candidates(c, nullptr, nullptr, nullptr, off[s].data()));
+    const int64_t ts = off[s][(size_t)q * (cn + 1) + cn];
+    qi[s].resize((size_t)std::max<int64_t>(ts, 1)); en[s].resize((size_t)std::max<int64_t>(ts, 1));
+    int64_t got = 0;
+    MCHK(sgtd_result_pairs(c, q, qi[s].data(), en[s].data(), ts, &got));
+    return (int)SGTD_OK;
+  }, [&](int s, int ks, int k) {
     const int64_t lo = off[s][(size_t)q * (cn + 1) + ks], hi = off[s][(size_t)q * (cn + 1) + ks + 1];
-    int64_t o = g->pair_off[i + (size_t)q];   // = pair_off[q * (cn + 1) + k]
+    int64_t o = g->pair_off[(size_t)q * (cn + 1) + k];
     for (int64_t r = lo; r < hi; r++, o++) {
       if (q_idx) q_idx[o] = qi[s][(size_t)r];
       if (db_entry) db_entry[o] = ((int64_t)s << SGTD_ENTRY_SHARD_SHIFT) | en[s][(size_t)r];
     }
-  }
-  return SGTD_OK;
+  });
 }
 
 int fetch_entries(sgtd_engine *e, const int64_t *db_entry, int64_t n, sgtd_desc_soa *out) {
@@ -441,7 +481,7 @@ int result_votes(sgtd_engine *e, int q, uint32_t *votes, int64_t capacity, uint3
 int verify(sgtd_engine *e) {
   Group *g = G(e);
   CHK(merge(e));
-  g->refined = false; g->overlapped = false; g->aligned = false;
+  stale_stages(g);
   for (sgtd_engine *c : g->dev) MCHK(sgtd_verify(c));   // every owner verifies its local candidates
   g->verified = true;
   return SGTD_OK;
@@ -456,35 +496,24 @@ int result_verify(sgtd_engine *e, int q, double *score, double *pose) {
     if (score) score[k] = -1.0;
     if (pose) std::fill(pose + (size_t)k * 12, pose + (size_t)k * 12 + 12, 0.0);
   }
-  for (int k = 0; k < g->n_cand[q]; k++) {
-    const size_t i = (size_t)q * cn + k;
-    const int s = g->owner[i], ks = g->owner_slot[i];
-    sgtd_engine *c = g->dev[s];
-    if (ss[s].empty()) {
-      ss[s].resize(cn); pp[s].resize((size_t)cn * 12);
-      MCHK(sgtd_result_verify(c, q, ss[s].data(), pp[s].data()));
-    }
+  return gather(e, q, [&](sgtd_engine *c, int s) {
+    ss[s].resize(cn); pp[s].resize((size_t)cn * 12);
+    return sgtd_result_verify(c, q, ss[s].data(), pp[s].data());
+  }, [&](int s, int ks, int k) {
     if (score) score[k] = ss[s][ks];
     if (pose) std::copy(pp[s].begin() + (size_t)ks * 12, pp[s].begin() + (size_t)ks * 12 + 12, pose + (size_t)k * 12);
-  }
-  return SGTD_OK;
+  });
 }
 
 // every owner refits the poses of its local candidates
 int refine_poses(sgtd_engine *e, int iterations) {
-  Group *g = G(e);
-  if (!g->batch_valid || !g->verified) { e->err = "sgtd_refine_poses needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  g->refined = false;
-  for (sgtd_engine *c : g->dev) MCHK(sgtd_refine_poses(c, iterations));
-  g->refined = true;
-  return SGTD_OK;
+  return fan_out(e, "sgtd_refine_poses", nullptr, &G(e)->refined, [&](sgtd_engine *c) { return sgtd_refine_poses(c, iterations); });
 }
 
-// the refined results of query q's merged candidates, each from its owner (result_verify's pattern)
+// the refined results of query q's merged candidates
 int result_refined(sgtd_engine *e, int q, double *pose, double *rmse, double *rmse_verify, int32_t *n_pairs, double *moments) {
   Group *g = G(e);
-  if (!g->batch_valid || !g->verified || !g->refined) { e->err = "no refined poses: sgtd_refine_poses comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  CHK(group_result_ready(e, q, g->refined, kNoRefined));
   const int cn = e->cfg.candidate_num;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   struct Owned { std::vector<double> pose, rmse, rmse_v, mom; std::vector<int32_t> np; };
@@ -496,22 +525,18 @@ int result_refined(sgtd_engine *e, int q, double *pose, double *rmse, double *rm
     if (n_pairs) n_pairs[k] = 0;
     if (moments) std::fill(moments + (size_t)k * 15, moments + (size_t)k * 15 + 15, nan);
   }
-  for (int k = 0; k < g->n_cand[q]; k++) {
-    const size_t i = (size_t)q * cn + k;
-    const int s = g->owner[i], ks = g->owner_slot[i];
+  return gather(e, q, [&](sgtd_engine *c, int s) {
     Owned &o = own[s];
-    if (o.np.empty()) {
-      sgtd_engine *c = g->dev[s];
-      o.pose.resize((size_t)cn * 12); o.rmse.resize(cn); o.rmse_v.resize(cn); o.mom.resize((size_t)cn * 15); o.np.resize(cn);
-      MCHK(sgtd_result_refined(c, q, o.pose.data(), o.rmse.data(), o.rmse_v.data(), o.np.data(), o.mom.data()));
-    }
+    o.pose.resize((size_t)cn * 12); o.rmse.resize(cn); o.rmse_v.resize(cn); o.mom.resize((size_t)cn * 15); o.np.resize(cn);
+    return sgtd_result_refined(c, q, o.pose.data(), o.rmse.data(), o.rmse_v.data(), o.np.data(), o.mom.data());
+  }, [&](int s, int ks, int k) {
+    const Owned &o = own[s];
     if (pose) std::copy(o.pose.begin() + (size_t)ks * 12, o.pose.begin() + (size_t)ks * 12 + 12, pose + (size_t)k * 12);
     if (rmse) rmse[k] = o.rmse[ks];
     if (rmse_verify) rmse_verify[k] = o.rmse_v[ks];
     if (n_pairs) n_pairs[k] = o.np[ks];
     if (moments) std::copy(o.mom.begin() + (size_t)ks * 15, o.mom.begin() + (size_t)ks * 15 + 15, moments + (size_t)k * 15);
-  }
-  return SGTD_OK;
+  });
 }
 
 int nq_of(sgtd_engine *e, int *nq) {
@@ -528,20 +553,14 @@ int has_overlap(sgtd_engine *e) {
 
 // every owner computes the overlap of its local candidates (the checks ran in sgtd_overlap)
 int overlap(sgtd_engine *e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
-  Group *g = G(e);
-  if (!g->batch_valid || !g->verified) { e->err = "sgtd_overlap needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if ((flags & SGTD_OVERLAP_REFINED) && !g->refined) { e->err = "SGTD_OVERLAP_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
-  g->overlapped = false;
-  for (sgtd_engine *c : g->dev) MCHK(sgtd_overlap(c, radius, flags, q_xyz, q_label, q_kp_off));
-  g->overlapped = true;
-  return SGTD_OK;
+  return fan_out(e, "sgtd_overlap", (flags & SGTD_OVERLAP_REFINED) ? "SGTD_OVERLAP_REFINED" : nullptr, &G(e)->overlapped,
+                 [&](sgtd_engine *c) { return sgtd_overlap(c, radius, flags, q_xyz, q_label, q_kp_off); });
 }
 
-// the overlap results of query q's merged candidates, each from its owner (result_refined's pattern)
+// the overlap results of query q's merged candidates
 int result_overlap(sgtd_engine *e, int q, int32_t *n_query_kp, int32_t *n_frame_kp, int32_t *n_hit_query, int32_t *n_hit_frame, double *overlap, double *rms) {
   Group *g = G(e);
-  if (!has_overlap(e)) { e->err = "no overlap results: sgtd_overlap comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  CHK(group_result_ready(e, q, g->overlapped, kNoOverlap));
   const int cn = e->cfg.candidate_num;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   struct Owned { std::vector<int32_t> c[4]; std::vector<double> ov, rms; };
@@ -552,21 +571,17 @@ int result_overlap(sgtd_engine *e, int q, int32_t *n_query_kp, int32_t *n_frame_
     if (overlap) overlap[k] = nan;
     if (rms) rms[k] = nan;
   }
-  for (int k = 0; k < g->n_cand[q]; k++) {
-    const size_t i = (size_t)q * cn + k;
-    const int s = g->owner[i], ks = g->owner_slot[i];
+  return gather(e, q, [&](sgtd_engine *c, int s) {
     Owned &o = own[s];
-    if (o.ov.empty()) {
-      sgtd_engine *c = g->dev[s];
-      for (int a = 0; a < 4; a++) o.c[a].resize(cn);
-      o.ov.resize(cn); o.rms.resize(cn);
-      MCHK(sgtd_result_overlap(c, q, o.c[0].data(), o.c[1].data(), o.c[2].data(), o.c[3].data(), o.ov.data(), o.rms.data()));
-    }
+    for (int a = 0; a < 4; a++) o.c[a].resize(cn);
+    o.ov.resize(cn); o.rms.resize(cn);
+    return sgtd_result_overlap(c, q, o.c[0].data(), o.c[1].data(), o.c[2].data(), o.c[3].data(), o.ov.data(), o.rms.data());
+  }, [&](int s, int ks, int k) {
+    const Owned &o = own[s];
     for (int a = 0; a < 4; a++) if (out[a]) out[a][k] = o.c[a][ks];
     if (overlap) overlap[k] = o.ov[ks];
     if (rms) rms[k] = o.rms[ks];
-  }
-  return SGTD_OK;
+  });
 }
 
 int has_aligned(sgtd_engine *e) {
@@ -576,21 +591,15 @@ int has_aligned(sgtd_engine *e) {
 
 // every owner aligns its local candidates (the checks ran in sgtd_align_keypoints)
 int align_keypoints(sgtd_engine *e, double radius, int iterations, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
-  Group *g = G(e);
-  if (!g->batch_valid || !g->verified) { e->err = "sgtd_align_keypoints needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if ((flags & SGTD_ALIGN_REFINED) && !g->refined) { e->err = "SGTD_ALIGN_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
-  g->aligned = false;
-  for (sgtd_engine *c : g->dev) MCHK(sgtd_align_keypoints(c, radius, iterations, flags, q_xyz, q_label, q_kp_off));
-  g->aligned = true;
-  return SGTD_OK;
+  return fan_out(e, "sgtd_align_keypoints", (flags & SGTD_ALIGN_REFINED) ? "SGTD_ALIGN_REFINED" : nullptr, &G(e)->aligned,
+                 [&](sgtd_engine *c) { return sgtd_align_keypoints(c, radius, iterations, flags, q_xyz, q_label, q_kp_off); });
 }
 
-// the aligned results of query q's merged candidates, each from its owner (result_refined's pattern)
+// the aligned results of query q's merged candidates
 int result_aligned(sgtd_engine *e, int q, double *pose, int32_t *n_fits, int32_t *n_corr, int32_t *stop, int32_t *counts_before, int32_t *counts_after,
                    double *overlap_before, double *rms_before, double *overlap_after, double *rms_after, double *moments) {
   Group *g = G(e);
-  if (!has_aligned(e)) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= g->nq) return SGTD_ERR_INVALID;
+  CHK(group_result_ready(e, q, g->aligned, kNoAligned));
   const int cn = e->cfg.candidate_num;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   struct Owned { std::vector<double> pose, mom, val[4]; std::vector<int32_t> fit[3], cnt[2]; };
@@ -604,32 +613,28 @@ int result_aligned(sgtd_engine *e, int q, double *pose, int32_t *n_fits, int32_t
     for (int a = 0; a < 2; a++) if (cnt[a]) std::fill(cnt[a] + (size_t)k * 4, cnt[a] + (size_t)k * 4 + 4, -1);
     for (int a = 0; a < 4; a++) if (val[a]) val[a][k] = nan;
   }
-  for (int k = 0; k < g->n_cand[q]; k++) {
-    const size_t i = (size_t)q * cn + k;
-    const int s = g->owner[i], ks = g->owner_slot[i];
+  return gather(e, q, [&](sgtd_engine *c, int s) {
     Owned &o = own[s];
-    if (o.pose.empty()) {
-      sgtd_engine *c = g->dev[s];
-      o.pose.resize((size_t)cn * 12); o.mom.resize((size_t)cn * 15);
-      for (int a = 0; a < 4; a++) o.val[a].resize(cn);
-      for (int a = 0; a < 3; a++) o.fit[a].resize(cn);
-      for (int a = 0; a < 2; a++) o.cnt[a].resize((size_t)cn * 4);
-      MCHK(sgtd_result_aligned(c, q, o.pose.data(), o.fit[0].data(), o.fit[1].data(), o.fit[2].data(), o.cnt[0].data(), o.cnt[1].data(),
-                               o.val[0].data(), o.val[1].data(), o.val[2].data(), o.val[3].data(), o.mom.data()));
-    }
+    o.pose.resize((size_t)cn * 12); o.mom.resize((size_t)cn * 15);
+    for (int a = 0; a < 4; a++) o.val[a].resize(cn);
+    for (int a = 0; a < 3; a++) o.fit[a].resize(cn);
+    for (int a = 0; a < 2; a++) o.cnt[a].resize((size_t)cn * 4);
+    return sgtd_result_aligned(c, q, o.pose.data(), o.fit[0].data(), o.fit[1].data(), o.fit[2].data(), o.cnt[0].data(), o.cnt[1].data(),
+                               o.val[0].data(), o.val[1].data(), o.val[2].data(), o.val[3].data(), o.mom.data());
+  }, [&](int s, int ks, int k) {
+    const Owned &o = own[s];
     if (pose) std::copy(o.pose.begin() + (size_t)ks * 12, o.pose.begin() + (size_t)ks * 12 + 12, pose + (size_t)k * 12);
     if (moments) std::copy(o.mom.begin() + (size_t)ks * 15, o.mom.begin() + (size_t)ks * 15 + 15, moments + (size_t)k * 15);
     for (int a = 0; a < 3; a++) if (fit[a]) fit[a][k] = o.fit[a][ks];
     for (int a = 0; a < 2; a++) if (cnt[a]) std::copy(o.cnt[a].begin() + (size_t)ks * 4, o.cnt[a].begin() + (size_t)ks * 4 + 4, cnt[a] + (size_t)k * 4);
     for (int a = 0; a < 4; a++) if (val[a]) val[a][k] = o.val[a][ks];
-  }
-  return SGTD_OK;
+  });
 }
 
 int result_aligned_pairs(sgtd_engine *e, int q, int cand, int32_t *frame_kp, int64_t capacity, int64_t *n) {
   Group *g = G(e);
-  if (!has_aligned(e)) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= g->nq || cand < 0 || cand >= g->n_cand[q]) return SGTD_ERR_INVALID;
+  CHK(group_result_ready(e, q, g->aligned, kNoAligned));
+  if (cand < 0 || cand >= g->n_cand[q]) return SGTD_ERR_INVALID;
   const size_t i = (size_t)q * e->cfg.candidate_num + cand;
   sgtd_engine *c = g->dev[g->owner[i]];
   MCHK(sgtd_result_aligned_pairs(c, q, g->owner_slot[i], frame_kp, capacity, n));
@@ -652,23 +657,17 @@ int result_inlier_pairs(sgtd_engine *e, int q, int64_t *cand_off, int32_t *q_idx
   const int cn = e->cfg.candidate_num;
   std::vector<std::vector<int32_t>> qi(g->n);
   std::vector<std::vector<int64_t>> en(g->n), off(g->n);
-  std::vector<bool> have(g->n, false);
   int64_t o = 0;
   bool fits = true;
   for (int k = 0; k <= cn; k++) cand_off[k] = 0;
-  for (int k = 0; k < g->n_cand[q]; k++) {
-    const size_t i = (size_t)q * cn + k;
-    const int s = g->owner[i], ks = g->owner_slot[i];
-    if (!have[s]) {   // the owner's inlier pairs of this query, once
-      sgtd_engine *c = g->dev[s];
-      off[s].resize((size_t)cn + 1);
-      int64_t ns = 0;
-      int st = sgtd_result_inlier_pairs(c, q, off[s].data(), nullptr, nullptr, 0, &ns);
-      if (st != SGTD_OK && st != SGTD_ERR_CAPACITY) MCHK(st);
-      qi[s].resize((size_t)std::max<int64_t>(ns, 1)); en[s].resize((size_t)std::max<int64_t>(ns, 1));
-      MCHK(sgtd_result_inlier_pairs(c, q, off[s].data(), qi[s].data(), en[s].data(), ns, &ns));
-      have[s] = true;
-    }
+  CHK(gather(e, q, [&](sgtd_engine *c, int s) {   // the owner's inlier pairs of this query: how many, then the pairs
+    off[s].resize((size_t)cn + 1);
+    int64_t ns = 0;
+    const int st = sgtd_result_inlier_pairs(c, q, off[s].data(), nullptr, nullptr, 0, &ns);
+    if (st != SGTD_OK && st != SGTD_ERR_CAPACITY) return st;
+    qi[s].resize((size_t)std::max<int64_t>(ns, 1)); en[s].resize((size_t)std::max<int64_t>(ns, 1));
+    return sgtd_result_inlier_pairs(c, q, off[s].data(), qi[s].data(), en[s].data(), ns, &ns);
+  }, [&](int s, int ks, int k) {
     cand_off[k] = o;
     for (int64_t r = off[s][(size_t)ks]; r < off[s][(size_t)ks + 1]; r++, o++) {
       if (o < capacity) {
@@ -676,7 +675,7 @@ int result_inlier_pairs(sgtd_engine *e, int q, int64_t *cand_off, int32_t *q_idx
         if (db_entry) db_entry[o] = ((int64_t)s << SGTD_ENTRY_SHARD_SHIFT) | en[s][(size_t)r];
       } else fits = false;
     }
-  }
+  }));
   for (int k = g->n_cand[q]; k <= cn; k++) cand_off[k] = o;
   *n_pairs = o;
   return fits ? SGTD_OK : SGTD_ERR_CAPACITY;

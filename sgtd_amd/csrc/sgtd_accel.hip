@@ -336,6 +336,12 @@ namespace {
     if (_r != SGTD_OK) return _r; \
   } while (0)
 
+// what the stages on a verified batch left (sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints) belongs to the
+// verification before this one
+void stale_stages(sgtd_engine *e) { e->refined = false; e->overlapped = false; e->aligned = false; }
+// the batch's candidates or lists are new: so is, or will be, everything after them
+void new_results(sgtd_engine *e, bool verified) { e->verified = verified; stale_stages(e); }
+
 int ensure(sgtd_engine *e, DevBuf &b, size_t bytes, bool keep = false) {
   if (bytes <= b.bytes) return SGTD_OK;
   if (b.borrowed) { e->err = "a table attached from another handle cannot grow here"; return SGTD_ERR_STATE; }
@@ -508,11 +514,15 @@ int device_scan(sgtd_engine *e, const u32 *in, u32 *out, long long n, size_t lvl
 // ---------------------------------------------------------------------------
 // BuildSingleScanSTD launch for a batch of frames (inputs already on device)
 // ---------------------------------------------------------------------------
+// keypoints of one frame: the kernels keep a frame's keypoint indices and counts in 16 bits
+constexpr int kMaxKeypoints = 65535;
+bool keypoint_count_ok(long long n) { return n >= 0 && n <= kMaxKeypoints; }
+
 int launch_build(sgtd_engine *e, const float *d_xyz, const u32 *d_label, const long long *d_kp_off,
                  int n_frames, int max_n, u32 frame_id0, int frame_step, DescArrays out,
                  long long out_stride, u32 *out_count) {
   if (n_frames <= 0) return SGTD_OK;
-  if (max_n > 65535) return SGTD_ERR_UNSUPPORTED;
+  if (max_n > kMaxKeypoints) return SGTD_ERR_UNSUPPORTED;
   const int K = e->dc.K, tpi = e->dc.tpi;
   long long max_t = (long long)std::max(max_n, 1) * tpi;
   int max_slots = 64;
@@ -573,7 +583,7 @@ int stage_inputs(sgtd_engine *e, const float *xyz, const u32 *label, const int64
   for (int f = 0; f <= n_frames; f++) off[f] = kp_off[f];
   for (int f = 0; f < n_frames; f++) {
     long long n = off[f + 1] - off[f];
-    if (n < 0 || n > 65535) return SGTD_ERR_INVALID;
+    if (!keypoint_count_ok(n)) return SGTD_ERR_INVALID;
     mx = std::max(mx, (int)n);
   }
   *max_n = mx;
@@ -1126,7 +1136,7 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
     HIPCHK(hipGetLastError());
   }
   e->lists_pending = false;
-  e->verified = false; e->refined = false; e->overlapped = false; e->aligned = false;
+  new_results(e, false);
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -1535,7 +1545,7 @@ int launch_select(sgtd_engine *e) {
       batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
       HIPCHK(hipGetLastError());
       e->lists_pending = true;
-      e->verified = false; e->refined = false; e->overlapped = false; e->aligned = false;
+      new_results(e, false);
       e->batch_synced = false;
       return SGTD_OK;
     }
@@ -1592,7 +1602,7 @@ int launch_select(sgtd_engine *e) {
     HIPCHK(hipGetLastError());
   }
   e->batch_valid = true;
-  e->verified = false; e->refined = false; e->overlapped = false; e->aligned = false;
+  new_results(e, false);
   e->batch_synced = false;
   return SGTD_OK;
 }
@@ -2738,6 +2748,22 @@ int sgtd_verify_masked(sgtd_handle e, const uint64_t *d_keep) {
 }  // extern "C"
 
 namespace {
+// The batch's nb (query, candidate) slots in the order of the candidates' frames (empty slots last), for the kernels that
+// take one block per slot: the table gathers and the keypoints of one frame stay close.  *order: the slots in dispatch
+// order, in the handle's v_oval
+int frame_order(sgtd_engine *e, size_t nb, const u32 **order) {
+  for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
+  u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
+  const u32 last = e->frame_hi + 1u;          // key of a candidate slot that is empty
+  verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), e->dc.cand_num, (u32)nb, last, kin, vin);
+  HIPCHK(hipGetLastError());
+  int bits = 1;
+  while (bits < 32 && (last >> bits)) bits++;
+  CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
+  *order = vin;
+  return SGTD_OK;
+}
+
 // candidate_verify + triangle_solver (STDesc.cpp:462-571) of every (query, candidate) of the batch, enqueued behind it;
 // total = an upper bound on the pairs of all lists (sizes the per-pair scratch); guard: the kernels look at the batch's
 // overflow flags first (the batch has not been waited for)
@@ -2788,17 +2814,8 @@ int verify_enqueue(sgtd_engine *e, int64_t total, bool guard) {
   // a batch of many candidates is dispatched in the order of the candidates' frames (SGTD_VERIFY_ORDER=0: as they stand)
   static const bool order_on = [] { const char *o = getenv("SGTD_VERIFY_ORDER"); return !(o && !atoi(o)); }();
   if (mfma && order_on && !guard && nq * cn >= 4096 && e->have_frames) {
-    const u32 nb = (u32)(nq * cn);
-    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], (size_t)nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], (size_t)nb * sizeof(u32))); }
-    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
-    const u32 last = e->frame_hi + 1u;          // key of a candidate slot that is empty
-    verify_order_keys_kernel<<<grid_for(nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, nb, last, kin, vin);
-    HIPCHK(hipGetLastError());
-    int bits = 1;
-    while (bits < 32 && (last >> bits)) bits++;
-    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
-    P.order = vin;
-    grid = 8 * (int)((nb + 7) / 8);
+    CHK(frame_order(e, (size_t)(nq * cn), &P.order));
+    grid = 8 * ((nq * cn + 7) / 8);
   }
   verify_solve_kernel<<<nq * cn, SGTD_WAVE, 0, e->stream>>>(P);
   HIPCHK(hipGetLastError());
@@ -2834,7 +2851,7 @@ int sgtd_verify(sgtd_handle e) {
   CHK(sync_batch(e));
   if (!e->batch_valid) return SGTD_ERR_INVALID;
   const int cn = e->dc.cand_num, nq = e->nq;
-  e->refined = false; e->overlapped = false; e->aligned = false;
+  stale_stages(e);
   if (nq == 0) { e->verified = true; return SGTD_OK; }
   int64_t total = 0;
   for (int q = 0; q < nq; q++) total = std::max<int64_t>(total, (int64_t)e->h_pair_base[q] + e->h_pair_off[(size_t)q * (cn + 1) + cn]);
@@ -3194,7 +3211,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   }
   stage_times(e);
   e->batch_synced = true;
-  e->verified = !lists_only; e->refined = false; e->overlapped = false; e->aligned = false;
+  new_results(e, !lists_only);
   io->n_cand = (int32_t)w[12];
   if (io->cand_frame) std::memcpy(io->cand_frame, cf, (size_t)cn * 4);
   if (io->cand_votes) std::memcpy(io->cand_votes, cv, (size_t)cn * 4);
@@ -3392,18 +3409,69 @@ int sgtd_set_position_prior(sgtd_handle e, const double *center, const double *r
   return SGTD_OK;
 }
 
-// world[k * 12 ..] = the stored pose M of candidate k's frame composed with its relative pose (R, t cast to f32), each
-// operation an f32 rounding in the order include/sgtd_accel.h states; NaNs past n_cand, for rejected candidates and for
-// frames without a pose
-static void world_poses_of(const sgtd_engine *e, int n_cand, const int *cand_frame, const double *score, const double *pose,
-                           float *world) {
+}  // extern "C"
+
+// ---- what the stages on a verified batch share (sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints) and what reads
+// their results ----
+namespace {
+// "<who> needs <what> on the pending batch"
+int needs(sgtd_engine *e, const char *who, const char *what) {
+  e->err = std::string(who) + " needs " + what + " on the pending batch";
+  return SGTD_ERR_STATE;
+}
+
+// what a stage's getter says where the stage has not run on the pending batch
+const char kNoRefined[] = "no refined poses: sgtd_refine_poses comes after sgtd_verify on the pending batch";
+const char kNoOverlap[] = "no overlap results: sgtd_overlap comes after sgtd_verify on the pending batch";
+const char kNoAligned[] = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch";
+
+// a stage's getter of query q on a single-device handle: the stage has run on the pending batch (`missing` says what
+// has not), q is one of its queries, the table is still the one the batch ran on
+int result_ready(sgtd_engine *e, int q, bool done, const char *missing) {
+  if (!e->batch_valid || !e->verified || !done) { e->err = missing; return SGTD_ERR_STATE; }
+  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  return view_current(e);
+}
+
+// what a keypoint pass's kernel takes from the batch, the keypoint store's device copy (prepare_keypoints) and the call:
+// the members OverlapParams and AlignParams have in common, but the query keypoints (stage_query_keypoints)
+template <class Params>
+void keypoint_params(sgtd_engine *e, bool refined, double radius, size_t nb, Params *P) {
+  P->n_cand = e->n_cand.as<int>(); P->cand_frame = e->cand_frame.as<int>(); P->cand_num = e->dc.cand_num;
+  P->score = e->v_score.as<double>();
+  P->pose = refined ? e->r_pose.as<double>() : e->v_pose.as<double>();
+  P->kp = e->kp_dev.as<uint4>(); P->f_word = e->kp_word.as<u64>(); P->n_ids = (u32)e->has_kps.size();
+  P->rr = radius * radius;
+  P->order = nullptr; P->n_blocks = (u32)nb;
+}
+
+// query q's candidate count and frames, of a single-device handle or of a group
+int batch_candidates(sgtd_engine *e, int q, int *n_cand, int *cand_frame) {
+  if (e->grp) return multi::candidates_of(e, q, n_cand, cand_frame);
+  CHK(sync_batch(e));
   const int cn = e->cfg.candidate_num;
+  *n_cand = e->h_n_cand[(size_t)q];
+  std::memcpy(cand_frame, e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
+  return SGTD_OK;
+}
+
+// world[k * 12 ..] = the stored pose M of the frame of query q's candidate k composed with its relative pose (R, t cast
+// to f32), each operation an f32 rounding in the order include/sgtd_accel.h states; NaNs past the query's candidates, for
+// candidates without a result (has(k) says which have one) and for frames without a pose.  pose: what a stage's getter
+// gave for q (which has checked q)
+template <class Has>
+int world_poses_of(sgtd_engine *e, int q, const double *pose, Has has, float *world) {
+  const int cn = e->cfg.candidate_num;
+  std::vector<int> cand_frame((size_t)cn);
+  int n_cand = 0;
+  CHK(batch_candidates(e, q, &n_cand, cand_frame.data()));
   const float nan = std::numeric_limits<float>::quiet_NaN();
   for (int k = 0; k < cn; k++) {
     float *w = world + (size_t)k * 12;
     std::fill(w, w + 12, nan);
-    if (k >= n_cand || score[k] < 0.0) continue;
-    const size_t id = (size_t)(u32)cand_frame[k];
+    if (k >= n_cand || !has(k)) continue;
+    const size_t id = (size_t)(u32)cand_frame[(size_t)k];
     if (id >= e->has_pose.size() || !e->has_pose[id]) continue;
     const float *M = e->poses.data() + id * 12;
     const double *rel = pose + (size_t)k * 12;
@@ -3416,32 +3484,25 @@ static void world_poses_of(const sgtd_engine *e, int n_cand, const int *cand_fra
       w[i * 4 + 3] = ((m[0] * t[0] + m[1] * t[1]) + m[2] * t[2]) + m[3];
     }
   }
+  return SGTD_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int sgtd_result_world_poses(sgtd_handle e, int q, float *world) {
   if (!e || !world) return SGTD_ERR_INVALID;
-  const int cn = e->cfg.candidate_num;
-  std::vector<double> score((size_t)cn), pose((size_t)cn * 12);
-  std::vector<int> frames((size_t)cn);
-  int n_cand = 0;
-  if (e->grp) {
-    CHK(multi::result_verify(e, q, score.data(), pose.data()));
-    CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
-  } else {
-    CHK(sgtd_result_verify(e, q, score.data(), pose.data()));
-    CHK(sync_batch(e));
-    n_cand = e->h_n_cand[(size_t)q];
-    std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
-  }
-  world_poses_of(e, n_cand, frames.data(), score.data(), pose.data(), world);
-  return SGTD_OK;
+  const size_t cn = (size_t)e->cfg.candidate_num;
+  std::vector<double> score(cn), pose(cn * 12);
+  CHK(sgtd_result_verify(e, q, score.data(), pose.data()));
+  return world_poses_of(e, q, pose.data(), [&](int k) { return score[(size_t)k] >= 0.0; }, world);
 }
 
 // ---- sgtd_refine_poses: the least-squares refit over every candidate's inlier pairs (refine_kernels.hip.h) ----
 int sgtd_refine_poses(sgtd_handle e, int iterations) {
   if (!e || iterations < 1) return SGTD_ERR_INVALID;
   if (e->grp) return multi::refine_poses(e, iterations);
-  if (!e->batch_valid || !e->verified) { e->err = "sgtd_refine_poses needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+  if (!e->batch_valid || !e->verified) return needs(e, "sgtd_refine_poses", "sgtd_verify");
   HIPCHK(hipSetDevice(e->cfg.device_id));
   CHK(sync_batch(e));
   e->refined = false;
@@ -3467,19 +3528,7 @@ int sgtd_refine_poses(sgtd_handle e, int iterations) {
   P.order = nullptr; P.n_blocks = (u32)nb;
   P.pose = e->r_pose.as<double>(); P.rmse = e->r_rmse.as<double>(); P.rmse_verify = e->r_rmse_v.as<double>();
   P.n_pairs = e->r_npairs.as<int>(); P.moments = e->r_moments.as<double>();
-  // a batch of many candidates in the order of the candidates' frames, as its verification was dispatched: the table
-  // gathers of one frame stay close
-  if (nb >= 4096 && e->have_frames) {
-    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
-    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
-    const u32 last = e->frame_hi + 1u;
-    verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, (u32)nb, last, kin, vin);
-    HIPCHK(hipGetLastError());
-    int bits = 1;
-    while (bits < 32 && (last >> bits)) bits++;
-    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
-    P.order = vin;
-  }
+  if (nb >= 4096 && e->have_frames) CHK(frame_order(e, nb, &P.order));      // (as its verification was dispatched)
   const size_t lds = refine_lds_bytes();
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&refine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device)
   refine_kernel<<<(int)nb, SGTD_REFINE_THREADS, lds, e->stream>>>(P);
@@ -3492,10 +3541,7 @@ int sgtd_result_refined(sgtd_handle e, int q, double *pose, double *rmse, double
   PinScope pin_scope(e && !e->grp ? e : nullptr);
   if (!e) return SGTD_ERR_INVALID;
   if (e->grp) return multi::result_refined(e, q, pose, rmse, rmse_verify, n_pairs, moments);
-  if (!e->batch_valid || !e->verified || !e->refined) { e->err = "no refined poses: sgtd_refine_poses comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(view_current(e));
+  CHK(result_ready(e, q, e->refined, kNoRefined));
   const size_t cn = (size_t)e->dc.cand_num, o = (size_t)q * cn;
   if (pose) CHK(d2h(e, pose, e->r_pose.as<double>() + o * 12, cn * 12 * sizeof(double)));
   if (rmse) CHK(d2h(e, rmse, e->r_rmse.as<double>() + o, cn * sizeof(double)));
@@ -3508,22 +3554,11 @@ int sgtd_result_refined(sgtd_handle e, int q, double *pose, double *rmse, double
 
 int sgtd_result_refined_world_poses(sgtd_handle e, int q, float *world) {
   if (!e || !world) return SGTD_ERR_INVALID;
-  const int cn = e->cfg.candidate_num;
-  std::vector<double> has((size_t)cn), pose((size_t)cn * 12);
-  std::vector<int32_t> np((size_t)cn);
-  std::vector<int> frames((size_t)cn);
-  int n_cand = 0;
+  const size_t cn = (size_t)e->cfg.candidate_num;
+  std::vector<double> pose(cn * 12);
+  std::vector<int32_t> np(cn);
   CHK(sgtd_result_refined(e, q, pose.data(), nullptr, nullptr, np.data(), nullptr));
-  if (e->grp) {
-    CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
-  } else {
-    CHK(sync_batch(e));
-    n_cand = e->h_n_cand[(size_t)q];
-    std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
-  }
-  for (int k = 0; k < cn; k++) has[(size_t)k] = np[(size_t)k] > 0 ? 1.0 : -1.0;     // (a candidate without a result has no pairs)
-  world_poses_of(e, n_cand, frames.data(), has.data(), pose.data(), world);
-  return SGTD_OK;
+  return world_poses_of(e, q, pose.data(), [&](int k) { return np[(size_t)k] > 0; }, world);     // (a candidate without a result has no pairs)
 }
 
 // ---- sgtd_set_frame_keypoints / sgtd_overlap: the keypoint overlap of the verified candidates (overlap_kernels.hip.h) ----
@@ -3531,10 +3566,8 @@ int sgtd_set_frame_keypoints(sgtd_handle e, const uint32_t *frame_ids, const int
   if (!e || n < 0 || (n > 0 && !frame_ids)) return SGTD_ERR_INVALID;
   if (n > 0 && xyz && (!kp_off || !label)) return SGTD_ERR_INVALID;
   if (n > 0 && xyz)
-    for (int64_t i = 0; i < n; i++) {
-      const int64_t cnt = kp_off[i + 1] - kp_off[i];
-      if (cnt < 0 || cnt > 65535) return SGTD_ERR_INVALID;
-    }
+    for (int64_t i = 0; i < n; i++)
+      if (!keypoint_count_ok(kp_off[i + 1] - kp_off[i])) return SGTD_ERR_INVALID;
   for (int64_t i = 0; i < n; i++)
     if (frame_ids[i] >= (uint32_t)e->cfg.max_frame_n) return SGTD_ERR_FRAME_LIMIT;
   if (e->grp) CHK(multi::set_frame_keypoints(e, frame_ids, kp_off, xyz, label, n));
@@ -3620,55 +3653,56 @@ static int stage_query_keypoints(sgtd_engine *e, int nq, const float *q_xyz, con
   return SGTD_OK;
 }
 
-int sgtd_overlap(sgtd_handle e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
-  if (!e || !(radius >= 0.0) || std::isinf(radius) || (flags & ~SGTD_OVERLAP_REFINED)) return SGTD_ERR_INVALID;
+// The head of a keypoint pass (`pass`: its entry point's name) in two parts, the hand-over to a group between them.
+// First what holds for both kinds of handle: the arguments, a verified batch (*nq: its queries), the caller's keypoint counts
+static int keypoint_pass_args(sgtd_engine *e, const char *pass, double radius, const float *q_xyz, const uint32_t *q_label,
+                              const int64_t *q_kp_off, int *nq) {
+  if (!(radius >= 0.0) || std::isinf(radius)) return SGTD_ERR_INVALID;
   if (q_xyz && (!q_label || !q_kp_off)) return SGTD_ERR_INVALID;
-  int nq = 0;
   if (e->grp) {
-    if (multi::nq_of(e, &nq) != SGTD_OK) { e->err = "sgtd_overlap needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
+    if (multi::nq_of(e, nq) != SGTD_OK) return needs(e, pass, "sgtd_verify");
   } else {
-    if (!e->batch_valid || !e->verified) { e->err = "sgtd_overlap needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-    nq = e->nq;
+    if (!e->batch_valid || !e->verified) return needs(e, pass, "sgtd_verify");
+    *nq = e->nq;
   }
   if (q_xyz)
-    for (int q = 0; q < nq; q++) {
-      const int64_t cnt = q_kp_off[q + 1] - q_kp_off[q];
-      if (cnt < 0 || cnt > 65535) return SGTD_ERR_INVALID;
-    }
-  if (e->grp) return multi::overlap(e, radius, flags, q_xyz, q_label, q_kp_off);
-  if ((flags & SGTD_OVERLAP_REFINED) && !e->refined) { e->err = "SGTD_OVERLAP_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
-  if (!q_xyz && e->last_kind != 1) { e->err = "the batch has no keypoints of its own (sgtd_query_descs, sgtd_search_frame): pass them to sgtd_overlap"; return SGTD_ERR_STATE; }
+    for (int q = 0; q < *nq; q++)
+      if (!keypoint_count_ok(q_kp_off[q + 1] - q_kp_off[q])) return SGTD_ERR_INVALID;
+  return SGTD_OK;
+}
+
+// ... then, on a single device: the refit if its poses are asked for (refined_flag: the flag's name, or NULL), keypoints
+// to run on, the batch settled; the pass's results (*done) are gone from here on
+static int keypoint_pass_begin(sgtd_engine *e, const char *pass, const char *refined_flag, bool own_keypoints, bool *done) {
+  if (refined_flag && !e->refined) return needs(e, refined_flag, "sgtd_refine_poses");
+  if (own_keypoints && e->last_kind != 1) {
+    e->err = std::string("the batch has no keypoints of its own (sgtd_query_descs, sgtd_search_frame): pass them to ") + pass;
+    return SGTD_ERR_STATE;
+  }
   HIPCHK(hipSetDevice(e->cfg.device_id));
   CHK(sync_batch(e));
-  e->overlapped = false;
-  const int cn = e->dc.cand_num;
+  *done = false;
+  return SGTD_OK;
+}
+
+int sgtd_overlap(sgtd_handle e, double radius, int flags, const float *q_xyz, const uint32_t *q_label, const int64_t *q_kp_off) {
+  if (!e || (flags & ~SGTD_OVERLAP_REFINED)) return SGTD_ERR_INVALID;
+  int nq = 0;
+  CHK(keypoint_pass_args(e, "sgtd_overlap", radius, q_xyz, q_label, q_kp_off, &nq));
+  if (e->grp) return multi::overlap(e, radius, flags, q_xyz, q_label, q_kp_off);
+  const bool refined = (flags & SGTD_OVERLAP_REFINED) != 0;
+  CHK(keypoint_pass_begin(e, "sgtd_overlap", refined ? "SGTD_OVERLAP_REFINED" : nullptr, !q_xyz, &e->overlapped));
   if (nq == 0) { e->overlapped = true; return SGTD_OK; }
   CHK(prepare_keypoints(e));
-  const size_t nb = (size_t)nq * cn;
+  const size_t nb = (size_t)nq * e->dc.cand_num;
   CHK(ensure(e, e->o_cnt, nb * sizeof(int4)));
   CHK(ensure(e, e->o_val, nb * sizeof(double2)));
   OverlapParams P;
-  P.n_cand = e->n_cand.as<int>(); P.cand_frame = e->cand_frame.as<int>(); P.cand_num = cn;
-  P.score = e->v_score.as<double>();
-  P.pose = (flags & SGTD_OVERLAP_REFINED) ? e->r_pose.as<double>() : e->v_pose.as<double>();
+  keypoint_params(e, refined, radius, nb, &P);
   CHK(stage_query_keypoints(e, nq, q_xyz, q_label, q_kp_off, &P.q_xyz, &P.q_label, &P.q_off, nullptr));
-  P.kp = e->kp_dev.as<uint4>(); P.f_word = e->kp_word.as<u64>(); P.n_ids = (u32)e->has_kps.size();
   P.hit_off = (u32)overlap_hit_off(e->kp_dev_max);
-  P.rr = radius * radius;
-  P.order = nullptr; P.n_blocks = (u32)nb;
   P.cnt = e->o_cnt.as<int4>(); P.val = e->o_val.as<double2>();
-  // a batch of many candidates in the order of the candidates' frames, as sgtd_refine_poses: a frame's keypoints stay in cache
-  if (nb >= 4096 && e->have_frames) {
-    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
-    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
-    const u32 last = e->frame_hi + 1u;
-    verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, (u32)nb, last, kin, vin);
-    HIPCHK(hipGetLastError());
-    int bits = 1;
-    while (bits < 32 && (last >> bits)) bits++;
-    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
-    P.order = vin;
-  }
+  if (nb >= 4096 && e->have_frames) CHK(frame_order(e, nb, &P.order));      // (as its verification was dispatched)
   const size_t lds = overlap_lds_bytes(e->kp_dev_max);
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&overlap_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device)
   overlap_kernel<<<(int)nb, SGTD_OVERLAP_THREADS, lds, e->stream>>>(P);
@@ -3682,10 +3716,7 @@ int sgtd_result_overlap(sgtd_handle e, int q, int32_t *n_query_kp, int32_t *n_fr
   PinScope pin_scope(e && !e->grp ? e : nullptr);
   if (!e) return SGTD_ERR_INVALID;
   if (e->grp) return multi::result_overlap(e, q, n_query_kp, n_frame_kp, n_hit_query, n_hit_frame, overlap, rms);
-  if (!e->batch_valid || !e->verified || !e->overlapped) { e->err = "no overlap results: sgtd_overlap comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(view_current(e));
+  CHK(result_ready(e, q, e->overlapped, kNoOverlap));
   const size_t cn = (size_t)e->dc.cand_num, o = (size_t)q * cn;
   std::vector<int4> cnt(cn);
   std::vector<double2> val(cn);
@@ -3711,7 +3742,7 @@ int sgtd_search_loop_overlap(sgtd_handle e, double icp_threshold, double min_ove
   if (!e) return SGTD_ERR_INVALID;
   const bool gate = min_overlap > 0.0;
   const bool have = e->grp ? multi::has_overlap(e) != 0 : (e->batch_valid && e->verified && e->overlapped);
-  if (gate && !have) { e->err = "sgtd_search_loop_overlap with min_overlap > 0 needs sgtd_overlap on the pending batch"; return SGTD_ERR_STATE; }
+  if (gate && !have) return needs(e, "sgtd_search_loop_overlap with min_overlap > 0", "sgtd_overlap");
   const int cn = e->cfg.candidate_num;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   int nq = 0;
@@ -3722,7 +3753,7 @@ int sgtd_search_loop_overlap(sgtd_handle e, double icp_threshold, double min_ove
     score.resize((size_t)nq * cn); ov.assign((size_t)nq * cn, nan); n_cand.resize((size_t)nq); frames.resize((size_t)nq * cn);
     for (int q = 0; q < nq; q++) {
       CHK(multi::result_verify(e, q, score.data() + (size_t)q * cn, nullptr));
-      CHK(multi::candidates_of(e, q, &n_cand[(size_t)q], frames.data() + (size_t)q * cn));
+      CHK(batch_candidates(e, q, &n_cand[(size_t)q], frames.data() + (size_t)q * cn));
       if (have) CHK(multi::result_overlap(e, q, nullptr, nullptr, nullptr, nullptr, ov.data() + (size_t)q * cn, nullptr));
     }
   } else {
@@ -3761,26 +3792,12 @@ int sgtd_search_loop_overlap(sgtd_handle e, double icp_threshold, double min_ove
 // ---- sgtd_align_keypoints: closest-keypoint alignment of the verified candidates (align_kernels.hip.h) ----
 int sgtd_align_keypoints(sgtd_handle e, double radius, int iterations, int flags, const float *q_xyz, const uint32_t *q_label,
                          const int64_t *q_kp_off) {
-  if (!e || !(radius >= 0.0) || std::isinf(radius) || iterations < 1 || (flags & ~SGTD_ALIGN_REFINED)) return SGTD_ERR_INVALID;
-  if (q_xyz && (!q_label || !q_kp_off)) return SGTD_ERR_INVALID;
+  if (!e || iterations < 1 || (flags & ~SGTD_ALIGN_REFINED)) return SGTD_ERR_INVALID;
   int nq = 0;
-  if (e->grp) {
-    if (multi::nq_of(e, &nq) != SGTD_OK) { e->err = "sgtd_align_keypoints needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  } else {
-    if (!e->batch_valid || !e->verified) { e->err = "sgtd_align_keypoints needs sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-    nq = e->nq;
-  }
-  if (q_xyz)
-    for (int q = 0; q < nq; q++) {
-      const int64_t cnt = q_kp_off[q + 1] - q_kp_off[q];
-      if (cnt < 0 || cnt > 65535) return SGTD_ERR_INVALID;
-    }
+  CHK(keypoint_pass_args(e, "sgtd_align_keypoints", radius, q_xyz, q_label, q_kp_off, &nq));
   if (e->grp) return multi::align_keypoints(e, radius, iterations, flags, q_xyz, q_label, q_kp_off);
-  if ((flags & SGTD_ALIGN_REFINED) && !e->refined) { e->err = "SGTD_ALIGN_REFINED needs sgtd_refine_poses on the pending batch"; return SGTD_ERR_STATE; }
-  if (!q_xyz && e->last_kind != 1) { e->err = "the batch has no keypoints of its own (sgtd_query_descs, sgtd_search_frame): pass them to sgtd_align_keypoints"; return SGTD_ERR_STATE; }
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(sync_batch(e));
-  e->aligned = false;
+  const bool refined = (flags & SGTD_ALIGN_REFINED) != 0;
+  CHK(keypoint_pass_begin(e, "sgtd_align_keypoints", refined ? "SGTD_ALIGN_REFINED" : nullptr, !q_xyz, &e->aligned));
   const int cn = e->dc.cand_num;
   if (nq == 0) { e->a_qoff.assign(1, 0); e->aligned = true; return SGTD_OK; }
   CHK(prepare_keypoints(e));
@@ -3794,28 +3811,12 @@ int sgtd_align_keypoints(sgtd_handle e, double radius, int iterations, int flags
   CHK(ensure(e, e->a_val, nb * 4 * sizeof(double)));
   CHK(ensure(e, e->a_mom, nb * 15 * sizeof(double)));
   CHK(ensure(e, e->a_assign, std::max<size_t>(total * (size_t)cn, 1) * sizeof(int)));
-  P.n_cand = e->n_cand.as<int>(); P.cand_frame = e->cand_frame.as<int>(); P.cand_num = cn;
-  P.score = e->v_score.as<double>();
-  P.pose = (flags & SGTD_ALIGN_REFINED) ? e->r_pose.as<double>() : e->v_pose.as<double>();
-  P.kp = e->kp_dev.as<uint4>(); P.f_word = e->kp_word.as<u64>(); P.n_ids = (u32)e->has_kps.size();
+  keypoint_params(e, refined, radius, nb, &P);
   P.hit_off = (u32)align_hit_off(e->kp_dev_max); P.asg_off = (u32)align_asg_off(e->kp_dev_max);
-  P.rr = radius * radius;
   P.iterations = iterations;
-  P.order = nullptr; P.n_blocks = (u32)nb;
   P.o_pose = e->a_pose.as<double>(); P.fit = e->a_fit.as<int4>(); P.cnt = e->a_cnt.as<int4>(); P.val = e->a_val.as<double>();
   P.moments = e->a_mom.as<double>(); P.assign = e->a_assign.as<int>();
-  // a batch of many candidates in the order of the candidates' frames, as sgtd_overlap: a frame's keypoints stay in cache
-  if (nb >= 4096 && e->have_frames) {
-    for (int k = 0; k < 2; k++) { CHK(ensure(e, e->v_okey[k], nb * sizeof(u32))); CHK(ensure(e, e->v_oval[k], nb * sizeof(u32))); }
-    u32 *kin = e->v_okey[0].as<u32>(), *kout = e->v_okey[1].as<u32>(), *vin = e->v_oval[0].as<u32>(), *vout = e->v_oval[1].as<u32>();
-    const u32 last = e->frame_hi + 1u;
-    verify_order_keys_kernel<<<grid_for((long long)nb, 256), 256, 0, e->stream>>>(e->cand_frame.as<int>(), e->n_cand.as<int>(), cn, (u32)nb, last, kin, vin);
-    HIPCHK(hipGetLastError());
-    int bits = 1;
-    while (bits < 32 && (last >> bits)) bits++;
-    CHK(radix_sort_pairs<u32>(e, kin, kout, vin, vout, (long long)nb, bits, false));
-    P.order = vin;
-  }
+  if (nb >= 4096 && e->have_frames) CHK(frame_order(e, nb, &P.order));      // (as its verification was dispatched)
   const size_t lds = align_lds_bytes(e->kp_dev_max);
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device)
   align_kernel<<<(int)nb, SGTD_ALIGN_THREADS, lds, e->stream>>>(P);
@@ -3830,10 +3831,7 @@ int sgtd_result_aligned(sgtd_handle e, int q, double *pose, int32_t *n_fits, int
   PinScope pin_scope(e && !e->grp ? e : nullptr);
   if (!e) return SGTD_ERR_INVALID;
   if (e->grp) return multi::result_aligned(e, q, pose, n_fits, n_corr, stop, counts_before, counts_after, overlap_before, rms_before, overlap_after, rms_after, moments);
-  if (!e->batch_valid || !e->verified || !e->aligned) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(view_current(e));
+  CHK(result_ready(e, q, e->aligned, kNoAligned));
   const size_t cn = (size_t)e->dc.cand_num, o = (size_t)q * cn;
   std::vector<int4> fit(cn), cnt(cn * 2);
   std::vector<double> val(cn * 4);
@@ -3861,10 +3859,7 @@ int sgtd_result_aligned_pairs(sgtd_handle e, int q, int cand, int32_t *frame_kp,
   PinScope pin_scope(e && !e->grp ? e : nullptr);
   if (!e || !n) return SGTD_ERR_INVALID;
   if (e->grp) return multi::result_aligned_pairs(e, q, cand, frame_kp, capacity, n);
-  if (!e->batch_valid || !e->verified || !e->aligned) { e->err = "no aligned results: sgtd_align_keypoints comes after sgtd_verify on the pending batch"; return SGTD_ERR_STATE; }
-  if (q < 0 || q >= e->nq) return SGTD_ERR_INVALID;
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(view_current(e));
+  CHK(result_ready(e, q, e->aligned, kNoAligned));
   CHK(sync_batch(e));
   if (cand < 0 || cand >= e->h_n_cand[(size_t)q]) return SGTD_ERR_INVALID;
   const int64_t nqk = e->a_qoff[(size_t)q + 1] - e->a_qoff[(size_t)q];
@@ -3880,22 +3875,11 @@ int sgtd_result_aligned_pairs(sgtd_handle e, int q, int cand, int32_t *frame_kp,
 
 int sgtd_result_aligned_world_poses(sgtd_handle e, int q, float *world) {
   if (!e || !world) return SGTD_ERR_INVALID;
-  const int cn = e->cfg.candidate_num;
-  std::vector<double> has((size_t)cn), pose((size_t)cn * 12);
-  std::vector<int32_t> stop((size_t)cn);
-  std::vector<int> frames((size_t)cn);
-  int n_cand = 0;
+  const size_t cn = (size_t)e->cfg.candidate_num;
+  std::vector<double> pose(cn * 12);
+  std::vector<int32_t> stop(cn);
   CHK(sgtd_result_aligned(e, q, pose.data(), nullptr, nullptr, stop.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-  if (e->grp) {
-    CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
-  } else {
-    CHK(sync_batch(e));
-    n_cand = e->h_n_cand[(size_t)q];
-    std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
-  }
-  for (int k = 0; k < cn; k++) has[(size_t)k] = stop[(size_t)k] >= 0 ? 1.0 : -1.0;     // (stop -1: a candidate without a result)
-  world_poses_of(e, n_cand, frames.data(), has.data(), pose.data(), world);
-  return SGTD_OK;
+  return world_poses_of(e, q, pose.data(), [&](int k) { return stop[(size_t)k] >= 0; }, world);     // (stop -1: a candidate without a result)
 }
 
 // the lowest registration fitness among the candidates that pass the bounds, in host code over the public results (one
@@ -3904,7 +3888,7 @@ int sgtd_search_loop_aligned(sgtd_handle e, double min_overlap, double max_rms, 
                              double *best_rms, double *best_overlap) {
   if (!e || std::isnan(min_overlap) || std::isnan(max_rms)) return SGTD_ERR_INVALID;
   const bool have = e->grp ? multi::has_aligned(e) != 0 : (e->batch_valid && e->verified && e->aligned);
-  if (!have) { e->err = "sgtd_search_loop_aligned needs sgtd_align_keypoints on the pending batch"; return SGTD_ERR_STATE; }
+  if (!have) return needs(e, "sgtd_search_loop_aligned", "sgtd_align_keypoints");
   const int cn = e->cfg.candidate_num;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   const bool gate_ov = min_overlap > 0.0, gate_rms = max_rms > 0.0 && !std::isinf(max_rms);
@@ -3917,12 +3901,7 @@ int sgtd_search_loop_aligned(sgtd_handle e, double min_overlap, double max_rms, 
     int n_cand = 0;
     CHK(sgtd_result_verify(e, q, score.data(), nullptr));
     CHK(sgtd_result_aligned(e, q, nullptr, nullptr, nullptr, stop.data(), nullptr, nullptr, nullptr, nullptr, ov.data(), rms.data(), nullptr));
-    if (e->grp) {
-      CHK(multi::candidates_of(e, q, &n_cand, frames.data()));
-    } else {
-      n_cand = e->h_n_cand[(size_t)q];
-      std::memcpy(frames.data(), e->h_cand_frame.data() + (size_t)q * cn, (size_t)cn * sizeof(int));
-    }
+    CHK(batch_candidates(e, q, &n_cand, frames.data()));       // (settled and current: the two getters above looked)
     int bc = -1;
     for (int c = 0; c < n_cand; c++) {
       if (stop[(size_t)c] < 0 || std::isnan(rms[(size_t)c])) continue;

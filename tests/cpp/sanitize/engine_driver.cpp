@@ -1,13 +1,17 @@
 // engine_driver.cpp — the engine's host code (sgtd_accel.hip, multi_impl.hip.h) under ASan + UBSan, against hip_stub.cpp.
 // No kernel runs: "device" buffers are zeroed host memory and the launch hook below leaves behind what selected kernels
 // would have — overflow flags, record needs, pair totals, a frame's packed results — so that the host walks its growth,
-// re-run, stale-view, capacity and table-file paths with every copy checked by the sanitizer.  Compiled for the host only
+// re-run, stale-view, capacity and table-file paths with every copy checked by the sanitizer.  The stages on a verified batch
+// (sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints) run in a scenario of their own below, whose stand-in results name the
+// (query, candidate) slot they belong to.  Compiled for the host only
 // (hipcc --cuda-host-only: the kernel headers are needed for the argument structs); tests/test_sanitizers.py builds and runs it.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <random>
 #include <string>
 #include <vector>
@@ -24,15 +28,22 @@ namespace kernels_of_the_engine {
 #include "../../../sgtd_amd/csrc/probe_kernels.hip.h"
 #include "../../../sgtd_amd/csrc/select_kernels.hip.h"
 #include "../../../sgtd_amd/csrc/verify_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/refine_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/overlap_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/align_kernels.hip.h"
 }  // namespace kernels_of_the_engine
 using kernels_of_the_engine::ProbeBuffers;
 using kernels_of_the_engine::frame_pack_bytes;
 using kernels_of_the_engine::u32;
+using kernels_of_the_engine::u64;
 
 extern "C" {
 typedef void (*launch_hook_t)(const char *name, void **args, void *user);
 void sgtd_stub_set_launch_hook(launch_hook_t h, void *user);
 unsigned long long sgtd_stub_launches();
+unsigned long long sgtd_stub_copies();
+unsigned long long sgtd_stub_waits();
+unsigned sgtd_stub_grid_x();
 size_t sgtd_stub_device_bytes();
 size_t sgtd_stub_device_peak();
 size_t sgtd_stub_device_blocks();
@@ -54,7 +65,74 @@ struct Scenario {
   long long frame_inliers = -1;     // pack_frame_kernel: inlier pairs the frame's verification "found" (-1: leave zeros)
   int frame_overflow = 0;           // pack_frame_kernel: the next packs carry a set overflow flag (sgtd_search_frame falls back)
   unsigned long long sweeps = 0, packs = 0;
+  // the stages' scenario: the candidate tables and the results of the verification and of the three stages are filled in
+  bool stages = false;
+  int expect_order = -1;            // the frame-ordered dispatch of the four kernels that take one: 1 it must be there, 0 it must not, -1 either
+  unsigned long long stage_launches[4] = {0, 0, 0, 0};      // verify, refine, overlap, align
 };
+
+// bytes from p to the end of the block it lies in
+size_t room_of(const void *p) {
+  hipDeviceptr_t base; size_t size;
+  REQUIRE(hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess);
+  return size - (size_t)(static_cast<const char *>(p) - static_cast<const char *>(base));
+}
+
+// ---- what the stages' scenario leaves in the candidate tables: functions of (query, slot) alone, the same on every "device"
+int cand_count_of(int q, int cn) { return q % 7 == 3 ? 0 : std::min(cn, 18 + (q * 11) % 40); }
+int cand_frame_of(int q, int k) { return (q + k) % 64; }           // (a device's local id: distinct within a query)
+int cand_votes_of(int q, int k) { return (cand_frame_of(q, k) * 13 + q * 5) % 41; }      // (some below the merge's five)
+const double kNaN = std::numeric_limits<double>::quiet_NaN();
+
+void fill_candidates(int nq, int cn, int *n_cand, int *frame, int *votes) {
+  REQUIRE(room_of(n_cand) >= (size_t)nq * 4 && room_of(frame) >= (size_t)nq * cn * 4 && room_of(votes) >= (size_t)nq * cn * 4);
+  for (int q = 0; q < nq; q++) {
+    n_cand[q] = cand_count_of(q, cn);
+    for (int k = 0; k < cn; k++) {
+      const bool live = k < n_cand[q];
+      frame[(size_t)q * cn + k] = live ? cand_frame_of(q, k) : -1;
+      votes[(size_t)q * cn + k] = live ? cand_votes_of(q, k) : 0;
+    }
+  }
+}
+void fill_offsets(int nq, int cn, const int *n_cand, const int *votes, long long *pair_off, u32 *q_pairs) {
+  REQUIRE(room_of(pair_off) >= (size_t)nq * (cn + 1) * 8 && room_of(q_pairs) >= (size_t)nq * 4);
+  for (int q = 0; q < nq; q++) {
+    long long acc = 0;
+    for (int k = 0; k <= cn; k++) {
+      pair_off[(size_t)q * (cn + 1) + k] = acc;
+      if (k < n_cand[q]) acc += votes[(size_t)q * cn + k];
+    }
+    q_pairs[q] = (u32)acc;
+  }
+}
+
+// what every kernel of a stage is handed in common: the frame-ordered dispatch as the scenario expects it, the batch's tables
+template <class P> int stage_head(Scenario &S, const P &p, int stage) {
+  S.stage_launches[stage]++;
+  const u32 nb = p.n_blocks;
+  REQUIRE(p.cand_num > 0 && nb % (u32)p.cand_num == 0 && sgtd_stub_grid_x() >= nb);
+  if (S.expect_order >= 0) REQUIRE((p.order != nullptr) == (S.expect_order == 1));
+  if (p.order) REQUIRE(room_of(p.order) >= (size_t)nb * 4);
+  const int nq = (int)(nb / (u32)p.cand_num);
+  REQUIRE(room_of(p.n_cand) >= (size_t)nq * 4 && room_of(p.score) >= (size_t)nb * 8);
+  return nq;
+}
+template <class P> bool slot_live(const P &p, u32 blk) {
+  return (int)(blk % (u32)p.cand_num) < p.n_cand[blk / (u32)p.cand_num] && p.score[blk] >= 0.0;
+}
+// the keypoint passes' inputs: the query keypoints with their offsets, the store's device copy
+template <class P> void keypoint_room(const P &p, int nq) {
+  REQUIRE(room_of(p.cand_frame) >= (size_t)p.n_blocks * 4 && room_of(p.pose) >= (size_t)p.n_blocks * 12 * 8);
+  REQUIRE(room_of(p.q_off) >= (size_t)(nq + 1) * 8);
+  const size_t last = (size_t)p.q_off[nq];
+  if (last) REQUIRE(room_of(p.q_xyz) >= last * 12 && room_of(p.q_label) >= last * 4);
+  REQUIRE(room_of(p.f_word) >= (size_t)std::max<u32>(p.n_ids, 1) * 8);
+  size_t kp_end = 0;
+  for (u32 id = 0; id < p.n_ids; id++)
+    if (p.f_word[id] != SGTD_OVERLAP_NONE) kp_end = std::max(kp_end, (size_t)(p.f_word[id] >> 16) + (size_t)(p.f_word[id] & 0xFFFFull));
+  REQUIRE(room_of(p.kp) >= std::max<size_t>(kp_end, 1) * 16);
+}
 
 std::vector<const void *> g_gathers_into;      // gather_pair_entries_kernel launches: the `side` array each was handed
 
@@ -95,7 +173,13 @@ void hook(const char *name, void **args, void *user) {
     const int nq = *static_cast<int *>(args[2]);
     int *overflow = *static_cast<int **>(args[4]);
     REQUIRE(sgtd_stub_block_size(q_pair_base) >= (size_t)(nq + 1) * sizeof(u32));
-    for (int q = 0; q <= nq; q++) q_pair_base[q] = (u32)((unsigned long long)S.pairs_total * q / nq);
+    if (S.stages) {
+      const u32 *q_pairs = *static_cast<u32 **>(args[0]);
+      q_pair_base[0] = 0;
+      for (int q = 0; q < nq; q++) q_pair_base[q + 1] = q_pair_base[q] + q_pairs[q];
+    } else {
+      for (int q = 0; q <= nq; q++) q_pair_base[q] = (u32)((unsigned long long)S.pairs_total * q / nq);
+    }
     if (S.pair_overflows > 0) { S.pair_overflows--; overflow[1] = 1; }
   } else if (strstr(name, "block_scan_kernel")) {
     // a one-query batch: the scan leaves the query's base and total itself (no query_base_kernel launch)
@@ -111,15 +195,83 @@ void hook(const char *name, void **args, void *user) {
     const long long cap = *static_cast<long long *>(args[2]);
     int *qi = *static_cast<int **>(args[3]);
     const kernels_of_the_engine::DescArrays &out = *static_cast<const kernels_of_the_engine::DescArrays *>(args[5]);
-    auto room_of = [](const void *p) {        // bytes from p to the end of the block it lies in
-      hipDeviceptr_t base; size_t size;
-      REQUIRE(hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess);
-      return size - (size_t)(static_cast<const char *>(p) - static_cast<const char *>(base));
-    };
     REQUIRE(room_of(out.side) >= (size_t)cap * 24 && room_of(out.angle) >= (size_t)cap * 24 && room_of(out.center) >= (size_t)cap * 24);
     REQUIRE(room_of(out.vertex) >= (size_t)cap * 36 && room_of(out.label) >= (size_t)cap * 12 && room_of(out.node_id) >= (size_t)cap * 12);
     REQUIRE(room_of(out.frame) >= (size_t)cap * 4 && room_of(qi) >= (size_t)cap * 4);
     g_gathers_into.push_back(out.side);
+  } else if (S.stages && strstr(name, "topk_kernel")) {
+    // the candidate tables (votes_topk_kernel leaves the lists' offsets too); one block per query
+    const bool fused = strstr(name, "votes_topk_kernel") != nullptr;
+    const int cn = *static_cast<int *>(args[fused ? 5 : 3]), nq = (int)sgtd_stub_grid_x();
+    int *n_cand = *static_cast<int **>(args[fused ? 8 : 4]), *frame = *static_cast<int **>(args[fused ? 9 : 5]), *votes = *static_cast<int **>(args[fused ? 10 : 6]);
+    fill_candidates(nq, cn, n_cand, frame, votes);
+    if (fused) fill_offsets(nq, cn, n_cand, votes, *static_cast<long long **>(args[11]), *static_cast<u32 **>(args[12]));
+  } else if (S.stages && strstr(name, "cand_prefix_kernel")) {
+    fill_offsets(*static_cast<int *>(args[3]), *static_cast<int *>(args[2]), *static_cast<int **>(args[0]), *static_cast<int **>(args[1]),
+                 *static_cast<long long **>(args[4]), *static_cast<u32 **>(args[5]));
+  } else if (S.stages && strstr(name, "verify_solve_kernel")) {
+    const kernels_of_the_engine::VerifyParams &P = *static_cast<const kernels_of_the_engine::VerifyParams *>(args[0]);
+    const int nq = stage_head(S, P, 0);
+    REQUIRE(room_of(P.pose) >= (size_t)P.n_blocks * 12 * 8 && room_of(P.pair_off) >= (size_t)nq * (P.cand_num + 1) * 8);
+    for (u32 b = 0; b < P.n_blocks; b++) {
+      const bool live = (int)(b % (u32)P.cand_num) < P.n_cand[b / (u32)P.cand_num];
+      P.score[b] = (live && b % 11 != 5) ? 0.05 + 0.001 * (double)((b * 37u) % 800u) : -1.0;
+      for (int i = 0; i < 12; i++) P.pose[(size_t)b * 12 + i] = P.score[b] >= 0.0 ? (i % 4 == 0 && i < 9 ? 1.0 : 0.0) + 0.001 * (double)((b + i) % 17u) + (i >= 9 ? (double)(b % 13u) : 0.0) : 0.0;
+    }
+  } else if (S.stages && strstr(name, "refine_kernel")) {
+    const kernels_of_the_engine::RefineParams &P = *static_cast<const kernels_of_the_engine::RefineParams *>(args[0]);
+    const int nq = stage_head(S, P, 1);
+    const size_t nb = P.n_blocks;
+    REQUIRE(room_of(P.v_pose) >= nb * 12 * 8 && room_of(P.pair_off) >= (size_t)nq * (P.cand_num + 1) * 8 && room_of(P.q_pair_base) >= (size_t)(nq + 1) * 4);
+    REQUIRE(room_of(P.pose) >= nb * 12 * 8 && room_of(P.rmse) >= nb * 8 && room_of(P.rmse_verify) >= nb * 8 && room_of(P.n_pairs) >= nb * 4 && room_of(P.moments) >= nb * 15 * 8);
+    // every list lies inside the flags of the verification and, from the second iteration on, inside each half of the stage's own
+    for (int q = 0; q < nq; q++) {
+      const size_t end = (size_t)P.q_pair_base[q] + (size_t)P.pair_off[(size_t)q * (P.cand_num + 1) + P.cand_num];
+      REQUIRE(end <= P.flag_half);
+      if (end) REQUIRE(room_of(P.v_inlier) >= end);
+    }
+    if (P.iterations > 1) REQUIRE(room_of(P.flag) >= 2 * P.flag_half);
+    for (u32 b = 0; b < P.n_blocks; b++) {
+      const bool live = slot_live(P, b) && b % 13 != 4;       // (a candidate without a result has no pairs)
+      for (int i = 0; i < 12; i++) P.pose[(size_t)b * 12 + i] = live ? P.v_pose[(size_t)b * 12 + i] + 0.25 : 0.0;
+      P.rmse[b] = live ? 0.125 * (double)(b % 9u) : kNaN;
+      P.rmse_verify[b] = live ? 0.5 + 0.125 * (double)(b % 7u) : kNaN;
+      P.n_pairs[b] = live ? 3 + (int)(b % 5u) : 0;
+      for (int i = 0; i < 15; i++) P.moments[(size_t)b * 15 + i] = live ? (double)b + (double)i / 16.0 : kNaN;
+    }
+  } else if (S.stages && strstr(name, "overlap_kernel")) {
+    const kernels_of_the_engine::OverlapParams &P = *static_cast<const kernels_of_the_engine::OverlapParams *>(args[0]);
+    const int nq = stage_head(S, P, 2);
+    keypoint_room(P, nq);
+    REQUIRE(room_of(P.cnt) >= (size_t)P.n_blocks * 16 && room_of(P.val) >= (size_t)P.n_blocks * 16);
+    for (u32 b = 0; b < P.n_blocks; b++) {
+      const bool live = slot_live(P, b);
+      const int q = (int)(b / (u32)P.cand_num), nqk = (int)(P.q_off[q + 1] - P.q_off[q]);
+      // (the second value is the pose the pass was handed: sgtd_verify's or sgtd_refine_poses')
+      P.cnt[b] = live ? make_int4(nqk, 10 + (int)(b % 20u), (int)(b % 7u), (int)(b % 5u)) : make_int4(-1, -1, -1, -1);
+      P.val[b] = live ? make_double2((double)(b % 10u) / 10.0, P.pose[(size_t)b * 12]) : make_double2(kNaN, kNaN);
+    }
+  } else if (S.stages && strstr(name, "align_kernel")) {
+    const kernels_of_the_engine::AlignParams &P = *static_cast<const kernels_of_the_engine::AlignParams *>(args[0]);
+    const int nq = stage_head(S, P, 3);
+    keypoint_room(P, nq);
+    const size_t nb = P.n_blocks, total = (size_t)(P.q_off[nq] - P.q_off[0]);
+    REQUIRE(room_of(P.o_pose) >= nb * 12 * 8 && room_of(P.fit) >= nb * 16 && room_of(P.cnt) >= nb * 32 && room_of(P.val) >= nb * 32 && room_of(P.moments) >= nb * 15 * 8);
+    REQUIRE(room_of(P.assign) >= std::max<size_t>(total * (size_t)P.cand_num, 1) * 4);
+    for (u32 b = 0; b < P.n_blocks; b++) {
+      const bool live = slot_live(P, b) && b % 17 != 2;        // (stop -1: a candidate without a result)
+      const int q = (int)(b / (u32)P.cand_num), c = (int)(b % (u32)P.cand_num), nqk = (int)(P.q_off[q + 1] - P.q_off[q]);
+      for (int i = 0; i < 12; i++) P.o_pose[(size_t)b * 12 + i] = live ? P.pose[(size_t)b * 12 + i] + 0.5 : 0.0;
+      for (int i = 0; i < 15; i++) P.moments[(size_t)b * 15 + i] = live ? 0.5 * (double)b + (double)i / 16.0 : kNaN;
+      P.fit[b] = live ? make_int4(1 + (int)(b % 3u), (int)(b % 9u), (int)(b % 3u), 0) : make_int4(0, 0, -1, 0);
+      P.cnt[(size_t)b * 2] = live ? make_int4(nqk, 10 + (int)(b % 20u), (int)(b % 7u), (int)(b % 5u)) : make_int4(-1, -1, -1, -1);
+      P.cnt[(size_t)b * 2 + 1] = live ? make_int4(nqk, 10 + (int)(b % 20u), (int)(b % 8u), (int)(b % 6u)) : make_int4(-1, -1, -1, -1);
+      const double rms_after = b % 6 == 1 ? kNaN : 0.25 + 0.03125 * (double)(b % 23u);
+      const double v[4] = {(double)(b % 7u) / 8.0, P.pose[(size_t)b * 12], (double)(b % 10u) / 10.0, rms_after};
+      for (int i = 0; i < 4; i++) P.val[(size_t)b * 4 + i] = live ? v[i] : kNaN;
+      int *asg = P.assign + (size_t)(P.q_off[q] - P.q_off[0]) * (size_t)P.cand_num + (size_t)c * (size_t)nqk;
+      for (int j = 0; j < nqk; j++) asg[j] = live ? (j * 7 + c + q) % 19 - 1 : -1;
+    }
   } else if (strstr(name, "pack_frame_kernel")) {
     S.packs++;
     const int cn = *static_cast<int *>(args[12]);
@@ -162,11 +314,470 @@ Descs random_descs(std::mt19937 &rng, size_t n, uint32_t frame) {
   }
   return d;
 }
+
+// ---- the stages on a verified batch: sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints and what reads their results ----
+// One line per call goes to the transcript (if one is asked for): the call, its status, the handle's error text, the stand-in's
+// launch, copy and wait counts, a hash of every output array.  Two builds of the engine behave alike if their transcripts are equal.
+FILE *g_transcript = nullptr;
+void hash_bytes(u64 &h, const void *p, size_t n) {
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; }
+}
+template <class... V> void logged(int line, int expect, const char *call, sgtd_handle h, int st, const V &...outs) {
+  u64 hash = 1469598103934665603ull;
+  (void)std::initializer_list<int>{(hash_bytes(hash, outs.data(), outs.size() * sizeof(outs[0])), 0)...};
+  if (g_transcript)
+    fprintf(g_transcript, "%s = %d \"%s\" launches %llu copies %llu waits %llu out %016llx\n", call, st, sgtd_last_error(h), sgtd_stub_launches(),
+            sgtd_stub_copies(), sgtd_stub_waits(), (unsigned long long)hash);
+  if (st != expect) { fprintf(stderr, "engine_driver: %s = %d, not %d, at line %d (%s)\n", call, st, expect, line, sgtd_last_error(h)); exit(1); }
+}
+#define CALL(expect, h, call, ...) logged(__LINE__, expect, #call, h, (call), ##__VA_ARGS__)
+
+bool same(double a, double b) { return std::memcmp(&a, &b, sizeof(a)) == 0 || (std::isnan(a) && std::isnan(b)); }
+bool same(const double *a, const double *b, size_t n) { for (size_t i = 0; i < n; i++) if (!same(a[i], b[i])) return false; return true; }
+
+struct Keypoints {        // of some frames or queries: offsets, positions, labels
+  std::vector<int64_t> off{0};
+  std::vector<float> xyz;
+  std::vector<uint32_t> label;
+  void add(std::mt19937 &rng, int n) {
+    std::uniform_real_distribution<float> u(-20.f, 20.f);
+    for (int i = 0; i < n; i++) { for (int k = 0; k < 3; k++) xyz.push_back(u(rng)); label.push_back(3 + rng() % 9); }
+    if (xyz.empty()) xyz.reserve(3);
+    if (label.empty()) label.reserve(1);
+    off.push_back((int64_t)label.size());
+  }
+};
+
+// one query's results as the public getters give them
+struct Results {
+  int cn;
+  std::vector<int32_t> n_cand, frame;       // of the whole batch
+  std::vector<int64_t> pair_off;            // of the whole batch: [nq][cn + 1]
+  std::vector<int32_t> p_q; std::vector<int64_t> p_entry, i_off, i_entry; std::vector<int32_t> i_q;      // match lists and inlier pairs
+  std::vector<double> score, pose;
+  std::vector<double> r_pose, rmse, rmse_v, r_mom; std::vector<int32_t> np;
+  std::vector<int32_t> o_cnt[4]; std::vector<double> o_ov, o_rms;
+  std::vector<double> a_pose, a_mom, a_val[4]; std::vector<int32_t> a_fit[3], a_cnt[2];
+  explicit Results(int cn_, int nq) : cn(cn_), n_cand((size_t)nq), frame((size_t)nq * cn_), pair_off((size_t)nq * (cn_ + 1)), i_off((size_t)cn_ + 1), score(cn_), pose((size_t)cn_ * 12), r_pose((size_t)cn_ * 12), rmse(cn_), rmse_v(cn_),
+      r_mom((size_t)cn_ * 15), np(cn_), o_ov(cn_), o_rms(cn_), a_pose((size_t)cn_ * 12), a_mom((size_t)cn_ * 15) {
+    for (auto &v : o_cnt) v.resize(cn_);
+    for (auto &v : a_val) v.resize(cn_);
+    for (auto &v : a_fit) v.resize(cn_);
+    for (auto &v : a_cnt) v.resize((size_t)cn_ * 4);
+  }
+  void candidates(sgtd_handle h) { CALL(SGTD_OK, h, sgtd_result_candidates(h, n_cand.data(), frame.data(), nullptr, pair_off.data()), n_cand, frame, pair_off); }
+  // query q's match lists (all of them: their total is the last offset) and inlier pairs (how many first, then the pairs)
+  void lists(sgtd_handle h, int q) {
+    std::vector<int64_t> n(1, -1);
+    const size_t total = (size_t)pair_off[(size_t)q * (cn + 1) + cn];
+    p_q.assign(total + 1, -7); p_entry.assign(total + 1, -7);
+    if (total > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_pairs(h, q, p_q.data(), p_entry.data(), (int64_t)total - 1, n.data()), n);
+    CALL(SGTD_OK, h, sgtd_result_pairs(h, q, p_q.data(), p_entry.data(), (int64_t)total, n.data()), p_q, p_entry, n);
+    REQUIRE(n[0] == (int64_t)total && p_q[total] == -7 && p_entry[total] == -7);
+    const int st = sgtd_result_inlier_pairs(h, q, i_off.data(), nullptr, nullptr, 0, n.data());
+    REQUIRE(st == SGTD_OK || st == SGTD_ERR_CAPACITY);
+    i_q.assign((size_t)n[0] + 1, -7); i_entry.assign((size_t)n[0] + 1, -7);
+    CALL(SGTD_OK, h, sgtd_result_inlier_pairs(h, q, i_off.data(), i_q.data(), i_entry.data(), n[0], n.data()), i_off, i_q, i_entry, n);
+    REQUIRE(i_off[(size_t)cn] == n[0] && i_q[(size_t)n[0]] == -7);
+  }
+  void verify(sgtd_handle h, int q) { CALL(SGTD_OK, h, sgtd_result_verify(h, q, score.data(), pose.data()), score, pose); }
+  void refined(sgtd_handle h, int q) { CALL(SGTD_OK, h, sgtd_result_refined(h, q, r_pose.data(), rmse.data(), rmse_v.data(), np.data(), r_mom.data()), r_pose, rmse, rmse_v, np, r_mom); }
+  void overlap(sgtd_handle h, int q) {
+    CALL(SGTD_OK, h, sgtd_result_overlap(h, q, o_cnt[0].data(), o_cnt[1].data(), o_cnt[2].data(), o_cnt[3].data(), o_ov.data(), o_rms.data()), o_cnt[0], o_cnt[1], o_cnt[2], o_cnt[3], o_ov, o_rms);
+  }
+  void aligned(sgtd_handle h, int q) {
+    CALL(SGTD_OK, h, sgtd_result_aligned(h, q, a_pose.data(), a_fit[0].data(), a_fit[1].data(), a_fit[2].data(), a_cnt[0].data(), a_cnt[1].data(), a_val[0].data(), a_val[1].data(),
+                                         a_val[2].data(), a_val[3].data(), a_mom.data()), a_pose, a_fit[0], a_fit[1], a_fit[2], a_cnt[0], a_cnt[1], a_val[0], a_val[1], a_val[2], a_val[3], a_mom);
+  }
+};
+
+struct Stages {
+  sgtd_handle h = nullptr;
+  int n_dev = 1, cn = 0, n_frames = 130;
+  std::vector<float> map_pose;            // [n_frames][12]; frame 5 has none
+  std::vector<char> has_pose;
+  Keypoints own, theirs;                  // the batch's keypoints, and others the caller passes to a keypoint pass
+  std::vector<int> kp_count;              // of the batch's queries: whose keypoints a pass ran on (own or theirs)
+  bool refined = false, overlapped = false, aligned = false;
+
+  // the world pose of candidate k as include/sgtd_accel.h states it: every operation an f32 rounding, NaN where there is none
+  void check_world(const std::vector<float> &world, int n_cand, const int32_t *frame, const double *pose, const std::vector<char> &has) const {
+    for (int k = 0; k < cn; k++) {
+      float w[12];
+      for (float &x : w) x = std::numeric_limits<float>::quiet_NaN();
+      const bool live = k < n_cand && has[(size_t)k] && frame[k] >= 0 && frame[k] < n_frames && has_pose[(size_t)frame[k]];
+      if (live) {
+        const float *M = map_pose.data() + (size_t)frame[k] * 12;
+        float R[9], t[3];
+        for (int i = 0; i < 9; i++) R[i] = (float)pose[(size_t)k * 12 + i];
+        for (int i = 0; i < 3; i++) t[i] = (float)pose[(size_t)k * 12 + 9 + i];
+        for (int i = 0; i < 3; i++) {
+          const float *m = M + i * 4;
+          for (int j = 0; j < 3; j++) w[i * 4 + j] = (m[0] * R[j] + m[1] * R[3 + j]) + m[2] * R[6 + j];
+          w[i * 4 + 3] = ((m[0] * t[0] + m[1] * t[1]) + m[2] * t[2]) + m[3];
+        }
+      }
+      for (int i = 0; i < 12; i++) REQUIRE(live ? std::memcmp(&w[i], &world[(size_t)k * 12 + i], 4) == 0 : std::isnan(world[(size_t)k * 12 + i]));
+    }
+  }
+
+  // every getter of every query of a verified batch, with what can be derived from them asserted; on a handle of several
+  // "devices" each merged candidate's results against its owner's own getters
+  void read_all(int nq) {
+    Results r(cn, nq);
+    r.candidates(h);
+    std::vector<Results> dev;
+    for (int s = 0; s < n_dev && n_dev > 1; s++) { dev.emplace_back(cn, nq); dev.back().candidates(sgtd_device_handle(h, s)); }
+    std::vector<float> world((size_t)cn * 12);
+    std::vector<char> has((size_t)cn);
+    std::vector<std::vector<double>> all_score, all_ov, all_a_ov, all_a_rms; std::vector<std::vector<int32_t>> all_stop;
+    for (int q = 0; q < nq; q++) {
+      const int nc = r.n_cand[(size_t)q];
+      const int32_t *frame = r.frame.data() + (size_t)q * cn;
+      r.verify(h, q);
+      r.lists(h, q);
+      all_score.push_back(r.score);
+      CALL(SGTD_OK, h, sgtd_result_world_poses(h, q, world.data()), world);
+      for (int k = 0; k < cn; k++) has[(size_t)k] = r.score[(size_t)k] >= 0.0;
+      check_world(world, nc, frame, r.pose.data(), has);
+      if (refined) {
+        r.refined(h, q);
+        CALL(SGTD_OK, h, sgtd_result_refined_world_poses(h, q, world.data()), world);
+        for (int k = 0; k < cn; k++) has[(size_t)k] = r.np[(size_t)k] > 0;
+        check_world(world, nc, frame, r.r_pose.data(), has);
+      }
+      if (overlapped) {
+        r.overlap(h, q);
+        all_ov.push_back(r.o_ov);
+        for (int k = 0; k < nc; k++) REQUIRE(r.o_cnt[0][(size_t)k] == -1 || r.o_cnt[0][(size_t)k] == kp_count[(size_t)q]);
+      }
+      std::vector<std::vector<int32_t>> asg((size_t)cn);
+      if (aligned) {
+        r.aligned(h, q);
+        all_stop.push_back(r.a_fit[2]); all_a_ov.push_back(r.a_val[2]); all_a_rms.push_back(r.a_val[3]);
+        CALL(SGTD_OK, h, sgtd_result_aligned_world_poses(h, q, world.data()), world);
+        for (int k = 0; k < cn; k++) has[(size_t)k] = r.a_fit[2][(size_t)k] >= 0;
+        check_world(world, nc, frame, r.a_pose.data(), has);
+        // every candidate's assignment: its length with no array, a capacity one short, all of it
+        for (int k = 0; k < nc; k++) {
+          std::vector<int64_t> n(1, -1);
+          CALL(SGTD_OK, h, sgtd_result_aligned_pairs(h, q, k, nullptr, 0, n.data()), n);
+          REQUIRE(n[0] == kp_count[(size_t)q]);
+          asg[(size_t)k].assign((size_t)n[0] + 1, -7);
+          if (n[0] > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_aligned_pairs(h, q, k, asg[(size_t)k].data(), n[0] - 1, n.data()), n);
+          CALL(SGTD_OK, h, sgtd_result_aligned_pairs(h, q, k, asg[(size_t)k].data(), n[0], n.data()), asg[(size_t)k], n);
+          REQUIRE(asg[(size_t)k][(size_t)n[0]] == -7);
+        }
+        std::vector<int64_t> n(1, -1);
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_aligned_pairs(h, q, nc, nullptr, 0, n.data()));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_aligned_pairs(h, q, 0, nullptr, 0, nullptr));
+      }
+      if (n_dev == 1) continue;
+      // ---- the gather from the owners
+      std::vector<Results> &d = dev;
+      for (int s = 0; s < n_dev; s++) {
+        sgtd_handle c = sgtd_device_handle(h, s);
+        d[(size_t)s].verify(c, q);
+        d[(size_t)s].lists(c, q);
+        if (refined) d[(size_t)s].refined(c, q);
+        if (overlapped) d[(size_t)s].overlap(c, q);
+        if (aligned) d[(size_t)s].aligned(c, q);
+      }
+      int from[2] = {0, 0};
+      for (int k = 0; k < cn; k++) {
+        if (k >= nc) {        // no candidate: what the handle states for an empty slot
+          REQUIRE(r.score[(size_t)k] == -1.0);
+          for (int i = 0; i < 12; i++) REQUIRE(r.pose[(size_t)k * 12 + i] == 0.0);
+          if (refined) REQUIRE(r.np[(size_t)k] == 0 && std::isnan(r.rmse[(size_t)k]) && std::isnan(r.rmse_v[(size_t)k]) && std::isnan(r.r_mom[(size_t)k * 15]) && r.r_pose[(size_t)k * 12] == 0.0);
+          if (overlapped) REQUIRE(r.o_cnt[0][(size_t)k] == -1 && r.o_cnt[3][(size_t)k] == -1 && std::isnan(r.o_ov[(size_t)k]) && std::isnan(r.o_rms[(size_t)k]));
+          if (aligned) REQUIRE(r.a_fit[0][(size_t)k] == 0 && r.a_fit[1][(size_t)k] == 0 && r.a_fit[2][(size_t)k] == -1 && r.a_cnt[0][(size_t)k * 4] == -1 && r.a_cnt[1][(size_t)k * 4 + 3] == -1 &&
+                               std::isnan(r.a_val[0][(size_t)k]) && std::isnan(r.a_val[3][(size_t)k]) && std::isnan(r.a_mom[(size_t)k * 15]) && r.a_pose[(size_t)k * 12] == 0.0);
+          continue;
+        }
+        // the owner: the shard of the merged (global) frame id; the slot: where the owner's own table has the frame's local id
+        const uint32_t g = (uint32_t)frame[k];
+        const int s = (int)((g / 64u) % (uint32_t)n_dev);
+        const int32_t local = (int32_t)((g / (64u * (uint32_t)n_dev)) * 64u + g % 64u);
+        const Results &o = d[(size_t)s];
+        int ks = -1;
+        for (int j = 0; j < o.n_cand[(size_t)q]; j++) if (o.frame[(size_t)q * cn + j] == local) ks = j;
+        REQUIRE(ks >= 0);
+        from[s]++;
+        REQUIRE(same(r.score[(size_t)k], o.score[(size_t)ks]) && same(&r.pose[(size_t)k * 12], &o.pose[(size_t)ks * 12], 12));
+        {     // its match list and inlier pairs: the owner's, the owner in the entry ids' upper bits
+          const int64_t *mo = &r.pair_off[(size_t)q * (cn + 1) + k], *oo = &o.pair_off[(size_t)q * (cn + 1) + ks];
+          REQUIRE(mo[1] - mo[0] == oo[1] - oo[0] && r.i_off[(size_t)k + 1] - r.i_off[(size_t)k] == o.i_off[(size_t)ks + 1] - o.i_off[(size_t)ks]);
+          for (int64_t j = 0; j < mo[1] - mo[0]; j++)
+            REQUIRE(r.p_q[(size_t)(mo[0] + j)] == o.p_q[(size_t)(oo[0] + j)] && r.p_entry[(size_t)(mo[0] + j)] == (((int64_t)s << 40) | o.p_entry[(size_t)(oo[0] + j)]));
+          for (int64_t j = 0; j < r.i_off[(size_t)k + 1] - r.i_off[(size_t)k]; j++)
+            REQUIRE(r.i_q[(size_t)(r.i_off[(size_t)k] + j)] == o.i_q[(size_t)(o.i_off[(size_t)ks] + j)] &&
+                    r.i_entry[(size_t)(r.i_off[(size_t)k] + j)] == (((int64_t)s << 40) | o.i_entry[(size_t)(o.i_off[(size_t)ks] + j)]));
+        }
+        if (refined) REQUIRE(same(&r.r_pose[(size_t)k * 12], &o.r_pose[(size_t)ks * 12], 12) && same(r.rmse[(size_t)k], o.rmse[(size_t)ks]) && same(r.rmse_v[(size_t)k], o.rmse_v[(size_t)ks]) &&
+                             r.np[(size_t)k] == o.np[(size_t)ks] && same(&r.r_mom[(size_t)k * 15], &o.r_mom[(size_t)ks * 15], 15));
+        if (overlapped) {
+          for (int a = 0; a < 4; a++) REQUIRE(r.o_cnt[a][(size_t)k] == o.o_cnt[a][(size_t)ks]);
+          REQUIRE(same(r.o_ov[(size_t)k], o.o_ov[(size_t)ks]) && same(r.o_rms[(size_t)k], o.o_rms[(size_t)ks]));
+        }
+        if (aligned) {
+          REQUIRE(same(&r.a_pose[(size_t)k * 12], &o.a_pose[(size_t)ks * 12], 12) && same(&r.a_mom[(size_t)k * 15], &o.a_mom[(size_t)ks * 15], 15));
+          for (int a = 0; a < 3; a++) REQUIRE(r.a_fit[a][(size_t)k] == o.a_fit[a][(size_t)ks]);
+          for (int a = 0; a < 2; a++) REQUIRE(std::memcmp(&r.a_cnt[a][(size_t)k * 4], &o.a_cnt[a][(size_t)ks * 4], 16) == 0);
+          for (int a = 0; a < 4; a++) REQUIRE(same(r.a_val[a][(size_t)k], o.a_val[a][(size_t)ks]));
+          std::vector<int32_t> mine((size_t)kp_count[(size_t)q] + 1, -7);
+          std::vector<int64_t> n(1, -1);
+          sgtd_handle c = sgtd_device_handle(h, s);
+          CALL(SGTD_OK, c, sgtd_result_aligned_pairs(c, q, ks, mine.data(), kp_count[(size_t)q], n.data()), mine, n);
+          REQUIRE(mine == asg[(size_t)k]);
+        }
+      }
+      if (nc == cn) REQUIRE(from[0] > 0 && from[1] > 0);       // (a full merged list draws on both owners)
+    }
+    // ---- the three search loops, against their rules over the public results
+    std::vector<int32_t> bc((size_t)nq), bf((size_t)nq);
+    std::vector<double> bs((size_t)nq), bo((size_t)nq);
+    CALL(SGTD_OK, h, sgtd_search_loop(h, 0.4, bc.data(), bf.data(), bs.data()), bc, bf, bs);
+    auto pick_score = [&](int q, double thr, double min_ov, int *cand, double *score) {     // the highest score above thr (the first of equals)
+      *cand = -1; *score = 0.0;
+      for (int c = 0; c < r.n_cand[(size_t)q]; c++) {
+        if (min_ov > 0.0 && !(all_ov[(size_t)q][(size_t)c] >= min_ov)) continue;
+        if (all_score[(size_t)q][(size_t)c] > *score) { *score = all_score[(size_t)q][(size_t)c]; *cand = c; }
+      }
+      if (!(*cand >= 0 && *score > thr)) { *cand = -1; *score = 0.0; }
+    };
+    for (int q = 0; q < nq && n_dev > 1; q++) {     // (on one device the rule runs in a kernel: nothing to compare with here)
+      int c; double sc;
+      pick_score(q, 0.4, 0.0, &c, &sc);
+      REQUIRE(bc[(size_t)q] == c && same(bs[(size_t)q], sc) && bf[(size_t)q] == (c >= 0 ? r.frame[(size_t)q * cn + c] : -1));
+    }
+    for (double min_ov : {0.0, 0.5}) {
+      if (min_ov > 0.0 && !overlapped) {
+        CALL(SGTD_ERR_STATE, h, sgtd_search_loop_overlap(h, 0.4, min_ov, bc.data(), bf.data(), bs.data(), bo.data()));
+        continue;
+      }
+      CALL(SGTD_OK, h, sgtd_search_loop_overlap(h, 0.4, min_ov, bc.data(), bf.data(), bs.data(), bo.data()), bc, bf, bs, bo);
+      for (int q = 0; q < nq; q++) {
+        int c; double sc;
+        pick_score(q, 0.4, min_ov, &c, &sc);
+        REQUIRE(bc[(size_t)q] == c && same(bs[(size_t)q], sc) && bf[(size_t)q] == (c >= 0 ? r.frame[(size_t)q * cn + c] : -1));
+        REQUIRE(same(bo[(size_t)q], c >= 0 && overlapped ? all_ov[(size_t)q][(size_t)c] : kNaN));
+      }
+    }
+    if (!aligned) {
+      CALL(SGTD_ERR_STATE, h, sgtd_search_loop_aligned(h, 0.0, 0.0, bc.data(), bf.data(), bs.data(), bo.data()));
+      return;
+    }
+    const double bounds[3][2] = {{0.0, 0.0}, {0.5, 0.0}, {0.3, 0.6}};
+    for (const double *b : bounds) {
+      CALL(SGTD_OK, h, sgtd_search_loop_aligned(h, b[0], b[1], bc.data(), bf.data(), bs.data(), bo.data()), bc, bf, bs, bo);
+      for (int q = 0; q < nq; q++) {       // the lowest rms after alignment inside the bounds; of equals the higher score, then the first
+        int best = -1;
+        const std::vector<double> &rms = all_a_rms[(size_t)q], &ov = all_a_ov[(size_t)q], &sc = all_score[(size_t)q];
+        for (int c = 0; c < r.n_cand[(size_t)q]; c++) {
+          if (all_stop[(size_t)q][(size_t)c] < 0 || std::isnan(rms[(size_t)c])) continue;
+          if (b[0] > 0.0 && !(ov[(size_t)c] >= b[0])) continue;
+          if (b[1] > 0.0 && !(rms[(size_t)c] <= b[1])) continue;
+          if (best < 0 || rms[(size_t)c] < rms[(size_t)best] || (rms[(size_t)c] == rms[(size_t)best] && sc[(size_t)c] > sc[(size_t)best])) best = c;
+        }
+        REQUIRE(bc[(size_t)q] == best && bf[(size_t)q] == (best >= 0 ? r.frame[(size_t)q * cn + best] : -1));
+        REQUIRE(same(bs[(size_t)q], best >= 0 ? rms[(size_t)best] : kNaN) && same(bo[(size_t)q], best >= 0 ? ov[(size_t)best] : kNaN));
+      }
+    }
+  }
+
+  // the state errors of a batch none of whose stage results exist (any more)
+  void nothing_to_read() {
+    std::vector<double> d((size_t)cn * 15);
+    std::vector<int32_t> i((size_t)cn * 4);
+    std::vector<float> w((size_t)cn * 12);
+    std::vector<int64_t> n(1);
+    CALL(SGTD_ERR_STATE, h, sgtd_result_refined(h, 0, d.data(), nullptr, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_STATE, h, sgtd_result_refined_world_poses(h, 0, w.data()));
+    CALL(SGTD_ERR_STATE, h, sgtd_result_overlap(h, 0, i.data(), nullptr, nullptr, nullptr, d.data(), nullptr));
+    CALL(SGTD_ERR_STATE, h, sgtd_search_loop_overlap(h, 0.4, 0.5, i.data(), nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_STATE, h, sgtd_result_aligned(h, 0, d.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_STATE, h, sgtd_result_aligned_pairs(h, 0, 0, nullptr, 0, n.data()));
+    CALL(SGTD_ERR_STATE, h, sgtd_result_aligned_world_poses(h, 0, w.data()));
+    CALL(SGTD_ERR_STATE, h, sgtd_search_loop_aligned(h, 0.0, 0.0, i.data(), nullptr, nullptr, nullptr));
+    refined = overlapped = aligned = false;
+  }
+  void stages_refuse(int expect) {       // the three stages where the batch is not verified
+    CALL(expect, h, sgtd_refine_poses(h, 1));
+    CALL(expect, h, sgtd_overlap(h, 0.5, 0, nullptr, nullptr, nullptr));
+    CALL(expect, h, sgtd_overlap(h, 0.5, 0, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+    CALL(expect, h, sgtd_align_keypoints(h, 0.5, 3, 0, nullptr, nullptr, nullptr));
+    CALL(expect, h, sgtd_align_keypoints(h, 0.5, 3, 0, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+  }
+  void counts_of(const Keypoints &k, int nq) { kp_count.resize((size_t)nq); for (int q = 0; q < nq; q++) kp_count[(size_t)q] = (int)(k.off[(size_t)q + 1] - k.off[(size_t)q]); }
+  void frames_batch(std::mt19937 &rng, int nq) {
+    own = Keypoints(); theirs = Keypoints();
+    for (int q = 0; q < nq; q++) { own.add(rng, q == 2 ? 0 : 12 + q % 5); theirs.add(rng, 7 + q % 3); }
+    CALL(SGTD_OK, h, sgtd_query_frames(h, own.xyz.data(), own.label.data(), own.off.data(), nq, 0));
+    refined = overlapped = aligned = false;
+  }
+
+  void run(Scenario &S, const sgtd_config &cfg, std::mt19937 &rng, int n_dev_) {
+    n_dev = n_dev_; cn = cfg.candidate_num;
+    S.stages = true; S.expect_order = -1;
+    if (n_dev == 1) OK(sgtd_create(&cfg, &h));
+    else { const int ids[2] = {0, 0}; OK(sgtd_create_multi(&cfg, ids, 2, &h)); }
+    g_last = h;
+    for (int f = 0; f < n_frames; f++) { Descs d = random_descs(rng, 60, (uint32_t)f); sgtd_desc_soa s = d.soa(); OK(sgtd_add(h, &s, 60)); }
+    OK(sgtd_finalize(h));
+    // ---- the map's poses (all frames but 5) and keypoints (all but 9; frame 11 has an empty set); a set of 65536 is refused
+    std::uniform_real_distribution<float> u(-1.f, 1.f);
+    std::vector<uint32_t> ids;
+    Keypoints map_kp;
+    map_pose.assign((size_t)n_frames * 12, 0.f); has_pose.assign((size_t)n_frames, 0);
+    std::vector<float> rows;
+    for (int f = 0; f < n_frames; f++) {
+      if (f == 5) continue;
+      ids.push_back((uint32_t)f); has_pose[(size_t)f] = 1;
+      for (int i = 0; i < 12; i++) { map_pose[(size_t)f * 12 + i] = u(rng) * (i % 4 == 3 ? 50.f : 1.f); rows.push_back(map_pose[(size_t)f * 12 + i]); }
+    }
+    CALL(SGTD_OK, h, sgtd_set_frame_poses(h, ids.data(), rows.data(), (int64_t)ids.size()));
+    ids.clear();
+    for (int f = 0; f < n_frames; f++) {
+      if (f == 9) continue;
+      ids.push_back((uint32_t)f);
+      map_kp.add(rng, f == 11 ? 0 : 20 + f % 7);
+    }
+    CALL(SGTD_OK, h, sgtd_set_frame_keypoints(h, ids.data(), map_kp.off.data(), map_kp.xyz.data(), map_kp.label.data(), (int64_t)ids.size()));
+    {
+      const uint32_t one[1] = {3};
+      const int64_t big[2] = {0, 65536}, most[2] = {0, 65535};
+      std::vector<float> xyz((size_t)65536 * 3, 1.f);
+      std::vector<uint32_t> lab(65536, 4u);
+      CALL(SGTD_ERR_INVALID, h, sgtd_set_frame_keypoints(h, one, big, xyz.data(), lab.data(), 1));
+      CALL(SGTD_OK, h, sgtd_set_frame_keypoints(h, one, most, xyz.data(), lab.data(), 1));
+      CALL(SGTD_OK, h, sgtd_set_frame_keypoints(h, one, map_kp.off.data() + 3, map_kp.xyz.data(), map_kp.label.data(), 1));
+    }
+    // ---- no batch yet: every stage and every getter refuses
+    theirs.add(rng, 5);
+    stages_refuse(SGTD_ERR_STATE);
+    nothing_to_read();
+
+    // ---- a batch of nine query frames: the stages before sgtd_verify; each getter before its stage; *_REFINED before
+    // sgtd_refine_poses; each stage with the batch's own keypoints and with the caller's, from sgtd_verify's poses and
+    // from the refined ones; every getter after every step
+    const int nq = 9;
+    frames_batch(rng, nq);
+    stages_refuse(SGTD_ERR_STATE);
+    CALL(SGTD_OK, h, sgtd_verify(h));
+    nothing_to_read();
+    read_all(nq);
+    CALL(SGTD_ERR_STATE, h, sgtd_overlap(h, 0.5, SGTD_OVERLAP_REFINED, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_STATE, h, sgtd_align_keypoints(h, 0.5, 3, SGTD_ALIGN_REFINED, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_overlap(h, -1.0, 0, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_overlap(h, 0.5, 2, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_overlap(h, 0.5, 0, theirs.xyz.data(), nullptr, theirs.off.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_align_keypoints(h, 0.5, 0, 0, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_align_keypoints(h, 0.5, 3, 2, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_refine_poses(h, 0));
+    {     // a query with 65536 keypoints (the count is refused before anything is read); and that mistake together with a missing refit
+      std::vector<int64_t> off(theirs.off);
+      for (int q = 4; q <= nq; q++) off[(size_t)q] += 65536 - (theirs.off[4] - theirs.off[3]);
+      CALL(SGTD_ERR_INVALID, h, sgtd_overlap(h, 0.5, 0, theirs.xyz.data(), theirs.label.data(), off.data()));
+      CALL(SGTD_ERR_INVALID, h, sgtd_align_keypoints(h, 0.5, 3, 0, theirs.xyz.data(), theirs.label.data(), off.data()));
+      CALL(SGTD_ERR_INVALID, h, sgtd_overlap(h, 0.5, SGTD_OVERLAP_REFINED, theirs.xyz.data(), theirs.label.data(), off.data()));
+      CALL(SGTD_ERR_INVALID, h, sgtd_align_keypoints(h, 0.5, 3, SGTD_ALIGN_REFINED, theirs.xyz.data(), theirs.label.data(), off.data()));
+    }
+    counts_of(theirs, nq);
+    CALL(SGTD_OK, h, sgtd_overlap(h, 0.5, 0, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+    overlapped = true;
+    read_all(nq);
+    counts_of(own, nq);
+    CALL(SGTD_OK, h, sgtd_overlap(h, 0.5, 0, nullptr, nullptr, nullptr));
+    read_all(nq);
+    CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.5, 3, 0, nullptr, nullptr, nullptr));
+    aligned = true;
+    read_all(nq);
+    CALL(SGTD_OK, h, sgtd_refine_poses(h, 1));
+    refined = true;
+    read_all(nq);
+    CALL(SGTD_OK, h, sgtd_refine_poses(h, 3));
+    counts_of(theirs, nq);
+    CALL(SGTD_OK, h, sgtd_overlap(h, 0.5, SGTD_OVERLAP_REFINED, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+    CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.5, 2, SGTD_ALIGN_REFINED, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+    read_all(nq);
+    counts_of(own, nq);
+    CALL(SGTD_OK, h, sgtd_overlap(h, 0.5, SGTD_OVERLAP_REFINED, nullptr, nullptr, nullptr));
+    CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.5, 1, SGTD_ALIGN_REFINED, nullptr, nullptr, nullptr));
+    read_all(nq);
+    {     // a query out of range
+      std::vector<double> d((size_t)cn * 15);
+      std::vector<float> w((size_t)cn * 12);
+      std::vector<int64_t> n(1);
+      for (int q : {-1, nq}) {
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_refined(h, q, d.data(), nullptr, nullptr, nullptr, nullptr));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_overlap(h, q, nullptr, nullptr, nullptr, nullptr, d.data(), nullptr));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_aligned(h, q, d.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_aligned_pairs(h, q, 0, nullptr, 0, n.data()));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_world_poses(h, q, w.data()));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_refined_world_poses(h, q, w.data()));
+        CALL(SGTD_ERR_INVALID, h, sgtd_result_aligned_world_poses(h, q, w.data()));
+      }
+    }
+    // a new sgtd_verify makes the three results stale; so does a new batch
+    CALL(SGTD_OK, h, sgtd_verify(h));
+    nothing_to_read();
+    CALL(SGTD_OK, h, sgtd_refine_poses(h, 2)); CALL(SGTD_OK, h, sgtd_overlap(h, 0.25, 0, nullptr, nullptr, nullptr)); CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.25, 2, 0, nullptr, nullptr, nullptr));
+    refined = overlapped = aligned = true;
+    read_all(nq);
+    frames_batch(rng, nq);
+    nothing_to_read();
+    stages_refuse(SGTD_ERR_STATE);
+
+    // ---- a batch of descriptors has no keypoints of its own: a keypoint pass takes the caller's; so does a batch of no
+    // descriptors.  (A batch of no QUERIES, nq == 0, cannot be made through the public calls: sgtd_query_frames refuses
+    // n_queries <= 0, a descriptor batch and sgtd_search_frame are one query.  The stages' `nq == 0` exits are therefore
+    // not reached here or anywhere; the nearest cases run instead: this batch of one query without descriptors, and
+    // query 2 of every frame batch, which has no keypoints.)
+    for (int64_t n_descs : {(int64_t)400, (int64_t)0}) {
+      Descs q = random_descs(rng, 400, (uint32_t)n_frames);
+      sgtd_desc_soa qs = q.soa();
+      CALL(SGTD_OK, h, sgtd_query_descs(h, &qs, n_descs));
+      CALL(SGTD_OK, h, sgtd_verify(h));
+      CALL(SGTD_ERR_STATE, h, sgtd_overlap(h, 0.5, 0, nullptr, nullptr, nullptr));
+      CALL(SGTD_ERR_STATE, h, sgtd_align_keypoints(h, 0.5, 3, 0, nullptr, nullptr, nullptr));
+      CALL(SGTD_ERR_STATE, h, sgtd_overlap(h, 0.5, SGTD_OVERLAP_REFINED, nullptr, nullptr, nullptr));      // (two mistakes: the missing refit is named)
+      nothing_to_read();
+      counts_of(theirs, 1);
+      CALL(SGTD_OK, h, sgtd_refine_poses(h, 2));
+      CALL(SGTD_OK, h, sgtd_overlap(h, 0.5, SGTD_OVERLAP_REFINED, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+      CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.5, 3, 0, theirs.xyz.data(), theirs.label.data(), theirs.off.data()));
+      refined = overlapped = aligned = true;
+      read_all(1);
+    }
+
+    // ---- the frame-ordered dispatch: from 4096 (query, candidate) slots on, on a table that has frames, all four kernels
+    // that take an order get one (82 queries of 50 candidates: 4100); one query fewer (4050) and none does
+    for (int big : {82, 81}) {
+      REQUIRE(cn == 50);
+      S.expect_order = big == 82 ? 1 : 0;
+      for (unsigned long long &n : S.stage_launches) n = 0;
+      frames_batch(rng, big);
+      CALL(SGTD_OK, h, sgtd_verify(h));
+      CALL(SGTD_OK, h, sgtd_refine_poses(h, 2));
+      CALL(SGTD_OK, h, sgtd_overlap(h, 0.5, 0, nullptr, nullptr, nullptr));
+      CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.5, 2, SGTD_ALIGN_REFINED, nullptr, nullptr, nullptr));
+      for (unsigned long long n : S.stage_launches) REQUIRE(n == (unsigned long long)n_dev);
+      S.expect_order = -1;
+      refined = overlapped = aligned = true;
+      counts_of(own, big);
+      if (big == 81) read_all(big);
+    }
+    OK(sgtd_destroy(h));
+    S.stages = false;
+  }
+};
 }  // namespace
 
 int main(int argc, char **argv) {
   const int frames = argc > 1 ? atoi(argv[1]) : 40;
   const std::string dir = argc > 2 ? argv[2] : "/tmp";
+  if (argc > 3) { g_transcript = fopen(argv[3], "w"); REQUIRE(g_transcript); }     // (one line per call of the stages' scenario)
   std::mt19937 rng(20261003);
   Scenario S;
   sgtd_stub_set_launch_hook(hook, &S);
@@ -385,6 +996,11 @@ int main(int argc, char **argv) {
   }
 
   OK(sgtd_destroy(h));
+
+  // ---- the stages on a verified batch, on one device and on two "devices" behind one handle
+  for (int n_dev : {1, 2}) { Stages st; st.run(S, cfg, rng, n_dev); }
+  g_last = nullptr;
+  if (g_transcript) fclose(g_transcript);
   REQUIRE(sgtd_stub_device_blocks() == 0 && sgtd_stub_device_bytes() == 0);       // every device buffer was freed
   printf("engine host code under the sanitizers: ok (%llu launches, %llu sweeps, %llu frame packs, device peak %.1f MB)\n",
          sgtd_stub_launches(), S.sweeps, S.packs, sgtd_stub_device_peak() / 1048576.0);

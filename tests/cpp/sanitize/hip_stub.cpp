@@ -31,7 +31,8 @@ std::map<void *, size_t> &host_blocks() { static std::map<void *, size_t> b; ret
 #define g_kernels kernels()
 #define g_blocks blocks()
 size_t g_allocated = 0, g_peak = 0;
-unsigned long long g_launches = 0;
+unsigned long long g_launches = 0, g_copies = 0, g_waits = 0;
+unsigned g_grid_x = 0;
 typedef void (*launch_hook_t)(const char *name, void **args, void *user);
 launch_hook_t g_hook = nullptr;
 void *g_hook_user = nullptr;
@@ -46,6 +47,9 @@ extern "C" {
 // ---- the test's side
 void sgtd_stub_set_launch_hook(launch_hook_t h, void *user) { g_hook = h; g_hook_user = user; }
 unsigned long long sgtd_stub_launches() { return g_launches; }
+unsigned long long sgtd_stub_copies() { return g_copies; }      // hipMemcpy, hipMemcpyAsync and hipMemsetAsync calls
+unsigned long long sgtd_stub_waits() { return g_waits; }        // stream, event and device waits
+unsigned sgtd_stub_grid_x() { return g_grid_x; }                // of the launch whose hook is running
 size_t sgtd_stub_device_bytes() { return g_allocated; }
 size_t sgtd_stub_device_peak() { return g_peak; }
 size_t sgtd_stub_device_blocks() { return g_blocks.size(); }
@@ -80,6 +84,7 @@ hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, s
     auto it = g_kernels.find(fn);
     name = it == g_kernels.end() ? "?" : it->second;
     g_launches++;
+    g_grid_x = grid.x;
   }
   // what a real launch would refuse
   if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024 || shmem > 160 * 1024) {
@@ -153,9 +158,9 @@ hipError_t hipHostFree(void *p) {
   free(p);
   return hipSuccess;
 }
-hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { if (n) memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { if (n) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { g_copies++; if (n) memmove(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { g_copies++; if (n) memmove(d, s, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { g_copies++; if (n) memset(d, v, n); return hipSuccess; }
 
 // (what the engine asks before it lets a kernel write a caller's array: page-locked blocks are device-visible at their own address)
 hipError_t hipPointerGetAttributes(hipPointerAttribute_t *a, const void *p) {
@@ -185,16 +190,16 @@ hipError_t hipMemGetAddressRange(hipDeviceptr_t *base, size_t *size, hipDevicept
 }
 
 // ---- streams and events
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) { g_waits++; return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { g_waits++; return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new Event{0}); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete reinterpret_cast<Event *>(e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { reinterpret_cast<Event *>(e)->t = now_ms(); return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(reinterpret_cast<Event *>(b)->t - reinterpret_cast<Event *>(a)->t); return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t) { g_waits++; return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
-hipError_t hipDeviceSynchronize() { return hipSuccess; }
+hipError_t hipDeviceSynchronize() { g_waits++; return hipSuccess; }
 hipError_t hipStreamCreate(hipStream_t *s) { *s = nullptr; return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = nullptr; return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }

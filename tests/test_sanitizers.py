@@ -73,7 +73,15 @@ def test_engine_host_code_under_asan_and_ubsan(tmp_path):
     pairs, sgtd_search_frame's four ways out (one wait, too little room, a gather enqueued again, the fall-back after an
     overflow), views over an owner whose table changes under a pending batch, save / load / append and truncated table files,
     two "devices" behind one handle — and at the end every device buffer freed.  (First run: sgtd_destroy kept the entry-id
-    map's four buffers, 8 bytes per map frame plus up to 8 per entry, of every handle it destroyed.)"""
+    map's four buffers, 8 bytes per map frame plus up to 8 per entry, of every handle it destroyed.)
+
+    Then the stages on a verified batch, on one device and on two "devices": sgtd_refine_poses, sgtd_overlap and
+    sgtd_align_keypoints from either pose and with either set of keypoints, every getter, the three world-pose getters
+    against the f32 rule, the three search loops against their rules, a group's gathered results against the owners' own
+    getters, the state errors, and the frame-ordered dispatch at 4100 and 4050 (query, candidate) slots.  The launch hook
+    checks the room of every array a stage's kernel is handed.  With a file name as its third argument the driver writes
+    one line per call (status, error text, launch / copy / wait counts, a hash of the outputs): two builds of the engine
+    whose transcripts are equal behave alike."""
     san = ASAN + ["-fno-omit-frame-pointer"]
     hip = [HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-host-only", "-Wno-unused-function", "-Wno-unused-result"] + san
     objs = {n: str(tmp_path / (n + ".o")) for n in ("accel", "driver", "stub", "fatbin")}
