@@ -301,6 +301,7 @@ struct sgtd_engine {
   size_t pool_units = 0;                    // pass pool capacity in 16-B units (0: sized by the first batch; grown on overflow)
   size_t group_cap = 0;                     // GroupRows reserved (0: sized by the first batch; grown on overflow)
   size_t group_cap_hook = 0;                // SGTD_GROUP_CAP (test hook): the first reservation
+  size_t amb_min = 65536;                   // SGTD_AMB_MIN (test hook): the undecided queue's floor in entries (above it: rec_cap / 64)
   int sorted_chunk = 0;                // > 0: fixed descriptors per ticket (SGTD_SORTED_CHUNK), else adaptive
   bool diag = false;                   // diagnostic probe build: cell index + distance per match
   int select_mode = 0;                 // SGTD_SELECT_MODE (test hook): 0 auto, 1 the five-kernel passes over the records, 2 the per-query
@@ -960,7 +961,7 @@ int rec_alloc(sgtd_engine *e, bool compact_lists) {
     CHK(ensure(e, e->rec_dis, e->rec_cap * sizeof(double)));
   }
   CHK(ensure(e, e->pairs, e->pair_cap * sizeof(u64)));
-  CHK(ensure(e, e->amb_queue, std::max<size_t>(65536, e->rec_cap / 64) * sizeof(uint2)));
+  CHK(ensure(e, e->amb_queue, std::max<size_t>(e->amb_min, e->rec_cap / 64) * sizeof(uint2)));
   return SGTD_OK;
 }
 
@@ -2048,6 +2049,8 @@ int sgtd_create(const sgtd_config *cfg, sgtd_handle *out) {
   if (const char *o = getenv("SGTD_POOL_UNITS")) e->pool_units = (size_t)std::max(64ll, atoll(o));
   if (const char *o = getenv("SGTD_GROUP_CAP")) e->group_cap_hook = (size_t)std::max(1ll, atoll(o));
   if (const char *o = getenv("SGTD_PAIR_CAP")) { e->pair_cap = (size_t)std::max(64ll, atoll(o)); e->rec_cap_fixed = true; }
+  // test hook: the undecided queue's floor, so that a small record buffer gives a queue of rec_cap / 64 entries that overflows
+  if (const char *o = getenv("SGTD_AMB_MIN")) e->amb_min = (size_t)std::max(1ll, atoll(o));
   for (int i = 0; i < EV_COUNT; i++)
     if (hipEventCreate(&e->ev[i]) != hipSuccess) { delete e; return SGTD_ERR_HIP; }
   if (hipEventCreateWithFlags(&e->ev_cand, hipEventDisableTiming) != hipSuccess ||
