@@ -1,6 +1,6 @@
 // filter_kernels.hip.h — sgtd_set_frame_filter: the match records of frames a query may not see leave its lists.
 //
-// One pass right after resolve_undecided_kernel (sgtd_accel.hip, launch_select), only when the batch has a filter.
+// One pass right after resolve_undecided_kernel (sgtd_accel.hip, plan_and_sweep), only when the batch has a filter.
 // Every later stage already skips dead records (votes, top-k, the match lists, verification, the one-frame path), so
 // the sweep and the vote and list passes run unchanged.
 //

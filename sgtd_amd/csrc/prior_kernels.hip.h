@@ -1,6 +1,6 @@
 // prior_kernels.hip.h — sgtd_set_position_prior: the batch's frame-filter rows built on the device from the map poses.
 //
-// Runs in launch_select where prepare_filter would upload host rows, only when the batch has a prior.  It writes the
+// Runs in reserve_select (sgtd_accel.hip) where prepare_filter would upload host rows, only when the batch has a prior.  It writes the
 // rows filter_records_kernel / filter_compact_kernel read (filter_kernels.hip.h: bit f of row r = local frame f of
 // the table's span allowed to query r), so the filter pass and everything after it run unchanged.
 //

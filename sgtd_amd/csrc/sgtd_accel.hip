@@ -115,6 +115,21 @@ struct PinnedVec {
 constexpr size_t kCtrWords = 1024 + 8 * 1024;   // ProbeBuffers::ctr: counters + the sweep's ticket-queue heads
 enum { EV_START = 0, EV_BUILD, EV_SORT, EV_PROBE, EV_VOTES, EV_TOPK, EV_COUNT_T, EV_SCAN, EV_WRITE, EV_COUNT };
 
+// Every decision of a batch's query pipeline, made once when the batch is enqueued (plan_select) and kept in the handle:
+// the stages of launch_select and whatever runs on the batch later (a re-run of the list pass, sgtd_finish_lists,
+// sgtd_result_rough, sync_batch) read the same form and geometry.
+struct SelectPlan {
+  int nq = 0, cn = 0; long long n_slots = 0; u32 span = 1, frame_lo = 0, id_bits = 13;                  // batch shape
+  // block geometry: descriptors per block of the block passes over the match records, blocks per query, groups of four blocks,
+  // the block passes' grid (workgroup b serves query (b/8/groups)*8 + b%8)
+  u32 chunk = SGTD_PROBE_CHUNK; int blocks = 0, groups = 0, agrid = 0;
+  u32 tile_span = 1, n_tiles = 1; size_t hist_bytes = 0; bool lds_votes = false;                        // vote tiling
+  bool votes_fit = false, table_fits = false, per_query = false, fused_pairs = false, fused_votes = false, votes_per_query = false;   // form of the record passes
+  int cbits = 1, sub_bits = 0, key_bits = 0; bool small = false, pair = false; size_t max_pass_slots = 0;   // ordering
+  int row_slots = 1; u32 ticket = 2; int sgrid = 0, pgrid = 0; bool narrow = false, frames = false;     // reservations and the sweep's shape
+  bool narrow_pairs = false;      // list form: 4-byte words of the compact lists where an entry's rank among its frame's fits 19 bits, else 8
+};
+
 }  // namespace
 
 namespace multi { struct Group; }
@@ -288,10 +303,10 @@ struct sgtd_engine {
   bool defer_lists = false;                   // sgtd_set_deferred_lists: a batch stops behind the candidate tables, sgtd_finish_lists writes the lists
   bool lists_pending = false;                 // ... and has not been called for the batch yet
   bool lists_masked = false;                  // the batch's lists were written for a subset of its candidates (pair_off holds the masked offsets)
-  bool fused_votes_last = false;              // the batch's candidate tables came from votes_topk_kernel (it also wrote the unmasked offsets)
   const u64 *verify_keep = nullptr;           // sgtd_verify_masked: device mask of the candidates to verify (one launch)
   const u64 *list_keep = nullptr;             // the mask the batch's lists were last written with (a re-run of the list pass: the same)
-  bool pairs_per_query = false;               // the batch's match lists were written by pairs_query_kernel (a re-run of the write pass: the same)
+  SelectPlan plan;                            // the pending batch's (plan_select): fused_pairs = its match lists come from pairs_query_kernel,
+                                              // fused_votes = its candidate tables came from votes_topk_kernel (it also wrote the unmasked offsets)
   DevBuf rough_qi, rough_entry, rough_frame, rough_cell, rough_dis;
   size_t rec_cap = (size_t)1 << 25;    // match records (grown on overflow)
   bool rec_cap_fixed = false;          // SGTD_REC_CAP given: no pre-sizing from the table statistics
@@ -965,33 +980,123 @@ int rec_alloc(sgtd_engine *e, bool compact_lists) {
   return SGTD_OK;
 }
 
-// descriptors per block of the block passes over the match records (one wave per block): 128 — or 64 / 32 where the batch would
-// otherwise have fewer than a thousand blocks (a one-frame batch: 57 blocks = 57 waves on 1 024 SIMDs; SGTD_BLOCK_CHUNK overrides)
-u32 block_chunk(const sgtd_engine *e) {
-  if (const char *o = getenv("SGTD_BLOCK_CHUNK")) { const int c = atoi(o); if (c == 32 || c == 64 || c == 128) return (u32)c; }
-  u32 c = SGTD_PROBE_CHUNK;
-  while (c > SGTD_SUB_DESCS && (long long)e->nq * ((e->q_stride + c - 1) / c) < 1024) c >>= 1;
-  return c;
-}
+// descriptors a pass of the sweep serves (pairs / quads of neighbours share a visit list, probe_kernels.hip.h)
+constexpr double kDescsPerPass = SGTD_PAIR >= 4 ? 3.2 : (SGTD_PAIR >= 2 ? 1.9 : 1.0);
+// candidate pairs the pair buffer holds, as a kernel is told (grown by sync_batch while a batch is pending: never stored)
+u32 pair_room(const sgtd_engine *e) { return (u32)std::min<size_t>(e->pair_cap, 0xFFFFFFF0u); }
 
 struct Views {
   TableView T;
   QueryView Q;
   ProbeBuffers B;
   u32 span;
-  int blocks_per_query;
 };
 
+// pass 2 of the match-list assembly, both word widths of the compact lists (ahead of plan_select: the code object keeps its kernels in the order this file first names them)
+int launch_block_write(sgtd_engine *e, const SelectPlan &p, const Views &v, const CompactLists &CL) {
+  auto write = [&](auto kernel) {
+    kernel<<<p.agrid, 256, 0, e->stream>>>(v.Q, v.B, CL, p.blocks, e->blk_count.as<u32>(), p.cn, e->pair_off.as<long long>(), e->q_pair_base.as<u32>(),
+                                           e->pairs.as<u64>(), v.T.map, e->n_cand.as<int>(), e->cand_frame.as<int>());
+  };
+  if (p.narrow_pairs) write(&block_write_kernel<true>); else write(&block_write_kernel<false>);
+  HIPCHK(hipGetLastError());
+  return SGTD_OK;
+}
+
+// The batch's plan from the handle's state at enqueue: launches nothing, allocates nothing, changes nothing.  The per-batch
+// experiment knobs are read here, once each.
+SelectPlan plan_select(const sgtd_engine *e) {
+  SelectPlan p;
+  const int nq = p.nq = e->nq, cn = p.cn = e->dc.cand_num;
+  const long long n_slots = p.n_slots = (long long)nq * e->q_stride;
+  const u32 span = p.span = e->have_frames ? (e->frame_hi - e->frame_lo + 1) : 1;
+  p.frame_lo = e->have_frames ? e->frame_lo : 0;
+  p.id_bits = e->id_bits ? e->id_bits : 13;
+  // descriptors per block of the block passes over the match records (one wave per block): 128 — or 64 / 32 where the batch would
+  // otherwise have fewer than a thousand blocks (a one-frame batch: 57 blocks = 57 waves on 1 024 SIMDs; SGTD_BLOCK_CHUNK overrides)
+  while (p.chunk > SGTD_SUB_DESCS && (long long)nq * ((e->q_stride + p.chunk - 1) / p.chunk) < 1024) p.chunk >>= 1;
+  if (const char *o = getenv("SGTD_BLOCK_CHUNK")) { const int c = atoi(o); if (c == 32 || c == 64 || c == 128) p.chunk = (u32)c; }
+  p.blocks = (int)((e->q_stride + p.chunk - 1) / p.chunk);
+  p.groups = (p.blocks + 3) / 4;
+  p.agrid = ((nq + 7) / 8) * p.groups * 8;
+  // one 16-wave workgroup per (query, frame tile) when that fills the chip: the tile's LDS histogram is final (no flush
+  // atomics); spans beyond LDS take several tiles of 36 Ki frames
+  p.tile_span = span <= 36 * 1024 ? span : 36 * 1024;
+  p.n_tiles = (span + p.tile_span - 1) / p.tile_span;
+  p.hist_bytes = (size_t)span * sizeof(u32);
+  p.lds_votes = p.hist_bytes <= 150 * 1024;
+  // Which passes over the match records (STDesc.cpp:404-453): one workgroup per query (select_kernels.hip.h) when the batch has a
+  // query for every CU — votes + top-k in one launch while the query's vote histogram fits LDS, the match lists in one launch
+  // while an entry's rank among its frame's fits the image word — else the five-kernel form with one wave per 128-descriptor block.
+  // (automatic choice where a query's vote histogram fits LDS: with the candidates' hash instead of the frame -> slot byte table
+  // the list pass is slower than the block passes — 100 000-frame map, 256 queries: 6.1 against 2.9 ms)
+  static const size_t votes_room = lds_room(&votes_topk_kernel), list_room = lds_room(&pairs_query_kernel<true>);
+  p.votes_fit = votes_topk_lds_bytes(span) <= votes_room;
+  // ... or at least its frame -> slot byte table beside a tile's image (one workgroup per CU then; 100 000 frames, 256 queries:
+  // votes by tiles + top-k + this list pass 15.1 ms per step against 16.1 with the block passes, gpurun_out/r05o_*)
+  p.table_fits = (size_t)SGTD_PQ_TILE_RECS * sizeof(u32) + (((size_t)span + 15) & ~(size_t)15) + 16 <= list_room;
+  p.per_query = e->select_mode == 2 || (e->select_mode == 0 && nq >= e->n_cus && (p.votes_fit || p.table_fits));
+  // (an image word of the list pass is slot(6) | descriptor(9) | rank: with 64 candidates AND ranks of the full width the
+  // word of slot 63, descriptor 511, rank 2^17 - 1 would be the pass's "no record" marker — that corner takes the block form)
+  p.fused_pairs = p.per_query && !e->wide_pairs && p.id_bits <= SGTD_PQ_RANK_BITS && !(cn == SGTD_MAX_CAND && p.id_bits == SGTD_PQ_RANK_BITS);
+  p.fused_votes = p.fused_pairs && p.votes_fit;     // (block_count_kernel wants topk_kernel's slot table)
+  p.votes_per_query = p.n_tiles == 1 ? nq >= e->n_cus : ((long long)nq * p.n_tiles >= e->n_cus / 4 && p.n_tiles <= 8);
+  p.narrow_pairs = p.id_bits <= SGTD_NARROW_RANK_BITS && !e->wide_pairs;
+  // bits per cell coordinate of the sort key: the largest cell a built descriptor can have
+  while ((1ll << p.cbits) < (long long)(e->dc.max_len * e->dc.scale) + 3 && p.cbits < 16) p.cbits++;
+  // (+ the position inside the cell, home_keys_kernel: the bits that are free below the next multiple of a sort
+  // digit, or four bits and one more pass)
+  const int spare = (8 - (12 + 3 * p.cbits) % 8) % 8;
+  p.sub_bits = spare >= 2 ? std::min(spare, 6) : 4;
+  if (const char *o = getenv("SGTD_HOME_SUB_BITS")) p.sub_bits = std::min(6, std::max(0, atoi(o)));   // experiment knob
+  p.key_bits = 12 + 3 * p.cbits + p.sub_bits;
+  // one frame per call: the clearing of the batch's counters and tables and the whole ordering of its descriptors in ONE
+  // launch (small_order_kernel; SGTD_SMALL_ORDER=0: the general form)
+  const bool small_on = [] { const char *o = getenv("SGTD_SMALL_ORDER"); return !(o && !atoi(o)); }();
+  p.small = small_on && nq == 1 && n_slots <= SGTD_SMALL_SLOTS && p.key_bits <= 32 && !p.fused_votes && span <= (1u << 20);
+  // pass slots: at most one per group and one per two descriptors (probe_kernels.hip.h)
+  p.pair = !e->diag && SGTD_PAIR >= 2;
+  p.max_pass_slots = (size_t)pass_slot_count((u32)n_slots, (u32)n_slots, p.pair) + 64;
+  p.row_slots = e->n_seg > 1 ? 2 : 1;       // with a tail segment: its 27 rows in the second KB of the slot
+  // pass slots per wave ticket: about 1.5k entry visits (neighbouring home cells then go to different waves of one XCD at
+  // about the same time and find each other's buckets in its L2: at six waves per SIMD tickets of 4 / 3 / 2 pass slots
+  // fetch 8.0 / 6.0 / 4.2 GB per sweep of the default batch in the same 4.8-5.0 ms; 1: 3.1 GB in 6.0 ms), from the visits per descriptor the
+  // previous batch measured (2 until there is one); SGTD_SORTED_CHUNK overrides
+  if (e->stats.last_D > 0 && e->stats.last_P_swept > 0) {
+    // last_P_swept counts a pass's shared list once: visits per pass ~ P_swept / (D / descriptors per pass)
+    const double per_pass = (double)e->stats.last_P_swept / ((double)e->stats.last_D / (p.pair ? kDescsPerPass : 1.0));
+    p.ticket = (u32)std::min(8.0, std::max(1.0, std::floor(1536.0 / per_pass + 0.5)));
+  }
+  if (e->sorted_chunk > 0) p.ticket = (u32)std::min(SGTD_TICKET_MAX, e->sorted_chunk);
+  // the sweep's grid is sized by resident waves, not by work items: every wave pulls tickets
+  p.sgrid = e->n_cus * 8;
+  if (const char *o = getenv("SGTD_SWEEP_BLOCKS_PER_CU")) p.sgrid = e->n_cus * std::max(1, atoi(o));   // experiment knob
+  // the planner: resident workgroups (five waves per SIMD: 100 vector registers, 7 KB of staged rows per wave) x 4 rounds,
+  // grid-stride over the slots
+  int plan_per_cu = 20;
+  if (const char *o = getenv("SGTD_PLAN_BLOCKS_PER_CU")) plan_per_cu = std::max(1, atoi(o));   // experiment knob
+  p.pgrid = (int)std::min<long long>(grid_for((long long)p.max_pass_slots, SGTD_PLAN_THREADS), (long long)e->n_cus * plan_per_cu);
+  // 32-bit byte offsets into the probe layout while it stays below 4 GB (record addresses are a wave-uniform base + a 32-bit lane offset either way)
+  const u32 n0 = (u32)(e->seg[0].g1 - e->seg[0].g0), n1 = (u32)(e->seg[1].g1 - e->seg[1].g0);
+  p.narrow = ((unsigned long long)n0 + SGTD_SENTINELS + (e->n_seg > 1 ? n1 + SGTD_SENTINELS : 0u)) * sizeof(HotEntry) < (1ull << 32);
+  // can a descriptor of the batch carry a frame id the table holds?  Frames built by sgtd_query_frames are stamped with the current
+  // frame id (one beyond the newest map frame in the reference's use); descriptors handed in by the caller carry whatever they carry
+  p.frames = e->last_kind != 1 || (e->have_frames && e->last_qframe >= e->frame_lo && e->last_qframe <= e->frame_hi);
+  return p;
+}
+
+// the kernels' views of the table, the batch's descriptors and its work buffers as they stand now, in the batch's geometry
 Views make_views(sgtd_engine *e) {
+  const SelectPlan &p = e->plan;
   Views v;
-  v.span = e->have_frames ? (e->frame_hi - e->frame_lo + 1) : 1;
+  v.span = p.span;
   TableView &T = v.T;
   const sgtd_engine::Segment &S = e->seg[0], &S1 = e->seg[1];
-  T.ent = S.hot.as<HotEntry>(); T.map = id_map(e, e->id_bits ? e->id_bits : 13); T.cold_side = e->tab.side.as<double>();
+  T.ent = S.hot.as<HotEntry>(); T.map = id_map(e, p.id_bits); T.cold_side = e->tab.side.as<double>();
   T.dir = S.dir.as<BucketDir>();
   T.hash = S.hash.as<HashSlot>(); T.hash_mask = S.hash_mask;
   T.coarse_at = e->coarse_at; T.whole_at = e->whole_at;
-  T.n_entries = (u32)(S.g1 - S.g0); T.frame_lo = e->have_frames ? e->frame_lo : 0; T.frame_span = v.span;
+  T.n_entries = (u32)(S.g1 - S.g0); T.frame_lo = p.frame_lo; T.frame_span = v.span;
   // the tail segment (appends after the table was finalized): its own directory and hash, its probe
   // layout behind the main segment's in the same buffer
   T.tail_off = e->n_seg > 1 ? T.n_entries + SGTD_SENTINELS : 0u;
@@ -1000,11 +1105,11 @@ Views make_views(sgtd_engine *e) {
   QueryView &Q = v.Q;
   Q.side = e->qd.side.as<double>(); Q.qrec = e->qd.qrec.as<QueryRec>();
   Q.label = e->qd.label.as<int>(); Q.frame = e->qd.frame.as<u32>();
-  Q.count = e->q_count.as<u32>(); Q.stride = e->q_stride; Q.n_queries = e->nq; Q.chunk = block_chunk(e);
+  Q.count = e->q_count.as<u32>(); Q.stride = e->q_stride; Q.n_queries = e->nq; Q.chunk = p.chunk;
   ProbeBuffers &B = v.B;
   B.rec_cell = e->rec_cell.as<unsigned char>(); B.rec_dis = e->rec_dis.as<double>();
   B.rec_cap = (u32)std::min<size_t>(e->rec_cap >> SGTD_REC_SHIFT, kIndexLimit);      // granules
-  B.rec = e->rec.as<u32>(); B.id_bits = e->id_bits ? e->id_bits : 13;
+  B.rec = e->rec.as<u32>(); B.id_bits = p.id_bits;
   B.ctr = e->cursors.as<u32>();
   // the smallest slab: the streams of all resident waves hold one each (8192 waves x SGTD_PAIR streams) — together
   // at most a quarter of the record buffer (a 33 M-record buffer of a small batch: 512-record slabs).  (A slab is one
@@ -1021,7 +1126,7 @@ Views make_views(sgtd_engine *e) {
   // room a list gets when its pass starts (ProbeBuffers::rec_rate): three times the matches per visited entry
   // and descriptor of the batch before; a quarter of the visit list for the first batch
   {
-    const double per_pass = SGTD_PAIR >= 4 ? 3.2 : (SGTD_PAIR >= 2 ? 1.9 : 1.0);
+    const double per_pass = kDescsPerPass;
     B.rec_rate = 64;
     if (e->stats.last_P_swept > 0 && e->stats.last_M > 0) {
       // three times the batch before's matches per visited entry and descriptor — but not more than lets the
@@ -1044,23 +1149,7 @@ Views make_views(sgtd_engine *e) {
   B.amb_cap = (u32)std::min<size_t>(e->amb_queue.bytes / sizeof(uint2), 0xFFFFFFF0u);
   B.list = e->list.as<uint2>(); B.n_visit = e->n_visit.as<u32>();
   B.votes = e->votes.as<u32>();
-  v.blocks_per_query = (int)((e->q_stride + block_chunk(e) - 1) / block_chunk(e));
   return v;
-}
-
-// pass 2 of the match-list assembly (both word widths of the compact lists)
-int launch_block_write(sgtd_engine *e, const Views &v, const CompactLists &CL, int agrid, int blocks) {
-  const int cn = e->dc.cand_num;
-  if (v.T.map.bits <= SGTD_NARROW_RANK_BITS && !e->wide_pairs)
-    block_write_kernel<true><<<agrid, 256, 0, e->stream>>>(v.Q, v.B, CL, blocks, e->blk_count.as<u32>(), cn, e->pair_off.as<long long>(),
-                                                            e->q_pair_base.as<u32>(), e->pairs.as<u64>(), v.T.map, e->n_cand.as<int>(),
-                                                            e->cand_frame.as<int>());
-  else
-    block_write_kernel<false><<<agrid, 256, 0, e->stream>>>(v.Q, v.B, CL, blocks, e->blk_count.as<u32>(), cn, e->pair_off.as<long long>(),
-                                                             e->q_pair_base.as<u32>(), e->pairs.as<u64>(), v.T.map, e->n_cand.as<int>(),
-                                                             e->cand_frame.as<int>());
-  HIPCHK(hipGetLastError());
-  return SGTD_OK;
 }
 
 // the match lists of every query by a workgroup of its own (select_kernels.hip.h); the slot of a record's frame
@@ -1071,17 +1160,13 @@ int launch_pairs_query(sgtd_engine *e, const Views &v, const u64 *keep = nullptr
   const size_t tab = (((size_t)v.span + 15) & ~(size_t)15) + 16;     // (+ the bytes that answer for dead records)
   // (up to 100 KB two workgroups share a CU; a span whose byte table only fits alone — 100 000 frames: 132 KB with the
   // image — still beats the candidates' hash: one workgroup per CU)
-  static const size_t room = lds_room(&pairs_query_kernel<true>);
-  if (img + tab <= room) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&pairs_query_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(img + tab)));
-    pairs_query_kernel<true><<<e->nq, SGTD_PQ_THREADS, img + tab, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), cn,
-                                                                                e->pair_off.as<long long>(), e->q_pair_base.as<u32>(),
-                                                                                e->pairs.as<u64>(), v.T.map, v.span, v.T.frame_lo, keep);
-  } else {
-    pairs_query_kernel<false><<<e->nq, SGTD_PQ_THREADS, img, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), cn,
-                                                                           e->pair_off.as<long long>(), e->q_pair_base.as<u32>(),
-                                                                           e->pairs.as<u64>(), v.T.map, v.span, v.T.frame_lo, keep);
-  }
+  const bool table = e->plan.table_fits;
+  if (table) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&pairs_query_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(img + tab)));
+  auto lists = [&](auto kernel) {
+    kernel<<<e->nq, SGTD_PQ_THREADS, table ? img + tab : img, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), cn, e->pair_off.as<long long>(),
+                                                                           e->q_pair_base.as<u32>(), e->pairs.as<u64>(), v.T.map, v.span, v.T.frame_lo, keep);
+  };
+  if (table) lists(&pairs_query_kernel<true>); else lists(&pairs_query_kernel<false>);
   HIPCHK(hipGetLastError());
   return SGTD_OK;
 }
@@ -1116,7 +1201,7 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
     cand_prefix_masked_kernel<<<grid_for(nq, 256), 256, 0, e->stream>>>(e->n_cand.as<int>(), e->cand_votes.as<int>(), keep, cn, nq,
                                                                           e->pair_off.as<long long>(), e->q_pairs.as<u32>());
     HIPCHK(hipGetLastError());
-  } else if (!e->fused_votes_last || e->lists_masked) {
+  } else if (!e->plan.fused_votes || e->lists_masked) {
     // (votes_topk_kernel leaves the unmasked offsets itself)
     cand_prefix_kernel<<<grid_for(nq, 256), 256, 0, e->stream>>>(e->n_cand.as<int>(), e->cand_votes.as<int>(), cn, nq,
                                                                    e->pair_off.as<long long>(), e->q_pairs.as<u32>());
@@ -1126,8 +1211,7 @@ int launch_lists(sgtd_engine *e, const Views &v, const u64 *keep, bool first) {
   e->list_keep = keep;
   if (e->timing && first) HIPCHK(hipEventRecord(e->ev[EV_COUNT_T], e->stream));
   if (!first) HIPCHK(hipMemsetAsync(v.B.overflow() + 1, 0, sizeof(int), e->stream));
-  query_base_kernel<<<1, 256, 0, e->stream>>>(e->q_pairs.as<u32>(), e->q_pair_base.as<u32>(), nq,
-                                               (u32)std::min<size_t>(e->pair_cap, 0xFFFFFFF0u), v.B.overflow());
+  query_base_kernel<<<1, 256, 0, e->stream>>>(e->q_pairs.as<u32>(), e->q_pair_base.as<u32>(), nq, pair_room(e), v.B.overflow());
   HIPCHK(hipGetLastError());
   if (e->timing && first) HIPCHK(hipEventRecord(e->ev[EV_SCAN], e->stream));
   CHK(launch_pairs_query(e, v, keep));
@@ -1250,359 +1334,294 @@ int launch_filter(sgtd_engine *e, const Views &v) {
   return SGTD_OK;
 }
 
-int launch_select(sgtd_engine *e) {
-  const int nq = e->nq;
-  const long long n_slots = (long long)nq * e->q_stride;
-  const int cn = e->dc.cand_num;
-  const u32 span = e->have_frames ? (e->frame_hi - e->frame_lo + 1) : 1;
-  const int blocks = (int)((e->q_stride + block_chunk(e) - 1) / block_chunk(e));
+// every work buffer of the batch, its filter's or prior's rows, and the reservations that grow from batch to batch
+int reserve_select(sgtd_engine *e, const SelectPlan &p) {
+  const int nq = p.nq, cn = p.cn;
+  const size_t slots = (size_t)std::max<long long>(p.n_slots, 1), n_slots = (size_t)p.n_slots;
   CHK(ensure(e, e->cursors, kCtrWords * sizeof(u32)));
   if (!e->totals.p) {
     CHK(ensure(e, e->totals, 4 * sizeof(unsigned long long)));
     HIPCHK(hipMemsetAsync(e->totals.p, 0, 4 * sizeof(unsigned long long), e->stream));
   }
-  CHK(ensure(e, e->list, (size_t)std::max<long long>(n_slots, 1) * sizeof(uint2)));
-  CHK(ensure(e, e->n_visit, (size_t)std::max<long long>(n_slots, 1) * sizeof(u32)));
-  CHK(ensure(e, e->votes, (size_t)nq * span * sizeof(u32)));
-  CHK(ensure(e, e->slot_of, (size_t)nq * span + 4));      // (+ a word: small_order_kernel clears it by words)
-  CHK(ensure(e, e->q_M, (size_t)nq * sizeof(u32)));
+  CHK(ensure(e, e->list, slots * sizeof(uint2)));
+  CHK(ensure(e, e->n_visit, slots * sizeof(u32)));
+  CHK(ensure(e, e->votes, (size_t)nq * p.span * sizeof(u32)));
+  CHK(ensure(e, e->slot_of, (size_t)nq * p.span + 4));      // (+ a word: small_order_kernel clears it by words)
+  for (DevBuf *b : {&e->q_M, &e->q_pairs, &e->q_prefix}) CHK(ensure(e, *b, (size_t)nq * sizeof(u32)));
   CHK(ensure(e, e->q_P, (size_t)nq * sizeof(unsigned long long)));
-  CHK(ensure(e, e->q_pairs, (size_t)nq * sizeof(u32)));
   CHK(ensure(e, e->q_pair_base, (size_t)(nq + 1) * sizeof(u32)));
-  CHK(ensure(e, e->blk_count, (size_t)nq * blocks * 64 * sizeof(u32)));
-  CHK(ensure(e, e->c_blk, (size_t)nq * blocks * 2 * sizeof(u32)));
+  CHK(ensure(e, e->blk_count, (size_t)nq * p.blocks * 64 * sizeof(u32)));
+  CHK(ensure(e, e->c_blk, (size_t)nq * p.blocks * 2 * sizeof(u32)));
   CHK(ensure(e, e->n_cand, (size_t)nq * sizeof(int)));
-  CHK(ensure(e, e->cand_frame, (size_t)nq * cn * sizeof(int)));
-  CHK(ensure(e, e->cand_votes, (size_t)nq * cn * sizeof(int)));
+  for (DevBuf *b : {&e->cand_frame, &e->cand_votes}) CHK(ensure(e, *b, (size_t)nq * cn * sizeof(int)));
   CHK(ensure(e, e->pair_off, (size_t)nq * (cn + 1) * sizeof(long long)));
-  if (e->batch_prior) CHK(prepare_prior(e, e->have_frames ? e->frame_lo : 0, span));
-  else if (e->batch_filt) CHK(prepare_filter(e, e->have_frames ? e->frame_lo : 0, span));
+  if (e->batch_prior) CHK(prepare_prior(e, p.frame_lo, p.span));
+  else if (e->batch_filt) CHK(prepare_filter(e, p.frame_lo, p.span));
+  CHK(rec_alloc(e, !p.fused_pairs));
+  // one GroupRow (1 KB) per distinct home cell of the batch: at most one per descriptor slot, in practice a twelfth of that (0.7 M
+  // cells for 9.1 M descriptors at the default batch).  Reserved: every slot for small batches, an eighth of the slots for large
+  // ones — a 15-GB reservation cost the first batch 0.4 s of hipMalloc — and what a batch really needed, plus a quarter, once one
+  // has overflowed it (group_resolve_kernel raises the overflow flag, sync_batch re-runs).
+  if (e->group_cap_hook) { if (e->group_cap == 0) e->group_cap = e->group_cap_hook; }
+  else {
+    // distinct home cells of a batch: every slot's for small batches (a single frame: ~40 % of its slots), about
+    // 1.5 M at most on the shipped resolution (0.39 M for 256 frames, 0.7 M for 2048), never more than half the slots
+    const long long want = p.n_slots <= 65536 ? p.n_slots : std::min<long long>(p.n_slots / 2, std::max<long long>(p.n_slots / 8, 1500000));
+    e->group_cap = std::max<size_t>(e->group_cap, (size_t)want);
+  }
+  CHK(ensure(e, e->cell_rows, std::max<size_t>(e->group_cap, 1) * SGTD_GROUP_ROW_BYTES * p.row_slots));
+  // the order of the batch's descriptors by home key: sort keys and values, group ids, pass slots
+  for (DevBuf *b : {&e->keyA, &e->keyB}) CHK(ensure(e, *b, n_slots * sizeof(u64)));
+  for (DevBuf *b : {&e->valA, &e->valB, &e->gid, &e->group_first}) CHK(ensure(e, *b, n_slots * sizeof(u32)));
+  for (DevBuf *b : {&e->n_valid, &e->n_groups}) CHK(ensure(e, *b, sizeof(u32)));
+  for (DevBuf *b : {&e->pos_of_slot, &e->rec_off}) CHK(ensure(e, *b, p.max_pass_slots * sizeof(u32)));
+  // 160 B per descriptor slot (110 used at the 10 000-frame default), 256 B for tables beyond 1e8 entries (more of
+  // the 27 cells of a home cell have a bucket: 190 B used at 100 000 frames); grown on overflow
+  if (e->pool_units == 0) e->pool_units = std::max<size_t>(65536, n_slots * (e->n_entries > 100000000 ? 16 : 10));
+  CHK(ensure(e, e->pass_pool, (e->pool_units + SGTD_PASS_SLACK_UNITS) * sizeof(uint4)));
+  return SGTD_OK;
+}
 
-  // Which passes over the match records (STDesc.cpp:404-453): one workgroup per query (select_kernels.hip.h) when
-  // the batch has a query for every CU — votes + top-k in one launch while the query's vote histogram fits LDS,
-  // the match lists in one launch while an entry's rank among its frame's fits the image word — else the
-  // five-kernel form with one wave per 128-descriptor block.
-  const u32 tile_span = span <= 36 * 1024 ? span : 36 * 1024;
-  const u32 n_tiles = (span + tile_span - 1) / tile_span;
-  // (automatic choice where a query's vote histogram fits LDS: with the candidates' hash instead of the frame -> slot
-  // byte table the list pass is slower than the block passes — 100 000-frame map, 256 queries: 6.1 against 2.9 ms)
-  static const size_t votes_room = lds_room(&votes_topk_kernel), list_room = lds_room(&pairs_query_kernel<true>);
-  const bool votes_fit = votes_topk_lds_bytes(span) <= votes_room;
-  // ... or at least its frame -> slot byte table beside a tile's image (one workgroup per CU then; 100 000 frames, 256 queries:
-  // votes by tiles + top-k + this list pass 15.1 ms per step against 16.1 with the block passes, gpurun_out/r05o_*)
-  const bool table_fits = (size_t)SGTD_PQ_TILE_RECS * sizeof(u32) + (((size_t)span + 15) & ~(size_t)15) + 16 <= list_room;
-  const bool per_query = e->select_mode == 2 || (e->select_mode == 0 && nq >= e->n_cus && (votes_fit || table_fits));
-  // (an image word of the list pass is slot(6) | descriptor(9) | rank: with 64 candidates AND ranks of the full width the
-  // word of slot 63, descriptor 511, rank 2^17 - 1 would be the pass's "no record" marker — that corner takes the block form)
-  const bool fused_pairs = per_query && !e->wide_pairs && (e->id_bits ? e->id_bits : 13) <= SGTD_PQ_RANK_BITS &&
-                           !(cn == SGTD_MAX_CAND && (e->id_bits ? e->id_bits : 13) == SGTD_PQ_RANK_BITS);
-  const bool fused_votes = fused_pairs && votes_fit;     // (block_count_kernel wants topk_kernel's slot table)
-  CHK(rec_alloc(e, !fused_pairs));
-  const bool votes_per_query = n_tiles == 1 ? nq >= e->n_cus : ((long long)nq * n_tiles >= e->n_cus / 4 && n_tiles <= 8);
-  // bits per cell coordinate of the sort key: the largest cell a built descriptor can have
-  int cbits = 1;
-  while ((1ll << cbits) < (long long)(e->dc.max_len * e->dc.scale) + 3 && cbits < 16) cbits++;
-  // (+ the position inside the cell, home_keys_kernel: the bits that are free below the next multiple of a sort
-  // digit, or four bits and one more pass)
-  const int spare = (8 - (12 + 3 * cbits) % 8) % 8;
-  int sub_bits = spare >= 2 ? std::min(spare, 6) : 4;
-  if (const char *o = getenv("SGTD_HOME_SUB_BITS")) sub_bits = std::min(6, std::max(0, atoi(o)));   // experiment knob
-  const int key_bits = 12 + 3 * cbits + sub_bits;
-  // one frame per call: the clearing of the batch's counters and tables and the whole ordering of its descriptors in ONE
-  // launch (small_order_kernel; SGTD_SMALL_ORDER=0: the general form)
-  const bool small_on = [] { const char *o = getenv("SGTD_SMALL_ORDER"); return !(o && !atoi(o)); }();
-  const bool small = small_on && nq == 1 && n_slots <= SGTD_SMALL_SLOTS && key_bits <= 32 && !fused_votes && span <= (1u << 20);
+// the sweep records of descriptors the caller handed in, and the general form's clearing of the batch's counters and tables
+// (a one-frame batch: inside small_order_kernel)
+int clear_batch(sgtd_engine *e, const SelectPlan &p) {
+  const int nq = p.nq, cn = p.cn;
   if (e->thr2_pending > 0) {      // (not inside small_order_kernel: the thresholds and gate masks of 7 000 descriptors are 50 us of ONE workgroup's time, 5 us of eighteen's)
     thr2_kernel<<<grid_for(e->thr2_pending, 256), 256, 0, e->stream>>>(e->qd.side.as<double>(), e->qd.frame.as<u32>(), e->qd.qrec.as<QueryRec>(), e->thr2_pending,
                                                                         e->dc.rough);
     HIPCHK(hipGetLastError());
   }
-  if (!small) {
-    HIPCHK(hipMemsetAsync(e->cursors.p, 0, kCtrWords * sizeof(u32), e->stream));
-    if (!fused_votes) {
-      if (!votes_per_query) HIPCHK(hipMemsetAsync(e->votes.p, 0, (size_t)nq * span * sizeof(u32), e->stream));   // (global vote atomics)
-      HIPCHK(hipMemsetAsync(e->slot_of.p, 0xFF, (size_t)nq * span, e->stream));
-      HIPCHK(hipMemsetAsync(e->cand_frame.p, 0xFF, (size_t)nq * cn * sizeof(int), e->stream));
-      HIPCHK(hipMemsetAsync(e->cand_votes.p, 0, (size_t)nq * cn * sizeof(int), e->stream));
-    }
-    HIPCHK(hipMemsetAsync(e->q_M.p, 0, (size_t)nq * sizeof(u32), e->stream));
-    HIPCHK(hipMemsetAsync(e->q_P.p, 0, (size_t)nq * sizeof(unsigned long long), e->stream));
+  if (p.small) return SGTD_OK;
+  HIPCHK(hipMemsetAsync(e->cursors.p, 0, kCtrWords * sizeof(u32), e->stream));
+  if (!p.fused_votes) {
+    if (!p.votes_per_query) HIPCHK(hipMemsetAsync(e->votes.p, 0, (size_t)nq * p.span * sizeof(u32), e->stream));   // (global vote atomics)
+    HIPCHK(hipMemsetAsync(e->slot_of.p, 0xFF, (size_t)nq * p.span, e->stream));
+    HIPCHK(hipMemsetAsync(e->cand_frame.p, 0xFF, (size_t)nq * cn * sizeof(int), e->stream));
+    HIPCHK(hipMemsetAsync(e->cand_votes.p, 0, (size_t)nq * cn * sizeof(int), e->stream));
   }
+  HIPCHK(hipMemsetAsync(e->q_M.p, 0, (size_t)nq * sizeof(u32), e->stream));
+  HIPCHK(hipMemsetAsync(e->q_P.p, 0, (size_t)nq * sizeof(unsigned long long), e->stream));
+  return SGTD_OK;
+}
 
-  Views v = make_views(e);
-  const size_t hist_bytes = (size_t)span * sizeof(u32);
-  const bool lds_votes = hist_bytes <= 150 * 1024;
-  const int groups = (blocks + 3) / 4;
-  const int agrid = ((nq + 7) / 8) * groups * 8;   // workgroup b serves query (b/8/groups)*8 + b%8
-  // one GroupRow (1 KB) per distinct home cell of the batch: at most one per descriptor slot, in practice a
-  // twelfth of that (0.7 M cells for 9.1 M descriptors at the default batch).  Reserved: every slot for
-  // small batches, an eighth of the slots for large ones — a 15-GB reservation cost the first batch
-  // 0.4 s of hipMalloc — and what a batch really needed, plus a quarter, once one has overflowed it
-  // (group_resolve_kernel raises the overflow flag, sync_batch re-runs).
-  if (e->group_cap_hook) { if (e->group_cap == 0) e->group_cap = e->group_cap_hook; }
-  else {
-    // distinct home cells of a batch: every slot's for small batches (a single frame: ~40 % of its slots), about
-    // 1.5 M at most on the shipped resolution (0.39 M for 256 frames, 0.7 M for 2048), never more than half the slots
-    const long long want = n_slots <= 65536 ? n_slots : std::min<long long>(n_slots / 2, std::max<long long>(n_slots / 8, 1500000));
-    e->group_cap = std::max<size_t>(e->group_cap, (size_t)want);
+// order of the batch's descriptors by home key (label code + truncated cell): stable 8-bit radix passes over
+// 12 + 3*cbits + sub_bits key bits, group heads, their scan, the groups' firsts and the pass slots — or all of it in
+// small_order_kernel's one launch.  *order: the descriptor slots in that order
+int order_descriptors(sgtd_engine *e, const SelectPlan &p, const Views &v, u32 **order) {
+  const long long n_slots = p.n_slots;
+  u32 *vin = e->valA.as<u32>(), *vout = e->valB.as<u32>(), *gid = e->gid.as<u32>();
+  const u32 *nv = e->n_valid.as<u32>();
+  if (p.small) {
+    SmallOrder SO;
+    SO.ctr = e->cursors.as<u32>(); SO.ctr_words = (u32)kCtrWords;
+    SO.q_M = e->q_M.as<u32>(); SO.q_P = e->q_P.as<unsigned long long>();
+    SO.votes = p.votes_per_query ? nullptr : e->votes.as<u32>(); SO.slot_of_words = e->slot_of.as<u32>(); SO.span = p.span;
+    SO.cand_frame = e->cand_frame.as<int>(); SO.cand_votes = e->cand_votes.as<int>(); SO.cand_num = p.cn;
+    SO.q_prefix = e->q_prefix.as<u32>(); SO.n_valid = e->n_valid.as<u32>(); SO.order = vin; SO.gid = gid;
+    SO.group_first = e->group_first.as<u32>(); SO.n_groups = e->n_groups.as<u32>(); SO.pos_of_slot = e->pos_of_slot.as<u32>();
+    SO.n_slots = (u32)n_slots; SO.max_pass_slots = (u32)p.max_pass_slots; SO.cbits = p.cbits; SO.sub_bits = p.sub_bits; SO.pair = p.pair ? 1 : 0; SO.key_bits = p.key_bits;
+    SO.qrec = nullptr; SO.n_qrec = 0; SO.rough = e->dc.rough;
+    const size_t lds = (size_t)SGTD_SMALL_SLOTS * 16;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&small_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device: before every launch)
+    small_order_kernel<<<1, SGTD_SMALL_THREADS, lds, e->stream>>>(v.Q, SO);
+    HIPCHK(hipGetLastError());
+    e->thr2_pending = 0; *order = vin;
+    return SGTD_OK;
   }
-  const int row_slots = e->n_seg > 1 ? 2 : 1;       // with a tail segment: its 27 rows in the second KB of the slot
-  CHK(ensure(e, e->cell_rows, std::max<size_t>(e->group_cap, 1) * SGTD_GROUP_ROW_BYTES * row_slots));
+  query_prefix_kernel<<<1, 256, 0, e->stream>>>(e->q_count.as<u32>(), e->q_prefix.as<u32>(), p.nq, e->n_valid.as<u32>());
+  HIPCHK(hipGetLastError());
+  // keys, their sort (only the n_valid compact elements are live) and the heads of the groups, in the key's width
+  auto sort_by_home = [&](auto *kin, auto *kout) -> int {
+    using Key = typename std::remove_pointer<decltype(kin)>::type;
+    home_keys_kernel<Key><<<grid_for(n_slots, 256), 256, 0, e->stream>>>(v.Q, e->q_prefix.as<u32>(), kin, vin, n_slots, p.cbits, p.sub_bits);
+    HIPCHK(hipGetLastError());
+    CHK(radix_sort_pairs(e, kin, kout, vin, vout, n_slots, p.key_bits, false, nv));
+    group_heads_kernel<Key><<<grid_for(n_slots, 256), 256, 0, e->stream>>>(kin, nv, gid, n_slots, p.cbits, p.sub_bits);
+    HIPCHK(hipGetLastError());
+    return SGTD_OK;
+  };
+  if (p.key_bits <= 32) CHK(sort_by_home(e->keyA.as<u32>(), e->keyB.as<u32>()));      // 32-bit keys: a third less traffic in every sort pass
+  else CHK(sort_by_home(e->keyA.as<u64>(), e->keyB.as<u64>()));
+  CHK(device_scan(e, gid, gid, n_slots));
+  group_first_kernel<<<grid_for(n_slots, 256), 256, 0, e->stream>>>(gid, nv, e->group_first.as<u32>(), e->n_groups.as<u32>(), n_slots);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(e->pos_of_slot.p, 0xFF, p.max_pass_slots * sizeof(u32), e->stream));
+  pass_slots_kernel<<<grid_for(n_slots, 256), 256, 0, e->stream>>>(gid, e->group_first.as<u32>(), nv, e->pos_of_slot.as<u32>(), n_slots, p.pair ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  e->thr2_pending = 0; *order = vin;      // (where the sort's last pass left it)
+  return SGTD_OK;
+}
+
+// one GroupRow per home cell (both segments' directory rows), the passes' visit lists from it, then ONE sweep: a pass's
+// list runs through the main segment's ranges and then the tail's, cell by cell; the sweep's undecided records; the filter
+int plan_and_sweep(sgtd_engine *e, const SelectPlan &p, const Views &v, u32 *vin) {
+  const u32 *nv = e->n_valid.as<u32>();
   const unsigned char *rows = e->cell_rows.as<unsigned char>();
   const u32 rows_cap = (u32)std::min<size_t>(e->group_cap, 0xFFFFFFFFu);
-  {
-    // ---- order of the batch's descriptors by home key (label code + truncated cell):
-    // stable 8-bit radix passes over 12 + 3*cbits key bits, then one GroupRow of bucket
-    // lookups per distinct home cell
-    CHK(ensure(e, e->keyA, (size_t)n_slots * sizeof(u64)));
-    CHK(ensure(e, e->keyB, (size_t)n_slots * sizeof(u64)));
-    CHK(ensure(e, e->valA, (size_t)n_slots * sizeof(u32)));
-    CHK(ensure(e, e->valB, (size_t)n_slots * sizeof(u32)));
-    CHK(ensure(e, e->gid, (size_t)n_slots * sizeof(u32)));
-    CHK(ensure(e, e->n_valid, sizeof(u32)));
-    u64 *kin = e->keyA.as<u64>(), *kout = e->keyB.as<u64>();
-    u32 *vin = e->valA.as<u32>(), *vout = e->valB.as<u32>();
-    CHK(ensure(e, e->q_prefix, (size_t)nq * sizeof(u32)));
-    CHK(ensure(e, e->group_first, (size_t)n_slots * sizeof(u32)));
-    CHK(ensure(e, e->n_groups, sizeof(u32)));
-    // pass slots: at most one per group and one per two descriptors (probe_kernels.hip.h)
-    const bool pair = !e->diag && SGTD_PAIR >= 2;
-    const size_t max_pass_slots = (size_t)pass_slot_count((u32)n_slots, (u32)n_slots, pair) + 64;
-    CHK(ensure(e, e->pos_of_slot, max_pass_slots * sizeof(u32)));
-    CHK(ensure(e, e->rec_off, max_pass_slots * sizeof(u32)));
-    // 160 B per descriptor slot (110 used at the 10 000-frame default), 256 B for tables beyond 1e8 entries (more of
-    // the 27 cells of a home cell have a bucket: 190 B used at 100 000 frames); grown on overflow
-    if (e->pool_units == 0) e->pool_units = std::max<size_t>(65536, (size_t)n_slots * (e->n_entries > 100000000 ? 16 : 10));
-    CHK(ensure(e, e->pass_pool, (e->pool_units + SGTD_PASS_SLACK_UNITS) * sizeof(uint4)));
-    const u32 *nv = e->n_valid.as<u32>();
-    if (small) {
-      SmallOrder SO;
-      SO.ctr = e->cursors.as<u32>(); SO.ctr_words = (u32)kCtrWords;
-      SO.q_M = e->q_M.as<u32>(); SO.q_P = e->q_P.as<unsigned long long>();
-      SO.votes = votes_per_query ? nullptr : e->votes.as<u32>(); SO.slot_of_words = e->slot_of.as<u32>(); SO.span = span;
-      SO.cand_frame = e->cand_frame.as<int>(); SO.cand_votes = e->cand_votes.as<int>(); SO.cand_num = cn;
-      SO.q_prefix = e->q_prefix.as<u32>(); SO.n_valid = e->n_valid.as<u32>(); SO.order = vin; SO.gid = e->gid.as<u32>();
-      SO.group_first = e->group_first.as<u32>(); SO.n_groups = e->n_groups.as<u32>(); SO.pos_of_slot = e->pos_of_slot.as<u32>();
-      SO.n_slots = (u32)n_slots; SO.max_pass_slots = (u32)max_pass_slots; SO.cbits = cbits; SO.sub_bits = sub_bits; SO.pair = pair ? 1 : 0; SO.key_bits = key_bits;
-      SO.qrec = nullptr; SO.n_qrec = 0; SO.rough = e->dc.rough;
-      const size_t lds = (size_t)SGTD_SMALL_SLOTS * 16;
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&small_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (per device: before every launch)
-      small_order_kernel<<<1, SGTD_SMALL_THREADS, lds, e->stream>>>(v.Q, SO);
-      HIPCHK(hipGetLastError());
-    } else {
-    query_prefix_kernel<<<1, 256, 0, e->stream>>>(e->q_count.as<u32>(), e->q_prefix.as<u32>(), nq, e->n_valid.as<u32>());
-    HIPCHK(hipGetLastError());
-    if (key_bits <= 32) {      // 32-bit keys: a third less traffic in every sort pass
-      u32 *k32 = reinterpret_cast<u32 *>(kin), *k32o = reinterpret_cast<u32 *>(kout);
-      home_keys_kernel<u32><<<grid_for(n_slots, 256), 256, 0, e->stream>>>(v.Q, e->q_prefix.as<u32>(), k32, vin, n_slots, cbits, sub_bits);
-      HIPCHK(hipGetLastError());
-      CHK(radix_sort_pairs(e, k32, k32o, vin, vout, n_slots, key_bits, false, nv));   // only the n_valid compact elements are live
-      group_heads_kernel<u32><<<grid_for(n_slots, 256), 256, 0, e->stream>>>(k32, nv, e->gid.as<u32>(), n_slots, cbits, sub_bits);
-    } else {
-      home_keys_kernel<u64><<<grid_for(n_slots, 256), 256, 0, e->stream>>>(v.Q, e->q_prefix.as<u32>(), kin, vin, n_slots, cbits, sub_bits);
-      HIPCHK(hipGetLastError());
-      CHK(radix_sort_pairs(e, kin, kout, vin, vout, n_slots, key_bits, false, nv));
-      group_heads_kernel<u64><<<grid_for(n_slots, 256), 256, 0, e->stream>>>(kin, nv, e->gid.as<u32>(), n_slots, cbits, sub_bits);
-    }
-    HIPCHK(hipGetLastError());
-    CHK(device_scan(e, e->gid.as<u32>(), e->gid.as<u32>(), n_slots));
-    group_first_kernel<<<grid_for(n_slots, 256), 256, 0, e->stream>>>(e->gid.as<u32>(), nv, e->group_first.as<u32>(),
-                                                                        e->n_groups.as<u32>(), n_slots);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(e->pos_of_slot.p, 0xFF, max_pass_slots * sizeof(u32), e->stream));
-    pass_slots_kernel<<<grid_for(n_slots, 256), 256, 0, e->stream>>>(e->gid.as<u32>(), e->group_first.as<u32>(), nv,
-                                                                       e->pos_of_slot.as<u32>(), n_slots, pair ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    }
-    e->thr2_pending = 0;
-    // pass slots per wave ticket: about 1.5k entry visits (neighbouring home cells then go to different waves of one XCD at
-    // about the same time and find each other's buckets in its L2: at six waves per SIMD tickets of 4 / 3 / 2 pass slots
-    // fetch 8.0 / 6.0 / 4.2 GB per sweep of the default batch in the same 4.8-5.0 ms; 1: 3.1 GB in 6.0 ms), from the visits per descriptor the
-    // previous batch measured (2 until there is one); SGTD_SORTED_CHUNK overrides
-    u32 chunk = 2;
-    if (e->stats.last_D > 0 && e->stats.last_P_swept > 0) {
-      // last_P_swept counts a pass's shared list once: visits per pass ~ P_swept / (D / descriptors per pass)
-      const double per_pass = (double)e->stats.last_P_swept / ((double)e->stats.last_D / (pair ? (SGTD_PAIR >= 4 ? 3.2 : 1.9) : 1.0));
-      chunk = (u32)std::min(8.0, std::max(1.0, std::floor(1536.0 / per_pass + 0.5)));
-    }
-    if (e->sorted_chunk > 0) chunk = (u32)std::min(SGTD_TICKET_MAX, e->sorted_chunk);
-    // the grid is sized by resident waves, not by work items: every wave pulls tickets
-    int sgrid = e->n_cus * 8;
-    if (const char *o = getenv("SGTD_SWEEP_BLOCKS_PER_CU")) sgrid = e->n_cus * std::max(1, atoi(o));   // experiment knob
-    PassPool PP;
-    PP.pool = e->pass_pool.as<uint4>(); PP.rec_off = e->rec_off.as<u32>();
-    PP.cursor = v.B.pool_cursor(); PP.cap = (u32)std::min<size_t>(e->pool_units, 0xFFFFFF00u);
-    {
-      // one GroupRow per home cell (both segments' directory rows), the passes' visit lists from it, then
-      // ONE sweep: a pass's list runs through the main segment's ranges and then the tail's, cell by cell
-      Views &vs = v;
-      group_resolve_kernel<<<e->n_cus * 16, 256, 0, e->stream>>>(vs.T, vs.Q, vin, e->group_first.as<u32>(),
-                                                                  e->n_groups.as<u32>(), nv, e->cell_rows.as<unsigned char>(), rows_cap, vs.B.overflow());
-      HIPCHK(hipGetLastError());
-      // resident workgroups (five waves per SIMD: 100 vector registers, 7 KB of staged rows per wave) x 4 rounds,
-      // grid-stride over the slots
-      int plan_per_cu = 20;
-      if (const char *o = getenv("SGTD_PLAN_BLOCKS_PER_CU")) plan_per_cu = std::max(1, atoi(o));   // experiment knob
-      const int pgrid = (int)std::min<long long>(grid_for((long long)max_pass_slots, SGTD_PLAN_THREADS), (long long)e->n_cus * plan_per_cu);
+  PassPool PP;
+  PP.pool = e->pass_pool.as<uint4>(); PP.rec_off = e->rec_off.as<u32>();
+  PP.cursor = v.B.pool_cursor(); PP.cap = (u32)std::min<size_t>(e->pool_units, 0xFFFFFF00u);
+  group_resolve_kernel<<<e->n_cus * 16, 256, 0, e->stream>>>(v.T, v.Q, vin, e->group_first.as<u32>(),
+                                                              e->n_groups.as<u32>(), nv, e->cell_rows.as<unsigned char>(), rows_cap, v.B.overflow());
+  HIPCHK(hipGetLastError());
 #define SGTD_LAUNCH_PLAN(PR, TL)                                                                               \
-  plan_passes_kernel<PR, TL><<<pgrid, SGTD_PLAN_THREADS, 0, e->stream>>>(vs.T, vs.Q, vin, e->gid.as<u32>(), e->pos_of_slot.as<u32>(), nv, \
-                                                       e->n_groups.as<u32>(), rows, rows_cap, PP, vs.B.n_visit, vs.B.list,          \
-                                                       vs.B.overflow())
-      if (vs.T.tail_off) { if (pair) SGTD_LAUNCH_PLAN(true, true); else SGTD_LAUNCH_PLAN(false, true); }
-      else { if (pair) SGTD_LAUNCH_PLAN(true, false); else SGTD_LAUNCH_PLAN(false, false); }
+  plan_passes_kernel<PR, TL><<<p.pgrid, SGTD_PLAN_THREADS, 0, e->stream>>>(v.T, v.Q, vin, e->gid.as<u32>(), e->pos_of_slot.as<u32>(), nv, \
+                                                       e->n_groups.as<u32>(), rows, rows_cap, PP, v.B.n_visit, v.B.list,          \
+                                                       v.B.overflow())
+  if (v.T.tail_off) { if (p.pair) SGTD_LAUNCH_PLAN(true, true); else SGTD_LAUNCH_PLAN(false, true); }
+  else { if (p.pair) SGTD_LAUNCH_PLAN(true, false); else SGTD_LAUNCH_PLAN(false, false); }
 #undef SGTD_LAUNCH_PLAN
-      HIPCHK(hipGetLastError());
-      if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_SORT], e->stream));   // ms_probe = the sweep from here
-      // 32-bit byte offsets into the probe layout while it stays below 4 GB (record addresses
-      // are a wave-uniform base + a 32-bit lane offset either way)
-      const bool narrow = ((unsigned long long)vs.T.n_entries + SGTD_SENTINELS + (vs.T.tail_off ? vs.T.n_entries1 + SGTD_SENTINELS : 0u)) * sizeof(HotEntry) < (1ull << 32);
-      // can a descriptor of the batch carry a frame id the table holds?  Frames built by
-      // sgtd_query_frames are stamped with the current frame id (one beyond the newest map frame
-      // in the reference's use); descriptors handed in by the caller carry whatever they carry
-      const bool frames = e->last_kind != 1 || (e->have_frames && e->last_qframe >= e->frame_lo && e->last_qframe <= e->frame_hi);
-      // a loop batch (sgtd_loop_frames) takes the BOUND variants: an entry counts when its frame lies below the query's bound
+  HIPCHK(hipGetLastError());
+  if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_SORT], e->stream));   // ms_probe = the sweep from here
+  // a loop batch (sgtd_loop_frames) takes the BOUND variants: an entry counts when its frame lies below the query's bound
 #define SGTD_LAUNCH_SORTED(DG, WD, FR, BD)                                                                      \
-  probe_sorted_kernel<DG, WD, FR, BD><<<sgrid, SGTD_PROBE_THREADS, 0, e->stream>>>(                             \
-      vs.T, vs.B, vs.Q, PP, e->dc.rough, e->n_valid.as<u32>(), e->n_groups.as<u32>(), chunk)
-      if (e->diag) {
-        if (e->loop_batch) SGTD_LAUNCH_SORTED(true, true, true, true);
-        else SGTD_LAUNCH_SORTED(true, true, true, false);
-      } else if (e->loop_batch) {
-        if (narrow) SGTD_LAUNCH_SORTED(false, false, true, true);
-        else SGTD_LAUNCH_SORTED(false, true, true, true);
-      }
-      else if (narrow && frames) SGTD_LAUNCH_SORTED(false, false, true, false);
-      else if (narrow) SGTD_LAUNCH_SORTED(false, false, false, false);
-      else if (frames) SGTD_LAUNCH_SORTED(false, true, true, false);
-      else SGTD_LAUNCH_SORTED(false, true, false, false);
-#undef SGTD_LAUNCH_SORTED
-      HIPCHK(hipGetLastError());
-      resolve_undecided_kernel<<<64, 256, 0, e->stream>>>(vs.T, vs.Q, vs.B, e->q_M.as<u32>());
-      HIPCHK(hipGetLastError());
-      if (e->batch_filt || e->batch_prior) CHK(launch_filter(e, vs));
-    }
-    HIPCHK(hipGetLastError());
-#ifdef SGTD_EXP_PHASE
-    {
-      static int pcalls = 0;
-      if (++pcalls == 6) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        unsigned long long ph[8];
-        HIPCHK(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_phase), sizeof(ph)));
-        const double tot = (double)ph[7];
-        fprintf(stderr, "PHASE (fractions of wave life, %llu waves): prologue %.3f locate+issue %.3f wait-loads %.3f test %.3f epilogue %.3f between-passes %.3f rest %.3f\n",
-                ph[6], ph[0] / tot, ph[1] / tot, ph[2] / tot, ph[3] / tot, ph[4] / tot, ph[5] / tot,
-                (tot - ph[0] - ph[1] - ph[2] - ph[3] - ph[4] - ph[5]) / tot);
-      }
-    }
-#endif
-    if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_PROBE], e->stream));
-    // one 16-wave workgroup per (query, frame tile) when that fills the chip: the tile's LDS
-    // histogram is final (no flush atomics); spans beyond LDS take several tiles of 36 Ki frames
-    if (fused_votes) {
-      const size_t lds = votes_topk_lds_bytes(span);
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&votes_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      votes_topk_kernel<<<nq, SGTD_VT_THREADS, lds, e->stream>>>(v.Q, v.B, span, v.T.frame_lo, blocks, cn, e->q_M.as<u32>(),
-                                                                  e->q_P.as<unsigned long long>(), e->n_cand.as<int>(), e->cand_frame.as<int>(),
-                                                                  e->cand_votes.as<int>(), e->pair_off.as<long long>(), e->q_pairs.as<u32>());
-    } else if (votes_per_query) {
-      const size_t tile_bytes = (size_t)tile_span * sizeof(u32);
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&votes_query_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
-      votes_query_kernel<<<nq * (int)n_tiles, SGTD_VOTES_Q_THREADS, tile_bytes, e->stream>>>(
-          v.Q, v.B, span, v.T.frame_lo, tile_span, blocks, e->q_M.as<u32>(), e->q_P.as<unsigned long long>());
-    } else if (lds_votes) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&votes_kernel<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_bytes));
-      votes_kernel<true><<<agrid, 256, hist_bytes, e->stream>>>(v.Q, v.B, span, v.T.frame_lo, blocks, e->q_M.as<u32>(),
-                                                                e->q_P.as<unsigned long long>());
-    } else {
-      votes_kernel<false><<<agrid, 256, 0, e->stream>>>(v.Q, v.B, span, v.T.frame_lo, blocks, e->q_M.as<u32>(),
-                                                        e->q_P.as<unsigned long long>());
-    }
-    HIPCHK(hipGetLastError());
-    if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_VOTES], e->stream));
+  probe_sorted_kernel<DG, WD, FR, BD><<<p.sgrid, SGTD_PROBE_THREADS, 0, e->stream>>>(                           \
+      v.T, v.B, v.Q, PP, e->dc.rough, e->n_valid.as<u32>(), e->n_groups.as<u32>(), p.ticket)
+  if (e->diag) {
+    if (e->loop_batch) SGTD_LAUNCH_SORTED(true, true, true, true);
+    else SGTD_LAUNCH_SORTED(true, true, true, false);
+  } else if (e->loop_batch) {
+    if (p.narrow) SGTD_LAUNCH_SORTED(false, false, true, true);
+    else SGTD_LAUNCH_SORTED(false, true, true, true);
   }
-  if (!fused_votes) {
-    topk_kernel<<<nq, SGTD_TOPK_THREADS, 0, e->stream>>>(e->votes.as<u32>(), span, v.T.frame_lo, cn, e->n_cand.as<int>(),
-                                            e->cand_frame.as<int>(), e->cand_votes.as<int>(),
-                                            e->slot_of.as<unsigned char>());
+  else if (p.narrow && p.frames) SGTD_LAUNCH_SORTED(false, false, true, false);
+  else if (p.narrow) SGTD_LAUNCH_SORTED(false, false, false, false);
+  else if (p.frames) SGTD_LAUNCH_SORTED(false, true, true, false);
+  else SGTD_LAUNCH_SORTED(false, true, false, false);
+#undef SGTD_LAUNCH_SORTED
+  HIPCHK(hipGetLastError());
+  resolve_undecided_kernel<<<64, 256, 0, e->stream>>>(v.T, v.Q, v.B, e->q_M.as<u32>());
+  HIPCHK(hipGetLastError());
+  if (e->batch_filt || e->batch_prior) CHK(launch_filter(e, v));
+#ifdef SGTD_EXP_PHASE
+  {
+    static int pcalls = 0;
+    if (++pcalls == 6) {
+      HIPCHK(hipStreamSynchronize(e->stream));
+      unsigned long long ph[8];
+      HIPCHK(hipMemcpyFromSymbol(ph, HIP_SYMBOL(g_phase), sizeof(ph)));
+      const double tot = (double)ph[7];
+      fprintf(stderr, "PHASE (fractions of wave life, %llu waves): prologue %.3f locate+issue %.3f wait-loads %.3f test %.3f epilogue %.3f between-passes %.3f rest %.3f\n",
+              ph[6], ph[0] / tot, ph[1] / tot, ph[2] / tot, ph[3] / tot, ph[4] / tot, ph[5] / tot,
+              (tot - ph[0] - ph[1] - ph[2] - ph[3] - ph[4] - ph[5]) / tot);
+    }
+  }
+#endif
+  if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_PROBE], e->stream));
+  return SGTD_OK;
+}
+
+// the votes of every query's records, in the plan's form: with top-k in one launch per query, per (query, frame tile),
+// or by blocks into an LDS or a global histogram
+int launch_votes(sgtd_engine *e, const SelectPlan &p, const Views &v) {
+  u32 *q_M = e->q_M.as<u32>();
+  unsigned long long *q_P = e->q_P.as<unsigned long long>();
+  if (p.fused_votes) {
+    const size_t lds = votes_topk_lds_bytes(p.span);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&votes_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    votes_topk_kernel<<<p.nq, SGTD_VT_THREADS, lds, e->stream>>>(v.Q, v.B, p.span, v.T.frame_lo, p.blocks, p.cn, q_M, q_P, e->n_cand.as<int>(),
+                                                                  e->cand_frame.as<int>(), e->cand_votes.as<int>(), e->pair_off.as<long long>(),
+                                                                  e->q_pairs.as<u32>());
+  } else if (p.votes_per_query) {
+    const size_t tile_bytes = (size_t)p.tile_span * sizeof(u32);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&votes_query_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
+    votes_query_kernel<<<p.nq * (int)p.n_tiles, SGTD_VOTES_Q_THREADS, tile_bytes, e->stream>>>(v.Q, v.B, p.span, v.T.frame_lo, p.tile_span, p.blocks, q_M, q_P);
+  } else if (p.lds_votes) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&votes_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.hist_bytes));
+    votes_kernel<true><<<p.agrid, 256, p.hist_bytes, e->stream>>>(v.Q, v.B, p.span, v.T.frame_lo, p.blocks, q_M, q_P);
+  } else {
+    votes_kernel<false><<<p.agrid, 256, 0, e->stream>>>(v.Q, v.B, p.span, v.T.frame_lo, p.blocks, q_M, q_P);
+  }
+  HIPCHK(hipGetLastError());
+  if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_VOTES], e->stream));
+  return SGTD_OK;
+}
+
+int launch_topk(sgtd_engine *e, const SelectPlan &p, const Views &v) {
+  if (!p.fused_votes) {
+    topk_kernel<<<p.nq, SGTD_TOPK_THREADS, 0, e->stream>>>(e->votes.as<u32>(), p.span, v.T.frame_lo, p.cn, e->n_cand.as<int>(),
+                                                            e->cand_frame.as<int>(), e->cand_votes.as<int>(), e->slot_of.as<unsigned char>());
     HIPCHK(hipGetLastError());
   }
   if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_TOPK], e->stream));
-  CHK(export_candidates(e, v));      // (multi-GPU step: the local tables start travelling before the lists are written)
-  e->lists_pending = false;
-  e->lists_masked = false;
-  e->fused_votes_last = fused_votes;
-  if (fused_pairs) {
-    // the lists' offsets are the prefix sums of the candidates' votes; the lists themselves by one workgroup per query
-    e->pairs_per_query = true;
-    e->stats.select_form = fused_votes ? 2 : 1;
-    e->batch_valid = true;
-    if (e->defer_lists) {
-      // the caller writes the lists itself once it knows which candidates survive the merge (sgtd_finish_lists)
-      if (e->timing)
-        for (int k : {EV_COUNT_T, EV_SCAN, EV_WRITE}) HIPCHK(hipEventRecord(e->ev[k], e->stream));
-      batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
-      HIPCHK(hipGetLastError());
-      e->lists_pending = true;
-      new_results(e, false);
-      e->batch_synced = false;
-      return SGTD_OK;
-    }
-    return launch_lists(e, v, nullptr, /*first=*/true);
-  }
-  e->pairs_per_query = false;
-  e->stats.select_form = 0;
+  return SGTD_OK;
+}
+
+// the compact candidate lists between block_count_kernel and block_write_kernel, in the batch's geometry
+CompactLists compact_lists(sgtd_engine *e, const SelectPlan &p, const Views &v) {
   CompactLists CL;
   CL.pair = e->c_pair.as<u64>();
-  CL.blk_start = e->c_blk.as<u32>(); CL.blk_n = e->c_blk.as<u32>() + (size_t)nq * blocks;
+  CL.blk_start = e->c_blk.as<u32>(); CL.blk_n = e->c_blk.as<u32>() + (size_t)p.nq * p.blocks;
   CL.cursor = v.B.compact_cursor(); CL.cap = (u32)std::min<size_t>(e->c_pair.bytes / sizeof(u64), 0xFFFFFFF0u);
-  // the compact lists' words: 4 bytes where an entry's rank among its frame's fits 19 bits, else 8
-  const bool narrow_pairs = v.T.map.bits <= SGTD_NARROW_RANK_BITS && !e->wide_pairs;
-  if (span <= 48 * 1024) {
-    const int sl_bytes = (int)((span + 15) & ~15u);
-#define SGTD_LAUNCH_COUNT(NP)                                                                                          \
-  do {                                                                                                                 \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&block_count_kernel<true, NP>),                          \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, sl_bytes));                                 \
-    block_count_kernel<true, NP><<<agrid, 256, sl_bytes, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), cn, \
-                                                                      blocks, e->blk_count.as<u32>(), CL, nullptr, nullptr,      \
-                                                                      e->slot_of.as<unsigned char>(), span, v.T.frame_lo);        \
-  } while (0)
-    if (narrow_pairs) SGTD_LAUNCH_COUNT(true); else SGTD_LAUNCH_COUNT(false);
-#undef SGTD_LAUNCH_COUNT
-  } else {
-    if (narrow_pairs)
-      block_count_kernel<false, true><<<agrid, 256, 0, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), cn,
-                                                                    blocks, e->blk_count.as<u32>(), CL, nullptr, nullptr,
-                                                                    e->slot_of.as<unsigned char>(), span, v.T.frame_lo);
-    else
-      block_count_kernel<false, false><<<agrid, 256, 0, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), cn,
-                                                                     blocks, e->blk_count.as<u32>(), CL, nullptr, nullptr,
-                                                                     e->slot_of.as<unsigned char>(), span, v.T.frame_lo);
-  }
-  HIPCHK(hipGetLastError());
+  return CL;
+}
+
+// the match lists by the block passes: count (into the compact lists), scan, write
+int launch_block_lists(sgtd_engine *e, const SelectPlan &p, const Views &v) {
+  const int nq = p.nq;
+  const CompactLists CL = compact_lists(e, p, v);
+  // the frame -> slot byte table in LDS while the span fits
+  const int sl_bytes = p.span <= 48 * 1024 ? (int)((p.span + 15) & ~15u) : 0;
+  auto count = [&](auto kernel) -> int {
+    if (sl_bytes) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, sl_bytes));
+    kernel<<<p.agrid, 256, sl_bytes, e->stream>>>(v.Q, v.B, e->n_cand.as<int>(), e->cand_frame.as<int>(), p.cn, p.blocks, e->blk_count.as<u32>(), CL,
+                                                  nullptr, nullptr, e->slot_of.as<unsigned char>(), p.span, v.T.frame_lo);
+    HIPCHK(hipGetLastError());
+    return SGTD_OK;
+  };
+  if (sl_bytes) CHK(p.narrow_pairs ? count(&block_count_kernel<true, true>) : count(&block_count_kernel<true, false>));
+  else CHK(p.narrow_pairs ? count(&block_count_kernel<false, true>) : count(&block_count_kernel<false, false>));
   if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_COUNT_T], e->stream));
-  block_scan_kernel<<<nq, 64, 0, e->stream>>>(e->blk_count.as<u32>(), blocks, cn, e->n_cand.as<int>(),
+  // (a one-query batch: the scan leaves the query's base and the batch's totals itself)
+  block_scan_kernel<<<nq, 64, 0, e->stream>>>(e->blk_count.as<u32>(), p.blocks, p.cn, e->n_cand.as<int>(),
                                                e->pair_off.as<long long>(), e->q_pairs.as<u32>(),
-                                               v.B.overflow(), nq == 1 ? e->q_pair_base.as<u32>() : nullptr, (u32)std::min<size_t>(e->pair_cap, 0xFFFFFFF0u),
+                                               v.B.overflow(), nq == 1 ? e->q_pair_base.as<u32>() : nullptr, pair_room(e),
                                                nq == 1 ? e->totals.as<unsigned long long>() : nullptr);
   HIPCHK(hipGetLastError());
   if (nq != 1) {
-    query_base_kernel<<<1, 256, 0, e->stream>>>(e->q_pairs.as<u32>(), e->q_pair_base.as<u32>(), nq,
-                                                 (u32)std::min<size_t>(e->pair_cap, 0xFFFFFFF0u), v.B.overflow());
+    query_base_kernel<<<1, 256, 0, e->stream>>>(e->q_pairs.as<u32>(), e->q_pair_base.as<u32>(), nq, pair_room(e), v.B.overflow());
     HIPCHK(hipGetLastError());
   }
   if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_SCAN], e->stream));
-  CHK(launch_block_write(e, v, CL, agrid, blocks));
-  HIPCHK(hipGetLastError());
+  CHK(launch_block_write(e, p, v, CL));
   if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_WRITE], e->stream));
   if (nq != 1) {
     batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
     HIPCHK(hipGetLastError());
   }
   e->batch_valid = true;
+  new_results(e, false);
+  e->batch_synced = false;
+  return SGTD_OK;
+}
+
+// The engine's whole query pipeline behind descriptor construction, on the descriptors in e->qd: the batch's plan, then
+// its stages in order.
+int launch_select(sgtd_engine *e) {
+  e->plan = plan_select(e);
+  const SelectPlan &p = e->plan;
+  CHK(reserve_select(e, p));
+  CHK(clear_batch(e, p));
+  const Views v = make_views(e);
+  u32 *order = nullptr;
+  CHK(order_descriptors(e, p, v, &order));
+  CHK(plan_and_sweep(e, p, v, order));
+  CHK(launch_votes(e, p, v));
+  CHK(launch_topk(e, p, v));
+  CHK(export_candidates(e, v));      // (multi-GPU step: the local tables start travelling before the lists are written)
+  e->lists_pending = false;
+  e->lists_masked = false;
+  e->stats.select_form = p.fused_votes ? 2 : (p.fused_pairs ? 1 : 0);
+  if (!p.fused_pairs) return launch_block_lists(e, p, v);
+  // the lists' offsets are the prefix sums of the candidates' votes; the lists themselves by one workgroup per query
+  e->batch_valid = true;
+  if (!e->defer_lists) return launch_lists(e, v, nullptr, /*first=*/true);
+  // the caller writes the lists itself once it knows which candidates survive the merge (sgtd_finish_lists)
+  if (e->timing)
+    for (int k : {EV_COUNT_T, EV_SCAN, EV_WRITE}) HIPCHK(hipEventRecord(e->ev[k], e->stream));
+  batch_totals_kernel<<<1, 1, 0, e->stream>>>(v.B.ctr, e->totals.as<unsigned long long>());
+  HIPCHK(hipGetLastError());
+  e->lists_pending = true;
   new_results(e, false);
   e->batch_synced = false;
   return SGTD_OK;
@@ -1632,23 +1651,14 @@ int rerun(sgtd_engine *e) {
 // the candidate-pair buffer was too small: everything up to the per-block counts is intact,
 // only the output offsets and the write pass run again
 int rerun_write(sgtd_engine *e) {
-  const int nq = e->nq;
-  const int blocks = (int)((e->q_stride + block_chunk(e) - 1) / block_chunk(e));
-  const int groups = (blocks + 3) / 4;
-  const int agrid = ((nq + 7) / 8) * groups * 8;
+  const SelectPlan &p = e->plan;
   CHK(ensure(e, e->pairs, e->pair_cap * sizeof(u64)));
-  Views v = make_views(e);
+  const Views v = make_views(e);
   HIPCHK(hipMemsetAsync(v.B.overflow() + 1, 0, sizeof(int), e->stream));
-  if (e->pairs_per_query) return launch_lists(e, v, e->lists_masked ? e->list_keep : nullptr, /*first=*/false);
-  CompactLists CL;
-  CL.pair = e->c_pair.as<u64>();
-  CL.blk_start = e->c_blk.as<u32>(); CL.blk_n = e->c_blk.as<u32>() + (size_t)nq * blocks;
-  CL.cursor = v.B.compact_cursor(); CL.cap = (u32)std::min<size_t>(e->c_pair.bytes / sizeof(u64), 0xFFFFFFF0u);
-  query_base_kernel<<<1, 256, 0, e->stream>>>(e->q_pairs.as<u32>(), e->q_pair_base.as<u32>(), nq,
-                                               (u32)std::min<size_t>(e->pair_cap, 0xFFFFFFF0u), v.B.overflow());
+  if (p.fused_pairs) return launch_lists(e, v, e->lists_masked ? e->list_keep : nullptr, /*first=*/false);
+  query_base_kernel<<<1, 256, 0, e->stream>>>(e->q_pairs.as<u32>(), e->q_pair_base.as<u32>(), p.nq, pair_room(e), v.B.overflow());
   HIPCHK(hipGetLastError());
-  CHK(launch_block_write(e, v, CL, agrid, blocks));
-  return SGTD_OK;
+  return launch_block_write(e, p, v, compact_lists(e, p, v));
 }
 
 // A handle attached to another one's table (sgtd_attach_table) holds that table's device pointers.  Whatever changes the
@@ -2381,22 +2391,30 @@ static int prior_fits(sgtd_engine *e, int n_queries) {
   return SGTD_OK;
 }
 
-static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
-                              int n_queries, int device_ptrs, u32 qframe, bool loop, int32_t skip_near) {
-  CHK(settle_tail(e));
-  const float *dx; const u32 *dl; int max_n;
-  CHK(stage_inputs(e, xyz, label, kp_off, n_queries, device_ptrs, &dx, &dl, &max_n));
-  e->nq = n_queries;
-  e->q_stride = (long long)std::max(max_n, 1) * e->dc.tpi;
-  e->last_kind = 1; e->last_xyz = dx; e->last_label = dl; e->last_max_n = max_n;
-  e->last_qframe = qframe;
+// What every batch starts with: its shape and kind, the filter and the prior it runs under (a loop batch: none), the
+// product form of the sweep, the reservation rate's recovery, room for its descriptors and their counts.
+static int begin_batch(sgtd_engine *e, int nq, long long q_stride, int kind, bool loop = false, int32_t skip_near = 0) {
+  e->nq = nq;
+  e->q_stride = q_stride;
+  e->last_kind = kind;
   e->loop_batch = loop; e->loop_skip = loop ? skip_near : 0;
   e->batch_filt = loop ? nullptr : e->filt;
   e->batch_prior = loop ? nullptr : e->prior;
   e->diag = false;   // a new batch runs the product sweep; sgtd_result_rough re-runs it in the diagnostic form
   e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);   // (a cap a re-run needed recovers slowly)
-  CHK(ensure_store(e, e->qd, (size_t)e->q_stride * n_queries));
-  CHK(ensure(e, e->q_count, (size_t)n_queries * sizeof(u32)));
+  CHK(ensure_store(e, e->qd, (size_t)q_stride * nq));
+  CHK(ensure(e, e->q_count, (size_t)nq * sizeof(u32)));
+  return SGTD_OK;
+}
+
+static int query_frames_batch(sgtd_handle e, const float *xyz, const uint32_t *label, const int64_t *kp_off,
+                              int n_queries, int device_ptrs, u32 qframe, bool loop, int32_t skip_near) {
+  CHK(settle_tail(e));
+  const float *dx; const u32 *dl; int max_n;
+  CHK(stage_inputs(e, xyz, label, kp_off, n_queries, device_ptrs, &dx, &dl, &max_n));
+  e->last_xyz = dx; e->last_label = dl; e->last_max_n = max_n;
+  e->last_qframe = qframe;
+  CHK(begin_batch(e, n_queries, (long long)std::max(max_n, 1) * e->dc.tpi, /*kind=*/1, loop, skip_near));
   if (!e->rec_cap_fixed && e->stats.last_queries == 0) {
     // first batch of this handle: size the match-record buffer from the table statistics instead
     // of growing it through overflow re-runs (each costs a whole sweep)
@@ -2452,16 +2470,7 @@ int sgtd_query_descs(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq) {
   CHK(prior_fits(e, 1));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   CHK(settle_tail(e));
-  e->nq = 1;
-  e->q_stride = std::max<long long>(nq, 1);
-  e->last_kind = 2;
-  e->loop_batch = false;
-  e->batch_filt = e->filt;
-  e->batch_prior = e->prior;
-  e->diag = false;
-  e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
-  CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
-  CHK(ensure(e, e->q_count, sizeof(u32)));
+  CHK(begin_batch(e, 1, std::max<long long>(nq, 1), /*kind=*/2));
   CHK(copy_in(e, e->qd, 0, (size_t)nq, q));
   e->thr2_pending = nq;      // the descriptors' sweep records (thresholds, gate masks): launch_select writes them — one frame per call in its one launch
   u32 cnt = (u32)nq;
@@ -2619,7 +2628,7 @@ int sgtd_finish_lists(sgtd_handle e, const uint64_t *d_keep) {
   if (!e) return SGTD_ERR_INVALID;
   if (!e->batch_valid) return SGTD_ERR_STATE;
   HIPCHK(hipSetDevice(e->cfg.device_id));
-  if (!e->pairs_per_query) {
+  if (!e->plan.fused_pairs) {
     // the lists of this batch came from the passes of one wave per 128-descriptor block (small batches, frame spans
     // beyond LDS): they hold every local candidate already; a mask only matters to sgtd_verify_masked
     return SGTD_OK;
@@ -3054,16 +3063,7 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
 #endif
   CHK(settle_tail(e));
   // ---- sgtd_query_descs without its waits
-  e->nq = 1;
-  e->q_stride = std::max<long long>(nq, 1);
-  e->last_kind = 2;
-  e->loop_batch = false;
-  e->batch_filt = e->filt;
-  e->batch_prior = e->prior;
-  e->diag = false;
-  e->rec_rate_cap = e->stats.overflowed ? e->rec_rate_cap : std::min<u32>(256, e->rec_rate_cap * 2);
-  CHK(ensure_store(e, e->qd, (size_t)e->q_stride));
-  CHK(ensure(e, e->q_count, sizeof(u32)));
+  CHK(begin_batch(e, 1, std::max<long long>(nq, 1), /*kind=*/2));
   CHK(copy_in(e, e->qd, 0, (size_t)nq, q, /*wait=*/false));
   LAP("descriptors_in");
   e->thr2_pending = nq;      // the descriptors' sweep records (thresholds, gate masks): launch_select writes them — one frame per call in its one launch
@@ -3083,11 +3083,11 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   const long long *out_off = e->pair_off.as<long long>();
   if (!lists_only) {
     // ---- candidate_verify behind it, sized by what the pair buffer holds
-    CHK(verify_enqueue(e, (int64_t)std::min<size_t>(e->pair_cap, 0xFFFFFFF0u), /*guard=*/true));
+    CHK(verify_enqueue(e, (int64_t)pair_room(e), /*guard=*/true));
     // ---- the inlier pairs of every candidate, compacted by one workgroup per candidate, and the entries they name
     CHK(ensure(e, e->inl_counts, (size_t)SGTD_MAX_CAND * sizeof(u32)));
     CHK(ensure(e, e->inl_off, (size_t)(cn + 1) * sizeof(long long)));
-    CHK(ensure(e, e->inl_pairs, std::min<size_t>(e->pair_cap, 0xFFFFFFF0u) * sizeof(u64)));
+    CHK(ensure(e, e->inl_pairs, (size_t)pair_room(e) * sizeof(u64)));
     if (!e->verify_counted) {     // (the packed-f32 form of the vote pass does not count)
       inlier_count_kernel<<<cn, SGTD_INLIER_CAND_THREADS, 0, e->stream>>>(e->v_inlier.as<unsigned char>(), e->pair_off.as<long long>(), e->n_cand.as<int>(), ovf,
                                                                            e->inl_counts.as<u32>());

@@ -24,7 +24,7 @@ SGTD_TOPK_BINS = 8192
 SGTD_TOPK_POOL = 1024
 SGTD_CAND_HASH = 256
 SGTD_MAX_CAND = 64
-VOTES_TILE_FRAMES = 36 * 1024          # frames per tile of votes_query_kernel (launch_select)
+VOTES_TILE_FRAMES = 36 * 1024          # frames per tile of votes_query_kernel (plan_select)
 WAVE = 64
 PQ_WAVES = SGTD_PQ_THREADS // WAVE
 PQ_TILE_QUADS = PQ_WAVES * SGTD_PQ_WORDS * WAVE

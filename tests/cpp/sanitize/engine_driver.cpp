@@ -3,10 +3,13 @@
 // would have — overflow flags, record needs, pair totals, a frame's packed results — so that the host walks its growth,
 // re-run, stale-view, capacity and table-file paths with every copy checked by the sanitizer.  The stages on a verified batch
 // (sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints) run in a scenario of their own below, whose stand-in results name the
-// (query, candidate) slot they belong to.  Compiled for the host only
+// (query, candidate) slot they belong to.  The forms of the query pipeline (launch_select's plan and stages, the list pass run
+// again, deferred lists, the diagnostic re-run) run in a third scenario with the stand-in's trace on: every launch, memset,
+// attribute and event record is a line of the transcript.  Compiled for the host only
 // (hipcc --cuda-host-only: the kernel headers are needed for the argument structs); tests/test_sanitizers.py builds and runs it.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -46,8 +49,10 @@ unsigned long long sgtd_stub_waits();
 unsigned sgtd_stub_grid_x();
 size_t sgtd_stub_device_bytes();
 size_t sgtd_stub_device_peak();
+size_t sgtd_stub_device_peak_restart();
 size_t sgtd_stub_device_blocks();
 size_t sgtd_stub_block_size(const void *p);
+void sgtd_stub_set_trace(FILE *f);
 }
 
 #define REQUIRE(x) do { if (!(x)) { fprintf(stderr, "engine_driver: %s failed at line %d\n", #x, __LINE__); exit(1); } } while (0)
@@ -69,7 +74,12 @@ struct Scenario {
   bool stages = false;
   int expect_order = -1;            // the frame-ordered dispatch of the four kernels that take one: 1 it must be there, 0 it must not, -1 either
   unsigned long long stage_launches[4] = {0, 0, 0, 0};      // verify, refine, overlap, align
+  // the select-forms scenario
+  unsigned longest = 0;             // frame_longest_kernel: entries of the table's largest frame (0: leave the zero), sizes the entry ids' rank
+  unsigned rough_matches = 0;       // resolve_undecided_kernel: rough matches of query 0 (sgtd_result_rough has something to gather)
 };
+bool g_tracing = false;             // the select-forms scenario: every launch adds its scalars to the transcript (trace_args)
+void trace_args(const char *name, void **args);
 
 // bytes from p to the end of the block it lies in
 size_t room_of(const void *p) {
@@ -138,7 +148,12 @@ std::vector<const void *> g_gathers_into;      // gather_pair_entries_kernel lau
 
 void hook(const char *name, void **args, void *user) {
   Scenario &S = *static_cast<Scenario *>(user);
-  if (strstr(name, "probe_sorted_kernel")) {
+  if (g_tracing) trace_args(name, args);
+  if (strstr(name, "frame_longest_kernel")) {
+    if (S.longest) (*static_cast<u32 **>(args[4]))[0] = S.longest;
+  } else if (strstr(name, "resolve_undecided_kernel")) {
+    if (S.rough_matches) (*static_cast<u32 **>(args[3]))[0] = S.rough_matches;
+  } else if (strstr(name, "probe_sorted_kernel")) {
     S.sweeps++;
     const ProbeBuffers &B = *static_cast<const ProbeBuffers *>(args[1]);
     REQUIRE(sgtd_stub_block_size(B.ctr) >= 12 * sizeof(u32));
@@ -772,6 +787,326 @@ struct Stages {
     S.stages = false;
   }
 };
+// ---- the forms of the query pipeline (launch_select and what runs on its batch later), launch by launch ----
+// While the stand-in's trace is on, every launch, memset, attribute and event record of the engine is a line of the transcript,
+// and the hook adds the scalars of the launch it can type.  Two builds of the engine whose transcripts are equal enqueue the
+// same work with the same geometry.
+std::vector<std::string> g_launched;      // kernel names (as registered) launched while the trace was on, each once
+template <class T> const T &arg(void **a, int k) { return *static_cast<const T *>(a[k]); }
+
+void trace_args(const char *name, void **a) {
+  namespace K = kernels_of_the_engine;
+  FILE *f = g_transcript;
+  if (std::find(g_launched.begin(), g_launched.end(), name) == g_launched.end()) g_launched.push_back(name);
+  if (!f) return;
+  auto has = [&](const char *s) { return strstr(name, s) != nullptr; };
+  auto i = [&](const char *n, int k) { fprintf(f, " %s %d", n, arg<int>(a, k)); };
+  auto u = [&](const char *n, int k) { fprintf(f, " %s %u", n, arg<u32>(a, k)); };
+  auto l = [&](const char *n, int k) { fprintf(f, " %s %lld", n, arg<long long>(a, k)); };
+  auto p = [&](const char *n, int k) { fprintf(f, " %s %d", n, arg<const void *>(a, k) != nullptr); };
+  auto Q = [&](int k) { const K::QueryView &q = arg<K::QueryView>(a, k); fprintf(f, " Q{stride %lld n_queries %d chunk %u}", q.stride, q.n_queries, q.chunk); };
+  auto B = [&](int k) {
+    const ProbeBuffers &b = arg<ProbeBuffers>(a, k);
+    fprintf(f, " B{rec_cap %u rec_slab %u rec_rate %u id_bits %u amb_cap %u rec room %zu}", b.rec_cap, b.rec_slab, b.rec_rate, b.id_bits, b.amb_cap, sgtd_stub_block_size(b.rec));
+  };
+  auto T = [&](int k) {
+    const K::TableView &t = arg<K::TableView>(a, k);
+    fprintf(f, " T{n_entries %u frame_lo %u frame_span %u tail_off %u n_entries1 %u map.bits %u map.frame_lo %u by_frame %d coarse_at %u whole_at %u}", t.n_entries, t.frame_lo, t.frame_span,
+            t.tail_off, t.n_entries1, t.map.bits, t.map.frame_lo, t.map.by_frame != nullptr, t.coarse_at, t.whole_at);
+  };
+  auto M = [&](int k) { const K::IdMap &m = arg<K::IdMap>(a, k); fprintf(f, " map{bits %u frame_lo %u}", m.bits, m.frame_lo); };
+  auto PP = [&](int k) { fprintf(f, " pool.cap %u", arg<K::PassPool>(a, k).cap); };
+  auto CL = [&](int k) { const K::CompactLists &c = arg<K::CompactLists>(a, k); fprintf(f, " CL{cap %u blocks %lld}", c.cap, (long long)(c.blk_n - c.blk_start)); };
+  fprintf(f, "  args");
+  if (has("small_order_kernel")) {
+    const K::SmallOrder &o = arg<K::SmallOrder>(a, 1);
+    Q(0);
+    fprintf(f, " SO{ctr_words %u votes %d span %u cand_num %d n_slots %u max_pass_slots %u cbits %d sub_bits %d pair %d key_bits %d n_qrec %u rough %.17g}", o.ctr_words, o.votes != nullptr,
+            o.span, o.cand_num, o.n_slots, o.max_pass_slots, o.cbits, o.sub_bits, o.pair, o.key_bits, o.n_qrec, o.rough);
+  } else if (has("thr2_kernel")) { l("n", 3); fprintf(f, " rough %.17g", arg<double>(a, 4)); }
+  else if (has("loop_bound_kernel")) { l("stride", 1); i("nq", 2); u("frame0", 3); i("skip_near", 4); u("frame_lo", 5); }
+  else if (has("query_prefix_kernel")) i("nq", 2);
+  else if (has("home_keys_kernel")) { Q(0); l("n_slots", 4); i("cbits", 5); i("sub_bits", 6); }
+  else if (has("radix_hist_kernel")) { l("n", 1); i("shift", 2); i("nblocks", 4); p("n_dev", 5); }
+  else if (has("group_heads_kernel")) { l("n", 3); i("cbits", 4); i("sub_bits", 5); }
+  else if (has("group_first_kernel")) l("n", 4);
+  else if (has("pass_slots_kernel")) { l("n", 4); i("pair", 5); }
+  else if (has("group_resolve_kernel")) { T(0); Q(1); u("rows_cap", 7); fprintf(f, " rows room %zu", sgtd_stub_block_size(arg<const void *>(a, 6))); }
+  else if (has("plan_passes_kernel")) { T(0); Q(1); u("rows_cap", 8); PP(9); }
+  else if (has("probe_sorted_kernel")) { T(0); B(1); Q(2); PP(3); fprintf(f, " rough %.17g", arg<double>(a, 4)); u("ticket", 7); }
+  else if (has("resolve_undecided_kernel")) { T(0); Q(1); B(2); }
+  else if (has("filter_records_kernel") || has("filter_compact_kernel")) { Q(0); B(1); i("n_rows", 3); u("n_words", 4); u("span", 5); i("wg_per_q", 6); }
+  else if (has("prior_rows_kernel")) { u("span", 1); u("words", 2); i("prm_rows", 4); i("dims", 5); p("base", 6); i("base_rows", 7); i("n_rows", 8); }
+  else if (has("votes_topk_kernel")) { Q(0); B(1); u("span", 2); u("frame_lo", 3); i("blocks", 4); i("cn", 5); }
+  else if (has("votes_query_kernel")) { Q(0); B(1); u("span", 2); u("frame_lo", 3); u("tile_span", 4); i("blocks", 5); }
+  else if (has("votes_kernel")) { Q(0); B(1); u("span", 2); u("frame_lo", 3); i("blocks", 4); }
+  else if (has("topk_kernel")) { u("span", 1); u("frame_lo", 2); i("cn", 3); }
+  else if (has("export_candidates_kernel")) { i("nq", 3); i("cn", 4); u("serial", 5); }
+  else if (has("cand_prefix_masked_kernel")) { i("cn", 3); i("nq", 4); }
+  else if (has("cand_prefix_kernel")) { i("cn", 2); i("nq", 3); }
+  else if (has("query_base_kernel")) { i("nq", 2); u("pair_cap", 3); }
+  else if (has("pairs_query_kernel")) { Q(0); B(1); i("cn", 4); M(8); u("span", 9); u("frame_lo", 10); p("keep", 11); }
+  else if (has("block_count_kernel")) { Q(0); B(1); i("cn", 4); i("blocks", 5); CL(7); u("span", 11); u("frame_lo", 12); }
+  else if (has("block_scan_kernel")) { i("blocks", 1); i("cn", 2); p("base_of_one", 7); u("pair_cap", 8); p("totals_of_one", 9); }
+  else if (has("block_write_kernel")) { Q(0); B(1); CL(2); i("blocks", 3); i("cn", 5); M(9); }
+  else if (has("rough_gather_kernel")) { Q(0); B(1); M(2); i("q", 3); p("cell", 7); p("dis", 8); }
+  fprintf(f, "\n");
+}
+
+struct Env {      // an environment knob for the length of a scope
+  const char *key;
+  Env(const char *k, const char *v) : key(k) { setenv(k, v, 1); }
+  ~Env() { unsetenv(key); }
+};
+
+struct SelectForms {
+  Scenario &S;
+  std::mt19937 &rng;
+  sgtd_config base;
+  sgtd_handle h = nullptr;
+  void note(const char *fmt, long long a = 0, long long b = 0, long long c = 0) { if (g_transcript) { fprintf(g_transcript, "# "); fprintf(g_transcript, fmt, a, b, c); fprintf(g_transcript, "\n"); } }
+
+  // a finalized table of two frames, ids 0 and span - 1 (the span costs nothing but the per-frame arrays); `stamp`: the id
+  // the next query frame is stamped with, less two; tail: a third frame appended behind the finalized table
+  void table(const sgtd_config &cfg_, uint32_t span, uint32_t stamp = 0, bool tail = false) {
+    sgtd_config cfg = cfg_;
+    cfg.max_frame_n = 700000; cfg.first_frame_id = stamp;
+    note("table: span %lld, stamp %lld, tail %lld", span, stamp, tail);
+    OK(sgtd_create(&cfg, &h));
+    g_last = h;
+    for (uint32_t id : {0u, span - 1}) {
+      if (id == 0 && span == 1) continue;
+      Descs d = random_descs(rng, 60, id);
+      sgtd_desc_soa s = d.soa();
+      CALL(SGTD_OK, h, sgtd_add(h, &s, 60));
+    }
+    CALL(SGTD_OK, h, sgtd_finalize(h));
+    if (tail) {
+      Descs d = random_descs(rng, 40, span);      // (newer than the main segment's newest frame: the span grows by one)
+      sgtd_desc_soa s = d.soa();
+      CALL(SGTD_OK, h, sgtd_add(h, &s, 40));
+      CALL(SGTD_OK, h, sgtd_finalize(h));
+      sgtd_stats st;
+      OK(sgtd_get_stats(h, &st));
+      REQUIRE(st.tail_entries > 0);
+    }
+  }
+  void done() { OK(sgtd_destroy(h)); h = nullptr; g_last = nullptr; }
+
+  void frames(int nq, int kp = 14, bool sync = true) {
+    Keypoints k;
+    for (int q = 0; q < nq; q++) k.add(rng, kp - q % 3);
+    note("frames batch: %lld queries of up to %lld keypoints", nq, kp);
+    CALL(SGTD_OK, h, sgtd_query_frames(h, k.xyz.data(), k.label.data(), k.off.data(), nq, 0));
+    if (sync) CALL(SGTD_OK, h, sgtd_sync(h));
+  }
+  void descs(int n, bool sync = true) {
+    Descs q = random_descs(rng, (size_t)n, 3);
+    sgtd_desc_soa qs = q.soa();
+    note("one-query batch: %lld descriptors", n);
+    CALL(SGTD_OK, h, sgtd_query_descs(h, &qs, n));
+    if (sync) CALL(SGTD_OK, h, sgtd_sync(h));
+  }
+  void rough(int q) {       // the diagnostic re-run and its gather
+    std::vector<int32_t> qi(64), cell(64); std::vector<int64_t> en(64), n(1); std::vector<uint32_t> fr(64); std::vector<double> dis(64);
+    S.rough_matches = 5;
+    CALL(SGTD_OK, h, sgtd_result_rough(h, q, qi.data(), cell.data(), en.data(), fr.data(), dis.data(), 64, n.data()), n);
+    CALL(SGTD_OK, h, sgtd_result_rough(h, q, qi.data(), cell.data(), en.data(), fr.data(), dis.data(), 64, n.data()), n);      // (diagnostic already: no re-run)
+    S.rough_matches = 0;
+  }
+  // both overflows of a batch in the form the handle gives `nq` queries: a sweep that outgrows the records (a whole re-run), candidate
+  // pairs that outgrow their buffer (the list pass alone)
+  void overflows(int nq) {
+    sgtd_stats st;
+    S.sweep_overflows = 1; S.need = 200000;
+    frames(nq);
+    OK(sgtd_get_stats(h, &st));
+    REQUIRE(st.overflowed == 1 && S.sweep_overflows == 0);
+    S.pair_overflows = 1; S.pairs_total = 2000000;
+    frames(nq);
+    OK(sgtd_get_stats(h, &st));
+    REQUIRE(st.rewrites_total >= 1 && S.pair_overflows == 0);
+    S.pairs_total = 100;
+  }
+
+  void run() {
+    S.pairs_total = 100;
+    const size_t peak_before = sgtd_stub_device_peak_restart();
+    g_tracing = true;
+    sgtd_stub_set_trace(g_transcript);
+    // ---- spans on both sides of every threshold the choice of forms compares against, in the three select modes; the stand-in
+    // leaves a kernel 150 KB of dynamic LDS
+    const size_t room = 150 * 1024;
+    uint32_t fit_votes = 1, fit_table = 1;
+    while (kernels_of_the_engine::votes_topk_lds_bytes(fit_votes + 1) <= room) fit_votes++;
+    while ((size_t)SGTD_PQ_TILE_RECS * sizeof(u32) + (((size_t)fit_table + 1 + 15) & ~(size_t)15) + 16 <= room) fit_table++;
+    note("largest span whose vote histogram fits votes_topk_kernel: %lld; whose byte table fits pairs_query_kernel: %lld", fit_votes, fit_table);
+    std::vector<uint32_t> spans = {1, 100, fit_votes, fit_votes + 1, 36 * 1024, 36 * 1024 + 1, 150 * 1024 / 4, 150 * 1024 / 4 + 1, 48 * 1024, 48 * 1024 + 1,
+                                   fit_table, fit_table + 1, 8 * 36 * 1024, 8 * 36 * 1024 + 1};
+    for (uint32_t span : spans)
+      for (const char *mode : {"0", "1", "2"}) {
+        note("---- span %lld, SGTD_SELECT_MODE %lld", span, atoi(mode));
+        { Env m("SGTD_SELECT_MODE", mode); table(base, span); }
+        frames(8);
+        frames(span > 200000 ? 2 : 256);        // (few queries for the widest spans)
+        if (span <= 100) { frames(255); frames(256, 15); }     // (256 queries of 540 slots: 1280 blocks of 128, the chunk does not halve)
+        descs(700);
+        done();
+      }
+    // ---- the compact lists' 8-byte words (SGTD_WIDE_PAIRS=1), with the slot table in LDS and with the candidates' hash
+    for (uint32_t span : {48u * 1024, 48u * 1024 + 1}) {
+      { Env w("SGTD_WIDE_PAIRS", "1"); table(base, span); }
+      frames(8); frames(256); descs(700);
+      done();
+    }
+    // ---- one-query batches: at most 8 192 slots and more, the general ordering chain by SGTD_SMALL_ORDER=0; the block chunk by
+    // SGTD_BLOCK_CHUNK; the other per-batch knobs; sgtd_search_frame; timing on
+    table(base, 100);
+    descs(8192); descs(8193);
+    { Env o("SGTD_SMALL_ORDER", "0"); descs(700); }
+    { Env c("SGTD_BLOCK_CHUNK", "32"); frames(256, 15); descs(700); }
+    { Env c("SGTD_BLOCK_CHUNK", "64"); frames(8); }
+    { Env a("SGTD_HOME_SUB_BITS", "3"); Env b("SGTD_SWEEP_BLOCKS_PER_CU", "3"); Env c("SGTD_PLAN_BLOCKS_PER_CU", "2"); Env d("SGTD_REC_SLAB", "2048"); frames(8); descs(700); }
+    CALL(SGTD_OK, h, sgtd_set_timing(h, 1));
+    frames(8); frames(256); descs(700);
+    {
+      const int cn = base.candidate_num;
+      std::vector<int32_t> fcf((size_t)cn), fcv((size_t)cn), fqi(4000);
+      std::vector<int64_t> fpo((size_t)cn + 1), fio((size_t)cn + 1);
+      std::vector<double> fsc((size_t)cn), fps((size_t)cn * 12);
+      Descs ent; ent.resize(4000);
+      Descs q = random_descs(rng, 700, 3);
+      sgtd_desc_soa qs = q.soa();
+      sgtd_frame_search io{};
+      io.cand_frame = fcf.data(); io.cand_votes = fcv.data(); io.pair_off = fpo.data(); io.score = fsc.data(); io.pose = fps.data();
+      io.inlier_off = fio.data(); io.inlier_q_idx = fqi.data(); io.entries = ent.soa(); io.capacity = 4000;
+      S.frame_inliers = 10;
+      CALL(SGTD_OK, h, sgtd_set_deferred_lists(h, 1));          // (suspended inside the call)
+      CALL(SGTD_OK, h, sgtd_search_frame(h, &qs, 700, &io));
+      io.flags = SGTD_FRAME_LISTS_ONLY;
+      CALL(SGTD_OK, h, sgtd_search_frame(h, &qs, 700, &io));
+      CALL(SGTD_OK, h, sgtd_set_deferred_lists(h, 0));
+      S.frame_inliers = -1;
+    }
+    rough(0);
+    done();
+    // ---- the overflows, once in each list form and in a one-query batch (small work buffers: SGTD_REC_CAP, SGTD_PAIR_CAP)
+    { Env r("SGTD_REC_CAP", "1048576"); Env c("SGTD_PAIR_CAP", "65536"); table(base, 100); }
+    overflows(8); overflows(256);
+    { S.sweep_overflows = 1; S.need = 10; S.reservations = true; descs(700); S.reservations = false; S.pair_overflows = 1; S.pairs_total = 2000000; descs(700); S.pairs_total = 100; }
+    done();
+    // ---- a key of more than 32 bits (cells of a quarter of the default: 8 bits a coordinate)
+    { sgtd_config c = base; c.std_side_resolution = 0.25; table(c, 100); }
+    frames(8); descs(700);
+    done();
+    // ---- 64 candidates; ranks of 17 bits with them (the corner that takes the block form), of 18 and of 20 bits (8-byte compact words)
+    for (unsigned longest : {0u, 1u << 17, (1u << 17) + 1, (1u << 19) + 1}) {
+      sgtd_config c = base; c.candidate_num = 64;
+      S.longest = longest;
+      { Env m("SGTD_SELECT_MODE", "2"); table(c, 100); }
+      S.longest = 0;
+      frames(8); descs(700);
+      done();
+    }
+    // ---- a tail segment; a frames batch stamped outside the table's frame range; the diagnostic re-run of each
+    table(base, 100, 0, /*tail=*/true);
+    frames(8); rough(0); frames(256); descs(700); rough(0);
+    done();
+    table(base, 100, /*stamp=*/500);
+    frames(8); rough(0); frames(256);
+    done();
+    // ---- sgtd_loop_frames: the frames join the table, each is a query bounded by its own id; its diagnostic re-run
+    table(base, 100, /*stamp=*/100);
+    {
+      Keypoints k;
+      for (int q = 0; q < 6; q++) k.add(rng, 14);
+      CALL(SGTD_OK, h, sgtd_loop_frames(h, k.xyz.data(), k.label.data(), k.off.data(), 6, 2, 0));
+      CALL(SGTD_OK, h, sgtd_sync(h));
+      rough(0);
+    }
+    done();
+    // ---- deferred lists (one workgroup per query): finished with a mask, with none, by a plain sgtd_sync; with timing; on a batch
+    // in the block form (nothing to finish); a registered candidate-export buffer beside them
+    {
+      { Env m("SGTD_SELECT_MODE", "0"); table(base, 100); }
+      void *keep = nullptr, *packed = nullptr;
+      REQUIRE(hipMalloc(&keep, 256 * sizeof(u64)) == hipSuccess && hipMalloc(&packed, (size_t)(1 << 16) * sizeof(int)) == hipSuccess);
+      memset(keep, 0x55, 256 * sizeof(u64));
+      CALL(SGTD_OK, h, sgtd_set_candidate_export(h, static_cast<int32_t *>(packed), 1 << 16));
+      CALL(SGTD_OK, h, sgtd_set_deferred_lists(h, 1));
+      for (int timing : {0, 1}) {
+        CALL(SGTD_OK, h, sgtd_set_timing(h, timing));
+        frames(256, 14, false);
+        CALL(SGTD_OK, h, sgtd_finish_lists(h, static_cast<const uint64_t *>(keep)));
+        CALL(SGTD_OK, h, sgtd_sync(h));
+        if (!timing) {      // (the re-run of a masked list pass: the same mask)
+          S.pair_overflows = 1; S.pairs_total = 2000000;
+          CALL(SGTD_OK, h, sgtd_finish_lists(h, static_cast<const uint64_t *>(keep)));
+          CALL(SGTD_OK, h, sgtd_sync(h));
+          S.pairs_total = 100;
+        }
+        frames(256, 14, false);
+        CALL(SGTD_OK, h, sgtd_finish_lists(h, nullptr));
+        CALL(SGTD_OK, h, sgtd_sync(h));
+        frames(256, 14, false);
+        CALL(SGTD_OK, h, sgtd_sync(h));       // (finds the lists pending)
+        frames(8, 14, false);
+        CALL(SGTD_OK, h, sgtd_finish_lists(h, static_cast<const uint64_t *>(keep)));
+        CALL(SGTD_OK, h, sgtd_sync(h));
+      }
+      {     // a registered buffer too small for the batch's tables
+        CALL(SGTD_OK, h, sgtd_set_candidate_export(h, static_cast<int32_t *>(packed), 1024));
+        Keypoints k;
+        for (int q = 0; q < 256; q++) k.add(rng, 14);
+        CALL(SGTD_ERR_CAPACITY, h, sgtd_query_frames(h, k.xyz.data(), k.label.data(), k.off.data(), 256, 0));
+      }
+      done();
+      REQUIRE(hipFree(keep) == hipSuccess && hipFree(packed) == hipSuccess);
+    }
+    // ---- a frame filter (one row, a row per query) and a position prior over stored poses (alone, and with the filter), in both
+    // list forms and in the diagnostic re-run; then a span whose filter rows do not fit the filter kernels' LDS
+    for (uint32_t span : {100u, 600000u}) {
+      table(base, span);
+      const uint32_t words = (span + 63) / 64;
+      const int many = span == 100 ? 256 : 2;
+      std::vector<uint64_t> rows((size_t)words * many, 0x0F0F0F0F0F0F0F0Full);
+      std::vector<uint32_t> ids = {0, span - 1};
+      std::vector<float> poses(24, 0.f);
+      poses[0] = poses[5] = poses[10] = poses[12] = poses[17] = poses[22] = 1.f; poses[3] = 4.f; poses[15] = 90.f;
+      const double center[3] = {0.0, 0.0, 0.0}, radius[1] = {10.0};
+      std::vector<double> centers((size_t)many * 3, 1.0), radii((size_t)many, 20.0);
+      CALL(SGTD_OK, h, sgtd_set_frame_filter(h, 0, span, rows.data(), 1));
+      frames(8); frames(many); frames(many);      // (the second batch of the same filter reuses its rows)
+      descs(700); rough(0);
+      CALL(SGTD_OK, h, sgtd_set_frame_filter(h, 0, span, rows.data(), many));
+      frames(many);
+      CALL(SGTD_OK, h, sgtd_set_frame_poses(h, ids.data(), poses.data(), 2));
+      CALL(SGTD_OK, h, sgtd_set_position_prior(h, centers.data(), radii.data(), many, 3));
+      frames(many);
+      CALL(SGTD_OK, h, sgtd_set_frame_filter(h, 0, 0, nullptr, 0));
+      CALL(SGTD_OK, h, sgtd_set_position_prior(h, center, radius, 1, 2));
+      frames(8); frames(many); descs(700); rough(0);
+      done();
+    }
+    sgtd_stub_set_trace(nullptr);
+    g_tracing = false;
+    const size_t peak = sgtd_stub_device_peak_restart();
+    printf("select forms: %zu kernel forms launched, device peak %.1f MB (before: %.1f MB)\n", g_launched.size(), peak / 1048576.0, peak_before / 1048576.0);
+    REQUIRE(peak < ((size_t)2 << 30));
+    // ---- coverage, from the trace itself: every kernel instantiation these functions can launch was launched.  Not reached: the three
+    // probe_sorted_kernel forms with 64-bit probe offsets outside the diagnostic build — they need a probe layout of 4 GB, 268 M entries.
+    auto forms = [&](const char *kernel) { int n = 0; for (const std::string &k : g_launched) n += strstr(k.c_str(), kernel) != nullptr; return n; };
+    const struct { const char *kernel; int forms; } want[] = {
+        {"thr2_kernel", 1}, {"small_order_kernel", 1}, {"query_prefix_kernel", 1}, {"home_keys_kernel", 2}, {"group_heads_kernel", 2}, {"group_first_kernel", 1},
+        {"pass_slots_kernel", 1}, {"group_resolve_kernel", 1}, {"plan_passes_kernel", 4}, {"probe_sorted_kernel", 5}, {"resolve_undecided_kernel", 1},
+        {"filter_records_kernel", 2}, {"filter_compact_kernel", 2}, {"prior_rows_kernel", 1}, {"votes_topk_kernel", 1}, {"votes_query_kernel", 1}, {"votes_kernel", 2},
+        {"topk_kernel", 2 /* votes_topk_kernel too */}, {"export_candidates_kernel", 1}, {"cand_prefix_kernel", 1}, {"cand_prefix_masked_kernel", 1}, {"query_base_kernel", 1},
+        {"pairs_query_kernel", 2}, {"block_count_kernel", 4}, {"block_scan_kernel", 1}, {"block_write_kernel", 2}, {"batch_totals_kernel", 1}, {"loop_bound_kernel", 1},
+        {"rough_gather_kernel", 1}};
+    for (const auto &w : want)
+      if (forms(w.kernel) != w.forms) { fprintf(stderr, "engine_driver: %d forms of %s launched, not %d\n", forms(w.kernel), w.kernel, w.forms); exit(1); }
+  }
+};
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -999,6 +1334,9 @@ int main(int argc, char **argv) {
 
   // ---- the stages on a verified batch, on one device and on two "devices" behind one handle
   for (int n_dev : {1, 2}) { Stages st; st.run(S, cfg, rng, n_dev); }
+
+  // ---- the forms of the query pipeline, launch by launch
+  { SelectForms sf{S, rng, cfg}; sf.run(); }
   g_last = nullptr;
   if (g_transcript) fclose(g_transcript);
   REQUIRE(sgtd_stub_device_blocks() == 0 && sgtd_stub_device_bytes() == 0);       // every device buffer was freed

@@ -9,6 +9,10 @@
 //                     scenario can leave behind what a kernel would have (overflow flags, counts) and drive the host
 //                     through its growth and re-run paths
 //   streams, events = everything is synchronous and complete
+//   trace           = while a scenario has it on (sgtd_stub_set_trace), one line per kernel launch (name as registered, grid, block,
+//                     dynamic LDS), per hipMemsetAsync (value, bytes, the room of the block it starts), per hipFuncSetAttribute
+//                     (kernel, value) and per hipEventRecord (the event's number in creation order) — no addresses: two builds
+//                     of the engine whose traces are equal enqueue the same work
 // Test infrastructure only: nothing in the product links it.
 #include <hip/hip_runtime_api.h>
 
@@ -30,7 +34,7 @@ std::map<void *, size_t> &host_blocks() { static std::map<void *, size_t> b; ret
 #define g_mu mu()
 #define g_kernels kernels()
 #define g_blocks blocks()
-size_t g_allocated = 0, g_peak = 0;
+size_t g_allocated = 0, g_peak = 0, g_peak_part = 0;
 unsigned long long g_launches = 0, g_copies = 0, g_waits = 0;
 unsigned g_grid_x = 0;
 typedef void (*launch_hook_t)(const char *name, void **args, void *user);
@@ -38,7 +42,9 @@ launch_hook_t g_hook = nullptr;
 void *g_hook_user = nullptr;
 struct CallCfg { dim3 grid, block; size_t shmem; hipStream_t stream; };
 thread_local CallCfg t_cfg;
-struct Event { double t; };
+struct Event { double t; int id; };
+int g_events = 0;
+FILE *g_trace = nullptr;
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 constexpr size_t kTotalMem = 6ull << 30, kReserve = 2ull << 30;     // small on purpose: the engine sizes work buffers by what is free
 }  // namespace
@@ -46,12 +52,14 @@ constexpr size_t kTotalMem = 6ull << 30, kReserve = 2ull << 30;     // small on 
 extern "C" {
 // ---- the test's side
 void sgtd_stub_set_launch_hook(launch_hook_t h, void *user) { g_hook = h; g_hook_user = user; }
+void sgtd_stub_set_trace(FILE *f) { g_trace = f; }               // (nullptr: off; the hook may add a line of its own behind a launch's)
 unsigned long long sgtd_stub_launches() { return g_launches; }
 unsigned long long sgtd_stub_copies() { return g_copies; }      // hipMemcpy, hipMemcpyAsync and hipMemsetAsync calls
 unsigned long long sgtd_stub_waits() { return g_waits; }        // stream, event and device waits
 unsigned sgtd_stub_grid_x() { return g_grid_x; }                // of the launch whose hook is running
 size_t sgtd_stub_device_bytes() { return g_allocated; }
 size_t sgtd_stub_device_peak() { return g_peak; }
+size_t sgtd_stub_device_peak_restart() { const size_t p = g_peak_part; g_peak_part = g_allocated; return p; }      // the peak since the last call of this
 size_t sgtd_stub_device_blocks() { return g_blocks.size(); }
 size_t sgtd_stub_block_size(const void *p) {           // bytes of the allocation that starts at p (0: not one)
   std::lock_guard<std::mutex> l(g_mu);
@@ -91,6 +99,7 @@ hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, s
     fprintf(stderr, "hip_stub: invalid launch of %s: grid %u %u %u block %u %u %u shmem %zu\n", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
     return hipErrorInvalidConfiguration;
   }
+  if (g_trace) fprintf(g_trace, "launch %s grid %u %u %u block %u %u %u lds %zu\n", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
   if (g_hook) g_hook(name.c_str(), args, g_hook_user);
   return hipSuccess;
 }
@@ -115,7 +124,14 @@ hipError_t hipMemGetInfo(size_t *free_b, size_t *total_b) {
 hipError_t hipGetLastError() { return hipSuccess; }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "stub error"; }
 hipError_t hipFuncGetAttributes(hipFuncAttributes *a, const void *) { memset(a, 0, sizeof(*a)); a->sharedSizeBytes = 12928; a->maxThreadsPerBlock = 1024; return hipSuccess; }
-hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int value) { return value <= 160 * 1024 ? hipSuccess : hipErrorInvalidValue; }
+hipError_t hipFuncSetAttribute(const void *fn, hipFuncAttribute, int value) {
+  if (g_trace) {
+    std::lock_guard<std::mutex> l(g_mu);
+    auto it = g_kernels.find(fn);
+    fprintf(g_trace, "attribute %s %d\n", it == g_kernels.end() ? "?" : it->second.c_str(), value);
+  }
+  return value <= 160 * 1024 ? hipSuccess : hipErrorInvalidValue;
+}
 
 // ---- memory
 hipError_t hipMalloc(void **p, size_t n) {
@@ -123,7 +139,7 @@ hipError_t hipMalloc(void **p, size_t n) {
   void *q = calloc(n ? n : 1, 1);
   if (!q) { *p = nullptr; return hipErrorOutOfMemory; }
   std::lock_guard<std::mutex> l(g_mu);
-  g_blocks[q] = n; g_allocated += n; g_peak = g_allocated > g_peak ? g_allocated : g_peak;
+  g_blocks[q] = n; g_allocated += n; g_peak = g_allocated > g_peak ? g_allocated : g_peak; g_peak_part = g_allocated > g_peak_part ? g_allocated : g_peak_part;
   *p = q;
   return hipSuccess;
 }
@@ -160,7 +176,10 @@ hipError_t hipHostFree(void *p) {
 }
 hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { g_copies++; if (n) memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { g_copies++; if (n) memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { g_copies++; if (n) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) {
+  if (g_trace) fprintf(g_trace, "memset %d bytes %zu room %zu\n", v, n, sgtd_stub_block_size(d));
+  g_copies++; if (n) memset(d, v, n); return hipSuccess;
+}
 
 // (what the engine asks before it lets a kernel write a caller's array: page-locked blocks are device-visible at their own address)
 hipError_t hipPointerGetAttributes(hipPointerAttribute_t *a, const void *p) {
@@ -192,10 +211,13 @@ hipError_t hipMemGetAddressRange(hipDeviceptr_t *base, size_t *size, hipDevicept
 // ---- streams and events
 hipError_t hipStreamSynchronize(hipStream_t) { g_waits++; return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { g_waits++; return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new Event{0}); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new Event{0, g_events++}); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete reinterpret_cast<Event *>(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { reinterpret_cast<Event *>(e)->t = now_ms(); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
+  if (g_trace) fprintf(g_trace, "event %d\n", reinterpret_cast<Event *>(e)->id);
+  reinterpret_cast<Event *>(e)->t = now_ms(); return hipSuccess;
+}
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(reinterpret_cast<Event *>(b)->t - reinterpret_cast<Event *>(a)->t); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { g_waits++; return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }

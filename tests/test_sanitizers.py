@@ -81,7 +81,17 @@ def test_engine_host_code_under_asan_and_ubsan(tmp_path):
     getters, the state errors, and the frame-ordered dispatch at 4100 and 4050 (query, candidate) slots.  The launch hook
     checks the room of every array a stage's kernel is handed.  With a file name as its third argument the driver writes
     one line per call (status, error text, launch / copy / wait counts, a hash of the outputs): two builds of the engine
-    whose transcripts are equal behave alike."""
+    whose transcripts are equal behave alike.
+
+    Then the forms of the query pipeline (plan_select and the stages of launch_select, the list pass run again, deferred
+    lists, the diagnostic re-run) with the stand-in's trace on: fresh handles in the three select modes and with 8-byte
+    compact words, spans on both sides of every threshold the choice of forms compares against, one-query batches in
+    both orderings, 8 / 255 / 256 queries, every per-batch knob, a 40-bit home key, 64 candidates and ranks of 17, 18 and
+    20 bits, a tail segment, a loop batch, stamps inside and outside the table's frames, filters and priors, timing, a
+    candidate-export buffer, both overflows in each list form.  Every launch (name, grid, block, dynamic LDS, the scalars
+    the hook can type), memset, attribute and event record is a transcript line; the driver checks from the trace that
+    every kernel form these functions can launch was launched (all but the three sweeps with 64-bit probe offsets, which
+    need a 4-GB probe layout) and that the scenario's device peak stays under 2 GB."""
     san = ASAN + ["-fno-omit-frame-pointer"]
     hip = [HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-host-only", "-Wno-unused-function", "-Wno-unused-result"] + san
     objs = {n: str(tmp_path / (n + ".o")) for n in ("accel", "driver", "stub", "fatbin")}
