@@ -359,8 +359,10 @@ __global__ __launch_bounds__(256) void group_resolve_kernel(TableView T, QueryVi
 //                         with a fourth column whose gate fails everywhere)
 //     w1 = total          entries in the visit list
 //     then KM words each (pass_hdr_word): descriptor slots d; the descriptors' frames as the entry ids name
-//     them (frame - frame_lo, 0xFFFFFFFF for a frame the table does not hold); q0, q1, q2 (f32); lo2, hi2
-//     (f32_bounds)
+//     them (frame - frame_lo, 0xFFFFFFFF for a frame the table does not hold); q0, q1, q2 (f32); then what the
+//     sweep would otherwise derive per pass in all 64 lanes from lo2 and hi2 (f32_bounds): ngap in the field's
+//     word 0 (its other KM - 1 words are free) — minus the largest hi2 - lo2 of the columns, rounded away from
+//     zero, the wave-uniform "certainly inside" bound of the sums that run to d2 - hi2; and -hi2 per column
 //   ranges, 12 B each, n + 1 of them (lane j of the sweep loads range j):
 //     offc   exclusive offset of range j in the visit list
 //     dlc    start - offc (entry index of list position p in range j = p + dlc)
@@ -388,7 +390,7 @@ __global__ __launch_bounds__(256) void group_resolve_kernel(TableView T, QueryVi
 #define SGTD_PASS_HDR_WORDS (SGTD_PASS_KMAX == 4 ? 32 : 16)
 #define SGTD_PASS_HDR_UNITS (SGTD_PASS_HDR_WORDS / 4)          // the header in 16-B units
 #define SGTD_META_SENTINEL (((1u << SGTD_PASS_KMAX) - 1u) << 8)   // every gate fails
-enum { PH_SLOT = 0, PH_FRAME, PH_Q0, PH_Q1, PH_Q2, PH_LO2, PH_HI2 };
+enum { PH_SLOT = 0, PH_FRAME, PH_Q0, PH_Q1, PH_Q2, PH_NGAP, PH_NHI2 };
 __host__ __device__ constexpr int pass_hdr_word(int field, int k) { return 2 + field * SGTD_PASS_KMAX + k; }
 #define SGTD_PASS_SLACK_UNITS 64       // behind the pool: the sweep's 64 lanes load 12 B each whatever n is
 
@@ -897,7 +899,17 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
         for (int k = 0; k < KM; k++) {
           hw[pass_hdr_word(PH_SLOT, k)] = d[k]; hw[pass_hdr_word(PH_FRAME, k)] = qfr[k];
           hw[pass_hdr_word(PH_Q0, k)] = hq[k][0]; hw[pass_hdr_word(PH_Q1, k)] = hq[k][1]; hw[pass_hdr_word(PH_Q2, k)] = hq[k][2];
-          hw[pass_hdr_word(PH_LO2, k)] = hq[k][3]; hw[pass_hdr_word(PH_HI2, k)] = hq[k][4];
+          hw[pass_hdr_word(PH_NHI2, k)] = hq[k][4] ^ 0x80000000u;
+        }
+        {
+          // -(largest hi2 - lo2 of the columns), rounded away from zero (columns beyond K: 0 - 0, which changes nothing)
+          float ngap = 0.0f;
+#pragma unroll
+          for (int k = 0; k < KM; k++) {
+            const float gk = __uint_as_float(hq[k][4]) - __uint_as_float(hq[k][3]);
+            ngap = !(gk <= ngap) ? gk : ngap;           // (max that keeps a NaN: then nothing is certainly inside)
+          }
+          hw[pass_hdr_word(PH_NGAP, 0)] = __float_as_uint(-(ngap * 1.0001f + 1e-30f));
         }
         uint4 *h = P.pool + off;
 #pragma unroll
@@ -996,18 +1008,10 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
 #pragma unroll
   for (int k = 0; k < K; k++) {
     penc[k] = __uint_as_float((pv.meta >> (8 + k)) & 1u ? 0x7F800000u : 0u);
-    if constexpr (!DIAG) penc[k] = penc[k] - __uint_as_float(pv.word(PH_HI2, k));      // (+inf stays +inf; hi2 is finite)
+    if constexpr (!DIAG) penc[k] = penc[k] + __uint_as_float(pv.word(PH_NHI2, k));      // (+inf stays +inf; hi2 is finite)
   }
-  float ngap = 0.0f;      // -(largest hi2 - lo2 of the pass's columns), rounded away from zero
-  if constexpr (!DIAG) {
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-      const float g = __uint_as_float(pv.word(PH_HI2, k)) - __uint_as_float(pv.word(PH_LO2, k));
-      ngap = !(g <= ngap) ? g : ngap;           // (max that keeps a NaN: then nothing is certainly inside)
-    }
-    ngap = -(ngap * 1.0001f + 1e-30f);
-  }
-  const u32 ngapv = in_vgpr_f(ngap);
+  // -(largest hi2 - lo2 of the pass's columns), rounded away from zero: from the header (plan_passes_kernel)
+  const u32 ngapv = DIAG ? 0u : in_vgpr(pv.word(PH_NGAP, 0));
   const u32 cellc = pv.meta & 0xFFu;
   // narrow layout: the address delta in bytes, so that an entry's byte offset is ONE three-operand add
   const u32 dlc_sel = WIDE ? pv.dlc : pv.dlc << 4;
@@ -1020,7 +1024,8 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
   // does outgrow what its slab has left is moved to a fresh slab (relocate below, rare).
   bool fits = true;
   bool tight = false;   // some column's room is below the worst case: the groups check it
-  u32 next0[K];         // granule of the first record of the column's list
+  u32 next0[K];         // granule of the first record of the column's list (through the pass also lane k of slab.state: the
+                        // epilogue and make_room read it there, so that no scalar register holds it across the loop)
 #pragma unroll
   for (int k = 0; k < K; k++) next0[k] = 0;
   const u32 want = DIAG ? total : min(total, (total >> 8) * B.rec_rate + (((total & 255u) * B.rec_rate) >> 8) + 256u);
@@ -1035,20 +1040,42 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
     if (got + take <= (u64)B.rec_cap) { nxt = (u32)got; end = (u32)got + take; }
     else { nxt = 0; end = 0; }
   };
+  // The common case — every column's slab has room for what its list is expected to need — is decided for all columns
+  // at once where the cursors lie: lane 8 + k fetches column k's next granule (lane k) and its slab's end (lane 4 + k),
+  // compares as the per-column code below does and puts the room into its own word of the state; one ballot says
+  // whether any column needs a slab, a second whether any is tight.  Only then do the columns take their turns.
+  bool need_slab;
+  {
+    // (the lane as a value of this pass: derived from the kernel's lane id, the permute addresses would each be kept in a
+    // vector register through the whole kernel)
+    u32 col = (u32)lane;
+    asm volatile("" : "+v"(col));
+    col -= 8u;
+    const bool mine = col < pv.k_real;
+    const u32 nxt_v = (u32)__builtin_amdgcn_ds_bpermute((int)(col << 2), (int)slab.state);
+    const u32 end_v = (u32)__builtin_amdgcn_ds_bpermute((int)((col + 4u) << 2), (int)slab.state);
+    need_slab = __builtin_amdgcn_ballot_w64(mine && (u64)nxt_v + want_g > (u64)end_v) != 0ull;
+    const u32 room_v = room_of(nxt_v, end_v);      // (where a column does take a slab, its turn below writes the room again)
+    tight = !need_slab && __builtin_amdgcn_ballot_w64(mine && room_v < total) != 0ull;     // (else: column by column, from the slabs they end up with)
+    slab.state = mine ? room_v : slab.state;
+  }
   static_for<K>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     if ((u32)k >= pv.k_real) return;      // (the fourth column of a pass of three has no list)
-    u32 nxt = (u32)__builtin_amdgcn_readlane((int)slab.state, k), end = (u32)__builtin_amdgcn_readlane((int)slab.state, 4 + k);
-    if (total && (u64)nxt + want_g > (u64)end) {
-      // only the matches stay in a slab: slabs of 8 expected lists keep the space abandoned at a
-      // slab's end to about an eighth however long the visit lists are
-      new_slab(want_g > (1u << 28) ? want_g : max(B.rec_slab, 8u * want_g), nxt, end);
-      slab.state = write_lane<k>(slab.state, nxt);
-      slab.state = write_lane<4 + k>(slab.state, end);
+    u32 nxt = (u32)__builtin_amdgcn_readlane((int)slab.state, k);
+    if (need_slab) {
+      u32 end = (u32)__builtin_amdgcn_readlane((int)slab.state, 4 + k);
+      if (total && (u64)nxt + want_g > (u64)end) {
+        // only the matches stay in a slab: slabs of 8 expected lists keep the space abandoned at a
+        // slab's end to about an eighth however long the visit lists are
+        new_slab(want_g > (1u << 28) ? want_g : max(B.rec_slab, 8u * want_g), nxt, end);
+        slab.state = write_lane<k>(slab.state, nxt);
+        slab.state = write_lane<4 + k>(slab.state, end);
+      }
+      fits = fits && ((u64)nxt + want_g <= (u64)end);
+      tight = tight || (room_of(nxt, end) < total);
+      slab.state = write_lane<8 + k>(slab.state, room_of(nxt, end));
     }
-    fits = fits && ((u64)nxt + want_g <= (u64)end);
-    tight = tight || (room_of(nxt, end) < total);
-    slab.state = write_lane<8 + k>(slab.state, room_of(nxt, end));
     next0[k] = nxt;
   });
   if (!fits && lane == 0) B.overflow()[0] = 1;
@@ -1073,7 +1100,7 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
   u32 qfv[K];
 #pragma unroll
   for (int k = 0; k < K; k++) qfv[k] = (FRAMES || DIAG) ? in_vgpr(pv.word(PH_FRAME, k)) : 0u;
-  const float nhi0 = -__uint_as_float(pv.word(PH_HI2, 0));      // (one column: the sum starts from it)
+  const float nhi0 = __uint_as_float(pv.word(PH_NHI2, 0));      // (one column: the sum starts from it)
   f32x2 qx[KP], qy[KP], qz[KP];
   if constexpr (K >= 2) {
 #pragma unroll
@@ -1272,11 +1299,12 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
           u32 nxt, end;
           new_slab(max(B.rec_slab, need_g > (1u << 28) ? need_g : 4u * need_g), nxt, end);
           if (end - nxt < need_g) { fits = false; if (lane == 0) B.overflow()[0] = 1; return; }
-          u32 *from = B.rec_at(next0[k]), *to = B.rec_at(nxt);
+          u32 *from = B.rec_at((u32)__builtin_amdgcn_readlane((int)slab.state, k)), *to = B.rec_at(nxt);
           __builtin_amdgcn_s_waitcnt(0x0F70);   // the list's records so far are in L2 ...
           for (u32 i = (u32)lane; i < matches[k]; i += SGTD_WAVE)
             to[i] = __hip_atomic_load(from + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... and are read from there
           next0[k] = nxt;
+          slab.state = write_lane<k>(slab.state, nxt);
           list_base[k] = reinterpret_cast<char *>(to);
           if (lane == 0) atomicAdd(B.list_moves(), 1u);
           room = room_of(nxt, end);
@@ -1317,25 +1345,31 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
   } else {
     pending.touch();
   }
-  // the pass's results: lane k stores for descriptor k
+  // the pass's results: lane k stores for descriptor k — its list's first granule is its own word of the state
   {
-    u32 r_slot = pv.hv, r_ptr = next0[0], r_match = matches[0];
+    u32 r_slot = pv.hv, r_match = matches[0];
     // (lane k's own header word is not the slot: fetch the K slot words by lane)
     r_slot = (u32)__builtin_amdgcn_ds_bpermute((pass_hdr_word(PH_SLOT, 0) + min(lane, K - 1)) << 2, (int)pv.hv);
 #pragma unroll
     for (int k = 1; k < K; k++)
-      if (lane == k) { r_ptr = next0[k]; r_match = matches[k]; }
+      if (lane == k) r_match = matches[k];
+    const bool mine = (u32)lane < pv.k_real;
 #ifdef SGTD_EXP_NOSTORE
-    r_match = 0;      // (experiment build: no record was stored — the lists stay empty for the kernels behind)
+    // (experiment build: no record was stored — the lists stay empty for the kernels behind)
+    if (mine) B.list[r_slot] = make_uint2(slab.state, 0u);
+#else
+    if (mine) B.list[r_slot] = make_uint2(slab.state, fits ? r_match : 0u);
 #endif
-    if ((u32)lane < pv.k_real) B.list[r_slot] = make_uint2(r_ptr, fits ? r_match : 0u);
+    // the streams go on behind the lists
+    if (fits) {
+      if (mine) slab.state += granules(r_match);
+    } else {
+      static_for<K>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        if ((u32)k < pv.k_real && lane == 0) atomicAdd(B.rec_need(), (unsigned long long)matches[k]);
+      });
+    }
   }
-  static_for<K>([&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    if ((u32)k >= pv.k_real) return;
-    if (!fits && lane == 0) atomicAdd(B.rec_need(), (unsigned long long)matches[k]);
-    if (fits) slab.state = write_lane<k>(slab.state, next0[k] + granules(matches[k]));
-  });
   __builtin_amdgcn_wave_barrier();
   PH_ADD(4);
 }
