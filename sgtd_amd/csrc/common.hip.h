@@ -2,6 +2,13 @@
 // wave = 64 lanes everywhere (CDNA4); compiled with -ffp-contract=off so that
 // every f32/f64 multiply-add below is two individually rounded operations,
 // exactly like the reference binary (built -O3 without -march, no FMA).
+//
+// Instrument builds.  Three -D switches add clocks or counters to the product's code; the results stay the product's:
+//   SGTD_EXP_FRAME_LAPS  host time of sgtd_search_frame and of the frame build by part, one line per call to stderr
+//   SGTD_EXP_VSTAT       VSTAT / VMSTAT: counters of the verification kernels' steps, tests and votes, printed after every verification
+//   SGTD_EXP_PHASE       PH_ADD: the sweep's and the frame build's wave clocks by phase, printed once as fractions of wave life
+// Nothing else of the kind belongs in these headers: a build that changes what is computed in order to time a part of
+// it is measured on a branch, its numbers go to DESIGN.md and profiles/, and the code stays in git's history.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

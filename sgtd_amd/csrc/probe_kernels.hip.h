@@ -82,6 +82,10 @@ struct QueryView {
 // exactly where large batches pay (2048 query frames on a 100 000-frame map: 1.5e10).  The list passes read records four
 // at a time anyway (a quad is a granule: aligned 16-byte loads), and a list wastes at most three records at its end.
 #define SGTD_REC_SHIFT 2
+// the words of ProbeBuffers::ctr, the batch's counter block (described there): device and host name them here and nowhere by number.
+// The first CTR_COUNT words are what the host copies back after a batch and what the frame pack carries (verify_kernels.hip.h).
+enum { CTR_REC_CURSOR = 0, CTR_AMB_COUNT = 2, CTR_COMPACT_CURSOR = 3, CTR_REC_NEED = 4, CTR_SWEPT = 6, CTR_POOL_CURSOR = 8, CTR_LIST_MOVES = 9,
+       CTR_OVERFLOW = 10, CTR_COUNT = 12, CTR_XCD_HEADS = 1024 };
 struct ProbeBuffers {
   u32 *rec;             // [4 rec_cap] match records: the entry's id (frame and entry in one word, common.hip.h IdMap)
   unsigned char *rec_cell;  // [4 rec_cap] voxel_round index (diagnostic build only)
@@ -101,15 +105,15 @@ struct ProbeBuffers {
   // slab, 10-11 the overflow flags (0: match records / pass pool / undecided queue, 1: candidate pairs), from word 1024 the
   // sweep's eight ticket-queue heads, 1024 words (4 KB: own L2 channel) apart
   u32 *ctr;
-  __host__ __device__ __forceinline__ unsigned long long *rec_cursor() const { return reinterpret_cast<unsigned long long *>(ctr); }
-  __host__ __device__ __forceinline__ u32 *amb_count() const { return ctr + 2; }
-  __host__ __device__ __forceinline__ u32 *compact_cursor() const { return ctr + 3; }
-  __host__ __device__ __forceinline__ unsigned long long *rec_need() const { return reinterpret_cast<unsigned long long *>(ctr + 4); }
-  __host__ __device__ __forceinline__ unsigned long long *swept() const { return reinterpret_cast<unsigned long long *>(ctr + 6); }
-  __host__ __device__ __forceinline__ u32 *pool_cursor() const { return ctr + 8; }
-  __host__ __device__ __forceinline__ u32 *list_moves() const { return ctr + 9; }
-  __host__ __device__ __forceinline__ int *overflow() const { return reinterpret_cast<int *>(ctr + 10); }
-  __host__ __device__ __forceinline__ u32 *xcd_heads() const { return ctr + 1024; }
+  __host__ __device__ __forceinline__ unsigned long long *rec_cursor() const { return reinterpret_cast<unsigned long long *>(ctr + CTR_REC_CURSOR); }
+  __host__ __device__ __forceinline__ u32 *amb_count() const { return ctr + CTR_AMB_COUNT; }
+  __host__ __device__ __forceinline__ u32 *compact_cursor() const { return ctr + CTR_COMPACT_CURSOR; }
+  __host__ __device__ __forceinline__ unsigned long long *rec_need() const { return reinterpret_cast<unsigned long long *>(ctr + CTR_REC_NEED); }
+  __host__ __device__ __forceinline__ unsigned long long *swept() const { return reinterpret_cast<unsigned long long *>(ctr + CTR_SWEPT); }
+  __host__ __device__ __forceinline__ u32 *pool_cursor() const { return ctr + CTR_POOL_CURSOR; }
+  __host__ __device__ __forceinline__ u32 *list_moves() const { return ctr + CTR_LIST_MOVES; }
+  __host__ __device__ __forceinline__ int *overflow() const { return reinterpret_cast<int *>(ctr + CTR_OVERFLOW); }
+  __host__ __device__ __forceinline__ u32 *xcd_heads() const { return ctr + CTR_XCD_HEADS; }
   // per descriptor slot d:
   uint2 *list;          // {granule of the first record of the descriptor's list, its matches}
   u32 *n_visit;         // entries the reference's loop visits for the descriptor (STDesc.cpp:372)
@@ -590,12 +594,6 @@ __device__ __forceinline__ void reached_slices(float dq, float t_up, int n, int 
 #ifndef SGTD_PLAN_WAVES
 #define SGTD_PLAN_WAVES __attribute__((amdgpu_waves_per_eu(5)))
 #endif
-#ifndef SGTD_EXP_PLAN_STAGE
-// Experiment builds (never shipped): the planner stops behind stage 1 .. 5 (slot -> positions and descriptors -> the
-// group's masks -> the descriptors' records and reach -> room) or, 6, does everything but the walk; with the product
-// build, the differences are what each stage costs.
-#define SGTD_EXP_PLAN_STAGE 0
-#endif
 #ifndef SGTD_PLAN_INFLIGHT
 #define SGTD_PLAN_INFLIGHT 4u   // sets whose rows are in flight together in the staging copy
 #endif
@@ -634,11 +632,6 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
   for (u32 s_wg = blockIdx.x * blockDim.x; s_wg < n_pass; s_wg += gridDim.x * blockDim.x) {
   const u32 s = s_wg + threadIdx.x;
   const u32 p = (s < n_pass && !no_rows) ? pos_of_slot[s] : SGTD_NO_PASS;
-#if SGTD_EXP_PLAN_STAGE == 1
-  if (p == 0x12345678u) overflow[1] = 1;
-  if (s < n_pass) P.rec_off[s] = SGTD_NO_PASS;
-  continue;
-#endif
   constexpr int KM = SGTD_PASS_KMAX;
   int K = 0;
   u32 g = 0, d[KM];
@@ -659,9 +652,9 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
     for (int k = 0; k < KM; k++) d[k] = order[p + (k < K ? k : 0)];
     // a home cell none of whose 27 buckets exists in the table: nothing to plan or sweep — before
     // anything of the descriptors is read
-    u32 any = SGTD_EXP_PLAN_STAGE == 2 ? 1u : 0u;
+    u32 any = 0u;
 #pragma unroll
-    for (u32 sg = 0; sg < (SGTD_EXP_PLAN_STAGE == 2 ? 0u : SEGS); sg++) {
+    for (u32 sg = 0; sg < SEGS; sg++) {
       const uint2 m = *reinterpret_cast<const uint2 *>(rows + (size_t)g * ROWB + (size_t)sg * SGTD_GROUP_ROW_BYTES);
       ex_g[sg] = m.x; ov_g[sg] = m.y;
       any |= m.x;
@@ -674,11 +667,6 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
     }
   }
   u32 hq[KM][5];   // q0, q1, q2 (f32), lo2, hi2 as words
-#if SGTD_EXP_PLAN_STAGE == 3 || SGTD_EXP_PLAN_STAGE == 2
-  if ((ex_g[0] ^ d[0] ^ d[1] ^ d[2] ^ d[3]) == 0x12345678u) overflow[1] = 1;
-  if (s < n_pass) P.rec_off[s] = SGTD_NO_PASS;
-  continue;
-#endif
   if (!act) K = 0;
   u32 qfr[KM], gate[KM];
   // per descriptor and offset -1, 0, +1: the halves (second side) and thirds (third side) its
@@ -713,11 +701,6 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
   u32 gate_any = 0;
 #pragma unroll
   for (int k = 0; k < KM; k++) gate_any |= gate[k];
-#if SGTD_EXP_PLAN_STAGE == 4
-  { u32 x = gate_any; for (int k = 0; k < KM; k++) x ^= reach[k] ^ hq[k][0] ^ hq[k][4] ^ qfr[k]; if (x == 0x12345678u) overflow[1] = 1; }
-  if (s < n_pass) P.rec_off[s] = SGTD_NO_PASS;
-  continue;
-#endif
   // Room for the records, for all 64 x waves passes of the workgroup at once: an upper bound of a pass's ranges — two
   // per gated cell that has a bucket, one more where the bucket has an overflow slice — from the masks alone, one
   // scan per wave and ONE add to the pool's cursor per workgroup and trip (an address takes 88 M atomic adds per
@@ -756,11 +739,6 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
   __syncthreads();
   const bool room = s_room != 0u;
   const u32 off = s_base[threadIdx.x >> 6] + inc - units;
-#if SGTD_EXP_PLAN_STAGE == 5
-  { u32 x = gate_any ^ off; for (int k = 0; k < KM; k++) x ^= reach[k] ^ hq[k][0] ^ hq[k][4] ^ qfr[k]; if (x == 0x12345678u) overflow[1] = 1; }
-  if (s < n_pass) P.rec_off[s] = SGTD_NO_PASS;
-  continue;
-#endif
   // the wave's groups are consecutive ids (slots grow with the sorted position): first and last active lane
   const u64 act_mask = __builtin_amdgcn_ballot_w64(act);
   if (!act_mask) {
@@ -867,9 +845,6 @@ __global__ __launch_bounds__(SGTD_PLAN_THREADS) SGTD_PLAN_WAVES void plan_passes
       // every lane walks ITS cells — gated by one of its descriptors and holding a bucket in one of the segments, 7 of
       // the 27 on the synthetic maps — in ascending order; the wave runs as many trips as its busiest lane has cells
       u32 todo = gate_any & (ex_g[0] | ex_g[SEGS - 1]);
-#if SGTD_EXP_PLAN_STAGE == 6
-      todo = todo == 0x12345u ? 1u : 0u;
-#endif
 #pragma unroll 1
       while (todo) {
         const int c = __builtin_ctz(todo);
@@ -1083,18 +1058,10 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
 
   u32 matches[K];
   char *list_base[K];   // wave-uniform: the list's first record; record r of the list is at byte 4 r
-#ifdef SGTD_EXP_SHADOW16
-  // experiment (never shipped): a second, 2-byte stream of the records' frames behind the record buffer (the host
-  // allocates half as much again): what the extra store per test costs the sweep
-  char *shadow_base[K];
-#endif
 #pragma unroll
   for (int k = 0; k < K; k++) {
     matches[k] = 0;
     list_base[k] = reinterpret_cast<char *>(B.rec_at(next0[k]));
-#ifdef SGTD_EXP_SHADOW16
-    shadow_base[k] = reinterpret_cast<char *>(B.rec_at(B.rec_cap)) + 64 + ((size_t)next0[k] << (SGTD_REC_SHIFT + 1));
-#endif
   }
   // wave-uniform constants of the columns in vector registers
   u32 qfv[K];
@@ -1155,9 +1122,6 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
       // entry = position + the range's delta; beyond the list: the sentinel entries
       const float4 *pa = WIDE ? reinterpret_cast<const float4 *>(T.ent + (w_lo + lane + dsel))
                               : reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(T.ent) + (dsel + lane16 + (w_lo << 4)));
-#ifdef SGTD_EXP_L1
-      pa = reinterpret_cast<const float4 *>(T.ent) + lane;     // experiment: every load hits the same L1-resident KB
-#endif
       v[u] = *pa;
     }
     PH_ADD(1);
@@ -1218,13 +1182,7 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
       const u32 at = count + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
       if constexpr (!PUSH) {
         // wave-uniform base (the list) + a 32-bit lane offset: no 64-bit VALU address math
-#ifdef SGTD_EXP_NOSTORE
-        if (at == 0xFFFFFFF0u)
-#endif
         if (hit && fits) *reinterpret_cast<u32 *>(list_base[k] + (at << 2)) = id;
-#ifdef SGTD_EXP_SHADOW16
-        if (hit && fits) *reinterpret_cast<unsigned short *>(shadow_base[k] + (at << 1)) = (unsigned short)(id >> id_bits);
-#endif
         if constexpr (DIAG) {
           if (hit && fits) { B.rec_cell[B.rec_index(next0[k]) + at] = (unsigned char)cellv[u]; B.rec_dis[B.rec_index(next0[k]) + at] = dis; }
         }
@@ -1250,9 +1208,6 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
 #pragma unroll
       for (int k = 0; k < K; k++) test(std::false_type{}, u, k, DIAG ? 0.0f : d2[k], matches[k]);
     }
-#ifdef SGTD_EXP_NOSTORE
-    amb_any = 0;      // (experiment build: nothing was stored, nothing to decide again)
-#endif
     if (!DIAG && amb_any) {   // rare: about one in 10^4 matches
       u32 back[K];
 #pragma unroll
@@ -1354,12 +1309,7 @@ __device__ __forceinline__ void sweep_pass(const TableView &T, const ProbeBuffer
     for (int k = 1; k < K; k++)
       if (lane == k) r_match = matches[k];
     const bool mine = (u32)lane < pv.k_real;
-#ifdef SGTD_EXP_NOSTORE
-    // (experiment build: no record was stored — the lists stay empty for the kernels behind)
-    if (mine) B.list[r_slot] = make_uint2(slab.state, 0u);
-#else
     if (mine) B.list[r_slot] = make_uint2(slab.state, fits ? r_match : 0u);
-#endif
     // the streams go on behind the lists
     if (fits) {
       if (mine) slab.state += granules(r_match);
@@ -1783,14 +1733,7 @@ __device__ __forceinline__ void votes_of_block(const QueryView &Q, const ProbeBu
         u32 dd, addr, k;
         sub_locate_quad(s_pre, s_ptr, s_cnt, r < RQ ? r : 0u, dd, addr, k);
         nk[u] = r < RQ ? k : 0u;
-#ifdef SGTD_EXP_VOTES16
-        // experiment (never shipped): the pass as it would read a 2-byte frame stream — half the bytes per granule at
-        // the same places; the halves of the records it finds there stand in for frames (the counts are wrong, the time is what is asked)
-        const uint2 h = *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(B.rec) + ((size_t)addr << 3));
-        nrec[u] = make_uint4((h.x & 0xFFFFu) << B.id_bits, (h.x >> 16) << B.id_bits, (h.y & 0xFFFFu) << B.id_bits, (h.y >> 16) << B.id_bits);
-#else
         nrec[u] = *reinterpret_cast<const uint4 *>(B.rec_at(addr));      // (a granule: 16-byte aligned)
-#endif
       }
     };
     if (RQ) load2(0);
@@ -2065,8 +2008,8 @@ __global__ __launch_bounds__(256) void block_count_kernel(QueryView Q, ProbeBuff
 // over slots: pair_off[q][k] (relative to the query's first pair), q_pairs[q]
 __device__ __forceinline__ void batch_totals(const u32 *ctr, unsigned long long *tot) {
   tot[0] += 1ull;
-  tot[1] += (ctr[10] | ctr[11]) ? 1ull : 0ull;
-  tot[2] += (unsigned long long)ctr[9];
+  tot[1] += (ctr[CTR_OVERFLOW] | ctr[CTR_OVERFLOW + 1]) ? 1ull : 0ull;
+  tot[2] += (unsigned long long)ctr[CTR_LIST_MOVES];
 }
 // (one query: its base in the pair buffer is 0 and the batch's total is its own — query_base_kernel's work, done here: one launch less)
 __global__ __launch_bounds__(64) void block_scan_kernel(u32 *blk_count, int blocks_per_query, int cand_num,
@@ -2244,13 +2187,6 @@ __global__ __launch_bounds__(256) void block_write_kernel(QueryView Q, ProbeBuff
       const u32 c_own = c_owns[u];
       // rank = lanes below me in my group
       const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(gm >> 32), __builtin_amdgcn_mbcnt_lo((u32)gm, 0u)), count = (u32)__builtin_popcountll(gm);
-#ifdef SGTD_EXP_WRITE_DIRECT
-      // experiment: no staging lines — every pair goes straight to its list (runs of one slot are contiguous)
-      const u32 base = __shfl(running, s);
-      if (valid) pairs[base + rank] = pr[u];
-      running += c_own;
-      (void)count;
-#else
       u32 have = __shfl(fill, s);
       if (__builtin_amdgcn_ballot_w64(valid && have + count > (u32)CAP)) {   // some slot would overflow its line: drain all
         flush();
@@ -2263,7 +2199,6 @@ __global__ __launch_bounds__(256) void block_write_kernel(QueryView Q, ProbeBuff
         else s_stage[wid][s][have + rank] = pr[u];
       }
       if (c_own > (u32)CAP) running += c_own; else fill += c_own;
-#endif
       __builtin_amdgcn_wave_barrier();
     }
   }

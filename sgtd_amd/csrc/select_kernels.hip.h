@@ -365,14 +365,6 @@ __global__ __launch_bounds__(SGTD_PQ_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
       for (int u = 0; u < QW; u++) { rc[u] = nrec[u]; kk[u] = nk[u]; dd[u] = ndd[u]; }
       if (t + 1 < n_tiles) fetch(t + 1);     // in flight while this tile is sorted
-#if defined(SGTD_EXP_PQ) && SGTD_EXP_PQ == 2
-      {   // experiment build (never shipped): the locate and the loads alone — 1.31 ms of the kernel's 2.68
-        u32 x = 0;
-        for (int u = 0; u < QW; u++) x ^= rc[u].x ^ rc[u].y ^ rc[u].z ^ rc[u].w ^ kk[u] ^ dd[u];
-        if (x == 0x12345678u) pairs[0] = x;
-        continue;
-      }
-#endif
       // ---- the wave's candidate records, in stream order (word, lane, record of the quad), as image words
       // in its own region of the image
       u32 nd = 0;      // wave-uniform: dense words so far
@@ -412,10 +404,6 @@ __global__ __launch_bounds__(SGTD_PQ_THREADS) __attribute__((amdgpu_waves_per_eu
         }
         nd += (tot2 & 0xFFFFu) + (tot2 >> 16);
       }
-#if defined(SGTD_EXP_PQ) && SGTD_EXP_PQ == 3
-      if (nd == 0xFFFFFFFFu) pairs[0] = 0;     // experiment build (never shipped): locate, loads and the candidates' dense words alone
-      continue;
-#endif
       __builtin_amdgcn_wave_barrier();
       // ---- dense words back into registers; the wave's region of the image then serves as scratch for the
       // ranking: per batch of eight dense words and slot the lanes of the word that carry the slot (commutative
@@ -463,10 +451,6 @@ __global__ __launch_bounds__(SGTD_PQ_THREADS) __attribute__((amdgpu_waves_per_eu
       }
       s_cnt[wid][lane] = run_s;
       __syncthreads();
-#if defined(SGTD_EXP_PQ) && SGTD_EXP_PQ == 4
-      if (rk[0] == 0xFFFFFFF1u) pairs[0] = 0;     // experiment build (never shipped): everything up to the ranking and the first barrier
-      continue;
-#endif
       // ---- where the wave's records of slot s go in the image: behind the slots before s and the waves before it
       u32 tot = 0, mine_before = 0;
 #pragma unroll
@@ -494,10 +478,6 @@ __global__ __launch_bounds__(SGTD_PQ_THREADS) __attribute__((amdgpu_waves_per_eu
         }
       }
       __syncthreads();
-#if defined(SGTD_EXP_PQ) && SGTD_EXP_PQ == 5
-      out_next += tot;      // experiment build (never shipped): everything but the flush
-      continue;
-#endif
       // ---- the image goes out: position e of slot s's run continues candidate s's list
       for (u32 c = (u32)wid; c * SGTD_WAVE < n_img; c += NW) {      // (wave-uniform: the permutes read lanes 0..63)
         const u32 e = c * SGTD_WAVE + lane;
@@ -508,9 +488,6 @@ __global__ __launch_bounds__(SGTD_PQ_THREADS) __attribute__((amdgpu_waves_per_eu
         u32 g = (u32)__builtin_amdgcn_ds_bpermute((int)s4, (int)first_of_slot) + (wv & ((1u << SGTD_PQ_RANK_BITS) - 1u));
         if (ok) {
           if (map.by_frame) g = map.by_frame[g];
-#if defined(SGTD_EXP_PQ) && SGTD_EXP_PQ == 1
-          if (g == 0xFFFFFFF3u)      // experiment build (never shipped): no stores — 2.47 ms of 2.68
-#endif
           pairs[o + e] = ((u64)(sb0 + ((wv >> SGTD_PQ_RANK_BITS) & (SGTD_PQ_DESCS - 1u))) << 32) | (u64)g;
         }
       }

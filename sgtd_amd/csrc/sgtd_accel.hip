@@ -112,7 +112,7 @@ struct PinnedVec {
   size_t size() const { return n; }
 };
 
-constexpr size_t kCtrWords = 1024 + 8 * 1024;   // ProbeBuffers::ctr: counters + the sweep's ticket-queue heads
+constexpr size_t kCtrWords = CTR_XCD_HEADS + 8 * 1024;   // ProbeBuffers::ctr: counters + the sweep's ticket-queue heads
 enum { EV_START = 0, EV_BUILD, EV_SORT, EV_PROBE, EV_VOTES, EV_TOPK, EV_COUNT_T, EV_SCAN, EV_WRITE, EV_COUNT };
 
 // Every decision of a batch's query pipeline, made once when the batch is enqueued (plan_select) and kept in the handle:
@@ -963,11 +963,7 @@ int do_finalize(sgtd_engine *e, bool force_merge = false) {
 // the query pipeline on descriptors already in e->qd (strided)
 // ---------------------------------------------------------------------------
 int rec_alloc(sgtd_engine *e, bool compact_lists) {
-#ifdef SGTD_EXP_SHADOW16
-  CHK(ensure(e, e->rec, (e->rec_cap + 16) * sizeof(u32) * 3 / 2 + 256));     // (experiment build: the 2-byte shadow stream behind the records)
-#else
   CHK(ensure(e, e->rec, (e->rec_cap + 16) * sizeof(u32)));     // + a few quads: the list passes read four records at the last list's tail
-#endif
   // (the compact candidate lists between block_count and block_write: every block reserves room for all of its records —
   // twice the record buffer; the per-query list pass needs none)
   if (compact_lists) CHK(ensure(e, e->c_pair, std::min(e->rec_cap, kIndexLimit) * sizeof(u64)));
@@ -1700,7 +1696,7 @@ int sync_batch(sgtd_engine *e) {
     unsigned long long cursor = 0, need = 0;
     swept = 0;
     u32 total = 0, pool_used = 0;
-    u32 ctr[12];     // ProbeBuffers::ctr, one copy
+    u32 ctr[CTR_COUNT];     // ProbeBuffers::ctr, one copy
     u32 n_groups = 0;
     unsigned long long tot[3] = {0, 0, 0};
     // (deferred lists that nobody finished, or a re-run that changed the candidates: the lists of all of them)
@@ -1710,10 +1706,10 @@ int sync_batch(sgtd_engine *e) {
     if (e->n_groups.p) CHK(d2h(e, &n_groups, e->n_groups.p, sizeof(u32)));
     CHK(d2h(e, &total, e->q_pair_base.as<u32>() + e->nq, sizeof(u32)));
     CHK(xfer_sync(e));
-    std::memcpy(&cursor, ctr, 8); std::memcpy(&need, ctr + 4, 8); std::memcpy(&swept, ctr + 6, 8);
+    std::memcpy(&cursor, ctr + CTR_REC_CURSOR, 8); std::memcpy(&need, ctr + CTR_REC_NEED, 8); std::memcpy(&swept, ctr + CTR_SWEPT, 8);
     cursor <<= SGTD_REC_SHIFT;          // (the device counts granules of four records)
-    pool_used = ctr[8]; ovf[0] = (int)ctr[10]; ovf[1] = (int)ctr[11];
-    e->stats.last_list_moves = ctr[9];
+    pool_used = ctr[CTR_POOL_CURSOR]; ovf[0] = (int)ctr[CTR_OVERFLOW]; ovf[1] = (int)ctr[CTR_OVERFLOW + 1];
+    e->stats.last_list_moves = ctr[CTR_LIST_MOVES];
     e->stats.batches_total = (int64_t)tot[0]; e->stats.overflow_launches_total = (int64_t)tot[1]; e->stats.list_moves_total = (int64_t)tot[2];
     if (!ovf[0] && !ovf[1]) {
       // slab use varies a little from run to run (which wave sweeps what): when a batch comes within
@@ -2820,7 +2816,7 @@ int verify_enqueue(sgtd_engine *e, int64_t total, bool guard) {
     P.inl_count = e->inl_counts.as<u32>();
   }
   e->verify_counted = P.inl_count != nullptr;
-  P.overflow = guard ? reinterpret_cast<const int *>(e->cursors.as<u32>() + 10) : nullptr;
+  P.overflow = guard ? reinterpret_cast<const int *>(e->cursors.as<u32>() + CTR_OVERFLOW) : nullptr;
   P.order = nullptr; P.n_blocks = (u32)(nq * cn);
   int grid = nq * cn;
   // a batch of many candidates is dispatched in the order of the candidates' frames (SGTD_VERIFY_ORDER=0: as they stand)
@@ -3039,30 +3035,49 @@ static bool device_can_write(const void *p, size_t bytes) {
 // STDesc.cpp:84-147) as sgtd_query_descs + sgtd_verify + sgtd_result_candidates + sgtd_result_verify +
 // sgtd_result_inlier_entries issue it costs eight waits and some sixty small copies.  Everything is enqueued behind the
 // batch without looking at it — the kernels behind the lists check the batch's overflow flags themselves — the small
-// results come back as one packed block, then the inlier pairs' entries.
-int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_frame_search *io) {
-  PinScope pin_scope(e && !e->grp ? e : nullptr);
+// results come back as one packed block (FramePack), then the inlier pairs' entries.  The call by parts, in their order:
+#ifdef SGTD_EXP_FRAME_LAPS      // host time of the call by part, to stderr (an experiment build)
+struct FrameLaps {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t = t0;
+  std::string s;
+  void lap(const char *what) { const auto n = std::chrono::steady_clock::now(); char b[64]; snprintf(b, sizeof b, " %s %.0f", what, std::chrono::duration<double, std::micro>(n - t).count()); s += b; t = n; }
+  ~FrameLaps() { fprintf(stderr, "[frame laps us]%s | all %.0f\n", s.c_str(), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count()); }
+};
+#define LAP(x) c.laps.lap(x)
+#else
+#define LAP(x) do { } while (0)
+#endif
+// what the parts of one call share
+struct FrameCall {
+  sgtd_frame_search *io = nullptr;
+  int cn = 0;
+  bool lists_only = false;     // candidate_selector alone: no verification, every pair of every list
+  bool direct = false;         // the entries go straight into the caller's (page-locked) arrays
+  size_t pack_bytes = 0;       // the packed block's share of the handle's host block; the staged entries lie behind it
+  const int *ovf = nullptr;    // the batch's overflow flags on the device
+  // the pairs whose entries go to the caller, and their offsets per candidate: the inlier pairs (compacted by frame_verify), or — lists only —
+  // the match lists as they stand (a one-query batch's pairs start at 0 of the pair buffer; pair_off[cn] = their number)
+  const u64 *out_pairs = nullptr;
+  const long long *out_off = nullptr;
+  DescArrays host_out{};       // staged form: this frame's entries and query indices in the host block
+  int *host_qi = nullptr;
+#ifdef SGTD_EXP_FRAME_LAPS
+  FrameLaps laps;
+#endif
+};
+
+// 1. the checks, then sgtd_query_descs without its waits
+static int frame_batch(sgtd_engine *e, const sgtd_desc_soa *q, int64_t nq, sgtd_frame_search *io, FrameCall &c) {
   if (e && e->grp) { e->err = "not available on a multi-device handle"; return SGTD_ERR_UNSUPPORTED; }
   if (!e || !io || nq < 0 || (nq > 0 && (!q || !q->side || !q->label || !q->frame)) || io->capacity < 0) return SGTD_ERR_INVALID;
   CHK(filter_fits(e, 1));
   CHK(prior_fits(e, 1));
   HIPCHK(hipSetDevice(e->cfg.device_id));
-  const int cn = e->dc.cand_num;
-  const bool lists_only = (io->flags & SGTD_FRAME_LISTS_ONLY) != 0;     // candidate_selector alone: no verification, every pair of every list
+  c.io = io;
+  c.cn = e->dc.cand_num;
+  c.lists_only = (io->flags & SGTD_FRAME_LISTS_ONLY) != 0;
   io->n_cand = 0; io->n_inliers = 0;
-#ifdef SGTD_EXP_FRAME_LAPS      // host time of the call by part, to stderr (an experiment build)
-  struct Laps {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t = t0;
-    std::string s;
-    void lap(const char *what) { const auto n = std::chrono::steady_clock::now(); char b[64]; snprintf(b, sizeof b, " %s %.0f", what, std::chrono::duration<double, std::micro>(n - t).count()); s += b; t = n; }
-    ~Laps() { fprintf(stderr, "[frame laps us]%s | all %.0f\n", s.c_str(), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count()); }
-  } laps;
-#define LAP(x) laps.lap(x)
-#else
-#define LAP(x) do { } while (0)
-#endif
   CHK(settle_tail(e));
-  // ---- sgtd_query_descs without its waits
   CHK(begin_batch(e, 1, std::max<long long>(nq, 1), /*kind=*/2));
   CHK(copy_in(e, e->qd, 0, (size_t)nq, q, /*wait=*/false));
   LAP("descriptors_in");
@@ -3076,176 +3091,208 @@ int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_fr
   e->defer_lists = deferred;
   CHK(ls);
   LAP("select_launches");
-  const int *ovf = reinterpret_cast<const int *>(e->cursors.as<u32>() + 10);
-  // the pairs whose entries go to the caller, and their offsets per candidate: the inlier pairs (compacted below), or — lists only —
-  // the match lists as they stand (a one-query batch's pairs start at 0 of the pair buffer; pair_off[cn] = their number)
-  const u64 *out_pairs = e->pairs.as<u64>();
-  const long long *out_off = e->pair_off.as<long long>();
-  if (!lists_only) {
-    // ---- candidate_verify behind it, sized by what the pair buffer holds
-    CHK(verify_enqueue(e, (int64_t)pair_room(e), /*guard=*/true));
-    // ---- the inlier pairs of every candidate, compacted by one workgroup per candidate, and the entries they name
-    CHK(ensure(e, e->inl_counts, (size_t)SGTD_MAX_CAND * sizeof(u32)));
-    CHK(ensure(e, e->inl_off, (size_t)(cn + 1) * sizeof(long long)));
-    CHK(ensure(e, e->inl_pairs, (size_t)pair_room(e) * sizeof(u64)));
-    if (!e->verify_counted) {     // (the packed-f32 form of the vote pass does not count)
-      inlier_count_kernel<<<cn, SGTD_INLIER_CAND_THREADS, 0, e->stream>>>(e->v_inlier.as<unsigned char>(), e->pair_off.as<long long>(), e->n_cand.as<int>(), ovf,
-                                                                           e->inl_counts.as<u32>());
-      HIPCHK(hipGetLastError());
-    }
-    inlier_compact_kernel<<<cn, SGTD_INLIER_CAND_THREADS, 0, e->stream>>>(e->pairs.as<u64>(), e->v_inlier.as<unsigned char>(), e->pair_off.as<long long>(),
-                                                                           e->n_cand.as<int>(), ovf, e->inl_counts.as<u32>(), cn, e->inl_pairs.as<u64>(),
-                                                                           e->inl_off.as<long long>());
+  c.ovf = reinterpret_cast<const int *>(e->cursors.as<u32>() + CTR_OVERFLOW);
+  c.out_pairs = e->pairs.as<u64>();
+  c.out_off = e->pair_off.as<long long>();
+  return SGTD_OK;
+}
+
+// 2. candidate_verify behind it, sized by what the pair buffer holds, and the inlier pairs of every candidate, compacted by one
+// workgroup per candidate
+static int frame_verify(sgtd_engine *e, FrameCall &c) {
+  const int cn = c.cn;
+  CHK(verify_enqueue(e, (int64_t)pair_room(e), /*guard=*/true));
+  CHK(ensure(e, e->inl_counts, (size_t)SGTD_MAX_CAND * sizeof(u32)));
+  CHK(ensure(e, e->inl_off, (size_t)(cn + 1) * sizeof(long long)));
+  CHK(ensure(e, e->inl_pairs, (size_t)pair_room(e) * sizeof(u64)));
+  if (!e->verify_counted) {     // (the packed-f32 form of the vote pass does not count)
+    inlier_count_kernel<<<cn, SGTD_INLIER_CAND_THREADS, 0, e->stream>>>(e->v_inlier.as<unsigned char>(), e->pair_off.as<long long>(), e->n_cand.as<int>(), c.ovf,
+                                                                         e->inl_counts.as<u32>());
     HIPCHK(hipGetLastError());
-    out_pairs = e->inl_pairs.as<u64>();
-    out_off = e->inl_off.as<long long>();
   }
-  // the results go where the host reads them: page-locked memory the kernels write over the link — the packed block first (the
-  // handle's), then the inlier pairs' entries and query indices: straight into the CALLER's arrays when those are page-locked
-  // (sgtd_host_alloc: the 23 MB of a frame's 160 000 pairs on a 10 000-frame map cross the link once, at its rate, and the call
-  // has ONE wait), else into the handle's own block, room for `room` pairs, and from there with memcpy.  (Copies device ->
-  // host cost 0.15 ms each on this runtime and ran at 16 GB/s: eight of them for the entries were 1.4 ms of the call.)
-  const size_t pack_bytes = (frame_pack_bytes(cn) + 24 + 255) & ~(size_t)255;
-  const size_t ucap = (size_t)io->capacity;
-  const sgtd_desc_soa &o = io->entries;
-  static const bool direct_on = [] { const char *v = getenv("SGTD_FRAME_DIRECT"); return !(v && !atoi(v)); }();
-  const bool direct = direct_on && ucap > 0 && device_can_write(io->inlier_q_idx, ucap * 4) && device_can_write(o.side, ucap * 24) && device_can_write(o.angle, ucap * 24) &&
-                      device_can_write(o.center, ucap * 24) && device_can_write(o.vertex, ucap * 36) && device_can_write(o.label, ucap * 12) &&
-                      device_can_write(o.node_id, ucap * 12) && device_can_write(o.frame, ucap * 4);
-  DescArrays host_out{};
-  int *host_qi = nullptr;
-  auto gather = [&](size_t room) -> int {      // entries of the first `room` inlier pairs (the count is on the device)
-    const size_t need = pack_bytes + (direct ? 0 : room * 144);
-    if (need > e->frame_host_bytes) {
-      HIPCHK(hipStreamSynchronize(e->stream));          // (nothing may still be writing the block that is given back)
-      if (e->frame_host) (void)hipHostFree(e->frame_host);
-      e->frame_host = nullptr; e->frame_host_bytes = 0;
-      void *hp = nullptr;
-      if (hipHostMalloc(&hp, need, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); e->err = "hipHostMalloc of the frame results failed"; return SGTD_ERR_HIP; }
-      e->frame_host = static_cast<char *>(hp); e->frame_host_bytes = need;
-    }
-    if (direct) {
-      DescArrays user{};
-      user.side = o.side; user.angle = o.angle; user.center = o.center; user.vertex = o.vertex; user.label = o.label; user.frame = o.frame; user.node_id = o.node_id;
-      gather_pair_entries_kernel<<<1024, 256, 0, e->stream>>>(out_pairs, out_off + cn, (long long)ucap, io->inlier_q_idx, e->tab.view(), user, ovf);
-      HIPCHK(hipGetLastError());
-      return SGTD_OK;
-    }
-    char *at = e->frame_host + pack_bytes;               // (doubles first: every array stays aligned to its element)
-    host_out.side = reinterpret_cast<double *>(at); at += room * 24;
-    host_out.angle = reinterpret_cast<double *>(at); at += room * 24;
-    host_out.center = reinterpret_cast<double *>(at); at += room * 24;
-    host_out.vertex = reinterpret_cast<float *>(at); at += room * 36;
-    host_out.label = reinterpret_cast<int *>(at); at += room * 12;
-    host_out.node_id = reinterpret_cast<int *>(at); at += room * 12;
-    host_out.frame = reinterpret_cast<u32 *>(at); at += room * 4;
-    host_qi = reinterpret_cast<int *>(at);
-    host_out.qrec = nullptr;
-    gather_pair_entries_kernel<<<(unsigned)std::min<long long>(grid_for((long long)room * 8, 256), 1024), 256, 0, e->stream>>>(
-        out_pairs, out_off + cn, (long long)room, host_qi, e->tab.view(), host_out, ovf);
+  inlier_compact_kernel<<<cn, SGTD_INLIER_CAND_THREADS, 0, e->stream>>>(e->pairs.as<u64>(), e->v_inlier.as<unsigned char>(), e->pair_off.as<long long>(),
+                                                                         e->n_cand.as<int>(), c.ovf, e->inl_counts.as<u32>(), cn, e->inl_pairs.as<u64>(),
+                                                                         e->inl_off.as<long long>());
+  HIPCHK(hipGetLastError());
+  c.out_pairs = e->inl_pairs.as<u64>();
+  c.out_off = e->inl_off.as<long long>();
+  return SGTD_OK;
+}
+
+// 3. the entries of the first `room` pairs (their count is on the device) enqueued: into the caller's arrays, or into the handle's
+// host block behind the pack, which grows to hold them
+static int frame_gather(sgtd_engine *e, FrameCall &c, size_t room) {
+  const size_t need = c.pack_bytes + (c.direct ? 0 : room * 144);
+  if (need > e->frame_host_bytes) {
+    HIPCHK(hipStreamSynchronize(e->stream));          // (nothing may still be writing the block that is given back)
+    if (e->frame_host) (void)hipHostFree(e->frame_host);
+    e->frame_host = nullptr; e->frame_host_bytes = 0;
+    void *hp = nullptr;
+    if (hipHostMalloc(&hp, need, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); e->err = "hipHostMalloc of the frame results failed"; return SGTD_ERR_HIP; }
+    e->frame_host = static_cast<char *>(hp); e->frame_host_bytes = need;
+  }
+  if (c.direct) {
+    const sgtd_desc_soa &o = c.io->entries;
+    DescArrays user{};
+    user.side = o.side; user.angle = o.angle; user.center = o.center; user.vertex = o.vertex; user.label = o.label; user.frame = o.frame; user.node_id = o.node_id;
+    gather_pair_entries_kernel<<<1024, 256, 0, e->stream>>>(c.out_pairs, c.out_off + c.cn, (long long)c.io->capacity, c.io->inlier_q_idx, e->tab.view(), user, c.ovf);
     HIPCHK(hipGetLastError());
     return SGTD_OK;
-  };
+  }
+  DescArrays &h = c.host_out;
+  char *at = e->frame_host + c.pack_bytes;               // (doubles first: every array stays aligned to its element)
+  h.side = reinterpret_cast<double *>(at); at += room * 24;
+  h.angle = reinterpret_cast<double *>(at); at += room * 24;
+  h.center = reinterpret_cast<double *>(at); at += room * 24;
+  h.vertex = reinterpret_cast<float *>(at); at += room * 36;
+  h.label = reinterpret_cast<int *>(at); at += room * 12;
+  h.node_id = reinterpret_cast<int *>(at); at += room * 12;
+  h.frame = reinterpret_cast<u32 *>(at); at += room * 4;
+  c.host_qi = reinterpret_cast<int *>(at);
+  h.qrec = nullptr;
+  gather_pair_entries_kernel<<<(unsigned)std::min<long long>(grid_for((long long)room * 8, 256), 1024), 256, 0, e->stream>>>(
+      c.out_pairs, c.out_off + c.cn, (long long)room, c.host_qi, e->tab.view(), h, c.ovf);
+  HIPCHK(hipGetLastError());
+  return SGTD_OK;
+}
+
+// The results go where the host reads them: page-locked memory the kernels write over the link — the packed block first (the
+// handle's), then the inlier pairs' entries and query indices: straight into the CALLER's arrays when those are page-locked
+// (sgtd_host_alloc: the 23 MB of a frame's 160 000 pairs on a 10 000-frame map cross the link once, at its rate, and the call
+// has ONE wait), else into the handle's own block, room for `room` pairs, and from there with memcpy.  (Copies device ->
+// host cost 0.15 ms each on this runtime and ran at 16 GB/s: eight of them for the entries were 1.4 ms of the call.)
+static int frame_results(sgtd_engine *e, FrameCall &c) {
+  const int cn = c.cn;
+  c.pack_bytes = (FramePack(nullptr, cn).bytes() + 255) & ~(size_t)255;
+  const size_t ucap = (size_t)c.io->capacity;
+  const sgtd_desc_soa &o = c.io->entries;
+  static const bool direct_on = [] { const char *v = getenv("SGTD_FRAME_DIRECT"); return !(v && !atoi(v)); }();
+  c.direct = direct_on && ucap > 0 && device_can_write(c.io->inlier_q_idx, ucap * 4) && device_can_write(o.side, ucap * 24) && device_can_write(o.angle, ucap * 24) &&
+             device_can_write(o.center, ucap * 24) && device_can_write(o.vertex, ucap * 36) && device_can_write(o.label, ucap * 12) &&
+             device_can_write(o.node_id, ucap * 12) && device_can_write(o.frame, ucap * 4);
   if (e->frame_inl_cap == 0) e->frame_inl_cap = 16384;
-  CHK(gather(direct ? ucap : e->frame_inl_cap));
+  CHK(frame_gather(e, c, c.direct ? ucap : e->frame_inl_cap));
   pack_frame_kernel<<<1, 256, 0, e->stream>>>(e->cursors.as<u32>(), e->n_cand.as<int>(), e->q_M.as<u32>(), e->q_pair_base.as<u32>(), e->q_count.as<u32>(),
                                               e->q_P.as<unsigned long long>(), e->cand_frame.as<int>(), e->cand_votes.as<int>(),
-                                              e->pair_off.as<long long>(), lists_only ? nullptr : e->v_score.as<double>(), lists_only ? nullptr : e->v_pose.as<double>(), out_off,
+                                              e->pair_off.as<long long>(), c.lists_only ? nullptr : e->v_score.as<double>(), c.lists_only ? nullptr : e->v_pose.as<double>(), c.out_off,
                                               cn, reinterpret_cast<unsigned char *>(e->frame_host), e->totals.as<unsigned long long>());
   HIPCHK(hipGetLastError());
   LAP("verify_and_result_launches");
-  CHK(xfer_sync(e));                                        // ---- the call's one wait (nothing is queued for it: it also gives the staging back)
-  struct { const unsigned char *p; const unsigned char *data() const { return p; } } pack{reinterpret_cast<const unsigned char *>(e->frame_host)};
-  unsigned long long tot[3];                                // the handle's running totals, as sync_batch reads them
-  std::memcpy(tot, pack.data() + frame_pack_bytes(cn), sizeof(tot));
-  LAP("wait_1");
-  const u32 *w = reinterpret_cast<const u32 *>(pack.data());
-  if (w[10] | w[11]) {
-    // the batch outgrew a work buffer (a first frame, a frame unlike the ones before): sgtd_sync re-runs it, then the
-    // calls this one stands for, one after the other
-    CHK(sync_batch(e));
-    if (lists_only) {
-      std::vector<int64_t> off((size_t)cn + 1, 0);
-      CHK(sgtd_result_candidates(e, &io->n_cand, io->cand_frame, io->cand_votes, off.data()));
-      if (io->pair_off) std::memcpy(io->pair_off, off.data(), off.size() * sizeof(int64_t));
-      if (io->inlier_off) std::memcpy(io->inlier_off, off.data(), off.size() * sizeof(int64_t));
-      const int64_t total = off[(size_t)io->n_cand];
-      io->n_inliers = total;
-      if (total > io->capacity) return SGTD_ERR_CAPACITY;
-      if (total == 0) return SGTD_OK;
-      std::vector<int64_t> ids((size_t)total);
-      std::vector<int32_t> qi;
-      int64_t got = 0;
-      if (!io->inlier_q_idx) qi.resize((size_t)total);
-      CHK(sgtd_result_pairs(e, 0, io->inlier_q_idx ? io->inlier_q_idx : qi.data(), ids.data(), total, &got));
-      return sgtd_fetch_entries(e, ids.data(), total, &io->entries);
-    }
-    CHK(sgtd_verify(e));
-    CHK(sgtd_result_candidates(e, &io->n_cand, io->cand_frame, io->cand_votes, io->pair_off));
-    CHK(sgtd_result_verify(e, 0, io->score, io->pose));
-    std::vector<int64_t> off((size_t)cn + 1);
-    const int st = sgtd_result_inlier_entries(e, 0, off.data(), io->inlier_q_idx, &io->entries, io->capacity, &io->n_inliers);
+  return SGTD_OK;
+}
+
+// 4. the batch outgrew a work buffer (a first frame, a frame unlike the ones before): sgtd_sync re-runs it, then the calls this
+// one stands for, one after the other
+static int frame_fallback(sgtd_engine *e, FrameCall &c) {
+  sgtd_frame_search *io = c.io;
+  CHK(sync_batch(e));
+  if (c.lists_only) {
+    std::vector<int64_t> off((size_t)c.cn + 1, 0);
+    CHK(sgtd_result_candidates(e, &io->n_cand, io->cand_frame, io->cand_votes, off.data()));
+    if (io->pair_off) std::memcpy(io->pair_off, off.data(), off.size() * sizeof(int64_t));
     if (io->inlier_off) std::memcpy(io->inlier_off, off.data(), off.size() * sizeof(int64_t));
-    return st;
+    const int64_t total = off[(size_t)io->n_cand];
+    io->n_inliers = total;
+    if (total > io->capacity) return SGTD_ERR_CAPACITY;
+    if (total == 0) return SGTD_OK;
+    std::vector<int64_t> ids((size_t)total);
+    std::vector<int32_t> qi;
+    int64_t got = 0;
+    if (!io->inlier_q_idx) qi.resize((size_t)total);
+    CHK(sgtd_result_pairs(e, 0, io->inlier_q_idx ? io->inlier_q_idx : qi.data(), ids.data(), total, &got));
+    return sgtd_fetch_entries(e, ids.data(), total, &io->entries);
   }
-  // the host-side state every sgtd_result_* call reads, as sync_batch leaves it
-  const int *cf = reinterpret_cast<const int *>(pack.data() + 72), *cv = cf + cn;
-  const long long *po = reinterpret_cast<const long long *>(pack.data() + 72 + (size_t)cn * 8);
-  const double *sc = reinterpret_cast<const double *>(po + cn + 1), *ps = sc + cn;
-  const long long *ioff = reinterpret_cast<const long long *>(ps + (size_t)cn * 12);
+  CHK(sgtd_verify(e));
+  CHK(sgtd_result_candidates(e, &io->n_cand, io->cand_frame, io->cand_votes, io->pair_off));
+  CHK(sgtd_result_verify(e, 0, io->score, io->pose));
+  std::vector<int64_t> off((size_t)c.cn + 1);
+  const int st = sgtd_result_inlier_entries(e, 0, off.data(), io->inlier_q_idx, &io->entries, io->capacity, &io->n_inliers);
+  if (io->inlier_off) std::memcpy(io->inlier_off, off.data(), off.size() * sizeof(int64_t));
+  return st;
+}
+
+// 5. the host-side state every sgtd_result_* call reads, as sync_batch leaves it, from the pack
+static int frame_host_tables(sgtd_engine *e, const FrameCall &c, const FramePack &pack) {
+  const size_t cn = (size_t)c.cn;
   if (!(e->h_count.resize(1) && e->h_pair_base.resize(2) && e->h_q_M.resize(1) && e->h_q_P.resize(1) && e->h_n_cand.resize(1) &&
-        e->h_cand_frame.resize((size_t)cn) && e->h_cand_votes.resize((size_t)cn) && e->h_pair_off.resize((size_t)cn + 1))) {
+        e->h_cand_frame.resize(cn) && e->h_cand_votes.resize(cn) && e->h_pair_off.resize(cn + 1))) {
     e->err = "hipHostMalloc of the result tables failed";
     return SGTD_ERR_HIP;
   }
-  e->h_count[0] = w[15]; e->h_pair_base[0] = 0; e->h_pair_base[1] = w[14]; e->h_q_M[0] = w[13];
-  std::memcpy(&e->h_q_P[0], pack.data() + 64, 8);
-  e->h_n_cand[0] = (int)w[12];
-  std::memcpy(e->h_cand_frame.data(), cf, (size_t)cn * 4); std::memcpy(e->h_cand_votes.data(), cv, (size_t)cn * 4);
-  std::memcpy(e->h_pair_off.data(), po, ((size_t)cn + 1) * 8);
-  {
-    sgtd_stats &st = e->stats;
-    unsigned long long swept = 0;
-    std::memcpy(&swept, w + 6, 8);
-    st.overflowed = 0; st.last_list_moves = w[9];
-    st.last_queries = 1; st.last_D = w[15]; st.last_P = (int64_t)e->h_q_P[0]; st.last_M = w[13]; st.last_P_swept = (int64_t)swept;
-    st.last_cand_pairs = po[cn];
-    if (e->totals.p) { st.batches_total = (int64_t)tot[0]; st.overflow_launches_total = (int64_t)tot[1]; st.list_moves_total = (int64_t)tot[2]; }
+  e->h_count[0] = *pack.q_count(); e->h_pair_base[0] = 0; e->h_pair_base[1] = *pack.pairs_total(); e->h_q_M[0] = *pack.q_M();
+  std::memcpy(&e->h_q_P[0], pack.q_P(), 8);
+  e->h_n_cand[0] = *pack.n_cand();
+  std::memcpy(e->h_cand_frame.data(), pack.cand_frame(), cn * 4); std::memcpy(e->h_cand_votes.data(), pack.cand_votes(), cn * 4);
+  std::memcpy(e->h_pair_off.data(), pack.pair_off(), (cn + 1) * 8);
+  sgtd_stats &st = e->stats;
+  const u32 *ctr = pack.ctr();
+  unsigned long long swept = 0;
+  std::memcpy(&swept, ctr + CTR_SWEPT, 8);
+  st.overflowed = 0; st.last_list_moves = ctr[CTR_LIST_MOVES];
+  st.last_queries = 1; st.last_D = *pack.q_count(); st.last_P = (int64_t)e->h_q_P[0]; st.last_M = *pack.q_M(); st.last_P_swept = (int64_t)swept;
+  st.last_cand_pairs = pack.pair_off()[cn];
+  if (e->totals.p) {      // the handle's running totals, as sync_batch reads them
+    const unsigned long long *tot = pack.totals();
+    st.batches_total = (int64_t)tot[0]; st.overflow_launches_total = (int64_t)tot[1]; st.list_moves_total = (int64_t)tot[2];
   }
   stage_times(e);
   e->batch_synced = true;
-  new_results(e, !lists_only);
-  io->n_cand = (int32_t)w[12];
-  if (io->cand_frame) std::memcpy(io->cand_frame, cf, (size_t)cn * 4);
-  if (io->cand_votes) std::memcpy(io->cand_votes, cv, (size_t)cn * 4);
-  if (io->pair_off) std::memcpy(io->pair_off, po, ((size_t)cn + 1) * 8);
-  if (io->score && !lists_only) std::memcpy(io->score, sc, (size_t)cn * 8);
-  if (io->pose && !lists_only) std::memcpy(io->pose, ps, (size_t)cn * 96);
-  if (io->inlier_off) std::memcpy(io->inlier_off, ioff, ((size_t)cn + 1) * 8);
-  const int64_t n_inl = ioff[cn];
+  new_results(e, !c.lists_only);
+  return SGTD_OK;
+}
+
+// 6. the caller's io from the pack, then — staged form — the entries from the host block: gathered once more, with a wait, when the
+// frame has more pairs than the block had room for
+static int frame_copy_out(sgtd_engine *e, FrameCall &c, const FramePack &pack) {
+  sgtd_frame_search *io = c.io;
+  const size_t cn = (size_t)c.cn;
+  io->n_cand = (int32_t)*pack.n_cand();
+  if (io->cand_frame) std::memcpy(io->cand_frame, pack.cand_frame(), cn * 4);
+  if (io->cand_votes) std::memcpy(io->cand_votes, pack.cand_votes(), cn * 4);
+  if (io->pair_off) std::memcpy(io->pair_off, pack.pair_off(), (cn + 1) * 8);
+  if (io->score && !c.lists_only) std::memcpy(io->score, pack.score(), cn * 8);
+  if (io->pose && !c.lists_only) std::memcpy(io->pose, pack.pose(), cn * 96);
+  if (io->inlier_off) std::memcpy(io->inlier_off, pack.inl_off(), (cn + 1) * 8);
+  const int64_t n_inl = pack.inl_off()[cn];
   io->n_inliers = n_inl;
   if (n_inl > io->capacity) return SGTD_ERR_CAPACITY;       // (everything else is valid; sgtd_result_inlier_entries with more room gives the pairs)
   if (n_inl == 0) return SGTD_OK;
-  if (direct) { LAP("entries_in_place"); return SGTD_OK; }  // (the kernel wrote the caller's arrays)
+  if (c.direct) { LAP("entries_in_place"); return SGTD_OK; }  // (the kernel wrote the caller's arrays)
   if ((size_t)n_inl > e->frame_inl_cap) {                   // more inlier pairs than the gather had room for: once more, with room
-    e->frame_inl_cap = (size_t)n_inl + (size_t)n_inl / 2;   // (io, cf .. ioff were copied out above: the block may move)
-    CHK(gather(e->frame_inl_cap));
+    e->frame_inl_cap = (size_t)n_inl + (size_t)n_inl / 2;   // (everything of the pack was copied out above: the block may move)
+    CHK(frame_gather(e, c, e->frame_inl_cap));
     HIPCHK(hipStreamSynchronize(e->stream));
   } else if ((size_t)n_inl * 2 > e->frame_inl_cap) {
     e->frame_inl_cap = (size_t)n_inl * 2;                   // (room for the next frame; host_out still names this frame's arrays)
   }
   LAP("host_tables");
   const size_t n = (size_t)n_inl;
-  if (io->inlier_q_idx) std::memcpy(io->inlier_q_idx, host_qi, n * sizeof(int));
-  if (o.side) std::memcpy(o.side, host_out.side, n * 24);
-  if (o.angle) std::memcpy(o.angle, host_out.angle, n * 24);
-  if (o.center) std::memcpy(o.center, host_out.center, n * 24);
-  if (o.vertex) std::memcpy(o.vertex, host_out.vertex, n * 36);
-  if (o.label) std::memcpy(o.label, host_out.label, n * 12);
-  if (o.node_id) std::memcpy(o.node_id, host_out.node_id, n * 12);
-  if (o.frame) std::memcpy(o.frame, host_out.frame, n * 4);
+  const sgtd_desc_soa &o = io->entries;
+  const DescArrays &h = c.host_out;
+  if (io->inlier_q_idx) std::memcpy(io->inlier_q_idx, c.host_qi, n * sizeof(int));
+  if (o.side) std::memcpy(o.side, h.side, n * 24);
+  if (o.angle) std::memcpy(o.angle, h.angle, n * 24);
+  if (o.center) std::memcpy(o.center, h.center, n * 24);
+  if (o.vertex) std::memcpy(o.vertex, h.vertex, n * 36);
+  if (o.label) std::memcpy(o.label, h.label, n * 12);
+  if (o.node_id) std::memcpy(o.node_id, h.node_id, n * 12);
+  if (o.frame) std::memcpy(o.frame, h.frame, n * 4);
   LAP("entries_out");
   return SGTD_OK;
+}
+
+int sgtd_search_frame(sgtd_handle e, const sgtd_desc_soa *q, int64_t nq, sgtd_frame_search *io) {
+  PinScope pin_scope(e && !e->grp ? e : nullptr);
+  FrameCall c;
+  CHK(frame_batch(e, q, nq, io, c));
+  if (!c.lists_only) CHK(frame_verify(e, c));
+  CHK(frame_results(e, c));
+  CHK(xfer_sync(e));                                        // ---- the call's one wait (nothing is queued for it: it also gives the staging back)
+  const FramePack pack(e->frame_host, c.cn);
+  LAP("wait_1");
+  if (pack.overflowed()) return frame_fallback(e, c);
+  CHK(frame_host_tables(e, c, pack));
+  return frame_copy_out(e, c, pack);
 }
 #undef LAP
 

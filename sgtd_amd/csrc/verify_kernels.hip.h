@@ -23,6 +23,7 @@
 // binary is UNPINNED, parity with that restatement is exact.
 #pragma once
 #include "common.hip.h"
+#include "probe_kernels.hip.h"     // (the counter words the frame pack carries)
 
 #define SGTD_VERIFY_THREADS 256
 #define SGTD_VERIFY_MAX_HYP 64     // use_size <= 50 (:467-468)
@@ -632,27 +633,48 @@ __global__ __launch_bounds__(SGTD_INLIER_CAND_THREADS) void inlier_compact_kerne
 }
 
 // everything of a one-query batch the host needs after sgtd_search_frame's first (and usually only) wait, in one block:
-//   u32 ctr[12] | i32 n_cand, u32 q_M, u32 pairs_total, u32 q_count | u64 q_P | i32 cand_frame[cn] | i32 cand_votes[cn] |
+//   u32 ctr[CTR_COUNT] | i32 n_cand, u32 q_M, u32 pairs_total, u32 q_count | u64 q_P | i32 cand_frame[cn] | i32 cand_votes[cn] |
 //   i64 pair_off[cn + 1] | f64 score[cn] | f64 pose[cn * 12] | i64 inl_off[cn + 1] | u64 totals[3] (behind frame_pack_bytes: the handle's running counts)
 // `out` is page-locked host memory: the block is on the host when the stream has been waited for
 __host__ __device__ __forceinline__ size_t frame_pack_bytes(int cn) {
-  return 48 + 16 + 8 + (size_t)cn * 8 + (size_t)(cn + 1) * 8 + (size_t)cn * 8 + (size_t)cn * 96 + (size_t)(cn + 1) * 8;
+  return CTR_COUNT * sizeof(u32) + 16 + 8 + (size_t)cn * 8 + (size_t)(cn + 1) * 8 + (size_t)cn * 8 + (size_t)cn * 96 + (size_t)(cn + 1) * 8;
 }
+// The block's layout, for the kernel that writes it and the host code that reads it: every field starts where the one before
+// it ends (the 4-byte fields come in pairs, so every 8-byte field is 8-byte aligned in an 8-byte aligned block).
+struct FramePack {
+  unsigned char *base;
+  int cn;
+  __host__ __device__ FramePack(void *block, int cand_num) : base(static_cast<unsigned char *>(block)), cn(cand_num) {}
+  __host__ __device__ u32 *ctr() const { return reinterpret_cast<u32 *>(base); }          // ProbeBuffers::ctr's first CTR_COUNT words
+  __host__ __device__ bool overflowed() const { return (ctr()[CTR_OVERFLOW] | ctr()[CTR_OVERFLOW + 1]) != 0u; }
+  __host__ __device__ int *n_cand() const { return reinterpret_cast<int *>(ctr() + CTR_COUNT); }
+  __host__ __device__ u32 *q_M() const { return reinterpret_cast<u32 *>(n_cand() + 1); }
+  __host__ __device__ u32 *pairs_total() const { return q_M() + 1; }
+  __host__ __device__ u32 *q_count() const { return pairs_total() + 1; }
+  __host__ __device__ unsigned long long *q_P() const { return reinterpret_cast<unsigned long long *>(q_count() + 1); }
+  __host__ __device__ int *cand_frame() const { return reinterpret_cast<int *>(q_P() + 1); }
+  __host__ __device__ int *cand_votes() const { return cand_frame() + cn; }
+  __host__ __device__ long long *pair_off() const { return reinterpret_cast<long long *>(cand_frame() + (size_t)cn * 2); }      // (behind both)
+  __host__ __device__ double *score() const { return reinterpret_cast<double *>(pair_off() + cn + 1); }
+  __host__ __device__ double *pose() const { return score() + cn; }
+  __host__ __device__ long long *inl_off() const { return reinterpret_cast<long long *>(pose() + (size_t)cn * 12); }
+  __host__ __device__ unsigned long long *totals() const { return reinterpret_cast<unsigned long long *>(base + frame_pack_bytes(cn)); }     // = inl_off() + cn + 1
+  __host__ __device__ size_t bytes() const { return frame_pack_bytes(cn) + 3 * sizeof(unsigned long long); }     // (no pointer is formed: base may be null)
+};
 __global__ __launch_bounds__(256) void pack_frame_kernel(const u32 *ctr, const int *n_cand, const u32 *q_M, const u32 *q_pair_base, const u32 *q_count,
                                                          const unsigned long long *q_P, const int *cand_frame, const int *cand_votes,
                                                          const long long *pair_off, const double *score, const double *pose, const long long *inl_off,
                                                          int cn, unsigned char *out, const unsigned long long *totals) {
   const int t = threadIdx.x;
-  u32 *w = reinterpret_cast<u32 *>(out);
-  if (t < 12) w[t] = ctr[t];
-  if (t == 0) { w[12] = (u32)n_cand[0]; w[13] = q_M[0]; w[14] = q_pair_base[1]; w[15] = q_count[0]; *reinterpret_cast<unsigned long long *>(out + 64) = q_P[0]; }
-  int *cf = reinterpret_cast<int *>(out + 72), *cv = cf + cn;
-  long long *po = reinterpret_cast<long long *>(out + 72 + (size_t)cn * 8);
-  double *sc = reinterpret_cast<double *>(po + cn + 1), *ps = sc + cn;
-  long long *io = reinterpret_cast<long long *>(ps + (size_t)cn * 12);
+  const FramePack F(out, cn);
+  if (t < CTR_COUNT) F.ctr()[t] = ctr[t];
+  if (t == 0) { *F.n_cand() = n_cand[0]; *F.q_M() = q_M[0]; *F.pairs_total() = q_pair_base[1]; *F.q_count() = q_count[0]; *F.q_P() = q_P[0]; }
+  int *cf = F.cand_frame(), *cv = F.cand_votes();
+  long long *po = F.pair_off(), *io = F.inl_off();
+  double *sc = F.score(), *ps = F.pose();
   // (score / pose NULL: a call without verification — zeros)
   for (int k = t; k < cn; k += 256) { cf[k] = cand_frame[k]; cv[k] = cand_votes[k]; sc[k] = score ? score[k] : 0.0; }
   for (int k = t; k <= cn; k += 256) { po[k] = pair_off[k]; io[k] = inl_off[k]; }
   for (int k = t; k < cn * 12; k += 256) ps[k] = pose ? pose[k] : 0.0;
-  if (t < 3) reinterpret_cast<unsigned long long *>(out + frame_pack_bytes(cn))[t] = totals ? totals[t] : 0ull;
+  if (t < 3) F.totals()[t] = totals ? totals[t] : 0ull;
 }

@@ -52,16 +52,6 @@ typedef float sgtd_f32x16 __attribute__((ext_vector_type(16)));
 #ifndef SGTD_VM_WAVES
 #define SGTD_VM_WAVES 2
 #endif
-// SGTD_VM_PIPE (experiment switch): 1 / 2 = a software pipeline across tiles — the next tile prepared between the current tile's
-// MFMAs (one hypothesis tile's / both tiles', the order forced with sched_group_barrier).  Measured and not the default: 13.8 / 13.1
-// against 12.7 ms per batch on the same box — the kernel is bound by the NUMBER of vector instructions (4 cycles each on a SIMD
-// whichever wave they come from), not by where the MFMAs sit among them.
-#ifndef SGTD_VM_PIPE
-#define SGTD_VM_PIPE 0
-#endif
-#ifndef SGTD_VM_VALU_PER_MFMA
-#define SGTD_VM_VALU_PER_MFMA 18
-#endif
 
 #ifdef SGTD_EXP_VSTAT
 // experiment build: 0 (pair tile, hypothesis tile) steps, 1 pair tiles with something queued, 2 combinations queued for the
@@ -286,13 +276,9 @@ __global__ __launch_bounds__(NW * SGTD_WAVE) __attribute__((amdgpu_waves_per_eu(
         const float4 kk = *reinterpret_cast<const float4 *>(kap_buf + m * 32 + 8 * k + 4 * (int)hh);
         a[4 * k] = kk.x; a[4 * k + 1] = kk.y; a[4 * k + 2] = kk.z; a[4 * k + 3] = kk.w;
       }
-#ifdef SGTD_EXP_VM_NOMFMA
-      a[0] += (float)p.Aop[m][0][0] + (float)p.Aop[m][1][7] + (float)Bop[T][0][0];     // (experiment: timing without the matrix pipe)
-#else
       a = __builtin_amdgcn_mfma_f32_32x32x16_f16(p.Aop[m][0], Bop[T][0], a, 0, 0, 0);
       a = __builtin_amdgcn_mfma_f32_32x32x16_f16(p.Aop[m][1], Bop[T][1], a, 0, 0, 0);
       a = __builtin_amdgcn_mfma_f32_32x32x16_f16(p.Aop[m][2], Bop[T][2], a, 0, 0, 0);
-#endif
       acc[m] = a;
     }
   };
@@ -347,70 +333,6 @@ __global__ __launch_bounds__(NW * SGTD_WAVE) __attribute__((amdgpu_waves_per_eu(
     }
   };
 
-#if SGTD_VM_PIPE
-  // Software pipeline: while tile i's MFMAs run, the vector unit prepares tile i + 1 (its products are independent of them), then
-  // looks at tile i's results.  kap alternates between two LDS buffers (tile i's is read while tile i + 1's is written).
-  Tile raw;                                    // the vertices of the tile that is prepared next
-  vertices_of(pair_of((u32)wave), raw);
-  u64 pr_next = pair_of(min((u32)wave + STEP, last_tile));
-  Prep cur;
-  prepare(raw, (u32)wave, kap_w, cur);
-  vertices_of(pr_next, raw);                   // tile wave + STEP (clamped)
-  pr_next = pair_of(min((u32)wave + 2 * STEP, last_tile));
-  u32 flip = 0;
-  for (u32 tile = (u32)wave; tile < n_tiles; tile += STEP) {
-    float *kap_cur = kap_w + flip * 96, *kap_nxt = kap_w + (flip ^ 1u) * 96;
-    Prep nxt;
-    u32 word = 0, open = 0;
-#if SGTD_VM_PIPE == 2
-    // both hypothesis tiles' eighteen MFMAs with the whole preparation of the next tile between them
-    sgtd_f32x16 acc[3], acc1[3];
-    __builtin_amdgcn_sched_barrier(0);
-    products(0, cur, kap_cur, acc);
-    products(1, cur, kap_cur, acc1);
-    prepare(raw, tile + STEP, kap_nxt, nxt);
-    vertices_of(pr_next, raw);
-    pr_next = pair_of(min(tile + 3 * STEP, last_tile));
-#pragma unroll
-    for (int i = 0; i < 18; i++) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, SGTD_VM_VALU_PER_MFMA / 2, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    look(0, cur, acc, word, open);
-    look(1, cur, acc1, word, open);
-    words[(size_t)tile * 64 + lane] = word;
-    enqueue(tile, open);
-    cur = nxt;
-    flip ^= 1u;
-    continue;
-#else
-    sgtd_f32x16 acc[3];
-    __builtin_amdgcn_sched_barrier(0);
-    products(0, cur, kap_cur, acc);
-    prepare(raw, tile + STEP, kap_nxt, nxt);                       // (under tile i's first MFMAs)
-    vertices_of(pr_next, raw);                                     // tile i + 2 STEP's vertices, i + 3 STEP's pair word
-    pr_next = pair_of(min(tile + 3 * STEP, last_tile));
-    // (the order the scheduler is asked for: a matrix instruction, then its share of the preparation's vector instructions — left
-    // to itself it issues the nine MFMAs in a row and the wave stands at the matrix pipe while its vector work waits)
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, SGTD_VM_VALU_PER_MFMA, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);       // (the look's vector instructions, which wait for the MFMAs, stay behind this line)
-    look(0, cur, acc, word, open);
-    if (n_ht > 1) {
-      products(1, cur, kap_cur, acc);
-      look(1, cur, acc, word, open);
-    }
-    words[(size_t)tile * 64 + lane] = word;
-    enqueue(tile, open);
-    cur = nxt;
-    flip ^= 1u;
-#endif
-  }
-#else
   Tile cur;
   vertices_of(pair_of((u32)wave), cur);
   u64 pr_next = pair_of(min((u32)wave + STEP, last_tile));
@@ -433,7 +355,6 @@ __global__ __launch_bounds__(NW * SGTD_WAVE) __attribute__((amdgpu_waves_per_eu(
     cur = nxt;
     pr_next = pr_after;
   }
-#endif
   if (qn) { vm_drain(P, bid, queue, qn, base, qslot0, words, s_votes); VMSTAT(4, 1); }
 #pragma unroll
   for (int T = 0; T < 2; T++)

@@ -37,6 +37,7 @@ namespace kernels_of_the_engine {
 }  // namespace kernels_of_the_engine
 using kernels_of_the_engine::ProbeBuffers;
 using kernels_of_the_engine::frame_pack_bytes;
+using kernels_of_the_engine::FramePack;
 using kernels_of_the_engine::u32;
 using kernels_of_the_engine::u64;
 
@@ -86,6 +87,26 @@ size_t room_of(const void *p) {
   hipDeviceptr_t base; size_t size;
   REQUIRE(hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess);
   return size - (size_t)(static_cast<const char *>(p) - static_cast<const char *>(base));
+}
+
+// FramePack puts every field where the arithmetic it replaced put it (the offsets written out once more, as numbers), and
+// every 8-byte field on an 8-byte boundary
+bool frame_pack_layout_holds(int cn) {
+  namespace K = kernels_of_the_engine;
+  alignas(8) static unsigned char block[112 + 128 * 64];
+  const FramePack F(block, cn);
+  const size_t n = (size_t)cn;
+  auto at = [&](const void *p) { return (size_t)(static_cast<const unsigned char *>(p) - block); };
+  const size_t eight[] = {at(F.q_P()), at(F.pair_off()), at(F.score()), at(F.pose()), at(F.inl_off()), at(F.totals())};
+  for (size_t o : eight)
+    if (o % 8) return false;
+  return at(F.ctr()) == 0 && at(F.ctr() + K::CTR_SWEPT) == 24 && at(F.ctr() + K::CTR_LIST_MOVES) == 36 &&
+         at(F.ctr() + K::CTR_OVERFLOW) == 40 && K::CTR_COUNT == 12 &&
+         at(F.n_cand()) == 48 && at(F.q_M()) == 52 && at(F.pairs_total()) == 56 && at(F.q_count()) == 60 && at(F.q_P()) == 64 &&
+         at(F.cand_frame()) == 72 && at(F.cand_votes()) == 72 + n * 4 && at(F.pair_off()) == 72 + n * 8 &&
+         at(F.score()) == 72 + n * 8 + (n + 1) * 8 && at(F.pose()) == 72 + n * 8 + (n + 1) * 8 + n * 8 &&
+         at(F.inl_off()) == 72 + n * 8 + (n + 1) * 8 + n * 8 + n * 96 && at(F.totals()) == 72 + n * 8 + (n + 1) * 8 + n * 8 + n * 96 + (n + 1) * 8 &&
+         at(F.totals()) == frame_pack_bytes(cn) && F.bytes() == frame_pack_bytes(cn) + 24 && F.bytes() == 112 + 128 * n;
 }
 
 // ---- what the stages' scenario leaves in the candidate tables: functions of (query, slot) alone, the same on every "device"
@@ -292,16 +313,15 @@ void hook(const char *name, void **args, void *user) {
     const int cn = *static_cast<int *>(args[12]);
     unsigned char *out = *static_cast<unsigned char **>(args[13]);
     REQUIRE(sgtd_stub_block_size(out) >= frame_pack_bytes(cn));
-    u32 *w = reinterpret_cast<u32 *>(out);
-    memcpy(w, *static_cast<const u32 **>(args[0]), 12 * sizeof(u32));      // (the batch's counters and flags, as the kernel copies them)
-    if (S.frame_overflow > 0) { S.frame_overflow--; w[10] = 1; return; }
+    REQUIRE(frame_pack_layout_holds(1) && frame_pack_layout_holds(50) && frame_pack_layout_holds(64));
+    namespace K = kernels_of_the_engine;
+    const FramePack F(out, cn);
+    memcpy(F.ctr(), *static_cast<const u32 **>(args[0]), K::CTR_COUNT * sizeof(u32));      // (the batch's counters and flags, as the kernel copies them)
+    if (S.frame_overflow > 0) { S.frame_overflow--; F.ctr()[K::CTR_OVERFLOW] = 1; return; }
     if (S.frame_inliers >= 0) {
-      w[12] = 1; w[13] = 100; w[14] = (u32)S.frame_inliers; w[15] = 64;
-      long long *po = reinterpret_cast<long long *>(out + 72 + (size_t)cn * 8);
-      double *sc = reinterpret_cast<double *>(po + cn + 1), *ps = sc + cn;
-      long long *io = reinterpret_cast<long long *>(ps + (size_t)cn * 12);
-      for (int k = 1; k <= cn; k++) { po[k] = S.frame_inliers; io[k] = S.frame_inliers; }
-      sc[0] = (double)S.frame_inliers;
+      *F.n_cand() = 1; *F.q_M() = 100; *F.pairs_total() = (u32)S.frame_inliers; *F.q_count() = 64;
+      for (int k = 1; k <= cn; k++) { F.pair_off()[k] = S.frame_inliers; F.inl_off()[k] = S.frame_inliers; }
+      F.score()[0] = (double)S.frame_inliers;
     }
   }
 }

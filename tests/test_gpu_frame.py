@@ -130,6 +130,43 @@ def test_search_frame_equals_the_calls_it_stands_for(mods, monkeypatch):
     h.close()
 
 
+@pytest.mark.parametrize("cn", [1, 64])
+def test_search_frame_at_both_ends_of_candidate_num(mods, cn):
+    """every field of the packed block sgtd_search_frame reads behind its one wait lies at an offset that depends on
+    candidate_num, and pack_frame_kernel's 256 threads copy the 12 x candidate_num pose values in three trips at 64 where
+    most of them take none at 1: the call against the calls it stands for on handles at both ends of the envelope, with
+    ordinary and with page-locked arrays, and the lists alone"""
+    oracle, manager, synth = mods
+    m = synth.make_map(24, 120, stream=3)
+    qs = synth.make_queries(m, 2, stream=3)
+    g = manager.STDescManager(candidate_num=cn)
+    g.add_frames(m.xyz, m.label)
+    filled, inliers = [], []
+    for q in range(2):
+        d = g.BuildSingleScanSTD(qs.xyz[q], qs.label[q])
+        ref = _five_calls(g, d)
+        room = int(ref[1].pair_off[0, -1])
+        filled.append(int(ref[1].n_cand[0]))
+        for page_locked in (False, True):
+            fs = g.search_frame(d, capacity=room, page_locked=page_locked)
+            assert fs["status"] == 0
+            _same(fs, ref, cn)
+            inliers.append(fs["n_inliers"])
+        qi_all, de_all = g.result_pairs(0, ref[1])
+        ent_all = g.fetch_entries(de_all)
+        lo = g.search_frame(d, capacity=room, lists_only=True)
+        assert lo["status"] == 0 and lo["n_cand"] == filled[-1] and lo["n_inliers"] == room
+        assert np.array_equal(lo["cand_frame"], ref[1].cand_frame[0]) and np.array_equal(lo["cand_votes"], ref[1].cand_votes[0])
+        assert np.array_equal(lo["pair_off"], ref[1].pair_off[0]) and np.array_equal(lo["inlier_off"], ref[1].pair_off[0])
+        assert np.array_equal(lo["inlier_q_idx"], qi_all)
+        for name, _, _ in ent_all.FIELDS:
+            assert np.array_equal(getattr(lo["entries"], name), getattr(ent_all, name)), name
+    print("candidate_num", cn, "candidates filled", filled, "inlier pairs", inliers)
+    assert max(inliers) > 0
+    assert max(filled) == 1 if cn == 1 else max(filled) > 1      # (at 64 a query really fills more than one slot)
+    g.close()
+
+
 def test_build_one_block_form_and_the_general_form_agree(mods):
     """sgtd_build of one frame takes the one-transfer form up to 4 MB of descriptors and the general form beyond (more
     than ~850 keypoints: also the global-memory dedup); both against the oracle"""

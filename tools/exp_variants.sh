@@ -1,5 +1,5 @@
 #!/bin/bash
-# times the sweep of kernel variants under test (variants/lib_*.so, built with -DSGTD_EXP_*) and of launch
+# times the sweep of kernel variants under test (variants/lib_*.so: builds with other tuning constants, or of a branch) and of launch
 # knobs with a short bench run each; prints ms per kernel stage.   bash tools/exp_variants.sh [knob=value ...]
 ARGS="--full --steps 4 --warmup 1 --cpu-baseline off --verify off --boundary off --sweep none --profile-steps 2"
 run() {  # label, env...
