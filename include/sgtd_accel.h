@@ -115,6 +115,11 @@ typedef struct sgtd_stats {
   int64_t last_list_moves;   /* ... of the last batch                                         */
   int64_t device_allocs_total; /* hipMalloc calls of the handle's work and table buffers so far (a buffer that grows is
                                 freed and allocated again, which synchronises the device: a timed region should see none) */
+  /* the last sgtd_consistent_loops call: device time of the pair pass and of the greedy passes, ms (only when timing is
+   * enabled, as the ms_ fields above), and the greedy rounds it took (a clique shortcut counts as one) */
+  float ms_consistency_pairs, ms_consistency_greedy;
+  int32_t consistency_rounds;
+  int32_t reserved3;
 } sgtd_stats;
 
 typedef struct sgtd_engine *sgtd_handle;
@@ -632,6 +637,73 @@ int sgtd_result_inlier_entries(sgtd_handle h, int q, int64_t *cand_off, int32_t 
  * Arrays of n_queries; any may be NULL.  Requires sgtd_verify. */
 int sgtd_search_loop(sgtd_handle h, double icp_threshold, int32_t *best_cand, int32_t *best_frame,
                      double *best_score);
+
+/* Pairwise consistency over a list of n loop closures ("edges"), on the device: two loops agree when the cycle "loop i,
+ * odometry, loop j back, odometry" closes within max_trans and max_rot; from the agreement graph a mutually consistent
+ * set is chosen greedily (largest remaining degree first).  Every stage before this one judges a loop alone; this one
+ * drops the loops that verify well against the wrong place (perceptual aliases), which agree with few others. */
+/* The rule.  All arithmetic is f64, every operation rounded once (no contraction); f32 inputs are widened exactly.  A
+ * pose X is (R, t); stored poses (sgtd_set_frame_poses) and pose_a rows are row-major 3x4 [R | t].
+ *   inv(X):    R'[r][c] = R[c][r];  t'[r] = -((R'[r][0]*t[0] + R'[r][1]*t[1]) + R'[r][2]*t[2])
+ *   mul(X, Y): R[r][c] = (Xr[r][0]*Yr[0][c] + Xr[r][1]*Yr[1][c]) + Xr[r][2]*Yr[2][c]
+ *              t[r]    = ((Xr[r][0]*Yt[0] + Xr[r][1]*Yt[1]) + Xr[r][2]*Yt[2]) + Xt[r]
+ * Per edge i: B_i = the stored pose of frame_b[i]; A_i = pose_a row i when pose_a is given, otherwise the stored pose of
+ * frame_a[i]; T_i = rel_pose row i; P_i = mul(B_i, T_i), the query's pose in the map's world as loop i sees it (what
+ * sgtd_result_world_poses reports, here in f64).  The a side and the b side may live in different world frames (odometry
+ * against the map): only relative motions on each side enter.  An edge is valid when both its poses exist and all 36
+ * numbers of B_i, A_i, T_i are finite; an id beyond the stored range has no pose, which is no error.
+ * Per pair i < j of valid edges: U = mul(inv(P_i), P_j); V = mul(inv(A_j), A_i); Z = mul(U, V);
+ *   d2 = (Zt[0]*Zt[0] + Zt[1]*Zt[1]) + Zt[2]*Zt[2];  tr = (Z[0][0] + Z[1][1]) + Z[2][2];
+ *   consistent iff d2 <= tt and tr >= min_trace, with tt = max_trans*max_trans and min_trace = 1.0 + 2.0*cos(max_rot),
+ *   both computed once on the host and handed back in thresholds[0], thresholds[1].  A NaN makes a comparison false.
+ * adj(i, j) = adj(j, i) = the decision of the pair taken with the lower index first; adj(i, i) = 0; an invalid edge has
+ * an empty row and column.
+ * Choice: P = the valid edges, C empty.  While P is not empty: d(u) = |adj(u) & P| for every u in P; v = the u with the
+ * largest d(u), the lowest index among equals; v is appended to C; P = P & adj(v).  C is a clique by construction; it is
+ * the greedy choice, not the maximum clique.  (The library shortcuts where the outcome is the rule's: when every d(u)
+ * equals |P| - 1 the rest of P joins C in ascending index order.)
+ * Results: in_set[i] = 1 for members of C, else 0; degree[i] = |adj(i)|, -1 for an invalid edge; pick[i] = the position
+ * at which i was appended to C (0, 1, ...), else -1; *n_set = |C|.  n == 0: nothing is done, *n_set = 0.  One valid
+ * edge: C is that edge.
+ * sgtd_result_consistency_rows gives rows first .. first + n_rows - 1 of the bit matrix adj, ceil(n / 64) words each:
+ * bit j of row i is bit j & 63 of word j >> 6; the padding bits are 0 (parity and diagnostics).
+ * The call is independent of the pending batch and of the table and changes no other result; a view (sgtd_attach_table)
+ * runs on its own poses whatever state its owner's table is in; a multi-device handle runs on its first device with
+ * the group handle's poses.  The work is issued on the handle's stream; the host waits once per group of greedy rounds
+ * (the rounds run on the device and fall through once P is empty).  The results last until the next
+ * sgtd_consistent_loops call or sgtd_destroy; a call that fails on the device, or with SGTD_ERR_UNSUPPORTED, drops them.
+ * Device memory: 8 * n * ceil(n / 64) bytes for the matrix (128 MB at SGTD_MAX_LOOP_EDGES) plus O(n): about 600 bytes an edge
+ * and the pose store's copy.
+ * h == NULL, n < 0, n_set == NULL, with n > 0: frame_b == NULL, rel_pose == NULL, or frame_a == NULL while
+ * pose_a == NULL; max_trans NaN, negative or infinite; max_rot NaN or outside [0, pi]: SGTD_ERR_INVALID, before the
+ * device is touched.  n > SGTD_MAX_LOOP_EDGES: SGTD_ERR_UNSUPPORTED (sgtd_last_error says so).  The result calls before
+ * a successful run: SGTD_ERR_STATE; rows outside [0, n] (or rows == NULL with n_rows > 0): SGTD_ERR_INVALID. */
+#define SGTD_MAX_LOOP_EDGES 32768
+int sgtd_consistent_loops(sgtd_handle h, int64_t n,
+                          const uint32_t *frame_a,   /* [n] the query-side frame of loop i            */
+                          const uint32_t *frame_b,   /* [n] the candidate (map-side) frame            */
+                          const double *rel_pose,    /* [n*12] rot row-major (9), t (3): x_b = R p_a + t,
+                                                        the layout of sgtd_result_verify / _refined / _aligned */
+                          const float *pose_a,       /* NULL, or [n*12] row-major 3x4 [R|t] used in place of
+                                                        the stored pose of frame_a (frame_a may then be NULL) */
+                          double max_trans, double max_rot /* radians */, int32_t *n_set);
+/* arrays of n; any pointer may be NULL */
+int sgtd_result_consistent(sgtd_handle h, int32_t *in_set /*[n]*/, int32_t *degree /*[n]*/,
+                           int32_t *pick /*[n]*/, double *thresholds /*[2]*/);
+int sgtd_result_consistency_rows(sgtd_handle h, int64_t first, int64_t n_rows, uint64_t *rows);
+/* The edges sgtd_consistent_loops takes, from the pending verified batch, in host code: one edge for every query q whose
+ * sgtd_search_loop choice is accepted at icp_threshold, in ascending q.  query = q; frame_a = the frame id the query's
+ * descriptors carry (c + q for a sgtd_loop_frames batch, current_frame_id_ otherwise); frame_b = the chosen candidate's
+ * frame; rel_pose = its sgtd_result_verify pose, with SGTD_LOOP_EDGES_REFINED its sgtd_result_refined pose
+ * (SGTD_ERR_STATE when sgtd_refine_poses has not run on the batch); score = its verify_score.  Arrays of `capacity`
+ * edges, any may be NULL; *n_edges = the number needed; more than capacity: SGTD_ERR_CAPACITY (the first `capacity`
+ * edges are written).  Works on a multi-device handle.  A session in chunks appends each chunk's edges on its side and
+ * runs one sgtd_consistent_loops over all of them.  h == NULL, n_edges == NULL, capacity < 0 or unknown flag bits:
+ * SGTD_ERR_INVALID; no verification of the pending batch yet: SGTD_ERR_STATE. */
+#define SGTD_LOOP_EDGES_REFINED 1
+int sgtd_result_loop_edges(sgtd_handle h, double icp_threshold, int flags,
+                           int32_t *query, uint32_t *frame_a, uint32_t *frame_b, double *rel_pose, double *score,
+                           int64_t capacity, int64_t *n_edges);
 
 /* One query frame through candidate_selector (STDesc.cpp:318-460), candidate_verify for every candidate (:462-571) and the
  * inlier pairs of every candidate with the table entries they name — what SearchLoop (:84-147) needs — in ONE call: the

@@ -35,6 +35,7 @@ SYMBOLS = [
     "sgtd_set_frame_keypoints", "sgtd_overlap", "sgtd_result_overlap", "sgtd_search_loop_overlap",
     "sgtd_align_keypoints", "sgtd_result_aligned", "sgtd_result_aligned_pairs", "sgtd_result_aligned_world_poses",
     "sgtd_search_loop_aligned",
+    "sgtd_consistent_loops", "sgtd_result_consistent", "sgtd_result_consistency_rows", "sgtd_result_loop_edges",
 ]
 
 
@@ -85,6 +86,7 @@ class Stats(C.Structure):
         ("tail_entries", C.c_int64), ("ms_finalize", C.c_float), ("reserved2", C.c_float),
         ("batches_total", C.c_int64), ("overflow_launches_total", C.c_int64), ("reruns_total", C.c_int64), ("rewrites_total", C.c_int64),
         ("list_moves_total", C.c_int64), ("last_list_moves", C.c_int64), ("device_allocs_total", C.c_int64),
+        ("ms_consistency_pairs", C.c_float), ("ms_consistency_greedy", C.c_float), ("consistency_rounds", C.c_int32), ("reserved3", C.c_int32),
     ]
 
 
@@ -165,6 +167,10 @@ def lib():
     L.sgtd_result_aligned_pairs.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp]
     L.sgtd_result_aligned_world_poses.argtypes = [vp, C.c_int, vp]
     L.sgtd_search_loop_aligned.argtypes = [vp, C.c_double, C.c_double, vp, vp, vp, vp]
+    L.sgtd_consistent_loops.argtypes = [vp, i64, vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(i32)]
+    L.sgtd_result_consistent.argtypes = [vp, vp, vp, vp, vp]
+    L.sgtd_result_consistency_rows.argtypes = [vp, i64, i64, vp]
+    L.sgtd_result_loop_edges.argtypes = [vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

@@ -722,6 +722,7 @@ int get_stats(sgtd_engine *e, sgtd_stats *out) {
     t.reruns_total += x.reruns_total; t.rewrites_total += x.rewrites_total;
     t.list_moves_total += x.list_moves_total; t.last_list_moves += x.last_list_moves;
     t.ms_total = std::max(t.ms_total, x.ms_total);
+    if (s == 0) { t.ms_consistency_pairs = x.ms_consistency_pairs; t.ms_consistency_greedy = x.ms_consistency_greedy; t.consistency_rounds = x.consistency_rounds; }   // (sgtd_consistent_loops runs on the first device)
   }
   if (g->merged) {
     const int cn = e->cfg.candidate_num;

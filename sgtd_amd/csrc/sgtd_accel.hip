@@ -30,6 +30,7 @@
 #include "refine_kernels.hip.h"
 #include "overlap_kernels.hip.h"
 #include "align_kernels.hip.h"
+#include "consistency_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -291,6 +292,14 @@ struct sgtd_engine {
   DevBuf a_pose, a_fit, a_cnt, a_val, a_mom, a_assign;
   std::vector<long long> a_qoff;
   bool aligned = false;
+  // sgtd_consistent_loops (consistency_kernels.hip.h): independent of the batch.  ck_store / ck_has: the pose store's
+  // device copy, made for ck_store_serial; ck_in: the call's inputs; ck_soa / ck_valid: the prepared edges; ck_rows: the
+  // bit matrix; ck_pmask, ck_out (in_set, degree, pick), ck_state: the greedy choice.  ck_n < 0: no results.
+  DevBuf ck_store, ck_has, ck_in, ck_soa, ck_valid, ck_rows, ck_pmask, ck_out, ck_state;
+  u64 ck_store_serial = ~0ull;
+  int64_t ck_n = -1;
+  double ck_thr[2] = {0.0, 0.0};
+  hipEvent_t ck_ev[3] = {};
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -2103,8 +2112,11 @@ int sgtd_destroy(sgtd_handle e) {
                     // handle kept them, 8 bytes per map frame and, with frame ids out of insertion order, 8 bytes per entry)
                     &e->frame_first, &e->by_frame, &e->id_of_g, &e->longest,
                     &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows,
-                    &e->pos_dev, &e->prior_dev, &e->filt_base};
+                    &e->pos_dev, &e->prior_dev, &e->filt_base,
+                    &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state};
   for (DevBuf *b : bufs) free_buf(*b);
+  for (hipEvent_t ev : e->ck_ev)
+    if (ev) (void)hipEventDestroy(ev);
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
@@ -4038,6 +4050,201 @@ int sgtd_table_dump(sgtd_handle e, int64_t *keys, int64_t *bucket_off, int64_t *
     for (int64_t p = 0; p < E; p++) entry_ids[p] = pm[p];
   }
   return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_consistent_loops: pairwise consistency over a list of loop closures and the greedy clique
+// (consistency_kernels.hip.h) ----
+namespace {
+// the engine whose device, stream and buffers the consistency pass uses: the handle's own, a group's first device's
+sgtd_engine *cons_engine(sgtd_engine *e) { return e->grp ? multi::device_handle(e, 0) : e; }
+
+// the pose store `owner` holds (its own handle's, or the group's), copied to c's device when it changed
+int cons_upload_store(sgtd_engine *c, const sgtd_engine *owner) {
+  if (c->ck_store.p && c->ck_store_serial == owner->poses_serial) return SGTD_OK;
+  const size_t n_ids = owner->has_pose.size();
+  CHK(ensure(c, c->ck_store, std::max<size_t>(n_ids, 1) * 12 * sizeof(float)));
+  CHK(ensure(c, c->ck_has, std::max<size_t>(n_ids, 1)));
+  CHK(h2d(c, c->ck_store.p, owner->poses.data(), n_ids * 12 * sizeof(float)));
+  CHK(h2d(c, c->ck_has.p, owner->has_pose.data(), n_ids));
+  CHK(xfer_sync(c));
+  c->ck_store_serial = owner->poses_serial;
+  return SGTD_OK;
+}
+
+int cons_run(sgtd_engine *c, const sgtd_engine *owner, int n, const uint32_t *frame_a, const uint32_t *frame_b, const double *rel_pose,
+             const float *pose_a, double tt, double min_trace, int32_t *n_set) {
+  sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
+  HIPCHK(hipSetDevice(c->cfg.device_id));
+  CHK(cons_upload_store(c, owner));
+  const u32 words = (u32)((n + 63) / 64);
+  const size_t ns = (size_t)words * 64;
+  // the call's inputs, back to back: rel_pose, pose_a, frame_b, frame_a
+  const size_t o_rel = 0, o_pa = o_rel + (size_t)n * 12 * sizeof(double), o_fb = o_pa + (pose_a ? (size_t)n * 12 * sizeof(float) : 0),
+               o_fa = o_fb + (size_t)n * sizeof(u32), in_bytes = o_fa + (frame_a ? (size_t)n * sizeof(u32) : 0);
+  CHK(ensure(c, c->ck_in, in_bytes));
+  CHK(ensure(c, c->ck_soa, (size_t)SGTD_CONS_STREAMS * ns * sizeof(double)));
+  CHK(ensure(c, c->ck_valid, ns));
+  CHK(ensure(c, c->ck_rows, (size_t)n * words * sizeof(u64)));
+  CHK(ensure(c, c->ck_pmask, (size_t)words * sizeof(u64)));
+  CHK(ensure(c, c->ck_out, (size_t)n * 3 * sizeof(int)));
+  CHK(ensure(c, c->ck_state, sizeof(ConsState)));
+  if (c->timing)
+    for (hipEvent_t &ev : c->ck_ev)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+  char *in = c->ck_in.as<char>();
+  CHK(h2d(c, in + o_rel, rel_pose, (size_t)n * 12 * sizeof(double)));
+  if (pose_a) CHK(h2d(c, in + o_pa, pose_a, (size_t)n * 12 * sizeof(float)));
+  CHK(h2d(c, in + o_fb, frame_b, (size_t)n * sizeof(u32)));
+  if (frame_a) CHK(h2d(c, in + o_fa, frame_a, (size_t)n * sizeof(u32)));
+
+  ConsPrepareParams pp;
+  pp.store = c->ck_store.as<float>(); pp.has = c->ck_has.as<unsigned char>(); pp.n_ids = (u32)owner->has_pose.size();
+  pp.frame_a = frame_a ? reinterpret_cast<const u32 *>(in + o_fa) : nullptr;
+  pp.frame_b = reinterpret_cast<const u32 *>(in + o_fb);
+  pp.rel = reinterpret_cast<const double *>(in + o_rel);
+  pp.pose_a = pose_a ? reinterpret_cast<const float *>(in + o_pa) : nullptr;
+  pp.n = n; pp.ns = ns; pp.soa = c->ck_soa.as<double>(); pp.valid = c->ck_valid.as<unsigned char>();
+  cons_prepare_kernel<<<grid_for(n, SGTD_CONS_THREADS), SGTD_CONS_THREADS, 0, c->stream>>>(pp);
+  HIPCHK(hipGetLastError());
+
+  if (c->timing) HIPCHK(hipEventRecord(c->ck_ev[0], c->stream));
+  ConsPairParams pr;
+  pr.soa = pp.soa; pr.ns = ns; pr.valid = pp.valid; pr.n = n; pr.words = words; pr.tt = tt; pr.min_trace = min_trace;
+  pr.rows = c->ck_rows.as<u64>();
+  const dim3 pgrid((words + SGTD_CONS_TILE / SGTD_WAVE - 1) / (SGTD_CONS_TILE / SGTD_WAVE), (u32)grid_for(n, SGTD_CONS_ROWS));
+  cons_pair_kernel<<<pgrid, SGTD_CONS_THREADS, 0, c->stream>>>(pr);
+  HIPCHK(hipGetLastError());
+  if (c->timing) HIPCHK(hipEventRecord(c->ck_ev[1], c->stream));
+
+  int *in_set = c->ck_out.as<int>(), *degree = in_set + n, *pick = degree + n;
+  ConsState *st = c->ck_state.as<ConsState>();
+  HIPCHK(hipMemsetAsync(st, 0, sizeof(ConsState), c->stream));
+  cons_init_kernel<<<grid_for((long long)words * SGTD_WAVE, SGTD_CONS_THREADS), SGTD_CONS_THREADS, 0, c->stream>>>(
+      pp.valid, n, words, c->ck_pmask.as<u64>(), in_set, degree, pick, st);
+  HIPCHK(hipGetLastError());
+  // rounds in groups that fall through once the choice is complete; the state is read once per group
+  const int cgrid = std::min(grid_for(n, SGTD_CONS_THREADS / SGTD_WAVE), 4 * c->n_cus);
+  ConsState host{};
+  int group = 16, rounds_sent = 0;
+  for (;;) {
+    for (int r = 0; r < group; r++) {
+      cons_count_kernel<<<cgrid, SGTD_CONS_THREADS, 0, c->stream>>>(pr.rows, c->ck_pmask.as<u64>(), n, words, degree, st);
+      cons_select_kernel<<<1, SGTD_CONS_SELECT_THREADS, 0, c->stream>>>(pr.rows, c->ck_pmask.as<u64>(), words, in_set, pick, st);
+    }
+    HIPCHK(hipGetLastError());
+    rounds_sent += group;
+    CHK(d2h(c, &host, st, sizeof(ConsState)));
+    if (c->timing) HIPCHK(hipEventRecord(c->ck_ev[2], c->stream));
+    CHK(xfer_sync(c));
+    if (host.done) break;
+    if (rounds_sent > n + 16) { c->err = "sgtd_consistent_loops: the greedy choice did not end"; return SGTD_ERR_HIP; }   // (a round removes its pick from P)
+    group = std::min(group * 2, 256);
+  }
+  c->stats.consistency_rounds = host.round;
+  c->stats.ms_consistency_pairs = c->stats.ms_consistency_greedy = 0.f;
+  if (c->timing) {
+    HIPCHK(hipEventElapsedTime(&c->stats.ms_consistency_pairs, c->ck_ev[0], c->ck_ev[1]));
+    HIPCHK(hipEventElapsedTime(&c->stats.ms_consistency_greedy, c->ck_ev[1], c->ck_ev[2]));
+  }
+  *n_set = host.n_set;
+  return SGTD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sgtd_consistent_loops(sgtd_handle e, int64_t n, const uint32_t *frame_a, const uint32_t *frame_b, const double *rel_pose,
+                          const float *pose_a, double max_trans, double max_rot, int32_t *n_set) {
+  if (!e || n < 0 || !n_set) return SGTD_ERR_INVALID;
+  if (n > 0 && (!frame_b || !rel_pose || (!frame_a && !pose_a))) return SGTD_ERR_INVALID;
+  if (!(max_trans >= 0.0) || std::isinf(max_trans)) return SGTD_ERR_INVALID;
+  if (!(max_rot >= 0.0 && max_rot <= 3.14159265358979323846)) return SGTD_ERR_INVALID;
+  sgtd_engine *c = cons_engine(e);
+  c->ck_n = -1;
+  if (n > SGTD_MAX_LOOP_EDGES) {
+    e->err = "sgtd_consistent_loops takes at most " + std::to_string(SGTD_MAX_LOOP_EDGES) + " edges in one call (" + std::to_string(n) + " given)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  PinScope pin_scope(c);
+  const double tt = max_trans * max_trans, min_trace = 1.0 + 2.0 * std::cos(max_rot);
+  *n_set = 0;
+  if (n > 0) {
+    const int st = cons_run(c, e, (int)n, frame_a, frame_b, rel_pose, pose_a, tt, min_trace, n_set);
+    if (st != SGTD_OK) {
+      if (c != e) e->err = c->err;
+      return st;
+    }
+  }
+  c->ck_thr[0] = tt; c->ck_thr[1] = min_trace;
+  c->ck_n = n;
+  return SGTD_OK;
+}
+
+int sgtd_result_consistent(sgtd_handle e, int32_t *in_set, int32_t *degree, int32_t *pick, double *thresholds) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = cons_engine(e);
+  PinScope pin_scope(c);
+  if (c->ck_n < 0) { e->err = "no consistency results: sgtd_consistent_loops has not run"; return SGTD_ERR_STATE; }
+  if (thresholds) { thresholds[0] = c->ck_thr[0]; thresholds[1] = c->ck_thr[1]; }
+  const size_t n = (size_t)c->ck_n;
+  if (n == 0) return SGTD_OK;
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  const int *d = c->ck_out.as<int>();
+  if (st == SGTD_OK && in_set) st = d2h(c, in_set, d, n * sizeof(int));
+  if (st == SGTD_OK && degree) st = d2h(c, degree, d + n, n * sizeof(int));
+  if (st == SGTD_OK && pick) st = d2h(c, pick, d + 2 * n, n * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK && c != e) e->err = c->err;
+  return st;
+}
+
+int sgtd_result_consistency_rows(sgtd_handle e, int64_t first, int64_t n_rows, uint64_t *rows) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = cons_engine(e);
+  if (c->ck_n < 0) { e->err = "no consistency results: sgtd_consistent_loops has not run"; return SGTD_ERR_STATE; }
+  if (first < 0 || n_rows < 0 || first > c->ck_n || n_rows > c->ck_n - first || (n_rows > 0 && !rows)) return SGTD_ERR_INVALID;
+  if (n_rows == 0) return SGTD_OK;
+  const size_t words = (size_t)((c->ck_n + 63) / 64);
+  hipError_t hs = hipSetDevice(c->cfg.device_id);
+  if (hs == hipSuccess) hs = hipMemcpyAsync(rows, c->ck_rows.as<u64>() + (size_t)first * words, (size_t)n_rows * words * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
+  if (hs == hipSuccess) hs = hipStreamSynchronize(c->stream);
+  if (hs != hipSuccess) { e->err = std::string("sgtd_result_consistency_rows: ") + hipGetErrorString(hs); return SGTD_ERR_HIP; }
+  return SGTD_OK;
+}
+
+int sgtd_result_loop_edges(sgtd_handle e, double icp_threshold, int flags, int32_t *query, uint32_t *frame_a, uint32_t *frame_b,
+                           double *rel_pose, double *score, int64_t capacity, int64_t *n_edges) {
+  if (!e || !n_edges || capacity < 0 || (flags & ~SGTD_LOOP_EDGES_REFINED)) return SGTD_ERR_INVALID;
+  const bool refined = (flags & SGTD_LOOP_EDGES_REFINED) != 0;
+  const bool have_v = e->grp ? (e->grp->batch_valid && e->grp->verified) : (e->batch_valid && e->verified);
+  if (!have_v) return needs(e, "sgtd_result_loop_edges", "sgtd_verify");
+  if (refined && !(e->grp ? e->grp->refined : e->refined)) return needs(e, "SGTD_LOOP_EDGES_REFINED", "sgtd_refine_poses");
+  const int nq = e->grp ? e->grp->nq : e->nq;
+  const size_t cn = (size_t)e->cfg.candidate_num;
+  std::vector<int32_t> cand((size_t)std::max(nq, 1)), frame((size_t)std::max(nq, 1));
+  std::vector<double> best((size_t)std::max(nq, 1)), pose(cn * 12);
+  CHK(sgtd_search_loop(e, icp_threshold, cand.data(), frame.data(), best.data()));
+  int64_t m = 0;
+  for (int q = 0; q < nq; q++) {
+    if (cand[(size_t)q] < 0) continue;
+    if (m < capacity) {
+      if (rel_pose) {
+        if (refined) CHK(sgtd_result_refined(e, q, pose.data(), nullptr, nullptr, nullptr, nullptr));
+        else CHK(sgtd_result_verify(e, q, nullptr, pose.data()));
+        std::memcpy(rel_pose + (size_t)m * 12, pose.data() + (size_t)cand[(size_t)q] * 12, 12 * sizeof(double));
+      }
+      if (query) query[m] = q;
+      // the frame id the query's descriptors carry: c + q for a sgtd_loop_frames batch, current_frame_id_ otherwise
+      if (frame_a) frame_a[m] = e->grp ? e->grp->current_frame_id : (e->last_kind == 1 ? e->last_qframe + (e->loop_batch ? (u32)q : 0u) : e->current_frame_id);
+      if (frame_b) frame_b[m] = (uint32_t)frame[(size_t)q];
+      if (score) score[m] = best[(size_t)q];
+    }
+    m++;
+  }
+  *n_edges = m;
+  return m > capacity ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_get_stats(sgtd_handle e, sgtd_stats *out) {

@@ -677,6 +677,69 @@ class STDescManager:
         self._check(self._L.sgtd_search_loop(self._h, float(icp_threshold), _p(bc), _p(bf), _p(bs)))
         return bc, bf, bs
 
+    def loop_edges(self, icp_threshold=None, refined=False):
+        """sgtd_result_loop_edges after verify(): one edge for every query whose search_loop choice is accepted, as a
+        dict of query [m] (int32), frame_a, frame_b [m] (uint32), rel_pose [m, 12] (rot row-major, t: result_verify's
+        pose of the chosen candidate, or result_refined's with refined=True) and score [m] -- what consistent_loops takes"""
+        if icp_threshold is None:
+            icp_threshold = self.icp_threshold_
+        flags = 1 if refined else 0
+        cap = max(int(getattr(self, "_nq", 0)), 1)
+        q = np.zeros(cap, np.int32)
+        fa = np.zeros(cap, np.uint32)
+        fb = np.zeros(cap, np.uint32)
+        rel = np.zeros((cap, 12), np.float64)
+        sc = np.zeros(cap, np.float64)
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_loop_edges(self._h, float(icp_threshold), flags, _p(q), _p(fa), _p(fb), _p(rel), _p(sc),
+                                                   cap, C.byref(n)))
+        m = n.value
+        return {"query": q[:m].copy(), "frame_a": fa[:m].copy(), "frame_b": fb[:m].copy(), "rel_pose": rel[:m].copy(),
+                "score": sc[:m].copy()}
+
+    def consistent_loops(self, frame_a, frame_b, rel_pose, max_trans, max_rot, pose_a=None):
+        """sgtd_consistent_loops: the pairwise-consistency graph of n loop closures and its greedy clique, on the device.
+        frame_a / frame_b: (n,) frame ids whose poses set_frame_poses holds (frame_a may be None when pose_a, (n, 12) rows
+        of the row-major 3x4 [R | t], gives the query side's poses); rel_pose: (n, 12) f64 as loop_edges returns them;
+        max_rot in radians.  -> dict of in_set, degree, pick [n] (int32), n_set and thresholds (tt, min_trace)"""
+        fb = np.ascontiguousarray(frame_b, np.uint32).reshape(-1)
+        n = fb.size
+        rel = np.ascontiguousarray(rel_pose, np.float64).reshape(-1, 12)
+        if rel.shape[0] != n:
+            raise ValueError("rel_pose: (n, 12), one row per edge")
+        fa = None
+        if frame_a is not None:
+            fa = np.ascontiguousarray(frame_a, np.uint32).reshape(-1)
+            if fa.size != n:
+                raise ValueError("frame_a: one id per edge")
+        pa = None
+        if pose_a is not None:
+            pa = np.asarray(pose_a)
+            if pa.ndim == 3 and pa.shape[1:] == (4, 4):
+                pa = pa[:, :3, :]
+            pa = np.ascontiguousarray(pa, np.float32).reshape(-1, 12)
+            if pa.shape[0] != n:
+                raise ValueError("pose_a: (n, 12) rows or (n, 4, 4) matrices, one per edge")
+        n_set = C.c_int32(0)
+        self._check(self._L.sgtd_consistent_loops(self._h, n, None if fa is None else _p(fa), _p(fb), _p(rel),
+                                                  None if pa is None else _p(pa), float(max_trans), float(max_rot),
+                                                  C.byref(n_set)))
+        self._cons_n = n
+        in_set = np.zeros(n, np.int32)
+        degree = np.zeros(n, np.int32)
+        pick = np.zeros(n, np.int32)
+        thr = np.zeros(2, np.float64)
+        self._check(self._L.sgtd_result_consistent(self._h, _p(in_set), _p(degree), _p(pick), _p(thr)))
+        return {"in_set": in_set, "degree": degree, "pick": pick, "n_set": n_set.value, "thresholds": thr}
+
+    def consistency_rows(self):
+        """the bit matrix of the last consistent_loops call: (n, ceil(n / 64)) uint64, bit j of row i = bit j & 63 of word
+        j >> 6 (parity and diagnostics)"""
+        n = getattr(self, "_cons_n", 0)
+        rows = np.zeros((n, (n + 63) // 64), np.uint64)
+        self._check(self._L.sgtd_result_consistency_rows(self._h, 0, n, _p(rows)))
+        return rows
+
     def overlap(self, radius, refined=False, xyz=None, label=None, kp_off=None):
         """sgtd_overlap after verify(): under every verified candidate's relative pose (refined=True: refine_poses()'s),
         how many of the query's keypoints land within `radius` of a keypoint of the same label of the candidate's frame
