@@ -130,6 +130,112 @@ def greedy(adj, valid, shortcut=False):
     return in_set, degree, pick, n_set
 
 
+def adjacency_rows(P, A, valid, tt, min_trace, rows, block=16):
+    """the rule for the rows `rows` only -> (adj, gap_d2, gap_tr), each (len(rows), n): entry (k, j) is the decision of the
+    pair (rows[k], j) taken with the lower index first, as adjacency() gives it after mirroring; the gaps are those of the
+    ordered pair, +inf on the diagonal and for invalid edges"""
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    n = valid.size
+    adj = np.zeros((rows.size, n), bool)
+    gap_d2 = np.full((rows.size, n), np.inf)
+    gap_tr = np.full((rows.size, n), np.inf)
+    iP, iA = inv(P), inv(A)
+    col = lambda X: (X[0][None, :], X[1][None, :])                      # noqa: E731
+    with np.errstate(all="ignore"):
+        for k0 in range(0, rows.size, block):
+            r = rows[k0:k0 + block]
+            row = lambda X: (X[0][r, None], X[1][r, None])              # noqa: E731
+            col_hi = r[:, None] < np.arange(n)[None, :]
+            d2 = np.empty((r.size, n))
+            tr = np.empty((r.size, n))
+            for row_is_lo in (True, False):
+                if row_is_lo:
+                    U, V = mul(row(iP), col(P)), mul(col(iA), row(A))      # mul(inv(P_row), P_col), mul(inv(A_col), A_row)
+                else:
+                    U, V = mul(col(iP), row(P)), mul(row(iA), col(A))
+                Zr, Zt = mul(U, V)
+                take = col_hi == row_is_lo
+                d2[take] = ((Zt[..., 0] * Zt[..., 0] + Zt[..., 1] * Zt[..., 1]) + Zt[..., 2] * Zt[..., 2])[take]
+                tr[take] = ((Zr[..., 0, 0] + Zr[..., 1, 1]) + Zr[..., 2, 2])[take]
+            pair = (r[:, None] != np.arange(n)[None, :]) & valid[r, None] & valid[None, :]
+            adj[k0:k0 + block] = (d2 <= tt) & (tr >= min_trace) & pair
+            gap_d2[k0:k0 + block] = np.where(pair, np.abs(d2 - tt), np.inf)
+            gap_tr[k0:k0 + block] = np.where(pair, np.abs(tr - min_trace), np.inf)
+    return adj, gap_d2, gap_tr
+
+
+GREEDY_PARTS = dict(tie_high=False, total_degree=False, col_limit=None, row_limit=None, no_wave_prefix=False, psize_limit=None)
+WAVE_BITS = 64 * 64      # the columns whose words one wave of the library's select pass owns
+
+
+def greedy_fast(adj, valid, shortcut=False, parts=None):
+    """the choice with the degrees kept incrementally -> (in_set, degree, pick, n_set, rounds); adj symmetric.  rounds is
+    what consistency_rounds reports: one per pick, one for the shortcut when it fires (shortcut=True).
+    parts replaces pieces of the rule, for the mutants of tests/_consistency_edges.py (None: the rule itself):
+      tie_high        the highest index among equal degrees
+      total_degree    after round 0 the choice looks at the edge's degree, not at d(u) inside P
+      col_limit       d(u) counts the columns below col_limit only
+      row_limit       the rows u >= row_limit are never counted (no candidates, no degree)
+      no_wave_prefix  the shortcut's positions start again at |C| in every block of WAVE_BITS columns
+      psize_limit     after a pick |P| is taken over the columns below psize_limit only"""
+    p = dict(GREEDY_PARTS, **(parts or {}))
+    n = valid.size
+    idx_all = np.arange(n)
+    in_set = np.zeros(n, np.int32)
+    pick = np.full(n, -1, np.int32)
+    degree = np.full(n, -1, np.int32)
+    cols = np.ones(n, bool) if p["col_limit"] is None else idx_all < p["col_limit"]
+    rows_ok = np.ones(n, bool) if p["row_limit"] is None else idx_all < p["row_limit"]
+    P = np.asarray(valid, bool).copy()
+    counted = P & cols
+    D = np.count_nonzero(adj, axis=1) if counted.all() else np.count_nonzero(adj[np.flatnonzero(counted)], axis=0)
+    D = D.astype(np.int64)
+    deg0 = D.copy()
+    psize = int(P.sum())
+    n_set = rounds = 0
+    while psize > 0:
+        cand = P & rows_ok
+        if rounds == 0:
+            degree[cand] = D[cand]
+        if not cand.any():
+            break
+        key = np.where(cand, deg0 if (p["total_degree"] and rounds > 0) else D, -1)
+        if shortcut and int(np.count_nonzero(key == psize - 1)) == psize:
+            members = np.flatnonzero(P)
+            rank = np.arange(members.size)
+            if p["no_wave_prefix"]:
+                blk = members // WAVE_BITS
+                rank = rank - np.searchsorted(blk, blk, side="left")
+            pick[members] = n_set + rank
+            in_set[members] = 1
+            n_set += psize
+            rounds += 1
+            break
+        v = int(n - 1 - np.argmax(key[::-1])) if p["tie_high"] else int(np.argmax(key))
+        pick[v] = n_set
+        in_set[v] = 1
+        n_set += 1
+        rounds += 1
+        new_P = P & adj[v]
+        gone = np.flatnonzero(P & ~new_P & cols)
+        left = np.flatnonzero(new_P & cols)
+        if gone.size <= left.size:
+            D -= np.count_nonzero(adj[gone], axis=0)
+        else:
+            D = np.zeros(n, np.int64)
+            members = np.flatnonzero(new_P)
+            D[members] = np.count_nonzero(adj[np.ix_(members, left)], axis=1)
+        P = new_P
+        psize = int(P.sum()) if p["psize_limit"] is None else int(P[:p["psize_limit"]].sum())
+    return in_set, degree, pick, n_set, rounds
+
+
+def unpack_rows(rows, n):
+    """the inverse of pack_rows: (n, ceil(n / 64)) uint64 -> (n, n) bool (the padding bits are dropped)"""
+    bits = np.unpackbits(np.ascontiguousarray(rows, "<u8").view(np.uint8).reshape(rows.shape[0], -1), axis=1, bitorder="little")
+    return bits[:, :n].astype(bool)
+
+
 def pack_rows(adj):
     """(n, n) bool -> (n, ceil(n / 64)) uint64: bit j of row i = bit j & 63 of word j >> 6, padding bits 0"""
     n = adj.shape[0]
