@@ -705,6 +705,111 @@ int sgtd_result_loop_edges(sgtd_handle h, double icp_threshold, int flags,
                            int32_t *query, uint32_t *frame_a, uint32_t *frame_b, double *rel_pose, double *score,
                            int64_t capacity, int64_t *n_edges);
 
+/* Pose-graph relaxation on the device: the trajectory that honours a set of relative-pose measurements ("edges"), the
+ * last stage behind sgtd_consistent_loops.  A generic graph in caller arrays: n_nodes poses X_v (pose0 holds the start,
+ * row-major 3x4 [R | t]), n_edges measurements Z_k ~ inv(X_i) X_j between nodes i = node_i[k] and j = node_j[k] in the
+ * rel_pose layout (rot row-major (9), t (3)), weights w_trans[k], w_rot[k] (NULL = 1.0 each), and held nodes
+ * (fixed[v] != 0; fixed == NULL holds node 0 alone).  Orientation, as for sgtd_consistent_loops: a loop edge (frame_a,
+ * frame_b, T with x_b = R p_a + t) is i = frame_b's node, j = frame_a's node, Z = T; an odometry edge between
+ * consecutive frames with poses A_k, A_k+1 is i = k, j = k + 1, Z = mul(inv(A_k), A_k+1).
+ * The two uses:
+ *   a session closed against itself: nodes = its frames, pose0 = its odometry, edges = the odometry edges and the loops
+ *     sgtd_consistent_loops kept, node 0 held (fixed == NULL): the result is the odometry with its drift pulled out;
+ *   a session against a fixed map: nodes = the map frames the loops name, held at their stored poses B, and the query
+ *     frames, free, started from P = mul(B, T) of one loop carried along the odometry (P_k+1 = mul(P_k, mul(inv(A_k),
+ *     A_k+1))); edges = the odometry edges and the loops: the result is the session's trajectory in the map's world.
+ * The rule.  All arithmetic is f64, every operation (+, -, *, /, sqrt) rounded once, no contraction, nothing else is
+ * used; inv() and mul() are those of sgtd_consistent_loops.
+ *   QUAT(R) -> q = (w, x, y, z): tr = (R00 + R11) + R22;
+ *     tr > 0:                         s = sqrt(tr + 1.0) * 2.0;                 q = (0.25*s, (R21-R12)/s, (R02-R20)/s, (R10-R01)/s)
+ *     else R00 > R11 and R00 > R22:   s = sqrt(((1.0 + R00) - R11) - R22) * 2.0;  q = ((R21-R12)/s, 0.25*s, (R01+R10)/s, (R02+R20)/s)
+ *     else R11 > R22:                 s = sqrt(((1.0 + R11) - R00) - R22) * 2.0;  q = ((R02-R20)/s, (R01+R10)/s, 0.25*s, (R12+R21)/s)
+ *     else:                           s = sqrt(((1.0 + R22) - R00) - R11) * 2.0;  q = ((R10-R01)/s, (R02+R20)/s, (R12+R21)/s, 0.25*s)
+ *     then UNIT(q): nn = ((w*w + x*x) + y*y) + z*z; every component divided by sqrt(nn).
+ *   ROT(q): R00 = 1.0 - 2.0*(y*y + z*z); R01 = 2.0*(x*y - w*z); R02 = 2.0*(x*z + w*y);
+ *           R10 = 2.0*(x*y + w*z); R11 = 1.0 - 2.0*(x*x + z*z); R12 = 2.0*(y*z - w*x);
+ *           R20 = 2.0*(x*z - w*y); R21 = 2.0*(y*z + w*x); R22 = 1.0 - 2.0*(x*x + y*y).
+ *   M v and M^T v of a 3x3 M: (M v)[r] = (M[r][0]*v[0] + M[r][1]*v[1]) + M[r][2]*v[2]; M^T v the same over M[.][r];
+ *   |v|2 = (v[0]*v[0] + v[1]*v[1]) + v[2]*v[2].
+ *   SUM over elements e = 0, 1, ...: SGTD_RELAX_SUM_W accumulators start at +0.0, element e is added to accumulator
+ *     e mod W in ascending e, then acc[l] = acc[l] + acc[l + s] for l < s, s = W/2, W/4, ..., 1; the sum is acc[0].
+ *     MAX the same with m = v > m ? v : m.  DOT(u, v) over node vectors = SUM of u[e]*v[e], e = 6*node + a.
+ * State of node v: q_v = QUAT(R of pose0 row v), t_v, R_v = ROT(q_v) (what every residual uses, held nodes included).
+ * Residual of edge k = (i, j): D = mul(inv(X_i), X_j) with X = (R_v, t_v); E = mul(inv(Z_k), D); r_t = E's translation;
+ *   q_E = QUAT(E's rotation), its (x, y, z) negated when its w < 0; r_R = 2.0 * that (no angle is taken: monotone up to
+ *   180 degrees).  ct_k = w_trans[k] * |r_t|2, cr_k = w_rot[k] * |r_R|2 (the two numbers sgtd_result_relaxed gives per
+ *   edge), c_k = ct_k + cr_k, cost = SUM of c_k over the edges.
+ * Linearisation at the current state, right-multiplicative (X_v <- X_v (dR, dt): t_v += R_v dt, q_v <- UNIT(q_v (x)
+ * (1, dtheta/2))), with the usual first-order pose-graph blocks, exact at zero rotational residual: with A = the
+ * rotation of inv(Z_k), u = D's translation, B = A [u]x (B[r][0] = A[r][1]*u[2] - A[r][2]*u[1]; B[r][1] = A[r][2]*u[0]
+ * - A[r][0]*u[2]; B[r][2] = A[r][0]*u[1] - A[r][1]*u[0]), E_R and D_R the rotations of E and D:
+ *   d r_t / d(dt_i) = -A;  d r_t / d(dtheta_i) = B;  d r_t / d(dt_j) = E_R;  d r_R / d(dtheta_i) = -D_R^T;
+ *   d r_R / d(dtheta_j) = I; the other blocks are 0.
+ *   J^T y of one edge, y = (y_t, y_R): to node i ( -(A^T y_t), (B^T y_t) - (D_R y_R) ), to node j ( E_R^T y_t, y_R ).
+ *   GATHER(y) of a free node: from +0.0, its incident edges' shares added in ascending edge index; of a held node: 0.
+ *   g = GATHER(w_trans r_t, w_rot r_R).  H_vv[a][b] = from +0.0, over the incident edges in ascending index and the
+ *   edge's six residual rows r in ascending order, + (w_r * J[r][a]) * J[r][b], J the edge's 6x6 block for this node
+ *   (rows r_t, r_R; columns dt, dtheta; zeros and the identity written out), w_r = w_trans for r < 3, else w_rot.
+ * Step: (H + lambda diag-blocks(H)) x = -g by preconditioned CG.  M_v = H_vv + lambda*H_vv elementwise = L L^T, column
+ *   c = 0..5: s = M[c][c] - L[c][0]^2 - ... - L[c][c-1]^2 (subtracted in that order), L[c][c] = sqrt(s), below it
+ *   L[r][c] = (M[r][c] - L[r][0]*L[c][0] - ...) / L[c][c]; a node is solvable when it is free and every s > 0.
+ *   z = M^-1 r: y[a] = (r[a] - L[a][0]*y[0] - ...) / L[a][a], a = 0..5; z[a] = (y[a] - L[a+1][a]*z[a+1] - ... -
+ *   L[5][a]*z[5]) / L[a][a], a = 5..0; z = 0 for a node that is not solvable: it does not move (an isolated free node).
+ *   The block is taken whole: a free node all of whose edges have w_rot == 0 (or all w_trans == 0) has a singular
+ *   block and does not move either, not even in the part its edges do determine; give such edges a small weight.
+ *   r = -g (0 for held nodes), x = 0, p = 0, z = M^-1 r, rz = rz0 = DOT(r, z), beta = 0.  rz0 > 0 fails: the solve ends
+ *   "converged" at once (a zero gradient; no iteration is counted).  Up to max_inner times: p = z + beta*p;
+ *   Ap: per edge e_t = ((B b_i) - (A a_i)) + (E_R a_j), e_R = b_j - (D_R^T b_i) with p_v = (a_v, b_v), y = (w_trans e_t,
+ *   w_rot e_R), Ap_v = GATHER(y)_v + lambda*(H_vv p_v) ((H p)[a] summed left to right over b; 0 for held nodes);
+ *   pq = DOT(p, Ap); pq > 0 fails: CG ends; alpha = rz/pq; x = x + alpha*p; r = r - alpha*Ap; z = M^-1 r; rz' = DOT(r, z);
+ *   one CG iteration is counted; rz' <= (cg_tol*cg_tol)*rz0: CG ends; beta = rz'/rz; rz = rz'.
+ * Trial: every solvable node moves by x_v = (dt, dtheta): t' = (R_v dt) + t_v; h = 0.5*dtheta;
+ *   w' = ((w - x*h0) - y*h1) - z*h2;  x' = ((x + w*h0) + y*h2) - z*h1;  y' = ((y + w*h1) + z*h0) - x*h2;
+ *   z' = ((z + w*h2) + x*h1) - y*h0;  q' = UNIT(..), R' = ROT(q'); every other node keeps its state bit for bit.
+ *   cost' = the cost at the trial state; maxd = MAX of |x[e]|.  One outer iteration is counted.
+ *   cost' < cost: the trial becomes the state, lambda = max(lambda/3.0, lambda_min), and maxd <= step_tol ends the solve
+ *   "converged"; otherwise the state stays, lambda = 3.0*lambda, and lambda > lambda_max ends it "damping limit".
+ *   Otherwise max_outer iterations end it "outer limit".  So cost_after <= cost_before always; when no step is accepted
+ *   the poses are the start's state (R = ROT(QUAT(.)) of pose0, its t), cost_after = cost_before and the edge costs are
+ *   the start's.  Every node held: the cost is evaluated, status "nothing free".
+ * Results: pose row v = [R_v | t_v] of the final state; edge_cost[2k], [2k+1] = ct_k, cr_k there.
+ * The call is a pure function of its arguments: independent of the pending batch, the table and the stored poses; a
+ * view runs whatever state its owner's table is in; a multi-device handle runs on its first device.  The work is issued
+ * on the handle's stream; every decision is taken on the device, the host enqueues SGTD_RELAX_GROUP outer iterations at a
+ * time and reads the state once per group.  The results last until the next successful or device-failed
+ * sgtd_relax_poses call or sgtd_destroy.  Device memory: about 1 KB a node and 500 bytes an edge.
+ * h == NULL, a negative count, with a positive count: pose0, node_i, node_j or meas NULL; a node index outside
+ * [0, n_nodes), node_i[k] == node_j[k]; a non-finite pose0, meas or weight, a negative weight; an option that is not
+ * finite and > 0: SGTD_ERR_INVALID, before the device is touched and with the earlier results kept.  More than
+ * SGTD_RELAX_MAX_NODES nodes or SGTD_RELAX_MAX_EDGES edges: SGTD_ERR_UNSUPPORTED.  n_nodes == 0 or n_edges == 0: nothing
+ * is done, the report is "nothing free" with zero costs and lambda_init, and sgtd_result_relaxed then writes nothing
+ * (with n_nodes > 0 and no edge too: no pose comes back, the caller keeps pose0).
+ * sgtd_result_relaxed before a successful run: SGTD_ERR_STATE; either of its arrays may be NULL. */
+#define SGTD_RELAX_SUM_W 1024
+#define SGTD_RELAX_GROUP 4
+#define SGTD_RELAX_MAX_NODES (1 << 22)
+#define SGTD_RELAX_MAX_EDGES (1 << 22)
+enum { SGTD_RELAX_CONVERGED = 0, SGTD_RELAX_OUTER_LIMIT = 1, SGTD_RELAX_DAMPING_LIMIT = 2, SGTD_RELAX_NOTHING_FREE = 3 };
+typedef struct sgtd_relax_options {
+  int32_t max_outer;      /* outer (Levenberg-Marquardt) iterations, default 50 */
+  int32_t max_inner;      /* CG iterations per outer iteration, default 64      */
+  double lambda_init;     /* 1e-4 */
+  double lambda_min;      /* 1e-9 */
+  double lambda_max;      /* 1e9  */
+  double cg_tol;          /* 1e-4: CG ends when r^T z <= cg_tol^2 * its start   */
+  double step_tol;        /* 1e-6: metres and radians                           */
+} sgtd_relax_options;
+typedef struct sgtd_relax_report {
+  double cost_before, cost_after, lambda;      /* lambda: the damping the solve ended with */
+  int32_t outer_iterations, steps_accepted, cg_iterations, status;
+} sgtd_relax_report;
+void sgtd_default_relax_options(sgtd_relax_options *opt);
+int sgtd_relax_poses(sgtd_handle h, int64_t n_nodes, const double *pose0, const uint8_t *fixed,
+                     int64_t n_edges, const int32_t *node_i, const int32_t *node_j, const double *meas,
+                     const double *w_trans, const double *w_rot,
+                     const sgtd_relax_options *opt /* NULL = defaults */, sgtd_relax_report *report /* may be NULL */);
+int sgtd_result_relaxed(sgtd_handle h, double *pose /*[n*12]*/, double *edge_cost /*[m*2]: trans, rot*/);
+
 /* One query frame through candidate_selector (STDesc.cpp:318-460), candidate_verify for every candidate (:462-571) and the
  * inlier pairs of every candidate with the table entries they name — what SearchLoop (:84-147) needs — in ONE call: the
  * reference's one-frame-per-call pattern (semantic_graph_localization.cpp:590-603).  Equal, value for value, to

@@ -36,6 +36,7 @@ SYMBOLS = [
     "sgtd_align_keypoints", "sgtd_result_aligned", "sgtd_result_aligned_pairs", "sgtd_result_aligned_world_poses",
     "sgtd_search_loop_aligned",
     "sgtd_consistent_loops", "sgtd_result_consistent", "sgtd_result_consistency_rows", "sgtd_result_loop_edges",
+    "sgtd_default_relax_options", "sgtd_relax_poses", "sgtd_result_relaxed",
 ]
 
 
@@ -88,6 +89,18 @@ class Stats(C.Structure):
         ("list_moves_total", C.c_int64), ("last_list_moves", C.c_int64), ("device_allocs_total", C.c_int64),
         ("ms_consistency_pairs", C.c_float), ("ms_consistency_greedy", C.c_float), ("consistency_rounds", C.c_int32), ("reserved3", C.c_int32),
     ]
+
+
+class RelaxOptions(C.Structure):
+    """sgtd_relax_options"""
+    _fields_ = [("max_outer", C.c_int32), ("max_inner", C.c_int32), ("lambda_init", C.c_double), ("lambda_min", C.c_double),
+                ("lambda_max", C.c_double), ("cg_tol", C.c_double), ("step_tol", C.c_double)]
+
+
+class RelaxReport(C.Structure):
+    """sgtd_relax_report"""
+    _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("lambda_", C.c_double),
+                ("outer_iterations", C.c_int32), ("steps_accepted", C.c_int32), ("cg_iterations", C.c_int32), ("status", C.c_int32)]
 
 
 def build_library(force=False):
@@ -171,6 +184,10 @@ def lib():
     L.sgtd_result_consistent.argtypes = [vp, vp, vp, vp, vp]
     L.sgtd_result_consistency_rows.argtypes = [vp, i64, i64, vp]
     L.sgtd_result_loop_edges.argtypes = [vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_default_relax_options.argtypes = [C.POINTER(RelaxOptions)]
+    L.sgtd_default_relax_options.restype = None
+    L.sgtd_relax_poses.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, C.POINTER(RelaxOptions), C.POINTER(RelaxReport)]
+    L.sgtd_result_relaxed.argtypes = [vp, vp, vp]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

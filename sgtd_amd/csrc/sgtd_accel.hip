@@ -31,6 +31,7 @@
 #include "overlap_kernels.hip.h"
 #include "align_kernels.hip.h"
 #include "consistency_kernels.hip.h"
+#include "relax_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -300,6 +301,16 @@ struct sgtd_engine {
   int64_t ck_n = -1;
   double ck_thr[2] = {0.0, 0.0};
   hipEvent_t ck_ev[3] = {};
+  // sgtd_relax_poses (relax_kernels.hip.h): independent of the batch.  rx_in: the call's inputs and the node -> edge CSR;
+  // rx_state: the two sets of node records; rx_edge: the per-edge streams and costs; rx_node: the node vectors, blocks
+  // and factors; rx_ctl: RelaxState.  rx_n < 0: no results; rx_host_*: the sources of the uploads the host makes.
+  DevBuf rx_in, rx_state, rx_edge, rx_node, rx_ctl;
+  int64_t rx_n = -1, rx_m = 0;
+  int rx_cur = 0;
+  int rx_max_blocks = 0;      // SGTD_RELAX_MAX_BLOCKS (test hook, read at the handle's first run): the grid cap of its kernels
+  std::vector<int> rx_host_csr;
+  std::vector<double> rx_host_w;
+  std::vector<unsigned char> rx_host_held;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -2113,7 +2124,8 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->frame_first, &e->by_frame, &e->id_of_g, &e->longest,
                     &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows,
                     &e->pos_dev, &e->prior_dev, &e->filt_base,
-                    &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state};
+                    &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state,
+                    &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl};
   for (DevBuf *b : bufs) free_buf(*b);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
@@ -4258,6 +4270,215 @@ int sgtd_get_stats(sgtd_handle e, sgtd_stats *out) {
   e->stats.ms_finalize = e->ms_finalize;
   e->stats.tail_entries = e->n_seg > 1 ? e->seg[1].g1 - e->seg[1].g0 : 0;
   *out = e->stats;
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_relax_poses: pose-graph relaxation (relax_kernels.hip.h) ----
+namespace {
+static_assert(SGTD_RELAX_W == SGTD_RELAX_SUM_W, "relax_ctl_kernel's accumulators are the header's");
+size_t relax_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// rx_edge, in f64: iz 12, jac 27, y 6 streams of ms = m rounded up to 64, then csum [m], then ec [2][m][2]
+struct RelaxEdgeLayout {
+  size_t ms, iz, jac, y, csum, ec, total;
+  explicit RelaxEdgeLayout(size_t m) : ms((m + 63) & ~(size_t)63), iz(0), jac(12 * ms), y(39 * ms), csum(45 * ms), ec(45 * ms + m), total(45 * ms + 5 * m) {}
+  size_t ec_of(int set, size_t m) const { return ec + (size_t)set * m * 2; }
+};
+
+int relax_run(sgtd_engine *c, int n, const double *pose0, const uint8_t *fixed, int m, const int32_t *node_i, const int32_t *node_j,
+              const double *meas, const double *w_trans, const double *w_rot, const sgtd_relax_options &o, bool all_held, RelaxState *out) {
+  sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
+  HIPCHK(hipSetDevice(c->cfg.device_id));
+  const RelaxEdgeLayout lay((size_t)m);
+  const size_t ms = lay.ms;
+  // the node -> edge CSR, the entries of a node in ascending edge index: off [n + 1], then ent [2 m]
+  std::vector<int> &csr = c->rx_host_csr;
+  csr.assign((size_t)n + 1 + 2 * (size_t)m, 0);
+  int *off = csr.data(), *ent = off + n + 1;
+  for (int k = 0; k < m; k++) { off[node_i[k] + 1]++; off[node_j[k] + 1]++; }
+  for (int v = 0; v < n; v++) off[v + 1] += off[v];
+  {
+    std::vector<int> at(off, off + n);
+    for (int k = 0; k < m; k++) { ent[at[(size_t)node_i[k]]++] = k << 1; ent[at[(size_t)node_j[k]]++] = (k << 1) | 1; }
+  }
+  std::vector<double> &w = c->rx_host_w;
+  w.resize(2 * (size_t)m);
+  for (int k = 0; k < m; k++) { w[(size_t)k] = w_trans ? w_trans[k] : 1.0; w[(size_t)m + k] = w_rot ? w_rot[k] : 1.0; }
+  std::vector<unsigned char> &held = c->rx_host_held;
+  held.resize((size_t)n);
+  for (int v = 0; v < n; v++) held[(size_t)v] = fixed ? (fixed[v] != 0) : (v == 0);
+
+  // inputs, back to back (each at a 256-byte boundary): pose0, meas, weights, node_i, node_j, csr, held
+  const size_t o_pose = 0, o_meas = o_pose + relax_up((size_t)n * 12 * sizeof(double)), o_w = o_meas + relax_up((size_t)m * 12 * sizeof(double)),
+               o_i = o_w + relax_up(2 * (size_t)m * sizeof(double)), o_j = o_i + relax_up((size_t)m * sizeof(int)),
+               o_csr = o_j + relax_up((size_t)m * sizeof(int)), o_held = o_csr + relax_up(csr.size() * sizeof(int)),
+               in_bytes = o_held + relax_up((size_t)n);
+  // per-node: r x p z ap [n][6], H L [n][36], ok [n]
+  const size_t edge_bytes = lay.total * sizeof(double);
+  const size_t node_bytes = (size_t)n * (30 + 72) * sizeof(double) + (size_t)n;
+  CHK(ensure(c, c->rx_in, in_bytes));
+  CHK(ensure(c, c->rx_state, 2 * (size_t)n * SGTD_RELAX_REC * sizeof(double)));
+  CHK(ensure(c, c->rx_edge, edge_bytes));
+  CHK(ensure(c, c->rx_node, node_bytes));
+  CHK(ensure(c, c->rx_ctl, sizeof(RelaxState)));
+  char *in = c->rx_in.as<char>();
+  CHK(h2d(c, in + o_pose, pose0, (size_t)n * 12 * sizeof(double)));
+  CHK(h2d(c, in + o_meas, meas, (size_t)m * 12 * sizeof(double)));
+  CHK(h2d(c, in + o_w, w.data(), w.size() * sizeof(double)));
+  CHK(h2d(c, in + o_i, node_i, (size_t)m * sizeof(int)));
+  CHK(h2d(c, in + o_j, node_j, (size_t)m * sizeof(int)));
+  CHK(h2d(c, in + o_csr, csr.data(), csr.size() * sizeof(int)));
+  CHK(h2d(c, in + o_held, held.data(), (size_t)n));
+
+  RelaxParams P;
+  P.n = n; P.m = m; P.ms = ms;
+  P.state = c->rx_state.as<double>();
+  P.held = reinterpret_cast<const unsigned char *>(in + o_held);
+  P.ei = reinterpret_cast<const int *>(in + o_i); P.ej = reinterpret_cast<const int *>(in + o_j);
+  P.wt = reinterpret_cast<const double *>(in + o_w); P.wr = P.wt + m;
+  double *eb = c->rx_edge.as<double>();
+  P.iz = eb + lay.iz; P.jac = eb + lay.jac; P.y = eb + lay.y; P.csum = eb + lay.csum; P.ec = eb + lay.ec;
+  P.off = reinterpret_cast<const int *>(in + o_csr); P.ent = P.off + n + 1;
+  P.r = c->rx_node.as<double>(); P.x = P.r + (size_t)n * 6; P.p = P.x + (size_t)n * 6; P.z = P.p + (size_t)n * 6; P.ap = P.z + (size_t)n * 6;
+  P.H = P.ap + (size_t)n * 6; P.L = P.H + (size_t)n * 36;
+  P.ok = reinterpret_cast<unsigned char *>(P.L + (size_t)n * 36);
+  P.st = c->rx_ctl.as<RelaxState>();
+  P.lmin = o.lambda_min; P.lmax = o.lambda_max; P.tol2 = o.cg_tol * o.cg_tol; P.step_tol = o.step_tol;
+  P.max_outer = o.max_outer; P.all_held = all_held ? 1 : 0;
+
+  RelaxState host{};
+  host.lambda = o.lambda_init;
+  CHK(h2d(c, P.st, &host, sizeof(RelaxState)));
+  if (c->rx_max_blocks == 0) {
+    const char *hook = getenv("SGTD_RELAX_MAX_BLOCKS");
+    c->rx_max_blocks = hook && atoi(hook) > 0 ? atoi(hook) : 4 * c->n_cus;
+  }
+  const int ngrid = std::min(grid_for(n, SGTD_RELAX_THREADS), c->rx_max_blocks), egrid = std::min(grid_for(m, SGTD_RELAX_THREADS), c->rx_max_blocks);
+  hipStream_t s = c->stream;
+  relax_init_kernel<<<std::max(ngrid, egrid), SGTD_RELAX_THREADS, 0, s>>>(P, reinterpret_cast<const double *>(in + o_pose), reinterpret_cast<const double *>(in + o_meas));
+  relax_edge_kernel<<<egrid, SGTD_RELAX_THREADS, 0, s>>>(P, 0);
+  relax_ctl_kernel<<<1, SGTD_RELAX_W, 0, s>>>(P, RELAX_CTL_COST0);
+  HIPCHK(hipGetLastError());
+  // outer iterations in groups that fall through once the solve has ended; the state is read once per group.  Every
+  // iteration sent either counts as one or finds the solve ended, so max_outer of them are the hard bound
+  int sent = 0;
+  for (;;) {
+    const int group = std::min<int>(SGTD_RELAX_GROUP, o.max_outer - sent);
+    for (int g = 0; g < group; g++) {
+      relax_setup_kernel<<<ngrid, SGTD_RELAX_THREADS, 0, s>>>(P);
+      relax_ctl_kernel<<<1, SGTD_RELAX_W, 0, s>>>(P, RELAX_CTL_RZ0);
+      for (int it = 0; it < o.max_inner; it++) {
+        relax_cg_edge_kernel<<<egrid, SGTD_RELAX_THREADS, 0, s>>>(P);
+        relax_cg_node_kernel<<<ngrid, SGTD_RELAX_THREADS, 0, s>>>(P);
+        relax_ctl_kernel<<<1, SGTD_RELAX_W, 0, s>>>(P, RELAX_CTL_PQ);
+        relax_cg_update_kernel<<<ngrid, SGTD_RELAX_THREADS, 0, s>>>(P);
+        relax_ctl_kernel<<<1, SGTD_RELAX_W, 0, s>>>(P, RELAX_CTL_RZ);
+      }
+      relax_retract_kernel<<<ngrid, SGTD_RELAX_THREADS, 0, s>>>(P);
+      relax_edge_kernel<<<egrid, SGTD_RELAX_THREADS, 0, s>>>(P, 1);
+      relax_ctl_kernel<<<1, SGTD_RELAX_W, 0, s>>>(P, RELAX_CTL_ACCEPT);
+      relax_edge_kernel<<<egrid, SGTD_RELAX_THREADS, 0, s>>>(P, 0);
+      HIPCHK(hipGetLastError());
+    }
+    sent += group;
+    CHK(d2h(c, &host, P.st, sizeof(RelaxState)));
+    CHK(xfer_sync(c));
+    if (host.done) break;
+    if (sent >= o.max_outer) { c->err = "sgtd_relax_poses: the solve did not end within its outer limit"; return SGTD_ERR_HIP; }
+  }
+  *out = host;
+  return SGTD_OK;
+}
+
+bool relax_finite(const double *v, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+void sgtd_default_relax_options(sgtd_relax_options *o) {
+  if (!o) return;
+  o->max_outer = 50; o->max_inner = 64;
+  o->lambda_init = 1e-4; o->lambda_min = 1e-9; o->lambda_max = 1e9;
+  o->cg_tol = 1e-4; o->step_tol = 1e-6;
+}
+
+int sgtd_relax_poses(sgtd_handle e, int64_t n_nodes, const double *pose0, const uint8_t *fixed, int64_t n_edges, const int32_t *node_i,
+                     const int32_t *node_j, const double *meas, const double *w_trans, const double *w_rot, const sgtd_relax_options *opt,
+                     sgtd_relax_report *report) {
+  if (!e || n_nodes < 0 || n_edges < 0) return SGTD_ERR_INVALID;
+  if (n_nodes > 0 && !pose0) return SGTD_ERR_INVALID;
+  if (n_edges > 0 && (!node_i || !node_j || !meas)) return SGTD_ERR_INVALID;
+  sgtd_relax_options o;
+  sgtd_default_relax_options(&o);
+  if (opt) o = *opt;
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (o.max_outer <= 0 || o.max_inner <= 0 || !pos(o.lambda_init) || !pos(o.lambda_min) || !pos(o.lambda_max) || !pos(o.cg_tol) || !pos(o.step_tol))
+    return SGTD_ERR_INVALID;
+  if (n_nodes > SGTD_RELAX_MAX_NODES || n_edges > SGTD_RELAX_MAX_EDGES) {
+    e->err = "sgtd_relax_poses takes at most " + std::to_string(SGTD_RELAX_MAX_NODES) + " nodes and " + std::to_string(SGTD_RELAX_MAX_EDGES) + " edges";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  for (int64_t k = 0; k < n_edges; k++) {
+    if (node_i[k] < 0 || node_i[k] >= n_nodes || node_j[k] < 0 || node_j[k] >= n_nodes || node_i[k] == node_j[k]) return SGTD_ERR_INVALID;
+    if ((w_trans && !(std::isfinite(w_trans[k]) && w_trans[k] >= 0.0)) || (w_rot && !(std::isfinite(w_rot[k]) && w_rot[k] >= 0.0))) return SGTD_ERR_INVALID;
+  }
+  if (!relax_finite(pose0, (size_t)n_nodes * 12) || !relax_finite(meas, (size_t)n_edges * 12)) return SGTD_ERR_INVALID;
+  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
+  sgtd_relax_report rep{};
+  rep.lambda = o.lambda_init;
+  rep.status = SGTD_RELAX_NOTHING_FREE;
+  if (n_nodes == 0 || n_edges == 0) {
+    c->rx_n = 0; c->rx_m = 0;
+    if (report) *report = rep;
+    return SGTD_OK;
+  }
+  bool all_held = fixed != nullptr;
+  for (int64_t v = 0; all_held && v < n_nodes; v++) all_held = fixed[v] != 0;
+  if (!fixed && n_nodes == 1) all_held = true;
+  PinScope pin_scope(c);
+  c->rx_n = -1;
+  RelaxState st{};
+  const int rc = relax_run(c, (int)n_nodes, pose0, fixed, (int)n_edges, node_i, node_j, meas, w_trans, w_rot, o, all_held, &st);
+  if (rc != SGTD_OK) {
+    if (c != e) e->err = c->err;
+    return rc;
+  }
+  c->rx_n = n_nodes; c->rx_m = n_edges; c->rx_cur = st.cur;
+  rep.cost_before = st.cost_before; rep.cost_after = st.cost; rep.lambda = st.lambda;
+  rep.outer_iterations = st.outer; rep.steps_accepted = st.accepted; rep.cg_iterations = st.cg_total; rep.status = st.status;
+  if (report) *report = rep;
+  return SGTD_OK;
+}
+
+int sgtd_result_relaxed(sgtd_handle e, double *pose, double *edge_cost) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
+  if (c->rx_n < 0) { e->err = "no relaxed poses: sgtd_relax_poses has not run"; return SGTD_ERR_STATE; }
+  const size_t n = (size_t)c->rx_n, m = (size_t)c->rx_m;
+  if (n == 0) return SGTD_OK;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  std::vector<double> rec;
+  if (st == SGTD_OK && pose) {
+    rec.resize(n * SGTD_RELAX_REC);
+    st = d2h(c, rec.data(), c->rx_state.as<double>() + (size_t)c->rx_cur * n * SGTD_RELAX_REC, rec.size() * sizeof(double));
+  }
+  if (st == SGTD_OK && edge_cost) {
+    st = d2h(c, edge_cost, c->rx_edge.as<double>() + RelaxEdgeLayout(m).ec_of(c->rx_cur, m), m * 2 * sizeof(double));
+  }
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  if (pose)
+    for (size_t v = 0; v < n; v++)
+      for (int r = 0; r < 3; r++) {
+        for (int k = 0; k < 3; k++) pose[v * 12 + r * 4 + k] = rec[v * SGTD_RELAX_REC + 7 + r * 3 + k];
+        pose[v * 12 + r * 4 + 3] = rec[v * SGTD_RELAX_REC + 4 + r];
+      }
   return SGTD_OK;
 }
 

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, DescSoa, SgtdError, Stats
+from ._lib import Config, DescSoa, RelaxOptions, RelaxReport, SgtdError, Stats
 
 DEFAULTS = dict(descriptor_near_num=10, candidate_num=50, max_frame_n=20000, device_id=0,
                 descriptor_min_len=0.5, descriptor_max_len=50.0, std_side_resolution=1.0,
@@ -26,6 +26,100 @@ DEFAULTS = dict(descriptor_near_num=10, candidate_num=50, max_frame_n=20000, dev
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _rows34(poses):
+    """(n, 12) rows of the row-major 3x4 [R | t] or (n, 4, 4) -> (R [n, 3, 3], t [n, 3]) in f64"""
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = p[:, :3, :]
+    p = p.reshape(-1, 3, 4)
+    return p[:, :, :3].copy(), p[:, :, 3].copy()
+
+
+def relax_graph(frame_ids, poses, edges, in_set=None, held=None, w_loop=(1.0, 1.0)):
+    """The pose graph relax_session hands to sgtd_relax_poses, in host code (no device): nodes = the session's frames in
+    order, then (held=(map_ids, map_poses)) the map frames the chosen loops name, held, in the order the loops first name
+    them; edges = the odometry edges Z = inv(A_k) A_k+1 (weight 1), then the chosen loops (frame_a, frame_b, T) as
+    i = frame_b's node, j = frame_a's node, Z = T (weights w_loop).  frame_a is always a session frame id.  frame_b is a
+    session frame id when held is None and a map frame id otherwise: the two id spaces are independent and may overlap
+    (a map numbers its frames from 0 as a session does).  loop_edges() after query_frames stamps every query with the one
+    current frame id: the caller then sets frame_a = frame_ids[edges["query"]] first (after loop_frames the ids are the
+    frames' own).  A session of no frames gives an empty graph.
+    -> dict(pose0, fixed, node_i, node_j, meas, w_trans, w_rot, n_session)"""
+    ids = np.asarray(frame_ids).reshape(-1)
+    R, t = _rows34(poses)
+    F = ids.size
+    if R.shape[0] != F:
+        raise ValueError("poses: one per frame id")
+    session = {int(f): k for k, f in enumerate(ids)}
+    fa = np.asarray(edges["frame_a"]).reshape(-1)
+    fb = np.asarray(edges["frame_b"]).reshape(-1)
+    rel = np.asarray(edges["rel_pose"], np.float64).reshape(-1, 12)
+    if fb.size != fa.size or rel.shape[0] != fa.size:
+        raise ValueError("edges: frame_a, frame_b and rel_pose rows, one per edge")
+    keep = np.ones(fa.size, bool) if in_set is None else np.asarray(in_set).reshape(-1) != 0
+    if keep.size != fa.size:
+        raise ValueError("in_set: one flag per edge")
+    chosen = np.flatnonzero(keep)
+    for e in chosen:
+        if int(fa[e]) not in session:
+            raise ValueError("loop edge %d: frame_a %d is not a frame of the session" % (e, int(fa[e])))
+    Rt = np.swapaxes(R, 1, 2)
+    ni = list(range(max(F - 1, 0)))
+    nj = list(range(1, F))
+    meas = [np.concatenate([(Rt[k] @ R[k + 1]).reshape(9), Rt[k] @ (t[k + 1] - t[k])]) for k in range(F - 1)]
+    n_odo = len(ni)
+    R0, t0 = R, t
+    n_map = 0
+    if held is None:
+        for e in chosen:
+            if int(fb[e]) not in session:
+                raise ValueError("loop edge %d: frame_b %d is not a frame of the session" % (e, int(fb[e])))
+        b_node = session
+    else:
+        map_ids, map_poses = held
+        mR, mt = _rows34(map_poses)
+        where = {int(f): k for k, f in enumerate(np.asarray(map_ids).reshape(-1))}
+        if mR.shape[0] != len(where):
+            raise ValueError("held: (map_ids, map_poses), one pose per distinct map frame id")
+        b_node, used = {}, []      # the map frames have nodes of their own, whatever ids the session uses
+        for e in chosen:
+            f = int(fb[e])
+            if f not in where:
+                raise ValueError("loop edge %d names map frame %d, which has no held pose" % (e, f))
+            if f not in b_node:
+                b_node[f] = F + len(used)
+                used.append(where[f])
+        n_map = len(used)
+        if chosen.size:
+            # the session in the map's world: P = mul(B, T) at the first chosen loop's frame, carried by the odometry
+            e = chosen[0]
+            a, b = session[int(fa[e])], where[int(fb[e])]
+            Ra = mR[b] @ rel[e, :9].reshape(3, 3)
+            ta = mR[b] @ rel[e, 9:] + mt[b]
+            S = Ra @ Rt[a]                                   # P_k = P_a inv(A_a) A_k
+            R0 = S @ R
+            t0 = (S @ (t - t[a])[:, :, None])[:, :, 0] + ta
+        R0 = np.concatenate([R0, mR[used]])
+        t0 = np.concatenate([t0, mt[used]])
+    for e in chosen:
+        ni.append(b_node[int(fb[e])])
+        nj.append(session[int(fa[e])])
+        meas.append(rel[e])
+    n = F + n_map
+    fixed = np.zeros(n, np.uint8)
+    if held is None:
+        fixed[:1] = 1
+    else:
+        fixed[F:] = 1
+    m = len(ni)
+    w = np.ones((2, m))
+    w[0, n_odo:] = w_loop[0]
+    w[1, n_odo:] = w_loop[1]
+    return {"pose0": np.concatenate([R0, t0[:, :, None]], 2).reshape(n, 12), "fixed": fixed,
+            "node_i": np.array(ni, np.int32), "node_j": np.array(nj, np.int32),
+            "meas": np.array(meas, np.float64).reshape(m, 12), "w_trans": w[0].copy(), "w_rot": w[1].copy(), "n_session": F}
 
 
 class Descs:
@@ -731,6 +825,64 @@ class STDescManager:
         thr = np.zeros(2, np.float64)
         self._check(self._L.sgtd_result_consistent(self._h, _p(in_set), _p(degree), _p(pick), _p(thr)))
         return {"in_set": in_set, "degree": degree, "pick": pick, "n_set": n_set.value, "thresholds": thr}
+
+    def relax_poses(self, pose0, node_i, node_j, meas, fixed=None, w_trans=None, w_rot=None, **options):
+        """sgtd_relax_poses: pose-graph relaxation on the device.  pose0: (n, 12) rows of the row-major 3x4 [R | t] or
+        (n, 4, 4); node_i, node_j: (m,) node indices; meas: (m, 12) Z ~ inv(X_i) X_j in the rel_pose layout; fixed: (n,)
+        held nodes (None: node 0); w_trans, w_rot: (m,) weights (None: 1.0); options: fields of sgtd_relax_options.
+        -> dict of pose [n, 12], edge_cost [m, 2] and the report's fields.  With no node or no edge nothing runs and
+        sgtd_result_relaxed gives nothing: pose and edge_cost come back with 0 rows, whatever n is."""
+        p0 = np.asarray(pose0)
+        if p0.ndim == 3 and p0.shape[1:] == (4, 4):
+            p0 = p0[:, :3, :]
+        p0 = np.ascontiguousarray(p0, np.float64).reshape(-1, 12)
+        ni = np.ascontiguousarray(node_i, np.int32).reshape(-1)
+        nj = np.ascontiguousarray(node_j, np.int32).reshape(-1)
+        z = np.ascontiguousarray(meas, np.float64).reshape(-1, 12)
+        n, m = p0.shape[0], ni.size
+        if nj.size != m or z.shape[0] != m:
+            raise ValueError("node_i, node_j and meas: one entry per edge")
+        fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8).reshape(-1)
+        if fx is not None and fx.size != n:
+            raise ValueError("fixed: one flag per node")
+        ws = []
+        for w in (w_trans, w_rot):
+            w = None if w is None else np.ascontiguousarray(w, np.float64).reshape(-1)
+            if w is not None and w.size != m:
+                raise ValueError("weights: one per edge")
+            ws.append(w)
+        opt = RelaxOptions()
+        self._L.sgtd_default_relax_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(RelaxOptions._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        rep = RelaxReport()
+        self._check(self._L.sgtd_relax_poses(self._h, n, _p(p0), _p(fx), m, _p(ni), _p(nj), _p(z), _p(ws[0]), _p(ws[1]),
+                                             C.byref(opt), C.byref(rep)))
+        filled = n > 0 and m > 0
+        pose = np.zeros((n if filled else 0, 12), np.float64)
+        cost = np.zeros((m if filled else 0, 2), np.float64)
+        self._check(self._L.sgtd_result_relaxed(self._h, _p(pose), _p(cost)))
+        return {"pose": pose, "edge_cost": cost, "cost_before": rep.cost_before, "cost_after": rep.cost_after,
+                "lambda": rep.lambda_, "outer_iterations": rep.outer_iterations, "steps_accepted": rep.steps_accepted,
+                "cg_iterations": rep.cg_iterations, "status": rep.status}
+
+    def relax_session(self, frame_ids, poses, edges, in_set=None, held=None, w_loop=(1.0, 1.0), **options):
+        """A session's trajectory relaxed over its chosen loops (relax_graph + relax_poses).  frame_ids: (F,) the session's
+        frames in order; poses: their odometry, (F, 12) or (F, 4, 4); edges: loop_edges()'s dict (frame_a in the session: see
+        relax_graph for a batch of query_frames; map ids may overlap the session's);
+        in_set: consistent_loops()'s mask (None: every edge).  held=None: the session is closed against itself (frame_b in
+        the session too), its first frame held.  held=(map_ids, map_poses): against a fixed map: the map frames the chosen
+        loops name are held at those poses, the session starts from P = mul(B, T) of the first chosen loop carried along
+        the odometry.  -> dict(poses: {frame id: (12,) row} of the session's frames, graph: what relax_poses was given,
+        and relax_poses' result fields)"""
+        g = relax_graph(frame_ids, poses, edges, in_set, held, w_loop)
+        res = self.relax_poses(g["pose0"], g["node_i"], g["node_j"], g["meas"], g["fixed"], g["w_trans"], g["w_rot"], **options)
+        ids = np.asarray(frame_ids).reshape(-1)
+        res["poses"] = {int(f): res["pose"][k].copy() for k, f in enumerate(ids)} if res["pose"].shape[0] else {}
+        res["graph"] = g
+        return res
 
     def consistency_rows(self):
         """the bit matrix of the last consistent_loops call: (n, ceil(n / 64)) uint64, bit j of row i = bit j & 63 of word
