@@ -705,6 +705,90 @@ int sgtd_result_loop_edges(sgtd_handle h, double icp_threshold, int flags,
                            int32_t *query, uint32_t *frame_a, uint32_t *frame_b, double *rel_pose, double *score,
                            int64_t capacity, int64_t *n_edges);
 
+/* Consensus among the verified candidates of ONE query, for every query of a batch in one launch: a map is a trajectory,
+ * so the true place is seen by several neighbouring map frames, and several of a query's up to candidate_num verified
+ * candidates measure the same world pose (sgtd_result_world_poses shows them side by side), while a candidate that
+ * verifies against the wrong place stands alone or in a small group.  The call groups a query's candidates by the world
+ * pose they imply, chooses a mutually consistent set, counts its support and fuses one pose from it: what a caller that
+ * localises from one scan against a map with poses (sgtd_set_frame_poses) needs, without odometry and without a session.
+ * It is sgtd_consistent_loops' pair test taken inside one query, where the odometry term is the identity. */
+/* The rule, for one query with candidates k = 0 .. cn-1 (cn = cand_num <= 64).  All arithmetic is f64, every operation
+ * (+, -, *, /, sqrt) rounded once (no contraction); f32 inputs are widened exactly.  inv() and mul() are those of
+ * sgtd_consistent_loops; QUAT, UNIT and ROT those of sgtd_relax_poses.
+ * Validity: candidate k is valid when k < n_cand, it has a result (score >= 0: neither rejected nor masked out), its frame
+ *   has a stored pose B_k (an id beyond the stored range has none, which is no error) and all 24 numbers of B_k and of its
+ *   relative pose T_k are finite.  P_k = mul(B_k, T_k).
+ * Agreement, for valid k < l: Z = mul(inv(P_k), P_l); d2 = (Zt[0]*Zt[0] + Zt[1]*Zt[1]) + Zt[2]*Zt[2];
+ *   tr = (Z[0][0] + Z[1][1]) + Z[2][2]; the pair agrees iff d2 <= tt and tr >= min_trace, with tt = max_trans*max_trans and
+ *   min_trace = 1.0 + 2.0*cos(max_rot) computed once on the host as sgtd_consistent_loops computes them and handed back
+ *   in thresholds[0], thresholds[1].  A NaN makes a comparison false.  adj(k, l) = adj(l, k) = the decision taken with the
+ *   lower index first; adj(k, k) = 0; an invalid candidate has an empty row and column.  (sgtd_consistent_loops' decision
+ *   for two edges that share one pose_a: mul with the identity changes no bit of what the test reads.)
+ * Choice: sgtd_consistent_loops' greedy rule over the valid candidates: the largest remaining degree first, the lowest
+ *   index among equals, P = P & adj(v) after each pick v (with its shortcut, whose outcome is the rule's).  The seed is the
+ *   first pick; the members m_0 < m_1 < ... are taken in ascending candidate index; n_set is their count.
+ * Fusion: that[c] = (P_m.t[c] added one by one in ascending m from +0.0) / (double)n_set.  q_m = QUAT(rotation of P_m);
+ *   s_m = ((w*w_s + x*x_s) + y*y_s) + z*z_s against the seed's quaternion q_s; s_m < 0 negates all four components of q_m.
+ *   Q = their component-wise sum in ascending m from +0.0; qhat = UNIT(Q); Rhat = ROT(qhat).  The fused pose is
+ *   [Rhat | that], row-major 3x4 f64 (the layout of sgtd_relax_poses' pose0).
+ * Figures per query: n_valid, n_set, seed, the member mask (bit k of a u64);
+ *   support_score = the members' scores added in ascending m from +0.0;
+ *   spread_t2 = the maximum over the members of (e[0]*e[0] + e[1]*e[1]) + e[2]*e[2], e = P_m.t - that;
+ *   spread_trace = the minimum over the members of (r[0] + r[1]) + r[2],
+ *     r[i] = (Rhat[i][0]*R_m[i][0] + Rhat[i][1]*R_m[i][1]) + Rhat[i][2]*R_m[i][2]
+ *   (both start from the first member's value; then m = v > m ? v : m, respectively v < m ? v : m, in ascending m).
+ *   A query without a valid candidate: n_set 0, seed -1, mask 0, NaN pose and spreads, support_score 0.
+ * Per candidate (parity and diagnostics): the row adj(k) as a u64; degree = |adj(k)|, -1 when invalid; pick = the
+ *   position in the greedy order, else -1.
+ * sgtd_pose_consensus_rows takes caller host arrays for all queries back to back, in the layouts of
+ * sgtd_result_candidates (n_cand[n_queries], cand_frame[n_queries*cand_num]) and sgtd_result_verify
+ * (score[n_queries*cand_num], rel_pose[n_queries*cand_num*12]); it uses the handle's stored poses and is independent of
+ * the pending batch and of the table, as sgtd_consistent_loops is; the arrays are copied before the call returns.
+ * sgtd_pose_consensus is the same over the pending verified batch, on a single-device handle without a round trip
+ * through the host: the kernel reads the batch's candidates, scores and poses where the earlier stages left them, and the
+ * call only enqueues.  flags 0 takes sgtd_verify's pose, SGTD_CONSENSUS_REFINED sgtd_refine_poses', SGTD_CONSENSUS_ALIGNED
+ * sgtd_align_keypoints'; SGTD_ERR_STATE when that stage (or sgtd_verify) has not run on the batch; both flags together or
+ * unknown bits: SGTD_ERR_INVALID.
+ * The results last until the next consensus call (either form) or sgtd_destroy; a new batch or a new sgtd_verify* also
+ * drops the batch form's results; a failed call drops them.  The call changes no other result.  A view (sgtd_attach_table)
+ * uses its own poses and has results of its own; a multi-device handle gathers each candidate's result from its owner
+ * and runs the rows form on its first device with the group's poses (the single handle's values bit for bit).
+ * Device memory: 140 + 16 * cand_num bytes a query, the rows form's inputs and the pose store's copy.
+ * h == NULL, a negative count, a NULL array with a positive count, cand_num outside [1, 64], max_trans NaN, negative or
+ * infinite, max_rot NaN or outside [0, pi], min_support < 1: SGTD_ERR_INVALID, before the device is touched.  The getters
+ * before a successful run: SGTD_ERR_STATE; q or a range outside the run: SGTD_ERR_INVALID.  n_queries == 0 does nothing. */
+#define SGTD_CONSENSUS_REFINED 1   /* fuse sgtd_refine_poses' poses    */
+#define SGTD_CONSENSUS_ALIGNED 2   /* fuse sgtd_align_keypoints' poses */
+int sgtd_pose_consensus_rows(sgtd_handle h, int64_t n_queries, int cand_num,
+                             const int32_t *n_cand,      /* [n_queries]                 */
+                             const int32_t *cand_frame,  /* [n_queries*cand_num]        */
+                             const double *score,        /* [n_queries*cand_num]        */
+                             const double *rel_pose,     /* [n_queries*cand_num*12] rot row-major (9), t (3) */
+                             double max_trans, double max_rot /* radians */);
+int sgtd_pose_consensus(sgtd_handle h, double max_trans, double max_rot /* radians */, int flags);
+/* the per-query figures of queries first .. first + n - 1; any pointer may be NULL */
+int sgtd_result_consensus(sgtd_handle h, int64_t first, int64_t n,
+                          double *pose,           /* [n*12] row-major 3x4 [R | t] */
+                          int32_t *n_valid, int32_t *n_set, int32_t *seed, /* [n] each */
+                          uint64_t *mask,         /* [n] bit k: candidate k is a member */
+                          double *support_score, double *spread_t2, double *spread_trace, /* [n] each */
+                          double *thresholds);    /* [2] tt, min_trace */
+/* the per-candidate outputs of query q: arrays of the run's cand_num; any pointer may be NULL */
+int sgtd_result_consensus_rows(sgtd_handle h, int q, uint64_t *rows, int32_t *degree, int32_t *pick);
+/* SearchLoop's choice under consensus, for every query of the batch form's results, in host code: a query is accepted
+ * when n_set >= min_support (min_support >= 1); its choice is the member with the strictly largest verify_score, the
+ * first among equals; otherwise -1, -1, 0.  support = n_set, accepted or not.  Arrays of n_queries; any may be NULL.
+ * After sgtd_pose_consensus_rows (no batch stands behind those results): SGTD_ERR_STATE. */
+int sgtd_search_loop_consensus(sgtd_handle h, int min_support, int32_t *best_cand, int32_t *best_frame,
+                               double *best_score, int32_t *support);
+/* One edge per accepted query, in ascending q, with the conventions of sgtd_result_loop_edges (query, frame_a, capacity,
+ * *n_edges, SGTD_ERR_CAPACITY): frame_b = the chosen member's frame, with B its stored pose rel_pose = mul(inv(B), fused)
+ * in the rule's f64 arithmetic (rot row-major (9), t (3)), score = support_score.  The edges feed sgtd_consistent_loops
+ * and sgtd_relax_poses unchanged.  h == NULL, n_edges == NULL, capacity < 0, min_support < 1: SGTD_ERR_INVALID; state
+ * errors as sgtd_search_loop_consensus. */
+int sgtd_result_consensus_edges(sgtd_handle h, int min_support, int32_t *query, uint32_t *frame_a, uint32_t *frame_b,
+                                double *rel_pose, double *score, int64_t capacity, int64_t *n_edges);
+
 /* Pose-graph relaxation on the device: the trajectory that honours a set of relative-pose measurements ("edges"), the
  * last stage behind sgtd_consistent_loops.  A generic graph in caller arrays: n_nodes poses X_v (pose0 holds the start,
  * row-major 3x4 [R | t]), n_edges measurements Z_k ~ inv(X_i) X_j between nodes i = node_i[k] and j = node_j[k] in the

@@ -37,6 +37,8 @@ SYMBOLS = [
     "sgtd_search_loop_aligned",
     "sgtd_consistent_loops", "sgtd_result_consistent", "sgtd_result_consistency_rows", "sgtd_result_loop_edges",
     "sgtd_default_relax_options", "sgtd_relax_poses", "sgtd_result_relaxed",
+    "sgtd_pose_consensus_rows", "sgtd_pose_consensus", "sgtd_result_consensus", "sgtd_result_consensus_rows",
+    "sgtd_search_loop_consensus", "sgtd_result_consensus_edges",
 ]
 
 
@@ -188,6 +190,12 @@ def lib():
     L.sgtd_default_relax_options.restype = None
     L.sgtd_relax_poses.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, C.POINTER(RelaxOptions), C.POINTER(RelaxReport)]
     L.sgtd_result_relaxed.argtypes = [vp, vp, vp]
+    L.sgtd_pose_consensus_rows.argtypes = [vp, i64, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double]
+    L.sgtd_pose_consensus.argtypes = [vp, C.c_double, C.c_double, C.c_int]
+    L.sgtd_result_consensus.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgtd_result_consensus_rows.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.sgtd_search_loop_consensus.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.sgtd_result_consensus_edges.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

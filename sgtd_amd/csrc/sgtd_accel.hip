@@ -32,6 +32,7 @@
 #include "align_kernels.hip.h"
 #include "consistency_kernels.hip.h"
 #include "relax_kernels.hip.h"
+#include "consensus_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -301,6 +302,15 @@ struct sgtd_engine {
   int64_t ck_n = -1;
   double ck_thr[2] = {0.0, 0.0};
   hipEvent_t ck_ev[3] = {};
+  // sgtd_pose_consensus (consensus_kernels.hip.h): cs_in: the rows form's inputs; cs_out: every output of the call
+  // (ConsensusLayout); the pose store's device copy is ck_store / ck_has.  cs_n < 0: no results; cs_batch: they are the
+  // batch form's, and go with the batch's verification (stale_stages).  A group's results live on its first device's
+  // engine, which the group's batches and verifications pass through.
+  DevBuf cs_in, cs_out;
+  int64_t cs_n = -1;
+  int cs_cn = 0;
+  bool cs_batch = false;
+  double cs_thr[2] = {0.0, 0.0};
   // sgtd_relax_poses (relax_kernels.hip.h): independent of the batch.  rx_in: the call's inputs and the node -> edge CSR;
   // rx_state: the two sets of node records; rx_edge: the per-edge streams and costs; rx_node: the node vectors, blocks
   // and factors; rx_ctl: RelaxState.  rx_n < 0: no results; rx_host_*: the sources of the uploads the host makes.
@@ -374,7 +384,10 @@ namespace {
 
 // what the stages on a verified batch left (sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints) belongs to the
 // verification before this one
-void stale_stages(sgtd_engine *e) { e->refined = false; e->overlapped = false; e->aligned = false; }
+void stale_stages(sgtd_engine *e) {
+  e->refined = false; e->overlapped = false; e->aligned = false;
+  if (e->cs_batch) e->cs_n = -1;      // (sgtd_pose_consensus over this batch; the rows form's results stay)
+}
 // the batch's candidates or lists are new: so is, or will be, everything after them
 void new_results(sgtd_engine *e, bool verified) { e->verified = verified; stale_stages(e); }
 
@@ -2125,6 +2138,7 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows,
                     &e->pos_dev, &e->prior_dev, &e->filt_base,
                     &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state,
+                    &e->cs_in, &e->cs_out,
                     &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl};
   for (DevBuf *b : bufs) free_buf(*b);
   for (hipEvent_t ev : e->ck_ev)
@@ -4271,6 +4285,317 @@ int sgtd_get_stats(sgtd_handle e, sgtd_stats *out) {
   e->stats.tail_entries = e->n_seg > 1 ? e->seg[1].g1 - e->seg[1].g0 : 0;
   *out = e->stats;
   return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_pose_consensus: per query, the consistent set of its verified candidates and their fused pose
+// (consensus_kernels.hip.h) ----
+namespace {
+// cs_out: the 8-byte outputs first
+struct ConsensusLayout {
+  size_t pose, figs, mask, rows, counts, degree, pick, total;
+  ConsensusLayout(size_t nq, size_t cn) {
+    pose = 0; figs = pose + nq * 12 * sizeof(double); mask = figs + nq * 3 * sizeof(double); rows = mask + nq * sizeof(u64);
+    counts = rows + nq * cn * sizeof(u64); degree = counts + nq * 3 * sizeof(int); pick = degree + nq * cn * sizeof(int);
+    total = pick + nq * cn * sizeof(int);
+  }
+};
+
+bool consensus_bounds_ok(double max_trans, double max_rot) {
+  return max_trans >= 0.0 && !std::isinf(max_trans) && max_rot >= 0.0 && max_rot <= 3.14159265358979323846;
+}
+
+bool have_verified(const sgtd_engine *e) { return e->grp ? (e->grp->batch_valid && e->grp->verified) : (e->batch_valid && e->verified); }
+
+// one launch over nq queries whose candidates, scores and poses are on c's device; owner: whose pose store is used
+int consensus_launch(sgtd_engine *c, const sgtd_engine *owner, int nq, int cn, const int *d_n_cand, const int *d_cand_frame,
+                     const double *d_score, const double *d_rel, double tt, double min_trace) {
+  sgtd_engine *e = c;
+  CHK(cons_upload_store(c, owner));
+  const ConsensusLayout L((size_t)nq, (size_t)cn);
+  CHK(ensure(c, c->cs_out, L.total));
+  char *out = c->cs_out.as<char>();
+  ConsensusParams P;
+  P.store = c->ck_store.as<float>(); P.has = c->ck_has.as<unsigned char>(); P.n_ids = (u32)owner->has_pose.size();
+  P.n_cand = d_n_cand; P.cand_frame = d_cand_frame; P.score = d_score; P.rel = d_rel; P.cn = cn; P.tt = tt; P.min_trace = min_trace;
+  P.pose = reinterpret_cast<double *>(out + L.pose); P.figs = reinterpret_cast<double *>(out + L.figs);
+  P.mask = reinterpret_cast<u64 *>(out + L.mask); P.rows = reinterpret_cast<u64 *>(out + L.rows);
+  P.counts = reinterpret_cast<int *>(out + L.counts); P.degree = reinterpret_cast<int *>(out + L.degree);
+  P.pick = reinterpret_cast<int *>(out + L.pick);
+  consensus_kernel<<<nq, SGTD_WAVE, 0, c->stream>>>(P);
+  HIPCHK(hipGetLastError());
+  return SGTD_OK;
+}
+
+// the rows form: the caller's host arrays go to c's device first; the host waits for the pass
+int consensus_rows_run(sgtd_engine *c, const sgtd_engine *owner, int nq, int cn, const int32_t *n_cand, const int32_t *cand_frame,
+                       const double *score, const double *rel_pose, double tt, double min_trace) {
+  sgtd_engine *e = c;
+  HIPCHK(hipSetDevice(c->cfg.device_id));
+  const size_t nb = (size_t)nq * cn;
+  const size_t o_rel = 0, o_score = o_rel + nb * 12 * sizeof(double), o_frame = o_score + nb * sizeof(double),
+               o_n = o_frame + nb * sizeof(int), in_bytes = o_n + (size_t)nq * sizeof(int);
+  CHK(ensure(c, c->cs_in, in_bytes));
+  char *in = c->cs_in.as<char>();
+  CHK(h2d(c, in + o_rel, rel_pose, nb * 12 * sizeof(double)));
+  CHK(h2d(c, in + o_score, score, nb * sizeof(double)));
+  CHK(h2d(c, in + o_frame, cand_frame, nb * sizeof(int)));
+  CHK(h2d(c, in + o_n, n_cand, (size_t)nq * sizeof(int)));
+  CHK(consensus_launch(c, owner, nq, cn, reinterpret_cast<const int *>(in + o_n), reinterpret_cast<const int *>(in + o_frame),
+                       reinterpret_cast<const double *>(in + o_score), reinterpret_cast<const double *>(in + o_rel), tt, min_trace));
+  return xfer_sync(c);
+}
+
+// the relative poses of query q's candidates the flag names (the stage has run: the caller has checked)
+int consensus_batch_pose(sgtd_engine *e, int q, int flags, double *pose) {
+  if (flags & SGTD_CONSENSUS_REFINED) return sgtd_result_refined(e, q, pose, nullptr, nullptr, nullptr, nullptr);
+  if (flags & SGTD_CONSENSUS_ALIGNED)
+    return sgtd_result_aligned(e, q, pose, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return sgtd_result_verify(e, q, nullptr, pose);
+}
+
+// the pending batch's candidate frames and verify scores on the host, [nq * cn] each
+int consensus_batch_scores(sgtd_engine *e, int nq, std::vector<int> *frame, std::vector<double> *score) {
+  const size_t cn = (size_t)e->cfg.candidate_num;
+  frame->assign((size_t)nq * cn, -1);
+  score->assign((size_t)nq * cn, -1.0);
+  if (nq == 0) return SGTD_OK;
+  if (!e->grp) {
+    HIPCHK(hipSetDevice(e->cfg.device_id));
+    CHK(sync_batch(e));
+    std::memcpy(frame->data(), e->h_cand_frame.data(), (size_t)nq * cn * sizeof(int));
+    CHK(d2h(e, score->data(), e->v_score.as<double>(), (size_t)nq * cn * sizeof(double)));
+    return xfer_sync(e);
+  }
+  int n_cand = 0;
+  for (int q = 0; q < nq; q++) {
+    CHK(batch_candidates(e, q, &n_cand, frame->data() + (size_t)q * cn));
+    CHK(sgtd_result_verify(e, q, score->data() + (size_t)q * cn, nullptr));
+  }
+  return SGTD_OK;
+}
+
+// the getters' state checks; *out: the engine that holds the results
+int consensus_ready(sgtd_engine *e, sgtd_engine **out) {
+  sgtd_engine *c = cons_engine(e);
+  if (c->cs_n >= 0 && c->cs_batch && !have_verified(e)) c->cs_n = -1;      // (the batch went without a new one)
+  if (c->cs_n < 0) { e->err = "no consensus results: sgtd_pose_consensus has not run (or its batch has gone)"; return SGTD_ERR_STATE; }
+  *out = c;
+  return SGTD_OK;
+}
+
+// sgtd_search_loop_consensus' choice for every query of the batch form's results: cand, frame, score [nq] (-1, -1, 0
+// where the set is smaller than min_support) and n_set
+int consensus_choice(sgtd_engine *e, int min_support, std::vector<int32_t> *cand, std::vector<int32_t> *frame, std::vector<double> *best,
+                     std::vector<int32_t> *n_set) {
+  sgtd_engine *c = nullptr;
+  CHK(consensus_ready(e, &c));
+  if (!c->cs_batch) { e->err = "the consensus results are those of sgtd_pose_consensus_rows: the choice needs the batch form"; return SGTD_ERR_STATE; }
+  const int nq = (int)c->cs_n;
+  const size_t cn = (size_t)c->cs_cn;
+  cand->assign((size_t)nq, -1); frame->assign((size_t)nq, -1); best->assign((size_t)nq, 0.0); n_set->assign((size_t)nq, 0);
+  if (nq == 0) return SGTD_OK;
+  std::vector<uint64_t> mask((size_t)nq);
+  CHK(sgtd_result_consensus(e, 0, nq, nullptr, nullptr, n_set->data(), nullptr, mask.data(), nullptr, nullptr, nullptr, nullptr));
+  std::vector<int> frames;
+  std::vector<double> scores;
+  CHK(consensus_batch_scores(e, nq, &frames, &scores));
+  for (int q = 0; q < nq; q++) {
+    if ((*n_set)[(size_t)q] < min_support) continue;
+    int bk = -1;
+    double bs = 0.0;
+    for (u64 b = mask[(size_t)q]; b; b &= b - 1) {
+      const int k = __builtin_ctzll(b);
+      const double s = scores[(size_t)q * cn + k];
+      if (bk < 0 || s > bs) { bk = k; bs = s; }
+    }
+    if (bk < 0) continue;
+    (*cand)[(size_t)q] = bk; (*frame)[(size_t)q] = frames[(size_t)q * cn + bk]; (*best)[(size_t)q] = bs;
+  }
+  return SGTD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sgtd_pose_consensus_rows(sgtd_handle e, int64_t n_queries, int cand_num, const int32_t *n_cand, const int32_t *cand_frame,
+                             const double *score, const double *rel_pose, double max_trans, double max_rot) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = cons_engine(e);
+  c->cs_n = -1;
+  if (n_queries < 0 || cand_num < 1 || cand_num > SGTD_MAX_CAND || !consensus_bounds_ok(max_trans, max_rot)) return SGTD_ERR_INVALID;
+  if (n_queries > 0 && (!n_cand || !cand_frame || !score || !rel_pose)) return SGTD_ERR_INVALID;
+  if (n_queries > 0x7FFFFFFF / SGTD_MAX_CAND) {
+    e->err = "sgtd_pose_consensus_rows takes at most " + std::to_string(0x7FFFFFFF / SGTD_MAX_CAND) + " queries in one call";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  PinScope pin_scope(c);
+  const double tt = max_trans * max_trans, min_trace = 1.0 + 2.0 * std::cos(max_rot);
+  if (n_queries > 0) {
+    const int st = consensus_rows_run(c, e, (int)n_queries, cand_num, n_cand, cand_frame, score, rel_pose, tt, min_trace);
+    if (st != SGTD_OK) {
+      if (c != e) e->err = c->err;
+      return st;
+    }
+  }
+  c->cs_thr[0] = tt; c->cs_thr[1] = min_trace;
+  c->cs_n = n_queries; c->cs_cn = cand_num; c->cs_batch = false;
+  return SGTD_OK;
+}
+
+int sgtd_pose_consensus(sgtd_handle e, double max_trans, double max_rot, int flags) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = cons_engine(e);
+  c->cs_n = -1;
+  if ((flags & ~(SGTD_CONSENSUS_REFINED | SGTD_CONSENSUS_ALIGNED)) || flags == (SGTD_CONSENSUS_REFINED | SGTD_CONSENSUS_ALIGNED)) return SGTD_ERR_INVALID;
+  if (!consensus_bounds_ok(max_trans, max_rot)) return SGTD_ERR_INVALID;
+  PinScope pin_scope(c);
+  if (!have_verified(e)) return needs(e, "sgtd_pose_consensus", "sgtd_verify");
+  if ((flags & SGTD_CONSENSUS_REFINED) && !(e->grp ? e->grp->refined : e->refined)) return needs(e, "SGTD_CONSENSUS_REFINED", "sgtd_refine_poses");
+  if ((flags & SGTD_CONSENSUS_ALIGNED) && !(e->grp ? e->grp->aligned : e->aligned)) return needs(e, "SGTD_CONSENSUS_ALIGNED", "sgtd_align_keypoints");
+  const double tt = max_trans * max_trans, min_trace = 1.0 + 2.0 * std::cos(max_rot);
+  const int cn = e->cfg.candidate_num, nq = e->grp ? e->grp->nq : e->nq;
+  if (e->grp) {
+    // every candidate's result from its owner, then the rows form on the first device with the group's poses
+    const size_t nb = (size_t)std::max(nq, 1) * cn;
+    std::vector<int32_t> n_cand((size_t)std::max(nq, 1)), frame(nb);
+    std::vector<double> score(nb), pose(nb * 12);
+    for (int q = 0; q < nq; q++) {
+      CHK(batch_candidates(e, q, &n_cand[(size_t)q], frame.data() + (size_t)q * cn));
+      CHK(sgtd_result_verify(e, q, score.data() + (size_t)q * cn, nullptr));
+      CHK(consensus_batch_pose(e, q, flags, pose.data() + (size_t)q * cn * 12));
+    }
+    if (nq > 0) {
+      const int st = consensus_rows_run(c, e, nq, cn, n_cand.data(), frame.data(), score.data(), pose.data(), tt, min_trace);
+      if (st != SGTD_OK) { e->err = c->err; return st; }
+    }
+  } else {
+    HIPCHK(hipSetDevice(e->cfg.device_id));
+    CHK(view_current(e));
+    const double *rel = (flags & SGTD_CONSENSUS_REFINED) ? e->r_pose.as<double>() : (flags & SGTD_CONSENSUS_ALIGNED) ? e->a_pose.as<double>() : e->v_pose.as<double>();
+    // the batch's candidates, scores and poses are read where the earlier stages left them: nothing travels
+    if (nq > 0) CHK(consensus_launch(e, e, nq, cn, e->n_cand.as<int>(), e->cand_frame.as<int>(), e->v_score.as<double>(), rel, tt, min_trace));
+  }
+  c->cs_thr[0] = tt; c->cs_thr[1] = min_trace;
+  c->cs_n = nq; c->cs_cn = cn; c->cs_batch = true;
+  return SGTD_OK;
+}
+
+int sgtd_result_consensus(sgtd_handle e, int64_t first, int64_t n, double *pose, int32_t *n_valid, int32_t *n_set, int32_t *seed,
+                          uint64_t *mask, double *support_score, double *spread_t2, double *spread_trace, double *thresholds) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(consensus_ready(e, &c));
+  if (first < 0 || n < 0 || first > c->cs_n || n > c->cs_n - first) return SGTD_ERR_INVALID;
+  if (thresholds) { thresholds[0] = c->cs_thr[0]; thresholds[1] = c->cs_thr[1]; }
+  if (n == 0) return SGTD_OK;
+  PinScope pin_scope(c);
+  const ConsensusLayout L((size_t)c->cs_n, (size_t)c->cs_cn);
+  const char *out = c->cs_out.as<char>();
+  const size_t f = (size_t)first, m = (size_t)n;
+  std::vector<double> figs;
+  std::vector<int> counts;
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && pose) st = d2h(c, pose, out + L.pose + f * 12 * sizeof(double), m * 12 * sizeof(double));
+  if (st == SGTD_OK && mask) st = d2h(c, mask, out + L.mask + f * sizeof(u64), m * sizeof(u64));
+  if (st == SGTD_OK && (support_score || spread_t2 || spread_trace)) {
+    figs.resize(m * 3);
+    st = d2h(c, figs.data(), out + L.figs + f * 3 * sizeof(double), m * 3 * sizeof(double));
+  }
+  if (st == SGTD_OK && (n_valid || n_set || seed)) {
+    counts.resize(m * 3);
+    st = d2h(c, counts.data(), out + L.counts + f * 3 * sizeof(int), m * 3 * sizeof(int));
+  }
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) {
+    if (c != e) e->err = c->err;
+    return st;
+  }
+  for (size_t i = 0; i < m; i++) {
+    if (support_score) support_score[i] = figs[i * 3 + 0];
+    if (spread_t2) spread_t2[i] = figs[i * 3 + 1];
+    if (spread_trace) spread_trace[i] = figs[i * 3 + 2];
+    if (n_valid) n_valid[i] = counts[i * 3 + 0];
+    if (n_set) n_set[i] = counts[i * 3 + 1];
+    if (seed) seed[i] = counts[i * 3 + 2];
+  }
+  return SGTD_OK;
+}
+
+int sgtd_result_consensus_rows(sgtd_handle e, int q, uint64_t *rows, int32_t *degree, int32_t *pick) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(consensus_ready(e, &c));
+  if (q < 0 || q >= c->cs_n) return SGTD_ERR_INVALID;
+  PinScope pin_scope(c);
+  const size_t cn = (size_t)c->cs_cn, o = (size_t)q * cn;
+  const ConsensusLayout L((size_t)c->cs_n, cn);
+  const char *out = c->cs_out.as<char>();
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && rows) st = d2h(c, rows, out + L.rows + o * sizeof(u64), cn * sizeof(u64));
+  if (st == SGTD_OK && degree) st = d2h(c, degree, out + L.degree + o * sizeof(int), cn * sizeof(int));
+  if (st == SGTD_OK && pick) st = d2h(c, pick, out + L.pick + o * sizeof(int), cn * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK && c != e) e->err = c->err;
+  return st;
+}
+
+int sgtd_search_loop_consensus(sgtd_handle e, int min_support, int32_t *best_cand, int32_t *best_frame, double *best_score, int32_t *support) {
+  if (!e || min_support < 1) return SGTD_ERR_INVALID;
+  std::vector<int32_t> cand, frame, n_set;
+  std::vector<double> best;
+  CHK(consensus_choice(e, min_support, &cand, &frame, &best, &n_set));
+  const size_t nq = cand.size();
+  if (best_cand) std::copy(cand.begin(), cand.end(), best_cand);
+  if (best_frame) std::copy(frame.begin(), frame.end(), best_frame);
+  if (best_score) std::copy(best.begin(), best.end(), best_score);
+  if (support) std::copy(n_set.begin(), n_set.begin() + (std::ptrdiff_t)nq, support);
+  return SGTD_OK;
+}
+
+int sgtd_result_consensus_edges(sgtd_handle e, int min_support, int32_t *query, uint32_t *frame_a, uint32_t *frame_b, double *rel_pose,
+                                double *score, int64_t capacity, int64_t *n_edges) {
+  if (!e || !n_edges || capacity < 0 || min_support < 1) return SGTD_ERR_INVALID;
+  std::vector<int32_t> cand, frame, n_set;
+  std::vector<double> best;
+  CHK(consensus_choice(e, min_support, &cand, &frame, &best, &n_set));
+  const int nq = (int)cand.size();
+  std::vector<double> fused((size_t)std::max(nq, 1) * 12), support((size_t)std::max(nq, 1));
+  if (nq > 0) CHK(sgtd_result_consensus(e, 0, nq, fused.data(), nullptr, nullptr, nullptr, nullptr, support.data(), nullptr, nullptr, nullptr));
+  int64_t m = 0;
+  for (int q = 0; q < nq; q++) {
+    if (cand[(size_t)q] < 0) continue;
+    if (m < capacity) {
+      if (rel_pose) {
+        // rel_pose = mul(inv(B), fused), B the stored pose of the chosen member's frame (a member's frame has one)
+        const size_t id = (size_t)(u32)frame[(size_t)q];
+        if (id >= e->has_pose.size() || !e->has_pose[id]) { e->err = "sgtd_result_consensus_edges: the stored poses changed since sgtd_pose_consensus"; return SGTD_ERR_STATE; }
+        const float *M = e->poses.data() + id * 12;
+        const double *F = fused.data() + (size_t)q * 12;
+        double Br[9], Bt[3], Fr[9], Ft[3], Ir[9], It[3];
+        for (int r = 0; r < 3; r++) {
+          for (int cc = 0; cc < 3; cc++) { Br[r * 3 + cc] = (double)M[r * 4 + cc]; Fr[r * 3 + cc] = F[r * 4 + cc]; }
+          Bt[r] = (double)M[r * 4 + 3]; Ft[r] = F[r * 4 + 3];
+        }
+        for (int r = 0; r < 3; r++)
+          for (int cc = 0; cc < 3; cc++) Ir[r * 3 + cc] = Br[cc * 3 + r];
+        for (int r = 0; r < 3; r++) It[r] = -((Ir[r * 3 + 0] * Bt[0] + Ir[r * 3 + 1] * Bt[1]) + Ir[r * 3 + 2] * Bt[2]);
+        double *out = rel_pose + (size_t)m * 12;
+        for (int r = 0; r < 3; r++) {
+          for (int cc = 0; cc < 3; cc++) out[r * 3 + cc] = (Ir[r * 3 + 0] * Fr[cc] + Ir[r * 3 + 1] * Fr[3 + cc]) + Ir[r * 3 + 2] * Fr[6 + cc];
+          out[9 + r] = ((Ir[r * 3 + 0] * Ft[0] + Ir[r * 3 + 1] * Ft[1]) + Ir[r * 3 + 2] * Ft[2]) + It[r];
+        }
+      }
+      if (query) query[m] = q;
+      if (frame_a) frame_a[m] = e->grp ? e->grp->current_frame_id : (e->last_kind == 1 ? e->last_qframe + (e->loop_batch ? (u32)q : 0u) : e->current_frame_id);
+      if (frame_b) frame_b[m] = (uint32_t)frame[(size_t)q];
+      if (score) score[m] = support[(size_t)q];
+    }
+    m++;
+  }
+  *n_edges = m;
+  return m > capacity ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 }  // extern "C"

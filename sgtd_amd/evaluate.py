@@ -151,3 +151,43 @@ def evaluate_batch(mgr, map_pose4, query_xyz, query_label, query_pose4, metrics=
         else:
             account(metrics, query_pose4[q], map_pose4, int(bf[q]), None, None, (), ())
     return metrics
+
+
+def evaluate_consensus(mgr, map_pose4, query_xyz, query_label, query_pose4, max_trans, max_rot, min_support=2, kp_off=None,
+                       refine=0, icp_threshold=None):
+    """One batch localised twice: SearchLoop's choice with its own relative pose, and STDescManager.pose_consensus' fused
+    pose of the query's mutually consistent candidates (the map's poses set: set_frame_poses), each against ground truth.
+    refine: N > 0 fuses refine_poses(N)'s poses (SearchLoop's side is then accounted with the refined pose of its choice).
+    A localisation counts as right within 5 m and 10 degrees (the node's bound, :735).
+    -> dict(search_loop=..., consensus=...), each with accepted, wrong, t_errors, r_errors (lists over the accepted
+    queries, in query order) and queries; consensus also holds support (n_set of every query)."""
+    res = mgr.query_frames(query_xyz, query_label, kp_off)
+    mgr.verify()
+    if refine:
+        mgr.refine_poses(refine)
+    bc, bf, _ = mgr.search_loop(icp_threshold)
+    fused = mgr.pose_consensus(max_trans, max_rot, refined=bool(refine))
+    cc, _, _, support = mgr.search_loop_consensus(min_support)
+    nq = len(bf)
+    out = {name: {"queries": nq, "accepted": 0, "wrong": 0, "t_errors": [], "r_errors": []} for name in ("search_loop", "consensus")}
+    out["consensus"]["support"] = support.tolist()
+
+    def book(side, pose4, q):
+        t_e, r_e = compute_adj_rpe(query_pose4[q], pose4)
+        side["accepted"] += 1
+        side["wrong"] += not (t_e < 5 and r_e < 10)
+        side["t_errors"].append(t_e)
+        side["r_errors"].append(r_e)
+
+    for q in range(nq):
+        if bf[q] > 0:
+            _, rot, t = mgr.result_verify(q)
+            if refine:
+                r = mgr.result_refined(q)
+                rot, t = r["rot"], r["t"]
+            rel = np.eye(4, dtype=np.float32)
+            rel[:3, :3], rel[:3, 3] = rot[int(bc[q])], t[int(bc[q])]
+            book(out["search_loop"], (map_pose4[int(bf[q])] @ rel).astype(np.float32), q)
+        if cc[q] >= 0:
+            book(out["consensus"], matrix_from_row(fused["pose"][q]), q)
+    return out

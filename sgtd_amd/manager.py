@@ -892,6 +892,89 @@ class STDescManager:
         self._check(self._L.sgtd_result_consistency_rows(self._h, 0, n, _p(rows)))
         return rows
 
+    def pose_consensus(self, max_trans, max_rot, refined=False, aligned=False, fetch=True):
+        """sgtd_pose_consensus after verify(): per query of the pending batch, the mutually consistent set of its verified
+        candidates (by the world pose each implies: set_frame_poses) and one fused pose, in one launch.  refined / aligned:
+        fuse refine_poses' / align_keypoints' poses instead of verify's; max_rot in radians.  -> result_consensus()
+        (fetch=False: None, the call only enqueues)"""
+        flags = (1 if refined else 0) | (2 if aligned else 0)
+        self._check(self._L.sgtd_pose_consensus(self._h, float(max_trans), float(max_rot), flags))
+        self._consensus = (int(self._nq), int(self.config_setting_["candidate_num"]))
+        return self.result_consensus() if fetch else None
+
+    def pose_consensus_rows(self, n_cand, cand_frame, score, rel_pose, max_trans, max_rot):
+        """sgtd_pose_consensus_rows: the same over caller arrays, independent of the pending batch: n_cand (nq,),
+        cand_frame (nq, cn) as results() gives them, score (nq, cn) and rel_pose (nq, cn, 12) as result_verify /
+        result_refined / result_aligned give them (rot row-major (9), t (3)); cn <= 64.  -> result_consensus()"""
+        nc = np.ascontiguousarray(n_cand, np.int32).reshape(-1)
+        nq = nc.size
+        sc = np.asarray(score, np.float64)
+        if sc.ndim != 2 or sc.shape[0] != nq:
+            raise ValueError("score: (nq, cn)")
+        cn = sc.shape[1]
+        sc = np.ascontiguousarray(sc)
+        cf = np.ascontiguousarray(cand_frame, np.int32).reshape(nq, -1) if nq else np.zeros((0, cn), np.int32)
+        rel = np.ascontiguousarray(rel_pose, np.float64).reshape(nq, -1) if nq else np.zeros((0, cn * 12), np.float64)
+        if cf.shape[1] != cn or rel.shape[1] != cn * 12:
+            raise ValueError("cand_frame (nq, cn), score (nq, cn) and rel_pose (nq, cn, 12) do not agree")
+        self._check(self._L.sgtd_pose_consensus_rows(self._h, nq, cn, _p(nc), _p(cf), _p(sc), _p(rel), float(max_trans), float(max_rot)))
+        self._consensus = (nq, cn)
+        return self.result_consensus()
+
+    def result_consensus(self, first=0, n=None):
+        """sgtd_result_consensus for queries first .. first + n - 1 (all by default) -> dict of pose [n, 12] (row-major 3x4
+        [R | t], NaN without a valid candidate), n_valid, n_set, seed [n] (int32), mask [n] (uint64: bit k = candidate k is a
+        member), support_score, spread_t2, spread_trace [n] and thresholds (tt, min_trace)"""
+        nq = getattr(self, "_consensus", (0, 0))[0]
+        n = nq - first if n is None else int(n)
+        m = max(n, 0)
+        out = {"pose": np.zeros((m, 12), np.float64), "n_valid": np.zeros(m, np.int32), "n_set": np.zeros(m, np.int32),
+               "seed": np.zeros(m, np.int32), "mask": np.zeros(m, np.uint64), "support_score": np.zeros(m, np.float64),
+               "spread_t2": np.zeros(m, np.float64), "spread_trace": np.zeros(m, np.float64), "thresholds": np.zeros(2, np.float64)}
+        self._check(self._L.sgtd_result_consensus(self._h, int(first), n, _p(out["pose"]), _p(out["n_valid"]), _p(out["n_set"]),
+                                                  _p(out["seed"]), _p(out["mask"]), _p(out["support_score"]), _p(out["spread_t2"]),
+                                                  _p(out["spread_trace"]), _p(out["thresholds"])))
+        return out
+
+    def consensus_rows(self, q):
+        """sgtd_result_consensus_rows: query q's agreement rows (cn,) uint64 (bit l of row k: candidates k and l agree),
+        degree (cn,) (-1: invalid) and pick (cn,) (the position in the greedy order, else -1)"""
+        cn = getattr(self, "_consensus", (0, 0))[1]
+        rows = np.zeros(max(cn, 1), np.uint64)
+        degree = np.zeros(max(cn, 1), np.int32)
+        pick = np.zeros(max(cn, 1), np.int32)
+        self._check(self._L.sgtd_result_consensus_rows(self._h, int(q), _p(rows), _p(degree), _p(pick)))
+        return rows[:cn], degree[:cn], pick[:cn]
+
+    def search_loop_consensus(self, min_support=2):
+        """sgtd_search_loop_consensus after pose_consensus(): a query is accepted when its set has at least min_support
+        members; its choice is the member with the largest verify_score.  -> (best_cand, best_frame, best_score, support)
+        arrays; -1, -1, 0 where nothing is accepted; support = n_set"""
+        nq = getattr(self, "_consensus", (0, 0))[0]
+        bc = np.zeros(nq, np.int32)
+        bf = np.zeros(nq, np.int32)
+        bs = np.zeros(nq, np.float64)
+        sup = np.zeros(nq, np.int32)
+        self._check(self._L.sgtd_search_loop_consensus(self._h, int(min_support), _p(bc), _p(bf), _p(bs), _p(sup)))
+        return bc, bf, bs, sup
+
+    def consensus_edges(self, min_support=2, capacity=None):
+        """sgtd_result_consensus_edges after pose_consensus(): one edge per accepted query, loop_edges()'s dict: frame_b =
+        the chosen member's frame, rel_pose = inv(its stored pose) * the fused pose, score = support_score -- what
+        consistent_loops and relax_session take"""
+        cap = max(int(getattr(self, "_consensus", (0, 0))[0]), 1) if capacity is None else int(capacity)
+        room = max(cap, 1)
+        q = np.zeros(room, np.int32)
+        fa = np.zeros(room, np.uint32)
+        fb = np.zeros(room, np.uint32)
+        rel = np.zeros((room, 12), np.float64)
+        sc = np.zeros(room, np.float64)
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_consensus_edges(self._h, int(min_support), _p(q), _p(fa), _p(fb), _p(rel), _p(sc), cap, C.byref(n)))
+        m = min(n.value, cap)
+        return {"query": q[:m].copy(), "frame_a": fa[:m].copy(), "frame_b": fb[:m].copy(), "rel_pose": rel[:m].copy(),
+                "score": sc[:m].copy()}
+
     def overlap(self, radius, refined=False, xyz=None, label=None, kp_off=None):
         """sgtd_overlap after verify(): under every verified candidate's relative pose (refined=True: refine_poses()'s),
         how many of the query's keypoints land within `radius` of a keypoint of the same label of the candidate's frame
