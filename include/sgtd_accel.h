@@ -119,8 +119,13 @@ typedef struct sgtd_stats {
    * enabled, as the ms_ fields above), and the greedy rounds it took (a clique shortcut counts as one) */
   float ms_consistency_pairs, ms_consistency_greedy;
   int32_t consistency_rounds;
-  int32_t reserved3;
+  int32_t order_giveups_total; /* since the handle was created: batches whose ordering gave up a bounded wait between
+                                workgroups (a scheduling surprise) and were run again by sgtd_sync with the launch train;
+                                each also counts in overflow_launches_total and reruns_total. 0 in normal use       */
 } sgtd_stats;
+
+/* descriptors per tile of the batch ordering's sort passes and of its group index (the tests place their edges there) */
+void sgtd_order_tiles(int *sort_tile, int *group_tile);
 
 typedef struct sgtd_engine *sgtd_handle;
 

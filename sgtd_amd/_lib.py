@@ -23,7 +23,7 @@ SYMBOLS = [
     "sgtd_add", "sgtd_add_frames", "sgtd_finalize", "sgtd_query_frames", "sgtd_query_descs", "sgtd_max_batch",
     "sgtd_result_candidates", "sgtd_export_candidates_dev", "sgtd_result_query_desc_count", "sgtd_result_pairs",
     "sgtd_result_query_descs", "sgtd_result_votes", "sgtd_result_rough", "sgtd_fetch_entries", "sgtd_host_alloc", "sgtd_host_free",
-    "sgtd_table_dump", "sgtd_sync", "sgtd_get_stats",
+    "sgtd_table_dump", "sgtd_sync", "sgtd_get_stats", "sgtd_order_tiles",
     "sgtd_verify", "sgtd_export_verify_dev", "sgtd_result_verify", "sgtd_result_inliers", "sgtd_result_inlier_pairs", "sgtd_result_inlier_entries", "sgtd_search_loop",
     "sgtd_graphs_load", "sgtd_graphs_save_cache", "sgtd_graphs_load_cache", "sgtd_graphs_view",
     "sgtd_graphs_error", "sgtd_graphs_free", "sgtd_save_table", "sgtd_load_table",
@@ -89,7 +89,7 @@ class Stats(C.Structure):
         ("tail_entries", C.c_int64), ("ms_finalize", C.c_float), ("reserved2", C.c_float),
         ("batches_total", C.c_int64), ("overflow_launches_total", C.c_int64), ("reruns_total", C.c_int64), ("rewrites_total", C.c_int64),
         ("list_moves_total", C.c_int64), ("last_list_moves", C.c_int64), ("device_allocs_total", C.c_int64),
-        ("ms_consistency_pairs", C.c_float), ("ms_consistency_greedy", C.c_float), ("consistency_rounds", C.c_int32), ("reserved3", C.c_int32),
+        ("ms_consistency_pairs", C.c_float), ("ms_consistency_greedy", C.c_float), ("consistency_rounds", C.c_int32), ("order_giveups_total", C.c_int32),
     ]
 
 
@@ -211,6 +211,8 @@ def lib():
     L.sgtd_sync.argtypes = [vp]
     L.sgtd_max_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
     L.sgtd_get_stats.argtypes = [vp, C.POINTER(Stats)]
+    L.sgtd_order_tiles.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sgtd_order_tiles.restype = None
     L.sgtd_verify.argtypes = [vp]
     L.sgtd_result_verify.argtypes = [vp, C.c_int, vp, vp]
     L.sgtd_export_verify_dev.argtypes = [vp, vp, vp]

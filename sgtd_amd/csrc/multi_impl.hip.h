@@ -719,7 +719,7 @@ int get_stats(sgtd_engine *e, sgtd_stats *out) {
     t.overflowed |= x.overflowed;
     t.select_form = x.select_form;
     t.batches_total = x.batches_total; t.overflow_launches_total += x.overflow_launches_total;
-    t.reruns_total += x.reruns_total; t.rewrites_total += x.rewrites_total;
+    t.reruns_total += x.reruns_total; t.rewrites_total += x.rewrites_total; t.order_giveups_total += x.order_giveups_total;
     t.list_moves_total += x.list_moves_total; t.last_list_moves += x.last_list_moves;
     t.ms_total = std::max(t.ms_total, x.ms_total);
     if (s == 0) { t.ms_consistency_pairs = x.ms_consistency_pairs; t.ms_consistency_greedy = x.ms_consistency_greedy; t.consistency_rounds = x.consistency_rounds; }   // (sgtd_consistent_loops runs on the first device)

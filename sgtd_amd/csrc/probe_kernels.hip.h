@@ -85,7 +85,7 @@ struct QueryView {
 // the words of ProbeBuffers::ctr, the batch's counter block (described there): device and host name them here and nowhere by number.
 // The first CTR_COUNT words are what the host copies back after a batch and what the frame pack carries (verify_kernels.hip.h).
 enum { CTR_REC_CURSOR = 0, CTR_AMB_COUNT = 2, CTR_COMPACT_CURSOR = 3, CTR_REC_NEED = 4, CTR_SWEPT = 6, CTR_POOL_CURSOR = 8, CTR_LIST_MOVES = 9,
-       CTR_OVERFLOW = 10, CTR_COUNT = 12, CTR_XCD_HEADS = 1024 };
+       CTR_OVERFLOW = 10, CTR_COUNT = 12, CTR_ORDER_GIVEUP = 16, CTR_XCD_HEADS = 1024 };
 struct ProbeBuffers {
   u32 *rec;             // [4 rec_cap] match records: the entry's id (frame and entry in one word, common.hip.h IdMap)
   unsigned char *rec_cell;  // [4 rec_cap] voxel_round index (diagnostic build only)
@@ -102,7 +102,8 @@ struct ProbeBuffers {
   // add up beyond 2^32), 2 the undecided-record queue's fill, 3 the compact lists' cursor,
   // 4-5 matches that found no room (sizes the regrown buffer), 6-7 table entries the sweep
   // really loaded (after slice pruning), 8 the pass pool's cursor, 9 match lists that moved to a fresh
-  // slab, 10-11 the overflow flags (0: match records / pass pool / undecided queue, 1: candidate pairs), from word 1024 the
+  // slab, 10-11 the overflow flags (0: match records / pass pool / undecided queue, 1: candidate pairs), 16 the ordering's
+  // "a look-back gave up" word (order_kernels.hip.h; read by the host only behind overflow flag 0), from word 1024 the
   // sweep's eight ticket-queue heads, 1024 words (4 KB: own L2 channel) apart
   u32 *ctr;
   __host__ __device__ __forceinline__ unsigned long long *rec_cursor() const { return reinterpret_cast<unsigned long long *>(ctr + CTR_REC_CURSOR); }

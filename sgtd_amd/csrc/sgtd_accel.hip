@@ -20,6 +20,7 @@
 #include "common.hip.h"
 #include "table_kernels.hip.h"
 #include "probe_kernels.hip.h"
+#include "order_kernels.hip.h"
 #include "select_kernels.hip.h"
 #include "verify_kernels.hip.h"
 #include "verify_mfma.hip.h"
@@ -129,6 +130,7 @@ struct SelectPlan {
   u32 tile_span = 1, n_tiles = 1; size_t hist_bytes = 0; bool lds_votes = false;                        // vote tiling
   bool votes_fit = false, table_fits = false, per_query = false, fused_pairs = false, fused_votes = false, votes_per_query = false;   // form of the record passes
   int cbits = 1, sub_bits = 0, key_bits = 0; bool small = false, pair = false; size_t max_pass_slots = 0;   // ordering
+  bool order_fused = false; u32 order_tiles = 0, order_gtiles = 0;      // ... by order_kernels.hip.h's chain (32-bit keys, not `small`), its tiles
   int row_slots = 1; u32 ticket = 2; int sgrid = 0, pgrid = 0; bool narrow = false, frames = false;     // reservations and the sweep's shape
   bool narrow_pairs = false;      // list form: 4-byte words of the compact lists where an entry's rank among its frame's fits 19 bits, else 8
 };
@@ -227,6 +229,7 @@ struct sgtd_engine {
   bool prior_rows_valid = false;
   // sort scratch
   DevBuf keyA, keyB, valA, valB, hist, digit_tot, flags, bad_flag;
+  DevBuf order_work;                   // order_kernels.hip.h: tickets, digit histograms and tile state words of a batch's ordering
   std::vector<DevBuf> scan_lvl;
 
   // ---- build scratch
@@ -349,6 +352,11 @@ struct sgtd_engine {
   size_t amb_min = 65536;                   // SGTD_AMB_MIN (test hook): the undecided queue's floor in entries (above it: rec_cap / 64)
   int sorted_chunk = 0;                // > 0: fixed descriptors per ticket (SGTD_SORTED_CHUNK), else adaptive
   bool diag = false;                   // diagnostic probe build: cell index + distance per match
+  int order_form = -1;                 // SGTD_ORDER_FORM (test hook): 0 the launch train, 1 order_kernels.hip.h's chain wherever it applies; unset: the
+                                       // chain, except for a one-frame batch of at most SGTD_SMALL_SLOTS slots (plan_select)
+  u32 order_polls = SGTD_ORDER_POLLS_DEFAULT;   // SGTD_ORDER_POLLS (test hook): state words a look-back may load before it gives up
+  bool order_gave_up = false;          // the batch being synchronised gave up an ordering look-back: its re-runs take the launch train
+  bool order_train = false;            // ... set around such a re-run
   int select_mode = 0;                 // SGTD_SELECT_MODE (test hook): 0 auto, 1 the five-kernel passes over the records, 2 the per-query
                                        // workgroups (select_kernels.hip.h) wherever they are supported, whatever the batch size
   // host copies after sync
@@ -1083,6 +1091,14 @@ SelectPlan plan_select(const sgtd_engine *e) {
   // launch (small_order_kernel; SGTD_SMALL_ORDER=0: the general form)
   const bool small_on = [] { const char *o = getenv("SGTD_SMALL_ORDER"); return !(o && !atoi(o)); }();
   p.small = small_on && nq == 1 && n_slots <= SGTD_SMALL_SLOTS && p.key_bits <= 32 && !p.fused_votes && span <= (1u << 20);
+  // the general ordering: order_kernels.hip.h's chain for 32-bit keys, the launch train for wider ones, under SGTD_ORDER_FORM=0
+  // and for the re-runs of a batch whose look-back gave up.  Without the hook, a one-frame batch that small_order_kernel would
+  // have taken (it is here only under SGTD_SMALL_ORDER=0) keeps the launch train: the form that kernel is compared with
+  const bool small_shape = nq == 1 && n_slots <= SGTD_SMALL_SLOTS;
+  p.order_fused = !p.small && (e->order_form == 1 || (e->order_form < 0 && !small_shape)) && !e->order_train && p.key_bits <= 32 && n_slots > 0 &&
+                  n_slots < SGTD_ORDER_MAX_KEYS;
+  p.order_tiles = (u32)((n_slots + SGTD_OS_TILE - 1) / SGTD_OS_TILE);
+  p.order_gtiles = (u32)((n_slots + SGTD_GI_TILE - 1) / SGTD_GI_TILE);
   // pass slots: at most one per group and one per two descriptors (probe_kernels.hip.h)
   p.pair = !e->diag && SGTD_PAIR >= 2;
   p.max_pass_slots = (size_t)pass_slot_count((u32)n_slots, (u32)n_slots, p.pair) + 64;
@@ -1404,6 +1420,7 @@ int reserve_select(sgtd_engine *e, const SelectPlan &p) {
   for (DevBuf *b : {&e->valA, &e->valB, &e->gid, &e->group_first}) CHK(ensure(e, *b, n_slots * sizeof(u32)));
   for (DevBuf *b : {&e->n_valid, &e->n_groups}) CHK(ensure(e, *b, sizeof(u32)));
   for (DevBuf *b : {&e->pos_of_slot, &e->rec_off}) CHK(ensure(e, *b, p.max_pass_slots * sizeof(u32)));
+  if (p.order_fused) CHK(ensure(e, e->order_work, order_work_words((p.key_bits + 7) / 8, p.order_tiles, p.order_gtiles) * sizeof(u32)));
   // 160 B per descriptor slot (110 used at the 10 000-frame default), 256 B for tables beyond 1e8 entries (more of
   // the 27 cells of a home cell have a bucket: 190 B used at 100 000 frames); grown on overflow
   if (e->pool_units == 0) e->pool_units = std::max<size_t>(65536, n_slots * (e->n_entries > 100000000 ? 16 : 10));
@@ -1428,8 +1445,38 @@ int clear_batch(sgtd_engine *e, const SelectPlan &p) {
     HIPCHK(hipMemsetAsync(e->cand_frame.p, 0xFF, (size_t)nq * cn * sizeof(int), e->stream));
     HIPCHK(hipMemsetAsync(e->cand_votes.p, 0, (size_t)nq * cn * sizeof(int), e->stream));
   }
+  if (p.order_fused) return SGTD_OK;      // (q_M and q_P: order_begin_kernel)
   HIPCHK(hipMemsetAsync(e->q_M.p, 0, (size_t)nq * sizeof(u32), e->stream));
   HIPCHK(hipMemsetAsync(e->q_P.p, 0, (size_t)nq * sizeof(unsigned long long), e->stream));
+  return SGTD_OK;
+}
+
+// the general ordering of a batch with 32-bit home keys in nine launches, the counters' fill included (order_kernels.hip.h): what it leaves in order, gid,
+// group_first, n_groups, pos_of_slot and n_valid is what order_descriptors' launch train below leaves there
+int order_fused(sgtd_engine *e, const SelectPlan &p, const Views &v, u32 **order) {
+  const long long n_slots = p.n_slots;
+  const int passes = (p.key_bits + 7) / 8;
+  u32 *kin = e->keyA.as<u32>(), *kout = e->keyB.as<u32>(), *vin = e->valA.as<u32>(), *vout = e->valB.as<u32>();
+  u32 *nv = e->n_valid.as<u32>(), *work = e->order_work.as<u32>(), *giveup = e->cursors.as<u32>() + CTR_ORDER_GIVEUP;
+  order_begin_kernel<<<1, 256, 0, e->stream>>>(e->q_count.as<u32>(), e->q_prefix.as<u32>(), p.nq, nv, e->q_M.as<u32>(),
+                                               e->q_P.as<unsigned long long>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(work, 0, order_work_words(passes, p.order_tiles, p.order_gtiles) * sizeof(u32), e->stream));      // tickets, histograms, every pass's state words
+  home_keys_hist_kernel<<<(unsigned)std::min<long long>(grid_for(n_slots, 256), (long long)e->n_cus * 8), 256, 0, e->stream>>>(v.Q, e->q_prefix.as<u32>(), kin, vin, n_slots,
+                                                                                                                              p.cbits, p.sub_bits, work + OW_HIST, e->pos_of_slot.as<u32>(), p.max_pass_slots);
+  HIPCHK(hipGetLastError());
+  for (int pass = 0; pass < passes; pass++) {
+    order_sort_pass_kernel<<<p.order_tiles, SGTD_OS_THREADS, 0, e->stream>>>(kin, vin, kout, vout, nv, n_slots, work, p.order_tiles, pass, e->order_polls, giveup);
+    HIPCHK(hipGetLastError());
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+  }
+  order_groups_kernel<<<p.order_gtiles, SGTD_GI_THREADS, 0, e->stream>>>(kin, nv, e->gid.as<u32>(), e->group_first.as<u32>(), e->n_groups.as<u32>(), e->pos_of_slot.as<u32>(),
+                                                                        (u32)std::min<size_t>(p.max_pass_slots, 0xFFFFFFFFu), n_slots, work + OW_GROUP_TICKET,
+                                                                        reinterpret_cast<u64 *>(work + order_group_state_at(passes, p.order_tiles)), p.order_gtiles, p.cbits,
+                                                                        p.sub_bits, p.pair ? 1 : 0, e->order_polls, giveup, v.B.overflow());
+  HIPCHK(hipGetLastError());
+  e->thr2_pending = 0; *order = vin;
   return SGTD_OK;
 }
 
@@ -1457,6 +1504,7 @@ int order_descriptors(sgtd_engine *e, const SelectPlan &p, const Views &v, u32 *
     e->thr2_pending = 0; *order = vin;
     return SGTD_OK;
   }
+  if (p.order_fused) return order_fused(e, p, v, order);
   query_prefix_kernel<<<1, 256, 0, e->stream>>>(e->q_count.as<u32>(), e->q_prefix.as<u32>(), p.nq, e->n_valid.as<u32>());
   HIPCHK(hipGetLastError());
   // keys, their sort (only the n_valid compact elements are live) and the heads of the groups, in the key's width
@@ -1672,9 +1720,13 @@ int enqueue_frames(sgtd_engine *e) {
 }
 
 int rerun(sgtd_engine *e) {
-  if (e->last_kind == 1) return enqueue_frames(e);
-  if (e->timing) HIPCHK(hipEventRecord(e->ev[EV_START], e->stream));
-  return launch_select(e);
+  e->order_train = e->order_gave_up;      // (read by plan_select)
+  int st = SGTD_OK;
+  if (e->last_kind == 1) st = enqueue_frames(e);
+  else if (e->timing && hipEventRecord(e->ev[EV_START], e->stream) != hipSuccess) st = SGTD_ERR_HIP;
+  else st = launch_select(e);
+  e->order_train = false;
+  return st;
 }
 
 // the candidate-pair buffer was too small: everything up to the per-block counts is intact,
@@ -1723,6 +1775,7 @@ int sync_batch(sgtd_engine *e) {
   CHK(view_current(e));
   if (e->batch_synced) return SGTD_OK;
   e->stats.overflowed = 0;
+  e->order_gave_up = false;
   unsigned long long swept = 0;
   for (int attempt = 0; attempt < 12; attempt++) {
     int ovf[2] = {0, 0};
@@ -1757,6 +1810,18 @@ int sync_batch(sgtd_engine *e) {
       fprintf(stderr, "sgtd: batch re-run (attempt %d): flags %d %d, records %llu of %zu (+%llu wanted), pass pool %u of %zu units, home cells %u of %zu rows, pairs %u of %zu\n",
               attempt, ovf[0], ovf[1], cursor, e->rec_cap, need, pool_used, e->pool_units, n_groups, e->group_cap, total, e->pair_cap);
     if (attempt == 11) return SGTD_ERR_CAPACITY;
+    if (ovf[0] && e->plan.order_fused) {
+      // a look-back of the ordering gave up (order_kernels.hip.h): nothing was too small — the batch runs again with the launch train
+      u32 gave_up = 0;
+      CHK(d2h(e, &gave_up, e->cursors.as<u32>() + CTR_ORDER_GIVEUP, sizeof(u32)));
+      CHK(xfer_sync(e));
+      if (gave_up) {
+        e->stats.order_giveups_total++;
+        e->order_gave_up = true;
+        CHK(rerun(e));
+        continue;
+      }
+    }
     // grow towards the index limits; a batch that does not fit even there must be split
     const size_t lim = kRecLimit, pair_lim = kIndexLimit;
     if (ovf[0] && (size_t)n_groups > e->group_cap) {
@@ -2017,6 +2082,11 @@ int stream_table(sgtd_engine *e, FILE *f, size_t n, bool to_file) {
 
 extern "C" {
 
+void sgtd_order_tiles(int *sort_tile, int *group_tile) {
+  if (sort_tile) *sort_tile = SGTD_OS_TILE;
+  if (group_tile) *group_tile = SGTD_GI_TILE;
+}
+
 void sgtd_default_config(sgtd_config *cfg) {
   std::memset(cfg, 0, sizeof(*cfg));
   cfg->descriptor_near_num = 10;
@@ -2080,6 +2150,8 @@ int sgtd_create(const sgtd_config *cfg, sgtd_handle *out) {
   if (const char *o = getenv("SGTD_COARSE_AT")) e->coarse_at = (u32)std::min(62ll, std::max(0ll, atoll(o)));
   if (const char *o = getenv("SGTD_REC_RATE")) e->rec_rate_hook = (u32)std::min(256, std::max(1, atoi(o)));
   if (const char *o = getenv("SGTD_WIDE_PAIRS")) e->wide_pairs = atoi(o) != 0;
+  if (const char *o = getenv("SGTD_ORDER_FORM")) e->order_form = atoi(o) != 0 ? 1 : 0;
+  if (const char *o = getenv("SGTD_ORDER_POLLS")) e->order_polls = (u32)std::min(1ll << 30, std::max(0ll, atoll(o)));
   if (const char *o = getenv("SGTD_SELECT_MODE")) e->select_mode = std::min(2, std::max(0, atoi(o)));
   if (const char *o = getenv("SGTD_WHOLE_AT")) e->whole_at = (u32)std::min(62ll, std::max(0ll, atoll(o)));
   // test hook: start with a small match-record buffer so that the overflow / re-run path runs
@@ -2125,7 +2197,7 @@ int sgtd_destroy(sgtd_handle e) {
   free_store(e->tab); free_store(e->tmp); free_store(e->qd); free_store(e->fetch); free_buf(e->fetch_idx);
   DevBuf *bufs[] = {&e->seg[0].hot, &e->seg[0].perm, &e->seg[0].hash, &e->seg[0].bucket_start, &e->seg[0].bucket_key, &e->seg[0].dir,
                     &e->seg[1].hot, &e->seg[1].perm, &e->seg[1].hash, &e->seg[1].bucket_start, &e->seg[1].bucket_key, &e->seg[1].dir, &e->slice_of, &e->sq_sum,
-                    &e->keyA, &e->keyB, &e->valA, &e->valB, &e->hist, &e->digit_tot, &e->flags, &e->bad_flag,
+                    &e->keyA, &e->keyB, &e->valA, &e->valB, &e->hist, &e->digit_tot, &e->flags, &e->bad_flag, &e->order_work,
                     &e->kp_off_dev, &e->xyz_dev, &e->label_dev, &e->b_kp_off_dev, &e->b_xyz_dev, &e->b_label_dev, &e->ws_keys, &e->ws_slots, &e->cnt_scan,
                     &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->kp_dev, &e->kp_word, &e->o_cnt, &e->o_val, &e->o_qxyz, &e->o_qlabel, &e->o_qoff, &e->a_pose, &e->a_fit, &e->a_cnt, &e->a_val, &e->a_mom, &e->a_assign, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
                     &e->votes, &e->slot_of, &e->q_M, &e->q_P, &e->q_pairs, &e->q_pair_base,
