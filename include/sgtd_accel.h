@@ -971,6 +971,93 @@ int sgtd_graphs_view(const sgtd_graph_batch *b, int *n_frames, int64_t *n_keypoi
 const char *sgtd_graphs_error(const sgtd_graph_batch *b);
 void sgtd_graphs_free(sgtd_graph_batch *b);
 
+/* ---- labelled scans to keypoints (scan_kernels.hip.h) ----
+ * What the reference's producer create_semantic_graph does on the CPU (src/sgtd/src/get_json.cpp:41-343: per semantic
+ * class, DCVC clustering of the class's points, src/sgtd/include/cluster_manager.hpp:139-421, then one centroid and node
+ * label per cluster) for a batch of scans on the device: points f32 (x y z, or x y z intensity: the .bin layout) and
+ * labels u32 (sem | inst << 16: the .label layout) in, the xyz f32 + label u32 keypoints of sgtd_add_frames /
+ * sgtd_query_frames / sgtd_loop_frames out.
+ *
+ * The reference's clustering cannot be reproduced bit for bit: DCVC() (:272-355) is one sequential sweep whose partition
+ * depends on the order of the points and may split a connected group of voxels (:288, :332-334), labelAnalysis walks a
+ * std::unordered_map (:408), points outside the range gate keep an unset polarCor entry and are clustered all the same
+ * (:198,205), and the neighbour set is asymmetric at the azimuth seam (:377), at the top pitch layer (:213,235,370) and
+ * at y > polarNum.  This call computes the fixed point the sweep approximates — the connected components of the
+ * symmetrised curved-voxel graph — with every order fixed by point index.  Every sweep cluster lies inside one component.
+ *
+ * Arithmetic: f64, every operation rounded once (no contraction), f32 inputs widened exactly.
+ * Per point: sem = label & 0xFFFF, inst = label >> 16, class s = sem.  Dropped: s >= 32, node_label[s] == 0, or a
+ *   coordinate that is not finite.
+ * Per (scan, class): mode 1 (instances) when any kept point of the class has inst != 0 (get_json.cpp:138), else mode 2.
+ * Mode 1: one cluster per distinct inst (0 included), kept when its count > min_instance_points, in ascending inst order.
+ * Mode 2: r = sqrt((x*x + y*y) + z*z); in range iff neither r >= max_range nor r <= min_range (:198; points out of
+ *   range are dropped — a departure: the reference clusters garbage for them); pitch = (asin(z / r) * 180.0) / pi;
+ *   a = atan2(y, x), azimuth = ((a > 0.0 ? a : a + 2.0 * pi) * 180.0) / pi (:178-196; the device math library's f64
+ *   asin and atan2).  minPitch = maxPitch = 0.0 and minPolar = maxPolar = 5.0 to start with, then the min / max over the
+ *   in-range points (:200-203,482-485).  width = (int)(round(360.0 / delta_a) + 1.0), height = (int)((maxPitch -
+ *   minPitch) / delta_p); ring bounds (:214-220): range = minPolar, step = 1, while range <= maxPolar: range = range +
+ *   (start_r - step * delta_r), append, step++; polarNum = their number.  polar = the first k with r < bound[k], else
+ *   polarNum - 1 (:259-264); pit = (int)round((pitch - minPitch) / delta_p), azi = (int)round(azimuth / delta_a), C's
+ *   round (:234-237).  N(v) = searchKNN's set (:365-385) with its hard-coded 300 read as width - 1 (its value at the
+ *   shipped delta_a).  Two occupied voxels u, v are linked iff v is in N(u) or u is in N(v) (a departure: the reference
+ *   follows N one way); the points of a voxel belong together; clusters = the connected components, kept when their
+ *   count >= min_seg[s] (:409), ordered by their smallest point index (a departure: the reference's order is that of
+ *   an unordered_map).
+ * Keypoints of a scan: classes in ascending s, within a class the order above; label = node_label[s]; n_points = the
+ *   cluster's count; each centre coordinate = (float)(SUM / (double)n_points), SUM in the fixed order: 256 accumulators
+ *   from +0.0, the cluster's points in ascending point index, the point of rank k to accumulator k mod 256, then
+ *   acc[l] += acc[l + w] for l < w, w = 128, ..., 1 (a departure by rounding only from the running f32 sum of
+ *   get_json.cpp:266-274).  The edges and weights of gen_graphs (get_json.cpp:301-329) are not produced (nothing
+ *   downstream reads them); no file is read in C.
+ *
+ * sgtd_scan_keypoints leaves the keypoints on the device; it is independent of the pending batch, the table and the
+ * stored poses, uses buffers of its own, and its results last until the next scan call or sgtd_destroy.  points and
+ * labels are host arrays, or device arrays with device_ptrs != 0; pt_off (n_scans + 1 offsets, in points) is a host
+ * array.  sgtd_scan_device_view hands out borrowed device pointers (xyz f32 [n_keypoints * 3], label u32): with the
+ * fetched kp_off they are what sgtd_add_frames / sgtd_query_frames / sgtd_loop_frames take with device_ptrs = 1.  A view
+ * (sgtd_attach_table) runs the call whatever state its owner's table is in; a multi-device handle runs it on its first
+ * device (its tables take host arrays: fetch the keypoints for them).  sgtd_result_scan_point_clusters: cluster[i] = the index within the scan of the keypoint point i went into,
+ * or -1.  sgtd_result_scan_grids: grid rows per class = mode (0 none, 1 instance, 2 voxel), polarNum, width, height
+ * (zeros unless mode 2); range rows = minPitch, maxPitch, minPolar, maxPolar (zeros unless mode 2).
+ *
+ * Errors, before the device is touched: h == NULL, a negative count, a NULL array with a positive count, stride_floats
+ * neither 3 nor 4, offsets that decrease (or pt_off[0] != 0), a config value that is not finite and positive (delta_r may
+ * be 0), min_range >= max_range, a node_label outside [0, 2^31), a negative min_seg or min_instance_points:
+ * SGTD_ERR_INVALID.  More than SGTD_SCAN_MAX_SCANS scans or SGTD_SCAN_MAX_POINTS points in a batch, more than 1024
+ * azimuth cells (width), pitch layers (180 / delta_p + 2) or rings: SGTD_ERR_UNSUPPORTED (sgtd_last_error says which).
+ * The ring sequence qualifies when some n <= 1024 has every increment start_r - s * delta_r > 0 for s <= n and the
+ * increments sum to at least max_range - min_range (the defaults need 466, and 470 to reach 120 m from 0).  The getters before a successful run:
+ * SGTD_ERR_STATE; more than capacity: SGTD_ERR_CAPACITY (*n = the size needed, the first `capacity` entries written). */
+#define SGTD_SCAN_MAX_CLASSES 32
+#define SGTD_SCAN_MAX_SCANS 4096
+#define SGTD_SCAN_MAX_POINTS (1 << 28)
+#define SGTD_SCAN_MAX_CELLS 1024
+typedef struct sgtd_scan_config {
+  int32_t node_label[SGTD_SCAN_MAX_CLASSES]; /* semantic label s -> keypoint label; 0: class dropped */
+  int32_t min_seg[SGTD_SCAN_MAX_CLASSES];    /* voxel mode: smallest cluster kept (minSeg)            */
+  int32_t min_instance_points;               /* instance mode: kept when count > this (20)            */
+  int32_t reserved;
+  double start_r, delta_r, delta_p, delta_a; /* 0.35, 0.0004, 1.2, 1.2 (get_json.cpp:205-208)         */
+  double min_range, max_range;               /* 0.5, 120.0 (cluster_manager.hpp:198)                  */
+} sgtd_scan_config;
+/* node_label[10..18] = 3..11, else 0 (the net effect of get_json.cpp:10-12,137,288); min_seg[15] = min_seg[17] =
+ * min_seg[18] = 5, else 300 (get_json.cpp:164,178-181) */
+void sgtd_default_scan_config(sgtd_scan_config *cfg);
+/* the config part of sgtd_scan_keypoints' checks, without a handle (host code, no device needed): SGTD_OK,
+ * SGTD_ERR_INVALID or SGTD_ERR_UNSUPPORTED; *why (may be NULL) names the reason, a static string */
+int sgtd_scan_config_check(const sgtd_scan_config *cfg /* NULL = defaults */, const char **why);
+int sgtd_scan_keypoints(sgtd_handle h, const sgtd_scan_config *cfg /* NULL = defaults */, const float *points,
+                        int stride_floats /* 3, or 4 = x y z i */, const uint32_t *labels, const int64_t *pt_off /* host, n_scans + 1 */,
+                        int n_scans, int device_ptrs);
+/* kp_off [n_scans + 1]; xyz [capacity * 3], label, n_points [capacity]; any array may be NULL */
+int sgtd_result_scan_keypoints(sgtd_handle h, int64_t *kp_off, float *xyz, uint32_t *label, int32_t *n_points, int64_t capacity,
+                               int64_t *n_keypoints);
+int sgtd_result_scan_point_clusters(sgtd_handle h, int scan, int32_t *cluster, int64_t capacity, int64_t *n);
+int sgtd_result_scan_grids(sgtd_handle h, int scan, int32_t *grid /*[32*4]*/, double *range /*[32*4]*/);
+int sgtd_scan_device_view(sgtd_handle h, const float **d_xyz, const uint32_t **d_label);
+/* points per tile (workgroup) of the per-point passes: the tests place their edges there */
+void sgtd_scan_tiles(int *point_tile);
+
 /* Page-locked host memory for the destination buffers of the fetch calls (sgtd_fetch_entries,
  * sgtd_result_pairs, ...): a copy into it is one direct DMA transfer — pageable memory goes through the
  * runtime's staging at about a third of the rate.  Allocation is slow (milliseconds): keep the buffers

@@ -39,6 +39,8 @@ SYMBOLS = [
     "sgtd_default_relax_options", "sgtd_relax_poses", "sgtd_result_relaxed",
     "sgtd_pose_consensus_rows", "sgtd_pose_consensus", "sgtd_result_consensus", "sgtd_result_consensus_rows",
     "sgtd_search_loop_consensus", "sgtd_result_consensus_edges",
+    "sgtd_default_scan_config", "sgtd_scan_config_check", "sgtd_scan_keypoints", "sgtd_result_scan_keypoints", "sgtd_result_scan_point_clusters",
+    "sgtd_result_scan_grids", "sgtd_scan_device_view", "sgtd_scan_tiles",
 ]
 
 
@@ -103,6 +105,17 @@ class RelaxReport(C.Structure):
     """sgtd_relax_report"""
     _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("lambda_", C.c_double),
                 ("outer_iterations", C.c_int32), ("steps_accepted", C.c_int32), ("cg_iterations", C.c_int32), ("status", C.c_int32)]
+
+
+SCAN_MAX_CLASSES = 32
+
+
+class ScanConfig(C.Structure):
+    """sgtd_scan_config"""
+    _fields_ = [("node_label", C.c_int32 * SCAN_MAX_CLASSES), ("min_seg", C.c_int32 * SCAN_MAX_CLASSES),
+                ("min_instance_points", C.c_int32), ("reserved", C.c_int32),
+                ("start_r", C.c_double), ("delta_r", C.c_double), ("delta_p", C.c_double), ("delta_a", C.c_double),
+                ("min_range", C.c_double), ("max_range", C.c_double)]
 
 
 def build_library(force=False):
@@ -196,6 +209,16 @@ def lib():
     L.sgtd_result_consensus_rows.argtypes = [vp, C.c_int, vp, vp, vp]
     L.sgtd_search_loop_consensus.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.sgtd_result_consensus_edges.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_default_scan_config.argtypes = [C.POINTER(ScanConfig)]
+    L.sgtd_default_scan_config.restype = None
+    L.sgtd_scan_config_check.argtypes = [C.POINTER(ScanConfig), C.POINTER(C.c_char_p)]
+    L.sgtd_scan_keypoints.argtypes =[vp, C.POINTER(ScanConfig), vp, C.c_int, vp, vp, C.c_int, C.c_int]
+    L.sgtd_result_scan_keypoints.argtypes = [vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_scan_point_clusters.argtypes = [vp, C.c_int, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_scan_grids.argtypes = [vp, C.c_int, vp, vp]
+    L.sgtd_scan_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sgtd_scan_tiles.argtypes = [C.POINTER(C.c_int)]
+    L.sgtd_scan_tiles.restype = None
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

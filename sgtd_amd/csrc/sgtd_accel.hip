@@ -34,6 +34,7 @@
 #include "consistency_kernels.hip.h"
 #include "relax_kernels.hip.h"
 #include "consensus_kernels.hip.h"
+#include "scan_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -324,6 +325,16 @@ struct sgtd_engine {
   std::vector<int> rx_host_csr;
   std::vector<double> rx_host_w;
   std::vector<unsigned char> rx_host_held;
+  // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (SK_*: scan_run).  sk_n < 0:
+  // no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets on the host
+  enum { SK_PTS = 0, SK_LAB, SK_OFF, SK_SC, SK_R, SK_PITCH, SK_AZI, SK_MM, SK_VOTE, SK_GRID, SK_RANGE, SK_BOUNDS, SK_KEY_A, SK_KEY_B, SK_VAL_A, SK_VAL_B,
+         SK_FLAGS, SK_EXCL, SK_COUNTS, SK_VKEY, SK_VSTART, SK_NBR, SK_NBR_CNT, SK_PARENT, SK_CHANGED, SK_CCOUNT, SK_CMIN, SK_CKEY_A, SK_CKEY_B, SK_CVAL_A,
+         SK_CVAL_B, SK_KP_OFF, SK_CL_OF_ROOT, SK_KCOUNT, SK_CSTART, SK_PKEY_A, SK_PKEY_B, SK_PVAL_A, SK_PVAL_B, SK_CLUSTER, SK_XYZ, SK_LABEL, SK_NPOINTS,
+         SK_BUFS };
+  DevBuf sk[SK_BUFS];
+  int sk_n = -1;
+  int64_t sk_points = 0, sk_kept = 0;
+  std::vector<int64_t> sk_off, sk_kp_off;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -2213,6 +2224,7 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->cs_in, &e->cs_out,
                     &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl};
   for (DevBuf *b : bufs) free_buf(*b);
+  for (DevBuf &b : e->sk) free_buf(b);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto &b : e->scan_lvl) free_buf(b);
@@ -4876,6 +4888,337 @@ int sgtd_result_relaxed(sgtd_handle e, double *pose, double *edge_cost) {
         for (int k = 0; k < 3; k++) pose[v * 12 + r * 4 + k] = rec[v * SGTD_RELAX_REC + 7 + r * 3 + k];
         pose[v * 12 + r * 4 + 3] = rec[v * SGTD_RELAX_REC + 4 + r];
       }
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_scan_keypoints: labelled scans to keypoints on the device (scan_kernels.hip.h) ----
+namespace {
+
+int scan_bits(u64 v) { int b = 0; while (v) { b++; v >>= 1; } return std::max(b, 1); }
+
+// the ring envelope: some n <= SGTD_SCAN_MAX_CELLS has every increment start_r - s * delta_r > 0 for s <= n and the
+// increments sum to at least max_range - min_range
+bool scan_rings_fit(const sgtd_scan_config &c) {
+  double sum = 0.0;
+  for (int s = 1; s <= SGTD_SCAN_MAX_CELLS; s++) {
+    const double inc = c.start_r - (double)s * c.delta_r;
+    if (!(inc > 0.0)) return false;
+    sum += inc;
+    if (sum >= c.max_range - c.min_range) return true;
+  }
+  return false;
+}
+
+int scan_run(sgtd_engine *e, const ScanCfgDev &C, const float *points, int stride, const uint32_t *labels, const int64_t *pt_off, int S,
+             int device_ptrs) {
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  const long long P = pt_off[S];
+  const int n_sc = S * 32;
+  auto buf = [&](int k, size_t bytes) { return ensure(e, e->sk[k], std::max<size_t>(bytes, 16)); };
+  const size_t np = (size_t)P;
+  e->sk_off.assign(pt_off, pt_off + S + 1);
+  e->sk_kp_off.assign((size_t)S + 1, 0);
+  e->sk_points = P; e->sk_kept = 0;
+  CHK(buf(sgtd_engine::SK_GRID, (size_t)std::max(n_sc, 1) * 4 * sizeof(int)));
+  CHK(buf(sgtd_engine::SK_RANGE, (size_t)std::max(n_sc, 1) * 4 * sizeof(double)));
+  CHK(buf(sgtd_engine::SK_XYZ, 16));
+  CHK(buf(sgtd_engine::SK_LABEL, 16));
+  if (S == 0 || P == 0) {
+    if (n_sc > 0) {
+      HIPCHK(hipMemsetAsync(e->sk[sgtd_engine::SK_GRID].p, 0, (size_t)n_sc * 4 * sizeof(int), e->stream));
+      HIPCHK(hipMemsetAsync(e->sk[sgtd_engine::SK_RANGE].p, 0, (size_t)n_sc * 4 * sizeof(double), e->stream));
+    }
+    return xfer_sync(e);
+  }
+  const float *d_pts = points;
+  const u32 *d_lab = labels;
+  if (!device_ptrs) {
+    CHK(buf(sgtd_engine::SK_PTS, np * stride * sizeof(float)));
+    CHK(buf(sgtd_engine::SK_LAB, np * sizeof(u32)));
+    CHK(h2d(e, e->sk[sgtd_engine::SK_PTS].p, points, np * stride * sizeof(float)));
+    CHK(h2d(e, e->sk[sgtd_engine::SK_LAB].p, labels, np * sizeof(u32)));
+    d_pts = e->sk[sgtd_engine::SK_PTS].as<float>();
+    d_lab = e->sk[sgtd_engine::SK_LAB].as<u32>();
+  }
+  CHK(buf(sgtd_engine::SK_OFF, ((size_t)S + 1) * sizeof(long long)));
+  CHK(h2d(e, e->sk[sgtd_engine::SK_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(buf(sgtd_engine::SK_SC, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_R, np * sizeof(double)));
+  CHK(buf(sgtd_engine::SK_PITCH, np * sizeof(double)));
+  CHK(buf(sgtd_engine::SK_AZI, np * sizeof(double)));
+  CHK(buf(sgtd_engine::SK_MM, (size_t)n_sc * 4 * sizeof(u64)));
+  CHK(buf(sgtd_engine::SK_VOTE, (size_t)n_sc * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_BOUNDS, (size_t)n_sc * SGTD_SCAN_CELLS * sizeof(double)));
+  CHK(buf(sgtd_engine::SK_KEY_A, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::SK_KEY_B, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::SK_VAL_A, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_VAL_B, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_FLAGS, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_EXCL, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_COUNTS, 4 * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_VKEY, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::SK_VSTART, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_NBR, np * SGTD_SCAN_NBR * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_NBR_CNT, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_PARENT, np * sizeof(u32)));
+  constexpr int kMaxRounds = 4096, kGroup = 8;
+  CHK(buf(sgtd_engine::SK_CHANGED, kMaxRounds * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_CCOUNT, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_CMIN, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_CKEY_A, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::SK_CKEY_B, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::SK_CVAL_A, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_CVAL_B, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_KP_OFF, ((size_t)S + 1) * sizeof(long long)));
+  CHK(buf(sgtd_engine::SK_CL_OF_ROOT, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_PKEY_A, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_PKEY_B, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_PVAL_A, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_PVAL_B, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_CLUSTER, np * sizeof(int)));
+  auto *B = e->sk;
+  const hipStream_t st = e->stream;
+  const int gp = grid_for(P, 256);
+  const long long *d_off = B[sgtd_engine::SK_OFF].as<long long>();
+  int *grid = B[sgtd_engine::SK_GRID].as<int>();
+  double *range = B[sgtd_engine::SK_RANGE].as<double>(), *bounds = B[sgtd_engine::SK_BOUNDS].as<double>();
+
+  // per point, per (scan, class), keys
+  scan_init_kernel<<<grid_for(n_sc, 256), 256, 0, st>>>(B[sgtd_engine::SK_MM].as<u64>(), B[sgtd_engine::SK_VOTE].as<u32>(), n_sc);
+  ScanPointParams PP;
+  PP.pts = d_pts; PP.stride = stride; PP.labels = d_lab; PP.pt_off = d_off; PP.n = P;
+  PP.sc_of = B[sgtd_engine::SK_SC].as<u32>(); PP.r = B[sgtd_engine::SK_R].as<double>(); PP.pitch = B[sgtd_engine::SK_PITCH].as<double>();
+  PP.azimuth = B[sgtd_engine::SK_AZI].as<double>(); PP.mm = B[sgtd_engine::SK_MM].as<u64>(); PP.vote = B[sgtd_engine::SK_VOTE].as<u32>();
+  scan_point_kernel<<<grid_for(P, SGTD_SCAN_TILE), 256, 0, st>>>(PP, C);
+  scan_rings_kernel<<<grid_for(n_sc, 64), 64, 0, st>>>(PP.mm, PP.vote, n_sc, C, grid, range, bounds);
+  u64 *kin = B[sgtd_engine::SK_KEY_A].as<u64>(), *kout = B[sgtd_engine::SK_KEY_B].as<u64>();
+  u32 *vin = B[sgtd_engine::SK_VAL_A].as<u32>(), *vout = B[sgtd_engine::SK_VAL_B].as<u32>();
+  scan_keys_kernel<<<gp, 256, 0, st>>>(PP.sc_of, d_lab, PP.r, PP.pitch, PP.azimuth, grid, range, bounds, C, P, kin, vin);
+  HIPCHK(hipGetLastError());
+  CHK(radix_sort_pairs<u64>(e, kin, kout, vin, vout, P, 38 + scan_bits((u64)S), false));
+
+  // voxels, links, components
+  u32 *flags = B[sgtd_engine::SK_FLAGS].as<u32>(), *excl = B[sgtd_engine::SK_EXCL].as<u32>(), *counts = B[sgtd_engine::SK_COUNTS].as<u32>();
+  const u32 *n_vox_p = excl + P;
+  u64 *vkey = B[sgtd_engine::SK_VKEY].as<u64>();
+  u32 *vstart = B[sgtd_engine::SK_VSTART].as<u32>(), *nbr = B[sgtd_engine::SK_NBR].as<u32>(), *nbr_cnt = B[sgtd_engine::SK_NBR_CNT].as<u32>();
+  u32 *parent = B[sgtd_engine::SK_PARENT].as<u32>(), *changed = B[sgtd_engine::SK_CHANGED].as<u32>();
+  u32 *ccount = B[sgtd_engine::SK_CCOUNT].as<u32>(), *cmin = B[sgtd_engine::SK_CMIN].as<u32>();
+  HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(u32), st));
+  HIPCHK(hipMemsetAsync(changed, 0, kMaxRounds * sizeof(u32), st));
+  HIPCHK(hipMemsetAsync(ccount, 0, np * sizeof(u32), st));
+  HIPCHK(hipMemsetAsync(cmin, 0xFF, np * sizeof(u32), st));
+  HIPCHK(hipMemsetAsync(B[sgtd_engine::SK_CL_OF_ROOT].p, 0xFF, np * sizeof(u32), st));
+  scan_heads_kernel<<<grid_for(P + 1, 256), 256, 0, st>>>(kin, P, (u64)S << 38, flags, counts);
+  HIPCHK(hipGetLastError());
+  CHK(device_scan(e, flags, excl, P + 1));
+  scan_voxels_kernel<<<gp, 256, 0, st>>>(kin, flags, excl, P, counts, vkey, vstart);
+  scan_links_kernel<<<gp, 256, 0, st>>>(vkey, n_vox_p, grid, nbr, nbr_cnt, parent);
+  HIPCHK(hipGetLastError());
+  bool settled = false;
+  std::vector<u32> ch(kGroup);
+  for (int r0 = 0; r0 < kMaxRounds && !settled; r0 += kGroup) {
+    for (int r = r0; r < r0 + kGroup; r++) {
+      scan_hook_kernel<<<gp, 256, 0, st>>>(n_vox_p, nbr, nbr_cnt, parent, changed, r);
+      scan_jump_kernel<<<gp, 256, 0, st>>>(n_vox_p, parent, changed, r);
+    }
+    HIPCHK(hipGetLastError());
+    CHK(d2h(e, ch.data(), changed + r0, kGroup * sizeof(u32)));
+    CHK(xfer_sync(e));
+    for (int r = 0; r < kGroup; r++) settled = settled || ch[r] == 0;
+  }
+  if (!settled) { e->err = "sgtd_scan_keypoints: the components did not settle in " + std::to_string(kMaxRounds) + " rounds"; return SGTD_ERR_UNSUPPORTED; }
+  scan_component_kernel<<<gp, 256, 0, st>>>(n_vox_p, parent, vstart, vin, ccount, cmin);
+
+  // kept clusters in keypoint order, the offsets
+  u64 *ckin = B[sgtd_engine::SK_CKEY_A].as<u64>(), *ckout = B[sgtd_engine::SK_CKEY_B].as<u64>();
+  u32 *cvin = B[sgtd_engine::SK_CVAL_A].as<u32>(), *cvout = B[sgtd_engine::SK_CVAL_B].as<u32>();
+  scan_cluster_keys_kernel<<<gp, 256, 0, st>>>(n_vox_p, vkey, parent, ccount, cmin, grid, C, ckin, cvin);
+  HIPCHK(hipGetLastError());
+  CHK(radix_sort_pairs<u64>(e, ckin, ckout, cvin, cvout, P, 37 + scan_bits((u64)S), false, n_vox_p));
+  long long *d_kp_off = B[sgtd_engine::SK_KP_OFF].as<long long>();
+  scan_offsets_kernel<<<grid_for(S + 1, 256), 256, 0, st>>>(ckin, n_vox_p, S, d_kp_off);
+  HIPCHK(hipGetLastError());
+  CHK(d2h(e, e->sk_kp_off.data(), d_kp_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(xfer_sync(e));
+  const long long K = e->sk_kp_off[(size_t)S];
+  e->sk_kept = K;
+
+  // the points by keypoint, the centres
+  CHK(buf(sgtd_engine::SK_KCOUNT, (size_t)std::max<long long>(K, 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_CSTART, (size_t)std::max<long long>(K, 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_XYZ, (size_t)std::max<long long>(K, 1) * 3 * sizeof(float)));
+  CHK(buf(sgtd_engine::SK_LABEL, (size_t)std::max<long long>(K, 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::SK_NPOINTS, (size_t)std::max<long long>(K, 1) * sizeof(int)));
+  u32 *kcount = B[sgtd_engine::SK_KCOUNT].as<u32>(), *cstart = B[sgtd_engine::SK_CSTART].as<u32>();
+  u32 *cl_of_root = B[sgtd_engine::SK_CL_OF_ROOT].as<u32>();
+  if (K > 0)
+    scan_cluster_ids_kernel<<<grid_for(K, 256), 256, 0, st>>>(ckin, cvin, (u32)K, ccount, C, cl_of_root, kcount, B[sgtd_engine::SK_NPOINTS].as<int>(),
+                                                             B[sgtd_engine::SK_LABEL].as<u32>());
+  u32 *pkin = B[sgtd_engine::SK_PKEY_A].as<u32>(), *pkout = B[sgtd_engine::SK_PKEY_B].as<u32>();
+  u32 *pvin = B[sgtd_engine::SK_PVAL_A].as<u32>(), *pvout = B[sgtd_engine::SK_PVAL_B].as<u32>();
+  scan_point_clusters_kernel<<<gp, 256, 0, st>>>(kin, vin, flags, excl, counts, parent, cl_of_root, d_kp_off, P, (u32)K, pkin, pvin,
+                                                 B[sgtd_engine::SK_CLUSTER].as<int>());
+  HIPCHK(hipGetLastError());
+  if (K > 0) {
+    CHK(radix_sort_pairs<u32>(e, pkin, pkout, pvin, pvout, P, scan_bits((u64)K), false));
+    CHK(device_scan(e, kcount, cstart, K));
+    float *xyz = B[sgtd_engine::SK_XYZ].as<float>();
+    scan_sum_wave_kernel<<<grid_for(K, 4), 256, 0, st>>>(d_pts, stride, pvin, cstart, kcount, (u32)K, xyz);
+    scan_sum_block_kernel<<<(unsigned)K, 256, 0, st>>>(d_pts, stride, pvin, cstart, kcount, xyz);
+    HIPCHK(hipGetLastError());
+  }
+  // (the caller's arrays are read for the last time by the sums: the call returns when they are done)
+  return xfer_sync(e);
+}
+
+sgtd_engine *scan_engine(sgtd_engine *e) { return e->grp ? multi::device_handle(e, 0) : e; }
+
+int scan_ready(sgtd_engine *e, sgtd_engine **out) {
+  sgtd_engine *c = scan_engine(e);
+  if (c->sk_n < 0) { e->err = "no scan keypoints: sgtd_scan_keypoints has not run"; return SGTD_ERR_STATE; }
+  *out = c;
+  return SGTD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sgtd_scan_tiles(int *point_tile) {
+  if (point_tile) *point_tile = SGTD_SCAN_TILE;
+}
+
+void sgtd_default_scan_config(sgtd_scan_config *cfg) {
+  if (!cfg) return;
+  std::memset(cfg, 0, sizeof(*cfg));
+  for (int s = 0; s < SGTD_SCAN_MAX_CLASSES; s++) cfg->min_seg[s] = 300;
+  for (int s = 10; s <= 18; s++) cfg->node_label[s] = s - 7;
+  cfg->min_seg[15] = cfg->min_seg[17] = cfg->min_seg[18] = 5;
+  cfg->min_instance_points = 20;
+  cfg->start_r = 0.35; cfg->delta_r = 0.0004; cfg->delta_p = 1.2; cfg->delta_a = 1.2;
+  cfg->min_range = 0.5; cfg->max_range = 120.0;
+}
+
+int sgtd_scan_config_check(const sgtd_scan_config *cfg, const char **why) {
+  const char *dummy;
+  if (!why) why = &dummy;
+  *why = "";
+  sgtd_scan_config c;
+  sgtd_default_scan_config(&c);
+  if (cfg) c = *cfg;
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  *why = "a config value is not finite and positive, min_range >= max_range, or a label or count is negative";
+  if (!pos(c.start_r) || !(std::isfinite(c.delta_r) && c.delta_r >= 0.0) || !pos(c.delta_p) || !pos(c.delta_a) || !pos(c.min_range) ||
+      !pos(c.max_range) || c.min_range >= c.max_range || c.min_instance_points < 0)
+    return SGTD_ERR_INVALID;
+  for (int s = 0; s < SGTD_SCAN_MAX_CLASSES; s++)
+    if (c.node_label[s] < 0 || c.min_seg[s] < 0) return SGTD_ERR_INVALID;
+  *why = "delta_a gives more than 1024 azimuth cells";
+  if (!(std::round(360.0 / c.delta_a) + 1.0 <= (double)SGTD_SCAN_MAX_CELLS)) return SGTD_ERR_UNSUPPORTED;
+  *why = "delta_p gives more than 1024 pitch layers";
+  if (!(180.0 / c.delta_p + 2.0 <= (double)SGTD_SCAN_MAX_CELLS)) return SGTD_ERR_UNSUPPORTED;
+  *why = "start_r and delta_r do not cover the range gate with at most 1024 rings of positive width";
+  if (!scan_rings_fit(c)) return SGTD_ERR_UNSUPPORTED;
+  *why = "";
+  return SGTD_OK;
+}
+
+int sgtd_scan_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const float *points, int stride_floats, const uint32_t *labels,
+                        const int64_t *pt_off, int n_scans, int device_ptrs) {
+  if (!e || n_scans < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  sgtd_scan_config c;
+  sgtd_default_scan_config(&c);
+  if (cfg) c = *cfg;
+  const char *why = nullptr;
+  const int cs = sgtd_scan_config_check(&c, &why);
+  if (cs == SGTD_ERR_INVALID) return cs;
+  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
+  for (int s = 0; s < n_scans; s++)
+    if (pt_off[s + 1] < pt_off[s]) return SGTD_ERR_INVALID;
+  const int64_t P = pt_off[n_scans];
+  if (P > 0 && (!points || !labels)) return SGTD_ERR_INVALID;
+  if (n_scans > SGTD_SCAN_MAX_SCANS || P > SGTD_SCAN_MAX_POINTS) {
+    e->err = "sgtd_scan_keypoints takes at most " + std::to_string(SGTD_SCAN_MAX_SCANS) + " scans and " + std::to_string(SGTD_SCAN_MAX_POINTS) +
+             " points in one call";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (cs != SGTD_OK) {
+    e->err = std::string("sgtd_scan_keypoints: ") + why;
+    return cs;
+  }
+  sgtd_engine *k = scan_engine(e);
+  k->sk_n = -1;
+  PinScope pin_scope(k);
+  ScanCfgDev C;
+  for (int s = 0; s < 32; s++) { C.node_label[s] = c.node_label[s]; C.min_seg[s] = c.min_seg[s]; }
+  C.min_inst = c.min_instance_points; C.n_scans = n_scans;
+  C.start_r = c.start_r; C.delta_r = c.delta_r; C.delta_p = c.delta_p; C.delta_a = c.delta_a; C.min_range = c.min_range; C.max_range = c.max_range;
+  const int rc = scan_run(k, C, points, stride_floats, labels, pt_off, n_scans, device_ptrs);
+  if (rc != SGTD_OK) {
+    if (k != e) e->err = k->err;
+    return rc;
+  }
+  k->sk_n = n_scans;
+  return SGTD_OK;
+}
+
+int sgtd_result_scan_keypoints(sgtd_handle e, int64_t *kp_off, float *xyz, uint32_t *label, int32_t *n_points, int64_t capacity, int64_t *n_keypoints) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(scan_ready(e, &c));
+  const int64_t K = c->sk_kept;
+  if (n_keypoints) *n_keypoints = K;
+  if (kp_off) std::memcpy(kp_off, c->sk_kp_off.data(), c->sk_kp_off.size() * sizeof(int64_t));
+  const size_t m = (size_t)std::min(K, capacity);
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && xyz && m) st = d2h(c, xyz, c->sk[sgtd_engine::SK_XYZ].p, m * 3 * sizeof(float));
+  if (st == SGTD_OK && label && m) st = d2h(c, label, c->sk[sgtd_engine::SK_LABEL].p, m * sizeof(u32));
+  if (st == SGTD_OK && n_points && m) st = d2h(c, n_points, c->sk[sgtd_engine::SK_NPOINTS].p, m * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return K > capacity && (xyz || label || n_points) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_scan_point_clusters(sgtd_handle e, int scan, int32_t *cluster, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(scan_ready(e, &c));
+  if (scan < 0 || scan >= c->sk_n) return SGTD_ERR_INVALID;
+  const int64_t first = c->sk_off[(size_t)scan], need = c->sk_off[(size_t)scan + 1] - first;
+  if (n) *n = need;
+  const size_t m = cluster ? (size_t)std::min(need, capacity) : 0;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && m) st = d2h(c, cluster, c->sk[sgtd_engine::SK_CLUSTER].as<int>() + first, m * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return need > capacity && cluster ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_scan_grids(sgtd_handle e, int scan, int32_t *grid, double *range) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(scan_ready(e, &c));
+  if (scan < 0 || scan >= c->sk_n) return SGTD_ERR_INVALID;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && grid) st = d2h(c, grid, c->sk[sgtd_engine::SK_GRID].as<int>() + (size_t)scan * 128, 128 * sizeof(int));
+  if (st == SGTD_OK && range) st = d2h(c, range, c->sk[sgtd_engine::SK_RANGE].as<double>() + (size_t)scan * 128, 128 * sizeof(double));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return SGTD_OK;
+}
+
+int sgtd_scan_device_view(sgtd_handle e, const float **d_xyz, const uint32_t **d_label) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(scan_ready(e, &c));
+  if (d_xyz) *d_xyz = c->sk[sgtd_engine::SK_XYZ].as<float>();
+  if (d_label) *d_label = c->sk[sgtd_engine::SK_LABEL].as<u32>();
   return SGTD_OK;
 }
 

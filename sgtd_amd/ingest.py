@@ -128,3 +128,14 @@ def write_cache(cache_path, xyz, label, pose12):
         fh.write(np.ascontiguousarray(pose12, np.float32).reshape(f, 12).tobytes())
         fh.write(np.ascontiguousarray(label).astype(np.uint32).reshape(f * n).tobytes())
         fh.write(xyz.reshape(f * n * 3).tobytes())
+
+
+def read_scan(bin_path, label_path):
+    """a LiDAR scan and its per-point labels in the SemanticKITTI layouts the reference's producer reads
+    (src/sgtd/src/get_json.cpp:41-343): .bin = f32 x y z intensity per point, .label = u32 sem | inst << 16 per point.
+    Returns points (n, 4) f32 and labels (n,) u32 — what STDescManager.scan_keypoints takes."""
+    points = np.fromfile(bin_path, dtype=np.float32)
+    labels = np.fromfile(label_path, dtype=np.uint32)
+    if points.size % 4 or points.size // 4 != labels.size:
+        raise ValueError("%s holds %d floats, %s %d labels: not one x y z i row per label" % (bin_path, points.size, label_path, labels.size))
+    return points.reshape(-1, 4), labels

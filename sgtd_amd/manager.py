@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, DescSoa, RelaxOptions, RelaxReport, SgtdError, Stats
+from ._lib import Config, DescSoa, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats
 
 DEFAULTS = dict(descriptor_near_num=10, candidate_num=50, max_frame_n=20000, device_id=0,
                 descriptor_min_len=0.5, descriptor_max_len=50.0, std_side_resolution=1.0,
@@ -554,6 +554,111 @@ class STDescManager:
         res = BatchResult(*(np.concatenate([getattr(r, k) for r in parts]) for k in ("n_cand", "cand_frame", "cand_votes", "pair_off")),
                           c0 + np.arange(nf, dtype=np.int64))
         return res
+
+    # ---- labelled scans to keypoints (sgtd_scan_keypoints) --------------------------------------------------
+    def default_scan_config(self):
+        c = ScanConfig()
+        self._L.sgtd_default_scan_config(C.byref(c))
+        return c
+
+    def _scan_config(self, config):
+        """None, a ScanConfig, or a dict of the fields to change from the defaults (arrays: whole, or {class: value})"""
+        if config is None or isinstance(config, ScanConfig):
+            return config
+        c = self.default_scan_config()
+        for k, v in dict(config).items():
+            if k in ("node_label", "min_seg"):
+                arr = getattr(c, k)
+                items = v.items() if isinstance(v, dict) else enumerate(v)
+                for s, x in items:
+                    arr[int(s)] = int(x)
+            else:
+                setattr(c, k, v)
+        return c
+
+    def scan_keypoints(self, points, labels, pt_off=None, config=None, fetch=True):
+        """labelled scans to keypoints on the device (sgtd_scan_keypoints): points (total, 3 or 4) f32 — or (S, N, 3 or 4)
+        with pt_off None — numpy or torch.cuda tensor, labels u32 (sem | inst << 16), pt_off the S + 1 offsets.  Returns
+        xyz (K, 3) f32, label (K,) u32, kp_off (S + 1,) i64 and n_points (K,) i32; fetch=False leaves them on the device
+        (scan_results, add_scans, query_scans)."""
+        is_torch = hasattr(points, "data_ptr")
+        if is_torch:
+            assert points.is_cuda and labels.is_cuda and points.is_contiguous() and labels.is_contiguous()
+            shape = tuple(points.shape)
+            pp, lp, dev = C.c_void_p(points.data_ptr()), C.c_void_p(labels.data_ptr()), 1
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            labels = np.ascontiguousarray(labels, dtype=np.uint32)
+            shape = points.shape
+            pp, lp, dev = _p(points), _p(labels), 0
+        if len(shape) < 2 or shape[-1] not in (3, 4):
+            raise ValueError("points: (total, 3 or 4) or (S, N, 3 or 4)")
+        if pt_off is None:
+            if len(shape) != 3:
+                raise ValueError("points: (S, N, 3 or 4), or pt_off")
+            off = np.arange(shape[0] + 1, dtype=np.int64) * shape[1]
+        else:
+            off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+            if off.size < 1:
+                raise ValueError("pt_off: n_scans + 1 offsets")
+            if off[-1] > int(np.prod(shape[:-1])):
+                raise ValueError("pt_off names more points than were given")
+        cfg = self._scan_config(config)
+        self._scan_n = off.size - 1
+        self._check(self._L.sgtd_scan_keypoints(self._h, C.byref(cfg) if cfg is not None else None, pp, int(shape[-1]), lp, _p(off),
+                                                off.size - 1, dev))
+        return self.scan_results() if fetch else None
+
+    def scan_results(self):
+        n = C.c_int64(0)
+        off = np.zeros(self._scan_n + 1, np.int64)
+        st = self._L.sgtd_result_scan_keypoints(self._h, _p(off), None, None, None, 0, C.byref(n))
+        self._check(st)
+        k = n.value
+        xyz, label, n_points = np.zeros((k, 3), np.float32), np.zeros(k, np.uint32), np.zeros(k, np.int32)
+        self._check(self._L.sgtd_result_scan_keypoints(self._h, _p(off), _p(xyz), _p(label), _p(n_points), k, C.byref(n)))
+        return xyz, label, off, n_points
+
+    def scan_point_clusters(self, scan):
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_scan_point_clusters(self._h, int(scan), None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        self._check(self._L.sgtd_result_scan_point_clusters(self._h, int(scan), _p(out), n.value, C.byref(n)))
+        return out
+
+    def scan_grids(self, scan):
+        """(32, 4) i32 mode, polarNum, width, height and (32, 4) f64 minPitch, maxPitch, minPolar, maxPolar of one scan"""
+        grid, rng = np.zeros((32, 4), np.int32), np.zeros((32, 4), np.float64)
+        self._check(self._L.sgtd_result_scan_grids(self._h, int(scan), _p(grid), _p(rng)))
+        return grid, rng
+
+    def _scan_view(self):
+        """the scan keypoints as add_frames / query_frames arguments: xyz, label, offsets, device_ptrs — borrowed device
+        pointers, except on a multi-device handle, whose tables take host arrays"""
+        if self.device_count > 1:
+            xyz, label, off, _ = self.scan_results()
+            self._keep = (xyz, label)
+            return _p(xyz), _p(label), off, 0
+        x, l = C.c_void_p(), C.c_void_p()
+        self._check(self._L.sgtd_scan_device_view(self._h, C.byref(x), C.byref(l)))
+        off = np.zeros(self._scan_n + 1, np.int64)
+        self._check(self._L.sgtd_result_scan_keypoints(self._h, _p(off), None, None, None, 0, None))
+        return x, l, off, 1
+
+    def add_scans(self, points, labels, pt_off=None, config=None):
+        """scan_keypoints, then add_frames on the keypoints where they lie on the device; returns their offsets"""
+        self.scan_keypoints(points, labels, pt_off, config, fetch=False)
+        x, l, off, dev = self._scan_view()
+        self._check(self._L.sgtd_add_frames(self._h, x, l, _p(off), off.size - 1, dev))
+        return off
+
+    def query_scans(self, points, labels, pt_off=None, config=None, fetch=True):
+        """scan_keypoints, then query_frames on the keypoints where they lie on the device"""
+        self.scan_keypoints(points, labels, pt_off, config, fetch=False)
+        x, l, off, dev = self._scan_view()
+        self._nq = off.size - 1
+        self._check(self._L.sgtd_query_frames(self._h, x, l, _p(off), self._nq, dev))
+        return self.results() if fetch else None
 
     def results(self):
         nq, cn = self._nq, self.config_setting_["candidate_num"]

@@ -333,3 +333,91 @@ def make_skewed_queries(world, n_queries, stream=1, sigma=0.05, shift_sigma=0.5)
     n_kp = rng.integers(world._kp[0], world._kp[1] + 1, n_queries)
     xyz, label, off = _observe_ragged(world.landmarks, world.landmark_label, world._tree, pose, n_kp, sigma, rng)
     return RaggedFrames(xyz, label, off, pose, gt.astype(np.int64))
+
+
+# ---- labelled scans (what sgtd_scan_keypoints takes: points f32 x y z i, labels u32 sem | inst << 16) ----
+SCAN_CLASSES = (10, 11, 13, 15, 16, 17, 18)     # semantic classes the default scan config keeps (get_json.cpp:10-12)
+
+
+def _c_round(v):
+    t = np.trunc(v)
+    return t + np.where(np.abs(v - t) >= 0.5, np.sign(v), 0.0)
+
+
+def scan_clear_of_boundaries(points, labels, margin=1e-9, delta_p=1.2, delta_a=1.2, start_r=0.35, delta_r=0.0004,
+                             min_range=0.5, max_range=120.0):
+    """true when no point of a scan lies within `margin` of a rounding boundary of the scan rule (include/sgtd_accel.h):
+    pitch and azimuth cells, ring bounds, the range gates and the pitch span's layer count, per semantic class"""
+    p = np.asarray(points, np.float32)[:, :3].astype(np.float64)
+    sem = np.asarray(labels, np.uint32) & 0xFFFF
+    r = np.sqrt((p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]) + p[:, 2] * p[:, 2])
+    if np.any(np.abs(r - max_range) < margin) or np.any(np.abs(r - min_range) < margin):
+        return False
+    ok = ~(r >= max_range) & ~(r <= min_range) & np.isfinite(p).all(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pitch = (np.arcsin(p[:, 2] / r) * 180.0) / np.pi
+    a = np.arctan2(p[:, 1], p[:, 0])
+    azimuth = (np.where(a > 0.0, a, a + 2.0 * np.pi) * 180.0) / np.pi
+    half = lambda v: np.abs(v - np.floor(v) - 0.5)
+    for s in np.unique(sem):
+        m = ok & (sem == s)
+        if not m.any():
+            continue
+        lo, hi = min(0.0, pitch[m].min()), max(0.0, pitch[m].max())
+        h = (hi - lo) / delta_p
+        if h > margin and abs(h - np.round(h)) < margin:
+            return False
+        if np.any(half((pitch[m] - lo) / delta_p) < margin) or np.any(half(azimuth[m] / delta_a) < margin):
+            return False
+        rg, top, step, bounds = min(5.0, r[m].min()), max(5.0, r[m].max()), 1, []
+        while rg <= top and step <= 4096:
+            rg = rg + (start_r - step * delta_r)
+            bounds.append(rg)
+            step += 1
+        b = np.array(bounds)
+        k = np.clip(np.searchsorted(b, r[m]), 1, len(b) - 1) if len(b) > 1 else np.zeros(m.sum(), np.int64)
+        if np.any(np.abs(r[m] - b[k]) < margin) or np.any(np.abs(r[m] - b[np.maximum(k - 1, 0)]) < margin):
+            return False
+    return True
+
+
+def make_scans(n_scans, n_points, stream=1, n_blobs=12, classes=SCAN_CLASSES, instances=False, sigma=(0.08, 0.3),
+               r_range=(4.0, 45.0), stray=0.02, stride=4):
+    """labelled scans: n_points points per scan (a sequence: per scan) in n_blobs Gaussian blobs (sigma drawn from
+    `sigma`, m) around landmark positions at r_range metres from the sensor, every blob of one class of `classes`;
+    `stray` of the points carry the unlabelled class 0 anywhere in view.  instances: blobs carry instance ids 1, 2, ...
+    (sem | inst << 16) and clustering goes by them; otherwise the ids are 0 and it goes by curved voxels.  A draw that
+    puts a point within 1e-9 cell of a rounding boundary of the scan rule is rejected and drawn again.
+    Returns points (total, stride) f32, labels (total,) u32, pt_off (n_scans + 1,) i64."""
+    counts = np.broadcast_to(np.asarray(n_points, np.int64), (n_scans,)) if n_scans else np.zeros(0, np.int64)
+    pts, labs = [], []
+    for s in range(n_scans):
+        n = int(counts[s])
+        for attempt in range(64):
+            rng = _rng(stream, 5000 + s * 64 + attempt)
+            nb = max(1, min(n_blobs, n)) if n else 0
+            rad, ang = rng.uniform(r_range[0], r_range[1], nb), rng.uniform(-np.pi, np.pi, nb)
+            centre = np.stack([rad * np.cos(ang), rad * np.sin(ang), rng.uniform(-1.5, 2.0, nb)], axis=1)
+            sg = rng.uniform(sigma[0], sigma[1], nb)
+            cls = rng.choice(np.asarray(classes), nb) if nb else np.zeros(0, np.int64)
+            which = rng.integers(0, nb, n) if nb else np.zeros(0, np.int64)
+            p = np.zeros((n, stride), np.float32)
+            p[:, :3] = (centre[which] + rng.normal(0.0, 1.0, (n, 3)) * sg[which, None]).astype(np.float32)
+            if stride > 3:
+                p[:, 3] = rng.random(n).astype(np.float32)
+            lab = cls[which].astype(np.uint32)
+            if instances:
+                lab |= (which.astype(np.uint32) + 1) << 16
+            lost = rng.random(n) < stray
+            lab[lost] = 0
+            p[lost, :3] = rng.uniform(-50.0, 50.0, (int(lost.sum()), 3)).astype(np.float32) * np.array([1.0, 1.0, 0.05], np.float32)
+            if scan_clear_of_boundaries(p, lab):
+                break
+        else:
+            raise RuntimeError("no draw of scan %d keeps clear of the rounding boundaries" % s)
+        pts.append(p)
+        labs.append(lab)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    points = np.concatenate(pts) if pts else np.zeros((0, stride), np.float32)
+    labels = np.concatenate(labs) if labs else np.zeros(0, np.uint32)
+    return points, labels, off
