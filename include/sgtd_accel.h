@@ -1011,7 +1011,9 @@ void sgtd_graphs_free(sgtd_graph_batch *b);
  *   downstream reads them); no file is read in C.
  *
  * sgtd_scan_keypoints leaves the keypoints on the device; it is independent of the pending batch, the table and the
- * stored poses, uses buffers of its own, and its results last until the next scan call or sgtd_destroy.  points and
+ * stored poses, uses buffers of its own, and its results last until the next scan call, the next
+ * sgtd_local_map_keypoints (which clusters in the same work buffers: the scan getters return SGTD_ERR_STATE after it
+ * until a scan call has run again) or sgtd_destroy.  points and
  * labels are host arrays, or device arrays with device_ptrs != 0; pt_off (n_scans + 1 offsets, in points) is a host
  * array.  sgtd_scan_device_view hands out borrowed device pointers (xyz f32 [n_keypoints * 3], label u32): with the
  * fetched kp_off they are what sgtd_add_frames / sgtd_query_frames / sgtd_loop_frames take with device_ptrs = 1.  A view
@@ -1057,6 +1059,78 @@ int sgtd_result_scan_grids(sgtd_handle h, int scan, int32_t *grid /*[32*4]*/, do
 int sgtd_scan_device_view(sgtd_handle h, const float **d_xyz, const uint32_t **d_label);
 /* points per tile (workgroup) of the per-point passes: the tests place their edges there */
 void sgtd_scan_tiles(int *point_tile);
+
+/* ---- posed, labelled scans to the keypoints of local maps (local_map_kernels.hip.h) ----
+ * What the reference's map-side producer local_map does (src/sgtd/src/local_map.cpp:213-482, gen_graphs :767-923, the
+ * graph_DCVC_map files the localization node loads as its map): for every anchor scan j the scans whose pose lies within
+ * `radius` of j's are moved into j's frame and appended behind j's own points, and the merged cloud is clustered like a
+ * single scan.  A local map sees each object from several places: denser clusters, steadier keypoints, more of them.
+ *
+ * The rule.  All arithmetic is f64, every operation rounded once (no contraction); f32 inputs are widened exactly.  inv()
+ * and mul() are those of sgtd_consistent_loops above, in their operation order.
+ * Inputs: n_scans labelled scans as sgtd_scan_keypoints takes them; pose12 [n_scans * 12], a host array, f32, row-major
+ *   3x4 [R | t]: the pose T_i of the frame scan i's points are given in (the sensor pose; the reference multiplies a fixed
+ *   extrinsic in, BASE2OUSTER, :300 — here the caller composes it into the pose beforehand); anchors [n_anchors], a host
+ *   array of scan indices (NULL: every scan, in order, n_anchors ignored); repeats are allowed, each entry is a local map
+ *   of its own.
+ * Members of anchor j: j itself, always, first.  Every other scan i iff d2 <= rr with dx = (double)t_i[0] - (double)t_j[0]
+ *   (dy, dz alike), d2 = (dx*dx + dy*dy) + dz*dz, rr = radius * radius, listed in ascending i.  d2 == rr is in (the
+ *   reference skips on > 15, :272).  A translation that is not finite makes d2 NaN or infinite: such a scan is a member of
+ *   its own local map only.  With max_members = m > 0: the anchor and the m - 1 other members with the smallest (d2, i),
+ *   ordered lexicographically (ties in d2 go to the smaller index), still listed in ascending i behind the anchor; m == 1
+ *   keeps the anchor alone.
+ * Merged cloud of anchor j: j's own points first, x y z as given (:260-264); then, for each other member i in list order,
+ *   its points in their order, each p'[r] = (float)(((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3]), r = 0..2, with
+ *   M = mul(inv(T_j), T_i) (:300-302,320-325).  Labels are carried along unchanged.  A coordinate that is NaN or infinite
+ *   (a NaN in a rotation gives such points) is dropped by the scan rule as it is today.
+ * Keypoints of anchor j: the rule of sgtd_scan_keypoints, unchanged, on the merged cloud as if it were one scan (classes,
+ *   modes, range gate, the grid from the merged cloud's own min / max, components, size filter, order by smallest merged
+ *   point index, the fixed-order 256-accumulator centres): xyz f32 in the anchor's frame, label u32, n_points.
+ * Departures from the reference: local_map_creation re-opens the anchor's own files for every neighbour
+ *   (current_scan_path, :281,305) and so merges copies of the anchor's cloud, not the neighbours' — this call merges the
+ *   neighbours' clouds, plainly what was meant; the reference inverts T_j as a general 4x4 in f32 (:300), here it is the
+ *   rigid inverse in f64; the distance test runs in f64 on the given (sensor) translations, not in f32 on base
+ *   translations; the class rules of :372-442 (the lumped classes 9 / 10, the skipped classes, the per-class minima) are
+ *   expressed through sgtd_scan_config's node_label / min_seg; "one cluster for the whole class" is not offered; densitys,
+ *   edges and weights of the graph file are not produced (nothing downstream reads them).
+ *
+ * Passes: a local map of 30 members holds millions of points and the scan pipeline needs about 280 bytes of work space a
+ * point, so consecutive anchors go into one pass while the sum of their merged sizes stays within max_pass_points (and
+ * their number within SGTD_SCAN_MAX_SCANS); the keypoints of every pass are appended on the device.  No result depends on
+ * where the pass boundaries fall.  An anchor whose merged cloud alone exceeds max_pass_points fails the call with
+ * SGTD_ERR_UNSUPPORTED before any clustering runs (sgtd_last_error names the anchor and its size); no results are left
+ * and the handle stays usable.
+ *
+ * The results stay on the device in buffers of their own until the next local-map call or sgtd_destroy;
+ * sgtd_scan_keypoints does not disturb them.  The call clusters in the scan pipeline's work buffers and so invalidates the
+ * results of an earlier sgtd_scan_keypoints (its getters: SGTD_ERR_STATE).  It is independent of the pending batch, the
+ * table and the stored poses; a view (sgtd_attach_table) runs it whatever state its owner is in, a multi-device handle on
+ * its first device.  sgtd_local_map_device_view: borrowed device pointers (xyz f32 [n_keypoints * 3], label u32), with the
+ * fetched kp_off what sgtd_add_frames / sgtd_query_frames take with device_ptrs = 1.  sgtd_result_local_map_members:
+ * mem_off [n_anchors + 1], member [capacity] (scan indices, the anchor first), merged_points [n_anchors], the number of
+ * passes.  sgtd_local_map_stage_ms: milliseconds of the last call's member selection, gathers and scan passes between
+ * events on its stream (zeros unless sgtd_set_timing is on).
+ *
+ * Errors, before the device is touched, SGTD_ERR_INVALID: everything sgtd_scan_keypoints rejects so; pose12 == NULL with
+ * n_scans > 0; n_anchors < 0; an anchor outside [0, n_scans); radius NaN, negative or infinite; max_members < 0;
+ * max_pass_points < 0 or above SGTD_SCAN_MAX_POINTS; reserved != 0.  The getters before a successful run: SGTD_ERR_STATE;
+ * more than capacity: SGTD_ERR_CAPACITY (the size needed reported, the first `capacity` entries written). */
+typedef struct sgtd_local_map_options {
+  double  radius;           /* 15.0 (local_map.cpp:272); finite, >= 0 */
+  int32_t max_members;      /* 0 = no cap; otherwise >= 1, the anchor included */
+  int32_t reserved;         /* 0 */
+  int64_t max_pass_points;  /* merged points clustered in one pass; 0 = default (1 << 26); <= SGTD_SCAN_MAX_POINTS */
+} sgtd_local_map_options;
+void sgtd_default_local_map_options(sgtd_local_map_options *opt);
+int sgtd_local_map_keypoints(sgtd_handle h, const sgtd_scan_config *cfg, const sgtd_local_map_options *opt,
+                             const float *points, int stride_floats, const uint32_t *labels, const int64_t *pt_off,
+                             const float *pose12, int n_scans, const int32_t *anchors, int n_anchors, int device_ptrs);
+int sgtd_result_local_map_keypoints(sgtd_handle h, int64_t *kp_off /* n_anchors + 1 */, float *xyz, uint32_t *label,
+                                    int32_t *n_points, int64_t capacity, int64_t *n_keypoints);
+int sgtd_result_local_map_members(sgtd_handle h, int64_t *mem_off /* n_anchors + 1 */, int32_t *member, int64_t capacity,
+                                  int64_t *n_members, int64_t *merged_points /* n_anchors */, int32_t *n_passes);
+int sgtd_local_map_device_view(sgtd_handle h, const float **d_xyz, const uint32_t **d_label);
+int sgtd_local_map_stage_ms(sgtd_handle h, float *ms_members, float *ms_gather, float *ms_scan);
 
 /* Page-locked host memory for the destination buffers of the fetch calls (sgtd_fetch_entries,
  * sgtd_result_pairs, ...): a copy into it is one direct DMA transfer — pageable memory goes through the

@@ -41,6 +41,8 @@ SYMBOLS = [
     "sgtd_search_loop_consensus", "sgtd_result_consensus_edges",
     "sgtd_default_scan_config", "sgtd_scan_config_check", "sgtd_scan_keypoints", "sgtd_result_scan_keypoints", "sgtd_result_scan_point_clusters",
     "sgtd_result_scan_grids", "sgtd_scan_device_view", "sgtd_scan_tiles",
+    "sgtd_default_local_map_options", "sgtd_local_map_keypoints", "sgtd_result_local_map_keypoints", "sgtd_result_local_map_members",
+    "sgtd_local_map_device_view", "sgtd_local_map_stage_ms",
 ]
 
 
@@ -116,6 +118,11 @@ class ScanConfig(C.Structure):
                 ("min_instance_points", C.c_int32), ("reserved", C.c_int32),
                 ("start_r", C.c_double), ("delta_r", C.c_double), ("delta_p", C.c_double), ("delta_a", C.c_double),
                 ("min_range", C.c_double), ("max_range", C.c_double)]
+
+
+class LocalMapOptions(C.Structure):
+    """sgtd_local_map_options"""
+    _fields_ = [("radius", C.c_double), ("max_members", C.c_int32), ("reserved", C.c_int32), ("max_pass_points", C.c_int64)]
 
 
 def build_library(force=False):
@@ -219,6 +226,14 @@ def lib():
     L.sgtd_scan_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.sgtd_scan_tiles.argtypes = [C.POINTER(C.c_int)]
     L.sgtd_scan_tiles.restype = None
+    L.sgtd_default_local_map_options.argtypes = [C.POINTER(LocalMapOptions)]
+    L.sgtd_default_local_map_options.restype = None
+    L.sgtd_local_map_keypoints.argtypes = [vp, C.POINTER(ScanConfig), C.POINTER(LocalMapOptions), vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int,
+                                           C.c_int]
+    L.sgtd_result_local_map_keypoints.argtypes = [vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_local_map_members.argtypes = [vp, vp, vp, i64, C.POINTER(i64), vp, C.POINTER(i32)]
+    L.sgtd_local_map_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.sgtd_local_map_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

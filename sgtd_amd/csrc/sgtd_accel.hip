@@ -35,6 +35,7 @@
 #include "relax_kernels.hip.h"
 #include "consensus_kernels.hip.h"
 #include "scan_kernels.hip.h"
+#include "local_map_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -335,6 +336,18 @@ struct sgtd_engine {
   int sk_n = -1;
   int64_t sk_points = 0, sk_kept = 0;
   std::vector<int64_t> sk_off, sk_kp_off;
+  // sgtd_local_map_keypoints (local_map_kernels.hip.h): the member lists, the pass's segments and merged cloud, and the
+  // appended keypoints of all passes (LM_XYZ / LM_LABEL / LM_NPOINTS); the clustering runs in the sk buffers above.
+  // lm_n < 0: no results; lm_kp_off / lm_mem_off / lm_merged: per anchor, on the host; lm_ms: members, gather, scan
+  // passes of the last call (filled under sgtd_set_timing)
+  enum { LM_POSE = 0, LM_OFF, LM_ANCH, LM_COUNT, LM_MERGED, LM_MEM_OFF, LM_MEMBER, LM_SEG, LM_CNT, LM_START, LM_MPTS, LM_MLAB, LM_XYZ, LM_LABEL,
+         LM_NPOINTS, LM_BUFS };
+  DevBuf lm[LM_BUFS];
+  int lm_n = -1, lm_passes = 0;
+  int64_t lm_kept = 0;
+  std::vector<int64_t> lm_kp_off, lm_mem_off, lm_merged;
+  hipEvent_t lm_ev[3] = {nullptr, nullptr, nullptr};
+  float lm_ms[3] = {0.f, 0.f, 0.f};
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -2225,6 +2238,9 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl};
   for (DevBuf *b : bufs) free_buf(*b);
   for (DevBuf &b : e->sk) free_buf(b);
+  for (DevBuf &b : e->lm) free_buf(b);
+  for (hipEvent_t ev : e->lm_ev)
+    if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto &b : e->scan_lvl) free_buf(b);
@@ -4911,9 +4927,25 @@ bool scan_rings_fit(const sgtd_scan_config &c) {
   return false;
 }
 
+// the pipeline from "points on the device" onward: d_pts / d_lab are device arrays (nullptr: scan_run's own staging
+// buffers SK_PTS / SK_LAB, which it has filled), pt_off is the host's.  sgtd_local_map_keypoints calls it once per pass.
+int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int stride, const u32 *d_lab, const int64_t *pt_off, int S);
+
 int scan_run(sgtd_engine *e, const ScanCfgDev &C, const float *points, int stride, const uint32_t *labels, const int64_t *pt_off, int S,
              int device_ptrs) {
   HIPCHK(hipSetDevice(e->cfg.device_id));
+  const long long P = pt_off[S];
+  if (device_ptrs || S == 0 || P == 0) return scan_device(e, C, points, stride, labels, pt_off, S);
+  auto buf = [&](int k, size_t bytes) { return ensure(e, e->sk[k], std::max<size_t>(bytes, 16)); };
+  const size_t np = (size_t)P;
+  CHK(buf(sgtd_engine::SK_PTS, np * stride * sizeof(float)));
+  CHK(buf(sgtd_engine::SK_LAB, np * sizeof(u32)));
+  CHK(h2d(e, e->sk[sgtd_engine::SK_PTS].p, points, np * stride * sizeof(float)));
+  CHK(h2d(e, e->sk[sgtd_engine::SK_LAB].p, labels, np * sizeof(u32)));
+  return scan_device(e, C, nullptr, stride, nullptr, pt_off, S);
+}
+
+int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int stride, const u32 *d_lab, const int64_t *pt_off, int S) {
   const long long P = pt_off[S];
   const int n_sc = S * 32;
   auto buf = [&](int k, size_t bytes) { return ensure(e, e->sk[k], std::max<size_t>(bytes, 16)); };
@@ -4932,16 +4964,8 @@ int scan_run(sgtd_engine *e, const ScanCfgDev &C, const float *points, int strid
     }
     return xfer_sync(e);
   }
-  const float *d_pts = points;
-  const u32 *d_lab = labels;
-  if (!device_ptrs) {
-    CHK(buf(sgtd_engine::SK_PTS, np * stride * sizeof(float)));
-    CHK(buf(sgtd_engine::SK_LAB, np * sizeof(u32)));
-    CHK(h2d(e, e->sk[sgtd_engine::SK_PTS].p, points, np * stride * sizeof(float)));
-    CHK(h2d(e, e->sk[sgtd_engine::SK_LAB].p, labels, np * sizeof(u32)));
-    d_pts = e->sk[sgtd_engine::SK_PTS].as<float>();
-    d_lab = e->sk[sgtd_engine::SK_LAB].as<u32>();
-  }
+  if (!d_pts) d_pts = e->sk[sgtd_engine::SK_PTS].as<float>();
+  if (!d_lab) d_lab = e->sk[sgtd_engine::SK_LAB].as<u32>();
   CHK(buf(sgtd_engine::SK_OFF, ((size_t)S + 1) * sizeof(long long)));
   CHK(h2d(e, e->sk[sgtd_engine::SK_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
   CHK(buf(sgtd_engine::SK_SC, np * sizeof(u32)));
@@ -5083,6 +5107,179 @@ int scan_ready(sgtd_engine *e, sgtd_engine **out) {
   return SGTD_OK;
 }
 
+ScanCfgDev scan_cfg_dev(const sgtd_scan_config &c, int n_scans) {
+  ScanCfgDev C;
+  for (int s = 0; s < 32; s++) { C.node_label[s] = c.node_label[s]; C.min_seg[s] = c.min_seg[s]; }
+  C.min_inst = c.min_instance_points; C.n_scans = n_scans;
+  C.start_r = c.start_r; C.delta_r = c.delta_r; C.delta_p = c.delta_p; C.delta_a = c.delta_a; C.min_range = c.min_range; C.max_range = c.max_range;
+  return C;
+}
+
+// ---- sgtd_local_map_keypoints (local_map_kernels.hip.h) ----
+int local_map_ready(sgtd_engine *e, sgtd_engine **out) {
+  sgtd_engine *c = scan_engine(e);
+  if (c->lm_n < 0) { e->err = "no local-map keypoints: sgtd_local_map_keypoints has not run"; return SGTD_ERR_STATE; }
+  *out = c;
+  return SGTD_OK;
+}
+
+// milliseconds between two recorded events of the call's stream, added to *ms (the stream is waited for)
+int lm_lap(sgtd_engine *e, int a, int b, float *ms) {
+  HIPCHK(hipEventSynchronize(e->lm_ev[b]));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, e->lm_ev[a], e->lm_ev[b]));
+  *ms += t;
+  return SGTD_OK;
+}
+
+int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_map_options &opt, const float *points, int stride,
+                  const uint32_t *labels, const int64_t *pt_off, const float *pose12, int S, const int32_t *anchors, int A, int device_ptrs) {
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  auto buf = [&](int k, size_t bytes, bool keep = false) { return ensure(e, e->lm[k], std::max<size_t>(bytes, 16), keep); };
+  auto *B = e->lm;
+  const hipStream_t st = e->stream;
+  const bool timed = e->timing;
+  if (timed)
+    for (hipEvent_t &ev : e->lm_ev)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+  e->lm_ms[0] = e->lm_ms[1] = e->lm_ms[2] = 0.f;
+  e->lm_kp_off.assign((size_t)A + 1, 0);
+  e->lm_mem_off.assign((size_t)A + 1, 0);
+  e->lm_merged.assign((size_t)A, 0);
+  e->lm_kept = 0; e->lm_passes = 0;
+  CHK(buf(sgtd_engine::LM_XYZ, 16));
+  CHK(buf(sgtd_engine::LM_LABEL, 16));
+  CHK(buf(sgtd_engine::LM_NPOINTS, 16));
+  CHK(buf(sgtd_engine::LM_MEMBER, 16));
+  if (A == 0) return SGTD_OK;
+
+  // members: counts and merged sizes, the host's plan, then the lists
+  std::vector<int32_t> anch((size_t)A);
+  for (int a = 0; a < A; a++) anch[(size_t)a] = anchors ? anchors[a] : a;
+  CHK(buf(sgtd_engine::LM_POSE, (size_t)S * 12 * sizeof(float)));
+  CHK(buf(sgtd_engine::LM_OFF, ((size_t)S + 1) * sizeof(long long)));
+  CHK(buf(sgtd_engine::LM_ANCH, (size_t)A * sizeof(int)));
+  CHK(buf(sgtd_engine::LM_COUNT, (size_t)A * sizeof(int)));
+  CHK(buf(sgtd_engine::LM_MERGED, (size_t)A * sizeof(long long)));
+  CHK(buf(sgtd_engine::LM_MEM_OFF, ((size_t)A + 1) * sizeof(long long)));
+  CHK(h2d(e, B[sgtd_engine::LM_POSE].p, pose12, (size_t)S * 12 * sizeof(float)));
+  CHK(h2d(e, B[sgtd_engine::LM_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(h2d(e, B[sgtd_engine::LM_ANCH].p, anch.data(), (size_t)A * sizeof(int)));
+  const float *d_pose = B[sgtd_engine::LM_POSE].as<float>();
+  const long long *d_off = B[sgtd_engine::LM_OFF].as<long long>();
+  const int *d_anch = B[sgtd_engine::LM_ANCH].as<int>();
+  const double rr = opt.radius * opt.radius;
+  if (timed) HIPCHK(hipEventRecord(e->lm_ev[0], st));
+  lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, nullptr, nullptr, B[sgtd_engine::LM_COUNT].as<int>(),
+                                                   B[sgtd_engine::LM_MERGED].as<long long>());
+  HIPCHK(hipGetLastError());
+  if (timed) HIPCHK(hipEventRecord(e->lm_ev[1], st));
+  std::vector<int32_t> count((size_t)A);
+  CHK(d2h(e, count.data(), B[sgtd_engine::LM_COUNT].p, (size_t)A * sizeof(int)));
+  CHK(d2h(e, e->lm_merged.data(), B[sgtd_engine::LM_MERGED].p, (size_t)A * sizeof(long long)));
+  CHK(xfer_sync(e));
+  if (timed) CHK(lm_lap(e, 0, 1, &e->lm_ms[0]));
+  const int64_t cap = opt.max_pass_points > 0 ? opt.max_pass_points : (int64_t)1 << 26;
+  for (int a = 0; a < A; a++) {
+    e->lm_mem_off[(size_t)a + 1] = e->lm_mem_off[(size_t)a] + count[(size_t)a];
+    if (e->lm_merged[(size_t)a] > cap) {
+      e->err = "sgtd_local_map_keypoints: the merged cloud of anchor " + std::to_string(a) + " (scan " + std::to_string(anch[(size_t)a]) + ") holds " +
+               std::to_string(e->lm_merged[(size_t)a]) + " points, more than max_pass_points = " + std::to_string(cap) +
+               " (lower radius or max_members, or raise max_pass_points)";
+      return SGTD_ERR_UNSUPPORTED;
+    }
+  }
+  const int64_t M = e->lm_mem_off[(size_t)A];
+  CHK(buf(sgtd_engine::LM_MEMBER, (size_t)M * sizeof(int)));
+  CHK(h2d(e, B[sgtd_engine::LM_MEM_OFF].p, e->lm_mem_off.data(), ((size_t)A + 1) * sizeof(long long)));
+  const long long *d_mem_off = B[sgtd_engine::LM_MEM_OFF].as<long long>();
+  int *d_member = B[sgtd_engine::LM_MEMBER].as<int>();
+  if (timed) HIPCHK(hipEventRecord(e->lm_ev[0], st));
+  lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, d_mem_off, d_member, B[sgtd_engine::LM_COUNT].as<int>(),
+                                                   B[sgtd_engine::LM_MERGED].as<long long>());
+  HIPCHK(hipGetLastError());
+  if (timed) {
+    HIPCHK(hipEventRecord(e->lm_ev[1], st));
+    CHK(lm_lap(e, 0, 1, &e->lm_ms[0]));
+  }
+
+  // the scans on the device (the scan pipeline's staging buffers: it reads the merged cloud, not these)
+  const float *d_pts = points;
+  const u32 *d_lab = labels;
+  const size_t np = (size_t)pt_off[S];
+  e->sk_n = -1;
+  if (!device_ptrs && np) {
+    CHK(ensure(e, e->sk[sgtd_engine::SK_PTS], np * stride * sizeof(float)));
+    CHK(ensure(e, e->sk[sgtd_engine::SK_LAB], np * sizeof(u32)));
+    CHK(h2d(e, e->sk[sgtd_engine::SK_PTS].p, points, np * stride * sizeof(float)));
+    CHK(h2d(e, e->sk[sgtd_engine::SK_LAB].p, labels, np * sizeof(u32)));
+    d_pts = e->sk[sgtd_engine::SK_PTS].as<float>();
+    d_lab = e->sk[sgtd_engine::SK_LAB].as<u32>();
+  }
+  const bool vec = stride == 4 && ((uintptr_t)d_pts & 15) == 0;
+
+  // passes of consecutive anchors
+  std::vector<int64_t> pass_off;
+  for (int a0 = 0; a0 < A;) {
+    int a1 = a0;
+    int64_t Pp = 0;
+    while (a1 < A && a1 - a0 < SGTD_SCAN_MAX_SCANS && Pp + e->lm_merged[(size_t)a1] <= cap) Pp += e->lm_merged[(size_t)a1++];
+    const int na = a1 - a0;
+    const int64_t n_seg64 = e->lm_mem_off[(size_t)a1] - e->lm_mem_off[(size_t)a0];
+    if (n_seg64 > (int64_t)1 << 30) { e->err = "sgtd_local_map_keypoints: more than 2^30 members in one pass"; return SGTD_ERR_UNSUPPORTED; }
+    const int n_seg = (int)n_seg64;
+    pass_off.assign((size_t)na + 1, 0);
+    for (int a = 0; a < na; a++) pass_off[(size_t)a + 1] = pass_off[(size_t)a] + e->lm_merged[(size_t)(a0 + a)];
+    CHK(buf(sgtd_engine::LM_SEG, (size_t)n_seg * sizeof(LmSeg)));
+    CHK(buf(sgtd_engine::LM_CNT, ((size_t)n_seg + 1) * sizeof(u32)));
+    CHK(buf(sgtd_engine::LM_START, ((size_t)n_seg + 1) * sizeof(u32)));
+    CHK(buf(sgtd_engine::LM_MPTS, (size_t)Pp * 3 * sizeof(float)));
+    CHK(buf(sgtd_engine::LM_MLAB, (size_t)Pp * sizeof(u32)));
+    LmSeg *seg = B[sgtd_engine::LM_SEG].as<LmSeg>();
+    u32 *cnt = B[sgtd_engine::LM_CNT].as<u32>(), *start = B[sgtd_engine::LM_START].as<u32>();
+    float *m_pts = B[sgtd_engine::LM_MPTS].as<float>();
+    u32 *m_lab = B[sgtd_engine::LM_MLAB].as<u32>();
+    if (timed) HIPCHK(hipEventRecord(e->lm_ev[0], st));
+    if (Pp > 0) {
+      lm_segments_kernel<<<grid_for((long long)n_seg + 1, 256), 256, 0, st>>>(d_pose, d_off, d_anch, d_mem_off, d_member, a0, na, n_seg, seg, cnt);
+      HIPCHK(hipGetLastError());
+      CHK(device_scan(e, cnt, start, (long long)n_seg + 1));
+      const int tiles = grid_for(Pp, SGTD_SCAN_TILE);
+      if (vec) lm_gather_kernel<4, true><<<tiles, SGTD_LM_THREADS, 0, st>>>(d_pts, d_lab, seg, start, n_seg, (u32)Pp, m_pts, m_lab);
+      else if (stride == 4) lm_gather_kernel<4, false><<<tiles, SGTD_LM_THREADS, 0, st>>>(d_pts, d_lab, seg, start, n_seg, (u32)Pp, m_pts, m_lab);
+      else lm_gather_kernel<3, false><<<tiles, SGTD_LM_THREADS, 0, st>>>(d_pts, d_lab, seg, start, n_seg, (u32)Pp, m_pts, m_lab);
+      HIPCHK(hipGetLastError());
+    }
+    if (timed) HIPCHK(hipEventRecord(e->lm_ev[1], st));
+    const ScanCfgDev C = scan_cfg_dev(cfg, na);
+    CHK(scan_device(e, C, m_pts, 3, m_lab, pass_off.data(), na));
+    if (timed) {
+      HIPCHK(hipEventRecord(e->lm_ev[2], st));
+      CHK(lm_lap(e, 0, 1, &e->lm_ms[1]));
+      CHK(lm_lap(e, 1, 2, &e->lm_ms[2]));
+    }
+    // the pass's keypoints behind those of the passes before it
+    const int64_t K = e->sk_kept, K0 = e->lm_kept;
+    for (int a = 0; a <= na; a++) e->lm_kp_off[(size_t)(a0 + a)] = K0 + e->sk_kp_off[(size_t)a];
+    if (K > 0) {
+      CHK(buf(sgtd_engine::LM_XYZ, (size_t)(K0 + K) * 3 * sizeof(float), true));
+      CHK(buf(sgtd_engine::LM_LABEL, (size_t)(K0 + K) * sizeof(u32), true));
+      CHK(buf(sgtd_engine::LM_NPOINTS, (size_t)(K0 + K) * sizeof(int), true));
+      HIPCHK(hipMemcpyAsync(B[sgtd_engine::LM_XYZ].as<float>() + (size_t)K0 * 3, e->sk[sgtd_engine::SK_XYZ].p, (size_t)K * 3 * sizeof(float),
+                            hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(B[sgtd_engine::LM_LABEL].as<u32>() + (size_t)K0, e->sk[sgtd_engine::SK_LABEL].p, (size_t)K * sizeof(u32),
+                            hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(B[sgtd_engine::LM_NPOINTS].as<int>() + (size_t)K0, e->sk[sgtd_engine::SK_NPOINTS].p, (size_t)K * sizeof(int),
+                            hipMemcpyDeviceToDevice, st));
+    }
+    e->lm_kept = K0 + K;
+    e->lm_passes++;
+    a0 = a1;
+  }
+  // (the caller's arrays and the scan buffers are read for the last time by the copies: the call returns when they are done)
+  return xfer_sync(e);
+}
+
 }  // namespace
 
 extern "C" {
@@ -5152,10 +5349,7 @@ int sgtd_scan_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const float 
   sgtd_engine *k = scan_engine(e);
   k->sk_n = -1;
   PinScope pin_scope(k);
-  ScanCfgDev C;
-  for (int s = 0; s < 32; s++) { C.node_label[s] = c.node_label[s]; C.min_seg[s] = c.min_seg[s]; }
-  C.min_inst = c.min_instance_points; C.n_scans = n_scans;
-  C.start_r = c.start_r; C.delta_r = c.delta_r; C.delta_p = c.delta_p; C.delta_a = c.delta_a; C.min_range = c.min_range; C.max_range = c.max_range;
+  const ScanCfgDev C = scan_cfg_dev(c, n_scans);
   const int rc = scan_run(k, C, points, stride_floats, labels, pt_off, n_scans, device_ptrs);
   if (rc != SGTD_OK) {
     if (k != e) e->err = k->err;
@@ -5219,6 +5413,116 @@ int sgtd_scan_device_view(sgtd_handle e, const float **d_xyz, const uint32_t **d
   CHK(scan_ready(e, &c));
   if (d_xyz) *d_xyz = c->sk[sgtd_engine::SK_XYZ].as<float>();
   if (d_label) *d_label = c->sk[sgtd_engine::SK_LABEL].as<u32>();
+  return SGTD_OK;
+}
+
+void sgtd_default_local_map_options(sgtd_local_map_options *opt) {
+  if (!opt) return;
+  std::memset(opt, 0, sizeof(*opt));
+  opt->radius = 15.0;
+}
+
+int sgtd_local_map_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const sgtd_local_map_options *opt, const float *points, int stride_floats,
+                             const uint32_t *labels, const int64_t *pt_off, const float *pose12, int n_scans, const int32_t *anchors, int n_anchors,
+                             int device_ptrs) {
+  if (!e || n_scans < 0 || n_anchors < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  sgtd_scan_config c;
+  sgtd_default_scan_config(&c);
+  if (cfg) c = *cfg;
+  sgtd_local_map_options o;
+  sgtd_default_local_map_options(&o);
+  if (opt) o = *opt;
+  const char *why = nullptr;
+  const int cs = sgtd_scan_config_check(&c, &why);
+  if (cs == SGTD_ERR_INVALID) return cs;
+  if (!(std::isfinite(o.radius) && o.radius >= 0.0) || o.max_members < 0 || o.reserved != 0 || o.max_pass_points < 0 ||
+      o.max_pass_points > SGTD_SCAN_MAX_POINTS)
+    return SGTD_ERR_INVALID;
+  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
+  for (int s = 0; s < n_scans; s++)
+    if (pt_off[s + 1] < pt_off[s]) return SGTD_ERR_INVALID;
+  const int64_t P = pt_off[n_scans];
+  if (P > 0 && (!points || !labels)) return SGTD_ERR_INVALID;
+  if (n_scans > 0 && !pose12) return SGTD_ERR_INVALID;
+  const int A = anchors ? n_anchors : n_scans;      // NULL: every scan, in order
+  if (anchors)
+    for (int a = 0; a < n_anchors; a++)
+      if (anchors[a] < 0 || anchors[a] >= n_scans) return SGTD_ERR_INVALID;
+  if (n_scans > SGTD_SCAN_MAX_SCANS || P > SGTD_SCAN_MAX_POINTS) {
+    e->err = "sgtd_local_map_keypoints takes at most " + std::to_string(SGTD_SCAN_MAX_SCANS) + " scans and " + std::to_string(SGTD_SCAN_MAX_POINTS) +
+             " points in one call";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (cs != SGTD_OK) {
+    e->err = std::string("sgtd_local_map_keypoints: ") + why;
+    return cs;
+  }
+  sgtd_engine *k = scan_engine(e);
+  k->lm_n = -1;
+  PinScope pin_scope(k);
+  const int rc = local_map_run(k, c, o, points, stride_floats, labels, pt_off, pose12, n_scans, anchors, A, device_ptrs);
+  if (rc != SGTD_OK) {
+    if (k != e) e->err = k->err;
+    return rc;
+  }
+  k->lm_n = A;
+  return SGTD_OK;
+}
+
+int sgtd_result_local_map_keypoints(sgtd_handle e, int64_t *kp_off, float *xyz, uint32_t *label, int32_t *n_points, int64_t capacity,
+                                    int64_t *n_keypoints) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(local_map_ready(e, &c));
+  const int64_t K = c->lm_kept;
+  if (n_keypoints) *n_keypoints = K;
+  if (kp_off) std::memcpy(kp_off, c->lm_kp_off.data(), c->lm_kp_off.size() * sizeof(int64_t));
+  const size_t m = (size_t)std::min(K, capacity);
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && xyz && m) st = d2h(c, xyz, c->lm[sgtd_engine::LM_XYZ].p, m * 3 * sizeof(float));
+  if (st == SGTD_OK && label && m) st = d2h(c, label, c->lm[sgtd_engine::LM_LABEL].p, m * sizeof(u32));
+  if (st == SGTD_OK && n_points && m) st = d2h(c, n_points, c->lm[sgtd_engine::LM_NPOINTS].p, m * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return K > capacity && (xyz || label || n_points) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_local_map_members(sgtd_handle e, int64_t *mem_off, int32_t *member, int64_t capacity, int64_t *n_members, int64_t *merged_points,
+                                  int32_t *n_passes) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(local_map_ready(e, &c));
+  const int64_t M = c->lm_mem_off.back();
+  if (n_members) *n_members = M;
+  if (n_passes) *n_passes = c->lm_passes;
+  if (mem_off) std::memcpy(mem_off, c->lm_mem_off.data(), c->lm_mem_off.size() * sizeof(int64_t));
+  if (merged_points && !c->lm_merged.empty()) std::memcpy(merged_points, c->lm_merged.data(), c->lm_merged.size() * sizeof(int64_t));
+  const size_t m = member ? (size_t)std::min(M, capacity) : 0;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && m) st = d2h(c, member, c->lm[sgtd_engine::LM_MEMBER].p, m * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return M > capacity && member ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_local_map_device_view(sgtd_handle e, const float **d_xyz, const uint32_t **d_label) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(local_map_ready(e, &c));
+  if (d_xyz) *d_xyz = c->lm[sgtd_engine::LM_XYZ].as<float>();
+  if (d_label) *d_label = c->lm[sgtd_engine::LM_LABEL].as<u32>();
+  return SGTD_OK;
+}
+
+int sgtd_local_map_stage_ms(sgtd_handle e, float *ms_members, float *ms_gather, float *ms_scan) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(local_map_ready(e, &c));
+  if (ms_members) *ms_members = c->lm_ms[0];
+  if (ms_gather) *ms_gather = c->lm_ms[1];
+  if (ms_scan) *ms_scan = c->lm_ms[2];
   return SGTD_OK;
 }
 

@@ -139,3 +139,33 @@ def read_scan(bin_path, label_path):
     if points.size % 4 or points.size // 4 != labels.size:
         raise ValueError("%s holds %d floats, %s %d labels: not one x y z i row per label" % (bin_path, points.size, label_path, labels.size))
     return points.reshape(-1, 4), labels
+
+
+def sensor_poses(poses, extrinsic):
+    """pose · extrinsic in f64, rounded to f32: (n, 12) rows [R | t] of the sensor frames for callers that hold base
+    poses and a fixed extrinsic such as the reference's BASE2OUSTER (src/sgtd/src/local_map.cpp:300) — what
+    STDescManager.local_map_keypoints takes.  poses: (n, 12) rows or (n, 4, 4); extrinsic: 12 numbers, (3, 4) or (4, 4)."""
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 3 and p.shape[1:] == (4, 4):
+        p = p[:, :3, :]
+    p = p.reshape(-1, 3, 4)
+    x = np.asarray(extrinsic, np.float64)
+    x = x[:3, :] if x.shape == (4, 4) else x.reshape(3, 4)
+    out = np.empty_like(p)
+    out[:, :, :3] = p[:, :, :3] @ x[:, :3]
+    out[:, :, 3] = p[:, :, :3] @ x[:, 3] + p[:, :, 3]
+    return out.reshape(-1, 12).astype(np.float32)
+
+
+def read_pose_rows(path):
+    """poses in the KITTI layout: one line of 12 numbers per frame, the row-major 3x4 [R | t].  Returns (n, 12) f64."""
+    rows = []
+    with open(path) as f:
+        for n, line in enumerate(f):
+            if not line.strip():
+                continue
+            v = line.split()
+            if len(v) != 12:
+                raise ValueError("%s:%d holds %d numbers, not 12" % (path, n + 1, len(v)))
+            rows.append([float(t) for t in v])
+    return np.array(rows, np.float64).reshape(-1, 12)

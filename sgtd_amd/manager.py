@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, DescSoa, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats
+from ._lib import Config, DescSoa, LocalMapOptions, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats
 
 DEFAULTS = dict(descriptor_near_num=10, candidate_num=50, max_frame_n=20000, device_id=0,
                 descriptor_min_len=0.5, descriptor_max_len=50.0, std_side_resolution=1.0,
@@ -656,6 +656,121 @@ class STDescManager:
         """scan_keypoints, then query_frames on the keypoints where they lie on the device"""
         self.scan_keypoints(points, labels, pt_off, config, fetch=False)
         x, l, off, dev = self._scan_view()
+        self._nq = off.size - 1
+        self._check(self._L.sgtd_query_frames(self._h, x, l, _p(off), self._nq, dev))
+        return self.results() if fetch else None
+
+    # ---- posed scans to local-map keypoints (sgtd_local_map_keypoints) ----------------------------------------
+    @staticmethod
+    def _pose_rows(poses, n):
+        p = np.asarray(poses)
+        if p.ndim == 3 and p.shape[1:] == (4, 4):
+            p = p[:, :3, :].reshape(-1, 12)
+        if p.ndim != 2 or p.shape[1] != 12 or p.shape[0] != n:
+            raise ValueError("poses: (n_scans, 12) rows or (n_scans, 4, 4) matrices")
+        return np.ascontiguousarray(p, np.float32)
+
+    def local_map_keypoints(self, points, labels, pt_off, poses, anchors=None, radius=15.0, max_members=0, max_pass_points=0, config=None,
+                            fetch=True):
+        """posed, labelled scans to the keypoints of local maps on the device (sgtd_local_map_keypoints): the scans as
+        scan_keypoints takes them, poses (S, 12) rows or (S, 4, 4) of the frames the points are given in (sensor poses:
+        ingest.sensor_poses), anchors the scan indices to build a local map around (None: every scan).  Returns xyz (K, 3)
+        f32 in the anchors' frames, label (K,) u32, kp_off (A + 1,) i64, n_points (K,) i32; fetch=False leaves them on
+        the device (local_map_results, add_local_maps, query_local_maps)."""
+        is_torch = hasattr(points, "data_ptr")
+        if is_torch:
+            assert points.is_cuda and labels.is_cuda and points.is_contiguous() and labels.is_contiguous()
+            shape = tuple(points.shape)
+            pp, lp, dev = C.c_void_p(points.data_ptr()), C.c_void_p(labels.data_ptr()), 1
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            labels = np.ascontiguousarray(labels, dtype=np.uint32)
+            shape = points.shape
+            pp, lp, dev = _p(points), _p(labels), 0
+        if len(shape) < 2 or shape[-1] not in (3, 4):
+            raise ValueError("points: (total, 3 or 4) or (S, N, 3 or 4)")
+        if pt_off is None:
+            if len(shape) != 3:
+                raise ValueError("points: (S, N, 3 or 4), or pt_off")
+            off = np.arange(shape[0] + 1, dtype=np.int64) * shape[1]
+        else:
+            off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+            if off.size < 1:
+                raise ValueError("pt_off: n_scans + 1 offsets")
+            if off[-1] > int(np.prod(shape[:-1])):
+                raise ValueError("pt_off names more points than were given")
+        n_scans = off.size - 1
+        pose = self._pose_rows(poses, n_scans)
+        if anchors is None:
+            ap, na = None, n_scans
+        else:
+            anch = np.ascontiguousarray(np.asarray(anchors).reshape(-1), np.int32)
+            na = anch.size
+            ap = _p(anch if na else np.zeros(1, np.int32))
+        opt = LocalMapOptions()
+        self._L.sgtd_default_local_map_options(C.byref(opt))
+        opt.radius, opt.max_members, opt.max_pass_points = float(radius), int(max_members), int(max_pass_points)
+        cfg = self._scan_config(config)
+        self._lm_n = na
+        self._check(self._L.sgtd_local_map_keypoints(self._h, C.byref(cfg) if cfg is not None else None, C.byref(opt), pp, int(shape[-1]), lp,
+                                                     _p(off), _p(pose if n_scans else np.zeros((1, 12), np.float32)), n_scans, ap, na, dev))
+        return self.local_map_results() if fetch else None
+
+    def local_map_results(self):
+        n = C.c_int64(0)
+        off = np.zeros(self._lm_n + 1, np.int64)
+        self._check(self._L.sgtd_result_local_map_keypoints(self._h, _p(off), None, None, None, 0, C.byref(n)))
+        k = n.value
+        xyz, label, n_points = np.zeros((k, 3), np.float32), np.zeros(k, np.uint32), np.zeros(k, np.int32)
+        self._check(self._L.sgtd_result_local_map_keypoints(self._h, _p(off), _p(xyz), _p(label), _p(n_points), k, C.byref(n)))
+        return xyz, label, off, n_points
+
+    def local_map_members(self):
+        """mem_off (A + 1,) i64, member (M,) i32 scan indices (each anchor first, then ascending), merged_points (A,) i64,
+        and the number of passes of the last local_map_keypoints call"""
+        n, passes = C.c_int64(0), C.c_int32(0)
+        off, merged = np.zeros(self._lm_n + 1, np.int64), np.zeros(max(self._lm_n, 1), np.int64)
+        self._check(self._L.sgtd_result_local_map_members(self._h, _p(off), None, 0, C.byref(n), _p(merged), C.byref(passes)))
+        member = np.zeros(max(n.value, 1), np.int32)
+        self._check(self._L.sgtd_result_local_map_members(self._h, None, _p(member), n.value, None, None, None))
+        return off, member[:n.value], merged[:self._lm_n], passes.value
+
+    def local_map_stage_ms(self):
+        """(members, gather, scan passes) milliseconds of the last call between events (zeros unless set_timing is on)"""
+        ms = [C.c_float(0) for _ in range(3)]
+        self._check(self._L.sgtd_local_map_stage_ms(self._h, *[C.byref(m) for m in ms]))
+        return tuple(m.value for m in ms)
+
+    def _local_map_view(self):
+        """the local-map keypoints as add_frames / query_frames arguments (as _scan_view)"""
+        if self.device_count > 1:
+            xyz, label, off, _ = self.local_map_results()
+            self._keep = (xyz, label)
+            return _p(xyz), _p(label), off, 0
+        x, l = C.c_void_p(), C.c_void_p()
+        self._check(self._L.sgtd_local_map_device_view(self._h, C.byref(x), C.byref(l)))
+        off = np.zeros(self._lm_n + 1, np.int64)
+        self._check(self._L.sgtd_result_local_map_keypoints(self._h, _p(off), None, None, None, 0, None))
+        return x, l, off, 1
+
+    def add_local_maps(self, points, labels, pt_off, poses, anchors=None, **kw):
+        """local_map_keypoints, then add_frames on the keypoints where they lie on the device and set_frame_poses with
+        the anchors' poses under the ids the frames were added with; returns the keypoint offsets"""
+        self.local_map_keypoints(points, labels, pt_off, poses, anchors, fetch=False, **kw)
+        x, l, off, dev = self._local_map_view()
+        nf = off.size - 1
+        c0 = self.current_frame_id_
+        self._check(self._L.sgtd_add_frames(self._h, x, l, _p(off), nf, dev))
+        if nf:
+            rows = self._pose_rows(poses, np.asarray(poses).shape[0])
+            idx = np.arange(nf) if anchors is None else np.asarray(anchors, np.int64).reshape(-1)
+            self.set_frame_poses(np.arange(c0, c0 + nf, dtype=np.int64), rows[idx])
+        return off
+
+    def query_local_maps(self, points, labels, pt_off, poses, anchors=None, fetch=True, **kw):
+        """local_map_keypoints, then query_frames on the keypoints where they lie on the device"""
+        self.local_map_keypoints(points, labels, pt_off, poses, anchors, fetch=False, **kw)
+        x, l, off, dev = self._local_map_view()
         self._nq = off.size - 1
         self._check(self._L.sgtd_query_frames(self._h, x, l, _p(off), self._nq, dev))
         return self.results() if fetch else None

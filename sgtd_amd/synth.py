@@ -421,3 +421,49 @@ def make_scans(n_scans, n_points, stream=1, n_blobs=12, classes=SCAN_CLASSES, in
     points = np.concatenate(pts) if pts else np.zeros((0, stride), np.float32)
     labels = np.concatenate(labs) if labs else np.zeros(0, np.uint32)
     return points, labels, off
+
+
+def make_posed_scans(n_scans, n_points, stream=1, spacing=2.0, n_blobs=60, sensor_range=40.0, extent=None, classes=SCAN_CLASSES,
+                     sigma=(0.08, 0.3), yaw_step=0.02, stride=4):
+    """one static world of labelled Gaussian blobs seen from n_scans poses along a gently turning path, `spacing` metres
+    apart: every scan holds n_points points (a sequence: per scan) drawn from the blobs within sensor_range of its pose, expressed in that
+    scan's frame (so merging scans of neighbouring poses means something; make_scans draws unrelated scenes).  The blobs
+    lie within `extent` metres (default: the path's length plus the sensor range) around the path.  Returns points
+    (total, stride) f32, labels (total,) u32, pt_off (n_scans + 1,) i64 and poses (n_scans, 12) f32 rows [R | t], the
+    sensor poses in the world."""
+    rng = _rng(stream, 7000)
+    counts = np.broadcast_to(np.asarray(n_points, np.int64), (n_scans,)) if n_scans else np.zeros(0, np.int64)
+    yaw = np.arange(n_scans) * yaw_step
+    step = np.stack([np.cos(yaw), np.sin(yaw), np.zeros(n_scans)], axis=1) * spacing
+    pos = np.concatenate([np.zeros((1, 3)), np.cumsum(step, axis=0)])[:n_scans] if n_scans else np.zeros((0, 3))
+    poses = np.zeros((n_scans, 3, 4), np.float64)
+    poses[:, 0, 0], poses[:, 0, 1], poses[:, 1, 0], poses[:, 1, 1], poses[:, 2, 2] = np.cos(yaw), -np.sin(yaw), np.sin(yaw), np.cos(yaw), 1.0
+    poses[:, :, 3] = pos
+    poses = poses.reshape(-1, 12).astype(np.float32)
+    lo = (pos.min(axis=0) if n_scans else np.zeros(3)) - (extent or sensor_range)
+    hi = (pos.max(axis=0) if n_scans else np.zeros(3)) + (extent or sensor_range)
+    centre = rng.uniform(lo, hi, (n_blobs, 3))
+    centre[:, 2] = rng.uniform(-1.5, 2.0, n_blobs)
+    sg = rng.uniform(sigma[0], sigma[1], n_blobs)
+    cls = rng.choice(np.asarray(classes), n_blobs)
+    pts, labs = [], []
+    for s in range(n_scans):
+        p64 = poses[s].astype(np.float64).reshape(3, 4)
+        near = np.nonzero(np.linalg.norm(centre - p64[:, 3], axis=1) < sensor_range)[0]
+        n_points = int(counts[s]) if near.size else 0
+        p = np.zeros((n_points, stride), np.float32)
+        lab = np.zeros(n_points, np.uint32)
+        if n_points:
+            r = _rng(stream, 7001 + s)
+            which = near[r.integers(0, near.size, n_points)]
+            world = centre[which] + r.normal(0.0, 1.0, (n_points, 3)) * sg[which, None]
+            p[:, :3] = ((world - p64[:, 3]) @ p64[:, :3]).astype(np.float32)      # R^T (w - t)
+            if stride > 3:
+                p[:, 3] = r.random(n_points).astype(np.float32)
+            lab = cls[which].astype(np.uint32)
+        pts.append(p)
+        labs.append(lab)
+    off = np.concatenate([[0], np.cumsum([len(l) for l in labs])]).astype(np.int64)
+    points = np.concatenate(pts) if pts else np.zeros((0, stride), np.float32)
+    labels = np.concatenate(labs) if labs else np.zeros(0, np.uint32)
+    return points, labels, off, poses
