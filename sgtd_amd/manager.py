@@ -604,9 +604,9 @@ class STDescManager:
             if off[-1] > int(np.prod(shape[:-1])):
                 raise ValueError("pt_off names more points than were given")
         cfg = self._scan_config(config)
-        self._scan_n = off.size - 1
         self._check(self._L.sgtd_scan_keypoints(self._h, C.byref(cfg) if cfg is not None else None, pp, int(shape[-1]), lp, _p(off),
                                                 off.size - 1, dev))
+        self._scan_n = off.size - 1      # (after the call: one that is refused leaves the earlier results, and their count)
         return self.scan_results() if fetch else None
 
     def scan_results(self):
@@ -711,9 +711,9 @@ class STDescManager:
         self._L.sgtd_default_local_map_options(C.byref(opt))
         opt.radius, opt.max_members, opt.max_pass_points = float(radius), int(max_members), int(max_pass_points)
         cfg = self._scan_config(config)
-        self._lm_n = na
         self._check(self._L.sgtd_local_map_keypoints(self._h, C.byref(cfg) if cfg is not None else None, C.byref(opt), pp, int(shape[-1]), lp,
                                                      _p(off), _p(pose if n_scans else np.zeros((1, 12), np.float32)), n_scans, ap, na, dev))
+        self._lm_n = na      # (after the call, as scan_keypoints)
         return self.local_map_results() if fetch else None
 
     def local_map_results(self):

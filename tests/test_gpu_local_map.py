@@ -12,6 +12,7 @@ import pytest
 
 import _local_map_ref as ref
 import _scan_ref as sref
+from _local_map_edges import bits, euler_poses, eye_poses, lib_cfg, restate, same_as  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,33 +37,6 @@ def tile(mods):
     return t.value
 
 
-def lib_cfg(cfg):
-    return None if cfg is None else {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in cfg.items()}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def restate(p, l, off, poses, cfg, **kw):
-    want = ref.local_map_rule(p, l, off, poses, anchors=kw.get("anchors"), radius=kw.get("radius", 15.0), max_members=kw.get("max_members", 0),
-                              cfg=cfg)
-    for a, (xyz, lab) in enumerate(want["clouds"]):
-        assert sref.clear_of_boundaries(xyz, lab, cfg), "the merged cloud of anchor %d sits on a rounding boundary" % a
-    return want
-
-
-def same_as(h, got, want, max_pass_points=0):
-    gx, gl, go, gn = got
-    assert np.array_equal(go, want["kp_off"]), (go, want["kp_off"])
-    assert np.array_equal(gl, want["label"]) and np.array_equal(gn, want["n_points"])
-    assert np.array_equal(bits(gx), bits(want["xyz"]))
-    mem_off, member, merged, n_passes = h.local_map_members()
-    assert np.array_equal(mem_off, want["mem_off"]) and np.array_equal(member, want["member"]), (member, want["member"])
-    assert np.array_equal(merged, want["merged_points"])
-    assert n_passes == ref.plan_passes(want["merged_points"], max_pass_points)
-
-
 def check(h, p, l, off, poses, cfg, dev=False, want=None, **kw):
     """one call on handle h compared with the restatement, which is returned"""
     off = np.asarray(off, np.int64)
@@ -80,29 +54,6 @@ def check(h, p, l, off, poses, cfg, dev=False, want=None, **kw):
 def scans(synth, counts, stream, **kw):
     kw.setdefault("n_blobs", 12)
     return synth.make_scans(len(counts), counts, stream=stream, **kw)
-
-
-def eye_poses(t):
-    """identity rotations at the translations t (n, 3)"""
-    t = np.asarray(t, np.float32).reshape(-1, 3)
-    p = np.zeros((len(t), 12), np.float32)
-    p[:, [0, 5, 10]] = 1.0
-    p[:, [3, 7, 11]] = t
-    return p
-
-
-def euler_poses(n, seed):
-    """general rotations (yaw, pitch, roll) rounded to f32 — not exactly orthonormal — a few metres apart"""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((n, 3, 4))
-    for k in range(n):
-        y, p, r = rng.uniform(-np.pi, np.pi), rng.uniform(-0.4, 0.4), rng.uniform(-0.4, 0.4)
-        rz = np.array([[np.cos(y), -np.sin(y), 0], [np.sin(y), np.cos(y), 0], [0, 0, 1]])
-        ry = np.array([[np.cos(p), 0, np.sin(p)], [0, 1, 0], [-np.sin(p), 0, np.cos(p)]])
-        rx = np.array([[1, 0, 0], [0, np.cos(r), -np.sin(r)], [0, np.sin(r), np.cos(r)]])
-        out[k, :, :3] = rz @ ry @ rx
-        out[k, :, 3] = rng.uniform(-3.0, 3.0, 3)
-    return out.reshape(n, 12).astype(np.float32)
 
 
 # ---- shapes ----

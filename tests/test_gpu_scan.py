@@ -12,10 +12,9 @@ import numpy as np
 import pytest
 
 import _scan_ref as ref
+from _scan_edges import R0, R1, R2, bits, cell, edge_cfg, lib_cfg, restate, run, same_as, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-R0, R1, R2 = 19.85, 20.17, 20.5      # ring k, k + 1, k + 2 of a class whose minPolar is 5.0 (bounds 19.6716, 20.004, 20.336, 20.6676)
 
 
 @pytest.fixture(scope="module")
@@ -44,37 +43,11 @@ def small_cfg(min_seg=2):
     return cfg
 
 
-def lib_cfg(cfg):
-    return None if cfg is None else {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in cfg.items()}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
 def check(h, points, labels, off, cfg=None, dev=False):
     """one call on handle h compared with the restatement; returns the restatement's per-scan results"""
-    off = np.asarray(off, np.int64)
-    for s in range(len(off) - 1):
-        assert ref.clear_of_boundaries(points[off[s]:off[s + 1]], labels[off[s]:off[s + 1]], cfg), "scan %d sits on a rounding boundary" % s
-    res, xyz, lab, kp_off, npts = ref.batch_rule(points, labels, off, cfg)
-    if dev:
-        import torch
-        dp, dl = torch.from_numpy(np.ascontiguousarray(points)).cuda(), torch.from_numpy(labels.view(np.int32)).cuda()
-        got = h.scan_keypoints(dp, dl, off, lib_cfg(cfg))
-    else:
-        got = h.scan_keypoints(points, labels, off, lib_cfg(cfg))
-    gx, gl, go, gn = got
-    assert np.array_equal(go, kp_off), (go, kp_off)
-    assert np.array_equal(gl, lab) and np.array_equal(gn, npts)
-    assert np.array_equal(bits(gx), bits(xyz))
-    for s, r in enumerate(res):
-        assert np.array_equal(h.scan_point_clusters(s), r["cluster"]), s
-        grid, rng = h.scan_grids(s)
-        assert np.array_equal(grid, r["grid"]), (s, grid[10:19], r["grid"][10:19])
-        assert np.array_equal(bits(rng[:, 2:]), bits(r["range"][:, 2:])), s
-        assert np.all(np.abs(rng[:, :2] - r["range"][:, :2]) <= 1e-12), s
-    return res
+    want = restate(points, labels, off, cfg)
+    same_as(h, run(h, points, labels, off, cfg, dev), want)
+    return want[0]
 
 
 def scans(synth, counts, stream, **kw):
@@ -133,20 +106,6 @@ def test_dropped_points(g, mods):
 
 
 # ---- edges of the rule: scenes at cell centres ----
-def cell(azi, pit, r, n=1, cls=15, inst=0, jitter=0.0, seed=0):
-    """n points in the voxel (azimuth cell azi, pitch cell pit) at range r: at its centre, or within `jitter` metres of it"""
-    az, pt = np.deg2rad(azi * 1.2), np.deg2rad(pit * 1.2)
-    c = np.array([r * np.cos(pt) * np.cos(az), r * np.cos(pt) * np.sin(az), r * np.sin(pt)])
-    p = np.tile(c, (n, 1))
-    if jitter:
-        p = p + np.random.default_rng(seed).uniform(-jitter, jitter, (n, 3))
-    return p.astype(np.float32), np.full(n, cls | (inst << 16), np.uint32)
-
-
-def scene(*parts):
-    return np.concatenate([p for p, _ in parts]), np.concatenate([l for _, l in parts])
-
-
 def edge_scenes():
     """name -> (points, labels, the n_points the rule must give, in keypoint order)"""
     s = {}
@@ -171,13 +130,6 @@ def edge_scenes():
     # the component with the smaller voxel key (azimuth cell 10) has the larger first point index
     s["order"] = scene(cell(40, 0, R0, 6), cell(10, 0, R0, 5)) + ([6, 5],)
     return s
-
-
-def edge_cfg():
-    cfg = ref.default_cfg()
-    cfg["min_seg"] = cfg["min_seg"].copy()
-    cfg["min_seg"][16] = 5
-    return cfg
 
 
 def test_edges_of_the_rule(g):
