@@ -1132,6 +1132,125 @@ int sgtd_result_local_map_members(sgtd_handle h, int64_t *mem_off /* n_anchors +
 int sgtd_local_map_device_view(sgtd_handle h, const float **d_xyz, const uint32_t **d_label);
 int sgtd_local_map_stage_ms(sgtd_handle h, float *ms_members, float *ms_gather, float *ms_scan);
 
+/* Dense registration of raw clouds on the device: plane-regularised GICP (the node's enable_gicp path,
+ * semantic_graph_localization.cpp:651-723; fast_gicp::FastGICP, fast_gicp_impl.hpp / lsq_registration_impl.hpp), the one
+ * stage behind sgtd_verify that sees the dense geometry.  n_clouds clouds lie back to back in `points` (stride_floats 3
+ * or 4 floats a point, x y z first; cloud c = points pt_off[c] .. pt_off[c + 1]); pair k registers cloud src_cloud[k]
+ * onto cloud tgt_cloud[k] from init_pose[k] (rel_pose layout: rot row-major (9), t (3); x = R p + t takes a source point
+ * into the target's frame; NULL = the identity).  A cloud is given once and may be the source or the target of any number
+ * of pairs; covariances are computed once per cloud that some pair names.
+ * The rule.  All arithmetic is f64, every operation (+, -, *, /, sqrt) rounded once, no contraction, nothing else is used;
+ * the f32 coordinates are widened exactly.  UNIT, ROT, "M v" and the 6x6 Cholesky with its two substitutions are those of
+ * sgtd_relax_poses; mul3(a, b)[r][c] = (a[r][0]*b[0][c] + a[r][1]*b[1][c]) + a[r][2]*b[2][c]; svd3 is sgtd_verify's
+ * one-sided Jacobi SVD (singular values descending), unpinned against Eigen's as there.
+ *   d2(a, b) = (dx*dx + dy*dy) + dz*dz.  A search keeps the smallest (d2, index), lexicographically; a d2 that is NaN or
+ *     +inf is never chosen (a point with a non-finite coordinate has no neighbour and is nobody's; the reference's
+ *     kd-trees have no rule for it).
+ *   SUM over the source points i of a pair: sgtd_refine_poses' ordered sum: SGTD_REG_SUM_W accumulators start at +0.0,
+ *     point i is added to accumulator i mod W in ascending i, an unmatched point is skipped (not added as zero), then
+ *     acc[l] = acc[l] + acc[l + s] for l < s, s = W/2, ..., 1.
+ *   Covariance of point i of a cloud of n points (fast_gicp_impl.hpp:244-298, PLANE): k' = min(k_neighbors, n); the
+ *     neighbours are the (at most) k' points of the cloud with the smallest (d2(p_i, p_j), j), i itself included; mu[a] =
+ *     (from +0.0, + p_j[a] in that order) / (double)k'; c[a][b] = (from +0.0, + (p_j[a] - mu[a]) * (p_j[b] - mu[b]) in
+ *     that order) / (double)k'; c = U S V^T by svd3; a column b of U with (U[0][b]*V[0][b] + U[1][b]*V[1][b]) +
+ *     U[2][b]*V[2][b] < 0 is negated (svd3 completes the columns of U of zero singular values up to sign only: on an
+ *     exactly flat neighbourhood C n = plane_eps n needs the normal's two copies to agree); C = mul3(mul3(U, D), V^T)
+ *     with D = diag(1, 1, plane_eps), zeros written out.  Departures: ties by index where the reference has FLANN's
+ *     order; k' in the divisor where the reference keeps k; svd3 in place of JacobiSVD.
+ *   Correspondences at a pose (R, t) (:118-155): x_i = (R p_i) + t, x[r] = ((R[r][0]*p[0] + R[r][1]*p[1]) + R[r][2]*p[2])
+ *     + t[r]; j(i) = the target index with the smallest (d2(x_i, w_j), j) and dd_i that d2 (+inf when no target has one);
+ *     the match is kept iff dd_i < max_corr_dist * max_corr_dist, else j(i) = -1.  For a kept match S = C_B[j] + G with
+ *     RC = mul3(R, C_A[i]), G[r][c] = (RC[r][0]*R[c][0] + RC[r][1]*R[c][1]) + RC[r][2]*R[c][2], and M_i = inverse of S:
+ *       a00 = S11*S22 - S12*S21;  a01 = S02*S21 - S01*S22;  a02 = S01*S12 - S02*S11;
+ *       a10 = S12*S20 - S10*S22;  a11 = S00*S22 - S02*S20;  a12 = S02*S10 - S00*S12;
+ *       a20 = S10*S21 - S11*S20;  a21 = S01*S20 - S00*S21;  a22 = S00*S11 - S01*S10;
+ *       det = (S00*a00 + S01*a10) + S02*a20;  M[r][c] = a[r][c] / det.
+ *     Departures: the reference transforms and searches in f32, and inverts a 4x4 whose last row is padding.
+ *   Linearisation (:158-214): e = w_j - x_i; y = M_i e; cost_i = (e[0]*y[0] + e[1]*y[1]) + e[2]*y[2]; J = [A | -I] with
+ *     A = skew(x_i) = ((0, -x2, x1), (x2, 0, -x0), (-x1, x0, 0)), zeros written out; MA = mul3(M_i, A).  Only the lower
+ *     triangle of H is formed: for a >= b in 0..2: H[a][b] = SUM of (A[0][a]*MA[0][b] + A[1][a]*MA[1][b]) + A[2][a]*MA[2][b];
+ *     H[3+a][b] = SUM of -MA[a][b]; for a >= b: H[3+a][3+b] = SUM of M_i[a][b].  b[a] = SUM of (A[0][a]*y[0] + A[1][a]*y[1])
+ *     + A[2][a]*y[2], b[3+a] = SUM of -y[a]; y0 = SUM of cost_i; n = the number of kept matches.  One iteration is counted.
+ *     n == 0: the solve ends "no correspondence", the pose is kept.
+ *   Step (lsq_registration_impl.hpp:123-168).  On the first linearisation of a pair lambda = lm_init_lambda_factor * m, m
+ *     from 0.0 over a = 0..5: v = |H[a][a]|, m = v > m ? v : m.  nu = 2.0.  Up to lm_max_trials trials; when they run out
+ *     the solve ends "LM failed", the pose is kept (:69-71).  A trial: (H + lambda I) d = -b by the Cholesky column by
+ *     column (only the diagonal gets lambda: s starts from H[c][c] + lambda) and the two substitutions on r = -b.  A pivot
+ *     that is not > 0: the trial is rejected with no more work: lambda = nu*lambda, nu = 2.0*nu.  Otherwise
+ *     dR = ROT(UNIT((1.0, 0.5*d[0], 0.5*d[1], 0.5*d[2]))), dt = (d[3], d[4], d[5]) (departure: the first-order form of the
+ *     reference's se3_exp, which takes sin and cos; the same fixed point); the trial pose R' = mul3(dR, R), t' = (dR t) +
+ *     dt; yi = SUM of cost_i at the trial pose with the matches and M_i of the linearisation (:217-240); den = from t_0,
+ *     + t_a ascending, t_a = d[a] * (lambda*d[a] - b[a]); rho = (y0 - yi) / den; mr = from 0.0 over dR's entries row-major:
+ *     v = |dR[r][c] - I[r][c]|, m = v > m ? v : m; mt the same over |dt[a]|; u = mr / rotation_eps, v = mt / translation_eps;
+ *     conv = (v > u ? v : u) < 1.0.  Not (rho >= 0) (a NaN rho too; departure: the reference accepts a NaN): with conv the
+ *     iteration ends and the pose is kept; otherwise lambda = nu*lambda, nu = 2.0*nu and the next trial follows.
+ *     Otherwise the trial becomes the pose, f = 2.0*rho - 1.0, g = 1.0 - (f*f)*f, lambda = lambda * (g > 1.0/3.0 ? g :
+ *     1.0/3.0), and the iteration ends.  An iteration that ends with conv ends the solve "converged"; otherwise
+ *     max_iterations counted iterations end it "iteration limit".
+ *   Results per pair: the pose; cost = y0 of the first and of the last linearisation (NaN without one); the matches
+ *     under the final pose from one more correspondence pass: tgt_index[i] = j(i) or -1 and d2[i] = dd_i; n_matched;
+ *     fitness = SUM of dd_i over the kept matches / (double)n_matched, NaN without a match (with max_corr_dist = +inf
+ *     pcl's getFitnessScore, in f64); iterations; status.  An empty source or target: "no points", pose = init_pose, no
+ *     iteration.  No result of a pair depends on the other pairs of the call, or on how the work is tiled.
+ * On the device: covariances a lane per point, the cloud streamed through LDS in tiles of SGTD_REG_TGT_TILE; the search
+ * a workgroup per (tile of SGTD_REG_SRC_TILE source points, slice of the target), the slices' minima combined exactly;
+ * every SUM one workgroup per pair; one lane per pair takes every decision, the host enqueues SGTD_REG_GROUP rounds
+ * (search - match - linearise - trial; a pair in its trials skips the first three) and reads the number of unfinished
+ * pairs once per group.  The search is brute force: n_source * n_target distances per pass, so thin raw scans first.
+ * The call is a pure function of its arguments: independent of the pending batch, the table and the stored poses; it
+ * uses buffers of its own on the handle's stream; a view runs it whatever state its owner is in; a multi-device handle
+ * runs it on its first device.  The results last until the next sgtd_register_clouds call that passes its argument
+ * checks, or sgtd_destroy.  device_ptrs != 0: `points` is a device array (everything else is the host's).
+ * h == NULL, a negative count, with a positive count: pt_off, points, src_cloud or tgt_cloud NULL; a stride other than 3
+ * or 4; pt_off[0] != 0 or decreasing offsets; a cloud index outside [0, n_clouds); a non-finite init_pose; k_neighbors
+ * outside 3..32, max_iterations or lm_max_trials < 1, max_corr_dist NaN or <= 0 (+inf is allowed), another option not
+ * finite and > 0, reserved != 0: SGTD_ERR_INVALID, before the device is touched and with the earlier results kept.  A
+ * cloud of more than SGTD_REG_MAX_POINTS points, more than SGTD_REG_MAX_CLOUDS clouds, SGTD_REG_MAX_TOTAL_POINTS points in
+ * all, SGTD_REG_MAX_PAIRS pairs or SGTD_REG_MAX_SOURCE_POINTS source points summed over the pairs: SGTD_ERR_UNSUPPORTED
+ * (sgtd_last_error says which), the earlier results kept as well.
+ * The getters before a successful run: SGTD_ERR_STATE; a cloud or pair outside the run: SGTD_ERR_INVALID; more than
+ * capacity: SGTD_ERR_CAPACITY (*n = the size needed, the first `capacity` entries written).  Any array may be NULL.
+ * sgtd_result_register_covariances: row-major 3x3 per point of the cloud; *n = 0 for a cloud no pair names.
+ * sgtd_register_stage_ms: covariances, searches, everything else (matches, sums, control) and the whole call on the
+ * device, from events on the stream (zeros unless sgtd_set_timing is on; the events serialise the call). */
+#define SGTD_REG_SUM_W 256
+#define SGTD_REG_SRC_TILE 128
+#define SGTD_REG_TGT_TILE 512
+#define SGTD_REG_SLICE_TILES 2
+#define SGTD_REG_GROUP 4
+#define SGTD_REG_MAX_K 32
+#define SGTD_REG_MAX_POINTS (1 << 17)
+#define SGTD_REG_MAX_CLOUDS (1 << 16)
+#define SGTD_REG_MAX_TOTAL_POINTS (1 << 25)
+#define SGTD_REG_MAX_PAIRS (1 << 16)
+#define SGTD_REG_MAX_SOURCE_POINTS (1 << 24)
+enum { SGTD_REG_CONVERGED = 0, SGTD_REG_ITERATION_LIMIT = 1, SGTD_REG_LM_FAILED = 2, SGTD_REG_NO_CORRESPONDENCE = 3, SGTD_REG_NO_POINTS = 4 };
+typedef struct sgtd_register_options {
+  int32_t k_neighbors;           /* 20 (SG_localization.yaml:24); 3..32 */
+  int32_t max_iterations;        /* 64 (lsq_registration_impl.hpp:11; the node sets 10) */
+  int32_t lm_max_trials;         /* 10 (:17) */
+  int32_t reserved;              /* 0 */
+  double max_corr_dist;          /* +inf (fast_gicp's default); > 0, +inf allowed */
+  double lm_init_lambda_factor;  /* 1e-9 */
+  double rotation_eps;           /* 2e-3 */
+  double translation_eps;        /* 5e-4 */
+  double plane_eps;              /* 1e-3: the PLANE regularisation's third value */
+} sgtd_register_options;
+void sgtd_default_register_options(sgtd_register_options *o);
+int sgtd_register_clouds(sgtd_handle h, const sgtd_register_options *opt /* NULL = defaults */,
+                         const float *points, int stride_floats /* 3 or 4 */, const int64_t *pt_off /* host, n_clouds + 1 */, int n_clouds,
+                         const int32_t *src_cloud, const int32_t *tgt_cloud, const double *init_pose /* [n_pairs*12], NULL = identity */,
+                         int n_pairs, int device_ptrs /* points only */);
+int sgtd_result_registered(sgtd_handle h, double *pose /*[n*12]*/, double *fitness, double *cost /*[n*2] first, last*/,
+                           int32_t *n_matched, int32_t *iterations, int32_t *status);
+int sgtd_result_register_covariances(sgtd_handle h, int cloud, double *cov /*[cap*9]*/, int64_t capacity, int64_t *n);
+int sgtd_result_register_matches(sgtd_handle h, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n);
+int sgtd_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total);
+/* the tile sizes above, and the slice length (targets) a call uses unless the SGTD_REG_SLICE_TILES environment hook,
+ * read at every call, gives another number of tiles; a call whose slices' minima would pass 2^27 entries doubles the
+ * length until they fit (no result depends on it) */
+void sgtd_register_tiles(int *src_tile, int *tgt_tile, int *slice);
+
 /* Page-locked host memory for the destination buffers of the fetch calls (sgtd_fetch_entries,
  * sgtd_result_pairs, ...): a copy into it is one direct DMA transfer — pageable memory goes through the
  * runtime's staging at about a third of the rate.  Allocation is slow (milliseconds): keep the buffers

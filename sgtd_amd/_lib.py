@@ -43,6 +43,8 @@ SYMBOLS = [
     "sgtd_result_scan_grids", "sgtd_scan_device_view", "sgtd_scan_tiles",
     "sgtd_default_local_map_options", "sgtd_local_map_keypoints", "sgtd_result_local_map_keypoints", "sgtd_result_local_map_members",
     "sgtd_local_map_device_view", "sgtd_local_map_stage_ms",
+    "sgtd_default_register_options", "sgtd_register_clouds", "sgtd_result_registered", "sgtd_result_register_covariances",
+    "sgtd_result_register_matches", "sgtd_register_stage_ms", "sgtd_register_tiles",
 ]
 
 
@@ -123,6 +125,13 @@ class ScanConfig(C.Structure):
 class LocalMapOptions(C.Structure):
     """sgtd_local_map_options"""
     _fields_ = [("radius", C.c_double), ("max_members", C.c_int32), ("reserved", C.c_int32), ("max_pass_points", C.c_int64)]
+
+
+class RegisterOptions(C.Structure):
+    """sgtd_register_options"""
+    _fields_ = [("k_neighbors", C.c_int32), ("max_iterations", C.c_int32), ("lm_max_trials", C.c_int32), ("reserved", C.c_int32),
+                ("max_corr_dist", C.c_double), ("lm_init_lambda_factor", C.c_double), ("rotation_eps", C.c_double),
+                ("translation_eps", C.c_double), ("plane_eps", C.c_double)]
 
 
 def build_library(force=False):
@@ -234,6 +243,15 @@ def lib():
     L.sgtd_result_local_map_members.argtypes = [vp, vp, vp, i64, C.POINTER(i64), vp, C.POINTER(i32)]
     L.sgtd_local_map_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.sgtd_local_map_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.sgtd_default_register_options.argtypes = [C.POINTER(RegisterOptions)]
+    L.sgtd_default_register_options.restype = None
+    L.sgtd_register_clouds.argtypes = [vp, C.POINTER(RegisterOptions), vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int]
+    L.sgtd_result_registered.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.sgtd_result_register_covariances.argtypes = [vp, C.c_int, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_register_matches.argtypes = [vp, C.c_int, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_register_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.sgtd_register_tiles.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sgtd_register_tiles.restype = None
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

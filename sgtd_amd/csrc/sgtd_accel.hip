@@ -33,6 +33,7 @@
 #include "align_kernels.hip.h"
 #include "consistency_kernels.hip.h"
 #include "relax_kernels.hip.h"
+#include "register_kernels.hip.h"
 #include "consensus_kernels.hip.h"
 #include "scan_kernels.hip.h"
 #include "local_map_kernels.hip.h"
@@ -326,6 +327,19 @@ struct sgtd_engine {
   std::vector<int> rx_host_csr;
   std::vector<double> rx_host_w;
   std::vector<unsigned char> rx_host_held;
+  // sgtd_register_clouds (register_kernels.hip.h): independent of the batch.  rg_in: the call's index arrays, offsets and
+  // start poses; rg_pts: the points when the host gave them; rg_cov: a covariance per point; rg_part: the slices' minima;
+  // rg_match: the last pass's matches and M_i; rg_state: RegState per pair; rg_out: the result rows; rg_ctl: the count of
+  // unfinished pairs.  rg_n < 0: no results; rg_host_*: what the getters need of the call; rg_ms: covariances, searches,
+  // the rest, the whole call (filled under sgtd_set_timing)
+  DevBuf rg_in, rg_pts, rg_cov, rg_part, rg_match, rg_state, rg_out, rg_ctl;
+  int rg_n = -1;
+  std::vector<int64_t> rg_host_off;
+  std::vector<int> rg_host_idx;          // src [n], tgt [n], src_off [n + 1]
+  std::vector<unsigned char> rg_host_named;
+  std::vector<int> rg_host_up;           // (the source of the index upload)
+  hipEvent_t rg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float rg_ms[4] = {0.f, 0.f, 0.f, 0.f};
   // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (SK_*: scan_run).  sk_n < 0:
   // no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets on the host
   enum { SK_PTS = 0, SK_LAB, SK_OFF, SK_SC, SK_R, SK_PITCH, SK_AZI, SK_MM, SK_VOTE, SK_GRID, SK_RANGE, SK_BOUNDS, SK_KEY_A, SK_KEY_B, SK_VAL_A, SK_VAL_B,
@@ -2235,13 +2249,16 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->pos_dev, &e->prior_dev, &e->filt_base,
                     &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state,
                     &e->cs_in, &e->cs_out,
-                    &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl};
+                    &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl,
+                    &e->rg_in, &e->rg_pts, &e->rg_cov, &e->rg_part, &e->rg_match, &e->rg_state, &e->rg_out, &e->rg_ctl};
   for (DevBuf *b : bufs) free_buf(*b);
   for (DevBuf &b : e->sk) free_buf(b);
   for (DevBuf &b : e->lm) free_buf(b);
   for (hipEvent_t ev : e->lm_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->ck_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : e->rg_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
@@ -4904,6 +4921,315 @@ int sgtd_result_relaxed(sgtd_handle e, double *pose, double *edge_cost) {
         for (int k = 0; k < 3; k++) pose[v * 12 + r * 4 + k] = rec[v * SGTD_RELAX_REC + 7 + r * 3 + k];
         pose[v * 12 + r * 4 + 3] = rec[v * SGTD_RELAX_REC + 4 + r];
       }
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_register_clouds: dense GICP registration (register_kernels.hip.h) ----
+namespace {
+static_assert(SGTD_REG_W == SGTD_REG_SUM_W && SGTD_REG_THREADS == SGTD_REG_SRC_TILE && SGTD_REG_TILE == SGTD_REG_TGT_TILE && SGTD_REG_K == SGTD_REG_MAX_K,
+              "the register kernels' sizes are the header's");
+constexpr size_t kRegPartMax = (size_t)1 << 27;      // entries of the slices' minima (12 B each) a call may hold: longer slices beyond
+
+// tiles of a slice: the header's, or the SGTD_REG_SLICE_TILES environment hook's
+int reg_slice_tiles() {
+  const char *hook = getenv("SGTD_REG_SLICE_TILES");
+  return hook && atoi(hook) > 0 ? std::min(atoi(hook), 1 << 10) : SGTD_REG_SLICE_TILES;
+}
+
+struct RegOut {      // rg_out: pose [n][12], fitness [n], cost [n][2] in f64, then matched, iterations, status [n] in i32
+  size_t n;
+  explicit RegOut(size_t n_) : n(n_) {}
+  size_t bytes() const { return n * (15 * sizeof(double) + 3 * sizeof(int)); }
+  double *pose(void *p) const { return static_cast<double *>(p); }
+  double *fitness(void *p) const { return pose(p) + n * 12; }
+  double *cost(void *p) const { return fitness(p) + n; }
+  int *matched(void *p) const { return reinterpret_cast<int *>(cost(p) + n * 2); }
+  int *iters(void *p) const { return matched(p) + n; }
+  int *status(void *p) const { return iters(p) + n; }
+};
+
+int reg_lap(sgtd_engine *e, int kind) {
+  HIPCHK(hipEventRecord(e->rg_ev[1], e->stream));
+  HIPCHK(hipEventSynchronize(e->rg_ev[1]));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, e->rg_ev[0], e->rg_ev[1]));
+  e->rg_ms[kind] += t;
+  HIPCHK(hipEventRecord(e->rg_ev[0], e->stream));
+  return SGTD_OK;
+}
+
+int reg_run(sgtd_engine *c, const sgtd_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
+            const int32_t *src, const int32_t *tgt, const double *init, int n) {
+  sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
+  HIPCHK(hipSetDevice(c->cfg.device_id));
+  const bool timed = c->timing;
+  c->rg_ms[0] = c->rg_ms[1] = c->rg_ms[2] = c->rg_ms[3] = 0.f;
+  if (timed)
+    for (hipEvent_t &ev : c->rg_ev)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+  const size_t total = (size_t)pt_off[n_clouds];
+  // what the getters need, and the tiles: of the pairs' sources, of the clouds some pair names
+  c->rg_host_off.assign(pt_off, pt_off + n_clouds + 1);
+  c->rg_host_named.assign((size_t)n_clouds, 0);
+  std::vector<int> &idx = c->rg_host_idx;
+  idx.assign(3 * (size_t)n + 1, 0);
+  int *h_src = idx.data(), *h_tgt = h_src + n, *h_soff = h_tgt + n;
+  std::vector<int> tile_pair, tile_first, ctile_cloud, ctile_first;
+  int64_t max_tgt = 0;
+  for (int k = 0; k < n; k++) {
+    h_src[k] = src[k]; h_tgt[k] = tgt[k];
+    c->rg_host_named[(size_t)src[k]] = 1; c->rg_host_named[(size_t)tgt[k]] = 1;
+    const int ns = (int)(pt_off[src[k] + 1] - pt_off[src[k]]);
+    h_soff[k + 1] = h_soff[k] + ns;
+    for (int f = 0; f < ns; f += SGTD_REG_THREADS) { tile_pair.push_back(k); tile_first.push_back(f); }
+    max_tgt = std::max<int64_t>(max_tgt, pt_off[tgt[k] + 1] - pt_off[tgt[k]]);
+  }
+  for (int cl = 0; cl < n_clouds; cl++) {
+    if (!c->rg_host_named[(size_t)cl]) continue;
+    const int np = (int)(pt_off[cl + 1] - pt_off[cl]);
+    for (int f = 0; f < np; f += SGTD_REG_THREADS) { ctile_cloud.push_back(cl); ctile_first.push_back(f); }
+  }
+  if (n == 0) return SGTD_OK;      // (a run without a pair: no cloud is named, nothing comes back)
+  const int total_src = h_soff[n], n_tiles = (int)tile_pair.size(), n_ctiles = (int)ctile_cloud.size();
+  long long slice = (long long)reg_slice_tiles() * SGTD_REG_TILE;
+  auto slices_of = [&](long long len) { return (size_t)std::max<long long>((max_tgt + len - 1) / len, 1); };
+  while ((size_t)total_src * slices_of(slice) > kRegPartMax) slice *= 2;
+  const size_t n_slices = slices_of(slice);
+
+  // the index upload: src, tgt, src_off, tile_pair, tile_first, ctile_cloud, ctile_first
+  std::vector<int> &up = c->rg_host_up;
+  up.clear();
+  up.insert(up.end(), idx.begin(), idx.end());
+  const size_t u_tile = up.size();
+  up.insert(up.end(), tile_pair.begin(), tile_pair.end());
+  up.insert(up.end(), tile_first.begin(), tile_first.end());
+  const size_t u_ctile = up.size();
+  up.insert(up.end(), ctile_cloud.begin(), ctile_cloud.end());
+  up.insert(up.end(), ctile_first.begin(), ctile_first.end());
+  const size_t o_off = 0, o_init = o_off + relax_up((size_t)(n_clouds + 1) * sizeof(int64_t)), o_idx = o_init + relax_up((size_t)n * 12 * sizeof(double)),
+               in_bytes = o_idx + relax_up(up.size() * sizeof(int));
+  const size_t ts = (size_t)std::max(total_src, 1);
+  const RegOut out((size_t)n);
+  CHK(ensure(c, c->rg_in, in_bytes));
+  CHK(ensure(c, c->rg_cov, std::max<size_t>(total, 1) * 9 * sizeof(double)));
+  CHK(ensure(c, c->rg_part, ts * n_slices * (sizeof(double) + sizeof(int))));
+  CHK(ensure(c, c->rg_match, ts * (10 * sizeof(double) + sizeof(int))));
+  CHK(ensure(c, c->rg_state, (size_t)n * sizeof(RegState)));
+  CHK(ensure(c, c->rg_out, out.bytes()));
+  CHK(ensure(c, c->rg_ctl, 64));
+  char *in = c->rg_in.as<char>();
+  CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
+  if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
+  CHK(h2d(c, in + o_idx, up.data(), up.size() * sizeof(int)));
+
+  RegParams P;
+  P.pts = points; P.stride = stride;
+  P.pt_off = reinterpret_cast<const long long *>(in + o_off);
+  const int *di = reinterpret_cast<const int *>(in + o_idx);
+  P.src = di; P.tgt = di + n; P.src_off = di + 2 * (size_t)n;
+  P.tile_pair = di + u_tile; P.tile_first = P.tile_pair + n_tiles;
+  P.ctile_cloud = di + u_ctile; P.ctile_first = P.ctile_cloud + n_ctiles;
+  P.n_pairs = n; P.n_tiles = n_tiles; P.n_ctiles = n_ctiles; P.total_src = (int)ts; P.slice = (int)slice;
+  P.cov = c->rg_cov.as<double>();
+  P.part_d2 = c->rg_part.as<double>(); P.part_j = reinterpret_cast<int *>(P.part_d2 + ts * n_slices);
+  P.md2 = c->rg_match.as<double>(); P.M = P.md2 + ts; P.mj = reinterpret_cast<int *>(P.M + 9 * ts);
+  P.st = c->rg_state.as<RegState>();
+  P.unfinished = c->rg_ctl.as<int>();
+  void *ob = c->rg_out.p;
+  P.out_pose = out.pose(ob); P.out_fitness = out.fitness(ob); P.out_cost = out.cost(ob);
+  P.out_matched = out.matched(ob); P.out_iters = out.iters(ob); P.out_status = out.status(ob);
+  P.o.k = o.k_neighbors; P.o.max_iterations = o.max_iterations; P.o.lm_max_trials = o.lm_max_trials;
+  P.o.max2 = o.max_corr_dist * o.max_corr_dist; P.o.lambda_factor = o.lm_init_lambda_factor;
+  P.o.rotation_eps = o.rotation_eps; P.o.translation_eps = o.translation_eps; P.o.plane_eps = o.plane_eps;
+
+  int unfinished = 0;
+  for (int k = 0; k < n; k++)
+    if (pt_off[src[k] + 1] > pt_off[src[k]] && pt_off[tgt[k] + 1] > pt_off[tgt[k]]) unfinished++;
+  CHK(h2d(c, P.unfinished, &unfinished, sizeof(int)));
+  hipStream_t s = c->stream;
+  const dim3 sgrid((unsigned)n_tiles, (unsigned)n_slices);
+  if (timed) { HIPCHK(hipEventRecord(c->rg_ev[2], s)); HIPCHK(hipEventRecord(c->rg_ev[0], s)); }
+  if (n_ctiles) reg_cov_kernel<<<n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
+  if (timed) CHK(reg_lap(c, 0));
+  reg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, init ? reinterpret_cast<const double *>(in + o_init) : nullptr);
+  HIPCHK(hipGetLastError());
+  // rounds in groups that fall through for the pairs that have ended; the count of unfinished pairs is read once per
+  // group.  Every round is one trial of every unfinished pair, so max_iterations * lm_max_trials rounds are the hard bound
+  const long long bound = (long long)o.max_iterations * o.lm_max_trials;
+  long long sent = 0;
+  while (unfinished > 0) {
+    if (sent >= bound) { c->err = "sgtd_register_clouds: the solves did not end within their limits"; return SGTD_ERR_HIP; }
+    const int group = (int)std::min<long long>(SGTD_REG_GROUP, bound - sent);
+    for (int g = 0; g < group; g++) {
+      reg_search_kernel<<<sgrid, SGTD_REG_THREADS, 0, s>>>(P, 0);
+      if (timed) CHK(reg_lap(c, 1));
+      reg_match_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, 0);
+      reg_lin_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
+      reg_trial_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
+      if (timed) CHK(reg_lap(c, 2));
+      HIPCHK(hipGetLastError());
+    }
+    sent += group;
+    CHK(d2h(c, &unfinished, P.unfinished, sizeof(int)));
+    CHK(xfer_sync(c));
+  }
+  if (n_tiles) {
+    reg_search_kernel<<<sgrid, SGTD_REG_THREADS, 0, s>>>(P, 1);
+    if (timed) CHK(reg_lap(c, 1));
+    reg_match_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, 1);
+  }
+  reg_final_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
+  HIPCHK(hipGetLastError());
+  if (timed) {
+    CHK(reg_lap(c, 2));
+    HIPCHK(hipEventElapsedTime(&c->rg_ms[3], c->rg_ev[2], c->rg_ev[1]));
+  }
+  CHK(xfer_sync(c));
+  return SGTD_OK;
+}
+
+int reg_ready(sgtd_engine *e, sgtd_engine **out) {
+  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
+  if (c->rg_n < 0) { e->err = "no registered clouds: sgtd_register_clouds has not run"; return SGTD_ERR_STATE; }
+  *out = c;
+  return SGTD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void sgtd_default_register_options(sgtd_register_options *o) {
+  if (!o) return;
+  o->k_neighbors = 20; o->max_iterations = 64; o->lm_max_trials = 10; o->reserved = 0;
+  o->max_corr_dist = std::numeric_limits<double>::infinity();
+  o->lm_init_lambda_factor = 1e-9; o->rotation_eps = 2e-3; o->translation_eps = 5e-4; o->plane_eps = 1e-3;
+}
+
+void sgtd_register_tiles(int *src_tile, int *tgt_tile, int *slice) {
+  if (src_tile) *src_tile = SGTD_REG_SRC_TILE;
+  if (tgt_tile) *tgt_tile = SGTD_REG_TGT_TILE;
+  if (slice) *slice = reg_slice_tiles() * SGTD_REG_TGT_TILE;
+}
+
+int sgtd_register_clouds(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
+                         const int32_t *src_cloud, const int32_t *tgt_cloud, const double *init_pose, int n_pairs, int device_ptrs) {
+  if (!e || n_clouds < 0 || n_pairs < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (n_pairs > 0 && (!src_cloud || !tgt_cloud)) return SGTD_ERR_INVALID;
+  sgtd_register_options o;
+  sgtd_default_register_options(&o);
+  if (opt) o = *opt;
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (o.k_neighbors < 3 || o.k_neighbors > SGTD_REG_MAX_K || o.max_iterations < 1 || o.lm_max_trials < 1 || o.reserved != 0 || !(o.max_corr_dist > 0.0) ||
+      !pos(o.lm_init_lambda_factor) || !pos(o.rotation_eps) || !pos(o.translation_eps) || !pos(o.plane_eps))
+    return SGTD_ERR_INVALID;
+  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
+  for (int cl = 0; cl < n_clouds; cl++)
+    if (pt_off[cl + 1] < pt_off[cl]) return SGTD_ERR_INVALID;
+  const int64_t total = pt_off[n_clouds];
+  if (total > 0 && !points) return SGTD_ERR_INVALID;
+  int64_t total_src = 0, max_cloud = 0;
+  for (int k = 0; k < n_pairs; k++) {
+    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || tgt_cloud[k] < 0 || tgt_cloud[k] >= n_clouds) return SGTD_ERR_INVALID;
+    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
+  }
+  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
+  for (int cl = 0; cl < n_clouds; cl++) max_cloud = std::max(max_cloud, pt_off[cl + 1] - pt_off[cl]);
+  if (max_cloud > SGTD_REG_MAX_POINTS || n_clouds > SGTD_REG_MAX_CLOUDS || total > SGTD_REG_MAX_TOTAL_POINTS || n_pairs > SGTD_REG_MAX_PAIRS ||
+      total_src > SGTD_REG_MAX_SOURCE_POINTS) {
+    e->err = "sgtd_register_clouds takes at most " + std::to_string(SGTD_REG_MAX_POINTS) + " points a cloud, " + std::to_string(SGTD_REG_MAX_CLOUDS) +
+             " clouds, " + std::to_string(SGTD_REG_MAX_TOTAL_POINTS) + " points in all, " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " +
+             std::to_string(SGTD_REG_MAX_SOURCE_POINTS) + " source points over the pairs";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
+  PinScope pin_scope(c);
+  c->rg_n = -1;
+  const float *d_pts = points;
+  int rc = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (rc == SGTD_OK && !device_ptrs && total > 0) {
+    const size_t bytes = (size_t)total * stride_floats * sizeof(float);
+    rc = ensure(c, c->rg_pts, bytes);
+    if (rc == SGTD_OK) rc = h2d(c, c->rg_pts.p, points, bytes);
+    d_pts = c->rg_pts.as<float>();
+  }
+  if (rc == SGTD_OK) rc = reg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
+  if (rc != SGTD_OK) {
+    if (c != e) e->err = c->err;
+    return rc;
+  }
+  c->rg_n = n_pairs;
+  return SGTD_OK;
+}
+
+int sgtd_result_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *iterations, int32_t *status) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(reg_ready(e, &c));
+  const size_t n = (size_t)c->rg_n;
+  if (n == 0) return SGTD_OK;
+  const RegOut out(n);
+  void *ob = c->rg_out.p;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && pose) st = d2h(c, pose, out.pose(ob), n * 12 * sizeof(double));
+  if (st == SGTD_OK && fitness) st = d2h(c, fitness, out.fitness(ob), n * sizeof(double));
+  if (st == SGTD_OK && cost) st = d2h(c, cost, out.cost(ob), n * 2 * sizeof(double));
+  if (st == SGTD_OK && n_matched) st = d2h(c, n_matched, out.matched(ob), n * sizeof(int));
+  if (st == SGTD_OK && iterations) st = d2h(c, iterations, out.iters(ob), n * sizeof(int));
+  if (st == SGTD_OK && status) st = d2h(c, status, out.status(ob), n * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return SGTD_OK;
+}
+
+int sgtd_result_register_covariances(sgtd_handle e, int cloud, double *cov, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(reg_ready(e, &c));
+  if (cloud < 0 || (size_t)cloud >= c->rg_host_named.size()) return SGTD_ERR_INVALID;
+  const int64_t first = c->rg_host_off[(size_t)cloud];
+  const int64_t need = c->rg_host_named[(size_t)cloud] ? c->rg_host_off[(size_t)cloud + 1] - first : 0;
+  if (n) *n = need;
+  const size_t m = cov ? (size_t)std::min(need, capacity) : 0;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && m) st = d2h(c, cov, c->rg_cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_register_matches(sgtd_handle e, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(reg_ready(e, &c));
+  if (pair < 0 || pair >= c->rg_n) return SGTD_ERR_INVALID;
+  const int *soff = c->rg_host_idx.data() + 2 * (size_t)c->rg_n;
+  const int64_t first = soff[pair], need = soff[pair + 1] - first;
+  const size_t ts = (size_t)std::max(soff[c->rg_n], 1);
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  const double *md2 = c->rg_match.as<double>();
+  const int *mj = reinterpret_cast<const int *>(md2 + 10 * ts);
+  if (st == SGTD_OK && m && tgt_index) st = d2h(c, tgt_index, mj + first, m * sizeof(int));
+  if (st == SGTD_OK && m && d2) st = d2h(c, d2, md2 + first, m * sizeof(double));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return need > capacity && (tgt_index || d2) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(reg_ready(e, &c));
+  if (ms_cov) *ms_cov = c->rg_ms[0];
+  if (ms_search) *ms_search = c->rg_ms[1];
+  if (ms_rest) *ms_rest = c->rg_ms[2];
+  if (ms_total) *ms_total = c->rg_ms[3];
   return SGTD_OK;
 }
 

@@ -94,6 +94,23 @@ def account(metrics, gt_pose4, map_pose4, search_frame, loop_rot, loop_t, cand_f
     return t_err, r_err
 
 
+def choose_registered(frames, fitness, best_fitness, cap=100.0):
+    """the node's choice among registered candidates (:672-722), walked in the order given (STDescManager.register_loops'
+    order of one query): the first candidate with fitness < best_fitness wins and the walk ends; otherwise the lowest
+    fitness below `cap` (the first of equal ones); otherwise SearchLoop's choice stays.  NaN never wins.
+    -> (index, frame, fitness), or (-1, -1, NaN) when SearchLoop's choice stays"""
+    best, best_fit = -1, float(cap)
+    for k, f in enumerate(np.asarray(fitness, np.float64).reshape(-1)):
+        if f < best_fit:
+            best, best_fit = k, float(f)
+        if f < best_fitness:
+            best, best_fit = k, float(f)
+            break
+    if best < 0:
+        return -1, -1, float("nan")
+    return best, int(np.asarray(frames).reshape(-1)[best]), best_fit
+
+
 def frames_near(map_xy, prior_xy, radius):
     """the map frames within `radius` of each position prior: bool [n_priors, n_map_frames], column f = map frame f
     (a row of STDescManager.set_frame_filter's boolean form)"""

@@ -141,6 +141,30 @@ def read_scan(bin_path, label_path):
     return points.reshape(-1, 4), labels
 
 
+def voxel_downsample(points, leaf):
+    """one point per occupied voxel, on the host: the cell of a point is floor(x / leaf) per axis (in f64), the point that
+    comes out is the centroid of the cell's points (f64 mean of every column, rounded to f32), and the cells come out in
+    the order of their smallest point index.  points: (n, 3 or 4) f32; rows with a non-finite coordinate are dropped.
+    The node thins the query scan with pcl's ApproximateVoxelGrid (semantic_graph_localization.cpp:660) before GICP;
+    STDescManager.register_clouds searches by brute force and needs the same thinning."""
+    p = np.asarray(points, np.float32)
+    if p.ndim != 2 or p.shape[1] not in (3, 4):
+        raise ValueError("points: (n, 3 or 4)")
+    if not (np.isfinite(leaf) and leaf > 0):
+        raise ValueError("leaf: finite and positive")
+    p = p[np.isfinite(p[:, :3]).all(axis=1)]
+    if p.shape[0] == 0:
+        return p.copy()
+    cell = np.floor(p[:, :3].astype(np.float64) / float(leaf)).astype(np.int64)
+    _, first, inverse = np.unique(cell, axis=0, return_index=True, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    rank = np.argsort(np.argsort(first))            # cell -> its place by smallest point index
+    slot = rank[inverse]
+    count = np.bincount(slot, minlength=first.size).astype(np.float64)
+    out = np.stack([np.bincount(slot, weights=p[:, c].astype(np.float64), minlength=first.size) / count for c in range(p.shape[1])], 1)
+    return out.astype(np.float32)
+
+
 def sensor_poses(poses, extrinsic):
     """pose · extrinsic in f64, rounded to f32: (n, 12) rows [R | t] of the sensor frames for callers that hold base
     poses and a fixed extrinsic such as the reference's BASE2OUSTER (src/sgtd/src/local_map.cpp:300) — what

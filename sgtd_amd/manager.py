@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, DescSoa, LocalMapOptions, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats
+from ._lib import Config, DescSoa, LocalMapOptions, RegisterOptions, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats
 
 DEFAULTS = dict(descriptor_near_num=10, candidate_num=50, max_frame_n=20000, device_id=0,
                 descriptor_min_len=0.5, descriptor_max_len=50.0, std_side_resolution=1.0,
@@ -1334,6 +1334,156 @@ class STDescManager:
         bo = np.zeros(nq, np.float64)
         self._check(self._L.sgtd_search_loop_aligned(self._h, float(min_overlap), float(max_rms), _p(bc), _p(bf), _p(br), _p(bo)))
         return bc, bf, br, bo
+
+    # ---- dense registration of raw clouds (sgtd_register_clouds) ---------------------------------------------
+    def register_tiles(self):
+        """source tile, target tile and slice length (points) of the register kernels"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._L.sgtd_register_tiles(C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def register_clouds(self, points, pt_off, src, tgt, init=None, **options):
+        """sgtd_register_clouds: plane-regularised GICP of raw clouds on the device.  points: (total, 3 or 4) f32, numpy or
+        a torch.cuda tensor, the clouds back to back; pt_off: the n_clouds + 1 offsets; src, tgt: (n,) cloud indices of
+        the pairs; init: (n, 12) start poses in the rel_pose layout (rot row-major, t; x = R p + t takes a source point
+        into the target's frame), None = the identity; options: fields of sgtd_register_options.  -> dict of pose [n, 12],
+        fitness [n], cost [n, 2] (first and last linearisation), n_matched, iterations, status [n] (int32)"""
+        if hasattr(points, "data_ptr"):
+            assert points.is_cuda and points.is_contiguous()
+            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
+            self._keep = points
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            shape, pp, dev = points.shape, _p(points), 0
+        if len(shape) != 2 or shape[1] not in (3, 4):
+            raise ValueError("points: (total, 3 or 4)")
+        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+        if off.size < 1:
+            raise ValueError("pt_off: n_clouds + 1 offsets")
+        if off[-1] > shape[0]:
+            raise ValueError("pt_off names more points than were given")
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        t = np.ascontiguousarray(tgt, np.int32).reshape(-1)
+        n = s.size
+        if t.size != n:
+            raise ValueError("src and tgt: one cloud index per pair")
+        p0 = None
+        if init is not None:
+            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
+            if p0.shape[0] != n:
+                raise ValueError("init: (n, 12), one start pose per pair")
+        opt = RegisterOptions()
+        self._L.sgtd_default_register_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(RegisterOptions._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        self._check(self._L.sgtd_register_clouds(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(s), _p(t), _p(p0), n, dev))
+        self._reg_n = n
+        return self.result_registered()
+
+    def result_registered(self):
+        n = self._reg_n
+        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
+               "n_matched": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
+        self._check(self._L.sgtd_result_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
+                                                   _p(out["iterations"]), _p(out["status"])))
+        return out
+
+    def register_covariances(self, cloud):
+        """the regularised covariances of one cloud of the last register_clouds call: (n, 3, 3) f64; 0 rows for a cloud no
+        pair named"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_register_covariances(self._h, int(cloud), None, 0, C.byref(n)))
+        cov = np.zeros((n.value, 3, 3), np.float64)
+        self._check(self._L.sgtd_result_register_covariances(self._h, int(cloud), _p(cov), n.value, C.byref(n)))
+        return cov
+
+    def register_matches(self, pair):
+        """the correspondences of one pair under its final pose: (tgt_index (n,) int32, -1 where none; d2 (n,) f64)"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_register_matches(self._h, int(pair), None, None, 0, C.byref(n)))
+        j, d2 = np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
+        self._check(self._L.sgtd_result_register_matches(self._h, int(pair), _p(j), _p(d2), n.value, C.byref(n)))
+        return j, d2
+
+    def register_stage_ms(self):
+        """device milliseconds of the last register_clouds call: covariances, searches, the rest, the whole call (zeros
+        unless set_timing(True))"""
+        v = [C.c_float(0) for _ in range(4)]
+        self._check(self._L.sgtd_register_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def register_pairs(self, max_per_query=5, start="verify"):
+        """the (query, candidate) pairs register_loops forms, after verify(): per query its candidates with a verification
+        result (score >= 0) in descending verify score, ties in candidate order (the node's :603), the first max_per_query
+        of them -> (query [m], cand [m], frame [m] (int32), init [m, 12]) with the pose of the named stage: "verify",
+        "refined" (refine_poses) or "aligned" (align_keypoints); a stage that has not run on this batch raises its state
+        error"""
+        if start not in ("verify", "refined", "aligned"):
+            raise ValueError('start: "verify", "refined" or "aligned"')
+        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
+            raise ValueError("max_per_query: an integer, not negative")
+        res = self.results()
+        qs, cs, fs, init = [], [], [], []
+        for q in range(self._nq):
+            score, rot, t = self.result_verify(q)
+            if start == "refined":
+                r = self.result_refined(q)
+                rot, t = r["rot"], r["t"]
+            elif start == "aligned":
+                r = self.result_aligned(q)
+                rot, t = r["rot"], r["t"]
+            nc = int(res.n_cand[q])
+            ok = [c for c in range(nc) if score[c] >= 0]
+            ok.sort(key=lambda c: -score[c])      # (stable: ties stay in candidate order)
+            for c in ok[:int(max_per_query)]:
+                qs.append(q)
+                cs.append(c)
+                fs.append(int(res.cand_frame[q, c]))
+                init.append(np.concatenate([rot[c].reshape(9), t[c]]))
+        return (np.array(qs, np.int32), np.array(cs, np.int32), np.array(fs, np.int32),
+                np.array(init, np.float64).reshape(-1, 12))
+
+    def register_loops(self, query_points, query_pt_off, map_clouds, max_per_query=5, start="verify", **options):
+        """Dense registration of the batch's best candidates, after verify(): register_pairs' (query, candidate) pairs,
+        each the query's raw cloud (query_points (total, 3 or 4) f32 with the n_queries + 1 offsets query_pt_off) against
+        map_clouds[frame] (a dict or sequence of (n, 3 or 4) f32 arrays by frame id; a frame without a cloud is skipped),
+        started from the named stage's pose, in ONE register_clouds call.  -> dict of query, cand, frame [m] (int32),
+        init [m, 12] and register_clouds' fields per pair.  Thin raw scans first (ingest.voxel_downsample): the search is
+        brute force.  The world pose of a pair is result_world_poses' composition (the frame's stored pose times the
+        relative pose) with the registered pose in place of verify()'s; the node's :747 multiplies the GICP transform on
+        the other side of the loop transform, which is not reproduced here."""
+        qp = np.ascontiguousarray(query_points, dtype=np.float32)
+        if qp.ndim != 2 or qp.shape[1] not in (3, 4):
+            raise ValueError("query_points: (total, 3 or 4)")
+        qoff = np.asarray(query_pt_off, np.int64).reshape(-1)
+        if qoff.size != self._nq + 1:
+            raise ValueError("query_pt_off: n_queries + 1 offsets")
+        q, c, f, init = self.register_pairs(max_per_query, start)
+
+        def cloud_of(frame):
+            if isinstance(map_clouds, dict):
+                return map_clouds.get(int(frame))
+            return map_clouds[frame] if 0 <= frame < len(map_clouds) else None
+
+        has = np.array([cloud_of(int(x)) is not None for x in f], bool)
+        q, c, f, init = q[has], c[has], f[has], init[has]
+        frames = sorted(set(int(x) for x in f))
+        stride = qp.shape[1]
+        clouds = []
+        for x in frames:
+            a = np.ascontiguousarray(cloud_of(x), dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != stride:
+                raise ValueError("map_clouds: (n, %d) arrays, as the query points" % stride)
+            clouds.append(a)
+        pts = np.concatenate([qp[:qoff[-1]]] + clouds) if clouds else qp[:qoff[-1]]
+        off = np.concatenate([qoff, qoff[-1] + np.cumsum([a.shape[0] for a in clouds], dtype=np.int64)]).astype(np.int64)
+        slot = {x: self._nq + k for k, x in enumerate(frames)}
+        tgt = np.array([slot[int(x)] for x in f], np.int32)
+        out = self.register_clouds(pts, off, q, tgt, init if len(q) else None, **options)
+        out.update(query=q, cand=c, frame=f, init=init, src_cloud=q.copy(), tgt_cloud=tgt, points=pts, pt_off=off)
+        return out
 
     def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None, prior=None):
         """sgtd_search_frame: candidate_selector + candidate_verify + the inlier pairs of every candidate with their table
