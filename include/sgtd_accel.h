@@ -1251,6 +1251,107 @@ int sgtd_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_search, float
  * length until they fit (no result depends on it) */
 void sgtd_register_tiles(int *src_tile, int *tgt_tile, int *slice);
 
+/* Voxelised GICP of clouds against voxel maps on the device (fast_gicp::FastVGICP, fast_vgicp_impl.hpp /
+ * fast_vgicp_voxel.hpp): the target of a pair is a map of Gaussian voxels accumulated from any number of posed clouds,
+ * and a source point is matched by looking up the voxel it lands in (and its 6 or 26 neighbours), so an iteration's cost
+ * does not depend on the target's size.  The clouds are given as for sgtd_register_clouds.  Map m has the members
+ * map_off[m] .. map_off[m + 1] of map_cloud (cloud indices) and map_pose (12 doubles per member, rel_pose layout:
+ * x = R p + t takes the member's points into the map's frame; NULL = the identity for every member, which goes through
+ * the same arithmetic as one written out).  Pair k registers cloud src_cloud[k] onto map tgt_map[k] from init_pose[k]
+ * (NULL = the identity).  A cloud may be a member of several maps, several times of one, and the source of pairs;
+ * covariances are computed once per cloud that is a source or a member, by sgtd_register_clouds' covariance rule.
+ * The rule builds on sgtd_register_clouds': all arithmetic is f64, every operation (+, -, *, /, sqrt) rounded once, no
+ * contraction; floor is the one addition and is exact.  mul3, svd3, UNIT, ROT, the Cholesky, SUM (SGTD_REG_SUM_W
+ * accumulators), d2 and the covariance rule are the ones stated there.
+ *   A member point in its map: x = (R p) + t as x_i there; Cx[r][c] = (RC[r][0]*R[c][0] + RC[r][1]*R[c][1]) + RC[r][2]*R[c][2]
+ *     with RC = mul3(R, C), C the point's covariance in its cloud; q[a] = floor(x[a] / voxel_resolution - 0.5)
+ *     (fast_vgicp_voxel.hpp:159).  The point enters the map iff x[0], x[1], x[2] are finite and every q[a] lies in
+ *     [-2^15, 2^15); otherwise it belongs to no voxel (departure: the reference casts to int unchecked).  Its voxel has the
+ *     key map << 48 | (q0 + 2^15) << 32 | (q1 + 2^15) << 16 | (q2 + 2^15); the voxels of a map are numbered from 0 in
+ *     ascending key.
+ *   A voxel (ADDITIVE, :105-122) of n points: mean[a] = VSUM(x[a]) / (double)n, cov[r][c] = VSUM(Cx[r][c]) / (double)n, all
+ *     nine entries.  VSUM: the voxel's points are ordered by member position within the map (map_off order), then by point
+ *     index within the member; SGTD_VREG_SUM_W accumulators start at +0.0, the r-th point (r from 0) is added to accumulator
+ *     r mod SGTD_VREG_SUM_W in ascending r, then acc[l] = acc[l] + acc[l + s] for l < s, s = SGTD_VREG_SUM_W / 2, ..., 1.
+ *   Correspondences at a pose (R, t) (fast_vgicp_impl.hpp:73-116): x_i = (R p_i) + t and q from x_i as above; an x_i that
+ *     is not finite or whose q is out of range has none.  For every offset o of neighbor_mode, in this order, the voxel
+ *     with the coordinates q + o of the pair's map is a correspondence if it exists (a q + o outside [-2^15, 2^15) names no
+ *     voxel).  Mode 1: (0,0,0).  Mode 7: (0,0,0), (1,0,0), (-1,0,0), (0,1,0), (0,-1,0), (0,0,1), (0,0,-1)
+ *     (fast_vgicp_voxel.hpp:21-29).  Mode 27: (i-1, j-1, k-1) for i, j, k in 0..2, i outermost (:35-42).  For a
+ *     correspondence with voxel v: S = cov_v + G_i, G_i as G in sgtd_register_clouds' rule from C_A[i] and R; M = the inverse
+ *     of S by the cofactor form there; w = sqrt((double)n_v); Mw[r][c] = w * M[r][c].
+ *   Linearisation: per correspondence e = mean_v - x_i and everything as in sgtd_register_clouds' rule with Mw in place
+ *     of M_i: y = Mw e, cost = (e[0]*y[0] + e[1]*y[1]) + e[2]*y[2], MA = mul3(Mw, A), the 21 + 6 terms of H and b.  The term
+ *     of a point is the sum of its correspondences' terms in offset order, starting from +0.0; SUM runs over the points,
+ *     a point without a correspondence is skipped.  n = the number of correspondences; n == 0 ends the solve "no
+ *     correspondence".  The trial cost yi is SUM over the points of (from +0.0, + cost of each correspondence in offset
+ *     order) at the trial pose with the correspondences and Mw of the linearisation.  lambda, nu, the trials, rho, the
+ *     convergence test, the iteration count and the statuses are sgtd_register_clouds'.  There is no max_corr_dist: the
+ *     voxel neighbourhood is the gate.
+ *   Results per pair: the pose; cost = y0 of the first and of the last linearisation (NaN without one); iterations;
+ *     status; and from one more correspondence pass at the final pose: voxel[i * mode + o] = the index within the map of
+ *     the voxel at q + o, or -1; n_corr = the number of correspondences; n_matched = the number of source points with at
+ *     least one; fitness = SUM over those points of m_i / (double)n_matched, m_i = from +inf over the point's
+ *     correspondences in offset order: dd = d2(x_i, mean_v), m = dd < m ? dd : m; NaN without a matched point.  A pair whose
+ *     source is empty or whose map has no voxel: "no points", pose = init_pose, no iteration.  No result of a pair depends
+ *     on the other pairs or maps of the call, or on how the work is tiled.
+ * Departures from fast_gicp: those of sgtd_register_clouds (covariances, the first-order step, the rejected NaN rho, the
+ * 3x3 inverse); the range check of q; f64 transforms of f32 points where the reference's voxel map is built from the f32
+ * cloud; the fixed summation orders where the reference sums per OpenMP thread; one voxel numbering per map in key order
+ * where the reference keeps a hash map; member poses and several members per map where the reference has one target
+ * cloud; only the ADDITIVE mode (MULTIPLICATIVE and ADDITIVE_WEIGHTED are not offered); the fitness is taken against the
+ * voxel means where the node's getFitnessScore searches the raw target cloud.
+ * On the device: keys a lane per member point, the stable radix sort, voxel heads and per-map voxel ranges, a wave per
+ * voxel for VSUM; per round a lane per source point looks its voxels up by binary search in the map's sorted keys and
+ * writes the voxel ids and Mw to per-correspondence streams; the sums a workgroup per pair; one lane per pair decides, the
+ * host enqueues SGTD_REG_GROUP rounds and reads the number of unfinished pairs once per group.
+ * The call is a pure function of its arguments like sgtd_register_clouds: buffers of its own on the handle's stream,
+ * usable on a view, on the first device of a multi-device handle; its results last until the next sgtd_register_voxels
+ * call that passes its argument checks, or sgtd_destroy, and are independent of sgtd_register_clouds' (neither call
+ * disturbs the other's results).  device_ptrs != 0: `points` is a device array (everything else is the host's).
+ * SGTD_ERR_INVALID, before the device is touched and with the earlier results kept: everything sgtd_register_clouds
+ * rejects of the clouds, pairs, init_pose and the shared options; n_maps < 0; with a positive count: map_off, map_cloud or
+ * tgt_map NULL; map_off[0] != 0 or decreasing map_off; a member cloud outside [0, n_clouds); a pair's map outside
+ * [0, n_maps); a non-finite map_pose; a voxel_resolution that is not finite and > 0; a neighbor_mode other than 1, 7, 27.
+ * SGTD_ERR_UNSUPPORTED (sgtd_last_error says which), the earlier results kept as well: sgtd_register_clouds' caps on a
+ * cloud, the clouds, all points and the pairs; more than SGTD_VREG_MAX_MAPS maps; more than SGTD_VREG_MAX_MEMBER_POINTS
+ * member points summed over the maps; more than SGTD_VREG_MAX_CORR for the source points summed over the pairs times
+ * neighbor_mode (the per-correspondence streams hold 76 bytes each).
+ * The getters before a successful run: SGTD_ERR_STATE; a map or pair outside the run: SGTD_ERR_INVALID; more than
+ * capacity: SGTD_ERR_CAPACITY (*n = the size needed, the first `capacity` entries written).  Any array may be NULL.
+ * sgtd_result_voxel_map: the voxels of one map in their numbering: coord = q, n_points, mean, cov row-major.
+ * sgtd_result_voxel_matches: voxel[i * mode + o] of one pair under its final pose.
+ * sgtd_voxel_register_stage_ms: covariances, map build, correspondence passes, everything else and the whole call on
+ * the device (zeros unless sgtd_set_timing is on; the events serialise the call). */
+#define SGTD_VREG_SUM_W 64
+#define SGTD_VREG_MAX_MAPS 65535
+#define SGTD_VREG_MAX_MEMBER_POINTS (1 << 25)
+#define SGTD_VREG_MAX_CORR (1 << 26)
+typedef struct sgtd_voxel_register_options {
+  double voxel_resolution;       /* 1.0 (fast_vgicp_impl.hpp:22); finite and > 0 */
+  int32_t neighbor_mode;         /* 1 (DIRECT1, :23); 1, 7 or 27 */
+  int32_t k_neighbors;           /* the rest: as in sgtd_register_options, the same defaults and ranges */
+  int32_t max_iterations;
+  int32_t lm_max_trials;
+  double lm_init_lambda_factor;
+  double rotation_eps;
+  double translation_eps;
+  double plane_eps;
+  int64_t reserved;              /* 0 */
+} sgtd_voxel_register_options;
+void sgtd_default_voxel_register_options(sgtd_voxel_register_options *o);
+int sgtd_register_voxels(sgtd_handle h, const sgtd_voxel_register_options *opt /* NULL = defaults */,
+                         const float *points, int stride_floats /* 3 or 4 */, const int64_t *pt_off /* host, n_clouds + 1 */, int n_clouds,
+                         const int32_t *map_off /* n_maps + 1 */, const int32_t *map_cloud, const double *map_pose /* [members*12], NULL = identity */,
+                         int n_maps, const int32_t *src_cloud, const int32_t *tgt_map, const double *init_pose /* [n_pairs*12], NULL = identity */,
+                         int n_pairs, int device_ptrs /* points only */);
+int sgtd_result_voxel_registered(sgtd_handle h, double *pose /*[n*12]*/, double *fitness, double *cost /*[n*2] first, last*/,
+                                 int32_t *n_matched, int32_t *n_corr, int32_t *iterations, int32_t *status);
+int sgtd_result_voxel_map(sgtd_handle h, int map, int32_t *coord /*[cap*3]*/, int32_t *n_points, double *mean /*[cap*3]*/, double *cov /*[cap*9]*/,
+                          int64_t capacity, int64_t *n);
+int sgtd_result_voxel_matches(sgtd_handle h, int pair, int32_t *voxel /*[n_src*mode]*/, int64_t capacity, int64_t *n);
+int sgtd_voxel_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total);
+
 /* Page-locked host memory for the destination buffers of the fetch calls (sgtd_fetch_entries,
  * sgtd_result_pairs, ...): a copy into it is one direct DMA transfer — pageable memory goes through the
  * runtime's staging at about a third of the rate.  Allocation is slow (milliseconds): keep the buffers

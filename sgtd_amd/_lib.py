@@ -45,6 +45,8 @@ SYMBOLS = [
     "sgtd_local_map_device_view", "sgtd_local_map_stage_ms",
     "sgtd_default_register_options", "sgtd_register_clouds", "sgtd_result_registered", "sgtd_result_register_covariances",
     "sgtd_result_register_matches", "sgtd_register_stage_ms", "sgtd_register_tiles",
+    "sgtd_default_voxel_register_options", "sgtd_register_voxels", "sgtd_result_voxel_registered", "sgtd_result_voxel_map",
+    "sgtd_result_voxel_matches", "sgtd_voxel_register_stage_ms",
 ]
 
 
@@ -132,6 +134,13 @@ class RegisterOptions(C.Structure):
     _fields_ = [("k_neighbors", C.c_int32), ("max_iterations", C.c_int32), ("lm_max_trials", C.c_int32), ("reserved", C.c_int32),
                 ("max_corr_dist", C.c_double), ("lm_init_lambda_factor", C.c_double), ("rotation_eps", C.c_double),
                 ("translation_eps", C.c_double), ("plane_eps", C.c_double)]
+
+
+class VoxelRegisterOptions(C.Structure):
+    """sgtd_voxel_register_options"""
+    _fields_ = [("voxel_resolution", C.c_double), ("neighbor_mode", C.c_int32), ("k_neighbors", C.c_int32), ("max_iterations", C.c_int32),
+                ("lm_max_trials", C.c_int32), ("lm_init_lambda_factor", C.c_double), ("rotation_eps", C.c_double),
+                ("translation_eps", C.c_double), ("plane_eps", C.c_double), ("reserved", C.c_int64)]
 
 
 def build_library(force=False):
@@ -252,6 +261,13 @@ def lib():
     L.sgtd_register_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.sgtd_register_tiles.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.sgtd_register_tiles.restype = None
+    L.sgtd_default_voxel_register_options.argtypes = [C.POINTER(VoxelRegisterOptions)]
+    L.sgtd_default_voxel_register_options.restype = None
+    L.sgtd_register_voxels.argtypes = [vp, C.POINTER(VoxelRegisterOptions), vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int]
+    L.sgtd_result_voxel_registered.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgtd_result_voxel_map.argtypes = [vp, C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_voxel_matches.argtypes = [vp, C.c_int, vp, i64, C.POINTER(i64)]
+    L.sgtd_voxel_register_stage_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 5
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

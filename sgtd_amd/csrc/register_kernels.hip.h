@@ -346,6 +346,56 @@ __device__ inline void reg_next_trial(RegState &s, const RegParams &P) {
   }
 }
 
+// lane 0 behind a linearisation whose H, b and y0 are in s: the iteration is counted; "no correspondence", or the first
+// trial's solve (lambda from H on the pair's first linearisation)
+__device__ inline void reg_linearised(RegState &s, const RegParams &P, bool none) {
+  s.iters = s.iters + 1;
+  if (s.iters == 1) s.cost_first = s.y0;
+  s.cost_last = s.y0;
+  if (none) {
+    reg_end(s, P, REG_NO_CORRESPONDENCE);
+    return;
+  }
+  if (s.iters == 1) {
+    double m = 0.0;
+    for (int a = 0; a < 6; a++) {
+      const double v = fabs(s.H[a * (a + 1) / 2 + a]);
+      m = v > m ? v : m;
+    }
+    s.lambda = P.o.lambda_factor * m;
+  }
+  s.nu = 2.0;
+  s.trials = 0;
+  reg_next_trial(s, P);
+}
+
+// lane 0 behind a trial whose cost is yi: the trial is accepted, rejected (and the next one solved for) or ends the solve
+__device__ inline void reg_tried(RegState &s, const RegParams &P, double yi) {
+  double den = s.d[0] * (s.lambda * s.d[0] - s.b[0]);
+  for (int a = 1; a < 6; a++) den = den + s.d[a] * (s.lambda * s.d[a] - s.b[a]);
+  const double rho = (s.y0 - yi) / den;
+  bool ended = false;
+  if (!(rho >= 0.0)) {
+    if (s.conv) ended = true;
+    else {
+      s.lambda = s.nu * s.lambda;
+      s.nu = 2.0 * s.nu;
+      reg_next_trial(s, P);
+    }
+  } else {
+    for (int a = 0; a < 9; a++) s.R[a] = s.Rt[a];
+    for (int a = 0; a < 3; a++) s.t[a] = s.tt[a];
+    const double f = 2.0 * rho - 1.0, g = 1.0 - (f * f) * f, third = 1.0 / 3.0;
+    s.lambda = s.lambda * (g > third ? g : third);
+    ended = true;
+  }
+  if (ended) {
+    if (s.conv) reg_end(s, P, REG_CONVERGED);
+    else if (s.iters >= P.o.max_iterations) reg_end(s, P, REG_ITERATION_LIMIT);
+    else s.phase = REG_PHASE_LIN;
+  }
+}
+
 // one matched point's e = w_j - x_i under (R, t) and y = M_i e
 __device__ __forceinline__ void reg_residual(const RegParams &P, const double *R, const double *t, long long sbase, long long tbase, int i, int j,
                                              size_t g, double *x, double *M, double *y, double *cost) {
@@ -413,24 +463,7 @@ __global__ __launch_bounds__(SGTD_REG_W) void reg_lin_kernel(RegParams P) {
 #pragma unroll
   for (int a = 0; a < 6; a++) s.b[a] = acc[(21 + a) / 6][(21 + a) % 6];
   s.y0 = acc[27 / 6][27 % 6];
-  s.iters = s.iters + 1;
-  if (s.iters == 1) s.cost_first = s.y0;
-  s.cost_last = s.y0;
-  if (acc[28 / 6][28 % 6] == 0.0) {
-    reg_end(s, P, REG_NO_CORRESPONDENCE);
-  } else {
-    if (s.iters == 1) {
-      double m = 0.0;
-      for (int a = 0; a < 6; a++) {
-        const double v = fabs(s.H[a * (a + 1) / 2 + a]);
-        m = v > m ? v : m;
-      }
-      s.lambda = P.o.lambda_factor * m;
-    }
-    s.nu = 2.0;
-    s.trials = 0;
-    reg_next_trial(s, P);
-  }
+  reg_linearised(s, P, acc[28 / 6][28 % 6] == 0.0);
   *st = s;
 }
 
@@ -457,30 +490,7 @@ __global__ __launch_bounds__(SGTD_REG_W) void reg_trial_kernel(RegParams P) {
   refine_tree<1>(acc, red, bc);
   if (threadIdx.x != 0) return;
   RegState s = *st;
-  const double yi = acc[0];
-  double den = s.d[0] * (s.lambda * s.d[0] - s.b[0]);
-  for (int a = 1; a < 6; a++) den = den + s.d[a] * (s.lambda * s.d[a] - s.b[a]);
-  const double rho = (s.y0 - yi) / den;
-  bool ended = false;
-  if (!(rho >= 0.0)) {
-    if (s.conv) ended = true;
-    else {
-      s.lambda = s.nu * s.lambda;
-      s.nu = 2.0 * s.nu;
-      reg_next_trial(s, P);
-    }
-  } else {
-    for (int a = 0; a < 9; a++) s.R[a] = s.Rt[a];
-    for (int a = 0; a < 3; a++) s.t[a] = s.tt[a];
-    const double f = 2.0 * rho - 1.0, g = 1.0 - (f * f) * f, third = 1.0 / 3.0;
-    s.lambda = s.lambda * (g > third ? g : third);
-    ended = true;
-  }
-  if (ended) {
-    if (s.conv) reg_end(s, P, REG_CONVERGED);
-    else if (s.iters >= P.o.max_iterations) reg_end(s, P, REG_ITERATION_LIMIT);
-    else s.phase = REG_PHASE_LIN;
-  }
+  reg_tried(s, P, acc[0]);
   *st = s;
 }
 

@@ -34,6 +34,7 @@
 #include "consistency_kernels.hip.h"
 #include "relax_kernels.hip.h"
 #include "register_kernels.hip.h"
+#include "voxel_register_kernels.hip.h"
 #include "consensus_kernels.hip.h"
 #include "scan_kernels.hip.h"
 #include "local_map_kernels.hip.h"
@@ -340,6 +341,21 @@ struct sgtd_engine {
   std::vector<int> rg_host_up;           // (the source of the index upload)
   hipEvent_t rg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float rg_ms[4] = {0.f, 0.f, 0.f, 0.f};
+  // sgtd_register_voxels (voxel_register_kernels.hip.h): independent of the batch and of sgtd_register_clouds' buffers.
+  // VR_IN: the call's index arrays, offsets and poses; VR_PTS: the points when the host gave them; VR_COV: a covariance per
+  // point; VR_KEY_* / VR_VAL_*: the sort's pairs; VR_FLAGS .. VR_MAP_VOX: the voxels' heads, keys, first points and the
+  // maps' ranges; VR_MEAN / VR_VCOV: the Gaussians; VR_VID / VR_MW: the per-correspondence streams; VR_STATE, VR_OUT,
+  // VR_CTL as rg_*.  vr_n < 0: no results; vr_host_*: what the getters need of the call; vr_ms: covariances, map build,
+  // correspondence passes, the rest, the whole call (filled under sgtd_set_timing)
+  enum { VR_IN = 0, VR_PTS, VR_COV, VR_KEY_A, VR_KEY_B, VR_VAL_A, VR_VAL_B, VR_FLAGS, VR_EXCL, VR_COUNTS, VR_VKEY, VR_VSTART, VR_MAP_VOX, VR_MEAN, VR_VCOV,
+         VR_VID, VR_MW, VR_STATE, VR_OUT, VR_CTL, VR_BUFS };
+  DevBuf vr[VR_BUFS];
+  int vr_n = -1, vr_mode = 1;
+  std::vector<int> vr_host_soff;         // src_off [n + 1]
+  std::vector<u32> vr_host_map_vox;      // [n_maps + 1]
+  std::vector<int> vr_host_up;           // (the source of the index upload)
+  hipEvent_t vr_ev[3] = {nullptr, nullptr, nullptr};
+  float vr_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (SK_*: scan_run).  sk_n < 0:
   // no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets on the host
   enum { SK_PTS = 0, SK_LAB, SK_OFF, SK_SC, SK_R, SK_PITCH, SK_AZI, SK_MM, SK_VOTE, SK_GRID, SK_RANGE, SK_BOUNDS, SK_KEY_A, SK_KEY_B, SK_VAL_A, SK_VAL_B,
@@ -2259,6 +2275,9 @@ int sgtd_destroy(sgtd_handle e) {
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->rg_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (DevBuf &b : e->vr) free_buf(b);
+  for (hipEvent_t ev : e->vr_ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
@@ -5230,6 +5249,389 @@ int sgtd_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float
   if (ms_search) *ms_search = c->rg_ms[1];
   if (ms_rest) *ms_rest = c->rg_ms[2];
   if (ms_total) *ms_total = c->rg_ms[3];
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_register_voxels: voxelised GICP against voxel maps (voxel_register_kernels.hip.h) ----
+namespace {
+static_assert(SGTD_VREG_W == SGTD_VREG_SUM_W, "the voxel kernels' sizes are the header's");
+
+int vreg_bits(u64 v) { int b = 0; while (v) { b++; v >>= 1; } return std::max(b, 1); }
+
+struct VregOut {      // VR_OUT: RegOut's rows, then n_corr [n] in i32
+  RegOut r;
+  explicit VregOut(size_t n) : r(n) {}
+  size_t bytes() const { return r.bytes() + r.n * sizeof(int); }
+  int *corr(void *p) const { return r.status(p) + r.n; }
+};
+
+int vreg_lap(sgtd_engine *e, int kind) {
+  HIPCHK(hipEventRecord(e->vr_ev[1], e->stream));
+  HIPCHK(hipEventSynchronize(e->vr_ev[1]));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, e->vr_ev[0], e->vr_ev[1]));
+  e->vr_ms[kind] += t;
+  HIPCHK(hipEventRecord(e->vr_ev[0], e->stream));
+  return SGTD_OK;
+}
+
+int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
+             const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src, const int32_t *tgt,
+             const double *init, int n) {
+  sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
+  HIPCHK(hipSetDevice(c->cfg.device_id));
+  const bool timed = c->timing;
+  for (float &v : c->vr_ms) v = 0.f;
+  if (timed)
+    for (hipEvent_t &ev : c->vr_ev)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+  const size_t total = (size_t)pt_off[n_clouds];
+  const int mode = o.neighbor_mode, n_members = n_maps ? map_off[n_maps] : 0;
+  c->vr_mode = mode;
+  // the members' points back to back, the tiles: of the pairs' sources, of the clouds that are a source or a member
+  std::vector<unsigned char> named((size_t)n_clouds, 0);
+  std::vector<int> mem_map((size_t)n_members), mem_pt_off((size_t)n_members + 1, 0), tile_pair, tile_first, ctile_cloud, ctile_first;
+  for (int m = 0; m < n_maps; m++)
+    for (int j = map_off[m]; j < map_off[m + 1]; j++) {
+      mem_map[(size_t)j] = m;
+      named[(size_t)map_cloud[j]] = 1;
+      mem_pt_off[(size_t)j + 1] = mem_pt_off[(size_t)j] + (int)(pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]]);
+    }
+  const long long MP = mem_pt_off[(size_t)n_members];
+  std::vector<int> &soff = c->vr_host_soff;
+  soff.assign((size_t)n + 1, 0);
+  for (int k = 0; k < n; k++) {
+    named[(size_t)src[k]] = 1;
+    const int ns = (int)(pt_off[src[k] + 1] - pt_off[src[k]]);
+    soff[(size_t)k + 1] = soff[(size_t)k] + ns;
+    for (int f = 0; f < ns; f += SGTD_REG_THREADS) { tile_pair.push_back(k); tile_first.push_back(f); }
+  }
+  for (int cl = 0; cl < n_clouds; cl++) {
+    if (!named[(size_t)cl]) continue;
+    const int np = (int)(pt_off[cl + 1] - pt_off[cl]);
+    for (int f = 0; f < np; f += SGTD_REG_THREADS) { ctile_cloud.push_back(cl); ctile_first.push_back(f); }
+  }
+  const int total_src = soff[(size_t)n], n_tiles = (int)tile_pair.size(), n_ctiles = (int)ctile_cloud.size();
+
+  // the index upload: src, tgt_map, src_off, map_off, map_cloud, mem_map, mem_pt_off, the tiles
+  std::vector<int> &up = c->vr_host_up;
+  up.clear();
+  auto put = [&](const int *p, size_t cnt) { const size_t at = up.size(); up.insert(up.end(), p, p + cnt); return at; };
+  const size_t u_src = put(src, (size_t)n), u_tgt = put(tgt, (size_t)n), u_soff = put(soff.data(), soff.size());
+  const size_t u_moff = n_maps ? put(map_off, (size_t)n_maps + 1) : up.size(), u_mcl = put(map_cloud, (size_t)n_members);
+  const size_t u_mmap = put(mem_map.data(), mem_map.size()), u_mpo = put(mem_pt_off.data(), mem_pt_off.size());
+  const size_t u_tp = put(tile_pair.data(), tile_pair.size()), u_tf = put(tile_first.data(), tile_first.size());
+  const size_t u_cc = put(ctile_cloud.data(), ctile_cloud.size()), u_cf = put(ctile_first.data(), ctile_first.size());
+  const size_t o_off = 0, o_init = o_off + relax_up((size_t)(n_clouds + 1) * sizeof(int64_t)), o_pose = o_init + relax_up((size_t)n * 12 * sizeof(double)),
+               o_idx = o_pose + relax_up((size_t)n_members * 12 * sizeof(double)), in_bytes = o_idx + relax_up(up.size() * sizeof(int));
+  const size_t ts = (size_t)std::max(total_src, 1), mp = (size_t)std::max<long long>(MP, 1), nn = (size_t)std::max(n, 1);
+  const VregOut out((size_t)n);
+  auto *B = c->vr;
+  auto buf = [&](int which, size_t bytes) { return ensure(c, B[which], std::max<size_t>(bytes, 16)); };
+  CHK(buf(sgtd_engine::VR_IN, in_bytes));
+  CHK(buf(sgtd_engine::VR_COV, std::max<size_t>(total, 1) * 9 * sizeof(double)));
+  CHK(buf(sgtd_engine::VR_KEY_A, mp * sizeof(u64)));
+  CHK(buf(sgtd_engine::VR_KEY_B, mp * sizeof(u64)));
+  CHK(buf(sgtd_engine::VR_VAL_A, mp * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_VAL_B, mp * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_FLAGS, (mp + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_EXCL, (mp + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_COUNTS, 4 * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_VKEY, mp * sizeof(u64)));
+  CHK(buf(sgtd_engine::VR_VSTART, (mp + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_MAP_VOX, ((size_t)n_maps + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::VR_VID, ts * mode * sizeof(int)));
+  CHK(buf(sgtd_engine::VR_MW, ts * mode * 9 * sizeof(double)));
+  CHK(buf(sgtd_engine::VR_STATE, nn * sizeof(RegState)));
+  CHK(buf(sgtd_engine::VR_OUT, out.bytes()));
+  CHK(buf(sgtd_engine::VR_CTL, 64));
+  char *in = B[sgtd_engine::VR_IN].as<char>();
+  CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
+  if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
+  if (map_pose) CHK(h2d(c, in + o_pose, map_pose, (size_t)n_members * 12 * sizeof(double)));
+  CHK(h2d(c, in + o_idx, up.data(), up.size() * sizeof(int)));
+
+  RegParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.pts = points; P.stride = stride;
+  P.pt_off = reinterpret_cast<const long long *>(in + o_off);
+  const int *di = reinterpret_cast<const int *>(in + o_idx);
+  P.src = di + u_src; P.src_off = di + u_soff;
+  P.tile_pair = di + u_tp; P.tile_first = di + u_tf; P.ctile_cloud = di + u_cc; P.ctile_first = di + u_cf;
+  P.n_pairs = n; P.n_tiles = n_tiles; P.n_ctiles = n_ctiles; P.total_src = (int)ts;
+  P.cov = B[sgtd_engine::VR_COV].as<double>();
+  P.st = B[sgtd_engine::VR_STATE].as<RegState>();
+  P.unfinished = B[sgtd_engine::VR_CTL].as<int>();
+  void *ob = B[sgtd_engine::VR_OUT].p;
+  P.out_pose = out.r.pose(ob); P.out_fitness = out.r.fitness(ob); P.out_cost = out.r.cost(ob);
+  P.out_matched = out.r.matched(ob); P.out_iters = out.r.iters(ob); P.out_status = out.r.status(ob);
+  P.o.k = o.k_neighbors; P.o.max_iterations = o.max_iterations; P.o.lm_max_trials = o.lm_max_trials;
+  P.o.max2 = std::numeric_limits<double>::infinity(); P.o.lambda_factor = o.lm_init_lambda_factor;
+  P.o.rotation_eps = o.rotation_eps; P.o.translation_eps = o.translation_eps; P.o.plane_eps = o.plane_eps;
+  VregParams V;
+  std::memset(&V, 0, sizeof(V));
+  V.map_off = di + u_moff; V.map_cloud = di + u_mcl; V.mem_map = di + u_mmap; V.mem_pt_off = di + u_mpo;
+  V.map_pose = map_pose ? reinterpret_cast<const double *>(in + o_pose) : nullptr;
+  V.tgt_map = di + u_tgt;
+  V.n_maps = n_maps; V.n_members = n_members; V.n_member_pts = (int)MP; V.mode = mode; V.res = o.voxel_resolution;
+  V.map_vox = B[sgtd_engine::VR_MAP_VOX].as<u32>();
+  V.vid = B[sgtd_engine::VR_VID].as<int>(); V.Mw = B[sgtd_engine::VR_MW].as<double>();
+  V.out_corr = out.corr(ob);
+
+  hipStream_t s = c->stream;
+  if (timed) { HIPCHK(hipEventRecord(c->vr_ev[2], s)); HIPCHK(hipEventRecord(c->vr_ev[0], s)); }
+  if (n_ctiles) reg_cov_kernel<<<n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
+  HIPCHK(hipGetLastError());
+  if (timed) CHK(vreg_lap(c, 0));
+
+  // the maps: keys, the stable sort, the voxels' heads, the Gaussians, the maps' ranges
+  u32 n_vox = 0;
+  if (MP > 0) {
+    u64 *kin = B[sgtd_engine::VR_KEY_A].as<u64>(), *kout = B[sgtd_engine::VR_KEY_B].as<u64>();
+    u32 *vin = B[sgtd_engine::VR_VAL_A].as<u32>(), *vout = B[sgtd_engine::VR_VAL_B].as<u32>();
+    u32 *flags = B[sgtd_engine::VR_FLAGS].as<u32>(), *excl = B[sgtd_engine::VR_EXCL].as<u32>(), *counts = B[sgtd_engine::VR_COUNTS].as<u32>();
+    u64 *vkey = B[sgtd_engine::VR_VKEY].as<u64>();
+    u32 *vstart = B[sgtd_engine::VR_VSTART].as<u32>();
+    const int gp = grid_for(MP, 256);
+    vreg_keys_kernel<<<gp, 256, 0, s>>>(P, V, kin, vin);
+    HIPCHK(hipGetLastError());
+    CHK(radix_sort_pairs<u64>(c, kin, kout, vin, vout, MP, 48 + vreg_bits((u64)n_maps), true));
+    HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(u32), s));
+    scan_heads_kernel<<<grid_for(MP + 1, 256), 256, 0, s>>>(kin, MP, (u64)n_maps << 48, flags, counts);
+    HIPCHK(hipGetLastError());
+    CHK(device_scan(c, flags, excl, MP + 1));
+    scan_voxels_kernel<<<gp, 256, 0, s>>>(kin, flags, excl, MP, counts, vkey, vstart);
+    HIPCHK(hipGetLastError());
+    CHK(d2h(c, &n_vox, excl + MP, sizeof(u32)));
+    CHK(xfer_sync(c));
+    V.vkey = vkey; V.vstart = vstart; V.order = vin; V.n_vox = n_vox;
+    const size_t nv = std::max<size_t>(n_vox, 1);
+    CHK(buf(sgtd_engine::VR_MEAN, nv * 3 * sizeof(double)));
+    CHK(buf(sgtd_engine::VR_VCOV, nv * 9 * sizeof(double)));
+    V.vmean = B[sgtd_engine::VR_MEAN].as<double>(); V.vcov = B[sgtd_engine::VR_VCOV].as<double>();
+    if (n_vox) vreg_voxel_kernel<<<grid_for(n_vox, 4), 256, 0, s>>>(P, V);
+  }
+  vreg_ranges_kernel<<<grid_for(n_maps + 1, 256), 256, 0, s>>>(V);
+  HIPCHK(hipGetLastError());
+  c->vr_host_map_vox.assign((size_t)n_maps + 1, 0);
+  CHK(d2h(c, c->vr_host_map_vox.data(), V.map_vox, ((size_t)n_maps + 1) * sizeof(u32)));
+  CHK(xfer_sync(c));
+  if (timed) CHK(vreg_lap(c, 1));
+  if (n == 0) {
+    if (timed) HIPCHK(hipEventElapsedTime(&c->vr_ms[4], c->vr_ev[2], c->vr_ev[1]));
+    return SGTD_OK;
+  }
+
+  const std::vector<u32> &mv = c->vr_host_map_vox;
+  int unfinished = 0;
+  for (int k = 0; k < n; k++)
+    if (soff[(size_t)k + 1] > soff[(size_t)k] && mv[(size_t)tgt[k] + 1] > mv[(size_t)tgt[k]]) unfinished++;
+  CHK(h2d(c, P.unfinished, &unfinished, sizeof(int)));
+  vreg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, V, init ? reinterpret_cast<const double *>(in + o_init) : nullptr);
+  HIPCHK(hipGetLastError());
+  // rounds in groups, as sgtd_register_clouds' host loop: every round is one trial of every unfinished pair
+  const long long bound = (long long)o.max_iterations * o.lm_max_trials;
+  long long sent = 0;
+  while (unfinished > 0) {
+    if (sent >= bound) { c->err = "sgtd_register_voxels: the solves did not end within their limits"; return SGTD_ERR_HIP; }
+    const int group = (int)std::min<long long>(SGTD_REG_GROUP, bound - sent);
+    for (int g = 0; g < group; g++) {
+      if (timed) CHK(vreg_lap(c, 3));
+      vreg_corr_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, V, 0);
+      if (timed) CHK(vreg_lap(c, 2));
+      vreg_lin_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
+      vreg_trial_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
+      HIPCHK(hipGetLastError());
+    }
+    sent += group;
+    CHK(d2h(c, &unfinished, P.unfinished, sizeof(int)));
+    CHK(xfer_sync(c));
+  }
+  if (timed) CHK(vreg_lap(c, 3));
+  if (n_tiles) {
+    vreg_corr_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, V, 1);
+    if (timed) CHK(vreg_lap(c, 2));
+  }
+  vreg_final_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
+  HIPCHK(hipGetLastError());
+  if (timed) {
+    CHK(vreg_lap(c, 3));
+    HIPCHK(hipEventElapsedTime(&c->vr_ms[4], c->vr_ev[2], c->vr_ev[1]));
+  }
+  CHK(xfer_sync(c));
+  return SGTD_OK;
+}
+
+int vreg_ready(sgtd_engine *e, sgtd_engine **out) {
+  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
+  if (c->vr_n < 0) { e->err = "no voxel registration: sgtd_register_voxels has not run"; return SGTD_ERR_STATE; }
+  *out = c;
+  return SGTD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void sgtd_default_voxel_register_options(sgtd_voxel_register_options *o) {
+  if (!o) return;
+  o->voxel_resolution = 1.0; o->neighbor_mode = 1;
+  o->k_neighbors = 20; o->max_iterations = 64; o->lm_max_trials = 10;
+  o->lm_init_lambda_factor = 1e-9; o->rotation_eps = 2e-3; o->translation_eps = 5e-4; o->plane_eps = 1e-3;
+  o->reserved = 0;
+}
+
+int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
+                         const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src_cloud,
+                         const int32_t *tgt_map, const double *init_pose, int n_pairs, int device_ptrs) {
+  if (!e || n_clouds < 0 || n_pairs < 0 || n_maps < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (n_pairs > 0 && (!src_cloud || !tgt_map)) return SGTD_ERR_INVALID;
+  if (n_maps > 0 && !map_off) return SGTD_ERR_INVALID;
+  sgtd_voxel_register_options o;
+  sgtd_default_voxel_register_options(&o);
+  if (opt) o = *opt;
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (o.k_neighbors < 3 || o.k_neighbors > SGTD_REG_MAX_K || o.max_iterations < 1 || o.lm_max_trials < 1 || o.reserved != 0 || !pos(o.voxel_resolution) ||
+      (o.neighbor_mode != 1 && o.neighbor_mode != 7 && o.neighbor_mode != 27) || !pos(o.lm_init_lambda_factor) || !pos(o.rotation_eps) ||
+      !pos(o.translation_eps) || !pos(o.plane_eps))
+    return SGTD_ERR_INVALID;
+  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
+  for (int cl = 0; cl < n_clouds; cl++)
+    if (pt_off[cl + 1] < pt_off[cl]) return SGTD_ERR_INVALID;
+  const int64_t total = pt_off[n_clouds];
+  if (total > 0 && !points) return SGTD_ERR_INVALID;
+  if (n_maps > 0 && map_off[0] != 0) return SGTD_ERR_INVALID;
+  for (int m = 0; m < n_maps; m++)
+    if (map_off[m + 1] < map_off[m]) return SGTD_ERR_INVALID;
+  const int n_members = n_maps ? map_off[n_maps] : 0;
+  if (n_members > 0 && !map_cloud) return SGTD_ERR_INVALID;
+  int64_t total_src = 0, max_cloud = 0, member_pts = 0;
+  for (int j = 0; j < n_members; j++) {
+    if (map_cloud[j] < 0 || map_cloud[j] >= n_clouds) return SGTD_ERR_INVALID;
+    member_pts += pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]];
+  }
+  for (int k = 0; k < n_pairs; k++) {
+    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || tgt_map[k] < 0 || tgt_map[k] >= n_maps) return SGTD_ERR_INVALID;
+    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
+  }
+  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
+  if (map_pose && !relax_finite(map_pose, (size_t)n_members * 12)) return SGTD_ERR_INVALID;
+  for (int cl = 0; cl < n_clouds; cl++) max_cloud = std::max(max_cloud, pt_off[cl + 1] - pt_off[cl]);
+  if (max_cloud > SGTD_REG_MAX_POINTS || n_clouds > SGTD_REG_MAX_CLOUDS || total > SGTD_REG_MAX_TOTAL_POINTS || n_pairs > SGTD_REG_MAX_PAIRS) {
+    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_REG_MAX_POINTS) + " points a cloud, " + std::to_string(SGTD_REG_MAX_CLOUDS) +
+             " clouds, " + std::to_string(SGTD_REG_MAX_TOTAL_POINTS) + " points in all and " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (n_maps > SGTD_VREG_MAX_MAPS) {
+    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_VREG_MAX_MAPS) + " maps (SGTD_VREG_MAX_MAPS)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (member_pts > SGTD_VREG_MAX_MEMBER_POINTS) {
+    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_VREG_MAX_MEMBER_POINTS) + " member points over the maps (SGTD_VREG_MAX_MEMBER_POINTS)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (total_src * o.neighbor_mode > SGTD_VREG_MAX_CORR) {
+    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_VREG_MAX_CORR) +
+             " for the source points over the pairs times neighbor_mode (SGTD_VREG_MAX_CORR)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
+  PinScope pin_scope(c);
+  c->vr_n = -1;
+  const float *d_pts = points;
+  int rc = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (rc == SGTD_OK && !device_ptrs && total > 0) {
+    const size_t bytes = (size_t)total * stride_floats * sizeof(float);
+    rc = ensure(c, c->vr[sgtd_engine::VR_PTS], bytes);
+    if (rc == SGTD_OK) rc = h2d(c, c->vr[sgtd_engine::VR_PTS].p, points, bytes);
+    d_pts = c->vr[sgtd_engine::VR_PTS].as<float>();
+  }
+  if (rc == SGTD_OK)
+    rc = vreg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
+  if (rc != SGTD_OK) {
+    if (c != e) e->err = c->err;
+    return rc;
+  }
+  c->vr_n = n_pairs;
+  return SGTD_OK;
+}
+
+int sgtd_result_voxel_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *n_corr, int32_t *iterations,
+                                 int32_t *status) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(vreg_ready(e, &c));
+  const size_t n = (size_t)c->vr_n;
+  if (n == 0) return SGTD_OK;
+  const VregOut out(n);
+  void *ob = c->vr[sgtd_engine::VR_OUT].p;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && pose) st = d2h(c, pose, out.r.pose(ob), n * 12 * sizeof(double));
+  if (st == SGTD_OK && fitness) st = d2h(c, fitness, out.r.fitness(ob), n * sizeof(double));
+  if (st == SGTD_OK && cost) st = d2h(c, cost, out.r.cost(ob), n * 2 * sizeof(double));
+  if (st == SGTD_OK && n_matched) st = d2h(c, n_matched, out.r.matched(ob), n * sizeof(int));
+  if (st == SGTD_OK && n_corr) st = d2h(c, n_corr, out.corr(ob), n * sizeof(int));
+  if (st == SGTD_OK && iterations) st = d2h(c, iterations, out.r.iters(ob), n * sizeof(int));
+  if (st == SGTD_OK && status) st = d2h(c, status, out.r.status(ob), n * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return SGTD_OK;
+}
+
+int sgtd_result_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(vreg_ready(e, &c));
+  if (map < 0 || (size_t)map + 1 >= c->vr_host_map_vox.size()) return SGTD_ERR_INVALID;
+  const int64_t first = c->vr_host_map_vox[(size_t)map], need = (int64_t)c->vr_host_map_vox[(size_t)map + 1] - first;
+  if (n) *n = need;
+  const bool any = coord || n_points || mean || cov;
+  const size_t m = any ? (size_t)std::min(need, capacity) : 0;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  std::vector<u64> keys(coord ? m : 0);
+  std::vector<u32> starts(n_points && m ? m + 1 : 0);
+  auto *B = c->vr;
+  if (st == SGTD_OK && m && coord) st = d2h(c, keys.data(), B[sgtd_engine::VR_VKEY].as<u64>() + first, m * sizeof(u64));
+  if (st == SGTD_OK && m && n_points) st = d2h(c, starts.data(), B[sgtd_engine::VR_VSTART].as<u32>() + first, (m + 1) * sizeof(u32));
+  if (st == SGTD_OK && m && mean) st = d2h(c, mean, B[sgtd_engine::VR_MEAN].as<double>() + (size_t)first * 3, m * 3 * sizeof(double));
+  if (st == SGTD_OK && m && cov) st = d2h(c, cov, B[sgtd_engine::VR_VCOV].as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  for (size_t v = 0; v < keys.size(); v++)
+    for (int a = 0; a < 3; a++) coord[v * 3 + a] = (int32_t)((keys[v] >> (32 - 16 * a)) & 0xFFFFu) - 32768;
+  for (size_t v = 0; v + 1 < starts.size(); v++) n_points[v] = (int32_t)(starts[v + 1] - starts[v]);
+  return need > capacity && any ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_voxel_matches(sgtd_handle e, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(vreg_ready(e, &c));
+  if (pair < 0 || pair >= c->vr_n) return SGTD_ERR_INVALID;
+  const int64_t first = (int64_t)c->vr_host_soff[(size_t)pair] * c->vr_mode;
+  const int64_t need = (int64_t)c->vr_host_soff[(size_t)pair + 1] * c->vr_mode - first;
+  if (n) *n = need;
+  const size_t m = voxel ? (size_t)std::min(need, capacity) : 0;
+  PinScope pin_scope(c);
+  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  if (st == SGTD_OK && m) st = d2h(c, voxel, c->vr[sgtd_engine::VR_VID].as<int>() + first, m * sizeof(int));
+  if (st == SGTD_OK) st = xfer_sync(c);
+  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  return need > capacity && voxel ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(vreg_ready(e, &c));
+  if (ms_cov) *ms_cov = c->vr_ms[0];
+  if (ms_map) *ms_map = c->vr_ms[1];
+  if (ms_corr) *ms_corr = c->vr_ms[2];
+  if (ms_rest) *ms_rest = c->vr_ms[3];
+  if (ms_total) *ms_total = c->vr_ms[4];
   return SGTD_OK;
 }
 

@@ -17,7 +17,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Config, DescSoa, LocalMapOptions, RegisterOptions, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats
+from ._lib import (Config, DescSoa, LocalMapOptions, RegisterOptions, RelaxOptions, RelaxReport, ScanConfig, SgtdError, Stats,
+                   VoxelRegisterOptions)
 
 DEFAULTS = dict(descriptor_near_num=10, candidate_num=50, max_frame_n=20000, device_id=0,
                 descriptor_min_len=0.5, descriptor_max_len=50.0, std_side_resolution=1.0,
@@ -1483,6 +1484,179 @@ class STDescManager:
         tgt = np.array([slot[int(x)] for x in f], np.int32)
         out = self.register_clouds(pts, off, q, tgt, init if len(q) else None, **options)
         out.update(query=q, cand=c, frame=f, init=init, src_cloud=q.copy(), tgt_cloud=tgt, points=pts, pt_off=off)
+        return out
+
+    # ---- voxelised registration against voxel maps (sgtd_register_voxels) -------------------------------------
+    def register_voxels(self, points, pt_off, map_off, map_cloud, map_pose, src, tgt_map, init=None, **options):
+        """sgtd_register_voxels: voxelised GICP of clouds against maps of Gaussian voxels on the device.  points, pt_off:
+        as register_clouds; map m has the members map_cloud[map_off[m]:map_off[m + 1]] (cloud indices), posed by map_pose
+        (members, 12) in the rel_pose layout (x = R p + t takes a member's point into the map's frame), None = the
+        identity; src, tgt_map: (n,) the pairs' source clouds and target maps; init: (n, 12) start poses, None = the
+        identity; options: fields of sgtd_voxel_register_options.  -> result_voxel_registered()"""
+        if hasattr(points, "data_ptr"):
+            assert points.is_cuda and points.is_contiguous()
+            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
+            self._keep = points
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            shape, pp, dev = points.shape, _p(points), 0
+        if len(shape) != 2 or shape[1] not in (3, 4):
+            raise ValueError("points: (total, 3 or 4)")
+        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+        if off.size < 1:
+            raise ValueError("pt_off: n_clouds + 1 offsets")
+        if off[-1] > shape[0]:
+            raise ValueError("pt_off names more points than were given")
+        moff = np.ascontiguousarray(np.asarray(map_off).reshape(-1), np.int32)
+        if moff.size < 1:
+            raise ValueError("map_off: n_maps + 1 offsets")
+        mcl = np.ascontiguousarray(map_cloud, np.int32).reshape(-1)
+        if moff[-1] > mcl.size:
+            raise ValueError("map_off names more members than were given")
+        mp = None
+        if map_pose is not None:
+            mp = np.ascontiguousarray(map_pose, np.float64).reshape(-1, 12)
+            if mp.shape[0] != mcl.size:
+                raise ValueError("map_pose: (members, 12), one pose per member")
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        t = np.ascontiguousarray(tgt_map, np.int32).reshape(-1)
+        n = s.size
+        if t.size != n:
+            raise ValueError("src and tgt_map: one cloud and one map index per pair")
+        p0 = None
+        if init is not None:
+            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
+            if p0.shape[0] != n:
+                raise ValueError("init: (n, 12), one start pose per pair")
+        opt = VoxelRegisterOptions()
+        self._L.sgtd_default_voxel_register_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(VoxelRegisterOptions._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        self._check(self._L.sgtd_register_voxels(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(moff), _p(mcl), _p(mp),
+                                                 moff.size - 1, _p(s), _p(t), _p(p0), n, dev))
+        self._vreg_n = n
+        return self.result_voxel_registered()
+
+    def result_voxel_registered(self):
+        """-> dict of pose [n, 12], fitness [n], cost [n, 2] (first and last linearisation), n_matched, n_corr, iterations,
+        status [n] (int32) of the last register_voxels call"""
+        n = self._vreg_n
+        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
+               "n_matched": np.zeros(n, np.int32), "n_corr": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32),
+               "status": np.zeros(n, np.int32)}
+        self._check(self._L.sgtd_result_voxel_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
+                                                         _p(out["n_corr"]), _p(out["iterations"]), _p(out["status"])))
+        return out
+
+    def voxel_map(self, m):
+        """the voxels of map m of the last register_voxels call, in their numbering -> dict of coord (v, 3) int32,
+        n_points (v,) int32, mean (v, 3), cov (v, 3, 3) f64"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_voxel_map(self._h, int(m), None, None, None, None, 0, C.byref(n)))
+        v = n.value
+        out = {"coord": np.zeros((v, 3), np.int32), "n_points": np.zeros(v, np.int32), "mean": np.zeros((v, 3), np.float64),
+               "cov": np.zeros((v, 3, 3), np.float64)}
+        self._check(self._L.sgtd_result_voxel_map(self._h, int(m), _p(out["coord"]), _p(out["n_points"]), _p(out["mean"]), _p(out["cov"]), v,
+                                                  C.byref(n)))
+        return out
+
+    def voxel_matches(self, pair):
+        """the correspondences of one pair under its final pose: (n_src, mode) int32, the voxel's index within the map per
+        offset, -1 where there is none"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_voxel_matches(self._h, int(pair), None, 0, C.byref(n)))
+        v = np.zeros(n.value, np.int32)
+        self._check(self._L.sgtd_result_voxel_matches(self._h, int(pair), _p(v), n.value, C.byref(n)))
+        return v
+
+    def voxel_register_stage_ms(self):
+        """device milliseconds of the last register_voxels call: covariances, map build, correspondence passes, the rest,
+        the whole call (zeros unless set_timing(True))"""
+        v = [C.c_float(0) for _ in range(5)]
+        self._check(self._L.sgtd_voxel_register_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @staticmethod
+    def voxel_map_members(frame, frame_poses, has_cloud, radius=15.0, max_members=0):
+        """the members of the local map around `frame`: the frames that have a cloud and a pose whose position lies within
+        `radius` of the frame's, the frame itself first, then in ascending frame id, the first max_members of them (0 = no
+        cap).  frame_poses: a dict or sequence by frame id of 12 doubles (rot row-major, t: the frame in the world);
+        has_cloud(id) -> bool.  -> (members [k] int32, rel [k, 12] f64: T_frame^-1 T_member, composed in f64)"""
+        ids = sorted(frame_poses.keys()) if isinstance(frame_poses, dict) else range(len(frame_poses))
+        pose = lambda f: np.asarray(frame_poses[f], np.float64).reshape(12)
+        Rf, tf = pose(frame)[:9].reshape(3, 3), pose(frame)[9:]
+        members = [int(frame)]
+        for f in ids:
+            if int(f) == int(frame) or frame_poses[f] is None or not has_cloud(int(f)):
+                continue
+            d = pose(f)[9:] - tf
+            if float(d @ d) <= float(radius) * float(radius):
+                members.append(int(f))
+        if max_members:
+            members = members[:int(max_members)]
+        rel = np.zeros((len(members), 12), np.float64)
+        for k, f in enumerate(members):
+            Rm, tm = pose(f)[:9].reshape(3, 3), pose(f)[9:]
+            rel[k, :9] = (Rf.T @ Rm).reshape(9)
+            rel[k, 9:] = Rf.T @ (tm - tf)
+        return np.array(members, np.int32), rel
+
+    def register_loops_local(self, query_points, query_pt_off, map_clouds, frame_poses, radius=15.0, max_members=0, max_per_query=5,
+                             start="verify", **options):
+        """register_loops against local maps: for register_pairs' (query, frame) pairs the target is the voxel map of the
+        candidate frame's local map (voxel_map_members: the frames with a cloud within `radius` of the candidate's
+        position, the candidate first, each posed by T_frame^-1 T_member), one map per distinct candidate frame shared
+        among the queries, in ONE register_voxels call.  frame_poses: by frame id, 12 doubles (rot row-major, t); a
+        candidate without a cloud or a pose is skipped.  -> what register_loops returns (register_voxels' fields per
+        pair) plus tgt_map [m], map_frames (the maps' candidate frames) and members (per map, the member frame ids),
+        map_off, map_cloud, map_pose as given to the call.  evaluate.choose_registered works on its fitness."""
+        qp = np.ascontiguousarray(query_points, dtype=np.float32)
+        if qp.ndim != 2 or qp.shape[1] not in (3, 4):
+            raise ValueError("query_points: (total, 3 or 4)")
+        qoff = np.asarray(query_pt_off, np.int64).reshape(-1)
+        if qoff.size != self._nq + 1:
+            raise ValueError("query_pt_off: n_queries + 1 offsets")
+        q, c, f, init = self.register_pairs(max_per_query, start)
+
+        def cloud_of(frame):
+            if isinstance(map_clouds, dict):
+                return map_clouds.get(int(frame))
+            return map_clouds[frame] if 0 <= frame < len(map_clouds) else None
+
+        def pose_of(frame):
+            if isinstance(frame_poses, dict):
+                return frame_poses.get(int(frame))
+            return frame_poses[frame] if 0 <= frame < len(frame_poses) else None
+
+        has = np.array([cloud_of(int(x)) is not None and pose_of(int(x)) is not None for x in f], bool)
+        q, c, f, init = q[has], c[has], f[has], init[has]
+        map_frames = sorted(set(int(x) for x in f))
+        members, rels = [], []
+        for x in map_frames:
+            m, rel = self.voxel_map_members(x, frame_poses, lambda i: cloud_of(i) is not None, radius, max_members)
+            members.append(m)
+            rels.append(rel)
+        frames = sorted(set(int(i) for m in members for i in m))
+        stride = qp.shape[1]
+        clouds = []
+        for x in frames:
+            a = np.ascontiguousarray(cloud_of(x), dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != stride:
+                raise ValueError("map_clouds: (n, %d) arrays, as the query points" % stride)
+            clouds.append(a)
+        pts = np.concatenate([qp[:qoff[-1]]] + clouds) if clouds else qp[:qoff[-1]]
+        off = np.concatenate([qoff, qoff[-1] + np.cumsum([a.shape[0] for a in clouds], dtype=np.int64)]).astype(np.int64)
+        slot = {x: self._nq + k for k, x in enumerate(frames)}
+        map_off = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.int32)
+        map_cloud = np.array([slot[int(i)] for m in members for i in m], np.int32)
+        map_pose = np.concatenate(rels).reshape(-1, 12) if rels else np.zeros((0, 12))
+        map_slot = {x: k for k, x in enumerate(map_frames)}
+        tgt = np.array([map_slot[int(x)] for x in f], np.int32)
+        out = self.register_voxels(pts, off, map_off, map_cloud, map_pose, q, tgt, init if len(q) else None, **options)
+        out.update(query=q, cand=c, frame=f, init=init, src_cloud=q.copy(), tgt_map=tgt, points=pts, pt_off=off, map_frames=map_frames,
+                   members=members, map_off=map_off, map_cloud=map_cloud, map_pose=map_pose)
         return out
 
     def search_frame(self, stds_vec, capacity=16384, page_locked=False, lists_only=False, allowed=None, prior=None):
