@@ -139,6 +139,17 @@ struct SelectPlan {
   bool narrow_pairs = false;      // list form: 4-byte words of the compact lists where an entry's rank among its frame's fits 19 bits, else 8
 };
 
+// What a stage measures of a call under sgtd_set_timing: milliseconds per kind of work, between events on the call's
+// stream.  The events are made by the stage's first timed call and live as long as the handle.
+struct LapClock {
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  int start(sgtd_engine *e, bool timed);                       // a call begins: no milliseconds yet, the events exist if it is timed
+  int lap(sgtd_engine *e, int kind);                           // ms[kind] += the work since ev[0] (waited for); ev[0] is recorded anew
+  int span(sgtd_engine *e, int a, int b, int kind, bool wait); // ms[kind] += the time from ev[a] to ev[b], recorded both (wait: ev[b] is waited for)
+  void destroy();
+};
+
 }  // namespace
 
 namespace multi { struct Group; }
@@ -331,22 +342,21 @@ struct sgtd_engine {
   // sgtd_register_clouds (register_kernels.hip.h): independent of the batch.  rg_in: the call's index arrays, offsets and
   // start poses; rg_pts: the points when the host gave them; rg_cov: a covariance per point; rg_part: the slices' minima;
   // rg_match: the last pass's matches and M_i; rg_state: RegState per pair; rg_out: the result rows; rg_ctl: the count of
-  // unfinished pairs.  rg_n < 0: no results; rg_host_*: what the getters need of the call; rg_ms: covariances, searches,
-  // the rest, the whole call (filled under sgtd_set_timing)
+  // unfinished pairs.  rg_n < 0: no results; rg_host_*: what the getters need of the call; rg_clock.ms: covariances,
+  // searches, the rest, the whole call (filled under sgtd_set_timing)
   DevBuf rg_in, rg_pts, rg_cov, rg_part, rg_match, rg_state, rg_out, rg_ctl;
   int rg_n = -1;
   std::vector<int64_t> rg_host_off;
-  std::vector<int> rg_host_idx;          // src [n], tgt [n], src_off [n + 1]
+  std::vector<int> rg_host_soff;         // src_off [n + 1]
   std::vector<unsigned char> rg_host_named;
   std::vector<int> rg_host_up;           // (the source of the index upload)
-  hipEvent_t rg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float rg_ms[4] = {0.f, 0.f, 0.f, 0.f};
+  LapClock rg_clock;
   // sgtd_register_voxels (voxel_register_kernels.hip.h): independent of the batch and of sgtd_register_clouds' buffers.
   // VR_IN: the call's index arrays, offsets and poses; VR_PTS: the points when the host gave them; VR_COV: a covariance per
   // point; VR_KEY_* / VR_VAL_*: the sort's pairs; VR_FLAGS .. VR_MAP_VOX: the voxels' heads, keys, first points and the
   // maps' ranges; VR_MEAN / VR_VCOV: the Gaussians; VR_VID / VR_MW: the per-correspondence streams; VR_STATE, VR_OUT,
-  // VR_CTL as rg_*.  vr_n < 0: no results; vr_host_*: what the getters need of the call; vr_ms: covariances, map build,
-  // correspondence passes, the rest, the whole call (filled under sgtd_set_timing)
+  // VR_CTL as rg_*.  vr_n < 0: no results; vr_host_*: what the getters need of the call; vr_clock.ms: covariances, map
+  // build, correspondence passes, the rest, the whole call (filled under sgtd_set_timing)
   enum { VR_IN = 0, VR_PTS, VR_COV, VR_KEY_A, VR_KEY_B, VR_VAL_A, VR_VAL_B, VR_FLAGS, VR_EXCL, VR_COUNTS, VR_VKEY, VR_VSTART, VR_MAP_VOX, VR_MEAN, VR_VCOV,
          VR_VID, VR_MW, VR_STATE, VR_OUT, VR_CTL, VR_BUFS };
   DevBuf vr[VR_BUFS];
@@ -354,8 +364,7 @@ struct sgtd_engine {
   std::vector<int> vr_host_soff;         // src_off [n + 1]
   std::vector<u32> vr_host_map_vox;      // [n_maps + 1]
   std::vector<int> vr_host_up;           // (the source of the index upload)
-  hipEvent_t vr_ev[3] = {nullptr, nullptr, nullptr};
-  float vr_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  LapClock vr_clock;
   // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (SK_*: scan_run).  sk_n < 0:
   // no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets on the host
   enum { SK_PTS = 0, SK_LAB, SK_OFF, SK_SC, SK_R, SK_PITCH, SK_AZI, SK_MM, SK_VOTE, SK_GRID, SK_RANGE, SK_BOUNDS, SK_KEY_A, SK_KEY_B, SK_VAL_A, SK_VAL_B,
@@ -368,16 +377,15 @@ struct sgtd_engine {
   std::vector<int64_t> sk_off, sk_kp_off;
   // sgtd_local_map_keypoints (local_map_kernels.hip.h): the member lists, the pass's segments and merged cloud, and the
   // appended keypoints of all passes (LM_XYZ / LM_LABEL / LM_NPOINTS); the clustering runs in the sk buffers above.
-  // lm_n < 0: no results; lm_kp_off / lm_mem_off / lm_merged: per anchor, on the host; lm_ms: members, gather, scan
-  // passes of the last call (filled under sgtd_set_timing)
+  // lm_n < 0: no results; lm_kp_off / lm_mem_off / lm_merged: per anchor, on the host; lm_clock.ms: members, gather,
+  // scan passes of the last call (filled under sgtd_set_timing)
   enum { LM_POSE = 0, LM_OFF, LM_ANCH, LM_COUNT, LM_MERGED, LM_MEM_OFF, LM_MEMBER, LM_SEG, LM_CNT, LM_START, LM_MPTS, LM_MLAB, LM_XYZ, LM_LABEL,
          LM_NPOINTS, LM_BUFS };
   DevBuf lm[LM_BUFS];
   int lm_n = -1, lm_passes = 0;
   int64_t lm_kept = 0;
   std::vector<int64_t> lm_kp_off, lm_mem_off, lm_merged;
-  hipEvent_t lm_ev[3] = {nullptr, nullptr, nullptr};
-  float lm_ms[3] = {0.f, 0.f, 0.f};
+  LapClock lm_clock;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -2270,15 +2278,10 @@ int sgtd_destroy(sgtd_handle e) {
   for (DevBuf *b : bufs) free_buf(*b);
   for (DevBuf &b : e->sk) free_buf(b);
   for (DevBuf &b : e->lm) free_buf(b);
-  for (hipEvent_t ev : e->lm_ev)
-    if (ev) (void)hipEventDestroy(ev);
+  for (DevBuf &b : e->vr) free_buf(b);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : e->rg_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (DevBuf &b : e->vr) free_buf(b);
-  for (hipEvent_t ev : e->vr_ev)
-    if (ev) (void)hipEventDestroy(ev);
+  for (LapClock *k : {&e->rg_clock, &e->vr_clock, &e->lm_clock}) k->destroy();
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
@@ -3670,6 +3673,128 @@ void keypoint_params(sgtd_engine *e, bool refined, double radius, size_t nb, Par
   P->order = nullptr; P->n_blocks = (u32)nb;
 }
 
+// ---- what the cloud and graph stages share (sgtd_consistent_loops, sgtd_relax_poses, sgtd_pose_consensus,
+// sgtd_scan_keypoints, sgtd_local_map_keypoints, sgtd_register_clouds, sgtd_register_voxels): their results do not belong
+// to a batch and live on one engine ----
+// the engine a handle's batch-independent results live on: the handle itself, a group's first device
+sgtd_engine *home_engine(sgtd_engine *e) { return e->grp ? multi::device_handle(e, 0) : e; }
+
+// a getter's state check: *c is e's home engine, whose count `n` of results is negative while the stage has not run
+// (`missing` says so on the caller's handle)
+template <class N>
+int stage_ready(sgtd_engine *e, N sgtd_engine::*n, const char *missing, sgtd_engine **c) {
+  *c = home_engine(e);
+  if ((*c)->*n < 0) { e->err = missing; return SGTD_ERR_STATE; }
+  return SGTD_OK;
+}
+
+// A getter's copies from the home engine c to the caller's arrays: the device is selected, a copy is skipped where
+// the caller passed no array, has nothing to get or an earlier step failed, finish() waits for them all and hands a
+// group handle the failure's text.  (Leaving the scope drops what a failed getter left queued: PinScope.)
+struct CopyOut {
+  sgtd_engine *e, *c;
+  PinScope pin;
+  int st;
+  CopyOut(sgtd_engine *e_, sgtd_engine *c_) : e(e_), c(c_), pin(c_), st(hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP) {}
+  void get(void *dst, const void *dev_src, size_t bytes) {
+    if (st == SGTD_OK && dst && bytes) st = d2h(c, dst, dev_src, bytes);
+  }
+  int finish() {
+    if (st == SGTD_OK) st = xfer_sync(c);
+    if (st != SGTD_OK && c != e) e->err = c->err;
+    return st;
+  }
+};
+
+// An entry point's run on the home engine c: from here on the stage has no results (its count `n` is negative; no
+// device is touched yet), on_device() selects c's device and runs the stage's work at once (nothing may switch the
+// device in between: a group's getters do), and end() marks the results present unless that work failed, whose text
+// it hands a group handle.  A call with nothing to run ends without on_device().
+template <class N>
+struct StageRun {
+  sgtd_engine *e, *c;
+  N *n;
+  PinScope pin;
+  int st = SGTD_OK;
+  StageRun(sgtd_engine *e_, N sgtd_engine::*n_) : e(e_), c(home_engine(e_)), n(&(c->*n_)), pin(c) { *n = -1; }
+  int select() {
+    sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the stage)
+    HIPCHK(hipSetDevice(c->cfg.device_id));
+    return SGTD_OK;
+  }
+  template <class Work>
+  void on_device(Work &&work) {
+    st = select();
+    if (st == SGTD_OK) st = work(c);
+  }
+  int end(N have) {
+    if (st != SGTD_OK) {
+      if (c != e) e->err = c->err;
+      return st;
+    }
+    *n = have;
+    return SGTD_OK;
+  }
+};
+
+// the call's points on the device: the caller's array as it is, or (points from the host) a copy in buf
+int points_on_device(sgtd_engine *c, DevBuf &buf, const float *points, size_t floats, int device_ptrs, const float **d_pts) {
+  *d_pts = points;
+  if (device_ptrs || floats == 0) return SGTD_OK;
+  CHK(ensure(c, buf, floats * sizeof(float)));
+  CHK(h2d(c, buf.p, points, floats * sizeof(float)));
+  *d_pts = buf.as<float>();
+  return SGTD_OK;
+}
+
+// a call's clouds (scans), back to back: the offsets start at 0 and do not fall, a point has 3 or 4 floats, and where
+// there is a point there are the arrays (labels only where the call takes them: need_labels)
+bool cloud_set_ok(const int64_t *pt_off, int n_clouds, int stride_floats, const float *points, bool need_labels, const uint32_t *labels) {
+  if (n_clouds < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4) || pt_off[0] != 0) return false;
+  for (int cl = 0; cl < n_clouds; cl++)
+    if (pt_off[cl + 1] < pt_off[cl]) return false;
+  return pt_off[n_clouds] == 0 || (points && (labels || !need_labels));
+}
+
+int key_bits(u64 v) { int b = 0; while (v) { b++; v >>= 1; } return std::max(b, 1); }
+
+// The runs of equal keys in n sorted keys (keys from `drop` on belong to no run): head flags, their exclusive scan
+// (excl[n]: the count of runs), the runs' keys and first positions.  counts: zeroed on the stream by the caller.
+int voxel_runs(sgtd_engine *e, const u64 *keys, long long n, u64 drop, u32 *flags, u32 *excl, u32 *counts, u64 *vkey, u32 *vstart) {
+  scan_heads_kernel<<<grid_for(n + 1, 256), 256, 0, e->stream>>>(keys, n, drop, flags, counts);
+  HIPCHK(hipGetLastError());
+  CHK(device_scan(e, flags, excl, n + 1));
+  scan_voxels_kernel<<<grid_for(n, 256), 256, 0, e->stream>>>(keys, flags, excl, n, counts, vkey, vstart);
+  return SGTD_OK;      // (the caller asks for the launches' error, behind what it launches next)
+}
+
+int LapClock::start(sgtd_engine *e, bool timed) {
+  for (float &v : ms) v = 0.f;
+  if (timed)
+    for (hipEvent_t &v : ev)
+      if (!v) HIPCHK(hipEventCreate(&v));
+  return SGTD_OK;
+}
+int LapClock::lap(sgtd_engine *e, int kind) {
+  HIPCHK(hipEventRecord(ev[1], e->stream));
+  CHK(span(e, 0, 1, kind, true));
+  HIPCHK(hipEventRecord(ev[0], e->stream));
+  return SGTD_OK;
+}
+int LapClock::span(sgtd_engine *e, int a, int b, int kind, bool wait) {
+  if (wait) HIPCHK(hipEventSynchronize(ev[b]));
+  float t = 0.f;
+  HIPCHK(hipEventElapsedTime(&t, ev[a], ev[b]));
+  ms[kind] += t;
+  return SGTD_OK;
+}
+void LapClock::destroy() {
+  for (hipEvent_t &v : ev) {
+    if (v) (void)hipEventDestroy(v);
+    v = nullptr;
+  }
+}
+
 // query q's candidate count and frames, of a single-device handle or of a group
 int batch_candidates(sgtd_engine *e, int q, int *n_cand, int *cand_frame) {
   if (e->grp) return multi::candidates_of(e, q, n_cand, cand_frame);
@@ -4219,8 +4344,7 @@ int sgtd_table_dump(sgtd_handle e, int64_t *keys, int64_t *bucket_off, int64_t *
 // ---- sgtd_consistent_loops: pairwise consistency over a list of loop closures and the greedy clique
 // (consistency_kernels.hip.h) ----
 namespace {
-// the engine whose device, stream and buffers the consistency pass uses: the handle's own, a group's first device's
-sgtd_engine *cons_engine(sgtd_engine *e) { return e->grp ? multi::device_handle(e, 0) : e; }
+const char kNoConsistency[] = "no consistency results: sgtd_consistent_loops has not run";
 
 // the pose store `owner` holds (its own handle's, or the group's), copied to c's device when it changed
 int cons_upload_store(sgtd_engine *c, const sgtd_engine *owner) {
@@ -4238,7 +4362,6 @@ int cons_upload_store(sgtd_engine *c, const sgtd_engine *owner) {
 int cons_run(sgtd_engine *c, const sgtd_engine *owner, int n, const uint32_t *frame_a, const uint32_t *frame_b, const double *rel_pose,
              const float *pose_a, double tt, double min_trace, int32_t *n_set) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
-  HIPCHK(hipSetDevice(c->cfg.device_id));
   CHK(cons_upload_store(c, owner));
   const u32 words = (u32)((n + 63) / 64);
   const size_t ns = (size_t)words * 64;
@@ -4323,57 +4446,43 @@ int sgtd_consistent_loops(sgtd_handle e, int64_t n, const uint32_t *frame_a, con
   if (n > 0 && (!frame_b || !rel_pose || (!frame_a && !pose_a))) return SGTD_ERR_INVALID;
   if (!(max_trans >= 0.0) || std::isinf(max_trans)) return SGTD_ERR_INVALID;
   if (!(max_rot >= 0.0 && max_rot <= 3.14159265358979323846)) return SGTD_ERR_INVALID;
-  sgtd_engine *c = cons_engine(e);
-  c->ck_n = -1;
+  StageRun<int64_t> run(e, &sgtd_engine::ck_n);
   if (n > SGTD_MAX_LOOP_EDGES) {
     e->err = "sgtd_consistent_loops takes at most " + std::to_string(SGTD_MAX_LOOP_EDGES) + " edges in one call (" + std::to_string(n) + " given)";
     return SGTD_ERR_UNSUPPORTED;
   }
-  PinScope pin_scope(c);
   const double tt = max_trans * max_trans, min_trace = 1.0 + 2.0 * std::cos(max_rot);
   *n_set = 0;
-  if (n > 0) {
-    const int st = cons_run(c, e, (int)n, frame_a, frame_b, rel_pose, pose_a, tt, min_trace, n_set);
-    if (st != SGTD_OK) {
-      if (c != e) e->err = c->err;
-      return st;
-    }
-  }
-  c->ck_thr[0] = tt; c->ck_thr[1] = min_trace;
-  c->ck_n = n;
-  return SGTD_OK;
+  if (n > 0) run.on_device([&](sgtd_engine *c) { return cons_run(c, e, (int)n, frame_a, frame_b, rel_pose, pose_a, tt, min_trace, n_set); });
+  if (run.st == SGTD_OK) { run.c->ck_thr[0] = tt; run.c->ck_thr[1] = min_trace; }
+  return run.end(n);
 }
 
 int sgtd_result_consistent(sgtd_handle e, int32_t *in_set, int32_t *degree, int32_t *pick, double *thresholds) {
   if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = cons_engine(e);
-  PinScope pin_scope(c);
-  if (c->ck_n < 0) { e->err = "no consistency results: sgtd_consistent_loops has not run"; return SGTD_ERR_STATE; }
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::ck_n, kNoConsistency, &c));
   if (thresholds) { thresholds[0] = c->ck_thr[0]; thresholds[1] = c->ck_thr[1]; }
   const size_t n = (size_t)c->ck_n;
   if (n == 0) return SGTD_OK;
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
+  CopyOut out(e, c);
   const int *d = c->ck_out.as<int>();
-  if (st == SGTD_OK && in_set) st = d2h(c, in_set, d, n * sizeof(int));
-  if (st == SGTD_OK && degree) st = d2h(c, degree, d + n, n * sizeof(int));
-  if (st == SGTD_OK && pick) st = d2h(c, pick, d + 2 * n, n * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK && c != e) e->err = c->err;
-  return st;
+  out.get(in_set, d, n * sizeof(int));
+  out.get(degree, d + n, n * sizeof(int));
+  out.get(pick, d + 2 * n, n * sizeof(int));
+  return out.finish();
 }
 
 int sgtd_result_consistency_rows(sgtd_handle e, int64_t first, int64_t n_rows, uint64_t *rows) {
   if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = cons_engine(e);
-  if (c->ck_n < 0) { e->err = "no consistency results: sgtd_consistent_loops has not run"; return SGTD_ERR_STATE; }
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::ck_n, kNoConsistency, &c));
   if (first < 0 || n_rows < 0 || first > c->ck_n || n_rows > c->ck_n - first || (n_rows > 0 && !rows)) return SGTD_ERR_INVALID;
   if (n_rows == 0) return SGTD_OK;
   const size_t words = (size_t)((c->ck_n + 63) / 64);
-  hipError_t hs = hipSetDevice(c->cfg.device_id);
-  if (hs == hipSuccess) hs = hipMemcpyAsync(rows, c->ck_rows.as<u64>() + (size_t)first * words, (size_t)n_rows * words * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
-  if (hs == hipSuccess) hs = hipStreamSynchronize(c->stream);
-  if (hs != hipSuccess) { e->err = std::string("sgtd_result_consistency_rows: ") + hipGetErrorString(hs); return SGTD_ERR_HIP; }
-  return SGTD_OK;
+  CopyOut out(e, c);      // (rows of more than kPinMax bytes take d2h's direct copy: the staging bounds nothing)
+  out.get(rows, c->ck_rows.as<u64>() + (size_t)first * words, (size_t)n_rows * words * sizeof(u64));
+  return out.finish();
 }
 
 int sgtd_result_loop_edges(sgtd_handle e, double icp_threshold, int flags, int32_t *query, uint32_t *frame_a, uint32_t *frame_b,
@@ -4467,8 +4576,6 @@ int consensus_launch(sgtd_engine *c, const sgtd_engine *owner, int nq, int cn, c
 // the rows form: the caller's host arrays go to c's device first; the host waits for the pass
 int consensus_rows_run(sgtd_engine *c, const sgtd_engine *owner, int nq, int cn, const int32_t *n_cand, const int32_t *cand_frame,
                        const double *score, const double *rel_pose, double tt, double min_trace) {
-  sgtd_engine *e = c;
-  HIPCHK(hipSetDevice(c->cfg.device_id));
   const size_t nb = (size_t)nq * cn;
   const size_t o_rel = 0, o_score = o_rel + nb * 12 * sizeof(double), o_frame = o_score + nb * sizeof(double),
                o_n = o_frame + nb * sizeof(int), in_bytes = o_n + (size_t)nq * sizeof(int);
@@ -4514,11 +4621,9 @@ int consensus_batch_scores(sgtd_engine *e, int nq, std::vector<int> *frame, std:
 
 // the getters' state checks; *out: the engine that holds the results
 int consensus_ready(sgtd_engine *e, sgtd_engine **out) {
-  sgtd_engine *c = cons_engine(e);
+  sgtd_engine *c = home_engine(e);
   if (c->cs_n >= 0 && c->cs_batch && !have_verified(e)) c->cs_n = -1;      // (the batch went without a new one)
-  if (c->cs_n < 0) { e->err = "no consensus results: sgtd_pose_consensus has not run (or its batch has gone)"; return SGTD_ERR_STATE; }
-  *out = c;
-  return SGTD_OK;
+  return stage_ready(e, &sgtd_engine::cs_n, "no consensus results: sgtd_pose_consensus has not run (or its batch has gone)", out);
 }
 
 // sgtd_search_loop_consensus' choice for every query of the batch form's results: cand, frame, score [nq] (-1, -1, 0
@@ -4558,35 +4663,25 @@ extern "C" {
 int sgtd_pose_consensus_rows(sgtd_handle e, int64_t n_queries, int cand_num, const int32_t *n_cand, const int32_t *cand_frame,
                              const double *score, const double *rel_pose, double max_trans, double max_rot) {
   if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = cons_engine(e);
-  c->cs_n = -1;
+  StageRun<int64_t> run(e, &sgtd_engine::cs_n);
   if (n_queries < 0 || cand_num < 1 || cand_num > SGTD_MAX_CAND || !consensus_bounds_ok(max_trans, max_rot)) return SGTD_ERR_INVALID;
   if (n_queries > 0 && (!n_cand || !cand_frame || !score || !rel_pose)) return SGTD_ERR_INVALID;
   if (n_queries > 0x7FFFFFFF / SGTD_MAX_CAND) {
     e->err = "sgtd_pose_consensus_rows takes at most " + std::to_string(0x7FFFFFFF / SGTD_MAX_CAND) + " queries in one call";
     return SGTD_ERR_UNSUPPORTED;
   }
-  PinScope pin_scope(c);
   const double tt = max_trans * max_trans, min_trace = 1.0 + 2.0 * std::cos(max_rot);
-  if (n_queries > 0) {
-    const int st = consensus_rows_run(c, e, (int)n_queries, cand_num, n_cand, cand_frame, score, rel_pose, tt, min_trace);
-    if (st != SGTD_OK) {
-      if (c != e) e->err = c->err;
-      return st;
-    }
-  }
-  c->cs_thr[0] = tt; c->cs_thr[1] = min_trace;
-  c->cs_n = n_queries; c->cs_cn = cand_num; c->cs_batch = false;
-  return SGTD_OK;
+  if (n_queries > 0)
+    run.on_device([&](sgtd_engine *c) { return consensus_rows_run(c, e, (int)n_queries, cand_num, n_cand, cand_frame, score, rel_pose, tt, min_trace); });
+  if (run.st == SGTD_OK) { run.c->cs_thr[0] = tt; run.c->cs_thr[1] = min_trace; run.c->cs_cn = cand_num; run.c->cs_batch = false; }
+  return run.end(n_queries);
 }
 
 int sgtd_pose_consensus(sgtd_handle e, double max_trans, double max_rot, int flags) {
   if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = cons_engine(e);
-  c->cs_n = -1;
+  StageRun<int64_t> run(e, &sgtd_engine::cs_n);
   if ((flags & ~(SGTD_CONSENSUS_REFINED | SGTD_CONSENSUS_ALIGNED)) || flags == (SGTD_CONSENSUS_REFINED | SGTD_CONSENSUS_ALIGNED)) return SGTD_ERR_INVALID;
   if (!consensus_bounds_ok(max_trans, max_rot)) return SGTD_ERR_INVALID;
-  PinScope pin_scope(c);
   if (!have_verified(e)) return needs(e, "sgtd_pose_consensus", "sgtd_verify");
   if ((flags & SGTD_CONSENSUS_REFINED) && !(e->grp ? e->grp->refined : e->refined)) return needs(e, "SGTD_CONSENSUS_REFINED", "sgtd_refine_poses");
   if ((flags & SGTD_CONSENSUS_ALIGNED) && !(e->grp ? e->grp->aligned : e->aligned)) return needs(e, "SGTD_CONSENSUS_ALIGNED", "sgtd_align_keypoints");
@@ -4602,20 +4697,20 @@ int sgtd_pose_consensus(sgtd_handle e, double max_trans, double max_rot, int fla
       CHK(sgtd_result_verify(e, q, score.data() + (size_t)q * cn, nullptr));
       CHK(consensus_batch_pose(e, q, flags, pose.data() + (size_t)q * cn * 12));
     }
-    if (nq > 0) {
-      const int st = consensus_rows_run(c, e, nq, cn, n_cand.data(), frame.data(), score.data(), pose.data(), tt, min_trace);
-      if (st != SGTD_OK) { e->err = c->err; return st; }
-    }
+    // (the gather above left the device of a candidate's owner selected: on_device selects the first again)
+    if (nq > 0)
+      run.on_device([&](sgtd_engine *c) { return consensus_rows_run(c, e, nq, cn, n_cand.data(), frame.data(), score.data(), pose.data(), tt, min_trace); });
   } else {
-    HIPCHK(hipSetDevice(e->cfg.device_id));
-    CHK(view_current(e));
-    const double *rel = (flags & SGTD_CONSENSUS_REFINED) ? e->r_pose.as<double>() : (flags & SGTD_CONSENSUS_ALIGNED) ? e->a_pose.as<double>() : e->v_pose.as<double>();
-    // the batch's candidates, scores and poses are read where the earlier stages left them: nothing travels
-    if (nq > 0) CHK(consensus_launch(e, e, nq, cn, e->n_cand.as<int>(), e->cand_frame.as<int>(), e->v_score.as<double>(), rel, tt, min_trace));
+    run.on_device([&](sgtd_engine *) -> int {
+      CHK(view_current(e));
+      const double *rel = (flags & SGTD_CONSENSUS_REFINED) ? e->r_pose.as<double>() : (flags & SGTD_CONSENSUS_ALIGNED) ? e->a_pose.as<double>() : e->v_pose.as<double>();
+      // the batch's candidates, scores and poses are read where the earlier stages left them: nothing travels
+      if (nq > 0) CHK(consensus_launch(e, e, nq, cn, e->n_cand.as<int>(), e->cand_frame.as<int>(), e->v_score.as<double>(), rel, tt, min_trace));
+      return SGTD_OK;
+    });
   }
-  c->cs_thr[0] = tt; c->cs_thr[1] = min_trace;
-  c->cs_n = nq; c->cs_cn = cn; c->cs_batch = true;
-  return SGTD_OK;
+  if (run.st == SGTD_OK) { run.c->cs_thr[0] = tt; run.c->cs_thr[1] = min_trace; run.c->cs_cn = cn; run.c->cs_batch = true; }
+  return run.end(nq);
 }
 
 int sgtd_result_consensus(sgtd_handle e, int64_t first, int64_t n, double *pose, int32_t *n_valid, int32_t *n_set, int32_t *seed,
@@ -4626,28 +4721,18 @@ int sgtd_result_consensus(sgtd_handle e, int64_t first, int64_t n, double *pose,
   if (first < 0 || n < 0 || first > c->cs_n || n > c->cs_n - first) return SGTD_ERR_INVALID;
   if (thresholds) { thresholds[0] = c->cs_thr[0]; thresholds[1] = c->cs_thr[1]; }
   if (n == 0) return SGTD_OK;
-  PinScope pin_scope(c);
   const ConsensusLayout L((size_t)c->cs_n, (size_t)c->cs_cn);
-  const char *out = c->cs_out.as<char>();
+  const char *dev = c->cs_out.as<char>();
   const size_t f = (size_t)first, m = (size_t)n;
-  std::vector<double> figs;
-  std::vector<int> counts;
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && pose) st = d2h(c, pose, out + L.pose + f * 12 * sizeof(double), m * 12 * sizeof(double));
-  if (st == SGTD_OK && mask) st = d2h(c, mask, out + L.mask + f * sizeof(u64), m * sizeof(u64));
-  if (st == SGTD_OK && (support_score || spread_t2 || spread_trace)) {
-    figs.resize(m * 3);
-    st = d2h(c, figs.data(), out + L.figs + f * 3 * sizeof(double), m * 3 * sizeof(double));
-  }
-  if (st == SGTD_OK && (n_valid || n_set || seed)) {
-    counts.resize(m * 3);
-    st = d2h(c, counts.data(), out + L.counts + f * 3 * sizeof(int), m * 3 * sizeof(int));
-  }
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) {
-    if (c != e) e->err = c->err;
-    return st;
-  }
+  // (the figures and the counts come interleaved: through a host copy, where the caller asks for any of them)
+  std::vector<double> figs(support_score || spread_t2 || spread_trace ? m * 3 : 0);
+  std::vector<int> counts(n_valid || n_set || seed ? m * 3 : 0);
+  CopyOut out(e, c);
+  out.get(pose, dev + L.pose + f * 12 * sizeof(double), m * 12 * sizeof(double));
+  out.get(mask, dev + L.mask + f * sizeof(u64), m * sizeof(u64));
+  out.get(figs.data(), dev + L.figs + f * 3 * sizeof(double), figs.size() * sizeof(double));
+  out.get(counts.data(), dev + L.counts + f * 3 * sizeof(int), counts.size() * sizeof(int));
+  CHK(out.finish());
   for (size_t i = 0; i < m; i++) {
     if (support_score) support_score[i] = figs[i * 3 + 0];
     if (spread_t2) spread_t2[i] = figs[i * 3 + 1];
@@ -4664,17 +4749,14 @@ int sgtd_result_consensus_rows(sgtd_handle e, int q, uint64_t *rows, int32_t *de
   sgtd_engine *c = nullptr;
   CHK(consensus_ready(e, &c));
   if (q < 0 || q >= c->cs_n) return SGTD_ERR_INVALID;
-  PinScope pin_scope(c);
   const size_t cn = (size_t)c->cs_cn, o = (size_t)q * cn;
   const ConsensusLayout L((size_t)c->cs_n, cn);
-  const char *out = c->cs_out.as<char>();
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && rows) st = d2h(c, rows, out + L.rows + o * sizeof(u64), cn * sizeof(u64));
-  if (st == SGTD_OK && degree) st = d2h(c, degree, out + L.degree + o * sizeof(int), cn * sizeof(int));
-  if (st == SGTD_OK && pick) st = d2h(c, pick, out + L.pick + o * sizeof(int), cn * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK && c != e) e->err = c->err;
-  return st;
+  const char *dev = c->cs_out.as<char>();
+  CopyOut out(e, c);
+  out.get(rows, dev + L.rows + o * sizeof(u64), cn * sizeof(u64));
+  out.get(degree, dev + L.degree + o * sizeof(int), cn * sizeof(int));
+  out.get(pick, dev + L.pick + o * sizeof(int), cn * sizeof(int));
+  return out.finish();
 }
 
 int sgtd_search_loop_consensus(sgtd_handle e, int min_support, int32_t *best_cand, int32_t *best_frame, double *best_score, int32_t *support) {
@@ -4750,7 +4832,6 @@ struct RelaxEdgeLayout {
 int relax_run(sgtd_engine *c, int n, const double *pose0, const uint8_t *fixed, int m, const int32_t *node_i, const int32_t *node_j,
               const double *meas, const double *w_trans, const double *w_rot, const sgtd_relax_options &o, bool all_held, RelaxState *out) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
-  HIPCHK(hipSetDevice(c->cfg.device_id));
   const RelaxEdgeLayout lay((size_t)m);
   const size_t ms = lay.ms;
   // the node -> edge CSR, the entries of a node in ascending edge index: off [n + 1], then ent [2 m]
@@ -4889,11 +4970,11 @@ int sgtd_relax_poses(sgtd_handle e, int64_t n_nodes, const double *pose0, const 
     if ((w_trans && !(std::isfinite(w_trans[k]) && w_trans[k] >= 0.0)) || (w_rot && !(std::isfinite(w_rot[k]) && w_rot[k] >= 0.0))) return SGTD_ERR_INVALID;
   }
   if (!relax_finite(pose0, (size_t)n_nodes * 12) || !relax_finite(meas, (size_t)n_edges * 12)) return SGTD_ERR_INVALID;
-  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
   sgtd_relax_report rep{};
   rep.lambda = o.lambda_init;
   rep.status = SGTD_RELAX_NOTHING_FREE;
-  if (n_nodes == 0 || n_edges == 0) {
+  if (n_nodes == 0 || n_edges == 0) {      // (nothing runs and no device is touched: the empty result)
+    sgtd_engine *c = home_engine(e);
     c->rx_n = 0; c->rx_m = 0;
     if (report) *report = rep;
     return SGTD_OK;
@@ -4901,15 +4982,11 @@ int sgtd_relax_poses(sgtd_handle e, int64_t n_nodes, const double *pose0, const 
   bool all_held = fixed != nullptr;
   for (int64_t v = 0; all_held && v < n_nodes; v++) all_held = fixed[v] != 0;
   if (!fixed && n_nodes == 1) all_held = true;
-  PinScope pin_scope(c);
-  c->rx_n = -1;
+  StageRun<int64_t> run(e, &sgtd_engine::rx_n);
   RelaxState st{};
-  const int rc = relax_run(c, (int)n_nodes, pose0, fixed, (int)n_edges, node_i, node_j, meas, w_trans, w_rot, o, all_held, &st);
-  if (rc != SGTD_OK) {
-    if (c != e) e->err = c->err;
-    return rc;
-  }
-  c->rx_n = n_nodes; c->rx_m = n_edges; c->rx_cur = st.cur;
+  run.on_device([&](sgtd_engine *c) { return relax_run(c, (int)n_nodes, pose0, fixed, (int)n_edges, node_i, node_j, meas, w_trans, w_rot, o, all_held, &st); });
+  CHK(run.end(n_nodes));
+  run.c->rx_m = n_edges; run.c->rx_cur = st.cur;
   rep.cost_before = st.cost_before; rep.cost_after = st.cost; rep.lambda = st.lambda;
   rep.outer_iterations = st.outer; rep.steps_accepted = st.accepted; rep.cg_iterations = st.cg_total; rep.status = st.status;
   if (report) *report = rep;
@@ -4918,22 +4995,15 @@ int sgtd_relax_poses(sgtd_handle e, int64_t n_nodes, const double *pose0, const 
 
 int sgtd_result_relaxed(sgtd_handle e, double *pose, double *edge_cost) {
   if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
-  if (c->rx_n < 0) { e->err = "no relaxed poses: sgtd_relax_poses has not run"; return SGTD_ERR_STATE; }
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::rx_n, "no relaxed poses: sgtd_relax_poses has not run", &c));
   const size_t n = (size_t)c->rx_n, m = (size_t)c->rx_m;
   if (n == 0) return SGTD_OK;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  std::vector<double> rec;
-  if (st == SGTD_OK && pose) {
-    rec.resize(n * SGTD_RELAX_REC);
-    st = d2h(c, rec.data(), c->rx_state.as<double>() + (size_t)c->rx_cur * n * SGTD_RELAX_REC, rec.size() * sizeof(double));
-  }
-  if (st == SGTD_OK && edge_cost) {
-    st = d2h(c, edge_cost, c->rx_edge.as<double>() + RelaxEdgeLayout(m).ec_of(c->rx_cur, m), m * 2 * sizeof(double));
-  }
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  std::vector<double> rec(pose ? n * SGTD_RELAX_REC : 0);      // (the node records: the pose is part of one)
+  CopyOut out(e, c);
+  out.get(rec.data(), c->rx_state.as<double>() + (size_t)c->rx_cur * n * SGTD_RELAX_REC, rec.size() * sizeof(double));
+  out.get(edge_cost, c->rx_edge.as<double>() + RelaxEdgeLayout(m).ec_of(c->rx_cur, m), m * 2 * sizeof(double));
+  CHK(out.finish());
   if (pose)
     for (size_t v = 0; v < n; v++)
       for (int r = 0; r < 3; r++) {
@@ -4957,80 +5027,165 @@ int reg_slice_tiles() {
   return hook && atoi(hook) > 0 ? std::min(atoi(hook), 1 << 10) : SGTD_REG_SLICE_TILES;
 }
 
-struct RegOut {      // rg_out: pose [n][12], fitness [n], cost [n][2] in f64, then matched, iterations, status [n] in i32
+// ---- what sgtd_register_clouds and sgtd_register_voxels share on the host: one GICP call skeleton
+// the result rows, in one buffer: pose [n][12], fitness [n], cost [n][2] in f64, then matched, iterations, status [n] in
+// i32 and, where the call counts correspondences (sgtd_register_voxels), n_corr [n]
+struct RegOut {
   size_t n;
-  explicit RegOut(size_t n_) : n(n_) {}
-  size_t bytes() const { return n * (15 * sizeof(double) + 3 * sizeof(int)); }
+  bool with_corr;
+  RegOut(size_t n_, bool with_corr_) : n(n_), with_corr(with_corr_) {}
+  size_t bytes() const { return n * (15 * sizeof(double) + (with_corr ? 4 : 3) * sizeof(int)); }
   double *pose(void *p) const { return static_cast<double *>(p); }
   double *fitness(void *p) const { return pose(p) + n * 12; }
   double *cost(void *p) const { return fitness(p) + n; }
   int *matched(void *p) const { return reinterpret_cast<int *>(cost(p) + n * 2); }
   int *iters(void *p) const { return matched(p) + n; }
   int *status(void *p) const { return iters(p) + n; }
+  int *corr(void *p) const { return status(p) + n; }
 };
 
-int reg_lap(sgtd_engine *e, int kind) {
-  HIPCHK(hipEventRecord(e->rg_ev[1], e->stream));
-  HIPCHK(hipEventSynchronize(e->rg_ev[1]));
-  float t = 0.f;
-  HIPCHK(hipEventElapsedTime(&t, e->rg_ev[0], e->rg_ev[1]));
-  e->rg_ms[kind] += t;
-  HIPCHK(hipEventRecord(e->rg_ev[0], e->stream));
+// the rows a getter asks for, from the home engine c's buffer ob (n_corr: NULL where the call has none)
+int reg_rows_out(sgtd_engine *e, sgtd_engine *c, const RegOut &out, void *ob, double *pose, double *fitness, double *cost, int32_t *n_matched,
+                 int32_t *n_corr, int32_t *iterations, int32_t *status) {
+  const size_t n = out.n;
+  CopyOut copy(e, c);
+  copy.get(pose, out.pose(ob), n * 12 * sizeof(double));
+  copy.get(fitness, out.fitness(ob), n * sizeof(double));
+  copy.get(cost, out.cost(ob), n * 2 * sizeof(double));
+  copy.get(n_matched, out.matched(ob), n * sizeof(int));
+  if (out.with_corr) copy.get(n_corr, out.corr(ob), n * sizeof(int));
+  copy.get(iterations, out.iters(ob), n * sizeof(int));
+  copy.get(status, out.status(ob), n * sizeof(int));
+  return copy.finish();
+}
+
+// the options the two calls' structs share: their check, and what the kernels take of them
+bool gicp_options_ok(int k, int max_iterations, int lm_max_trials, int reserved, double lambda_factor, double rotation_eps, double translation_eps,
+                     double plane_eps) {
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  return k >= 3 && k <= SGTD_REG_MAX_K && max_iterations >= 1 && lm_max_trials >= 1 && reserved == 0 && pos(lambda_factor) && pos(rotation_eps) &&
+         pos(translation_eps) && pos(plane_eps);
+}
+RegOptionsDev gicp_options(int k, int max_iterations, int lm_max_trials, double max_corr_dist, double lambda_factor, double rotation_eps,
+                           double translation_eps, double plane_eps) {
+  RegOptionsDev o;
+  o.k = k; o.max_iterations = max_iterations; o.lm_max_trials = lm_max_trials;
+  o.max2 = max_corr_dist * max_corr_dist; o.lambda_factor = lambda_factor;
+  o.rotation_eps = rotation_eps; o.translation_eps = translation_eps; o.plane_eps = plane_eps;
+  return o;
+}
+
+// the caps both calls put on the clouds and the pairs, and the part of the message that names them
+bool gicp_caps_ok(const int64_t *pt_off, int n_clouds, int n_pairs) {
+  int64_t max_cloud = 0;
+  for (int cl = 0; cl < n_clouds; cl++) max_cloud = std::max(max_cloud, pt_off[cl + 1] - pt_off[cl]);
+  return max_cloud <= SGTD_REG_MAX_POINTS && n_clouds <= SGTD_REG_MAX_CLOUDS && pt_off[n_clouds] <= SGTD_REG_MAX_TOTAL_POINTS && n_pairs <= SGTD_REG_MAX_PAIRS;
+}
+std::string gicp_caps_text(const char *call) {
+  return std::string(call) + " takes at most " + std::to_string(SGTD_REG_MAX_POINTS) + " points a cloud, " + std::to_string(SGTD_REG_MAX_CLOUDS) +
+         " clouds, " + std::to_string(SGTD_REG_MAX_TOTAL_POINTS) + " points in all";
+}
+
+// The index arrays of a call, packed into one upload.  The two calls have in common: src [n], src_off [n + 1] (the
+// pairs' source points back to back), the tiles of SGTD_REG_THREADS points of the pairs' sources (the pair, the first
+// point within its source) and of the clouds that are named (the cloud, the first point).
+struct GicpIndex {
+  std::vector<int> &up;
+  std::vector<int> tile_pair, tile_first, ctile_cloud, ctile_first;
+  size_t u_src = 0, u_soff = 0, u_tiles = 0;
+  explicit GicpIndex(std::vector<int> &up_) : up(up_) { up.clear(); }
+  size_t put(const int *p, size_t cnt) { const size_t at = up.size(); up.insert(up.end(), p, p + cnt); return at; }
+  void tiles(const int64_t *pt_off, int n_clouds, const int32_t *src, int n, const unsigned char *named, std::vector<int> *soff) {
+    soff->assign((size_t)n + 1, 0);
+    for (int k = 0; k < n; k++) {
+      const int ns = (int)(pt_off[src[k] + 1] - pt_off[src[k]]);
+      (*soff)[(size_t)k + 1] = (*soff)[(size_t)k] + ns;
+      for (int f = 0; f < ns; f += SGTD_REG_THREADS) { tile_pair.push_back(k); tile_first.push_back(f); }
+    }
+    for (int cl = 0; cl < n_clouds; cl++) {
+      if (!named[cl]) continue;
+      const int np = (int)(pt_off[cl + 1] - pt_off[cl]);
+      for (int f = 0; f < np; f += SGTD_REG_THREADS) { ctile_cloud.push_back(cl); ctile_first.push_back(f); }
+    }
+  }
+  void put_tiles() {
+    u_tiles = put(tile_pair.data(), tile_pair.size());
+    put(tile_first.data(), tile_first.size());
+    put(ctile_cloud.data(), ctile_cloud.size());
+    put(ctile_first.data(), ctile_first.size());
+  }
+};
+
+// what RegParams holds for both calls: the points, the uploaded offsets (d_pt_off) and index arrays (di), the per-point
+// covariances, the solves' state and counter, the result rows, the options; the rest is zero
+void gicp_params(RegParams &P, const GicpIndex &G, const float *points, int stride, const void *d_pt_off, const int *di, int n, size_t total_src,
+                 double *cov, void *state, void *ctl, const RegOut &out, void *ob, const RegOptionsDev &o) {
+  std::memset(&P, 0, sizeof(P));
+  P.pts = points; P.stride = stride;
+  P.pt_off = static_cast<const long long *>(d_pt_off);
+  P.src = di + G.u_src; P.src_off = di + G.u_soff;
+  P.tile_pair = di + G.u_tiles; P.tile_first = P.tile_pair + G.tile_pair.size();
+  P.ctile_cloud = P.tile_first + G.tile_first.size(); P.ctile_first = P.ctile_cloud + G.ctile_cloud.size();
+  P.n_pairs = n; P.n_tiles = (int)G.tile_pair.size(); P.n_ctiles = (int)G.ctile_cloud.size(); P.total_src = (int)total_src;
+  P.cov = cov;
+  P.st = static_cast<RegState *>(state);
+  P.unfinished = static_cast<int *>(ctl);
+  P.out_pose = out.pose(ob); P.out_fitness = out.fitness(ob); P.out_cost = out.cost(ob);
+  P.out_matched = out.matched(ob); P.out_iters = out.iters(ob); P.out_status = out.status(ob);
+  P.o = o;
+}
+
+// The solves' rounds, in groups that fall through for the pairs that have ended; the count of unfinished pairs is read
+// once per group.  Every round (one call of `round`: its launches) is one trial of every unfinished pair, so
+// max_iterations * lm_max_trials rounds are the hard bound.
+template <class Round>
+int gicp_rounds(sgtd_engine *c, const char *call, const RegParams &P, int unfinished, Round &&round) {
+  const long long bound = (long long)P.o.max_iterations * P.o.lm_max_trials;
+  long long sent = 0;
+  while (unfinished > 0) {
+    if (sent >= bound) { c->err = std::string(call) + ": the solves did not end within their limits"; return SGTD_ERR_HIP; }
+    const int group = (int)std::min<long long>(SGTD_REG_GROUP, bound - sent);
+    for (int g = 0; g < group; g++) CHK(round());
+    sent += group;
+    CHK(d2h(c, &unfinished, P.unfinished, sizeof(int)));
+    CHK(xfer_sync(c));
+  }
   return SGTD_OK;
 }
 
 int reg_run(sgtd_engine *c, const sgtd_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
             const int32_t *src, const int32_t *tgt, const double *init, int n) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
-  HIPCHK(hipSetDevice(c->cfg.device_id));
   const bool timed = c->timing;
-  c->rg_ms[0] = c->rg_ms[1] = c->rg_ms[2] = c->rg_ms[3] = 0.f;
-  if (timed)
-    for (hipEvent_t &ev : c->rg_ev)
-      if (!ev) HIPCHK(hipEventCreate(&ev));
+  LapClock &clock = c->rg_clock;
+  CHK(clock.start(c, timed));
   const size_t total = (size_t)pt_off[n_clouds];
   // what the getters need, and the tiles: of the pairs' sources, of the clouds some pair names
   c->rg_host_off.assign(pt_off, pt_off + n_clouds + 1);
   c->rg_host_named.assign((size_t)n_clouds, 0);
-  std::vector<int> &idx = c->rg_host_idx;
-  idx.assign(3 * (size_t)n + 1, 0);
-  int *h_src = idx.data(), *h_tgt = h_src + n, *h_soff = h_tgt + n;
-  std::vector<int> tile_pair, tile_first, ctile_cloud, ctile_first;
   int64_t max_tgt = 0;
   for (int k = 0; k < n; k++) {
-    h_src[k] = src[k]; h_tgt[k] = tgt[k];
     c->rg_host_named[(size_t)src[k]] = 1; c->rg_host_named[(size_t)tgt[k]] = 1;
-    const int ns = (int)(pt_off[src[k] + 1] - pt_off[src[k]]);
-    h_soff[k + 1] = h_soff[k] + ns;
-    for (int f = 0; f < ns; f += SGTD_REG_THREADS) { tile_pair.push_back(k); tile_first.push_back(f); }
     max_tgt = std::max<int64_t>(max_tgt, pt_off[tgt[k] + 1] - pt_off[tgt[k]]);
   }
-  for (int cl = 0; cl < n_clouds; cl++) {
-    if (!c->rg_host_named[(size_t)cl]) continue;
-    const int np = (int)(pt_off[cl + 1] - pt_off[cl]);
-    for (int f = 0; f < np; f += SGTD_REG_THREADS) { ctile_cloud.push_back(cl); ctile_first.push_back(f); }
-  }
+  GicpIndex G(c->rg_host_up);
+  G.tiles(pt_off, n_clouds, src, n, c->rg_host_named.data(), &c->rg_host_soff);
   if (n == 0) return SGTD_OK;      // (a run without a pair: no cloud is named, nothing comes back)
-  const int total_src = h_soff[n], n_tiles = (int)tile_pair.size(), n_ctiles = (int)ctile_cloud.size();
+  const int total_src = c->rg_host_soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
   long long slice = (long long)reg_slice_tiles() * SGTD_REG_TILE;
   auto slices_of = [&](long long len) { return (size_t)std::max<long long>((max_tgt + len - 1) / len, 1); };
   while ((size_t)total_src * slices_of(slice) > kRegPartMax) slice *= 2;
   const size_t n_slices = slices_of(slice);
 
-  // the index upload: src, tgt, src_off, tile_pair, tile_first, ctile_cloud, ctile_first
-  std::vector<int> &up = c->rg_host_up;
-  up.clear();
-  up.insert(up.end(), idx.begin(), idx.end());
-  const size_t u_tile = up.size();
-  up.insert(up.end(), tile_pair.begin(), tile_pair.end());
-  up.insert(up.end(), tile_first.begin(), tile_first.end());
-  const size_t u_ctile = up.size();
-  up.insert(up.end(), ctile_cloud.begin(), ctile_cloud.end());
-  up.insert(up.end(), ctile_first.begin(), ctile_first.end());
+  // the index upload: src, tgt, src_off, the tiles
+  G.u_src = G.put(src, (size_t)n);
+  const size_t u_tgt = G.put(tgt, (size_t)n);
+  G.u_soff = G.put(c->rg_host_soff.data(), (size_t)n + 1);
+  G.put_tiles();
   const size_t o_off = 0, o_init = o_off + relax_up((size_t)(n_clouds + 1) * sizeof(int64_t)), o_idx = o_init + relax_up((size_t)n * 12 * sizeof(double)),
-               in_bytes = o_idx + relax_up(up.size() * sizeof(int));
+               in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1);
-  const RegOut out((size_t)n);
+  const RegOut out((size_t)n, false);
   CHK(ensure(c, c->rg_in, in_bytes));
   CHK(ensure(c, c->rg_cov, std::max<size_t>(total, 1) * 9 * sizeof(double)));
   CHK(ensure(c, c->rg_part, ts * n_slices * (sizeof(double) + sizeof(int))));
@@ -5041,27 +5196,16 @@ int reg_run(sgtd_engine *c, const sgtd_register_options &o, const float *points,
   char *in = c->rg_in.as<char>();
   CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
   if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
-  CHK(h2d(c, in + o_idx, up.data(), up.size() * sizeof(int)));
+  CHK(h2d(c, in + o_idx, G.up.data(), G.up.size() * sizeof(int)));
 
   RegParams P;
-  P.pts = points; P.stride = stride;
-  P.pt_off = reinterpret_cast<const long long *>(in + o_off);
   const int *di = reinterpret_cast<const int *>(in + o_idx);
-  P.src = di; P.tgt = di + n; P.src_off = di + 2 * (size_t)n;
-  P.tile_pair = di + u_tile; P.tile_first = P.tile_pair + n_tiles;
-  P.ctile_cloud = di + u_ctile; P.ctile_first = P.ctile_cloud + n_ctiles;
-  P.n_pairs = n; P.n_tiles = n_tiles; P.n_ctiles = n_ctiles; P.total_src = (int)ts; P.slice = (int)slice;
-  P.cov = c->rg_cov.as<double>();
+  gicp_params(P, G, points, stride, in + o_off, di, n, ts, c->rg_cov.as<double>(), c->rg_state.p, c->rg_ctl.p, out, c->rg_out.p,
+              gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.max_corr_dist, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps,
+                           o.plane_eps));
+  P.tgt = di + u_tgt; P.slice = (int)slice;
   P.part_d2 = c->rg_part.as<double>(); P.part_j = reinterpret_cast<int *>(P.part_d2 + ts * n_slices);
   P.md2 = c->rg_match.as<double>(); P.M = P.md2 + ts; P.mj = reinterpret_cast<int *>(P.M + 9 * ts);
-  P.st = c->rg_state.as<RegState>();
-  P.unfinished = c->rg_ctl.as<int>();
-  void *ob = c->rg_out.p;
-  P.out_pose = out.pose(ob); P.out_fitness = out.fitness(ob); P.out_cost = out.cost(ob);
-  P.out_matched = out.matched(ob); P.out_iters = out.iters(ob); P.out_status = out.status(ob);
-  P.o.k = o.k_neighbors; P.o.max_iterations = o.max_iterations; P.o.lm_max_trials = o.lm_max_trials;
-  P.o.max2 = o.max_corr_dist * o.max_corr_dist; P.o.lambda_factor = o.lm_init_lambda_factor;
-  P.o.rotation_eps = o.rotation_eps; P.o.translation_eps = o.translation_eps; P.o.plane_eps = o.plane_eps;
 
   int unfinished = 0;
   for (int k = 0; k < n; k++)
@@ -5069,52 +5213,37 @@ int reg_run(sgtd_engine *c, const sgtd_register_options &o, const float *points,
   CHK(h2d(c, P.unfinished, &unfinished, sizeof(int)));
   hipStream_t s = c->stream;
   const dim3 sgrid((unsigned)n_tiles, (unsigned)n_slices);
-  if (timed) { HIPCHK(hipEventRecord(c->rg_ev[2], s)); HIPCHK(hipEventRecord(c->rg_ev[0], s)); }
-  if (n_ctiles) reg_cov_kernel<<<n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
-  if (timed) CHK(reg_lap(c, 0));
+  if (timed) { HIPCHK(hipEventRecord(clock.ev[2], s)); HIPCHK(hipEventRecord(clock.ev[0], s)); }
+  if (P.n_ctiles) reg_cov_kernel<<<P.n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
+  if (timed) CHK(clock.lap(c, 0));
   reg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, init ? reinterpret_cast<const double *>(in + o_init) : nullptr);
   HIPCHK(hipGetLastError());
-  // rounds in groups that fall through for the pairs that have ended; the count of unfinished pairs is read once per
-  // group.  Every round is one trial of every unfinished pair, so max_iterations * lm_max_trials rounds are the hard bound
-  const long long bound = (long long)o.max_iterations * o.lm_max_trials;
-  long long sent = 0;
-  while (unfinished > 0) {
-    if (sent >= bound) { c->err = "sgtd_register_clouds: the solves did not end within their limits"; return SGTD_ERR_HIP; }
-    const int group = (int)std::min<long long>(SGTD_REG_GROUP, bound - sent);
-    for (int g = 0; g < group; g++) {
-      reg_search_kernel<<<sgrid, SGTD_REG_THREADS, 0, s>>>(P, 0);
-      if (timed) CHK(reg_lap(c, 1));
-      reg_match_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, 0);
-      reg_lin_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
-      reg_trial_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
-      if (timed) CHK(reg_lap(c, 2));
-      HIPCHK(hipGetLastError());
-    }
-    sent += group;
-    CHK(d2h(c, &unfinished, P.unfinished, sizeof(int)));
-    CHK(xfer_sync(c));
-  }
+  CHK(gicp_rounds(c, "sgtd_register_clouds", P, unfinished, [&]() -> int {
+    reg_search_kernel<<<sgrid, SGTD_REG_THREADS, 0, s>>>(P, 0);
+    if (timed) CHK(clock.lap(c, 1));
+    reg_match_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, 0);
+    reg_lin_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
+    reg_trial_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
+    if (timed) CHK(clock.lap(c, 2));
+    HIPCHK(hipGetLastError());
+    return SGTD_OK;
+  }));
   if (n_tiles) {
     reg_search_kernel<<<sgrid, SGTD_REG_THREADS, 0, s>>>(P, 1);
-    if (timed) CHK(reg_lap(c, 1));
+    if (timed) CHK(clock.lap(c, 1));
     reg_match_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, 1);
   }
   reg_final_kernel<<<n, SGTD_REG_W, 0, s>>>(P);
   HIPCHK(hipGetLastError());
   if (timed) {
-    CHK(reg_lap(c, 2));
-    HIPCHK(hipEventElapsedTime(&c->rg_ms[3], c->rg_ev[2], c->rg_ev[1]));
+    CHK(clock.lap(c, 2));
+    CHK(clock.span(c, 2, 1, 3, false));
   }
   CHK(xfer_sync(c));
   return SGTD_OK;
 }
 
-int reg_ready(sgtd_engine *e, sgtd_engine **out) {
-  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
-  if (c->rg_n < 0) { e->err = "no registered clouds: sgtd_register_clouds has not run"; return SGTD_ERR_STATE; }
-  *out = c;
-  return SGTD_OK;
-}
+const char kNoRegistered[] = "no registered clouds: sgtd_register_clouds has not run";
 }  // namespace
 
 extern "C" {
@@ -5134,121 +5263,86 @@ void sgtd_register_tiles(int *src_tile, int *tgt_tile, int *slice) {
 
 int sgtd_register_clouds(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
                          const int32_t *src_cloud, const int32_t *tgt_cloud, const double *init_pose, int n_pairs, int device_ptrs) {
-  if (!e || n_clouds < 0 || n_pairs < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (!e || n_pairs < 0) return SGTD_ERR_INVALID;
   if (n_pairs > 0 && (!src_cloud || !tgt_cloud)) return SGTD_ERR_INVALID;
   sgtd_register_options o;
   sgtd_default_register_options(&o);
   if (opt) o = *opt;
-  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (o.k_neighbors < 3 || o.k_neighbors > SGTD_REG_MAX_K || o.max_iterations < 1 || o.lm_max_trials < 1 || o.reserved != 0 || !(o.max_corr_dist > 0.0) ||
-      !pos(o.lm_init_lambda_factor) || !pos(o.rotation_eps) || !pos(o.translation_eps) || !pos(o.plane_eps))
+  if (!gicp_options_ok(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.reserved, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps, o.plane_eps) ||
+      !(o.max_corr_dist > 0.0))
     return SGTD_ERR_INVALID;
-  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
-  for (int cl = 0; cl < n_clouds; cl++)
-    if (pt_off[cl + 1] < pt_off[cl]) return SGTD_ERR_INVALID;
+  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
   const int64_t total = pt_off[n_clouds];
-  if (total > 0 && !points) return SGTD_ERR_INVALID;
-  int64_t total_src = 0, max_cloud = 0;
+  int64_t total_src = 0;
   for (int k = 0; k < n_pairs; k++) {
     if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || tgt_cloud[k] < 0 || tgt_cloud[k] >= n_clouds) return SGTD_ERR_INVALID;
     total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
   }
   if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
-  for (int cl = 0; cl < n_clouds; cl++) max_cloud = std::max(max_cloud, pt_off[cl + 1] - pt_off[cl]);
-  if (max_cloud > SGTD_REG_MAX_POINTS || n_clouds > SGTD_REG_MAX_CLOUDS || total > SGTD_REG_MAX_TOTAL_POINTS || n_pairs > SGTD_REG_MAX_PAIRS ||
-      total_src > SGTD_REG_MAX_SOURCE_POINTS) {
-    e->err = "sgtd_register_clouds takes at most " + std::to_string(SGTD_REG_MAX_POINTS) + " points a cloud, " + std::to_string(SGTD_REG_MAX_CLOUDS) +
-             " clouds, " + std::to_string(SGTD_REG_MAX_TOTAL_POINTS) + " points in all, " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " +
-             std::to_string(SGTD_REG_MAX_SOURCE_POINTS) + " source points over the pairs";
+  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs) || total_src > SGTD_REG_MAX_SOURCE_POINTS) {
+    e->err = gicp_caps_text("sgtd_register_clouds") + ", " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " + std::to_string(SGTD_REG_MAX_SOURCE_POINTS) +
+             " source points over the pairs";
     return SGTD_ERR_UNSUPPORTED;
   }
-  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
-  PinScope pin_scope(c);
-  c->rg_n = -1;
-  const float *d_pts = points;
-  int rc = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (rc == SGTD_OK && !device_ptrs && total > 0) {
-    const size_t bytes = (size_t)total * stride_floats * sizeof(float);
-    rc = ensure(c, c->rg_pts, bytes);
-    if (rc == SGTD_OK) rc = h2d(c, c->rg_pts.p, points, bytes);
-    d_pts = c->rg_pts.as<float>();
-  }
-  if (rc == SGTD_OK) rc = reg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
-  if (rc != SGTD_OK) {
-    if (c != e) e->err = c->err;
-    return rc;
-  }
-  c->rg_n = n_pairs;
-  return SGTD_OK;
+  StageRun<int> run(e, &sgtd_engine::rg_n);
+  run.on_device([&](sgtd_engine *c) -> int {
+    const float *d_pts = nullptr;
+    CHK(points_on_device(c, c->rg_pts, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
+    return reg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
+  });
+  return run.end(n_pairs);
 }
 
 int sgtd_result_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *iterations, int32_t *status) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(reg_ready(e, &c));
-  const size_t n = (size_t)c->rg_n;
-  if (n == 0) return SGTD_OK;
-  const RegOut out(n);
-  void *ob = c->rg_out.p;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && pose) st = d2h(c, pose, out.pose(ob), n * 12 * sizeof(double));
-  if (st == SGTD_OK && fitness) st = d2h(c, fitness, out.fitness(ob), n * sizeof(double));
-  if (st == SGTD_OK && cost) st = d2h(c, cost, out.cost(ob), n * 2 * sizeof(double));
-  if (st == SGTD_OK && n_matched) st = d2h(c, n_matched, out.matched(ob), n * sizeof(int));
-  if (st == SGTD_OK && iterations) st = d2h(c, iterations, out.iters(ob), n * sizeof(int));
-  if (st == SGTD_OK && status) st = d2h(c, status, out.status(ob), n * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
-  return SGTD_OK;
+  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
+  if (c->rg_n == 0) return SGTD_OK;
+  return reg_rows_out(e, c, RegOut((size_t)c->rg_n, false), c->rg_out.p, pose, fitness, cost, n_matched, nullptr, iterations, status);
 }
 
 int sgtd_result_register_covariances(sgtd_handle e, int cloud, double *cov, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(reg_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
   if (cloud < 0 || (size_t)cloud >= c->rg_host_named.size()) return SGTD_ERR_INVALID;
   const int64_t first = c->rg_host_off[(size_t)cloud];
   const int64_t need = c->rg_host_named[(size_t)cloud] ? c->rg_host_off[(size_t)cloud + 1] - first : 0;
   if (n) *n = need;
-  const size_t m = cov ? (size_t)std::min(need, capacity) : 0;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && m) st = d2h(c, cov, c->rg_cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  const size_t m = (size_t)std::min(need, capacity);
+  CopyOut out(e, c);
+  out.get(cov, c->rg_cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  CHK(out.finish());
   return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_result_register_matches(sgtd_handle e, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(reg_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
   if (pair < 0 || pair >= c->rg_n) return SGTD_ERR_INVALID;
-  const int *soff = c->rg_host_idx.data() + 2 * (size_t)c->rg_n;
+  const int *soff = c->rg_host_soff.data();
   const int64_t first = soff[pair], need = soff[pair + 1] - first;
   const size_t ts = (size_t)std::max(soff[c->rg_n], 1);
   if (n) *n = need;
   const size_t m = (size_t)std::min(need, capacity);
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
   const double *md2 = c->rg_match.as<double>();
   const int *mj = reinterpret_cast<const int *>(md2 + 10 * ts);
-  if (st == SGTD_OK && m && tgt_index) st = d2h(c, tgt_index, mj + first, m * sizeof(int));
-  if (st == SGTD_OK && m && d2) st = d2h(c, d2, md2 + first, m * sizeof(double));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CopyOut out(e, c);
+  out.get(tgt_index, mj + first, m * sizeof(int));
+  out.get(d2, md2 + first, m * sizeof(double));
+  CHK(out.finish());
   return need > capacity && (tgt_index || d2) ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(reg_ready(e, &c));
-  if (ms_cov) *ms_cov = c->rg_ms[0];
-  if (ms_search) *ms_search = c->rg_ms[1];
-  if (ms_rest) *ms_rest = c->rg_ms[2];
-  if (ms_total) *ms_total = c->rg_ms[3];
+  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
+  if (ms_cov) *ms_cov = c->rg_clock.ms[0];
+  if (ms_search) *ms_search = c->rg_clock.ms[1];
+  if (ms_rest) *ms_rest = c->rg_clock.ms[2];
+  if (ms_total) *ms_total = c->rg_clock.ms[3];
   return SGTD_OK;
 }
 
@@ -5258,41 +5352,19 @@ int sgtd_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float
 namespace {
 static_assert(SGTD_VREG_W == SGTD_VREG_SUM_W, "the voxel kernels' sizes are the header's");
 
-int vreg_bits(u64 v) { int b = 0; while (v) { b++; v >>= 1; } return std::max(b, 1); }
-
-struct VregOut {      // VR_OUT: RegOut's rows, then n_corr [n] in i32
-  RegOut r;
-  explicit VregOut(size_t n) : r(n) {}
-  size_t bytes() const { return r.bytes() + r.n * sizeof(int); }
-  int *corr(void *p) const { return r.status(p) + r.n; }
-};
-
-int vreg_lap(sgtd_engine *e, int kind) {
-  HIPCHK(hipEventRecord(e->vr_ev[1], e->stream));
-  HIPCHK(hipEventSynchronize(e->vr_ev[1]));
-  float t = 0.f;
-  HIPCHK(hipEventElapsedTime(&t, e->vr_ev[0], e->vr_ev[1]));
-  e->vr_ms[kind] += t;
-  HIPCHK(hipEventRecord(e->vr_ev[0], e->stream));
-  return SGTD_OK;
-}
-
 int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
              const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src, const int32_t *tgt,
              const double *init, int n) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
-  HIPCHK(hipSetDevice(c->cfg.device_id));
   const bool timed = c->timing;
-  for (float &v : c->vr_ms) v = 0.f;
-  if (timed)
-    for (hipEvent_t &ev : c->vr_ev)
-      if (!ev) HIPCHK(hipEventCreate(&ev));
+  LapClock &clock = c->vr_clock;
+  CHK(clock.start(c, timed));
   const size_t total = (size_t)pt_off[n_clouds];
   const int mode = o.neighbor_mode, n_members = n_maps ? map_off[n_maps] : 0;
   c->vr_mode = mode;
   // the members' points back to back, the tiles: of the pairs' sources, of the clouds that are a source or a member
   std::vector<unsigned char> named((size_t)n_clouds, 0);
-  std::vector<int> mem_map((size_t)n_members), mem_pt_off((size_t)n_members + 1, 0), tile_pair, tile_first, ctile_cloud, ctile_first;
+  std::vector<int> mem_map((size_t)n_members), mem_pt_off((size_t)n_members + 1, 0);
   for (int m = 0; m < n_maps; m++)
     for (int j = map_off[m]; j < map_off[m + 1]; j++) {
       mem_map[(size_t)j] = m;
@@ -5300,34 +5372,23 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
       mem_pt_off[(size_t)j + 1] = mem_pt_off[(size_t)j] + (int)(pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]]);
     }
   const long long MP = mem_pt_off[(size_t)n_members];
+  for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
   std::vector<int> &soff = c->vr_host_soff;
-  soff.assign((size_t)n + 1, 0);
-  for (int k = 0; k < n; k++) {
-    named[(size_t)src[k]] = 1;
-    const int ns = (int)(pt_off[src[k] + 1] - pt_off[src[k]]);
-    soff[(size_t)k + 1] = soff[(size_t)k] + ns;
-    for (int f = 0; f < ns; f += SGTD_REG_THREADS) { tile_pair.push_back(k); tile_first.push_back(f); }
-  }
-  for (int cl = 0; cl < n_clouds; cl++) {
-    if (!named[(size_t)cl]) continue;
-    const int np = (int)(pt_off[cl + 1] - pt_off[cl]);
-    for (int f = 0; f < np; f += SGTD_REG_THREADS) { ctile_cloud.push_back(cl); ctile_first.push_back(f); }
-  }
-  const int total_src = soff[(size_t)n], n_tiles = (int)tile_pair.size(), n_ctiles = (int)ctile_cloud.size();
+  GicpIndex G(c->vr_host_up);
+  G.tiles(pt_off, n_clouds, src, n, named.data(), &soff);
+  const int total_src = soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
 
   // the index upload: src, tgt_map, src_off, map_off, map_cloud, mem_map, mem_pt_off, the tiles
-  std::vector<int> &up = c->vr_host_up;
-  up.clear();
-  auto put = [&](const int *p, size_t cnt) { const size_t at = up.size(); up.insert(up.end(), p, p + cnt); return at; };
-  const size_t u_src = put(src, (size_t)n), u_tgt = put(tgt, (size_t)n), u_soff = put(soff.data(), soff.size());
-  const size_t u_moff = n_maps ? put(map_off, (size_t)n_maps + 1) : up.size(), u_mcl = put(map_cloud, (size_t)n_members);
-  const size_t u_mmap = put(mem_map.data(), mem_map.size()), u_mpo = put(mem_pt_off.data(), mem_pt_off.size());
-  const size_t u_tp = put(tile_pair.data(), tile_pair.size()), u_tf = put(tile_first.data(), tile_first.size());
-  const size_t u_cc = put(ctile_cloud.data(), ctile_cloud.size()), u_cf = put(ctile_first.data(), ctile_first.size());
+  G.u_src = G.put(src, (size_t)n);
+  const size_t u_tgt = G.put(tgt, (size_t)n);
+  G.u_soff = G.put(soff.data(), soff.size());
+  const size_t u_moff = n_maps ? G.put(map_off, (size_t)n_maps + 1) : G.up.size(), u_mcl = G.put(map_cloud, (size_t)n_members);
+  const size_t u_mmap = G.put(mem_map.data(), mem_map.size()), u_mpo = G.put(mem_pt_off.data(), mem_pt_off.size());
+  G.put_tiles();
   const size_t o_off = 0, o_init = o_off + relax_up((size_t)(n_clouds + 1) * sizeof(int64_t)), o_pose = o_init + relax_up((size_t)n * 12 * sizeof(double)),
-               o_idx = o_pose + relax_up((size_t)n_members * 12 * sizeof(double)), in_bytes = o_idx + relax_up(up.size() * sizeof(int));
+               o_idx = o_pose + relax_up((size_t)n_members * 12 * sizeof(double)), in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1), mp = (size_t)std::max<long long>(MP, 1), nn = (size_t)std::max(n, 1);
-  const VregOut out((size_t)n);
+  const RegOut out((size_t)n, true);
   auto *B = c->vr;
   auto buf = [&](int which, size_t bytes) { return ensure(c, B[which], std::max<size_t>(bytes, 16)); };
   CHK(buf(sgtd_engine::VR_IN, in_bytes));
@@ -5351,25 +5412,14 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
   if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
   if (map_pose) CHK(h2d(c, in + o_pose, map_pose, (size_t)n_members * 12 * sizeof(double)));
-  CHK(h2d(c, in + o_idx, up.data(), up.size() * sizeof(int)));
+  CHK(h2d(c, in + o_idx, G.up.data(), G.up.size() * sizeof(int)));
 
   RegParams P;
-  std::memset(&P, 0, sizeof(P));
-  P.pts = points; P.stride = stride;
-  P.pt_off = reinterpret_cast<const long long *>(in + o_off);
   const int *di = reinterpret_cast<const int *>(in + o_idx);
-  P.src = di + u_src; P.src_off = di + u_soff;
-  P.tile_pair = di + u_tp; P.tile_first = di + u_tf; P.ctile_cloud = di + u_cc; P.ctile_first = di + u_cf;
-  P.n_pairs = n; P.n_tiles = n_tiles; P.n_ctiles = n_ctiles; P.total_src = (int)ts;
-  P.cov = B[sgtd_engine::VR_COV].as<double>();
-  P.st = B[sgtd_engine::VR_STATE].as<RegState>();
-  P.unfinished = B[sgtd_engine::VR_CTL].as<int>();
   void *ob = B[sgtd_engine::VR_OUT].p;
-  P.out_pose = out.r.pose(ob); P.out_fitness = out.r.fitness(ob); P.out_cost = out.r.cost(ob);
-  P.out_matched = out.r.matched(ob); P.out_iters = out.r.iters(ob); P.out_status = out.r.status(ob);
-  P.o.k = o.k_neighbors; P.o.max_iterations = o.max_iterations; P.o.lm_max_trials = o.lm_max_trials;
-  P.o.max2 = std::numeric_limits<double>::infinity(); P.o.lambda_factor = o.lm_init_lambda_factor;
-  P.o.rotation_eps = o.rotation_eps; P.o.translation_eps = o.translation_eps; P.o.plane_eps = o.plane_eps;
+  gicp_params(P, G, points, stride, in + o_off, di, n, ts, B[sgtd_engine::VR_COV].as<double>(), B[sgtd_engine::VR_STATE].p, B[sgtd_engine::VR_CTL].p, out, ob,
+              gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, std::numeric_limits<double>::infinity(), o.lm_init_lambda_factor, o.rotation_eps,
+                           o.translation_eps, o.plane_eps));
   VregParams V;
   std::memset(&V, 0, sizeof(V));
   V.map_off = di + u_moff; V.map_cloud = di + u_mcl; V.mem_map = di + u_mmap; V.mem_pt_off = di + u_mpo;
@@ -5381,10 +5431,10 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   V.out_corr = out.corr(ob);
 
   hipStream_t s = c->stream;
-  if (timed) { HIPCHK(hipEventRecord(c->vr_ev[2], s)); HIPCHK(hipEventRecord(c->vr_ev[0], s)); }
-  if (n_ctiles) reg_cov_kernel<<<n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
+  if (timed) { HIPCHK(hipEventRecord(clock.ev[2], s)); HIPCHK(hipEventRecord(clock.ev[0], s)); }
+  if (P.n_ctiles) reg_cov_kernel<<<P.n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
   HIPCHK(hipGetLastError());
-  if (timed) CHK(vreg_lap(c, 0));
+  if (timed) CHK(clock.lap(c, 0));
 
   // the maps: keys, the stable sort, the voxels' heads, the Gaussians, the maps' ranges
   u32 n_vox = 0;
@@ -5397,12 +5447,9 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
     const int gp = grid_for(MP, 256);
     vreg_keys_kernel<<<gp, 256, 0, s>>>(P, V, kin, vin);
     HIPCHK(hipGetLastError());
-    CHK(radix_sort_pairs<u64>(c, kin, kout, vin, vout, MP, 48 + vreg_bits((u64)n_maps), true));
+    CHK(radix_sort_pairs<u64>(c, kin, kout, vin, vout, MP, 48 + key_bits((u64)n_maps), true));
     HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(u32), s));
-    scan_heads_kernel<<<grid_for(MP + 1, 256), 256, 0, s>>>(kin, MP, (u64)n_maps << 48, flags, counts);
-    HIPCHK(hipGetLastError());
-    CHK(device_scan(c, flags, excl, MP + 1));
-    scan_voxels_kernel<<<gp, 256, 0, s>>>(kin, flags, excl, MP, counts, vkey, vstart);
+    CHK(voxel_runs(c, kin, MP, (u64)n_maps << 48, flags, excl, counts, vkey, vstart));
     HIPCHK(hipGetLastError());
     CHK(d2h(c, &n_vox, excl + MP, sizeof(u32)));
     CHK(xfer_sync(c));
@@ -5418,9 +5465,9 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   c->vr_host_map_vox.assign((size_t)n_maps + 1, 0);
   CHK(d2h(c, c->vr_host_map_vox.data(), V.map_vox, ((size_t)n_maps + 1) * sizeof(u32)));
   CHK(xfer_sync(c));
-  if (timed) CHK(vreg_lap(c, 1));
+  if (timed) CHK(clock.lap(c, 1));
   if (n == 0) {
-    if (timed) HIPCHK(hipEventElapsedTime(&c->vr_ms[4], c->vr_ev[2], c->vr_ev[1]));
+    if (timed) CHK(clock.span(c, 2, 1, 4, false));
     return SGTD_OK;
   }
 
@@ -5431,45 +5478,31 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   CHK(h2d(c, P.unfinished, &unfinished, sizeof(int)));
   vreg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, V, init ? reinterpret_cast<const double *>(in + o_init) : nullptr);
   HIPCHK(hipGetLastError());
-  // rounds in groups, as sgtd_register_clouds' host loop: every round is one trial of every unfinished pair
-  const long long bound = (long long)o.max_iterations * o.lm_max_trials;
-  long long sent = 0;
-  while (unfinished > 0) {
-    if (sent >= bound) { c->err = "sgtd_register_voxels: the solves did not end within their limits"; return SGTD_ERR_HIP; }
-    const int group = (int)std::min<long long>(SGTD_REG_GROUP, bound - sent);
-    for (int g = 0; g < group; g++) {
-      if (timed) CHK(vreg_lap(c, 3));
-      vreg_corr_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, V, 0);
-      if (timed) CHK(vreg_lap(c, 2));
-      vreg_lin_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
-      vreg_trial_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
-      HIPCHK(hipGetLastError());
-    }
-    sent += group;
-    CHK(d2h(c, &unfinished, P.unfinished, sizeof(int)));
-    CHK(xfer_sync(c));
-  }
-  if (timed) CHK(vreg_lap(c, 3));
+  CHK(gicp_rounds(c, "sgtd_register_voxels", P, unfinished, [&]() -> int {
+    if (timed) CHK(clock.lap(c, 3));
+    vreg_corr_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, V, 0);
+    if (timed) CHK(clock.lap(c, 2));
+    vreg_lin_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
+    vreg_trial_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
+    HIPCHK(hipGetLastError());
+    return SGTD_OK;
+  }));
+  if (timed) CHK(clock.lap(c, 3));
   if (n_tiles) {
     vreg_corr_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, V, 1);
-    if (timed) CHK(vreg_lap(c, 2));
+    if (timed) CHK(clock.lap(c, 2));
   }
   vreg_final_kernel<<<n, SGTD_REG_W, 0, s>>>(P, V);
   HIPCHK(hipGetLastError());
   if (timed) {
-    CHK(vreg_lap(c, 3));
-    HIPCHK(hipEventElapsedTime(&c->vr_ms[4], c->vr_ev[2], c->vr_ev[1]));
+    CHK(clock.lap(c, 3));
+    CHK(clock.span(c, 2, 1, 4, false));
   }
   CHK(xfer_sync(c));
   return SGTD_OK;
 }
 
-int vreg_ready(sgtd_engine *e, sgtd_engine **out) {
-  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
-  if (c->vr_n < 0) { e->err = "no voxel registration: sgtd_register_voxels has not run"; return SGTD_ERR_STATE; }
-  *out = c;
-  return SGTD_OK;
-}
+const char kNoVoxelRegistered[] = "no voxel registration: sgtd_register_voxels has not run";
 }  // namespace
 
 extern "C" {
@@ -5485,28 +5518,23 @@ void sgtd_default_voxel_register_options(sgtd_voxel_register_options *o) {
 int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
                          const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src_cloud,
                          const int32_t *tgt_map, const double *init_pose, int n_pairs, int device_ptrs) {
-  if (!e || n_clouds < 0 || n_pairs < 0 || n_maps < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (!e || n_pairs < 0 || n_maps < 0) return SGTD_ERR_INVALID;
   if (n_pairs > 0 && (!src_cloud || !tgt_map)) return SGTD_ERR_INVALID;
   if (n_maps > 0 && !map_off) return SGTD_ERR_INVALID;
   sgtd_voxel_register_options o;
   sgtd_default_voxel_register_options(&o);
   if (opt) o = *opt;
-  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
-  if (o.k_neighbors < 3 || o.k_neighbors > SGTD_REG_MAX_K || o.max_iterations < 1 || o.lm_max_trials < 1 || o.reserved != 0 || !pos(o.voxel_resolution) ||
-      (o.neighbor_mode != 1 && o.neighbor_mode != 7 && o.neighbor_mode != 27) || !pos(o.lm_init_lambda_factor) || !pos(o.rotation_eps) ||
-      !pos(o.translation_eps) || !pos(o.plane_eps))
+  if (!gicp_options_ok(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.reserved, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps, o.plane_eps) ||
+      !(std::isfinite(o.voxel_resolution) && o.voxel_resolution > 0.0) || (o.neighbor_mode != 1 && o.neighbor_mode != 7 && o.neighbor_mode != 27))
     return SGTD_ERR_INVALID;
-  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
-  for (int cl = 0; cl < n_clouds; cl++)
-    if (pt_off[cl + 1] < pt_off[cl]) return SGTD_ERR_INVALID;
+  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
   const int64_t total = pt_off[n_clouds];
-  if (total > 0 && !points) return SGTD_ERR_INVALID;
   if (n_maps > 0 && map_off[0] != 0) return SGTD_ERR_INVALID;
   for (int m = 0; m < n_maps; m++)
     if (map_off[m + 1] < map_off[m]) return SGTD_ERR_INVALID;
   const int n_members = n_maps ? map_off[n_maps] : 0;
   if (n_members > 0 && !map_cloud) return SGTD_ERR_INVALID;
-  int64_t total_src = 0, max_cloud = 0, member_pts = 0;
+  int64_t total_src = 0, member_pts = 0;
   for (int j = 0; j < n_members; j++) {
     if (map_cloud[j] < 0 || map_cloud[j] >= n_clouds) return SGTD_ERR_INVALID;
     member_pts += pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]];
@@ -5517,10 +5545,8 @@ int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, 
   }
   if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
   if (map_pose && !relax_finite(map_pose, (size_t)n_members * 12)) return SGTD_ERR_INVALID;
-  for (int cl = 0; cl < n_clouds; cl++) max_cloud = std::max(max_cloud, pt_off[cl + 1] - pt_off[cl]);
-  if (max_cloud > SGTD_REG_MAX_POINTS || n_clouds > SGTD_REG_MAX_CLOUDS || total > SGTD_REG_MAX_TOTAL_POINTS || n_pairs > SGTD_REG_MAX_PAIRS) {
-    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_REG_MAX_POINTS) + " points a cloud, " + std::to_string(SGTD_REG_MAX_CLOUDS) +
-             " clouds, " + std::to_string(SGTD_REG_MAX_TOTAL_POINTS) + " points in all and " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs";
+  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs)) {
+    e->err = gicp_caps_text("sgtd_register_voxels") + " and " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs";
     return SGTD_ERR_UNSUPPORTED;
   }
   if (n_maps > SGTD_VREG_MAX_MAPS) {
@@ -5536,70 +5562,42 @@ int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, 
              " for the source points over the pairs times neighbor_mode (SGTD_VREG_MAX_CORR)";
     return SGTD_ERR_UNSUPPORTED;
   }
-  sgtd_engine *c = e->grp ? multi::device_handle(e, 0) : e;
-  PinScope pin_scope(c);
-  c->vr_n = -1;
-  const float *d_pts = points;
-  int rc = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (rc == SGTD_OK && !device_ptrs && total > 0) {
-    const size_t bytes = (size_t)total * stride_floats * sizeof(float);
-    rc = ensure(c, c->vr[sgtd_engine::VR_PTS], bytes);
-    if (rc == SGTD_OK) rc = h2d(c, c->vr[sgtd_engine::VR_PTS].p, points, bytes);
-    d_pts = c->vr[sgtd_engine::VR_PTS].as<float>();
-  }
-  if (rc == SGTD_OK)
-    rc = vreg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
-  if (rc != SGTD_OK) {
-    if (c != e) e->err = c->err;
-    return rc;
-  }
-  c->vr_n = n_pairs;
-  return SGTD_OK;
+  StageRun<int> run(e, &sgtd_engine::vr_n);
+  run.on_device([&](sgtd_engine *c) -> int {
+    const float *d_pts = nullptr;
+    CHK(points_on_device(c, c->vr[sgtd_engine::VR_PTS], points, (size_t)total * stride_floats, device_ptrs, &d_pts));
+    return vreg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
+  });
+  return run.end(n_pairs);
 }
 
 int sgtd_result_voxel_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *n_corr, int32_t *iterations,
                                  int32_t *status) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(vreg_ready(e, &c));
-  const size_t n = (size_t)c->vr_n;
-  if (n == 0) return SGTD_OK;
-  const VregOut out(n);
-  void *ob = c->vr[sgtd_engine::VR_OUT].p;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && pose) st = d2h(c, pose, out.r.pose(ob), n * 12 * sizeof(double));
-  if (st == SGTD_OK && fitness) st = d2h(c, fitness, out.r.fitness(ob), n * sizeof(double));
-  if (st == SGTD_OK && cost) st = d2h(c, cost, out.r.cost(ob), n * 2 * sizeof(double));
-  if (st == SGTD_OK && n_matched) st = d2h(c, n_matched, out.r.matched(ob), n * sizeof(int));
-  if (st == SGTD_OK && n_corr) st = d2h(c, n_corr, out.corr(ob), n * sizeof(int));
-  if (st == SGTD_OK && iterations) st = d2h(c, iterations, out.r.iters(ob), n * sizeof(int));
-  if (st == SGTD_OK && status) st = d2h(c, status, out.r.status(ob), n * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
-  return SGTD_OK;
+  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
+  if (c->vr_n == 0) return SGTD_OK;
+  return reg_rows_out(e, c, RegOut((size_t)c->vr_n, true), c->vr[sgtd_engine::VR_OUT].p, pose, fitness, cost, n_matched, n_corr, iterations, status);
 }
 
 int sgtd_result_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(vreg_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
   if (map < 0 || (size_t)map + 1 >= c->vr_host_map_vox.size()) return SGTD_ERR_INVALID;
   const int64_t first = c->vr_host_map_vox[(size_t)map], need = (int64_t)c->vr_host_map_vox[(size_t)map + 1] - first;
   if (n) *n = need;
   const bool any = coord || n_points || mean || cov;
   const size_t m = any ? (size_t)std::min(need, capacity) : 0;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
   std::vector<u64> keys(coord ? m : 0);
   std::vector<u32> starts(n_points && m ? m + 1 : 0);
   auto *B = c->vr;
-  if (st == SGTD_OK && m && coord) st = d2h(c, keys.data(), B[sgtd_engine::VR_VKEY].as<u64>() + first, m * sizeof(u64));
-  if (st == SGTD_OK && m && n_points) st = d2h(c, starts.data(), B[sgtd_engine::VR_VSTART].as<u32>() + first, (m + 1) * sizeof(u32));
-  if (st == SGTD_OK && m && mean) st = d2h(c, mean, B[sgtd_engine::VR_MEAN].as<double>() + (size_t)first * 3, m * 3 * sizeof(double));
-  if (st == SGTD_OK && m && cov) st = d2h(c, cov, B[sgtd_engine::VR_VCOV].as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CopyOut out(e, c);
+  out.get(keys.data(), B[sgtd_engine::VR_VKEY].as<u64>() + first, keys.size() * sizeof(u64));
+  out.get(starts.data(), B[sgtd_engine::VR_VSTART].as<u32>() + first, starts.size() * sizeof(u32));
+  out.get(mean, B[sgtd_engine::VR_MEAN].as<double>() + (size_t)first * 3, m * 3 * sizeof(double));
+  out.get(cov, B[sgtd_engine::VR_VCOV].as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  CHK(out.finish());
   for (size_t v = 0; v < keys.size(); v++)
     for (int a = 0; a < 3; a++) coord[v * 3 + a] = (int32_t)((keys[v] >> (32 - 16 * a)) & 0xFFFFu) - 32768;
   for (size_t v = 0; v + 1 < starts.size(); v++) n_points[v] = (int32_t)(starts[v + 1] - starts[v]);
@@ -5609,29 +5607,26 @@ int sgtd_result_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_poi
 int sgtd_result_voxel_matches(sgtd_handle e, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(vreg_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
   if (pair < 0 || pair >= c->vr_n) return SGTD_ERR_INVALID;
   const int64_t first = (int64_t)c->vr_host_soff[(size_t)pair] * c->vr_mode;
   const int64_t need = (int64_t)c->vr_host_soff[(size_t)pair + 1] * c->vr_mode - first;
   if (n) *n = need;
-  const size_t m = voxel ? (size_t)std::min(need, capacity) : 0;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && m) st = d2h(c, voxel, c->vr[sgtd_engine::VR_VID].as<int>() + first, m * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CopyOut out(e, c);
+  out.get(voxel, c->vr[sgtd_engine::VR_VID].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
+  CHK(out.finish());
   return need > capacity && voxel ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(vreg_ready(e, &c));
-  if (ms_cov) *ms_cov = c->vr_ms[0];
-  if (ms_map) *ms_map = c->vr_ms[1];
-  if (ms_corr) *ms_corr = c->vr_ms[2];
-  if (ms_rest) *ms_rest = c->vr_ms[3];
-  if (ms_total) *ms_total = c->vr_ms[4];
+  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
+  if (ms_cov) *ms_cov = c->vr_clock.ms[0];
+  if (ms_map) *ms_map = c->vr_clock.ms[1];
+  if (ms_corr) *ms_corr = c->vr_clock.ms[2];
+  if (ms_rest) *ms_rest = c->vr_clock.ms[3];
+  if (ms_total) *ms_total = c->vr_clock.ms[4];
   return SGTD_OK;
 }
 
@@ -5639,9 +5634,6 @@ int sgtd_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, fl
 
 // ---- sgtd_scan_keypoints: labelled scans to keypoints on the device (scan_kernels.hip.h) ----
 namespace {
-
-int scan_bits(u64 v) { int b = 0; while (v) { b++; v >>= 1; } return std::max(b, 1); }
-
 // the ring envelope: some n <= SGTD_SCAN_MAX_CELLS has every increment start_r - s * delta_r > 0 for s <= n and the
 // increments sum to at least max_range - min_range
 bool scan_rings_fit(const sgtd_scan_config &c) {
@@ -5661,7 +5653,6 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
 
 int scan_run(sgtd_engine *e, const ScanCfgDev &C, const float *points, int stride, const uint32_t *labels, const int64_t *pt_off, int S,
              int device_ptrs) {
-  HIPCHK(hipSetDevice(e->cfg.device_id));
   const long long P = pt_off[S];
   if (device_ptrs || S == 0 || P == 0) return scan_device(e, C, points, stride, labels, pt_off, S);
   auto buf = [&](int k, size_t bytes) { return ensure(e, e->sk[k], std::max<size_t>(bytes, 16)); };
@@ -5749,7 +5740,7 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
   u32 *vin = B[sgtd_engine::SK_VAL_A].as<u32>(), *vout = B[sgtd_engine::SK_VAL_B].as<u32>();
   scan_keys_kernel<<<gp, 256, 0, st>>>(PP.sc_of, d_lab, PP.r, PP.pitch, PP.azimuth, grid, range, bounds, C, P, kin, vin);
   HIPCHK(hipGetLastError());
-  CHK(radix_sort_pairs<u64>(e, kin, kout, vin, vout, P, 38 + scan_bits((u64)S), false));
+  CHK(radix_sort_pairs<u64>(e, kin, kout, vin, vout, P, 38 + key_bits((u64)S), false));
 
   // voxels, links, components
   u32 *flags = B[sgtd_engine::SK_FLAGS].as<u32>(), *excl = B[sgtd_engine::SK_EXCL].as<u32>(), *counts = B[sgtd_engine::SK_COUNTS].as<u32>();
@@ -5763,10 +5754,7 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
   HIPCHK(hipMemsetAsync(ccount, 0, np * sizeof(u32), st));
   HIPCHK(hipMemsetAsync(cmin, 0xFF, np * sizeof(u32), st));
   HIPCHK(hipMemsetAsync(B[sgtd_engine::SK_CL_OF_ROOT].p, 0xFF, np * sizeof(u32), st));
-  scan_heads_kernel<<<grid_for(P + 1, 256), 256, 0, st>>>(kin, P, (u64)S << 38, flags, counts);
-  HIPCHK(hipGetLastError());
-  CHK(device_scan(e, flags, excl, P + 1));
-  scan_voxels_kernel<<<gp, 256, 0, st>>>(kin, flags, excl, P, counts, vkey, vstart);
+  CHK(voxel_runs(e, kin, P, (u64)S << 38, flags, excl, counts, vkey, vstart));
   scan_links_kernel<<<gp, 256, 0, st>>>(vkey, n_vox_p, grid, nbr, nbr_cnt, parent);
   HIPCHK(hipGetLastError());
   bool settled = false;
@@ -5789,7 +5777,7 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
   u32 *cvin = B[sgtd_engine::SK_CVAL_A].as<u32>(), *cvout = B[sgtd_engine::SK_CVAL_B].as<u32>();
   scan_cluster_keys_kernel<<<gp, 256, 0, st>>>(n_vox_p, vkey, parent, ccount, cmin, grid, C, ckin, cvin);
   HIPCHK(hipGetLastError());
-  CHK(radix_sort_pairs<u64>(e, ckin, ckout, cvin, cvout, P, 37 + scan_bits((u64)S), false, n_vox_p));
+  CHK(radix_sort_pairs<u64>(e, ckin, ckout, cvin, cvout, P, 37 + key_bits((u64)S), false, n_vox_p));
   long long *d_kp_off = B[sgtd_engine::SK_KP_OFF].as<long long>();
   scan_offsets_kernel<<<grid_for(S + 1, 256), 256, 0, st>>>(ckin, n_vox_p, S, d_kp_off);
   HIPCHK(hipGetLastError());
@@ -5815,7 +5803,7 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
                                                  B[sgtd_engine::SK_CLUSTER].as<int>());
   HIPCHK(hipGetLastError());
   if (K > 0) {
-    CHK(radix_sort_pairs<u32>(e, pkin, pkout, pvin, pvout, P, scan_bits((u64)K), false));
+    CHK(radix_sort_pairs<u32>(e, pkin, pkout, pvin, pvout, P, key_bits((u64)K), false));
     CHK(device_scan(e, kcount, cstart, K));
     float *xyz = B[sgtd_engine::SK_XYZ].as<float>();
     scan_sum_wave_kernel<<<grid_for(K, 4), 256, 0, st>>>(d_pts, stride, pvin, cstart, kcount, (u32)K, xyz);
@@ -5826,14 +5814,18 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
   return xfer_sync(e);
 }
 
-sgtd_engine *scan_engine(sgtd_engine *e) { return e->grp ? multi::device_handle(e, 0) : e; }
-
-int scan_ready(sgtd_engine *e, sgtd_engine **out) {
-  sgtd_engine *c = scan_engine(e);
-  if (c->sk_n < 0) { e->err = "no scan keypoints: sgtd_scan_keypoints has not run"; return SGTD_ERR_STATE; }
-  *out = c;
-  return SGTD_OK;
+// the first m keypoints a stage left on its home engine c, to those of the caller's arrays that are given
+int keypoints_out(sgtd_engine *e, sgtd_engine *c, const DevBuf &xyz_dev, const DevBuf &label_dev, const DevBuf &n_points_dev, size_t m, float *xyz,
+                  uint32_t *label, int32_t *n_points) {
+  CopyOut out(e, c);
+  out.get(xyz, xyz_dev.p, m * 3 * sizeof(float));
+  out.get(label, label_dev.p, m * sizeof(u32));
+  out.get(n_points, n_points_dev.p, m * sizeof(int));
+  return out.finish();
 }
+
+const char kNoScan[] = "no scan keypoints: sgtd_scan_keypoints has not run";
+const char kNoLocalMap[] = "no local-map keypoints: sgtd_local_map_keypoints has not run";
 
 ScanCfgDev scan_cfg_dev(const sgtd_scan_config &c, int n_scans) {
   ScanCfgDev C;
@@ -5844,33 +5836,15 @@ ScanCfgDev scan_cfg_dev(const sgtd_scan_config &c, int n_scans) {
 }
 
 // ---- sgtd_local_map_keypoints (local_map_kernels.hip.h) ----
-int local_map_ready(sgtd_engine *e, sgtd_engine **out) {
-  sgtd_engine *c = scan_engine(e);
-  if (c->lm_n < 0) { e->err = "no local-map keypoints: sgtd_local_map_keypoints has not run"; return SGTD_ERR_STATE; }
-  *out = c;
-  return SGTD_OK;
-}
-
-// milliseconds between two recorded events of the call's stream, added to *ms (the stream is waited for)
-int lm_lap(sgtd_engine *e, int a, int b, float *ms) {
-  HIPCHK(hipEventSynchronize(e->lm_ev[b]));
-  float t = 0.f;
-  HIPCHK(hipEventElapsedTime(&t, e->lm_ev[a], e->lm_ev[b]));
-  *ms += t;
-  return SGTD_OK;
-}
 
 int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_map_options &opt, const float *points, int stride,
                   const uint32_t *labels, const int64_t *pt_off, const float *pose12, int S, const int32_t *anchors, int A, int device_ptrs) {
-  HIPCHK(hipSetDevice(e->cfg.device_id));
   auto buf = [&](int k, size_t bytes, bool keep = false) { return ensure(e, e->lm[k], std::max<size_t>(bytes, 16), keep); };
   auto *B = e->lm;
   const hipStream_t st = e->stream;
   const bool timed = e->timing;
-  if (timed)
-    for (hipEvent_t &ev : e->lm_ev)
-      if (!ev) HIPCHK(hipEventCreate(&ev));
-  e->lm_ms[0] = e->lm_ms[1] = e->lm_ms[2] = 0.f;
+  LapClock &clock = e->lm_clock;      // (ms: members, gather, scan passes; the events bracket the work they measure)
+  CHK(clock.start(e, timed));
   e->lm_kp_off.assign((size_t)A + 1, 0);
   e->lm_mem_off.assign((size_t)A + 1, 0);
   e->lm_merged.assign((size_t)A, 0);
@@ -5897,16 +5871,16 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
   const long long *d_off = B[sgtd_engine::LM_OFF].as<long long>();
   const int *d_anch = B[sgtd_engine::LM_ANCH].as<int>();
   const double rr = opt.radius * opt.radius;
-  if (timed) HIPCHK(hipEventRecord(e->lm_ev[0], st));
+  if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
   lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, nullptr, nullptr, B[sgtd_engine::LM_COUNT].as<int>(),
                                                    B[sgtd_engine::LM_MERGED].as<long long>());
   HIPCHK(hipGetLastError());
-  if (timed) HIPCHK(hipEventRecord(e->lm_ev[1], st));
+  if (timed) HIPCHK(hipEventRecord(clock.ev[1], st));
   std::vector<int32_t> count((size_t)A);
   CHK(d2h(e, count.data(), B[sgtd_engine::LM_COUNT].p, (size_t)A * sizeof(int)));
   CHK(d2h(e, e->lm_merged.data(), B[sgtd_engine::LM_MERGED].p, (size_t)A * sizeof(long long)));
   CHK(xfer_sync(e));
-  if (timed) CHK(lm_lap(e, 0, 1, &e->lm_ms[0]));
+  if (timed) CHK(clock.span(e, 0, 1, 0, true));
   const int64_t cap = opt.max_pass_points > 0 ? opt.max_pass_points : (int64_t)1 << 26;
   for (int a = 0; a < A; a++) {
     e->lm_mem_off[(size_t)a + 1] = e->lm_mem_off[(size_t)a] + count[(size_t)a];
@@ -5922,13 +5896,13 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
   CHK(h2d(e, B[sgtd_engine::LM_MEM_OFF].p, e->lm_mem_off.data(), ((size_t)A + 1) * sizeof(long long)));
   const long long *d_mem_off = B[sgtd_engine::LM_MEM_OFF].as<long long>();
   int *d_member = B[sgtd_engine::LM_MEMBER].as<int>();
-  if (timed) HIPCHK(hipEventRecord(e->lm_ev[0], st));
+  if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
   lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, d_mem_off, d_member, B[sgtd_engine::LM_COUNT].as<int>(),
                                                    B[sgtd_engine::LM_MERGED].as<long long>());
   HIPCHK(hipGetLastError());
   if (timed) {
-    HIPCHK(hipEventRecord(e->lm_ev[1], st));
-    CHK(lm_lap(e, 0, 1, &e->lm_ms[0]));
+    HIPCHK(hipEventRecord(clock.ev[1], st));
+    CHK(clock.span(e, 0, 1, 0, true));
   }
 
   // the scans on the device (the scan pipeline's staging buffers: it reads the merged cloud, not these)
@@ -5967,7 +5941,7 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
     u32 *cnt = B[sgtd_engine::LM_CNT].as<u32>(), *start = B[sgtd_engine::LM_START].as<u32>();
     float *m_pts = B[sgtd_engine::LM_MPTS].as<float>();
     u32 *m_lab = B[sgtd_engine::LM_MLAB].as<u32>();
-    if (timed) HIPCHK(hipEventRecord(e->lm_ev[0], st));
+    if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
     if (Pp > 0) {
       lm_segments_kernel<<<grid_for((long long)n_seg + 1, 256), 256, 0, st>>>(d_pose, d_off, d_anch, d_mem_off, d_member, a0, na, n_seg, seg, cnt);
       HIPCHK(hipGetLastError());
@@ -5978,13 +5952,13 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
       else lm_gather_kernel<3, false><<<tiles, SGTD_LM_THREADS, 0, st>>>(d_pts, d_lab, seg, start, n_seg, (u32)Pp, m_pts, m_lab);
       HIPCHK(hipGetLastError());
     }
-    if (timed) HIPCHK(hipEventRecord(e->lm_ev[1], st));
+    if (timed) HIPCHK(hipEventRecord(clock.ev[1], st));
     const ScanCfgDev C = scan_cfg_dev(cfg, na);
     CHK(scan_device(e, C, m_pts, 3, m_lab, pass_off.data(), na));
     if (timed) {
-      HIPCHK(hipEventRecord(e->lm_ev[2], st));
-      CHK(lm_lap(e, 0, 1, &e->lm_ms[1]));
-      CHK(lm_lap(e, 1, 2, &e->lm_ms[2]));
+      HIPCHK(hipEventRecord(clock.ev[2], st));
+      CHK(clock.span(e, 0, 1, 1, true));
+      CHK(clock.span(e, 1, 2, 2, true));
     }
     // the pass's keypoints behind those of the passes before it
     const int64_t K = e->sk_kept, K0 = e->lm_kept;
@@ -6053,18 +6027,15 @@ int sgtd_scan_config_check(const sgtd_scan_config *cfg, const char **why) {
 
 int sgtd_scan_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const float *points, int stride_floats, const uint32_t *labels,
                         const int64_t *pt_off, int n_scans, int device_ptrs) {
-  if (!e || n_scans < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (!e) return SGTD_ERR_INVALID;
   sgtd_scan_config c;
   sgtd_default_scan_config(&c);
   if (cfg) c = *cfg;
   const char *why = nullptr;
   const int cs = sgtd_scan_config_check(&c, &why);
   if (cs == SGTD_ERR_INVALID) return cs;
-  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
-  for (int s = 0; s < n_scans; s++)
-    if (pt_off[s + 1] < pt_off[s]) return SGTD_ERR_INVALID;
+  if (!cloud_set_ok(pt_off, n_scans, stride_floats, points, true, labels)) return SGTD_ERR_INVALID;
   const int64_t P = pt_off[n_scans];
-  if (P > 0 && (!points || !labels)) return SGTD_ERR_INVALID;
   if (n_scans > SGTD_SCAN_MAX_SCANS || P > SGTD_SCAN_MAX_POINTS) {
     e->err = "sgtd_scan_keypoints takes at most " + std::to_string(SGTD_SCAN_MAX_SCANS) + " scans and " + std::to_string(SGTD_SCAN_MAX_POINTS) +
              " points in one call";
@@ -6074,71 +6045,50 @@ int sgtd_scan_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const float 
     e->err = std::string("sgtd_scan_keypoints: ") + why;
     return cs;
   }
-  sgtd_engine *k = scan_engine(e);
-  k->sk_n = -1;
-  PinScope pin_scope(k);
-  const ScanCfgDev C = scan_cfg_dev(c, n_scans);
-  const int rc = scan_run(k, C, points, stride_floats, labels, pt_off, n_scans, device_ptrs);
-  if (rc != SGTD_OK) {
-    if (k != e) e->err = k->err;
-    return rc;
-  }
-  k->sk_n = n_scans;
-  return SGTD_OK;
+  StageRun<int> run(e, &sgtd_engine::sk_n);
+  run.on_device([&](sgtd_engine *k) { return scan_run(k, scan_cfg_dev(c, n_scans), points, stride_floats, labels, pt_off, n_scans, device_ptrs); });
+  return run.end(n_scans);
 }
 
 int sgtd_result_scan_keypoints(sgtd_handle e, int64_t *kp_off, float *xyz, uint32_t *label, int32_t *n_points, int64_t capacity, int64_t *n_keypoints) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(scan_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::sk_n, kNoScan, &c));
   const int64_t K = c->sk_kept;
   if (n_keypoints) *n_keypoints = K;
   if (kp_off) std::memcpy(kp_off, c->sk_kp_off.data(), c->sk_kp_off.size() * sizeof(int64_t));
-  const size_t m = (size_t)std::min(K, capacity);
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && xyz && m) st = d2h(c, xyz, c->sk[sgtd_engine::SK_XYZ].p, m * 3 * sizeof(float));
-  if (st == SGTD_OK && label && m) st = d2h(c, label, c->sk[sgtd_engine::SK_LABEL].p, m * sizeof(u32));
-  if (st == SGTD_OK && n_points && m) st = d2h(c, n_points, c->sk[sgtd_engine::SK_NPOINTS].p, m * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CHK(keypoints_out(e, c, c->sk[sgtd_engine::SK_XYZ], c->sk[sgtd_engine::SK_LABEL], c->sk[sgtd_engine::SK_NPOINTS], (size_t)std::min(K, capacity), xyz, label, n_points));
   return K > capacity && (xyz || label || n_points) ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_result_scan_point_clusters(sgtd_handle e, int scan, int32_t *cluster, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(scan_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::sk_n, kNoScan, &c));
   if (scan < 0 || scan >= c->sk_n) return SGTD_ERR_INVALID;
   const int64_t first = c->sk_off[(size_t)scan], need = c->sk_off[(size_t)scan + 1] - first;
   if (n) *n = need;
-  const size_t m = cluster ? (size_t)std::min(need, capacity) : 0;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && m) st = d2h(c, cluster, c->sk[sgtd_engine::SK_CLUSTER].as<int>() + first, m * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CopyOut out(e, c);
+  out.get(cluster, c->sk[sgtd_engine::SK_CLUSTER].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
+  CHK(out.finish());
   return need > capacity && cluster ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_result_scan_grids(sgtd_handle e, int scan, int32_t *grid, double *range) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(scan_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::sk_n, kNoScan, &c));
   if (scan < 0 || scan >= c->sk_n) return SGTD_ERR_INVALID;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && grid) st = d2h(c, grid, c->sk[sgtd_engine::SK_GRID].as<int>() + (size_t)scan * 128, 128 * sizeof(int));
-  if (st == SGTD_OK && range) st = d2h(c, range, c->sk[sgtd_engine::SK_RANGE].as<double>() + (size_t)scan * 128, 128 * sizeof(double));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
-  return SGTD_OK;
+  CopyOut out(e, c);
+  out.get(grid, c->sk[sgtd_engine::SK_GRID].as<int>() + (size_t)scan * 128, 128 * sizeof(int));
+  out.get(range, c->sk[sgtd_engine::SK_RANGE].as<double>() + (size_t)scan * 128, 128 * sizeof(double));
+  return out.finish();
 }
 
 int sgtd_scan_device_view(sgtd_handle e, const float **d_xyz, const uint32_t **d_label) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(scan_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::sk_n, kNoScan, &c));
   if (d_xyz) *d_xyz = c->sk[sgtd_engine::SK_XYZ].as<float>();
   if (d_label) *d_label = c->sk[sgtd_engine::SK_LABEL].as<u32>();
   return SGTD_OK;
@@ -6153,7 +6103,7 @@ void sgtd_default_local_map_options(sgtd_local_map_options *opt) {
 int sgtd_local_map_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const sgtd_local_map_options *opt, const float *points, int stride_floats,
                              const uint32_t *labels, const int64_t *pt_off, const float *pose12, int n_scans, const int32_t *anchors, int n_anchors,
                              int device_ptrs) {
-  if (!e || n_scans < 0 || n_anchors < 0 || !pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (!e || n_anchors < 0) return SGTD_ERR_INVALID;
   sgtd_scan_config c;
   sgtd_default_scan_config(&c);
   if (cfg) c = *cfg;
@@ -6166,11 +6116,8 @@ int sgtd_local_map_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const s
   if (!(std::isfinite(o.radius) && o.radius >= 0.0) || o.max_members < 0 || o.reserved != 0 || o.max_pass_points < 0 ||
       o.max_pass_points > SGTD_SCAN_MAX_POINTS)
     return SGTD_ERR_INVALID;
-  if (pt_off[0] != 0) return SGTD_ERR_INVALID;
-  for (int s = 0; s < n_scans; s++)
-    if (pt_off[s + 1] < pt_off[s]) return SGTD_ERR_INVALID;
+  if (!cloud_set_ok(pt_off, n_scans, stride_floats, points, true, labels)) return SGTD_ERR_INVALID;
   const int64_t P = pt_off[n_scans];
-  if (P > 0 && (!points || !labels)) return SGTD_ERR_INVALID;
   if (n_scans > 0 && !pose12) return SGTD_ERR_INVALID;
   const int A = anchors ? n_anchors : n_scans;      // NULL: every scan, in order
   if (anchors)
@@ -6185,34 +6132,20 @@ int sgtd_local_map_keypoints(sgtd_handle e, const sgtd_scan_config *cfg, const s
     e->err = std::string("sgtd_local_map_keypoints: ") + why;
     return cs;
   }
-  sgtd_engine *k = scan_engine(e);
-  k->lm_n = -1;
-  PinScope pin_scope(k);
-  const int rc = local_map_run(k, c, o, points, stride_floats, labels, pt_off, pose12, n_scans, anchors, A, device_ptrs);
-  if (rc != SGTD_OK) {
-    if (k != e) e->err = k->err;
-    return rc;
-  }
-  k->lm_n = A;
-  return SGTD_OK;
+  StageRun<int> run(e, &sgtd_engine::lm_n);
+  run.on_device([&](sgtd_engine *k) { return local_map_run(k, c, o, points, stride_floats, labels, pt_off, pose12, n_scans, anchors, A, device_ptrs); });
+  return run.end(A);
 }
 
 int sgtd_result_local_map_keypoints(sgtd_handle e, int64_t *kp_off, float *xyz, uint32_t *label, int32_t *n_points, int64_t capacity,
                                     int64_t *n_keypoints) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(local_map_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::lm_n, kNoLocalMap, &c));
   const int64_t K = c->lm_kept;
   if (n_keypoints) *n_keypoints = K;
   if (kp_off) std::memcpy(kp_off, c->lm_kp_off.data(), c->lm_kp_off.size() * sizeof(int64_t));
-  const size_t m = (size_t)std::min(K, capacity);
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && xyz && m) st = d2h(c, xyz, c->lm[sgtd_engine::LM_XYZ].p, m * 3 * sizeof(float));
-  if (st == SGTD_OK && label && m) st = d2h(c, label, c->lm[sgtd_engine::LM_LABEL].p, m * sizeof(u32));
-  if (st == SGTD_OK && n_points && m) st = d2h(c, n_points, c->lm[sgtd_engine::LM_NPOINTS].p, m * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CHK(keypoints_out(e, c, c->lm[sgtd_engine::LM_XYZ], c->lm[sgtd_engine::LM_LABEL], c->lm[sgtd_engine::LM_NPOINTS], (size_t)std::min(K, capacity), xyz, label, n_points));
   return K > capacity && (xyz || label || n_points) ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
@@ -6220,25 +6153,22 @@ int sgtd_result_local_map_members(sgtd_handle e, int64_t *mem_off, int32_t *memb
                                   int32_t *n_passes) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(local_map_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::lm_n, kNoLocalMap, &c));
   const int64_t M = c->lm_mem_off.back();
   if (n_members) *n_members = M;
   if (n_passes) *n_passes = c->lm_passes;
   if (mem_off) std::memcpy(mem_off, c->lm_mem_off.data(), c->lm_mem_off.size() * sizeof(int64_t));
   if (merged_points && !c->lm_merged.empty()) std::memcpy(merged_points, c->lm_merged.data(), c->lm_merged.size() * sizeof(int64_t));
-  const size_t m = member ? (size_t)std::min(M, capacity) : 0;
-  PinScope pin_scope(c);
-  int st = hipSetDevice(c->cfg.device_id) == hipSuccess ? SGTD_OK : SGTD_ERR_HIP;
-  if (st == SGTD_OK && m) st = d2h(c, member, c->lm[sgtd_engine::LM_MEMBER].p, m * sizeof(int));
-  if (st == SGTD_OK) st = xfer_sync(c);
-  if (st != SGTD_OK) { if (c != e) e->err = c->err; return st; }
+  CopyOut out(e, c);
+  out.get(member, c->lm[sgtd_engine::LM_MEMBER].p, (size_t)std::min(M, capacity) * sizeof(int));
+  CHK(out.finish());
   return M > capacity && member ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
 int sgtd_local_map_device_view(sgtd_handle e, const float **d_xyz, const uint32_t **d_label) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(local_map_ready(e, &c));
+  CHK(stage_ready(e, &sgtd_engine::lm_n, kNoLocalMap, &c));
   if (d_xyz) *d_xyz = c->lm[sgtd_engine::LM_XYZ].as<float>();
   if (d_label) *d_label = c->lm[sgtd_engine::LM_LABEL].as<u32>();
   return SGTD_OK;
@@ -6247,10 +6177,10 @@ int sgtd_local_map_device_view(sgtd_handle e, const float **d_xyz, const uint32_
 int sgtd_local_map_stage_ms(sgtd_handle e, float *ms_members, float *ms_gather, float *ms_scan) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(local_map_ready(e, &c));
-  if (ms_members) *ms_members = c->lm_ms[0];
-  if (ms_gather) *ms_gather = c->lm_ms[1];
-  if (ms_scan) *ms_scan = c->lm_ms[2];
+  CHK(stage_ready(e, &sgtd_engine::lm_n, kNoLocalMap, &c));
+  if (ms_members) *ms_members = c->lm_clock.ms[0];
+  if (ms_gather) *ms_gather = c->lm_clock.ms[1];
+  if (ms_scan) *ms_scan = c->lm_clock.ms[2];
   return SGTD_OK;
 }
 

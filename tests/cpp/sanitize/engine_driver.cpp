@@ -5,7 +5,9 @@
 // (sgtd_refine_poses, sgtd_overlap, sgtd_align_keypoints) run in a scenario of their own below, whose stand-in results name the
 // (query, candidate) slot they belong to.  The forms of the query pipeline (launch_select's plan and stages, the list pass run
 // again, deferred lists, the diagnostic re-run) run in a third scenario with the stand-in's trace on: every launch, memset,
-// attribute and event record is a line of the transcript.  Compiled for the host only
+// attribute and event record is a line of the transcript.  The stages that belong to no batch (sgtd_register_clouds,
+// sgtd_register_voxels, sgtd_scan_keypoints, sgtd_local_map_keypoints, sgtd_consistent_loops, sgtd_relax_poses, sgtd_pose_consensus)
+// and every getter of theirs run in a fourth, traced like the third, on one device and on two.  Compiled for the host only
 // (hipcc --cuda-host-only: the kernel headers are needed for the argument structs); tests/test_sanitizers.py builds and runs it.
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,13 @@ namespace kernels_of_the_engine {
 #include "../../../sgtd_amd/csrc/refine_kernels.hip.h"
 #include "../../../sgtd_amd/csrc/overlap_kernels.hip.h"
 #include "../../../sgtd_amd/csrc/align_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/consistency_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/relax_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/register_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/voxel_register_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/consensus_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/scan_kernels.hip.h"
+#include "../../../sgtd_amd/csrc/local_map_kernels.hip.h"
 }  // namespace kernels_of_the_engine
 using kernels_of_the_engine::ProbeBuffers;
 using kernels_of_the_engine::frame_pack_bytes;
@@ -78,14 +87,27 @@ struct Scenario {
   // the select-forms scenario
   unsigned longest = 0;             // frame_longest_kernel: entries of the table's largest frame (0: leave the zero), sizes the entry ids' rank
   unsigned rough_matches = 0;       // resolve_undecided_kernel: rough matches of query 0 (sgtd_result_rough has something to gather)
+  // the cloud and graph stages' scenario
+  long long solve_rounds = 0;       // reg_trial_kernel / vreg_trial_kernel: the launch of a call that leaves no pair unfinished (0: none does)
+  long long trials = 0;             // ... launches since the call's reg_init_kernel / vreg_init_kernel
+  size_t cloud_floats = 0;          // floats of the call's points (reg_cov_kernel checks the array it is handed)
+  std::vector<u32> map_voxels;      // vreg_ranges_kernel: voxels of each map (their sum: what scan_voxels_kernel leaves as the run's count)
+  unsigned voxels = 0;              // scan_voxels_kernel: the voxels of a scan pipeline's run
+  long long kept = 0;               // scan_offsets_kernel: keypoints the run keeps, spread over its scans
+  bool relax_ends = true;           // relax_ctl_kernel: an accepted step ends the solve
 };
 bool g_tracing = false;             // the select-forms scenario: every launch adds its scalars to the transcript (trace_args)
 void trace_args(const char *name, void **args);
 
-// bytes from p to the end of the block it lies in
+// bytes from p to the end of the block it lies in; none where p is the end of a block (an empty array may start there).  Any other
+// pointer is a stray one
 size_t room_of(const void *p) {
   hipDeviceptr_t base; size_t size;
-  REQUIRE(hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess);
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) {
+    const char *before = static_cast<const char *>(p) - 1;
+    REQUIRE(p && hipMemGetAddressRange(&base, &size, const_cast<char *>(before)) == hipSuccess && static_cast<const char *>(base) + size == p);
+    return 0;
+  }
   return size - (size_t)(static_cast<const char *>(p) - static_cast<const char *>(base));
 }
 
@@ -167,9 +189,161 @@ template <class P> void keypoint_room(const P &p, int nq) {
 
 std::vector<const void *> g_gathers_into;      // gather_pair_entries_kernel launches: the `side` array each was handed
 
+// `kernel` is the function the (mangled) name names: reg_init_kernel is not vreg_init_kernel
+bool names(const char *name, const char *kernel) {
+  const char *at = strstr(name, kernel);
+  return at && at > name && at[-1] >= '0' && at[-1] <= '9';
+}
+
+// ---- the cloud and graph stages (sgtd_register_clouds, sgtd_register_voxels, sgtd_scan_keypoints, sgtd_local_map_keypoints,
+// sgtd_consistent_loops, sgtd_relax_poses, sgtd_pose_consensus): the few words the host reads back, the room of what a launch is handed
+void reg_room(const kernels_of_the_engine::RegParams &P, bool dense) {
+  const size_t n = (size_t)P.n_pairs, ts = (size_t)P.total_src;
+  REQUIRE(room_of(P.src) >= n * 4 && room_of(P.src_off) >= (n + 1) * 4 && room_of(P.unfinished) >= 4);
+  REQUIRE(room_of(P.tile_pair) >= (size_t)P.n_tiles * 4 && room_of(P.tile_first) >= (size_t)P.n_tiles * 4);
+  REQUIRE(room_of(P.ctile_cloud) >= (size_t)P.n_ctiles * 4 && room_of(P.ctile_first) >= (size_t)P.n_ctiles * 4);
+  REQUIRE(room_of(P.st) >= std::max<size_t>(n, 1) * sizeof(kernels_of_the_engine::RegState));
+  REQUIRE(room_of(P.out_pose) >= n * 12 * 8 && room_of(P.out_fitness) >= n * 8 && room_of(P.out_cost) >= n * 16);
+  REQUIRE(room_of(P.out_matched) >= n * 4 && room_of(P.out_iters) >= n * 4 && room_of(P.out_status) >= n * 4);
+  if (dense) REQUIRE(room_of(P.tgt) >= n * 4 && room_of(P.md2) >= ts * 8 && room_of(P.M) >= ts * 72 && room_of(P.mj) >= ts * 4 && room_of(P.part_d2) >= ts * 8 && room_of(P.part_j) >= ts * 4);
+}
+void vreg_room(const kernels_of_the_engine::RegParams &P, const kernels_of_the_engine::VregParams &V) {
+  const size_t n = (size_t)P.n_pairs, ts = (size_t)P.total_src, nm = (size_t)V.n_members;
+  REQUIRE(room_of(V.tgt_map) >= n * 4 && room_of(V.map_off) >= (V.n_maps ? (size_t)V.n_maps + 1 : 0) * 4 && room_of(V.map_cloud) >= nm * 4);
+  REQUIRE(room_of(V.mem_map) >= nm * 4 && room_of(V.mem_pt_off) >= (nm + 1) * 4 && room_of(V.map_vox) >= ((size_t)V.n_maps + 1) * 4);
+  REQUIRE(room_of(V.vid) >= ts * (size_t)V.mode * 4 && room_of(V.Mw) >= ts * (size_t)V.mode * 72 && room_of(V.out_corr) >= n * 4);
+  if (V.map_pose) REQUIRE(room_of(V.map_pose) >= nm * 96);
+  if (V.n_vox) REQUIRE(room_of(V.vkey) >= (size_t)V.n_vox * 8 && room_of(V.vstart) >= ((size_t)V.n_vox + 1) * 4 && room_of(V.vmean) >= (size_t)V.n_vox * 24 && room_of(V.vcov) >= (size_t)V.n_vox * 72);
+}
+bool cloud_hook(Scenario &S, const char *name, void **args) {
+  namespace K = kernels_of_the_engine;
+  if (names(name, "reg_cov_kernel")) {
+    const K::RegParams &P = *static_cast<const K::RegParams *>(args[0]);
+    REQUIRE(P.n_ctiles > 0 && sgtd_stub_grid_x() == (unsigned)P.n_ctiles && room_of(P.pts) >= S.cloud_floats * 4 && room_of(P.cov) >= S.cloud_floats / (size_t)P.stride * 72);
+  } else if (names(name, "reg_init_kernel") || names(name, "vreg_init_kernel")) {
+    const K::RegParams &P = *static_cast<const K::RegParams *>(args[0]);
+    const bool dense = names(name, "reg_init_kernel");
+    reg_room(P, dense);
+    if (!dense) vreg_room(P, *static_cast<const K::VregParams *>(args[1]));
+    const double *init = *static_cast<const double **>(args[dense ? 1 : 2]);
+    if (init) REQUIRE(room_of(init) >= (size_t)P.n_pairs * 96);
+    S.trials = 0;
+  } else if (names(name, "reg_trial_kernel") || names(name, "vreg_trial_kernel")) {
+    const K::RegParams &P = *static_cast<const K::RegParams *>(args[0]);
+    REQUIRE(sgtd_stub_grid_x() == (unsigned)P.n_pairs);
+    if (++S.trials == S.solve_rounds) *P.unfinished = 0;
+  } else if (names(name, "reg_final_kernel") || names(name, "vreg_final_kernel")) {
+    // the result rows name their pair
+    const K::RegParams &P = *static_cast<const K::RegParams *>(args[0]);
+    for (int k = 0; k < P.n_pairs; k++) {
+      for (int i = 0; i < 12; i++) P.out_pose[(size_t)k * 12 + i] = (double)k + (double)i / 16.0;
+      P.out_fitness[k] = 0.5 * k; P.out_cost[2 * k] = 2.0 * k; P.out_cost[2 * k + 1] = 1.0 * k;
+      P.out_matched[k] = 3 * k; P.out_iters[k] = (int)S.trials; P.out_status[k] = k % 5;
+      if (names(name, "vreg_final_kernel")) static_cast<const K::VregParams *>(args[1])->out_corr[k] = 7 * k;
+    }
+  } else if (names(name, "vreg_ranges_kernel")) {
+    const K::VregParams &V = *static_cast<const K::VregParams *>(args[0]);
+    REQUIRE(room_of(V.map_vox) >= ((size_t)V.n_maps + 1) * 4);
+    V.map_vox[0] = 0;
+    for (int m = 0; m < V.n_maps; m++) V.map_vox[m + 1] = V.map_vox[m] + (V.n_vox ? S.map_voxels[(size_t)m] : 0u);
+    REQUIRE(V.map_vox[V.n_maps] == V.n_vox);
+  } else if (names(name, "scan_heads_kernel")) {
+    const long long n = *static_cast<long long *>(args[1]);
+    REQUIRE(room_of(*static_cast<void **>(args[0])) >= (size_t)n * 8 && room_of(*static_cast<void **>(args[3])) >= ((size_t)n + 1) * 4 && room_of(*static_cast<void **>(args[4])) >= 16);
+  } else if (names(name, "scan_voxels_kernel")) {
+    // the count of runs is the scan's last word
+    u32 *excl = *static_cast<u32 **>(args[2]);
+    const long long n = *static_cast<long long *>(args[3]);
+    REQUIRE(room_of(excl) >= ((size_t)n + 1) * 4 && room_of(*static_cast<void **>(args[5])) >= (size_t)n * 8 && room_of(*static_cast<void **>(args[6])) >= ((size_t)n + 1) * 4);
+    excl[n] = (u32)std::min<long long>(S.voxels, n);
+  } else if (names(name, "scan_point_kernel")) {
+    const K::ScanPointParams &P = *static_cast<const K::ScanPointParams *>(args[0]);
+    const size_t n = (size_t)P.n;
+    REQUIRE(room_of(P.pts) >= n * (size_t)P.stride * 4 && room_of(P.labels) >= n * 4 && room_of(P.sc_of) >= n * 4 && room_of(P.r) >= n * 8 && room_of(P.pitch) >= n * 8 && room_of(P.azimuth) >= n * 8);
+  } else if (names(name, "scan_jump_kernel")) {
+    REQUIRE(room_of(*static_cast<u32 **>(args[2])) >= ((size_t)*static_cast<int *>(args[3]) + 1) * 4);      // (changed[round] stays zero: settled)
+  } else if (names(name, "scan_offsets_kernel")) {
+    const int n_scans = *static_cast<int *>(args[2]);
+    long long *kp_off = *static_cast<long long **>(args[3]);
+    REQUIRE(room_of(kp_off) >= ((size_t)n_scans + 1) * 8);
+    for (int s = 0; s <= n_scans; s++) kp_off[s] = S.kept * s / n_scans;
+  } else if (names(name, "scan_sum_wave_kernel")) {
+    const u32 n_kept = *static_cast<u32 *>(args[5]);
+    float *xyz = *static_cast<float **>(args[6]);
+    REQUIRE(room_of(xyz) >= (size_t)n_kept * 12);
+    for (u32 i = 0; i < n_kept * 3; i++) xyz[i] = (float)i / 4.f;
+  } else if (names(name, "lm_members_kernel")) {
+    // an anchor's members: its scan and, for every other anchor, the next one
+    const long long *pt_off = *static_cast<const long long **>(args[1]), *mem_off = *static_cast<const long long **>(args[6]);
+    const int n_scans = *static_cast<int *>(args[2]), A = (int)sgtd_stub_grid_x();
+    const int *anchors = *static_cast<const int **>(args[3]);
+    int *member = *static_cast<int **>(args[7]), *count = *static_cast<int **>(args[8]);
+    long long *merged = *static_cast<long long **>(args[9]);
+    REQUIRE(room_of(pt_off) >= ((size_t)n_scans + 1) * 8 && room_of(anchors) >= (size_t)A * 4 && room_of(count) >= (size_t)A * 4 && room_of(merged) >= (size_t)A * 8);
+    REQUIRE(room_of(*static_cast<void **>(args[0])) >= (size_t)n_scans * 48);
+    if (mem_off) REQUIRE(room_of(mem_off) >= ((size_t)A + 1) * 8 && room_of(member) >= (size_t)mem_off[A] * 4);
+    for (int a = 0; a < A; a++) {
+      const int s = anchors[a], t = (s + 1) % n_scans, c = a % 2 == 1 && t != s ? 2 : 1;
+      count[a] = c;
+      merged[a] = (pt_off[s + 1] - pt_off[s]) + (c == 2 ? pt_off[t + 1] - pt_off[t] : 0);
+      if (mem_off) { member[mem_off[a]] = s; if (c == 2) member[mem_off[a] + 1] = t; }
+    }
+  } else if (names(name, "lm_gather_kernel")) {
+    const int n_seg = *static_cast<int *>(args[4]);
+    const u32 Pp = *static_cast<u32 *>(args[5]);
+    REQUIRE(room_of(*static_cast<void **>(args[2])) >= (size_t)n_seg * sizeof(K::LmSeg) && room_of(*static_cast<void **>(args[3])) >= ((size_t)n_seg + 1) * 4);
+    REQUIRE(room_of(*static_cast<void **>(args[6])) >= (size_t)Pp * 12 && room_of(*static_cast<void **>(args[7])) >= (size_t)Pp * 4);
+  } else if (names(name, "cons_pair_kernel")) {
+    const K::ConsPairParams &P = *static_cast<const K::ConsPairParams *>(args[0]);
+    REQUIRE(room_of(P.soa) >= (size_t)SGTD_CONS_STREAMS * P.ns * 8 && room_of(P.valid) >= P.ns && room_of(P.rows) >= (size_t)P.n * P.words * 8);
+    for (size_t i = 0; i < (size_t)P.n * P.words; i++) P.rows[i] = 0x0101010101010101ull * (i % 251);
+  } else if (names(name, "cons_select_kernel")) {
+    // the first round completes the choice
+    int *in_set = *static_cast<int **>(args[3]);
+    K::ConsState *st = *static_cast<K::ConsState **>(args[5]);
+    REQUIRE(room_of(st) >= sizeof(K::ConsState) && room_of(in_set) >= 12);
+    st->done = 1; st->n_set = 1; st->round = 1;
+    in_set[0] = 1;
+  } else if (names(name, "consensus_kernel")) {
+    const K::ConsensusParams &P = *static_cast<const K::ConsensusParams *>(args[0]);
+    const size_t nq = sgtd_stub_grid_x(), cn = (size_t)P.cn;
+    REQUIRE(room_of(P.n_cand) >= nq * 4 && room_of(P.cand_frame) >= nq * cn * 4 && room_of(P.score) >= nq * cn * 8 && room_of(P.rel) >= nq * cn * 96);
+    REQUIRE(room_of(P.pose) >= nq * 96 && room_of(P.figs) >= nq * 24 && room_of(P.mask) >= nq * 8 && room_of(P.counts) >= nq * 12);
+    REQUIRE(room_of(P.rows) >= nq * cn * 8 && room_of(P.degree) >= nq * cn * 4 && room_of(P.pick) >= nq * cn * 4);
+    REQUIRE(room_of(P.store) >= std::max<size_t>(P.n_ids, 1) * 48 && room_of(P.has) >= std::max<size_t>(P.n_ids, 1));
+    // every query's set: its first two candidates (its first, of one)
+    for (size_t q = 0; q < nq; q++) {
+      const int set = std::min(P.n_cand[q], 2);
+      P.mask[q] = set == 2 ? 3u : (u64)set;
+      P.counts[q * 3] = P.n_cand[q]; P.counts[q * 3 + 1] = set; P.counts[q * 3 + 2] = set ? 0 : -1;
+      for (int i = 0; i < 3; i++) P.figs[q * 3 + i] = (double)q + 0.25 * i;
+      for (int i = 0; i < 12; i++) P.pose[q * 12 + i] = set ? P.rel[q * cn * 12 + i] : kNaN;
+      for (size_t k = 0; k < cn; k++) { P.rows[q * cn + k] = P.mask[q]; P.degree[q * cn + k] = (int)k; P.pick[q * cn + k] = k < (size_t)set ? (int)k : -1; }
+    }
+  } else if (names(name, "relax_init_kernel")) {
+    const K::RelaxParams &P = *static_cast<const K::RelaxParams *>(args[0]);
+    const size_t n = (size_t)P.n, m = (size_t)P.m;
+    REQUIRE(room_of(P.state) >= 2 * n * SGTD_RELAX_REC * 8 && room_of(P.held) >= n && room_of(P.ok) >= n && room_of(P.ei) >= m * 4 && room_of(P.ej) >= m * 4);
+    REQUIRE(room_of(P.wt) >= 2 * m * 8 && room_of(P.iz) >= 45 * P.ms * 8 + 5 * m * 8 && room_of(P.ec) >= 4 * m * 8 && room_of(P.off) >= (n + 1 + 2 * m) * 4);
+    REQUIRE(room_of(P.r) >= n * 102 * 8 + n && room_of(P.st) >= sizeof(K::RelaxState));
+    REQUIRE(room_of(*static_cast<void **>(args[1])) >= n * 96 && room_of(*static_cast<void **>(args[2])) >= m * 96);
+    for (size_t i = 0; i < 2 * n * SGTD_RELAX_REC; i++) P.state[i] = (double)i / 8.0;
+  } else if (names(name, "relax_ctl_kernel")) {
+    const K::RelaxParams &P = *static_cast<const K::RelaxParams *>(args[0]);
+    if (*static_cast<int *>(args[1]) == K::RELAX_CTL_ACCEPT) {
+      P.st->outer++; P.st->accepted++; P.st->cg_total += 3; P.st->cost = 0.5; P.st->cost_before = 2.0; P.st->cur = 1;
+      if (S.relax_ends) { P.st->done = 1; P.st->status = 0; }
+    }
+  } else {
+    return false;
+  }
+  return true;
+}
+
 void hook(const char *name, void **args, void *user) {
   Scenario &S = *static_cast<Scenario *>(user);
   if (g_tracing) trace_args(name, args);
+  if (cloud_hook(S, name, args)) return;
   if (strstr(name, "frame_longest_kernel")) {
     if (S.longest) (*static_cast<u32 **>(args[4]))[0] = S.longest;
   } else if (strstr(name, "resolve_undecided_kernel")) {
@@ -870,6 +1044,51 @@ void trace_args(const char *name, void **a) {
   else if (has("block_scan_kernel")) { i("blocks", 1); i("cn", 2); p("base_of_one", 7); u("pair_cap", 8); p("totals_of_one", 9); }
   else if (has("block_write_kernel")) { Q(0); B(1); CL(2); i("blocks", 3); i("cn", 5); M(9); }
   else if (has("rough_gather_kernel")) { Q(0); B(1); M(2); i("q", 3); p("cell", 7); p("dis", 8); }
+  // ---- the cloud and graph stages
+  auto d = [&](const char *n, int k) { fprintf(f, " %s %.17g", n, arg<double>(a, k)); };
+  auto R = [&](int k) {
+    const K::RegParams &r = arg<K::RegParams>(a, k);
+    fprintf(f, " R{stride %d n_pairs %d n_tiles %d n_ctiles %d total_src %d slice %d k %d max_iterations %d lm_max_trials %d max2 %.17g lambda_factor %.17g eps %.17g %.17g %.17g}", r.stride, r.n_pairs,
+            r.n_tiles, r.n_ctiles, r.total_src, r.slice, r.o.k, r.o.max_iterations, r.o.lm_max_trials, r.o.max2, r.o.lambda_factor, r.o.rotation_eps, r.o.translation_eps, r.o.plane_eps);
+  };
+  auto V = [&](int k) {
+    const K::VregParams &v = arg<K::VregParams>(a, k);
+    fprintf(f, " V{n_maps %d n_members %d n_member_pts %d mode %d res %.17g n_vox %u map_pose %d}", v.n_maps, v.n_members, v.n_member_pts, v.mode, v.res, v.n_vox, v.map_pose != nullptr);
+  };
+  auto X = [&](int k) { const K::RelaxParams &r = arg<K::RelaxParams>(a, k); fprintf(f, " X{n %d m %d ms %zu max_outer %d all_held %d lmin %.17g lmax %.17g tol2 %.17g step_tol %.17g}", r.n, r.m, r.ms, r.max_outer, r.all_held, r.lmin, r.lmax, r.tol2, r.step_tol); };
+  if (names(name, "reg_cov_kernel") || names(name, "reg_lin_kernel") || names(name, "reg_trial_kernel") || names(name, "reg_final_kernel")) R(0);
+  else if (names(name, "reg_init_kernel")) { R(0); p("init", 1); }
+  else if (names(name, "reg_search_kernel") || names(name, "reg_match_kernel")) { R(0); i("final", 1); }
+  else if (names(name, "vreg_ranges_kernel")) V(0);
+  else if (names(name, "vreg_init_kernel")) { R(0); V(1); p("init", 2); }
+  else if (names(name, "vreg_corr_kernel")) { R(0); V(1); i("final", 2); }
+  else if (has("vreg_")) { R(0); V(1); }
+  else if (names(name, "scan_init_kernel")) i("n_sc", 2);
+  else if (names(name, "scan_point_kernel")) { const K::ScanPointParams &s = arg<K::ScanPointParams>(a, 0); fprintf(f, " stride %d n %lld n_scans %d", s.stride, s.n, arg<K::ScanCfgDev>(a, 1).n_scans); }
+  else if (names(name, "scan_rings_kernel")) i("n_sc", 2);
+  else if (names(name, "scan_keys_kernel")) l("n", 9);
+  else if (names(name, "scan_heads_kernel")) { l("n", 1); fprintf(f, " drop %llx", (unsigned long long)arg<u64>(a, 2)); }
+  else if (names(name, "scan_voxels_kernel")) l("n", 3);
+  else if (names(name, "scan_hook_kernel")) i("round", 5);
+  else if (names(name, "scan_jump_kernel")) i("round", 3);
+  else if (names(name, "scan_offsets_kernel")) i("n_scans", 2);
+  else if (names(name, "scan_cluster_ids_kernel")) u("n_kept", 2);
+  else if (names(name, "scan_point_clusters_kernel")) { l("n", 8); u("n_kept", 9); }
+  else if (names(name, "scan_sum_wave_kernel")) { i("stride", 1); u("n_kept", 5); }
+  else if (names(name, "scan_sum_block_kernel")) i("stride", 1);
+  else if (names(name, "lm_members_kernel")) { i("n_scans", 2); d("rr", 4); i("max_members", 5); p("mem_off", 6); }
+  else if (names(name, "lm_segments_kernel")) { i("a0", 5); i("n_pass", 6); i("n_seg", 7); }
+  else if (names(name, "lm_gather_kernel")) { i("n_seg", 4); u("n_points", 5); }
+  else if (names(name, "cons_prepare_kernel")) { const K::ConsPrepareParams &c = arg<K::ConsPrepareParams>(a, 0); fprintf(f, " n %d ns %zu n_ids %u frame_a %d pose_a %d", c.n, c.ns, c.n_ids, c.frame_a != nullptr, c.pose_a != nullptr); }
+  else if (names(name, "cons_pair_kernel")) { const K::ConsPairParams &c = arg<K::ConsPairParams>(a, 0); fprintf(f, " n %d ns %zu words %u tt %.17g min_trace %.17g", c.n, c.ns, c.words, c.tt, c.min_trace); }
+  else if (names(name, "cons_init_kernel")) { i("n", 1); u("words", 2); }
+  else if (names(name, "cons_count_kernel")) { i("n", 2); u("words", 3); }
+  else if (names(name, "cons_select_kernel")) u("words", 2);
+  else if (names(name, "consensus_kernel")) { const K::ConsensusParams &c = arg<K::ConsensusParams>(a, 0); fprintf(f, " n_ids %u cn %d tt %.17g min_trace %.17g", c.n_ids, c.cn, c.tt, c.min_trace); }
+  else if (names(name, "relax_init_kernel") || names(name, "relax_setup_kernel") || names(name, "relax_cg_edge_kernel") || names(name, "relax_cg_node_kernel") || names(name, "relax_cg_update_kernel") ||
+           names(name, "relax_retract_kernel")) X(0);
+  else if (names(name, "relax_edge_kernel")) { X(0); i("trial", 1); }
+  else if (names(name, "relax_ctl_kernel")) { X(0); i("mode", 1); }
   fprintf(f, "\n");
 }
 
@@ -1127,6 +1346,674 @@ struct SelectForms {
       if (forms(w.kernel) != w.forms) { fprintf(stderr, "engine_driver: %d forms of %s launched, not %d\n", forms(w.kernel), w.kernel, w.forms); exit(1); }
   }
 };
+
+// ---- the cloud and graph stages, launch by launch: sgtd_register_clouds, sgtd_register_voxels, sgtd_scan_keypoints,
+// sgtd_local_map_keypoints, sgtd_consistent_loops, sgtd_relax_poses, sgtd_pose_consensus (both forms) and every getter of theirs,
+// on one device and on two "devices" behind one handle (their results live on the first device's engine) ----
+struct Clouds {       // labelled clouds back to back
+  int stride;
+  std::vector<int64_t> off{0};
+  std::vector<float> pts;
+  std::vector<uint32_t> lab;
+  Clouds(std::mt19937 &rng, int stride_, std::initializer_list<int> sizes) : stride(stride_) {
+    std::uniform_real_distribution<float> u(-30.f, 30.f);
+    for (int n : sizes) {
+      for (int i = 0; i < n * stride; i++) pts.push_back(u(rng));
+      for (int i = 0; i < n; i++) lab.push_back(10 + rng() % 9);
+      off.push_back((int64_t)lab.size());
+    }
+    pts.reserve(4); lab.reserve(1);
+  }
+  int n() const { return (int)off.size() - 1; }
+};
+struct OnDevice {     // a copy in "device" memory, `skew` bytes into its block
+  void *block = nullptr;
+  char *p = nullptr;
+  OnDevice(const void *src, size_t bytes, size_t skew = 0) {
+    REQUIRE(hipMalloc(&block, bytes + skew + 16) == hipSuccess);
+    p = static_cast<char *>(block) + skew;
+    memcpy(p, src, bytes);
+  }
+  ~OnDevice() { REQUIRE(hipFree(block) == hipSuccess); }
+  template <class T> const T *as() const { return reinterpret_cast<const T *>(p); }
+};
+
+struct CloudStages {
+  Scenario &S;
+  std::mt19937 &rng;
+  sgtd_config cfg;
+  sgtd_handle h = nullptr;
+  int n_dev = 1;
+  void note(const char *text) { if (g_transcript) fprintf(g_transcript, "# %s\n", text); }
+  void timing(int on) { CALL(SGTD_OK, h, sgtd_set_timing(h, on)); }
+
+  // ---- sgtd_register_clouds
+  void registered(int expect, int n_pairs, int n_clouds) {
+    const size_t n = (size_t)std::max(n_pairs, 1);
+    std::vector<double> pose(n * 12, -7.0), fit(n, -7.0), cost(n * 2, -7.0), cov(700 * 9, -7.0), d2(700, -7.0);
+    std::vector<int32_t> matched(n, -7), iters(n, -7), status(n, -7), tgt(700, -7);
+    std::vector<int64_t> cnt(1, -7);
+    std::vector<float> ms(4, -7.f);
+    CALL(expect, h, sgtd_result_registered(h, pose.data(), fit.data(), cost.data(), matched.data(), iters.data(), status.data()), pose, fit, cost, matched, iters, status);
+    CALL(expect, h, sgtd_result_registered(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    CALL(expect, h, sgtd_register_stage_ms(h, &ms[0], &ms[1], &ms[2], &ms[3]));
+    CALL(expect, h, sgtd_register_stage_ms(h, nullptr, nullptr, nullptr, nullptr));
+    if (expect != SGTD_OK) {
+      CALL(expect, h, sgtd_result_register_covariances(h, 0, cov.data(), 700, cnt.data()), cnt);
+      CALL(expect, h, sgtd_result_register_matches(h, 0, tgt.data(), d2.data(), 700, cnt.data()), cnt);
+      return;
+    }
+    for (int cl = 0; cl < n_clouds; cl++) {
+      CALL(SGTD_OK, h, sgtd_result_register_covariances(h, cl, nullptr, 0, cnt.data()), cnt);
+      const int64_t need = cnt[0];
+      if (need > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_register_covariances(h, cl, cov.data(), need - 1, cnt.data()), cov, cnt);
+      cov.assign(700 * 9, -7.0);
+      CALL(SGTD_OK, h, sgtd_result_register_covariances(h, cl, cov.data(), need, cnt.data()), cov, cnt);
+      REQUIRE(cnt[0] == need && cov[(size_t)need * 9] == -7.0);
+    }
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_register_covariances(h, n_clouds, cov.data(), 700, cnt.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_register_covariances(h, 0, cov.data(), -1, cnt.data()));
+    for (int k = 0; k < n_pairs; k++) {
+      CALL(SGTD_OK, h, sgtd_result_register_matches(h, k, nullptr, nullptr, 0, cnt.data()), cnt);
+      const int64_t need = cnt[0];
+      if (need > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_register_matches(h, k, tgt.data(), nullptr, need - 1, cnt.data()), tgt, cnt);
+      tgt.assign(700, -7);
+      CALL(SGTD_OK, h, sgtd_result_register_matches(h, k, tgt.data(), d2.data(), need, nullptr), tgt, d2);
+      REQUIRE(cnt[0] == need && tgt[(size_t)need] == -7);
+    }
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_register_matches(h, n_pairs, tgt.data(), d2.data(), 700, cnt.data()));
+  }
+  void register_clouds() {
+    note("sgtd_register_clouds");
+    Env slice("SGTD_REG_SLICE_TILES", "1");       // (a slice of one tile of 512 targets: the cloud of 600 has two)
+    const Clouds c(rng, 3, {0, 5, 130, 600}), c4(rng, 4, {0, 5, 130, 600});
+    // an empty source; one tile; two source tiles against two target slices; the reverse; an empty target
+    const int32_t src[5] = {0, 1, 2, 3, 2}, tgt[5] = {3, 3, 3, 2, 0};
+    std::vector<double> init(5 * 12, 0.0);
+    for (int k = 0; k < 5; k++) init[(size_t)k * 12] = init[(size_t)k * 12 + 5] = init[(size_t)k * 12 + 10] = 1.0;
+    sgtd_register_options o;
+    sgtd_default_register_options(&o);
+    registered(SGTD_ERR_STATE, 5, 4);
+    S.cloud_floats = c.pts.size();
+    for (int on : {0, 1}) {
+      timing(on);
+      S.solve_rounds = 2;                         // (within the first group of SGTD_REG_GROUP rounds)
+      CALL(SGTD_OK, h, sgtd_register_clouds(h, nullptr, c.pts.data(), 3, c.off.data(), 4, src, tgt, nullptr, 5, 0));
+      registered(SGTD_OK, 5, 4);
+      S.solve_rounds = SGTD_REG_GROUP + 2;        // (in the second)
+      const OnDevice d(c.pts.data(), c.pts.size() * 4);
+      CALL(SGTD_OK, h, sgtd_register_clouds(h, &o, d.as<float>(), 3, c.off.data(), 4, src, tgt, init.data(), 5, 1));
+      registered(SGTD_OK, 5, 4);
+    }
+    S.cloud_floats = c4.pts.size();
+    S.solve_rounds = 1;
+    CALL(SGTD_OK, h, sgtd_register_clouds(h, &o, c4.pts.data(), 4, c4.off.data(), 4, src + 1, tgt + 1, init.data(), 2, 0));
+    registered(SGTD_OK, 2, 4);
+    // solves that never end: the rounds' bound and its error (on a group: raised on the first device's engine)
+    o.max_iterations = 1; o.lm_max_trials = 2;
+    S.solve_rounds = 0;
+    CALL(SGTD_ERR_HIP, h, sgtd_register_clouds(h, &o, c4.pts.data(), 4, c4.off.data(), 4, src, tgt, nullptr, 5, 0));
+    registered(SGTD_ERR_STATE, 5, 4);
+    sgtd_default_register_options(&o);
+    // only pairs none of whose solves starts; no pair; no cloud
+    CALL(SGTD_OK, h, sgtd_register_clouds(h, nullptr, c4.pts.data(), 4, c4.off.data(), 4, src, tgt, nullptr, 1, 0));
+    registered(SGTD_OK, 1, 4);
+    CALL(SGTD_OK, h, sgtd_register_clouds(h, nullptr, c4.pts.data(), 4, c4.off.data(), 4, nullptr, nullptr, nullptr, 0, 0));
+    registered(SGTD_OK, 0, 4);
+    const int64_t none[1] = {0};
+    CALL(SGTD_OK, h, sgtd_register_clouds(h, nullptr, nullptr, 3, none, 0, nullptr, nullptr, nullptr, 0, 0));
+    registered(SGTD_OK, 0, 0);
+    timing(0);
+    // every exit of the validation, in its order; the results of the last call stay
+    const float *p = c.pts.data();
+    const int64_t *off = c.off.data();
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, off, -1, src, tgt, nullptr, 5, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, off, 4, src, tgt, nullptr, -1, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, nullptr, 4, src, tgt, nullptr, 5, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 5, off, 4, src, tgt, nullptr, 5, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, off, 4, nullptr, tgt, nullptr, 5, 0));
+    for (int bad = 0; bad < 9; bad++) {
+      sgtd_register_options b;
+      sgtd_default_register_options(&b);
+      if (bad == 0) b.k_neighbors = 2; else if (bad == 1) b.k_neighbors = SGTD_REG_MAX_K + 1; else if (bad == 2) b.max_iterations = 0; else if (bad == 3) b.lm_max_trials = 0;
+      else if (bad == 4) b.reserved = 1; else if (bad == 5) b.max_corr_dist = 0.0; else if (bad == 6) b.lm_init_lambda_factor = kNaN; else if (bad == 7) b.rotation_eps = 0.0;
+      else b.plane_eps = -1.0;
+      CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, &b, p, 3, off, 4, src, tgt, nullptr, 5, 0));
+    }
+    const int64_t from_one[5] = {1, 1, 6, 136, 736}, back[5] = {0, 0, 5, 4, 604};
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, from_one, 4, src, tgt, nullptr, 5, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, back, 4, src, tgt, nullptr, 5, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, nullptr, 3, off, 4, src, tgt, nullptr, 5, 0));
+    const int32_t past[5] = {0, 1, 2, 4, 2}, below[5] = {3, -1, 3, 2, 0};
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, off, 4, past, tgt, nullptr, 5, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, off, 4, src, below, nullptr, 5, 0));
+    init[17] = std::numeric_limits<double>::infinity();
+    CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, nullptr, p, 3, off, 4, src, tgt, init.data(), 5, 0));
+    const int64_t large[2] = {0, (int64_t)SGTD_REG_MAX_POINTS + 1};
+    const int32_t zero[1] = {0};
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_register_clouds(h, nullptr, p, 3, large, 1, zero, zero, nullptr, 1, 0));
+    // (an invalid option together with a cloud too large: INVALID comes first)
+    { sgtd_register_options b; sgtd_default_register_options(&b); b.k_neighbors = 2; CALL(SGTD_ERR_INVALID, h, sgtd_register_clouds(h, &b, p, 3, large, 1, zero, zero, nullptr, 1, 0)); }
+    registered(SGTD_OK, 0, 0);
+  }
+
+  // ---- sgtd_register_voxels
+  void voxel_registered(int expect, int n_pairs, int n_maps) {
+    const size_t n = (size_t)std::max(n_pairs, 1);
+    std::vector<double> pose(n * 12, -7.0), fit(n, -7.0), cost(n * 2, -7.0), mean(8 * 3, -7.0), cov(8 * 9, -7.0);
+    std::vector<int32_t> matched(n, -7), corr(n, -7), iters(n, -7), status(n, -7), coord(8 * 3, -7), np(8, -7), vox(700 * 27, -7);
+    std::vector<int64_t> cnt(1, -7);
+    std::vector<float> ms(5, -7.f);
+    CALL(expect, h, sgtd_result_voxel_registered(h, pose.data(), fit.data(), cost.data(), matched.data(), corr.data(), iters.data(), status.data()), pose, fit, cost, matched, corr, iters, status);
+    CALL(expect, h, sgtd_result_voxel_registered(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    CALL(expect, h, sgtd_voxel_register_stage_ms(h, &ms[0], &ms[1], &ms[2], &ms[3], &ms[4]));
+    if (expect != SGTD_OK) {
+      CALL(expect, h, sgtd_result_voxel_map(h, 0, coord.data(), np.data(), mean.data(), cov.data(), 8, cnt.data()), cnt);
+      CALL(expect, h, sgtd_result_voxel_matches(h, 0, vox.data(), 700, cnt.data()), cnt);
+      return;
+    }
+    for (int m = 0; m < n_maps; m++) {
+      CALL(SGTD_OK, h, sgtd_result_voxel_map(h, m, nullptr, nullptr, nullptr, nullptr, 0, cnt.data()), cnt);
+      const int64_t need = cnt[0];
+      REQUIRE(need <= 8);
+      if (need > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_voxel_map(h, m, coord.data(), np.data(), nullptr, cov.data(), need - 1, cnt.data()), coord, np, cov, cnt);
+      CALL(SGTD_OK, h, sgtd_result_voxel_map(h, m, coord.data(), np.data(), mean.data(), cov.data(), need, cnt.data()), coord, np, mean, cov, cnt);
+      CALL(SGTD_OK, h, sgtd_result_voxel_map(h, m, nullptr, np.data(), nullptr, nullptr, need, nullptr), np);
+    }
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_voxel_map(h, n_maps, coord.data(), np.data(), mean.data(), cov.data(), 8, cnt.data()));
+    for (int k = 0; k < n_pairs; k++) {
+      CALL(SGTD_OK, h, sgtd_result_voxel_matches(h, k, nullptr, 0, cnt.data()), cnt);
+      const int64_t need = cnt[0];
+      if (need > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_voxel_matches(h, k, vox.data(), need - 1, cnt.data()), vox, cnt);
+      CALL(SGTD_OK, h, sgtd_result_voxel_matches(h, k, vox.data(), need, cnt.data()), vox, cnt);
+    }
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_voxel_matches(h, n_pairs, vox.data(), 700, cnt.data()));
+  }
+  void register_voxels() {
+    note("sgtd_register_voxels");
+    const Clouds c(rng, 3, {0, 5, 130, 600});
+    // maps: the cloud of 600; no member; the clouds of 130 and 5.  Pairs: against a map with voxels (one and two source tiles),
+    // an empty source, a map whose range stays empty
+    const int32_t map_off[4] = {0, 1, 1, 3}, map_cloud[3] = {3, 2, 1}, src[4] = {1, 2, 0, 1}, tgt[4] = {0, 2, 0, 1};
+    std::vector<double> init(4 * 12, 0.0), map_pose(3 * 12, 0.0);
+    for (int k = 0; k < 4; k++) init[(size_t)k * 12] = init[(size_t)k * 12 + 5] = init[(size_t)k * 12 + 10] = 1.0;
+    for (int k = 0; k < 3; k++) { map_pose[(size_t)k * 12] = map_pose[(size_t)k * 12 + 5] = map_pose[(size_t)k * 12 + 10] = 1.0; map_pose[(size_t)k * 12 + 3] = 0.5 * k; }
+    sgtd_voxel_register_options o;
+    sgtd_default_voxel_register_options(&o);
+    voxel_registered(SGTD_ERR_STATE, 4, 3);
+    S.cloud_floats = c.pts.size();
+    S.map_voxels = {5, 0, 3}; S.voxels = 8;
+    const int modes[3] = {1, 7, 27};
+    for (int on : {0, 1}) {
+      timing(on);
+      S.solve_rounds = 2;
+      o.neighbor_mode = modes[on];
+      CALL(SGTD_OK, h, sgtd_register_voxels(h, &o, c.pts.data(), 3, c.off.data(), 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4, 0));
+      voxel_registered(SGTD_OK, 4, 3);
+      S.solve_rounds = SGTD_REG_GROUP + 2;
+      o.neighbor_mode = modes[on + 1];
+      const OnDevice d(c.pts.data(), c.pts.size() * 4);
+      CALL(SGTD_OK, h, sgtd_register_voxels(h, &o, d.as<float>(), 3, c.off.data(), 4, map_off, map_cloud, map_pose.data(), 3, src, tgt, init.data(), 4, 1));
+      voxel_registered(SGTD_OK, 4, 3);
+      // maps and no pair
+      CALL(SGTD_OK, h, sgtd_register_voxels(h, nullptr, c.pts.data(), 3, c.off.data(), 4, map_off, map_cloud, nullptr, 3, nullptr, nullptr, nullptr, 0, 0));
+      voxel_registered(SGTD_OK, 0, 3);
+    }
+    o.max_iterations = 1; o.lm_max_trials = 2;
+    S.solve_rounds = 0;
+    CALL(SGTD_ERR_HIP, h, sgtd_register_voxels(h, &o, c.pts.data(), 3, c.off.data(), 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4, 0));
+    voxel_registered(SGTD_ERR_STATE, 4, 3);
+    // the hook leaves every range empty: no solve starts.  Maps whose members have no points.  No map
+    S.map_voxels = {0, 0, 0}; S.voxels = 0;
+    CALL(SGTD_OK, h, sgtd_register_voxels(h, nullptr, c.pts.data(), 3, c.off.data(), 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4, 0));
+    voxel_registered(SGTD_OK, 4, 3);
+    const int32_t hollow_off[3] = {0, 1, 2}, hollow_cloud[2] = {0, 0}, hollow_tgt[2] = {1, 0};
+    CALL(SGTD_OK, h, sgtd_register_voxels(h, nullptr, c.pts.data(), 3, c.off.data(), 4, hollow_off, hollow_cloud, map_pose.data(), 2, src, hollow_tgt, nullptr, 2, 0));
+    voxel_registered(SGTD_OK, 2, 2);
+    CALL(SGTD_OK, h, sgtd_register_voxels(h, nullptr, c.pts.data(), 3, c.off.data(), 4, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0));
+    voxel_registered(SGTD_OK, 0, 0);
+    timing(0);
+    // every exit of the validation, in its order
+    const float *p = c.pts.data();
+    const int64_t *off = c.off.data();
+    sgtd_default_voxel_register_options(&o);
+#define VOX(status, opt, pts, stride, off_, nc, mo, mc, mp, nm, s, t, in, np) CALL(status, h, sgtd_register_voxels(h, opt, pts, stride, off_, nc, mo, mc, mp, nm, s, t, in, np, 0))
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, -1, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, map_cloud, nullptr, -1, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 2, off, 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, map_cloud, nullptr, 3, src, nullptr, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, nullptr, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    for (int bad = 0; bad < 6; bad++) {
+      sgtd_voxel_register_options b;
+      sgtd_default_voxel_register_options(&b);
+      if (bad == 0) b.k_neighbors = 2; else if (bad == 1) b.max_iterations = 0; else if (bad == 2) b.reserved = 1; else if (bad == 3) b.voxel_resolution = 0.0; else if (bad == 4) b.neighbor_mode = 6;
+      else b.translation_eps = kNaN;
+      VOX(SGTD_ERR_INVALID, &b, p, 3, off, 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    }
+    const int64_t from_one[5] = {1, 1, 6, 136, 736}, back[5] = {0, 0, 5, 4, 604};
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, from_one, 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, back, 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, nullptr, 3, off, 4, map_off, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    const int32_t moff_one[4] = {1, 1, 1, 3}, moff_back[4] = {0, 2, 1, 3}, mcl_past[3] = {3, 4, 1}, tgt_past[4] = {0, 3, 0, 1}, src_below[4] = {1, -1, 0, 1};
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, moff_one, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, moff_back, map_cloud, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, nullptr, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, mcl_past, nullptr, 3, src, tgt, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, map_cloud, nullptr, 3, src, tgt_past, nullptr, 4);
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, map_cloud, nullptr, 3, src_below, tgt, nullptr, 4);
+    init[40] = kNaN;
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, map_cloud, nullptr, 3, src, tgt, init.data(), 4);
+    map_pose[30] = kNaN;
+    VOX(SGTD_ERR_INVALID, nullptr, p, 3, off, 4, map_off, map_cloud, map_pose.data(), 3, src, tgt, nullptr, 4);
+    // the caps: a cloud too large; too many maps; too many member points; too many correspondences
+    const int64_t large[2] = {0, (int64_t)SGTD_REG_MAX_POINTS + 1};
+    const int32_t zero[2] = {0, 0};
+    VOX(SGTD_ERR_UNSUPPORTED, nullptr, p, 3, large, 1, zero, zero, nullptr, 1, zero, zero, nullptr, 1);
+    {
+      std::vector<int32_t> many((size_t)SGTD_VREG_MAX_MAPS + 2, 0);
+      VOX(SGTD_ERR_UNSUPPORTED, nullptr, p, 3, off, 4, many.data(), map_cloud, nullptr, SGTD_VREG_MAX_MAPS + 1, src, zero, nullptr, 1);
+      const int64_t full[2] = {0, (int64_t)SGTD_REG_MAX_POINTS};
+      const int members = SGTD_VREG_MAX_MEMBER_POINTS / SGTD_REG_MAX_POINTS + 1;
+      const int32_t one_map[2] = {0, members};
+      std::vector<int32_t> same((size_t)members, 0);
+      VOX(SGTD_ERR_UNSUPPORTED, nullptr, p, 3, full, 1, one_map, same.data(), nullptr, 1, zero, zero, nullptr, 1);
+      const int pairs = SGTD_VREG_MAX_CORR / 27 / SGTD_REG_MAX_POINTS + 1;
+      std::vector<int32_t> zeros((size_t)pairs, 0);
+      sgtd_voxel_register_options b;
+      sgtd_default_voxel_register_options(&b);
+      b.neighbor_mode = 27;
+      VOX(SGTD_ERR_UNSUPPORTED, &b, p, 3, full, 1, zero, zero, nullptr, 1, zeros.data(), zeros.data(), nullptr, pairs);
+    }
+#undef VOX
+    voxel_registered(SGTD_OK, 0, 0);
+  }
+
+  // ---- sgtd_scan_keypoints and sgtd_local_map_keypoints
+  void scan_read(int expect, int n_scans, int64_t kept) {
+    const size_t k1 = (size_t)kept + 1;
+    std::vector<int64_t> kp_off((size_t)std::max(n_scans, 0) + 1, -7), cnt(1, -7);
+    std::vector<float> xyz(k1 * 3, -7.f);
+    std::vector<uint32_t> label(k1, 7u);
+    std::vector<int32_t> np(k1, -7), cluster(1100, -7), grid(128, -7);
+    std::vector<double> range(128, -7.0);
+    const float *dx = nullptr; const uint32_t *dl = nullptr;
+    CALL(expect, h, sgtd_result_scan_keypoints(h, kp_off.data(), xyz.data(), label.data(), np.data(), kept, cnt.data()), kp_off, xyz, label, np, cnt);
+    CALL(expect, h, sgtd_result_scan_keypoints(h, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+    CALL(expect, h, sgtd_scan_device_view(h, &dx, &dl));
+    if (expect != SGTD_OK) {
+      CALL(expect, h, sgtd_result_scan_point_clusters(h, 0, cluster.data(), 1100, cnt.data()));
+      CALL(expect, h, sgtd_result_scan_grids(h, 0, grid.data(), range.data()));
+      return;
+    }
+    REQUIRE(cnt[0] == kept && kp_off.back() == kept && xyz[(size_t)kept * 3] == -7.f);
+    if (kept > 0) {
+      CALL(SGTD_ERR_CAPACITY, h, sgtd_result_scan_keypoints(h, nullptr, xyz.data(), nullptr, np.data(), kept - 1, cnt.data()), xyz, np, cnt);
+      CALL(SGTD_OK, h, sgtd_result_scan_keypoints(h, nullptr, nullptr, nullptr, nullptr, kept - 1, cnt.data()), cnt);
+      REQUIRE(sgtd_stub_block_size(dx) >= (size_t)kept * 12 && sgtd_stub_block_size(dl) >= (size_t)kept * 4);
+    }
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_scan_keypoints(h, nullptr, nullptr, nullptr, nullptr, -1, cnt.data()));
+    for (int s = 0; s < n_scans; s++) {
+      CALL(SGTD_OK, h, sgtd_result_scan_point_clusters(h, s, nullptr, 0, cnt.data()), cnt);
+      const int64_t need = cnt[0];
+      if (need > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_scan_point_clusters(h, s, cluster.data(), need - 1, cnt.data()), cluster, cnt);
+      CALL(SGTD_OK, h, sgtd_result_scan_point_clusters(h, s, cluster.data(), need, cnt.data()), cluster, cnt);
+      CALL(SGTD_OK, h, sgtd_result_scan_grids(h, s, grid.data(), range.data()), grid, range);
+      CALL(SGTD_OK, h, sgtd_result_scan_grids(h, s, nullptr, nullptr));
+    }
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_scan_point_clusters(h, n_scans, cluster.data(), 1100, cnt.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_scan_grids(h, n_scans, grid.data(), range.data()));
+  }
+  void scan_keypoints() {
+    note("sgtd_scan_keypoints");
+    const Clouds one(rng, 3, {1025}), two(rng, 4, {1025, 7}), hollow(rng, 3, {0, 0});      // (1025: two tiles of SGTD_SCAN_TILE)
+    const int64_t none[1] = {0};
+    scan_read(SGTD_ERR_STATE, 1, 0);
+    CALL(SGTD_OK, h, sgtd_scan_keypoints(h, nullptr, nullptr, 3, nullptr, none, 0, 0));
+    scan_read(SGTD_OK, 0, 0);
+    CALL(SGTD_OK, h, sgtd_scan_keypoints(h, nullptr, nullptr, 3, nullptr, hollow.off.data(), 2, 0));
+    scan_read(SGTD_OK, 2, 0);
+    sgtd_scan_config sc;
+    sgtd_default_scan_config(&sc);
+    for (int on : {0, 1}) {
+      timing(on);
+      S.voxels = 40; S.kept = on ? 3 : 0;
+      CALL(SGTD_OK, h, sgtd_scan_keypoints(h, on ? &sc : nullptr, one.pts.data(), 3, one.lab.data(), one.off.data(), 1, 0));
+      scan_read(SGTD_OK, 1, S.kept);
+      S.kept = on ? 0 : 5;
+      const OnDevice dp(two.pts.data(), two.pts.size() * 4), dl(two.lab.data(), two.lab.size() * 4);
+      CALL(SGTD_OK, h, sgtd_scan_keypoints(h, &sc, dp.as<float>(), 4, dl.as<uint32_t>(), two.off.data(), 2, 1));
+      scan_read(SGTD_OK, 2, S.kept);
+    }
+    timing(0);
+    // every exit of the validation, in its order: the config's INVALID before the caps, its UNSUPPORTED after them
+    const float *p = one.pts.data();
+    const uint32_t *l = one.lab.data();
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, nullptr, p, 3, l, one.off.data(), -1, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, nullptr, p, 3, l, nullptr, 1, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, nullptr, p, 5, l, one.off.data(), 1, 0));
+    sgtd_scan_config bad = sc, wide = sc;
+    bad.start_r = -1.0; wide.delta_a = 0.1;
+    std::vector<int64_t> many((size_t)SGTD_SCAN_MAX_SCANS + 2, 0);
+    const int64_t from_one[2] = {1, 1026}, back[3] = {0, 5, 4};
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, &bad, p, 3, l, many.data(), SGTD_SCAN_MAX_SCANS + 1, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, nullptr, p, 3, l, from_one, 1, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, nullptr, p, 3, l, back, 2, 0));
+    CALL(SGTD_ERR_INVALID, h, sgtd_scan_keypoints(h, nullptr, p, 3, nullptr, one.off.data(), 1, 0));
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_scan_keypoints(h, &wide, p, 3, l, many.data(), SGTD_SCAN_MAX_SCANS + 1, 0));      // (the caps' text)
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_scan_keypoints(h, &wide, p, 3, l, one.off.data(), 1, 0));                       // (the config's)
+    scan_read(SGTD_OK, 2, 0);
+  }
+  // passes: those the call made, each of which keeps S.kept keypoints (where it has any point)
+  void local_map_read(int expect, int n_anchors, int n_passes) {
+    std::vector<int64_t> kp_off((size_t)n_anchors + 1, -7), mem_off((size_t)n_anchors + 1, -7), merged((size_t)n_anchors + 1, -7), cnt(1, 0);
+    if (expect == SGTD_OK) CALL(SGTD_OK, h, sgtd_result_local_map_keypoints(h, nullptr, nullptr, nullptr, nullptr, 0, cnt.data()), cnt);
+    const int64_t kept = cnt[0];
+    REQUIRE(kept <= S.kept * n_passes);
+    const size_t k1 = (size_t)kept + 1;
+    std::vector<float> xyz(k1 * 3, -7.f), ms(3, -7.f);
+    std::vector<uint32_t> label(k1, 7u);
+    std::vector<int32_t> np(k1, -7), member(64, -7), passes(1, -7);
+    const float *dx = nullptr; const uint32_t *dl = nullptr;
+    CALL(expect, h, sgtd_result_local_map_keypoints(h, kp_off.data(), xyz.data(), label.data(), np.data(), kept, cnt.data()), kp_off, xyz, label, np, cnt);
+    CALL(expect, h, sgtd_result_local_map_keypoints(h, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+    CALL(expect, h, sgtd_result_local_map_members(h, mem_off.data(), nullptr, 0, cnt.data(), merged.data(), passes.data()), mem_off, cnt, merged, passes);
+    CALL(expect, h, sgtd_local_map_device_view(h, &dx, &dl));
+    CALL(expect, h, sgtd_local_map_stage_ms(h, &ms[0], &ms[1], &ms[2]));
+    if (expect != SGTD_OK) return;
+    REQUIRE(kp_off.back() == kept && xyz[(size_t)kept * 3] == -7.f && (passes[0] == n_passes || kept == 0));
+    const int64_t need = cnt[0];
+    if (kept > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_local_map_keypoints(h, nullptr, nullptr, label.data(), nullptr, kept - 1, cnt.data()), label, cnt);
+    REQUIRE(need <= 63);
+    if (need > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_local_map_members(h, nullptr, member.data(), need - 1, cnt.data(), nullptr, nullptr), member, cnt);
+    CALL(SGTD_OK, h, sgtd_result_local_map_members(h, nullptr, member.data(), need, nullptr, nullptr, nullptr), member);
+    REQUIRE(member[(size_t)need] == -7);
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_local_map_members(h, nullptr, member.data(), -1, cnt.data(), nullptr, nullptr));
+  }
+  void local_map_keypoints() {
+    note("sgtd_local_map_keypoints");
+    const Clouds c3(rng, 3, {1025, 7, 0}), c4(rng, 4, {1025, 7, 0});
+    std::vector<float> pose(3 * 12, 0.f);
+    for (int s = 0; s < 3; s++) { pose[(size_t)s * 12] = pose[(size_t)s * 12 + 5] = pose[(size_t)s * 12 + 10] = 1.f; pose[(size_t)s * 12 + 3] = 2.f * s; }
+    const int64_t none[1] = {0};
+    const int32_t anchors[4] = {1, 0, 2, 0};
+    sgtd_local_map_options o;
+    sgtd_default_local_map_options(&o);
+    local_map_read(SGTD_ERR_STATE, 1, 0);
+    CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, nullptr, nullptr, 3, nullptr, none, nullptr, 0, nullptr, 0, 0));
+    local_map_read(SGTD_OK, 0, 0);
+    CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, nullptr, c3.pts.data(), 3, c3.lab.data(), c3.off.data(), pose.data(), 3, anchors, 0, 0));
+    local_map_read(SGTD_OK, 0, 0);
+    for (int on : {0, 1}) {
+      timing(on);
+      // every scan an anchor, one pass; the points with three floats each
+      S.voxels = 40; S.kept = on ? 0 : 4;
+      CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, nullptr, c3.pts.data(), 3, c3.lab.data(), c3.off.data(), pose.data(), 3, nullptr, 3, 0));
+      local_map_read(SGTD_OK, 3, 1);
+      scan_read(SGTD_ERR_STATE, 1, 0);       // (the clustering ran in the scan stage's buffers)
+      // anchors given, three passes (max_pass_points holds one merged cloud of two scans); four floats a point, from the host (16-byte rows) ...
+      o.max_pass_points = 1035; o.max_members = 2;
+      S.kept = 2;
+      CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, &o, c4.pts.data(), 4, c4.lab.data(), c4.off.data(), pose.data(), 3, anchors, 4, 0));
+      local_map_read(SGTD_OK, 4, 3);
+      // ... and on the device four bytes off a 16-byte boundary
+      const OnDevice dp(c4.pts.data(), c4.pts.size() * 4, 4), dl(c4.lab.data(), c4.lab.size() * 4);
+      CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, &o, dp.as<float>(), 4, dl.as<uint32_t>(), c4.off.data(), pose.data(), 3, anchors, 2, 1));
+      local_map_read(SGTD_OK, 2, 2);
+    }
+    timing(0);
+    // a merged cloud larger than a pass may be (on a group: raised on the first device's engine)
+    o.max_pass_points = 100;
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_local_map_keypoints(h, nullptr, &o, c3.pts.data(), 3, c3.lab.data(), c3.off.data(), pose.data(), 3, nullptr, 3, 0));
+    local_map_read(SGTD_ERR_STATE, 3, 0);
+    S.kept = 1;
+    CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, nullptr, c3.pts.data(), 3, c3.lab.data(), c3.off.data(), pose.data(), 3, anchors + 2, 1, 0));      // (a pass without a point)
+    local_map_read(SGTD_OK, 1, 0);
+    CALL(SGTD_OK, h, sgtd_local_map_keypoints(h, nullptr, nullptr, c3.pts.data(), 3, c3.lab.data(), c3.off.data(), pose.data(), 3, anchors, 1, 0));
+    // every exit of the validation, in its order
+    const float *p = c3.pts.data();
+    const uint32_t *l = c3.lab.data();
+    const int64_t *off = c3.off.data();
+    sgtd_scan_config sc, bad, wide;
+    sgtd_default_scan_config(&sc);
+    bad = wide = sc;
+    bad.min_range = 200.0; wide.delta_p = 0.1;
+    std::vector<int64_t> many((size_t)SGTD_SCAN_MAX_SCANS + 2, 0);
+    std::vector<float> many_poses(((size_t)SGTD_SCAN_MAX_SCANS + 1) * 12, 0.f);
+    const int64_t from_one[4] = {1, 1026, 1033, 1033}, back[4] = {0, 1025, 1024, 1032};
+    const int32_t past[2] = {0, 3};
+#define LM(status, cfg_, opt, pts, stride, lab, off_, pose_, ns, anch, na) CALL(status, h, sgtd_local_map_keypoints(h, cfg_, opt, pts, stride, lab, off_, pose_, ns, anch, na, 0))
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, off, pose.data(), -1, nullptr, 0);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, off, pose.data(), 3, anchors, -1);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, nullptr, pose.data(), 3, nullptr, 0);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 2, l, off, pose.data(), 3, nullptr, 0);
+    LM(SGTD_ERR_INVALID, &bad, nullptr, p, 3, l, many.data(), many_poses.data(), SGTD_SCAN_MAX_SCANS + 1, nullptr, 0);
+    for (int k = 0; k < 5; k++) {
+      sgtd_local_map_options b;
+      sgtd_default_local_map_options(&b);
+      if (k == 0) b.radius = -1.0; else if (k == 1) b.max_members = -1; else if (k == 2) b.reserved = 1; else if (k == 3) b.max_pass_points = -1; else b.max_pass_points = (int64_t)SGTD_SCAN_MAX_POINTS + 1;
+      LM(SGTD_ERR_INVALID, nullptr, &b, p, 3, l, off, pose.data(), 3, nullptr, 0);
+    }
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, from_one, pose.data(), 3, nullptr, 0);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, back, pose.data(), 3, nullptr, 0);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, nullptr, 3, l, off, pose.data(), 3, nullptr, 0);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, off, nullptr, 3, nullptr, 0);
+    LM(SGTD_ERR_INVALID, nullptr, nullptr, p, 3, l, off, pose.data(), 3, past, 2);
+    LM(SGTD_ERR_UNSUPPORTED, &wide, nullptr, p, 3, l, many.data(), many_poses.data(), SGTD_SCAN_MAX_SCANS + 1, nullptr, 0);
+    LM(SGTD_ERR_UNSUPPORTED, &wide, nullptr, p, 3, l, off, pose.data(), 3, nullptr, 0);
+#undef LM
+    local_map_read(SGTD_OK, 1, 1);
+  }
+
+  // ---- sgtd_consistent_loops, sgtd_relax_poses
+  void consistent_read(int expect, int64_t n) {
+    const size_t m = (size_t)std::max<int64_t>(n, 1), words = (m + 63) / 64;
+    std::vector<int32_t> in_set(m, -7), degree(m, -7), pick(m, -7);
+    std::vector<double> thr(2, -7.0);
+    std::vector<uint64_t> rows(m * words, 7u);
+    CALL(expect, h, sgtd_result_consistent(h, in_set.data(), degree.data(), pick.data(), thr.data()), in_set, degree, pick, thr);
+    CALL(expect, h, sgtd_result_consistent(h, nullptr, nullptr, nullptr, nullptr));
+    CALL(expect, h, sgtd_result_consistency_rows(h, 0, n, rows.data()), rows);
+    if (expect != SGTD_OK) return;
+    if (n > 1) CALL(SGTD_OK, h, sgtd_result_consistency_rows(h, 1, n - 1, rows.data()), rows);
+    CALL(SGTD_OK, h, sgtd_result_consistency_rows(h, n, 0, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_consistency_rows(h, 0, n + 1, rows.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_consistency_rows(h, -1, 0, rows.data()));
+    if (n > 0) CALL(SGTD_ERR_INVALID, h, sgtd_result_consistency_rows(h, 0, n, nullptr));
+  }
+  void consistent_loops() {
+    note("sgtd_consistent_loops");
+    const int n = 70;       // (two words a row)
+    std::vector<uint32_t> fa((size_t)n), fb((size_t)n);
+    std::vector<double> rel((size_t)n * 12, 0.0);
+    std::vector<float> pa((size_t)n * 12, 0.f);
+    for (int k = 0; k < n; k++) {
+      fa[(size_t)k] = (uint32_t)(k % 5); fb[(size_t)k] = (uint32_t)(k % 7 + 5);
+      rel[(size_t)k * 12] = rel[(size_t)k * 12 + 4] = rel[(size_t)k * 12 + 8] = 1.0; rel[(size_t)k * 12 + 9] = 0.25 * k;
+      pa[(size_t)k * 12] = pa[(size_t)k * 12 + 5] = pa[(size_t)k * 12 + 10] = 1.f;
+    }
+    std::vector<int32_t> n_set(1, -7);
+    consistent_read(SGTD_ERR_STATE, 5);
+    CALL(SGTD_OK, h, sgtd_consistent_loops(h, 0, nullptr, nullptr, nullptr, nullptr, 0.5, 0.1, n_set.data()), n_set);
+    consistent_read(SGTD_OK, 0);
+    for (int on : {0, 1}) {
+      timing(on);
+      CALL(SGTD_OK, h, sgtd_consistent_loops(h, 5, fa.data(), fb.data(), rel.data(), nullptr, 0.5, 0.1, n_set.data()), n_set);
+      consistent_read(SGTD_OK, 5);
+      CALL(SGTD_OK, h, sgtd_consistent_loops(h, n, on ? fa.data() : nullptr, fb.data(), rel.data(), pa.data(), 1.5, 0.2, n_set.data()), n_set);
+      consistent_read(SGTD_OK, n);
+    }
+    timing(0);
+    CALL(SGTD_ERR_INVALID, h, sgtd_consistent_loops(h, -1, fa.data(), fb.data(), rel.data(), nullptr, 0.5, 0.1, n_set.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_consistent_loops(h, 5, nullptr, fb.data(), rel.data(), nullptr, 0.5, 0.1, n_set.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_consistent_loops(h, 5, fa.data(), fb.data(), rel.data(), nullptr, -1.0, 0.1, n_set.data()));
+    CALL(SGTD_ERR_INVALID, h, sgtd_consistent_loops(h, 5, fa.data(), fb.data(), rel.data(), nullptr, 0.5, 4.0, n_set.data()));
+    consistent_read(SGTD_OK, n);       // (the results stay)
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_consistent_loops(h, (int64_t)SGTD_MAX_LOOP_EDGES + 1, fa.data(), fb.data(), rel.data(), nullptr, 0.5, 0.1, n_set.data()));
+    consistent_read(SGTD_ERR_STATE, 5);       // (they are gone)
+  }
+  void relaxed_read(int expect, int n, int m) {
+    std::vector<double> pose((size_t)std::max(n, 1) * 12, -7.0), cost((size_t)std::max(m, 1) * 2, -7.0);
+    CALL(expect, h, sgtd_result_relaxed(h, pose.data(), cost.data()), pose, cost);
+    CALL(expect, h, sgtd_result_relaxed(h, nullptr, cost.data()), cost);
+    CALL(expect, h, sgtd_result_relaxed(h, nullptr, nullptr));
+  }
+  void relax_poses() {
+    note("sgtd_relax_poses");
+    const int n = 4, m = 4;
+    std::vector<double> pose0((size_t)n * 12, 0.0), meas((size_t)m * 12, 0.0), wt((size_t)m, 2.0), wr((size_t)m, 0.5);
+    for (int v = 0; v < n; v++) { pose0[(size_t)v * 12] = pose0[(size_t)v * 12 + 5] = pose0[(size_t)v * 12 + 10] = 1.0; pose0[(size_t)v * 12 + 3] = 1.0 * v; }
+    for (int k = 0; k < m; k++) { meas[(size_t)k * 12] = meas[(size_t)k * 12 + 5] = meas[(size_t)k * 12 + 10] = 1.0; meas[(size_t)k * 12 + 3] = 1.0; }
+    const int32_t ni[4] = {0, 1, 2, 3}, nj[4] = {1, 2, 3, 0};
+    const uint8_t fixed[4] = {1, 0, 0, 1}, all[4] = {1, 1, 1, 1};
+    std::vector<sgtd_relax_report> rep(1);
+    sgtd_relax_options o;
+    sgtd_default_relax_options(&o);
+    Env blocks("SGTD_RELAX_MAX_BLOCKS", "2");
+    relaxed_read(SGTD_ERR_STATE, n, m);
+    CALL(SGTD_OK, h, sgtd_relax_poses(h, n, pose0.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rep.data()), rep);
+    relaxed_read(SGTD_OK, 0, 0);
+    CALL(SGTD_OK, h, sgtd_relax_poses(h, n, pose0.data(), nullptr, m, ni, nj, meas.data(), nullptr, nullptr, nullptr, rep.data()), rep);
+    relaxed_read(SGTD_OK, n, m);
+    o.max_inner = 2;
+    CALL(SGTD_OK, h, sgtd_relax_poses(h, n, pose0.data(), fixed, m, ni, nj, meas.data(), wt.data(), wr.data(), &o, nullptr));
+    relaxed_read(SGTD_OK, n, m);
+    CALL(SGTD_OK, h, sgtd_relax_poses(h, n, pose0.data(), all, m, ni, nj, meas.data(), wt.data(), nullptr, &o, rep.data()), rep);
+    // a solve that never ends, in the second group of SGTD_RELAX_GROUP iterations
+    S.relax_ends = false;
+    o.max_outer = SGTD_RELAX_GROUP + 1;
+    CALL(SGTD_ERR_HIP, h, sgtd_relax_poses(h, n, pose0.data(), fixed, m, ni, nj, meas.data(), wt.data(), wr.data(), &o, rep.data()));
+    S.relax_ends = true;
+    relaxed_read(SGTD_ERR_STATE, n, m);
+    CALL(SGTD_OK, h, sgtd_relax_poses(h, n, pose0.data(), fixed, m, ni, nj, meas.data(), wt.data(), wr.data(), &o, rep.data()), rep);
+    CALL(SGTD_ERR_INVALID, h, sgtd_relax_poses(h, n, nullptr, fixed, m, ni, nj, meas.data(), nullptr, nullptr, nullptr, nullptr));
+    o.cg_tol = 0.0;
+    CALL(SGTD_ERR_INVALID, h, sgtd_relax_poses(h, n, pose0.data(), fixed, m, ni, nj, meas.data(), nullptr, nullptr, &o, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_relax_poses(h, n, pose0.data(), fixed, m, ni, ni, meas.data(), nullptr, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_relax_poses(h, (int64_t)SGTD_RELAX_MAX_NODES + 1, pose0.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    relaxed_read(SGTD_OK, n, m);       // (the results stay)
+  }
+
+  // ---- sgtd_pose_consensus_rows, sgtd_pose_consensus
+  void consensus_read(int expect, int nq, int cn, bool batch) {
+    const size_t m = (size_t)std::max(nq, 1);
+    std::vector<double> pose(m * 12, -7.0), support(m, -7.0), t2(m, -7.0), trace(m, -7.0), thr(2, -7.0), best(m, -7.0), rel(m * 12, -7.0);
+    std::vector<int32_t> n_valid(m, -7), n_set(m, -7), seed(m, -7), degree((size_t)cn, -7), pick((size_t)cn, -7), cand(m, -7), frame(m, -7), query(m, -7);
+    std::vector<uint64_t> mask(m, 7u), rows((size_t)cn, 7u);
+    std::vector<uint32_t> fa(m, 7u), fb(m, 7u);
+    std::vector<int64_t> cnt(1, -7);
+    CALL(expect, h, sgtd_result_consensus(h, 0, nq, pose.data(), n_valid.data(), n_set.data(), seed.data(), mask.data(), support.data(), t2.data(), trace.data(), thr.data()), pose, n_valid, n_set, seed,
+         mask, support, t2, trace, thr);
+    CALL(expect, h, sgtd_result_consensus(h, 0, nq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    CALL(nq > 0 ? expect : (expect == SGTD_OK ? SGTD_ERR_INVALID : expect), h, sgtd_result_consensus_rows(h, 0, rows.data(), degree.data(), pick.data()), rows, degree, pick);
+    const int choice = expect != SGTD_OK || batch ? expect : SGTD_ERR_STATE;       // (the choice needs the batch form)
+    CALL(choice, h, sgtd_search_loop_consensus(h, 1, cand.data(), frame.data(), best.data(), n_set.data()), cand, frame, best, n_set);
+    CALL(choice, h, sgtd_result_consensus_edges(h, 2, query.data(), fa.data(), fb.data(), nullptr, best.data(), nq, cnt.data()), query, fa, fb, best, cnt);
+    if (expect != SGTD_OK) return;
+    if (nq > 1) {
+      CALL(SGTD_OK, h, sgtd_result_consensus(h, 1, nq - 1, pose.data(), nullptr, n_set.data(), nullptr, nullptr, nullptr, t2.data(), nullptr, nullptr), pose, n_set, t2);
+      CALL(SGTD_OK, h, sgtd_result_consensus_rows(h, nq - 1, nullptr, nullptr, nullptr));
+    }
+    CALL(SGTD_OK, h, sgtd_result_consensus(h, nq, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, thr.data()), thr);
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_consensus(h, 0, nq + 1, pose.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    CALL(SGTD_ERR_INVALID, h, sgtd_result_consensus_rows(h, nq, rows.data(), nullptr, nullptr));
+    if (batch && cnt[0] > 0) CALL(SGTD_ERR_CAPACITY, h, sgtd_result_consensus_edges(h, 2, query.data(), nullptr, fb.data(), nullptr, nullptr, cnt[0] - 1, cnt.data()), query, fb, cnt);
+  }
+  void pose_consensus() {
+    note("sgtd_pose_consensus_rows");
+    const int nq = 3, cn = 4;
+    std::vector<int32_t> n_cand = {4, 0, 1}, frame((size_t)nq * cn);
+    std::vector<double> score((size_t)nq * cn), rel((size_t)nq * cn * 12, 0.0);
+    for (int i = 0; i < nq * cn; i++) { frame[(size_t)i] = i % 6; score[(size_t)i] = 0.5 + 0.01 * i; rel[(size_t)i * 12] = rel[(size_t)i * 12 + 5] = rel[(size_t)i * 12 + 10] = 1.0; rel[(size_t)i * 12 + 3] = 0.1 * i; }
+    consensus_read(SGTD_ERR_STATE, nq, cn, false);
+    CALL(SGTD_OK, h, sgtd_pose_consensus_rows(h, 0, cn, nullptr, nullptr, nullptr, nullptr, 0.5, 0.1));
+    consensus_read(SGTD_OK, 0, cn, false);
+    CALL(SGTD_OK, h, sgtd_pose_consensus_rows(h, nq, cn, n_cand.data(), frame.data(), score.data(), rel.data(), 0.5, 0.1));
+    consensus_read(SGTD_OK, nq, cn, false);
+    CALL(SGTD_ERR_UNSUPPORTED, h, sgtd_pose_consensus_rows(h, (int64_t)0x7FFFFFFF / SGTD_MAX_CAND + 1, cn, n_cand.data(), frame.data(), score.data(), rel.data(), 0.5, 0.1));
+    consensus_read(SGTD_ERR_STATE, nq, cn, false);
+    CALL(SGTD_OK, h, sgtd_pose_consensus_rows(h, nq, cn, n_cand.data(), frame.data(), score.data(), rel.data(), 0.5, 0.1));
+    CALL(SGTD_ERR_INVALID, h, sgtd_pose_consensus_rows(h, nq, SGTD_MAX_CAND + 1, n_cand.data(), frame.data(), score.data(), rel.data(), 0.5, 0.1));
+    CALL(SGTD_ERR_INVALID, h, sgtd_pose_consensus_rows(h, nq, cn, n_cand.data(), nullptr, score.data(), rel.data(), 0.5, 0.1));
+    consensus_read(SGTD_ERR_STATE, nq, cn, false);      // (an invalid call takes the results with it)
+
+    // the batch form: a table, a batch of frames, its verification (the candidate tables and scores of the stages' scenario)
+    note("sgtd_pose_consensus");
+    S.stages = true; S.expect_order = -1;
+    const int n_frames = 130, bq = 5, bcn = cfg.candidate_num;
+    for (int f = 0; f < n_frames; f++) { Descs d = random_descs(rng, 60, (uint32_t)f); sgtd_desc_soa s = d.soa(); OK(sgtd_add(h, &s, 60)); }
+    OK(sgtd_finalize(h));
+    std::vector<uint32_t> ids;
+    std::vector<float> poses;
+    for (int f = 0; f < n_frames; f++) { ids.push_back((uint32_t)f); for (int i = 0; i < 12; i++) poses.push_back(i % 5 == 0 ? 1.f : (i % 4 == 3 ? 0.5f * f : 0.f)); }
+    CALL(SGTD_OK, h, sgtd_set_frame_poses(h, ids.data(), poses.data(), (int64_t)ids.size()));
+    Keypoints kp;
+    for (int q = 0; q < bq; q++) kp.add(rng, 12 + q);
+    CALL(SGTD_OK, h, sgtd_query_frames(h, kp.xyz.data(), kp.label.data(), kp.off.data(), bq, 0));
+    CALL(SGTD_ERR_STATE, h, sgtd_pose_consensus(h, 0.5, 0.1, 0));
+    CALL(SGTD_OK, h, sgtd_verify(h));
+    CALL(SGTD_ERR_STATE, h, sgtd_pose_consensus(h, 0.5, 0.1, SGTD_CONSENSUS_REFINED));
+    CALL(SGTD_ERR_STATE, h, sgtd_pose_consensus(h, 0.5, 0.1, SGTD_CONSENSUS_ALIGNED));
+    CALL(SGTD_ERR_INVALID, h, sgtd_pose_consensus(h, 0.5, 0.1, SGTD_CONSENSUS_REFINED | SGTD_CONSENSUS_ALIGNED));
+    CALL(SGTD_ERR_INVALID, h, sgtd_pose_consensus(h, 0.5, -0.1, 0));
+    consensus_read(SGTD_ERR_STATE, bq, bcn, true);
+    CALL(SGTD_OK, h, sgtd_pose_consensus(h, 0.5, 0.1, 0));
+    consensus_read(SGTD_OK, bq, bcn, true);
+    CALL(SGTD_OK, h, sgtd_refine_poses(h, 1));
+    CALL(SGTD_OK, h, sgtd_pose_consensus(h, 0.75, 0.2, SGTD_CONSENSUS_REFINED));
+    consensus_read(SGTD_OK, bq, bcn, true);
+    CALL(SGTD_OK, h, sgtd_align_keypoints(h, 0.5, 2, 0, nullptr, nullptr, nullptr));
+    CALL(SGTD_OK, h, sgtd_pose_consensus(h, 0.75, 0.2, SGTD_CONSENSUS_ALIGNED));
+    consensus_read(SGTD_OK, bq, bcn, true);
+    // the consistency pass over the store's poses, ids outside it among the edges
+    {
+      const uint32_t fa[4] = {0, 3, 129, 500}, fb[4] = {7, 9, 2, 1};
+      std::vector<double> r4(4 * 12, 0.0);
+      for (int k = 0; k < 4; k++) r4[(size_t)k * 12] = r4[(size_t)k * 12 + 4] = r4[(size_t)k * 12 + 8] = 1.0;
+      std::vector<int32_t> n_set(1, -7);
+      CALL(SGTD_OK, h, sgtd_consistent_loops(h, 4, fa, fb, r4.data(), nullptr, 0.5, 0.1, n_set.data()), n_set);
+      consistent_read(SGTD_OK, 4);
+    }
+    // a new batch takes the batch form's results with it
+    CALL(SGTD_OK, h, sgtd_query_frames(h, kp.xyz.data(), kp.label.data(), kp.off.data(), bq, 0));
+    consensus_read(SGTD_ERR_STATE, bq, bcn, true);
+    S.stages = false;
+  }
+
+  void run(int n_dev_) {
+    n_dev = n_dev_;
+    if (g_transcript) fprintf(g_transcript, "# ---- the cloud and graph stages on %d device(s)\n", n_dev);
+    if (n_dev == 1) OK(sgtd_create(&cfg, &h));
+    else { const int ids[2] = {0, 0}; OK(sgtd_create_multi(&cfg, ids, 2, &h)); }
+    g_last = h;
+    register_clouds();
+    register_voxels();
+    scan_keypoints();
+    local_map_keypoints();
+    consistent_loops();
+    relax_poses();
+    pose_consensus();
+    OK(sgtd_destroy(h));
+    h = nullptr; g_last = nullptr;
+  }
+
+  // every kernel these stages can launch was launched (lm_gather_kernel in its three forms)
+  static void check_coverage() {
+    const struct { const char *kernel; int forms; } want[] = {
+        {"reg_cov_kernel", 1}, {"reg_init_kernel", 1}, {"reg_search_kernel", 1}, {"reg_match_kernel", 1}, {"reg_lin_kernel", 1}, {"reg_trial_kernel", 1}, {"reg_final_kernel", 1},
+        {"vreg_keys_kernel", 1}, {"vreg_ranges_kernel", 1}, {"vreg_voxel_kernel", 1}, {"vreg_init_kernel", 1}, {"vreg_corr_kernel", 1}, {"vreg_lin_kernel", 1}, {"vreg_trial_kernel", 1},
+        {"vreg_final_kernel", 1}, {"scan_init_kernel", 1}, {"scan_point_kernel", 1}, {"scan_rings_kernel", 1}, {"scan_keys_kernel", 1}, {"scan_heads_kernel", 1}, {"scan_voxels_kernel", 1},
+        {"scan_links_kernel", 1}, {"scan_hook_kernel", 1}, {"scan_jump_kernel", 1}, {"scan_component_kernel", 1}, {"scan_cluster_keys_kernel", 1}, {"scan_offsets_kernel", 1},
+        {"scan_cluster_ids_kernel", 1}, {"scan_point_clusters_kernel", 1}, {"scan_sum_wave_kernel", 1}, {"scan_sum_block_kernel", 1}, {"lm_members_kernel", 1}, {"lm_segments_kernel", 1},
+        {"lm_gather_kernel", 3}, {"cons_prepare_kernel", 1}, {"cons_pair_kernel", 1}, {"cons_init_kernel", 1}, {"cons_count_kernel", 1}, {"cons_select_kernel", 1}, {"consensus_kernel", 1},
+        {"relax_init_kernel", 1}, {"relax_edge_kernel", 1}, {"relax_ctl_kernel", 1}, {"relax_setup_kernel", 1}, {"relax_cg_edge_kernel", 1}, {"relax_cg_node_kernel", 1},
+        {"relax_cg_update_kernel", 1}, {"relax_retract_kernel", 1}};
+    for (const auto &w : want) {
+      int n = 0;
+      for (const std::string &k : g_launched) n += names(k.c_str(), w.kernel);
+      if (n != w.forms) { fprintf(stderr, "engine_driver: %d forms of %s launched, not %d\n", n, w.kernel, w.forms); exit(1); }
+    }
+  }
+};
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -1357,6 +2244,18 @@ int main(int argc, char **argv) {
 
   // ---- the forms of the query pipeline, launch by launch
   { SelectForms sf{S, rng, cfg}; sf.run(); }
+
+  // ---- the cloud and graph stages, launch by launch, on one device and on two "devices" behind one handle
+  {
+    g_launched.clear();
+    g_tracing = true;
+    sgtd_stub_set_trace(g_transcript);
+    for (int n_dev : {1, 2}) { CloudStages cs{S, rng, cfg}; cs.run(n_dev); }
+    sgtd_stub_set_trace(nullptr);
+    g_tracing = false;
+    CloudStages::check_coverage();
+    printf("cloud and graph stages: %zu kernel forms launched\n", g_launched.size());
+  }
   g_last = nullptr;
   if (g_transcript) fclose(g_transcript);
   REQUIRE(sgtd_stub_device_blocks() == 0 && sgtd_stub_device_bytes() == 0);       // every device buffer was freed

@@ -11,7 +11,8 @@
 //   streams, events = everything is synchronous and complete
 //   trace           = while a scenario has it on (sgtd_stub_set_trace), one line per kernel launch (name as registered, grid, block,
 //                     dynamic LDS), per hipMemsetAsync (value, bytes, the room of the block it starts), per hipFuncSetAttribute
-//                     (kernel, value) and per hipEventRecord (the event's number in creation order) — no addresses: two builds
+//                     (kernel, value) and per hipEventRecord (the event's number, counted from its first record: an event made and never
+//                     recorded enqueues nothing and takes no number) — no addresses: two builds
 //                     of the engine whose traces are equal enqueue the same work
 // Test infrastructure only: nothing in the product links it.
 #include <hip/hip_runtime_api.h>
@@ -211,12 +212,14 @@ hipError_t hipMemGetAddressRange(hipDeviceptr_t *base, size_t *size, hipDevicept
 // ---- streams and events
 hipError_t hipStreamSynchronize(hipStream_t) { g_waits++; return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned int) { g_waits++; return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new Event{0, g_events++}); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new Event{0, -1}); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete reinterpret_cast<Event *>(e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
-  if (g_trace) fprintf(g_trace, "event %d\n", reinterpret_cast<Event *>(e)->id);
-  reinterpret_cast<Event *>(e)->t = now_ms(); return hipSuccess;
+  Event *ev = reinterpret_cast<Event *>(e);
+  if (ev->id < 0) ev->id = g_events++;
+  if (g_trace) fprintf(g_trace, "event %d\n", ev->id);
+  ev->t = now_ms(); return hipSuccess;
 }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(reinterpret_cast<Event *>(b)->t - reinterpret_cast<Event *>(a)->t); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { g_waits++; return hipSuccess; }

@@ -97,7 +97,7 @@ def test_lattice_600_one_anchor_per_pass(g):
 
 
 def test_anchors_4097(mods):
-    """4097 anchors: two passes, the first of SGTD_SCAN_MAX_SCANS anchors — scan_device with S = 4096, scan_bits(S) = 13,
+    """4097 anchors: two passes, the first of SGTD_SCAN_MAX_SCANS anchors — scan_device with S = 4096, key_bits(S) = 13,
     the largest drop key, 1 GiB of ring bounds — the second of one.  A handle of its own, closed at once."""
     h = mods[0].STDescManager()
     try:

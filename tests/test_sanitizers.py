@@ -91,7 +91,24 @@ def test_engine_host_code_under_asan_and_ubsan(tmp_path):
     candidate-export buffer, both overflows in each list form.  Every launch (name, grid, block, dynamic LDS, the scalars
     the hook can type), memset, attribute and event record is a transcript line; the driver checks from the trace that
     every kernel form these functions can launch was launched (all but the three sweeps with 64-bit probe offsets, which
-    need a 4-GB probe layout) and that the scenario's device peak stays under 2 GB."""
+    need a 4-GB probe layout) and that the scenario's device peak stays under 2 GB.
+
+    Then, with the trace still on, the stages that do not belong to a batch — sgtd_register_clouds, sgtd_register_voxels,
+    sgtd_scan_keypoints, sgtd_local_map_keypoints, sgtd_consistent_loops, sgtd_relax_poses and both forms of
+    sgtd_pose_consensus — on one device and on two "devices" behind one handle, whose results live on the first device's
+    engine.  The hook leaves behind the few words their host code reads back (the count of unfinished solves, the maps' voxel
+    ranges, the count of voxels, the keypoints' offsets, an anchor's members, the greedy choice's and the relaxation's state)
+    at the smallest shapes that walk every host path: clouds of 0, 5, 130 and 600 points with slices of one tile (two source
+    tiles, two target slices), an empty source and an empty target, no pair, points from the host and on the device, given
+    and absent start and map poses, solves that end in the first and in the second group of rounds and solves that never
+    end (the bound's error), maps without members, without member points and with empty and non-empty voxel ranges, the three
+    neighbour modes, a scan of 1025 points (two tiles), runs that keep no and a few keypoints, local maps in one and in
+    several passes with lm_gather_kernel in its three forms and a pass without a point, timing off and on.  Every getter runs
+    before its stage (the state error and its text), with every output NULL, with a capacity one short of the need
+    (SGTD_ERR_CAPACITY, the count still reported) and in full; a failure raised on the first device's engine arrives as the
+    group handle's text.  Every SGTD_ERR_INVALID and SGTD_ERR_UNSUPPORTED exit of the four cloud entry points is taken once,
+    in the order the checks come, and what each failed call leaves of the earlier results is read back.  The hook checks the
+    room of every array these launches are handed, and the driver that every kernel the stages can launch was launched."""
     san = ASAN + ["-fno-omit-frame-pointer"]
     hip = [HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-host-only", "-Wno-unused-function", "-Wno-unused-result"] + san
     objs = {n: str(tmp_path / (n + ".o")) for n in ("accel", "driver", "stub", "fatbin")}
