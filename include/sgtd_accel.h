@@ -1251,6 +1251,91 @@ int sgtd_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_search, float
  * length until they fit (no result depends on it) */
 void sgtd_register_tiles(int *src_tile, int *tgt_tile, int *slice);
 
+/* Dense clouds of map frames, keyed by global frame id, kept on the device with their covariances: frame frame_ids[i]
+ * gets the points pt_off[i] .. pt_off[i+1] of `points` (stride_floats floats each, x y z first; a host array, or with
+ * device_ptrs != 0 a device array; frame_ids and pt_off are the host's).  They are the targets of sgtd_register_stored
+ * and sgtd_register_stored_loops.
+ * The call behaves like sgtd_set_frame_keypoints: the clouds are copied at the call and are settings of the handle;
+ * later calls overwrite; an id repeated within one call: the last one wins; points == NULL with n > 0 forgets the clouds of
+ * those ids; frame_ids == NULL with n == 0 forgets all, frees the device memory and forgets k_neighbors and plane_eps;
+ * ids may name frames not (yet) added; sgtd_add*, sgtd_remove_frames and sgtd_load_table leave them alone, the table file
+ * does not hold them, a view (sgtd_attach_table) has a store of its own, and a multi-device handle keeps the store on its
+ * first device, where sgtd_register_clouds runs.  A frame stored with zero points "has a cloud" (count 0).  Non-finite
+ * coordinates are stored as given (the covariance rule says what they do).
+ * Kept per frame: its points (x, y, z) and each point's covariance by sgtd_register_clouds' covariance rule with this
+ * call's k_neighbors (3..32) and plane_eps, computed once, at the call.  The first call on an empty store fixes
+ * k_neighbors and plane_eps; a later one with other values: SGTD_ERR_STATE (forget all first).
+ * Memory: no host copy; 84 bytes a point on the device (12 of coordinates, 72 of covariance) in one arena, the stored
+ * clouds at its front in arrival order; sgtd_register_stored packs its own clouds behind them for the length of the
+ * call, so the arena also holds the room a call's clouds needed.  An overwritten or forgotten cloud stays as dead points
+ * until they outnumber the live ones or the arena has to grow; then the live clouds are copied, in order, into new
+ * arrays.  The arena always grows into new arrays that replace the old ones once they are complete, never by freeing
+ * first: a device allocation that fails leaves the store exactly as it was before the call.
+ * h == NULL, n < 0, frame_ids == NULL with n > 0, with points != NULL and n > 0: pt_off NULL, a stride other than 3 or 4,
+ * pt_off[0] != 0 or decreasing offsets, k_neighbors outside 3..32, plane_eps not finite and > 0: SGTD_ERR_INVALID; an id
+ * >= max_frame_n: SGTD_ERR_FRAME_LIMIT; a cloud of more than SGTD_REG_MAX_POINTS points, or more than
+ * SGTD_CLOUD_STORE_MAX_POINTS live points in the store after the call: SGTD_ERR_UNSUPPORTED (sgtd_last_error says
+ * which).  All before the device is touched and with the store unchanged.
+ * sgtd_frame_clouds_info: frames that have a cloud, their points, the bytes of the arena's device arrays, the settings
+ * (0 and 0.0 while there are none); any output may be NULL.
+ * sgtd_result_frame_cloud: the stored points (3 floats each) and covariances (row-major 3x3) of one frame; *n = its
+ * count, or -1 where the frame has no cloud (SGTD_OK); more than capacity: SGTD_ERR_CAPACITY (the first `capacity`
+ * points written).  xyz or cov may be NULL. */
+#define SGTD_CLOUD_STORE_MAX_POINTS (1 << 27)
+int sgtd_set_frame_clouds(sgtd_handle h, const uint32_t *frame_ids, const int64_t *pt_off /* n + 1 */,
+                          const float *points, int stride_floats /* 3 or 4 */, int64_t n,
+                          int k_neighbors, double plane_eps, int device_ptrs /* points only */);
+int sgtd_frame_clouds_info(sgtd_handle h, int64_t *n_frames, int64_t *n_points, int64_t *device_bytes,
+                           int32_t *k_neighbors, double *plane_eps);
+int sgtd_result_frame_cloud(sgtd_handle h, uint32_t frame, float *xyz /*[cap*3]*/, double *cov /*[cap*9]*/,
+                            int64_t capacity, int64_t *n /* -1: the frame has no cloud */);
+
+/* sgtd_register_clouds with the targets read from the cloud store: pair k registers the call's cloud src_cloud[k] onto
+ * the stored cloud of frame tgt_frame[k].  The results are those of sgtd_register_clouds on the call's clouds followed
+ * by the named frames' stored clouds, with the same options, bit for bit: pose, fitness, cost, n_matched, iterations,
+ * status, every match and d2, and the source clouds' covariances (a cloud's covariances depend on that cloud alone, and
+ * no result of a pair depends on the other pairs or on the tiling).  Covariances are computed only for the call's clouds
+ * that some pair names; no target point crosses the link and no target covariance is computed again.
+ * opt->k_neighbors or opt->plane_eps different from the store's: SGTD_ERR_STATE; a target frame without a stored cloud:
+ * SGTD_ERR_INVALID (sgtd_last_error names the frame); everything sgtd_register_clouds rejects or caps is rejected or
+ * capped the same way, its caps applied to the call's own clouds and pairs.  All before the device is touched and with
+ * the earlier results kept.  The call has result buffers of its own: it never touches sgtd_register_clouds' or
+ * sgtd_register_voxels' results, and they never touch its; its results last until the next sgtd_register_stored or
+ * sgtd_register_stored_loops call that passes its argument checks, or sgtd_destroy (later sgtd_set_frame_clouds calls
+ * do not change them).  A view uses its own store; a multi-device handle runs the call on its first device.
+ * The getters follow the sgtd_result_register* family: sgtd_result_stored_matches' tgt_index counts within the frame's
+ * cloud; sgtd_result_stored_covariances gives the call's clouds'.
+ *
+ * sgtd_register_stored_loops forms the pairs on the device from the pending batch's verification (after sgtd_verify,
+ * sgtd_verify_masked, or sgtd_search_frame with flags 0); cloud q of the call is query q's raw cloud (pt_off: n_queries
+ * + 1 offsets).  Per query: the candidates with a verification result (score >= 0) in descending score, ties in
+ * ascending candidate index; the first max_per_query of them (clamped to candidate_num); of those, the ones whose frame
+ * has no stored cloud are dropped, not replaced by the next candidate.  The rows are in (query, rank) order, init is the
+ * relative pose of the stage `start` names (sgtd_result_verify's, sgtd_result_refined's, sgtd_result_aligned's), and the
+ * getters above return the results per row; sgtd_result_stored_pairs returns the rows (*n = their count; more than
+ * capacity: SGTD_ERR_CAPACITY; after sgtd_register_stored: SGTD_ERR_STATE).  The host reads the rows back once, to size
+ * the tiles.  The call adds results and changes none of the batch's.
+ * max_per_query < 0, an unknown start and what sgtd_register_stored rejects: SGTD_ERR_INVALID; no verification of the
+ * pending batch, or the named stage has not run on it: SGTD_ERR_STATE; a multi-device handle: SGTD_ERR_UNSUPPORTED (its
+ * batch results live on several engines: form the pairs and use sgtd_register_stored).  sgtd_register_clouds' caps on
+ * the clouds are checked before the device is touched; its caps on the pairs can only be checked once the pairs are
+ * formed, and a call that fails there leaves no results. */
+int sgtd_register_stored(sgtd_handle h, const sgtd_register_options *opt /* NULL = defaults */,
+                         const float *points, int stride_floats, const int64_t *pt_off /* host, n_clouds + 1 */, int n_clouds,
+                         const int32_t *src_cloud, const uint32_t *tgt_frame, const double *init_pose /* [n_pairs*12], NULL = identity */,
+                         int n_pairs, int device_ptrs /* points only */);
+int sgtd_result_stored_registered(sgtd_handle h, double *pose /*[n*12]*/, double *fitness, double *cost /*[n*2] first, last*/,
+                                  int32_t *n_matched, int32_t *iterations, int32_t *status);
+int sgtd_result_stored_covariances(sgtd_handle h, int cloud, double *cov /*[cap*9]*/, int64_t capacity, int64_t *n);
+int sgtd_result_stored_matches(sgtd_handle h, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n);
+int sgtd_stored_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total);
+enum { SGTD_START_VERIFY = 0, SGTD_START_REFINED = 1, SGTD_START_ALIGNED = 2 };
+int sgtd_register_stored_loops(sgtd_handle h, const sgtd_register_options *opt /* NULL = defaults */,
+                               const float *points, int stride_floats, const int64_t *pt_off /* n_queries + 1 */,
+                               int max_per_query, int start, int device_ptrs /* points only */);
+int sgtd_result_stored_pairs(sgtd_handle h, int32_t *query, int32_t *cand, int32_t *frame, double *init /*[n*12]*/,
+                             int64_t capacity, int64_t *n);
+
 /* Voxelised GICP of clouds against voxel maps on the device (fast_gicp::FastVGICP, fast_vgicp_impl.hpp /
  * fast_vgicp_voxel.hpp): the target of a pair is a map of Gaussian voxels accumulated from any number of posed clouds,
  * and a source point is matched by looking up the voxel it lands in (and its 6 or 26 neighbours), so an iteration's cost

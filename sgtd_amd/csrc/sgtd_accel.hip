@@ -14,6 +14,7 @@
 #include <limits>
 #include <memory>
 #include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "build_kernel.hip.h"
@@ -35,6 +36,7 @@
 #include "relax_kernels.hip.h"
 #include "register_kernels.hip.h"
 #include "voxel_register_kernels.hip.h"
+#include "cloud_store_kernels.hip.h"
 #include "consensus_kernels.hip.h"
 #include "scan_kernels.hip.h"
 #include "local_map_kernels.hip.h"
@@ -351,6 +353,38 @@ struct sgtd_engine {
   std::vector<unsigned char> rg_host_named;
   std::vector<int> rg_host_up;           // (the source of the index upload)
   LapClock rg_clock;
+  // sgtd_set_frame_clouds (cloud_store_kernels.hip.h): the cloud store, settings of the handle.  st: the arena (points,
+  // covariances and the clouds' offsets on the device: the stored clouds are its first clouds, "slots", in arrival
+  // order, a call's own clouds follow for the length of the call) and what the host knows of it.  A slot whose frame was
+  // overwritten or forgotten is dead until the arena is rebuilt.  st_slot_of: frame id -> live slot or -1, on the host;
+  // st_table: its device copy, made for st_table_serial (sgtd_register_stored_loops).  st_k == 0: no settings yet.
+  struct CloudSlot { u32 frame; int64_t first, count; bool live; };
+  struct CloudArena {
+    DevBuf pts, cov, off;
+    int64_t cap = 0, off_cap = 0;    // points and offset rows the buffers hold
+    int64_t used = 0, live = 0;      // points of all slots, of the live ones
+    std::vector<CloudSlot> slots;
+  } st;
+  std::vector<int> st_slot_of;
+  int64_t st_frames = 0;             // frames that have a cloud
+  int st_k = 0;
+  double st_eps = 0.0;
+  DevBuf st_stage, st_idx, st_table;
+  u64 st_serial = 0, st_table_serial = ~0ull;
+  // sgtd_register_stored / sgtd_register_stored_loops: independent of the batch and of sgtd_register_clouds' and
+  // sgtd_register_voxels' buffers.  sr_in .. sr_ctl as rg_*; sr_pts: the call's points when the host gave them; sr_cov:
+  // the covariances of the call's clouds, copied out of the arena; sr_pairs: the loops form's counts, their scan, pair
+  // rows and start poses.  sr_n < 0: no results; sr_rows: the loops form's rows (query, candidate, frame) on the host,
+  // sr_loops: the results are that form's.
+  DevBuf sr_in, sr_pts, sr_cov, sr_part, sr_match, sr_state, sr_out, sr_ctl, sr_pairs;
+  int sr_n = -1;
+  bool sr_loops = false;
+  std::vector<int64_t> sr_host_off;
+  std::vector<int> sr_host_soff, sr_host_up;
+  std::vector<unsigned char> sr_host_named;
+  std::vector<int32_t> sr_rows;
+  size_t sr_init_off = 0;            // the rows' start poses within sr_pairs
+  LapClock sr_clock;
   // sgtd_register_voxels (voxel_register_kernels.hip.h): independent of the batch and of sgtd_register_clouds' buffers.
   // VR_IN: the call's index arrays, offsets and poses; VR_PTS: the points when the host gave them; VR_COV: a covariance per
   // point; VR_KEY_* / VR_VAL_*: the sort's pairs; VR_FLAGS .. VR_MAP_VOX: the voxels' heads, keys, first points and the
@@ -2274,14 +2308,16 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state,
                     &e->cs_in, &e->cs_out,
                     &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl,
-                    &e->rg_in, &e->rg_pts, &e->rg_cov, &e->rg_part, &e->rg_match, &e->rg_state, &e->rg_out, &e->rg_ctl};
+                    &e->rg_in, &e->rg_pts, &e->rg_cov, &e->rg_part, &e->rg_match, &e->rg_state, &e->rg_out, &e->rg_ctl,
+                    &e->st.pts, &e->st.cov, &e->st.off, &e->st_stage, &e->st_idx, &e->st_table,
+                    &e->sr_in, &e->sr_pts, &e->sr_cov, &e->sr_part, &e->sr_match, &e->sr_state, &e->sr_out, &e->sr_ctl, &e->sr_pairs};
   for (DevBuf *b : bufs) free_buf(*b);
   for (DevBuf &b : e->sk) free_buf(b);
   for (DevBuf &b : e->lm) free_buf(b);
   for (DevBuf &b : e->vr) free_buf(b);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
-  for (LapClock *k : {&e->rg_clock, &e->vr_clock, &e->lm_clock}) k->destroy();
+  for (LapClock *k : {&e->rg_clock, &e->sr_clock, &e->vr_clock, &e->lm_clock}) k->destroy();
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
@@ -5153,72 +5189,91 @@ int gicp_rounds(sgtd_engine *c, const char *call, const RegParams &P, int unfini
   return SGTD_OK;
 }
 
-int reg_run(sgtd_engine *c, const sgtd_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
-            const int32_t *src, const int32_t *tgt, const double *init, int n) {
+// Where a dense run keeps its buffers and finds its clouds: sgtd_register_clouds' own arrays, or sgtd_register_stored's
+// over the cloud store's arena, whose stored clouds come before the call's.
+struct RegSite {
+  const char *call;
+  DevBuf &in, &part, &match, &state, &out, &ctl;
+  std::vector<int> &up, &soff;      // the source of the index upload; src_off [n + 1]
+  LapClock &clock;
+  const float *pts;                 // the points of every cloud the kernels may name, on the device
+  int stride;
+  DevBuf *cov_buf;                  // the call's own covariances, grown to its points; NULL: `cov` is where they go
+  double *cov;
+  const long long *d_off;           // the clouds' offsets where they are on the device already; NULL: pt_off is uploaded
+  int first;                        // the index the kernels know the call's cloud 0 by
+  const double *d_init;             // the start poses where they are on the device already (init is NULL then)
+};
+
+// One dense GICP run.  pt_off, n_clouds, named, src: the call's clouds, which of them need covariances, the pairs'
+// sources; tgt, tgt_n: the targets as the kernels know them, and their sizes
+int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, const int64_t *pt_off, int n_clouds, const unsigned char *named,
+            const int32_t *src, const int32_t *tgt, const int64_t *tgt_n, const double *init, int n) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
   const bool timed = c->timing;
-  LapClock &clock = c->rg_clock;
+  LapClock &clock = S.clock;
   CHK(clock.start(c, timed));
   const size_t total = (size_t)pt_off[n_clouds];
-  // what the getters need, and the tiles: of the pairs' sources, of the clouds some pair names
-  c->rg_host_off.assign(pt_off, pt_off + n_clouds + 1);
-  c->rg_host_named.assign((size_t)n_clouds, 0);
+  // the tiles: of the pairs' sources, of the clouds that need covariances
   int64_t max_tgt = 0;
-  for (int k = 0; k < n; k++) {
-    c->rg_host_named[(size_t)src[k]] = 1; c->rg_host_named[(size_t)tgt[k]] = 1;
-    max_tgt = std::max<int64_t>(max_tgt, pt_off[tgt[k] + 1] - pt_off[tgt[k]]);
-  }
-  GicpIndex G(c->rg_host_up);
-  G.tiles(pt_off, n_clouds, src, n, c->rg_host_named.data(), &c->rg_host_soff);
+  for (int k = 0; k < n; k++) max_tgt = std::max<int64_t>(max_tgt, tgt_n[k]);
+  GicpIndex G(S.up);
+  G.tiles(pt_off, n_clouds, src, n, named, &S.soff);
   if (n == 0) return SGTD_OK;      // (a run without a pair: no cloud is named, nothing comes back)
-  const int total_src = c->rg_host_soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
+  const int total_src = S.soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
   long long slice = (long long)reg_slice_tiles() * SGTD_REG_TILE;
   auto slices_of = [&](long long len) { return (size_t)std::max<long long>((max_tgt + len - 1) / len, 1); };
   while ((size_t)total_src * slices_of(slice) > kRegPartMax) slice *= 2;
   const size_t n_slices = slices_of(slice);
 
-  // the index upload: src, tgt, src_off, the tiles
+  // the index upload: src, tgt, src_off, the tiles (clouds by the index the kernels know them by)
   G.u_src = G.put(src, (size_t)n);
   const size_t u_tgt = G.put(tgt, (size_t)n);
-  G.u_soff = G.put(c->rg_host_soff.data(), (size_t)n + 1);
+  G.u_soff = G.put(S.soff.data(), (size_t)n + 1);
+  if (S.first) {
+    for (int k = 0; k < n; k++) S.up[G.u_src + (size_t)k] += S.first;
+    for (int &cl : G.ctile_cloud) cl += S.first;
+  }
   G.put_tiles();
   const size_t o_off = 0, o_init = o_off + relax_up((size_t)(n_clouds + 1) * sizeof(int64_t)), o_idx = o_init + relax_up((size_t)n * 12 * sizeof(double)),
                in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1);
   const RegOut out((size_t)n, false);
-  CHK(ensure(c, c->rg_in, in_bytes));
-  CHK(ensure(c, c->rg_cov, std::max<size_t>(total, 1) * 9 * sizeof(double)));
-  CHK(ensure(c, c->rg_part, ts * n_slices * (sizeof(double) + sizeof(int))));
-  CHK(ensure(c, c->rg_match, ts * (10 * sizeof(double) + sizeof(int))));
-  CHK(ensure(c, c->rg_state, (size_t)n * sizeof(RegState)));
-  CHK(ensure(c, c->rg_out, out.bytes()));
-  CHK(ensure(c, c->rg_ctl, 64));
-  char *in = c->rg_in.as<char>();
-  CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
+  CHK(ensure(c, S.in, in_bytes));
+  if (S.cov_buf) CHK(ensure(c, *S.cov_buf, std::max<size_t>(total, 1) * 9 * sizeof(double)));
+  CHK(ensure(c, S.part, ts * n_slices * (sizeof(double) + sizeof(int))));
+  CHK(ensure(c, S.match, ts * (10 * sizeof(double) + sizeof(int))));
+  CHK(ensure(c, S.state, (size_t)n * sizeof(RegState)));
+  CHK(ensure(c, S.out, out.bytes()));
+  CHK(ensure(c, S.ctl, 64));
+  char *in = S.in.as<char>();
+  if (!S.d_off) CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
   if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
   CHK(h2d(c, in + o_idx, G.up.data(), G.up.size() * sizeof(int)));
+  const double *d_init = init ? reinterpret_cast<const double *>(in + o_init) : S.d_init;
 
   RegParams P;
   const int *di = reinterpret_cast<const int *>(in + o_idx);
-  gicp_params(P, G, points, stride, in + o_off, di, n, ts, c->rg_cov.as<double>(), c->rg_state.p, c->rg_ctl.p, out, c->rg_out.p,
+  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts, S.cov_buf ? S.cov_buf->as<double>() : S.cov,
+              S.state.p, S.ctl.p, out, S.out.p,
               gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.max_corr_dist, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps,
                            o.plane_eps));
   P.tgt = di + u_tgt; P.slice = (int)slice;
-  P.part_d2 = c->rg_part.as<double>(); P.part_j = reinterpret_cast<int *>(P.part_d2 + ts * n_slices);
-  P.md2 = c->rg_match.as<double>(); P.M = P.md2 + ts; P.mj = reinterpret_cast<int *>(P.M + 9 * ts);
+  P.part_d2 = S.part.as<double>(); P.part_j = reinterpret_cast<int *>(P.part_d2 + ts * n_slices);
+  P.md2 = S.match.as<double>(); P.M = P.md2 + ts; P.mj = reinterpret_cast<int *>(P.M + 9 * ts);
 
   int unfinished = 0;
   for (int k = 0; k < n; k++)
-    if (pt_off[src[k] + 1] > pt_off[src[k]] && pt_off[tgt[k] + 1] > pt_off[tgt[k]]) unfinished++;
+    if (pt_off[src[k] + 1] > pt_off[src[k]] && tgt_n[k] > 0) unfinished++;
   CHK(h2d(c, P.unfinished, &unfinished, sizeof(int)));
   hipStream_t s = c->stream;
   const dim3 sgrid((unsigned)n_tiles, (unsigned)n_slices);
   if (timed) { HIPCHK(hipEventRecord(clock.ev[2], s)); HIPCHK(hipEventRecord(clock.ev[0], s)); }
   if (P.n_ctiles) reg_cov_kernel<<<P.n_ctiles, SGTD_REG_THREADS, 0, s>>>(P);
   if (timed) CHK(clock.lap(c, 0));
-  reg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, init ? reinterpret_cast<const double *>(in + o_init) : nullptr);
+  reg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, d_init);
   HIPCHK(hipGetLastError());
-  CHK(gicp_rounds(c, "sgtd_register_clouds", P, unfinished, [&]() -> int {
+  CHK(gicp_rounds(c, S.call, P, unfinished, [&]() -> int {
     reg_search_kernel<<<sgrid, SGTD_REG_THREADS, 0, s>>>(P, 0);
     if (timed) CHK(clock.lap(c, 1));
     reg_match_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, 0);
@@ -5241,6 +5296,22 @@ int reg_run(sgtd_engine *c, const sgtd_register_options &o, const float *points,
   }
   CHK(xfer_sync(c));
   return SGTD_OK;
+}
+
+// sgtd_register_clouds' run: every cloud is the call's, and a cloud some pair names needs covariances
+int reg_clouds_run(sgtd_engine *c, const sgtd_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
+                   const int32_t *src, const int32_t *tgt, const double *init, int n) {
+  // what the getters need
+  c->rg_host_off.assign(pt_off, pt_off + n_clouds + 1);
+  c->rg_host_named.assign((size_t)n_clouds, 0);
+  std::vector<int64_t> tgt_n((size_t)n);
+  for (int k = 0; k < n; k++) {
+    c->rg_host_named[(size_t)src[k]] = 1; c->rg_host_named[(size_t)tgt[k]] = 1;
+    tgt_n[(size_t)k] = pt_off[tgt[k] + 1] - pt_off[tgt[k]];
+  }
+  const RegSite S{"sgtd_register_clouds", c->rg_in, c->rg_part, c->rg_match, c->rg_state, c->rg_out, c->rg_ctl, c->rg_host_up, c->rg_host_soff, c->rg_clock,
+                  points, stride, &c->rg_cov, nullptr, nullptr, 0, nullptr};
+  return reg_run(c, S, o, pt_off, n_clouds, c->rg_host_named.data(), src, tgt, tgt_n.data(), init, n);
 }
 
 const char kNoRegistered[] = "no registered clouds: sgtd_register_clouds has not run";
@@ -5288,7 +5359,7 @@ int sgtd_register_clouds(sgtd_handle e, const sgtd_register_options *opt, const 
   run.on_device([&](sgtd_engine *c) -> int {
     const float *d_pts = nullptr;
     CHK(points_on_device(c, c->rg_pts, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
-    return reg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
+    return reg_clouds_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
   });
   return run.end(n_pairs);
 }
@@ -5343,6 +5414,525 @@ int sgtd_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float
   if (ms_search) *ms_search = c->rg_clock.ms[1];
   if (ms_rest) *ms_rest = c->rg_clock.ms[2];
   if (ms_total) *ms_total = c->rg_clock.ms[3];
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_set_frame_clouds / sgtd_register_stored / sgtd_register_stored_loops (cloud_store_kernels.hip.h) ----
+namespace {
+using CloudSlot = sgtd_engine::CloudSlot;
+using CloudArena = sgtd_engine::CloudArena;
+constexpr int64_t kStoreInitPoints = 1 << 16;      // the arena's first capacity, unless the SGTD_CLOUD_STORE_INIT_POINTS hook (tests) gives another
+
+int64_t store_init_points() {
+  const char *hook = getenv("SGTD_CLOUD_STORE_INIT_POINTS");
+  return hook && atoll(hook) > 0 ? std::min<int64_t>(atoll(hook), SGTD_CLOUD_STORE_MAX_POINTS) : kStoreInitPoints;
+}
+
+// a new device array for the arena: the old one is neither freed nor touched, so a failure leaves the store as it was
+int store_alloc(sgtd_engine *e, DevBuf &b, size_t bytes) {
+  void *p = nullptr;
+  const hipError_t st_ = hipMalloc(&p, std::max<size_t>(bytes, 1));
+  if (st_ != hipSuccess) {
+    (void)hipGetLastError();
+    e->err = "hipMalloc of " + std::to_string(bytes) + " bytes for the cloud store: " + hipGetErrorString(st_);
+    return SGTD_ERR_HIP;
+  }
+  e->stats.device_allocs_total++;
+  b.p = p; b.bytes = bytes;
+  return SGTD_OK;
+}
+void store_free(CloudArena &A) { free_buf(A.pts); free_buf(A.cov); free_buf(A.off); }
+
+// A change of the arena that is not the store's until store_commit: the slots that die (`dies`, indices into the
+// current arena), and `next` where the change needs new arrays (the live slots, in order, copied into them).  Leaving
+// the scope frees whichever arrays are not the store's: next's after a failure, the old ones after a commit.
+struct StoreChange {
+  std::vector<int> dies;
+  CloudArena next;
+  bool rebuilt = false;
+  ~StoreChange() { store_free(next); }
+};
+
+// Room behind the slots for `pts` points and `clouds` clouds.  *A = the arena to write to: the store's own where they
+// fit and the dead points (the dying slots included) do not outnumber the live ones plus `incoming`; otherwise W.next,
+// NEW arrays into which the live slots are compacted and renumbered.  The store itself is unchanged either way.
+int store_prepare(sgtd_engine *e, StoreChange &W, int64_t pts, int64_t clouds, int64_t incoming, CloudArena **A) {
+  CloudArena &cur = e->st;
+  std::vector<unsigned char> dying(cur.slots.size(), 0);
+  int64_t live = cur.live;
+  for (int s : W.dies) { dying[(size_t)s] = 1; live -= cur.slots[(size_t)s].count; }
+  const int64_t dead = cur.used - live;
+  const bool fits = cur.pts.p && cur.cap >= cur.used + pts && cur.off_cap >= (int64_t)cur.slots.size() + clouds + 1;
+  *A = &cur;
+  if (fits && dead <= live + incoming) return SGTD_OK;
+  CloudArena &N = W.next;
+  std::vector<long long> move;      // from [n_live + 1], to [n_live + 1]
+  for (size_t s = 0; s < cur.slots.size(); s++)
+    if (cur.slots[s].live && !dying[s]) N.slots.push_back(cur.slots[s]);
+  const size_t nl = N.slots.size();
+  move.assign(2 * (nl + 1), 0);
+  int64_t at = 0;
+  for (size_t s = 0; s < nl; s++) {
+    move[s] = N.slots[s].first; move[nl + 1 + s] = at;
+    N.slots[s].first = at;
+    at += N.slots[s].count;
+  }
+  move[nl] = 0; move[2 * nl + 1] = at;
+  N.used = N.live = at;
+  const int64_t need = at + pts, rows = (int64_t)nl + clouds + 1;
+  N.cap = std::max<int64_t>(need + need / 2, cur.cap ? 1 : store_init_points());      // (the hook: a store's first capacity)
+  N.off_cap = std::max<int64_t>(2 * rows, 64);
+  CHK(store_alloc(e, N.pts, (size_t)N.cap * 3 * sizeof(float)));
+  CHK(store_alloc(e, N.cov, (size_t)N.cap * 9 * sizeof(double)));
+  CHK(store_alloc(e, N.off, (size_t)N.off_cap * sizeof(long long)));
+  CHK(ensure(e, e->st_idx, move.size() * sizeof(long long)));
+  CHK(h2d(e, e->st_idx.p, move.data(), move.size() * sizeof(long long)));
+  if (at > 0) {
+    StoreMoveParams P;
+    P.pts_in = cur.pts.as<float>(); P.cov_in = cur.cov.as<double>(); P.pts_out = N.pts.as<float>(); P.cov_out = N.cov.as<double>();
+    P.from = e->st_idx.as<long long>(); P.to = P.from + nl + 1; P.n_live = (int)nl; P.total = at;
+    const int grid = (int)std::min<long long>(grid_for(at * 12, SGTD_STORE_THREADS), (long long)e->n_cus * 16);
+    store_compact_kernel<<<grid, SGTD_STORE_THREADS, 0, e->stream>>>(P);
+    HIPCHK(hipGetLastError());
+  }
+  // the slots' offsets: row s = the first point of slot s, row n_live = the points in use
+  CHK(h2d(e, N.off.p, move.data() + nl + 1, (nl + 1) * sizeof(long long)));
+  CHK(xfer_sync(e));      // (move is this function's)
+  W.rebuilt = true;
+  *A = &W.next;
+  return SGTD_OK;
+}
+
+// the change becomes the store's: the work enqueued on the new arrays has been waited for
+void store_commit(sgtd_engine *e, StoreChange &W) {
+  CloudArena &cur = e->st;
+  if (W.rebuilt) {
+    std::swap(cur, W.next);      // (the old arrays are W's now, and go with it)
+    std::fill(e->st_slot_of.begin(), e->st_slot_of.end(), SGTD_STORE_NONE);
+    for (size_t s = 0; s < cur.slots.size(); s++) e->st_slot_of[cur.slots[s].frame] = (int)s;
+    e->st_frames = (int64_t)cur.slots.size();
+  } else {
+    for (int s : W.dies) {
+      CloudSlot &sl = cur.slots[(size_t)s];
+      sl.live = false;
+      cur.live -= sl.count;
+      e->st_slot_of[sl.frame] = SGTD_STORE_NONE;
+      e->st_frames--;
+    }
+  }
+  static std::atomic<u64> serial{0};
+  e->st_serial = ++serial;
+}
+
+// room for a call's own clouds behind the slots (a rebuild renumbers the slots: frames are looked up after this)
+int store_room(sgtd_engine *e, int64_t pts, int64_t clouds) {
+  StoreChange W;
+  CloudArena *A = nullptr;
+  CHK(store_prepare(e, W, pts, clouds, 0, &A));
+  if (W.rebuilt) store_commit(e, W);
+  return SGTD_OK;
+}
+
+// `total` points of the given stride, on the device, into the arena from point `first` on
+int store_pack(sgtd_engine *e, CloudArena &A, const float *d_src, int stride, int64_t total, int64_t first) {
+  if (total == 0) return SGTD_OK;
+  const int grid = (int)std::min<long long>(grid_for(total * 3, SGTD_STORE_THREADS), (long long)e->n_cus * 16);
+  store_pack_kernel<<<grid, SGTD_STORE_THREADS, 0, e->stream>>>(d_src, stride, total, A.pts.as<float>() + (size_t)first * 3);
+  HIPCHK(hipGetLastError());
+  return SGTD_OK;
+}
+
+// the offsets of `n` clouds that follow the arena's slots: rows [slots .. slots + n] of its offsets
+int store_tail_rows(sgtd_engine *e, CloudArena &A, const int64_t *pt_off, int64_t n, std::vector<long long> &rows) {
+  rows.resize((size_t)n + 1);
+  for (int64_t i = 0; i <= n; i++) rows[(size_t)i] = A.used + pt_off[i];
+  return h2d(e, A.off.as<long long>() + A.slots.size(), rows.data(), rows.size() * sizeof(long long));
+}
+
+// the set call on the home engine: the arguments are checked, `win[i]` says that cloud i is the last of its id
+int store_set(sgtd_engine *e, const uint32_t *frame_ids, const int64_t *pt_off, const float *points, int stride, int64_t n, const std::vector<unsigned char> &win,
+              int k, double eps, int device_ptrs) {
+  PinScope pin(e);
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  StoreChange W;
+  int64_t incoming = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (!win[(size_t)i]) continue;
+    const size_t id = frame_ids[i];
+    if (id < e->st_slot_of.size() && e->st_slot_of[id] != SGTD_STORE_NONE) W.dies.push_back(e->st_slot_of[id]);
+    if (points) incoming += pt_off[i + 1] - pt_off[i];
+  }
+  if (!points && W.dies.empty()) return SGTD_OK;
+  const int64_t total = points ? pt_off[n] : 0;
+  CloudArena *A = nullptr;
+  CHK(store_prepare(e, W, total, points ? n : 0, incoming, &A));
+  if (!points) { store_commit(e, W); return SGTD_OK; }
+  // the call's clouds become the slots behind the last one: packed, their offsets, the covariances of the ones that stay
+  const float *d_src = nullptr;
+  CHK(points_on_device(e, e->st_stage, points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(store_pack(e, *A, d_src, stride, total, A->used));
+  std::vector<long long> rows;
+  CHK(store_tail_rows(e, *A, pt_off, n, rows));
+  const int first = (int)A->slots.size();
+  std::vector<int> tiles[2];
+  for (int64_t i = 0; i < n; i++) {
+    if (!win[(size_t)i]) continue;
+    for (int64_t f = 0; f < pt_off[i + 1] - pt_off[i]; f += SGTD_REG_THREADS) { tiles[0].push_back(first + (int)i); tiles[1].push_back((int)f); }
+  }
+  const size_t nt = tiles[0].size();
+  if (nt) {
+    tiles[0].insert(tiles[0].end(), tiles[1].begin(), tiles[1].end());
+    CHK(ensure(e, e->st_idx, 2 * nt * sizeof(int)));
+    CHK(h2d(e, e->st_idx.p, tiles[0].data(), 2 * nt * sizeof(int)));
+    RegParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.pts = A->pts.as<float>(); P.stride = 3; P.pt_off = A->off.as<long long>(); P.cov = A->cov.as<double>();
+    P.ctile_cloud = e->st_idx.as<int>(); P.ctile_first = P.ctile_cloud + nt; P.n_ctiles = (int)nt;
+    P.o.k = k; P.o.plane_eps = eps;
+    reg_cov_kernel<<<P.n_ctiles, SGTD_REG_THREADS, 0, e->stream>>>(P);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(xfer_sync(e));      // (rows, tiles and the caller's points are read until here)
+  store_commit(e, W);
+  CloudArena &cur = e->st;
+  for (int64_t i = 0; i < n; i++) {
+    const size_t id = frame_ids[i];
+    const bool live = win[(size_t)i] != 0;
+    cur.slots.push_back(CloudSlot{frame_ids[i], cur.used + pt_off[i], pt_off[i + 1] - pt_off[i], live});
+    if (!live) continue;
+    if (id >= e->st_slot_of.size()) e->st_slot_of.resize(id + 1, SGTD_STORE_NONE);
+    e->st_slot_of[id] = (int)cur.slots.size() - 1;
+    cur.live += pt_off[i + 1] - pt_off[i];
+    e->st_frames++;
+  }
+  cur.used += total;
+  e->st_k = k; e->st_eps = eps;
+  if (!device_ptrs) free_buf(e->st_stage);      // (once a map: not worth keeping)
+  return SGTD_OK;
+}
+
+const char kNoStored[] = "no stored registration: sgtd_register_stored has not run";
+
+// The stored call's run on the home engine, behind store_room: the call's clouds packed behind the slots, their
+// offsets, the dense run over the arena (targets = slots), the call's covariances copied out of the arena
+int stored_run(sgtd_engine *c, const sgtd_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds, int device_ptrs,
+               const int32_t *src, const int32_t *slot, const double *init, const double *d_init, int n) {
+  sgtd_engine *e = c;
+  CloudArena &A = c->st;
+  c->sr_host_off.assign(pt_off, pt_off + n_clouds + 1);
+  c->sr_host_named.assign((size_t)n_clouds, 0);
+  std::vector<int64_t> tgt_n((size_t)n);
+  for (int k = 0; k < n; k++) {
+    c->sr_host_named[(size_t)src[k]] = 1;
+    tgt_n[(size_t)k] = A.slots[(size_t)slot[k]].count;
+  }
+  if (n == 0) { c->sr_host_soff.assign(1, 0); return SGTD_OK; }
+  const int64_t total = pt_off[n_clouds];
+  const float *d_src = nullptr;
+  CHK(points_on_device(c, c->sr_pts, points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(store_pack(c, A, d_src, stride, total, A.used));
+  std::vector<long long> rows;
+  CHK(store_tail_rows(c, A, pt_off, n_clouds, rows));
+  const RegSite S{"sgtd_register_stored", c->sr_in, c->sr_part, c->sr_match, c->sr_state, c->sr_out, c->sr_ctl, c->sr_host_up, c->sr_host_soff, c->sr_clock,
+                  A.pts.as<float>(), 3, nullptr, A.cov.as<double>(), A.off.as<long long>(), (int)A.slots.size(), d_init};
+  CHK(reg_run(c, S, o, pt_off, n_clouds, c->sr_host_named.data(), src, slot, tgt_n.data(), init, n));
+  CHK(ensure(c, c->sr_cov, std::max<size_t>((size_t)total, 1) * 9 * sizeof(double)));
+  if (total) HIPCHK(hipMemcpyAsync(c->sr_cov.p, A.cov.as<double>() + (size_t)A.used * 9, (size_t)total * 9 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  CHK(xfer_sync(c));
+  return SGTD_OK;
+}
+
+// what both stored calls check of their options and of the store's settings
+int stored_options(const sgtd_register_options *opt, sgtd_register_options *o) {
+  sgtd_default_register_options(o);
+  if (opt) *o = *opt;
+  if (!gicp_options_ok(o->k_neighbors, o->max_iterations, o->lm_max_trials, o->reserved, o->lm_init_lambda_factor, o->rotation_eps, o->translation_eps,
+                       o->plane_eps) ||
+      !(o->max_corr_dist > 0.0))
+    return SGTD_ERR_INVALID;
+  return SGTD_OK;
+}
+int stored_settings(sgtd_engine *e, const char *call, const sgtd_register_options &o) {
+  const sgtd_engine *c = home_engine(e);
+  if (c->st_k == 0 || (o.k_neighbors == c->st_k && o.plane_eps == c->st_eps)) return SGTD_OK;
+  e->err = std::string(call) + ": k_neighbors and plane_eps must be the cloud store's (" + std::to_string(c->st_k) + ", " + std::to_string(c->st_eps) + ")";
+  return SGTD_ERR_STATE;
+}
+}  // namespace
+
+extern "C" {
+
+int sgtd_set_frame_clouds(sgtd_handle e, const uint32_t *frame_ids, const int64_t *pt_off, const float *points, int stride_floats, int64_t n,
+                          int k_neighbors, double plane_eps, int device_ptrs) {
+  if (!e || n < 0 || n > std::numeric_limits<int>::max() - 1 || (n > 0 && !frame_ids)) return SGTD_ERR_INVALID;
+  const bool put = n > 0 && points;
+  if (put) {
+    if (!cloud_set_ok(pt_off, (int)n, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+    if (k_neighbors < 3 || k_neighbors > SGTD_REG_MAX_K || !(std::isfinite(plane_eps) && plane_eps > 0.0)) return SGTD_ERR_INVALID;
+  }
+  for (int64_t i = 0; i < n; i++)
+    if (frame_ids[i] >= (uint32_t)e->cfg.max_frame_n) return SGTD_ERR_FRAME_LIMIT;
+  sgtd_engine *c = home_engine(e);
+  if (n == 0) {
+    if (frame_ids) return SGTD_OK;
+    (void)hipSetDevice(c->cfg.device_id);
+    (void)hipStreamSynchronize(c->stream);
+    store_free(c->st);
+    c->st = CloudArena();
+    for (DevBuf *b : {&c->st_stage, &c->st_idx, &c->st_table}) free_buf(*b);
+    c->st_slot_of.clear(); c->st_frames = 0; c->st_k = 0; c->st_eps = 0.0;
+    c->st_serial = 0; c->st_table_serial = ~0ull;
+    return SGTD_OK;
+  }
+  // the last cloud of an id wins; the store's live points behind the call
+  std::vector<unsigned char> win((size_t)n, 0);
+  std::unordered_set<uint32_t> seen;
+  int64_t live = c->st.live;
+  for (int64_t i = n - 1; i >= 0; i--) {
+    if (!seen.insert(frame_ids[i]).second) continue;
+    win[(size_t)i] = 1;
+    const size_t id = frame_ids[i];
+    if (id < c->st_slot_of.size() && c->st_slot_of[id] != SGTD_STORE_NONE) live -= c->st.slots[(size_t)c->st_slot_of[id]].count;
+    if (put) live += pt_off[i + 1] - pt_off[i];
+  }
+  if (put) {
+    for (int64_t i = 0; i < n; i++)
+      if (pt_off[i + 1] - pt_off[i] > SGTD_REG_MAX_POINTS) {
+        e->err = "sgtd_set_frame_clouds takes at most " + std::to_string(SGTD_REG_MAX_POINTS) + " points a cloud";
+        return SGTD_ERR_UNSUPPORTED;
+      }
+    if (live > SGTD_CLOUD_STORE_MAX_POINTS) {
+      e->err = "sgtd_set_frame_clouds: the cloud store holds at most " + std::to_string(SGTD_CLOUD_STORE_MAX_POINTS) + " live points";
+      return SGTD_ERR_UNSUPPORTED;
+    }
+    if (c->st_k != 0 && (k_neighbors != c->st_k || plane_eps != c->st_eps)) {
+      e->err = "sgtd_set_frame_clouds: the cloud store was made with k_neighbors " + std::to_string(c->st_k) + " and plane_eps " + std::to_string(c->st_eps) +
+               ": forget all clouds first";
+      return SGTD_ERR_STATE;
+    }
+  }
+  const int st = store_set(c, frame_ids, pt_off, put ? points : nullptr, stride_floats, n, win, k_neighbors, plane_eps, device_ptrs);
+  if (st != SGTD_OK && c != e) e->err = c->err;
+  return st;
+}
+
+int sgtd_frame_clouds_info(sgtd_handle e, int64_t *n_frames, int64_t *n_points, int64_t *device_bytes, int32_t *k_neighbors, double *plane_eps) {
+  if (!e) return SGTD_ERR_INVALID;
+  const sgtd_engine *c = home_engine(e);
+  if (n_frames) *n_frames = c->st_frames;
+  if (n_points) *n_points = c->st.live;
+  if (device_bytes) *device_bytes = (int64_t)(c->st.pts.bytes + c->st.cov.bytes + c->st.off.bytes);
+  if (k_neighbors) *k_neighbors = c->st_k;
+  if (plane_eps) *plane_eps = c->st_eps;
+  return SGTD_OK;
+}
+
+int sgtd_result_frame_cloud(sgtd_handle e, uint32_t frame, float *xyz, double *cov, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = home_engine(e);
+  const int slot = frame < c->st_slot_of.size() ? c->st_slot_of[frame] : SGTD_STORE_NONE;
+  if (slot == SGTD_STORE_NONE) { if (n) *n = -1; return SGTD_OK; }
+  const CloudSlot &sl = c->st.slots[(size_t)slot];
+  if (n) *n = sl.count;
+  const size_t m = (size_t)std::min(sl.count, capacity);
+  CopyOut out(e, c);
+  out.get(xyz, c->st.pts.as<float>() + (size_t)sl.first * 3, m * 3 * sizeof(float));
+  out.get(cov, c->st.cov.as<double>() + (size_t)sl.first * 9, m * 9 * sizeof(double));
+  CHK(out.finish());
+  return sl.count > capacity && (xyz || cov) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_register_stored(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
+                         const int32_t *src_cloud, const uint32_t *tgt_frame, const double *init_pose, int n_pairs, int device_ptrs) {
+  if (!e || n_pairs < 0) return SGTD_ERR_INVALID;
+  if (n_pairs > 0 && (!src_cloud || !tgt_frame)) return SGTD_ERR_INVALID;
+  sgtd_register_options o;
+  CHK(stored_options(opt, &o));
+  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  const int64_t total = pt_off[n_clouds];
+  int64_t total_src = 0;
+  for (int k = 0; k < n_pairs; k++) {
+    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds) return SGTD_ERR_INVALID;
+    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
+  }
+  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
+  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs) || total_src > SGTD_REG_MAX_SOURCE_POINTS) {
+    e->err = gicp_caps_text("sgtd_register_stored") + ", " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " + std::to_string(SGTD_REG_MAX_SOURCE_POINTS) +
+             " source points over the pairs";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  CHK(stored_settings(e, "sgtd_register_stored", o));
+  {
+    const sgtd_engine *c = home_engine(e);
+    for (int k = 0; k < n_pairs; k++)
+      if (tgt_frame[k] >= c->st_slot_of.size() || c->st_slot_of[tgt_frame[k]] == SGTD_STORE_NONE) {
+        e->err = "sgtd_register_stored: frame " + std::to_string(tgt_frame[k]) + " has no stored cloud (sgtd_set_frame_clouds)";
+        return SGTD_ERR_INVALID;
+      }
+  }
+  StageRun<int> run(e, &sgtd_engine::sr_n);
+  run.c->sr_loops = false;
+  run.on_device([&](sgtd_engine *c) -> int {
+    if (n_pairs > 0) CHK(store_room(c, total, n_clouds));
+    std::vector<int32_t> slot((size_t)n_pairs);
+    for (int k = 0; k < n_pairs; k++) slot[(size_t)k] = c->st_slot_of[tgt_frame[k]];
+    return stored_run(c, o, points, stride_floats, pt_off, n_clouds, device_ptrs, src_cloud, slot.data(), init_pose, nullptr, n_pairs);
+  });
+  return run.end(n_pairs);
+}
+
+int sgtd_register_stored_loops(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off,
+                               int max_per_query, int start, int device_ptrs) {
+  if (!e || max_per_query < 0 || start < SGTD_START_VERIFY || start > SGTD_START_ALIGNED) return SGTD_ERR_INVALID;
+  sgtd_register_options o;
+  CHK(stored_options(opt, &o));
+  if (!pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (e->grp) {
+    e->err = "sgtd_register_stored_loops: a multi-device handle's batch results live on several engines: form the pairs and use sgtd_register_stored";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (!e->batch_valid || !e->verified) return needs(e, "sgtd_register_stored_loops", "sgtd_verify");
+  if (start == SGTD_START_REFINED && !e->refined) return needs(e, "sgtd_register_stored_loops", "sgtd_refine_poses");
+  if (start == SGTD_START_ALIGNED && !e->aligned) return needs(e, "sgtd_register_stored_loops", "sgtd_align_keypoints");
+  const int nq = e->nq, cn = e->dc.cand_num, mpq = std::min(max_per_query, cn);
+  if (!cloud_set_ok(pt_off, nq, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  if (!gicp_caps_ok(pt_off, nq, 0)) { e->err = gicp_caps_text("sgtd_register_stored_loops"); return SGTD_ERR_UNSUPPORTED; }
+  CHK(stored_settings(e, "sgtd_register_stored_loops", o));
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(sync_batch(e));
+  const int64_t total = pt_off[nq];
+  const size_t upper = (size_t)nq * mpq;
+  int n = 0;
+  StageRun<int> run(e, &sgtd_engine::sr_n);
+  e->sr_loops = true;
+  e->sr_rows.clear();
+  run.on_device([&](sgtd_engine *c) -> int {
+    std::vector<int32_t> src, slot;
+    if (upper > 0 && c->st_frames > 0) {
+      CHK(store_room(c, total, nq));
+      if (c->st_table_serial != c->st_serial || !c->st_table.p) {
+        CHK(ensure(c, c->st_table, std::max<size_t>(c->st_slot_of.size(), 1) * sizeof(int)));
+        CHK(h2d(c, c->st_table.p, c->st_slot_of.data(), c->st_slot_of.size() * sizeof(int)));
+        c->st_table_serial = c->st_serial;
+      }
+      // the pairs: counts per query, their scan, the rows; the host reads the total and the rows back once
+      const size_t o_count = 0, o_first = o_count + relax_up(((size_t)nq + 1) * sizeof(u32)), o_rows = o_first + relax_up(((size_t)nq + 1) * sizeof(u32)),
+                   o_init = o_rows + relax_up(upper * sizeof(int4));
+      CHK(ensure(c, c->sr_pairs, o_init + upper * 12 * sizeof(double)));
+      char *pb = c->sr_pairs.as<char>();
+      c->sr_init_off = o_init;
+      StorePairParams P;
+      P.score = c->v_score.as<double>(); P.n_cand = c->n_cand.as<int>(); P.cand_frame = c->cand_frame.as<int>();
+      P.pose = start == SGTD_START_REFINED ? c->r_pose.as<double>() : start == SGTD_START_ALIGNED ? c->a_pose.as<double>() : c->v_pose.as<double>();
+      P.slot_of = c->st_table.as<int>(); P.n_ids = (u32)c->st_slot_of.size();
+      P.cand_num = cn; P.nq = nq; P.max_per_query = mpq;
+      P.count = reinterpret_cast<u32 *>(pb + o_count); P.first = reinterpret_cast<const u32 *>(pb + o_first);
+      P.rows = reinterpret_cast<int4 *>(pb + o_rows); P.init = reinterpret_cast<double *>(pb + o_init);
+      HIPCHK(hipMemsetAsync(P.count, 0, ((size_t)nq + 1) * sizeof(u32), c->stream));
+      const int grid = grid_for(nq, SGTD_STORE_THREADS / 64);
+      store_pairs_kernel<<<grid, SGTD_STORE_THREADS, 0, c->stream>>>(P, 0);
+      HIPCHK(hipGetLastError());
+      CHK(device_scan(c, P.count, reinterpret_cast<u32 *>(pb + o_first), (long long)nq + 1));
+      store_pairs_kernel<<<grid, SGTD_STORE_THREADS, 0, c->stream>>>(P, 1);
+      HIPCHK(hipGetLastError());
+      u32 found = 0;
+      std::vector<int32_t> rows(upper * 4);
+      CHK(d2h(c, &found, P.first + nq, sizeof(u32)));
+      CHK(d2h(c, rows.data(), P.rows, upper * sizeof(int4)));
+      CHK(xfer_sync(c));
+      int64_t total_src = 0;
+      for (u32 k = 0; k < found; k++) total_src += pt_off[rows[(size_t)k * 4] + 1] - pt_off[rows[(size_t)k * 4]];
+      if (found > SGTD_REG_MAX_PAIRS || total_src > SGTD_REG_MAX_SOURCE_POINTS) {
+        c->err = "sgtd_register_stored_loops: the pairs formed pass " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs or " +
+                 std::to_string(SGTD_REG_MAX_SOURCE_POINTS) + " source points over the pairs";
+        return SGTD_ERR_UNSUPPORTED;
+      }
+      n = (int)found;
+      for (int k = 0; k < n; k++) {
+        const int32_t *r = rows.data() + (size_t)k * 4;
+        src.push_back(r[0]); slot.push_back(r[3]);
+        c->sr_rows.insert(c->sr_rows.end(), r, r + 3);
+      }
+    }
+    return stored_run(c, o, points, stride_floats, pt_off, nq, device_ptrs, src.data(), slot.data(), nullptr,
+                      n ? reinterpret_cast<const double *>(c->sr_pairs.as<char>() + c->sr_init_off) : nullptr, n);
+  });
+  return run.end(n);
+}
+
+int sgtd_result_stored_pairs(sgtd_handle e, int32_t *query, int32_t *cand, int32_t *frame, double *init, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
+  if (!c->sr_loops) { e->err = "no pair rows: sgtd_register_stored_loops has not run"; return SGTD_ERR_STATE; }
+  const int64_t need = c->sr_n;
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  for (size_t k = 0; k < m; k++) {
+    if (query) query[k] = c->sr_rows[k * 3];
+    if (cand) cand[k] = c->sr_rows[k * 3 + 1];
+    if (frame) frame[k] = c->sr_rows[k * 3 + 2];
+  }
+  if (m) {
+    CopyOut out(e, c);
+    out.get(init, c->sr_pairs.as<char>() + c->sr_init_off, m * 12 * sizeof(double));
+    CHK(out.finish());
+  }
+  return need > capacity && (query || cand || frame || init) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_stored_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *iterations, int32_t *status) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
+  if (c->sr_n == 0) return SGTD_OK;
+  return reg_rows_out(e, c, RegOut((size_t)c->sr_n, false), c->sr_out.p, pose, fitness, cost, n_matched, nullptr, iterations, status);
+}
+
+int sgtd_result_stored_covariances(sgtd_handle e, int cloud, double *cov, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
+  if (cloud < 0 || (size_t)cloud >= c->sr_host_named.size()) return SGTD_ERR_INVALID;
+  const int64_t first = c->sr_host_off[(size_t)cloud];
+  const int64_t need = c->sr_host_named[(size_t)cloud] ? c->sr_host_off[(size_t)cloud + 1] - first : 0;
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  CopyOut out(e, c);
+  out.get(cov, c->sr_cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  CHK(out.finish());
+  return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_stored_matches(sgtd_handle e, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
+  if (pair < 0 || pair >= c->sr_n) return SGTD_ERR_INVALID;
+  const int *soff = c->sr_host_soff.data();
+  const int64_t first = soff[pair], need = soff[pair + 1] - first;
+  const size_t ts = (size_t)std::max(soff[c->sr_n], 1);
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  const double *md2 = c->sr_match.as<double>();
+  const int *mj = reinterpret_cast<const int *>(md2 + 10 * ts);
+  CopyOut out(e, c);
+  out.get(tgt_index, mj + first, m * sizeof(int));
+  out.get(d2, md2 + first, m * sizeof(double));
+  CHK(out.finish());
+  return need > capacity && (tgt_index || d2) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_stored_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
+  if (ms_cov) *ms_cov = c->sr_clock.ms[0];
+  if (ms_search) *ms_search = c->sr_clock.ms[1];
+  if (ms_rest) *ms_rest = c->sr_clock.ms[2];
+  if (ms_total) *ms_total = c->sr_clock.ms[3];
   return SGTD_OK;
 }
 

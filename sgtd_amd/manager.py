@@ -1486,6 +1486,184 @@ class STDescManager:
         out.update(query=q, cand=c, frame=f, init=init, src_cloud=q.copy(), tgt_cloud=tgt, points=pts, pt_off=off)
         return out
 
+    # ---- map clouds kept on the device (sgtd_set_frame_clouds) and registration against them --------------------
+    def _points_arg(self, points, what="points"):
+        """(total, 3 or 4) f32, numpy or a torch.cuda tensor -> (shape, pointer, device_ptrs); the array is kept alive"""
+        if hasattr(points, "data_ptr"):
+            if not (points.is_cuda and points.is_contiguous()):
+                raise ValueError(what + ": a contiguous torch.cuda tensor")
+            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            shape, pp, dev = points.shape, _p(points), 0
+        self._keep = points
+        if len(shape) != 2 or shape[1] not in (3, 4):
+            raise ValueError(what + ": (total, 3 or 4)")
+        return shape, pp, dev
+
+    @staticmethod
+    def _frame_ids(frames):
+        f = np.asarray(frames).reshape(-1)
+        if f.size and (not np.issubdtype(f.dtype, np.integer) or f.min() < 0 or f.max() > 0xFFFFFFFF):
+            raise ValueError("frames: frame ids (integers, not negative)")
+        return np.ascontiguousarray(f, np.uint32)
+
+    def set_frame_clouds(self, frames, clouds, k_neighbors=20, plane_eps=1e-3):
+        """sgtd_set_frame_clouds: the dense clouds of map frames, kept on the device with their covariances (84 bytes a
+        point), the targets of register_stored / register_loops_stored.  frames: the frame ids; clouds: a list of (n, 3 or
+        4) f32 arrays, one per id, or (points, pt_off) with the clouds back to back (points numpy or a torch.cuda tensor)
+        and the len(frames) + 1 offsets; clouds=None forgets the clouds of those ids, and frames=None with clouds=None
+        forgets all (and the settings).  The first call fixes k_neighbors and plane_eps until all are forgotten."""
+        if frames is None:
+            if clouds is not None:
+                raise ValueError("frames=None forgets all clouds: clouds must be None")
+            self._check(self._L.sgtd_set_frame_clouds(self._h, None, None, None, 3, 0, 0, 0.0, 0))
+            return
+        ids = self._frame_ids(frames)
+        if clouds is None:
+            if ids.size:
+                self._check(self._L.sgtd_set_frame_clouds(self._h, _p(ids), None, None, 3, ids.size, 0, 0.0, 0))
+            return
+        if isinstance(k_neighbors, bool) or not isinstance(k_neighbors, (int, np.integer)) or not 3 <= k_neighbors <= 32:
+            raise ValueError("k_neighbors: an integer in 3..32")
+        if not (np.isfinite(plane_eps) and plane_eps > 0):
+            raise ValueError("plane_eps: finite and > 0")
+        if isinstance(clouds, tuple) and len(clouds) == 2 and not isinstance(clouds[0], (list, tuple)) and np.ndim(clouds[1]) == 1 \
+                and getattr(clouds[0], "ndim", 0) == 2:
+            points, off = clouds
+            off = np.ascontiguousarray(np.asarray(off).reshape(-1), np.int64)
+        else:
+            arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in clouds]
+            strides = {a.shape[1] for a in arrs if a.ndim == 2}
+            if any(a.ndim != 2 for a in arrs) or len(strides) > 1 or not strides <= {3, 4}:
+                raise ValueError("clouds: (n, 3) or (n, 4) arrays of one width")
+            stride = strides.pop() if strides else 3
+            off = np.concatenate([[0], np.cumsum([a.shape[0] for a in arrs])]).astype(np.int64)
+            points = np.concatenate(arrs) if arrs else np.zeros((0, stride), np.float32)
+        if off.size != ids.size + 1:
+            raise ValueError("clouds: one cloud (len(frames) + 1 offsets) per frame id")
+        if ids.size == 0:
+            return
+        if not hasattr(points, "data_ptr") and len(points) == 0:
+            points = np.zeros((1, np.shape(points)[1] if np.ndim(points) == 2 else 3), np.float32)     # (a non-NULL array: NULL forgets)
+        shape, pp, dev = self._points_arg(points, "clouds")
+        if off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] > shape[0]:
+            raise ValueError("pt_off: from 0, not decreasing, within the points given")
+        self._check(self._L.sgtd_set_frame_clouds(self._h, _p(ids), _p(off), pp, int(shape[1]), ids.size, int(k_neighbors), float(plane_eps), dev))
+
+    def frame_clouds_info(self):
+        """-> dict of n_frames, n_points (live), device_bytes (the arena's arrays), k_neighbors and plane_eps (0 while the
+        store has no settings)"""
+        a, b, c, k, e = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_double(0)
+        self._check(self._L.sgtd_frame_clouds_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(k), C.byref(e)))
+        return {"n_frames": a.value, "n_points": b.value, "device_bytes": c.value, "k_neighbors": k.value, "plane_eps": e.value}
+
+    def frame_cloud(self, frame):
+        """the stored cloud of one frame: (xyz (n, 3) f32, cov (n, 3, 3) f64), or None where the frame has none"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_frame_cloud(self._h, int(frame), None, None, 0, C.byref(n)))
+        if n.value < 0:
+            return None
+        xyz, cov = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3, 3), np.float64)
+        self._check(self._L.sgtd_result_frame_cloud(self._h, int(frame), _p(xyz), _p(cov), n.value, C.byref(n)))
+        return xyz, cov
+
+    def _register_options(self, options):
+        opt = RegisterOptions()
+        self._L.sgtd_default_register_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(RegisterOptions._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        return opt
+
+    def register_stored(self, points, pt_off, src, tgt_frame, init=None, **options):
+        """sgtd_register_stored: register_clouds with the targets read from the cloud store.  points, pt_off: the call's
+        clouds as register_clouds takes them; src: (n,) cloud indices; tgt_frame: (n,) frame ids that have a stored cloud;
+        init, options and the returned dict as register_clouds'.  The results are register_clouds' on the call's clouds
+        followed by the frames' stored clouds, bit for bit."""
+        shape, pp, dev = self._points_arg(points)
+        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+        if off.size < 1:
+            raise ValueError("pt_off: n_clouds + 1 offsets")
+        if off[-1] > shape[0]:
+            raise ValueError("pt_off names more points than were given")
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        t = self._frame_ids(tgt_frame)
+        n = s.size
+        if t.size != n:
+            raise ValueError("src and tgt_frame: one cloud index and one frame id per pair")
+        p0 = None
+        if init is not None:
+            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
+            if p0.shape[0] != n:
+                raise ValueError("init: (n, 12), one start pose per pair")
+        opt = self._register_options(options)
+        self._check(self._L.sgtd_register_stored(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(s), _p(t), _p(p0), n, dev))
+        self._stored_n = n
+        return self.result_stored_registered()
+
+    def result_stored_registered(self):
+        n = self._stored_n
+        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
+               "n_matched": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
+        self._check(self._L.sgtd_result_stored_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
+                                                          _p(out["iterations"]), _p(out["status"])))
+        return out
+
+    def register_loops_stored(self, query_points, query_pt_off, max_per_query=5, start="verify", **options):
+        """sgtd_register_stored_loops, after verify(): register_loops with the map clouds read from the cloud store and the
+        pairs formed on the device (register_pairs' rule; a candidate whose frame has no stored cloud is dropped).
+        query_points: (total, 3 or 4) f32, numpy or a torch.cuda tensor, with the n_queries + 1 offsets query_pt_off.
+        -> register_loops' dict: query, cand, frame [m] (int32), init [m, 12] and register_clouds' fields per pair"""
+        starts = {"verify": 0, "refined": 1, "aligned": 2}
+        if start not in starts:
+            raise ValueError('start: "verify", "refined" or "aligned"')
+        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
+            raise ValueError("max_per_query: an integer, not negative")
+        shape, pp, dev = self._points_arg(query_points, "query_points")
+        qoff = np.ascontiguousarray(np.asarray(query_pt_off).reshape(-1), np.int64)
+        if qoff.size != self._nq + 1:
+            raise ValueError("query_pt_off: n_queries + 1 offsets")
+        if qoff[-1] > shape[0]:
+            raise ValueError("query_pt_off names more points than were given")
+        opt = self._register_options(options)
+        self._check(self._L.sgtd_register_stored_loops(self._h, C.byref(opt), pp, int(shape[1]), _p(qoff), int(max_per_query), starts[start], dev))
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_pairs(self._h, None, None, None, None, 0, C.byref(n)))
+        m = n.value
+        q, c, f, init = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 12), np.float64)
+        self._check(self._L.sgtd_result_stored_pairs(self._h, _p(q), _p(c), _p(f), _p(init), m, C.byref(n)))
+        self._stored_n = m
+        out = self.result_stored_registered()
+        out.update(query=q, cand=c, frame=f, init=init)
+        return out
+
+    def stored_covariances(self, cloud):
+        """the regularised covariances of one of the call's clouds of the last register_stored / register_loops_stored
+        call: (n, 3, 3) f64; 0 rows for a cloud no pair named"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_covariances(self._h, int(cloud), None, 0, C.byref(n)))
+        cov = np.zeros((n.value, 3, 3), np.float64)
+        self._check(self._L.sgtd_result_stored_covariances(self._h, int(cloud), _p(cov), n.value, C.byref(n)))
+        return cov
+
+    def stored_matches(self, pair):
+        """the correspondences of one pair under its final pose: (tgt_index (n,) int32 within the frame's stored cloud, -1
+        where none; d2 (n,) f64)"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_matches(self._h, int(pair), None, None, 0, C.byref(n)))
+        j, d2 = np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
+        self._check(self._L.sgtd_result_stored_matches(self._h, int(pair), _p(j), _p(d2), n.value, C.byref(n)))
+        return j, d2
+
+    def stored_register_stage_ms(self):
+        """device milliseconds of the last register_stored / register_loops_stored call: covariances, searches, the rest,
+        the whole run (zeros unless set_timing(True))"""
+        v = [C.c_float(0) for _ in range(4)]
+        self._check(self._L.sgtd_stored_register_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     # ---- voxelised registration against voxel maps (sgtd_register_voxels) -------------------------------------
     def register_voxels(self, points, pt_off, map_off, map_cloud, map_pose, src, tgt_map, init=None, **options):
         """sgtd_register_voxels: voxelised GICP of clouds against maps of Gaussian voxels on the device.  points, pt_off:
