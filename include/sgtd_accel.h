@@ -1437,6 +1437,85 @@ int sgtd_result_voxel_map(sgtd_handle h, int map, int32_t *coord /*[cap*3]*/, in
 int sgtd_result_voxel_matches(sgtd_handle h, int pair, int32_t *voxel /*[n_src*mode]*/, int64_t capacity, int64_t *n);
 int sgtd_voxel_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total);
 
+/* Voxelised GICP of the call's clouds against voxel maps whose members are stored clouds (sgtd_set_frame_clouds).
+ * The call's clouds are the sources; map m has the members map_off[m] .. map_off[m + 1] of map_frame, global frame ids
+ * that name stored clouds (a frame may be a member of several maps and several times of one); map_pose, src_cloud,
+ * tgt_map, init_pose and the options are sgtd_register_voxels'.
+ * The results are those of sgtd_register_voxels on [the call's clouds] followed by [the named frames' stored clouds]
+ * (member j of map_frame being cloud n_clouds + j there), with the same options, bit for bit: every result row, every
+ * voxel of every map, every match.  No member point crosses the link and no member covariance is computed again: the
+ * call packs its clouds behind the arena's slots for its length, computes the covariances of its clouds that some pair
+ * names, and runs sgtd_register_voxels' kernels over the arena, the members' points and covariances read in place.
+ * Every call builds its maps anew.
+ * Buffers and results of its own, as sgtd_register_stored has: it neither touches the results of sgtd_register_clouds,
+ * sgtd_register_voxels and sgtd_register_stored nor is touched by them; its results last until the next
+ * sgtd_register_stored_voxels call that passes its argument checks, or sgtd_destroy (later sgtd_set_frame_clouds calls
+ * do not change them).  A view uses its own store; a multi-device handle runs the call on its first device.
+ * Before the device is touched and with the earlier results kept: everything sgtd_register_voxels rejects or caps, its
+ * caps applied to the call's clouds, the pairs, the maps and the member points (SGTD_ERR_INVALID, SGTD_ERR_UNSUPPORTED);
+ * a member frame without a stored cloud: SGTD_ERR_INVALID (sgtd_last_error names the frame); opt's k_neighbors or
+ * plane_eps other than the store's: SGTD_ERR_STATE.
+ * The getters mirror sgtd_register_voxels', with the same SGTD_ERR_STATE, SGTD_ERR_INVALID and SGTD_ERR_CAPACITY
+ * conditions; sgtd_stored_voxel_register_stage_ms' covariance time is that of the call's clouds alone. */
+int sgtd_register_stored_voxels(sgtd_handle h, const sgtd_voxel_register_options *opt /* NULL = defaults */,
+                                const float *points, int stride_floats /* 3 or 4 */, const int64_t *pt_off /* host, n_clouds + 1 */, int n_clouds,
+                                const int32_t *map_off /* n_maps + 1 */, const uint32_t *map_frame, const double *map_pose /* [members*12], NULL = identity */,
+                                int n_maps, const int32_t *src_cloud, const int32_t *tgt_map, const double *init_pose /* [n_pairs*12], NULL = identity */,
+                                int n_pairs, int device_ptrs /* points only */);
+int sgtd_result_stored_voxel_registered(sgtd_handle h, double *pose /*[n*12]*/, double *fitness, double *cost /*[n*2] first, last*/,
+                                        int32_t *n_matched, int32_t *n_corr, int32_t *iterations, int32_t *status);
+int sgtd_result_stored_voxel_map(sgtd_handle h, int map, int32_t *coord /*[cap*3]*/, int32_t *n_points, double *mean /*[cap*3]*/,
+                                 double *cov /*[cap*9]*/, int64_t capacity, int64_t *n);
+int sgtd_result_stored_voxel_matches(sgtd_handle h, int pair, int32_t *voxel /*[n_src*mode]*/, int64_t capacity, int64_t *n);
+int sgtd_stored_voxel_register_stage_ms(sgtd_handle h, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total);
+
+/* sgtd_register_stored_local_loops: the pairs of the pending batch's verification, the local voxel maps around their
+ * candidate frames and the members' relative poses, all formed on the device from the verification's results, the cloud
+ * store and the poses of sgtd_set_frame_poses, then registered as sgtd_register_stored_voxels does.  Cloud q of the call
+ * is query q's raw cloud (pt_off: n_queries + 1 offsets).  All arithmetic below is f64, every operation rounded once (no
+ * contraction), on the stored f32 poses widened exactly; inv() and mul() are those of sgtd_consistent_loops above.
+ * Eligible frame: it has a stored cloud (sgtd_set_frame_clouds; one of zero points counts) and a stored pose, and all 12
+ *   floats of the pose are finite.
+ * Rows: sgtd_register_stored_loops' rule.  Per query the candidates with a verification result (score >= 0) in descending
+ *   score, ties in ascending candidate index; the first max_per_query of them (clamped to candidate_num); of those, the
+ *   ones whose frame is not eligible are dropped, not replaced.  The rows are in (query, rank) order; init is the relative
+ *   pose of the stage `start` names (SGTD_START_*).
+ * Maps: one per distinct frame among the rows, numbered in ascending frame id and shared among the queries; a row's
+ *   tgt_map names the map of its frame.
+ * Members of the map of frame j: sgtd_local_map_keypoints' member rule over the eligible frames.  j itself, always,
+ *   first.  Every other eligible frame i iff d2 <= rr with dx = (double)t_i[0] - (double)t_j[0] (dy, dz alike),
+ *   d2 = (dx*dx + dy*dy) + dz*dz, rr = radius * radius, listed in ascending frame id; d2 == rr is in.  With
+ *   max_members = m > 0: j and the m - 1 other members with the smallest (d2, id), ordered lexicographically (ties in d2
+ *   go to the smaller id), still listed in ascending id behind j; m == 1 keeps j alone.  This is not
+ *   STDescManager.voxel_map_members' cut, which keeps the first m in id order; with max_members = 0 the two agree on
+ *   membership.
+ * Member poses, in the rel_pose layout: the identity, written out (1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0), for j;
+ *   mul(inv(T_j), T_i) for every other member i.
+ * Results: those of sgtd_register_stored_voxels on these maps (map_frame = the members, map_pose = the member poses) and
+ *   rows (src_cloud = query, tgt_map, init_pose = init), bit for bit, through sgtd_register_stored_voxels' getters;
+ *   sgtd_result_stored_local_pairs returns the rows, sgtd_result_stored_local_maps the maps' frames, member offsets
+ *   (n_maps + 1), member ids and member poses (*n = the counts; more than a capacity: SGTD_ERR_CAPACITY with the first
+ *   entries written; after sgtd_register_stored_voxels: SGTD_ERR_STATE).
+ * On the device: a lane per frame id for eligibility, a wave per query for the rows, flags over the frame ids and a scan
+ *   for the maps, a workgroup per map that streams every id's translation (counts first, lists second; ascending id by
+ *   prefix sums; the max_members cut by a radix select over (bits of d2, id)), a lane per member for the poses.  The pose
+ *   store's device copy is the one sgtd_consistent_loops and sgtd_pose_consensus use.  The host reads back the rows, the
+ *   maps' frames and the member counts and points once, to size the tiles and check the caps; the members, their poses
+ *   and the start poses stay on the device.  The call adds results and changes none of the batch's.
+ * max_per_query < 0, an unknown start, a radius that is NaN, negative or infinite, max_members < 0 and the options
+ * sgtd_register_voxels rejects: SGTD_ERR_INVALID; k_neighbors or plane_eps other than the store's, no verification of the
+ * pending batch, or the named stage has not run on it: SGTD_ERR_STATE; a multi-device handle: SGTD_ERR_UNSUPPORTED.
+ * sgtd_register_clouds' caps on the clouds are checked before the device is touched; the caps on the pairs, the maps,
+ * the member points (and as many members) and the correspondences can only be checked once rows and maps are formed: a
+ * call that fails there returns SGTD_ERR_UNSUPPORTED and leaves no results. */
+int sgtd_register_stored_local_loops(sgtd_handle h, const sgtd_voxel_register_options *opt /* NULL = defaults */,
+                                     const float *points, int stride_floats, const int64_t *pt_off /* n_queries + 1 */,
+                                     int max_per_query, int start, double radius, int max_members /* 0 = no cap */, int device_ptrs /* points only */);
+int sgtd_result_stored_local_pairs(sgtd_handle h, int32_t *query, int32_t *cand, int32_t *frame, int32_t *tgt_map, double *init /*[n*12]*/,
+                                   int64_t capacity, int64_t *n);
+int sgtd_result_stored_local_maps(sgtd_handle h, uint32_t *map_frame, int64_t *mem_off /* n_maps + 1 */, uint32_t *member,
+                                  double *member_pose /*[members*12]*/, int64_t cap_maps, int64_t cap_members, int64_t *n_maps, int64_t *n_members);
+
 /* Page-locked host memory for the destination buffers of the fetch calls (sgtd_fetch_entries,
  * sgtd_result_pairs, ...): a copy into it is one direct DMA transfer — pageable memory goes through the
  * runtime's staging at about a third of the rate.  Allocation is slow (milliseconds): keep the buffers

@@ -50,6 +50,8 @@ SYMBOLS = [
     "sgtd_set_frame_clouds", "sgtd_frame_clouds_info", "sgtd_result_frame_cloud",
     "sgtd_register_stored", "sgtd_result_stored_registered", "sgtd_result_stored_covariances", "sgtd_result_stored_matches",
     "sgtd_stored_register_stage_ms", "sgtd_register_stored_loops", "sgtd_result_stored_pairs",
+    "sgtd_register_stored_voxels", "sgtd_result_stored_voxel_registered", "sgtd_result_stored_voxel_map", "sgtd_result_stored_voxel_matches",
+    "sgtd_stored_voxel_register_stage_ms", "sgtd_register_stored_local_loops", "sgtd_result_stored_local_pairs", "sgtd_result_stored_local_maps",
 ]
 
 
@@ -281,6 +283,15 @@ def lib():
     L.sgtd_stored_register_stage_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 4
     L.sgtd_register_stored_loops.argtypes = [vp, C.POINTER(RegisterOptions), vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
     L.sgtd_result_stored_pairs.argtypes = [vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_register_stored_voxels.argtypes = [vp, C.POINTER(VoxelRegisterOptions), vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int,
+                                              C.c_int]
+    L.sgtd_result_stored_voxel_registered.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgtd_result_stored_voxel_map.argtypes = [vp, C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_stored_voxel_matches.argtypes = [vp, C.c_int, vp, i64, C.POINTER(i64)]
+    L.sgtd_stored_voxel_register_stage_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 5
+    L.sgtd_register_stored_local_loops.argtypes = [vp, C.POINTER(VoxelRegisterOptions), vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
+    L.sgtd_result_stored_local_pairs.argtypes = [vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_result_stored_local_maps.argtypes = [vp, vp, vp, vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64)]
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

@@ -37,6 +37,7 @@
 #include "register_kernels.hip.h"
 #include "voxel_register_kernels.hip.h"
 #include "cloud_store_kernels.hip.h"
+#include "stored_local_kernels.hip.h"
 #include "consensus_kernels.hip.h"
 #include "scan_kernels.hip.h"
 #include "local_map_kernels.hip.h"
@@ -399,6 +400,26 @@ struct sgtd_engine {
   std::vector<u32> vr_host_map_vox;      // [n_maps + 1]
   std::vector<int> vr_host_up;           // (the source of the index upload)
   LapClock vr_clock;
+  // sgtd_register_stored_voxels: the same run over the cloud store's arena (VregSite), independent of the batch and of
+  // the other registration calls' buffers.  sv[VR_*] as vr[] (VR_PTS: the call's points when the host gave them, before
+  // they are packed behind the slots; VR_COV: unused, the covariances are the arena's).  sv_n < 0: no results; sv_host_*,
+  // sv_mode, sv_clock as vr_*
+  DevBuf sv[VR_BUFS];
+  int sv_n = -1, sv_mode = 1;
+  std::vector<int> sv_host_soff, sv_host_up;
+  std::vector<u32> sv_host_map_vox;
+  LapClock sv_clock;
+  // sgtd_register_stored_local_loops (stored_local_kernels.hip.h): sv_form: the per-id streams, the rows and the per-map
+  // records (StoredLocalParams); sv_members: the member lists, slots, sizes, point offsets and relative poses.  sv_local:
+  // the results are that form's; sv_rows: its rows (query, candidate, frame, map), sv_map_frame, sv_mem_off: the maps'
+  // frames and member offsets, on the host; sv_init_off / sv_member_off / sv_pose_off: where the start poses (in sv_form),
+  // the member ids and their poses (in sv_members) lie
+  DevBuf sv_form, sv_members;
+  bool sv_local = false;
+  std::vector<int32_t> sv_rows;
+  std::vector<u32> sv_map_frame;
+  std::vector<int64_t> sv_mem_off;
+  size_t sv_init_off = 0, sv_member_off = 0, sv_pose_off = 0;
   // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (SK_*: scan_run).  sk_n < 0:
   // no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets on the host
   enum { SK_PTS = 0, SK_LAB, SK_OFF, SK_SC, SK_R, SK_PITCH, SK_AZI, SK_MM, SK_VOTE, SK_GRID, SK_RANGE, SK_BOUNDS, SK_KEY_A, SK_KEY_B, SK_VAL_A, SK_VAL_B,
@@ -2310,14 +2331,16 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl,
                     &e->rg_in, &e->rg_pts, &e->rg_cov, &e->rg_part, &e->rg_match, &e->rg_state, &e->rg_out, &e->rg_ctl,
                     &e->st.pts, &e->st.cov, &e->st.off, &e->st_stage, &e->st_idx, &e->st_table,
-                    &e->sr_in, &e->sr_pts, &e->sr_cov, &e->sr_part, &e->sr_match, &e->sr_state, &e->sr_out, &e->sr_ctl, &e->sr_pairs};
+                    &e->sr_in, &e->sr_pts, &e->sr_cov, &e->sr_part, &e->sr_match, &e->sr_state, &e->sr_out, &e->sr_ctl, &e->sr_pairs,
+                    &e->sv_form, &e->sv_members};
   for (DevBuf *b : bufs) free_buf(*b);
   for (DevBuf &b : e->sk) free_buf(b);
   for (DevBuf &b : e->lm) free_buf(b);
   for (DevBuf &b : e->vr) free_buf(b);
+  for (DevBuf &b : e->sv) free_buf(b);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
-  for (LapClock *k : {&e->rg_clock, &e->sr_clock, &e->vr_clock, &e->lm_clock}) k->destroy();
+  for (LapClock *k : {&e->rg_clock, &e->sr_clock, &e->vr_clock, &e->sv_clock, &e->lm_clock}) k->destroy();
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
@@ -5535,6 +5558,15 @@ int store_room(sgtd_engine *e, int64_t pts, int64_t clouds) {
   return SGTD_OK;
 }
 
+// the frame -> slot table on the device, made again when the store has changed (the loops forms read it)
+int store_table(sgtd_engine *e) {
+  if (e->st_table_serial == e->st_serial && e->st_table.p) return SGTD_OK;
+  CHK(ensure(e, e->st_table, std::max<size_t>(e->st_slot_of.size(), 1) * sizeof(int)));
+  CHK(h2d(e, e->st_table.p, e->st_slot_of.data(), e->st_slot_of.size() * sizeof(int)));
+  e->st_table_serial = e->st_serial;
+  return SGTD_OK;
+}
+
 // `total` points of the given stride, on the device, into the arena from point `first` on
 int store_pack(sgtd_engine *e, CloudArena &A, const float *d_src, int stride, int64_t total, int64_t first) {
   if (total == 0) return SGTD_OK;
@@ -5654,9 +5686,9 @@ int stored_options(const sgtd_register_options *opt, sgtd_register_options *o) {
     return SGTD_ERR_INVALID;
   return SGTD_OK;
 }
-int stored_settings(sgtd_engine *e, const char *call, const sgtd_register_options &o) {
+int stored_settings(sgtd_engine *e, const char *call, int k_neighbors, double plane_eps) {
   const sgtd_engine *c = home_engine(e);
-  if (c->st_k == 0 || (o.k_neighbors == c->st_k && o.plane_eps == c->st_eps)) return SGTD_OK;
+  if (c->st_k == 0 || (k_neighbors == c->st_k && plane_eps == c->st_eps)) return SGTD_OK;
   e->err = std::string(call) + ": k_neighbors and plane_eps must be the cloud store's (" + std::to_string(c->st_k) + ", " + std::to_string(c->st_eps) + ")";
   return SGTD_ERR_STATE;
 }
@@ -5763,7 +5795,7 @@ int sgtd_register_stored(sgtd_handle e, const sgtd_register_options *opt, const 
              " source points over the pairs";
     return SGTD_ERR_UNSUPPORTED;
   }
-  CHK(stored_settings(e, "sgtd_register_stored", o));
+  CHK(stored_settings(e, "sgtd_register_stored", o.k_neighbors, o.plane_eps));
   {
     const sgtd_engine *c = home_engine(e);
     for (int k = 0; k < n_pairs; k++)
@@ -5799,7 +5831,7 @@ int sgtd_register_stored_loops(sgtd_handle e, const sgtd_register_options *opt, 
   const int nq = e->nq, cn = e->dc.cand_num, mpq = std::min(max_per_query, cn);
   if (!cloud_set_ok(pt_off, nq, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
   if (!gicp_caps_ok(pt_off, nq, 0)) { e->err = gicp_caps_text("sgtd_register_stored_loops"); return SGTD_ERR_UNSUPPORTED; }
-  CHK(stored_settings(e, "sgtd_register_stored_loops", o));
+  CHK(stored_settings(e, "sgtd_register_stored_loops", o.k_neighbors, o.plane_eps));
   HIPCHK(hipSetDevice(e->cfg.device_id));
   CHK(sync_batch(e));
   const int64_t total = pt_off[nq];
@@ -5812,11 +5844,7 @@ int sgtd_register_stored_loops(sgtd_handle e, const sgtd_register_options *opt, 
     std::vector<int32_t> src, slot;
     if (upper > 0 && c->st_frames > 0) {
       CHK(store_room(c, total, nq));
-      if (c->st_table_serial != c->st_serial || !c->st_table.p) {
-        CHK(ensure(c, c->st_table, std::max<size_t>(c->st_slot_of.size(), 1) * sizeof(int)));
-        CHK(h2d(c, c->st_table.p, c->st_slot_of.data(), c->st_slot_of.size() * sizeof(int)));
-        c->st_table_serial = c->st_serial;
-      }
+      CHK(store_table(c));
       // the pairs: counts per query, their scan, the rows; the host reads the total and the rows back once
       const size_t o_count = 0, o_first = o_count + relax_up(((size_t)nq + 1) * sizeof(u32)), o_rows = o_first + relax_up(((size_t)nq + 1) * sizeof(u32)),
                    o_init = o_rows + relax_up(upper * sizeof(int4));
@@ -5942,47 +5970,79 @@ int sgtd_stored_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search
 namespace {
 static_assert(SGTD_VREG_W == SGTD_VREG_SUM_W, "the voxel kernels' sizes are the header's");
 
-int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
-             const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src, const int32_t *tgt,
-             const double *init, int n) {
+// Where a voxel run keeps its buffers and finds its clouds: sgtd_register_voxels' own arrays, or
+// sgtd_register_stored_voxels' over the cloud store's arena, whose stored clouds come before the call's.
+struct VregSite {
+  const char *call;
+  DevBuf *B;                        // the run's buffers (VR_*)
+  int &mode;
+  std::vector<int> &soff, &up;      // src_off [n + 1]; the source of the index upload
+  std::vector<u32> &map_vox;        // [n_maps + 1], read back for the getters
+  LapClock &clock;
+  const float *pts;                 // the points of every cloud the kernels may name, on the device
+  int stride;
+  double *cov;                      // the covariances of those clouds; NULL: VR_COV, grown to the call's points
+  const long long *d_off;           // the clouds' offsets where they are on the device already; NULL: pt_off is uploaded
+  int first;                        // the index the kernels know the call's cloud 0 by
+  // the members where they were formed on the device (sgtd_register_stored_local_loops): their clouds, maps, first points
+  // [members + 1] and poses, the members' points in all, and the pairs' start poses; mem_cloud, mem_n, map_pose and init
+  // are NULL then
+  const int *d_mem_cloud = nullptr, *d_mem_map = nullptr, *d_mem_pt_off = nullptr;
+  const double *d_map_pose = nullptr;
+  long long d_member_pts = 0;
+  const double *d_init = nullptr;
+};
+
+// One voxelised run.  pt_off, n_clouds, named, src: the call's clouds, which of them need covariances, the pairs'
+// sources; mem_cloud, mem_n: the maps' members as the kernels know them, and their sizes
+int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_options &o, const int64_t *pt_off, int n_clouds, const unsigned char *named,
+             const int32_t *map_off, const int32_t *mem_cloud, const int64_t *mem_n, const double *map_pose, int n_maps, const int32_t *src,
+             const int32_t *tgt, const double *init, int n) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
   const bool timed = c->timing;
-  LapClock &clock = c->vr_clock;
+  LapClock &clock = S.clock;
   CHK(clock.start(c, timed));
   const size_t total = (size_t)pt_off[n_clouds];
   const int mode = o.neighbor_mode, n_members = n_maps ? map_off[n_maps] : 0;
-  c->vr_mode = mode;
-  // the members' points back to back, the tiles: of the pairs' sources, of the clouds that are a source or a member
-  std::vector<unsigned char> named((size_t)n_clouds, 0);
-  std::vector<int> mem_map((size_t)n_members), mem_pt_off((size_t)n_members + 1, 0);
-  for (int m = 0; m < n_maps; m++)
-    for (int j = map_off[m]; j < map_off[m + 1]; j++) {
-      mem_map[(size_t)j] = m;
-      named[(size_t)map_cloud[j]] = 1;
-      mem_pt_off[(size_t)j + 1] = mem_pt_off[(size_t)j] + (int)(pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]]);
-    }
-  const long long MP = mem_pt_off[(size_t)n_members];
-  for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
-  std::vector<int> &soff = c->vr_host_soff;
-  GicpIndex G(c->vr_host_up);
-  G.tiles(pt_off, n_clouds, src, n, named.data(), &soff);
+  S.mode = mode;
+  // the members' points back to back, the tiles: of the pairs' sources, of the clouds that need covariances
+  const bool on_device = S.d_mem_cloud != nullptr;
+  std::vector<int> mem_map, mem_pt_off;
+  if (!on_device) {
+    mem_map.resize((size_t)n_members);
+    mem_pt_off.assign((size_t)n_members + 1, 0);
+    for (int m = 0; m < n_maps; m++)
+      for (int j = map_off[m]; j < map_off[m + 1]; j++) {
+        mem_map[(size_t)j] = m;
+        mem_pt_off[(size_t)j + 1] = mem_pt_off[(size_t)j] + (int)mem_n[j];
+      }
+  }
+  const long long MP = on_device ? S.d_member_pts : mem_pt_off[(size_t)n_members];
+  std::vector<int> &soff = S.soff;
+  GicpIndex G(S.up);
+  G.tiles(pt_off, n_clouds, src, n, named, &soff);
   const int total_src = soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
 
-  // the index upload: src, tgt_map, src_off, map_off, map_cloud, mem_map, mem_pt_off, the tiles
+  // the index upload: src, tgt_map, src_off, map_off, map_cloud, mem_map, mem_pt_off, the tiles (clouds by the index the
+  // kernels know them by)
   G.u_src = G.put(src, (size_t)n);
   const size_t u_tgt = G.put(tgt, (size_t)n);
   G.u_soff = G.put(soff.data(), soff.size());
-  const size_t u_moff = n_maps ? G.put(map_off, (size_t)n_maps + 1) : G.up.size(), u_mcl = G.put(map_cloud, (size_t)n_members);
+  const size_t u_moff = n_maps ? G.put(map_off, (size_t)n_maps + 1) : G.up.size(), u_mcl = G.put(mem_cloud, on_device ? 0 : (size_t)n_members);
   const size_t u_mmap = G.put(mem_map.data(), mem_map.size()), u_mpo = G.put(mem_pt_off.data(), mem_pt_off.size());
+  if (S.first) {
+    for (int k = 0; k < n; k++) S.up[G.u_src + (size_t)k] += S.first;
+    for (int &cl : G.ctile_cloud) cl += S.first;
+  }
   G.put_tiles();
   const size_t o_off = 0, o_init = o_off + relax_up((size_t)(n_clouds + 1) * sizeof(int64_t)), o_pose = o_init + relax_up((size_t)n * 12 * sizeof(double)),
                o_idx = o_pose + relax_up((size_t)n_members * 12 * sizeof(double)), in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1), mp = (size_t)std::max<long long>(MP, 1), nn = (size_t)std::max(n, 1);
   const RegOut out((size_t)n, true);
-  auto *B = c->vr;
+  auto *B = S.B;
   auto buf = [&](int which, size_t bytes) { return ensure(c, B[which], std::max<size_t>(bytes, 16)); };
   CHK(buf(sgtd_engine::VR_IN, in_bytes));
-  CHK(buf(sgtd_engine::VR_COV, std::max<size_t>(total, 1) * 9 * sizeof(double)));
+  if (!S.cov) CHK(buf(sgtd_engine::VR_COV, std::max<size_t>(total, 1) * 9 * sizeof(double)));
   CHK(buf(sgtd_engine::VR_KEY_A, mp * sizeof(u64)));
   CHK(buf(sgtd_engine::VR_KEY_B, mp * sizeof(u64)));
   CHK(buf(sgtd_engine::VR_VAL_A, mp * sizeof(u32)));
@@ -5999,7 +6059,7 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   CHK(buf(sgtd_engine::VR_OUT, out.bytes()));
   CHK(buf(sgtd_engine::VR_CTL, 64));
   char *in = B[sgtd_engine::VR_IN].as<char>();
-  CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
+  if (!S.d_off) CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
   if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
   if (map_pose) CHK(h2d(c, in + o_pose, map_pose, (size_t)n_members * 12 * sizeof(double)));
   CHK(h2d(c, in + o_idx, G.up.data(), G.up.size() * sizeof(int)));
@@ -6007,13 +6067,15 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   RegParams P;
   const int *di = reinterpret_cast<const int *>(in + o_idx);
   void *ob = B[sgtd_engine::VR_OUT].p;
-  gicp_params(P, G, points, stride, in + o_off, di, n, ts, B[sgtd_engine::VR_COV].as<double>(), B[sgtd_engine::VR_STATE].p, B[sgtd_engine::VR_CTL].p, out, ob,
+  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts,
+              S.cov ? S.cov : B[sgtd_engine::VR_COV].as<double>(), B[sgtd_engine::VR_STATE].p, B[sgtd_engine::VR_CTL].p, out, ob,
               gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, std::numeric_limits<double>::infinity(), o.lm_init_lambda_factor, o.rotation_eps,
                            o.translation_eps, o.plane_eps));
   VregParams V;
   std::memset(&V, 0, sizeof(V));
   V.map_off = di + u_moff; V.map_cloud = di + u_mcl; V.mem_map = di + u_mmap; V.mem_pt_off = di + u_mpo;
   V.map_pose = map_pose ? reinterpret_cast<const double *>(in + o_pose) : nullptr;
+  if (on_device) { V.map_cloud = S.d_mem_cloud; V.mem_map = S.d_mem_map; V.mem_pt_off = S.d_mem_pt_off; V.map_pose = S.d_map_pose; }
   V.tgt_map = di + u_tgt;
   V.n_maps = n_maps; V.n_members = n_members; V.n_member_pts = (int)MP; V.mode = mode; V.res = o.voxel_resolution;
   V.map_vox = B[sgtd_engine::VR_MAP_VOX].as<u32>();
@@ -6052,8 +6114,8 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   }
   vreg_ranges_kernel<<<grid_for(n_maps + 1, 256), 256, 0, s>>>(V);
   HIPCHK(hipGetLastError());
-  c->vr_host_map_vox.assign((size_t)n_maps + 1, 0);
-  CHK(d2h(c, c->vr_host_map_vox.data(), V.map_vox, ((size_t)n_maps + 1) * sizeof(u32)));
+  S.map_vox.assign((size_t)n_maps + 1, 0);
+  CHK(d2h(c, S.map_vox.data(), V.map_vox, ((size_t)n_maps + 1) * sizeof(u32)));
   CHK(xfer_sync(c));
   if (timed) CHK(clock.lap(c, 1));
   if (n == 0) {
@@ -6061,14 +6123,14 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
     return SGTD_OK;
   }
 
-  const std::vector<u32> &mv = c->vr_host_map_vox;
+  const std::vector<u32> &mv = S.map_vox;
   int unfinished = 0;
   for (int k = 0; k < n; k++)
     if (soff[(size_t)k + 1] > soff[(size_t)k] && mv[(size_t)tgt[k] + 1] > mv[(size_t)tgt[k]]) unfinished++;
   CHK(h2d(c, P.unfinished, &unfinished, sizeof(int)));
-  vreg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, V, init ? reinterpret_cast<const double *>(in + o_init) : nullptr);
+  vreg_init_kernel<<<grid_for(n, SGTD_REG_W), SGTD_REG_W, 0, s>>>(P, V, init ? reinterpret_cast<const double *>(in + o_init) : S.d_init);
   HIPCHK(hipGetLastError());
-  CHK(gicp_rounds(c, "sgtd_register_voxels", P, unfinished, [&]() -> int {
+  CHK(gicp_rounds(c, S.call, P, unfinished, [&]() -> int {
     if (timed) CHK(clock.lap(c, 3));
     vreg_corr_kernel<<<n_tiles, SGTD_REG_THREADS, 0, s>>>(P, V, 0);
     if (timed) CHK(clock.lap(c, 2));
@@ -6092,6 +6154,124 @@ int vreg_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *
   return SGTD_OK;
 }
 
+// sgtd_register_voxels' run: every cloud is the call's, and a cloud that is a source or a member needs covariances
+int vreg_clouds_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
+                    const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src, const int32_t *tgt,
+                    const double *init, int n) {
+  const int n_members = n_maps ? map_off[n_maps] : 0;
+  std::vector<unsigned char> named((size_t)n_clouds, 0);
+  std::vector<int64_t> mem_n((size_t)n_members);
+  for (int j = 0; j < n_members; j++) {
+    named[(size_t)map_cloud[j]] = 1;
+    mem_n[(size_t)j] = pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]];
+  }
+  for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
+  const VregSite S{"sgtd_register_voxels", c->vr, c->vr_mode, c->vr_host_soff, c->vr_host_up, c->vr_host_map_vox, c->vr_clock,
+                   points, stride, nullptr, nullptr, 0};
+  return vreg_run(c, S, o, pt_off, n_clouds, named.data(), map_off, map_cloud, mem_n.data(), map_pose, n_maps, src, tgt, init, n);
+}
+
+// the options of a voxel call: the defaults or the caller's, checked
+int vreg_options(const sgtd_voxel_register_options *opt, sgtd_voxel_register_options *o) {
+  sgtd_default_voxel_register_options(o);
+  if (opt) *o = *opt;
+  if (!gicp_options_ok(o->k_neighbors, o->max_iterations, o->lm_max_trials, o->reserved, o->lm_init_lambda_factor, o->rotation_eps, o->translation_eps,
+                       o->plane_eps) ||
+      !(std::isfinite(o->voxel_resolution) && o->voxel_resolution > 0.0) || (o->neighbor_mode != 1 && o->neighbor_mode != 7 && o->neighbor_mode != 27))
+    return SGTD_ERR_INVALID;
+  return SGTD_OK;
+}
+
+// What both voxel calls check of their arguments before the device is touched, in sgtd_register_voxels' order.
+// member_points(j, &np): the points of member j, or the code that rejects it (its text is the callback's).
+template <class MemberPoints>
+int vreg_check(sgtd_engine *e, const char *call, const sgtd_voxel_register_options *opt, sgtd_voxel_register_options *o, const float *points,
+               int stride_floats, const int64_t *pt_off, int n_clouds, const int32_t *map_off, const void *members, const double *map_pose, int n_maps,
+               const int32_t *src_cloud, const int32_t *tgt_map, const double *init_pose, int n_pairs, MemberPoints &&member_points) {
+  if (!e || n_pairs < 0 || n_maps < 0) return SGTD_ERR_INVALID;
+  if (n_pairs > 0 && (!src_cloud || !tgt_map)) return SGTD_ERR_INVALID;
+  if (n_maps > 0 && !map_off) return SGTD_ERR_INVALID;
+  CHK(vreg_options(opt, o));
+  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  if (n_maps > 0 && map_off[0] != 0) return SGTD_ERR_INVALID;
+  for (int m = 0; m < n_maps; m++)
+    if (map_off[m + 1] < map_off[m]) return SGTD_ERR_INVALID;
+  const int n_members = n_maps ? map_off[n_maps] : 0;
+  if (n_members > 0 && !members) return SGTD_ERR_INVALID;
+  int64_t total_src = 0, member_pts = 0;
+  for (int j = 0; j < n_members; j++) {
+    int64_t np = 0;
+    CHK(member_points(j, &np));
+    member_pts += np;
+  }
+  for (int k = 0; k < n_pairs; k++) {
+    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || tgt_map[k] < 0 || tgt_map[k] >= n_maps) return SGTD_ERR_INVALID;
+    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
+  }
+  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
+  if (map_pose && !relax_finite(map_pose, (size_t)n_members * 12)) return SGTD_ERR_INVALID;
+  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs)) {
+    e->err = gicp_caps_text(call) + " and " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (n_maps > SGTD_VREG_MAX_MAPS) {
+    e->err = std::string(call) + " takes at most " + std::to_string(SGTD_VREG_MAX_MAPS) + " maps (SGTD_VREG_MAX_MAPS)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (member_pts > SGTD_VREG_MAX_MEMBER_POINTS) {
+    e->err = std::string(call) + " takes at most " + std::to_string(SGTD_VREG_MAX_MEMBER_POINTS) + " member points over the maps (SGTD_VREG_MAX_MEMBER_POINTS)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (total_src * o->neighbor_mode > SGTD_VREG_MAX_CORR) {
+    e->err = std::string(call) + " takes at most " + std::to_string(SGTD_VREG_MAX_CORR) +
+             " for the source points over the pairs times neighbor_mode (SGTD_VREG_MAX_CORR)";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  return SGTD_OK;
+}
+
+// The getters of a voxel run, over the buffers and host arrays of the call that made it (c: its home engine)
+int vreg_map_out(sgtd_engine *e, sgtd_engine *c, DevBuf *B, const std::vector<u32> &map_vox, int map, int32_t *coord, int32_t *n_points, double *mean,
+                 double *cov, int64_t capacity, int64_t *n) {
+  if (map < 0 || (size_t)map + 1 >= map_vox.size()) return SGTD_ERR_INVALID;
+  const int64_t first = map_vox[(size_t)map], need = (int64_t)map_vox[(size_t)map + 1] - first;
+  if (n) *n = need;
+  const bool any = coord || n_points || mean || cov;
+  const size_t m = any ? (size_t)std::min(need, capacity) : 0;
+  std::vector<u64> keys(coord ? m : 0);
+  std::vector<u32> starts(n_points && m ? m + 1 : 0);
+  CopyOut out(e, c);
+  out.get(keys.data(), B[sgtd_engine::VR_VKEY].as<u64>() + first, keys.size() * sizeof(u64));
+  out.get(starts.data(), B[sgtd_engine::VR_VSTART].as<u32>() + first, starts.size() * sizeof(u32));
+  out.get(mean, B[sgtd_engine::VR_MEAN].as<double>() + (size_t)first * 3, m * 3 * sizeof(double));
+  out.get(cov, B[sgtd_engine::VR_VCOV].as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  CHK(out.finish());
+  for (size_t v = 0; v < keys.size(); v++)
+    for (int a = 0; a < 3; a++) coord[v * 3 + a] = (int32_t)((keys[v] >> (32 - 16 * a)) & 0xFFFFu) - 32768;
+  for (size_t v = 0; v + 1 < starts.size(); v++) n_points[v] = (int32_t)(starts[v + 1] - starts[v]);
+  return need > capacity && any ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int vreg_matches_out(sgtd_engine *e, sgtd_engine *c, DevBuf *B, const std::vector<int> &soff, int mode, int n_pairs, int pair, int32_t *voxel,
+                     int64_t capacity, int64_t *n) {
+  if (pair < 0 || pair >= n_pairs) return SGTD_ERR_INVALID;
+  const int64_t first = (int64_t)soff[(size_t)pair] * mode;
+  const int64_t need = (int64_t)soff[(size_t)pair + 1] * mode - first;
+  if (n) *n = need;
+  CopyOut out(e, c);
+  out.get(voxel, B[sgtd_engine::VR_VID].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
+  CHK(out.finish());
+  return need > capacity && voxel ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+void vreg_ms_out(const LapClock &clock, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
+  if (ms_cov) *ms_cov = clock.ms[0];
+  if (ms_map) *ms_map = clock.ms[1];
+  if (ms_corr) *ms_corr = clock.ms[2];
+  if (ms_rest) *ms_rest = clock.ms[3];
+  if (ms_total) *ms_total = clock.ms[4];
+}
+
 const char kNoVoxelRegistered[] = "no voxel registration: sgtd_register_voxels has not run";
 }  // namespace
 
@@ -6108,55 +6288,19 @@ void sgtd_default_voxel_register_options(sgtd_voxel_register_options *o) {
 int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
                          const int32_t *map_off, const int32_t *map_cloud, const double *map_pose, int n_maps, const int32_t *src_cloud,
                          const int32_t *tgt_map, const double *init_pose, int n_pairs, int device_ptrs) {
-  if (!e || n_pairs < 0 || n_maps < 0) return SGTD_ERR_INVALID;
-  if (n_pairs > 0 && (!src_cloud || !tgt_map)) return SGTD_ERR_INVALID;
-  if (n_maps > 0 && !map_off) return SGTD_ERR_INVALID;
   sgtd_voxel_register_options o;
-  sgtd_default_voxel_register_options(&o);
-  if (opt) o = *opt;
-  if (!gicp_options_ok(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.reserved, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps, o.plane_eps) ||
-      !(std::isfinite(o.voxel_resolution) && o.voxel_resolution > 0.0) || (o.neighbor_mode != 1 && o.neighbor_mode != 7 && o.neighbor_mode != 27))
-    return SGTD_ERR_INVALID;
-  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  CHK(vreg_check(e, "sgtd_register_voxels", opt, &o, points, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map,
+                 init_pose, n_pairs, [&](int j, int64_t *np) -> int {
+                   if (map_cloud[j] < 0 || map_cloud[j] >= n_clouds) return SGTD_ERR_INVALID;
+                   *np = pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]];
+                   return SGTD_OK;
+                 }));
   const int64_t total = pt_off[n_clouds];
-  if (n_maps > 0 && map_off[0] != 0) return SGTD_ERR_INVALID;
-  for (int m = 0; m < n_maps; m++)
-    if (map_off[m + 1] < map_off[m]) return SGTD_ERR_INVALID;
-  const int n_members = n_maps ? map_off[n_maps] : 0;
-  if (n_members > 0 && !map_cloud) return SGTD_ERR_INVALID;
-  int64_t total_src = 0, member_pts = 0;
-  for (int j = 0; j < n_members; j++) {
-    if (map_cloud[j] < 0 || map_cloud[j] >= n_clouds) return SGTD_ERR_INVALID;
-    member_pts += pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]];
-  }
-  for (int k = 0; k < n_pairs; k++) {
-    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || tgt_map[k] < 0 || tgt_map[k] >= n_maps) return SGTD_ERR_INVALID;
-    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
-  }
-  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
-  if (map_pose && !relax_finite(map_pose, (size_t)n_members * 12)) return SGTD_ERR_INVALID;
-  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs)) {
-    e->err = gicp_caps_text("sgtd_register_voxels") + " and " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs";
-    return SGTD_ERR_UNSUPPORTED;
-  }
-  if (n_maps > SGTD_VREG_MAX_MAPS) {
-    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_VREG_MAX_MAPS) + " maps (SGTD_VREG_MAX_MAPS)";
-    return SGTD_ERR_UNSUPPORTED;
-  }
-  if (member_pts > SGTD_VREG_MAX_MEMBER_POINTS) {
-    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_VREG_MAX_MEMBER_POINTS) + " member points over the maps (SGTD_VREG_MAX_MEMBER_POINTS)";
-    return SGTD_ERR_UNSUPPORTED;
-  }
-  if (total_src * o.neighbor_mode > SGTD_VREG_MAX_CORR) {
-    e->err = "sgtd_register_voxels takes at most " + std::to_string(SGTD_VREG_MAX_CORR) +
-             " for the source points over the pairs times neighbor_mode (SGTD_VREG_MAX_CORR)";
-    return SGTD_ERR_UNSUPPORTED;
-  }
   StageRun<int> run(e, &sgtd_engine::vr_n);
   run.on_device([&](sgtd_engine *c) -> int {
     const float *d_pts = nullptr;
     CHK(points_on_device(c, c->vr[sgtd_engine::VR_PTS], points, (size_t)total * stride_floats, device_ptrs, &d_pts));
-    return vreg_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
+    return vreg_clouds_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
   });
   return run.end(n_pairs);
 }
@@ -6174,49 +6318,305 @@ int sgtd_result_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_poi
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  if (map < 0 || (size_t)map + 1 >= c->vr_host_map_vox.size()) return SGTD_ERR_INVALID;
-  const int64_t first = c->vr_host_map_vox[(size_t)map], need = (int64_t)c->vr_host_map_vox[(size_t)map + 1] - first;
-  if (n) *n = need;
-  const bool any = coord || n_points || mean || cov;
-  const size_t m = any ? (size_t)std::min(need, capacity) : 0;
-  std::vector<u64> keys(coord ? m : 0);
-  std::vector<u32> starts(n_points && m ? m + 1 : 0);
-  auto *B = c->vr;
-  CopyOut out(e, c);
-  out.get(keys.data(), B[sgtd_engine::VR_VKEY].as<u64>() + first, keys.size() * sizeof(u64));
-  out.get(starts.data(), B[sgtd_engine::VR_VSTART].as<u32>() + first, starts.size() * sizeof(u32));
-  out.get(mean, B[sgtd_engine::VR_MEAN].as<double>() + (size_t)first * 3, m * 3 * sizeof(double));
-  out.get(cov, B[sgtd_engine::VR_VCOV].as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
-  CHK(out.finish());
-  for (size_t v = 0; v < keys.size(); v++)
-    for (int a = 0; a < 3; a++) coord[v * 3 + a] = (int32_t)((keys[v] >> (32 - 16 * a)) & 0xFFFFu) - 32768;
-  for (size_t v = 0; v + 1 < starts.size(); v++) n_points[v] = (int32_t)(starts[v + 1] - starts[v]);
-  return need > capacity && any ? SGTD_ERR_CAPACITY : SGTD_OK;
+  return vreg_map_out(e, c, c->vr, c->vr_host_map_vox, map, coord, n_points, mean, cov, capacity, n);
 }
 
 int sgtd_result_voxel_matches(sgtd_handle e, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  if (pair < 0 || pair >= c->vr_n) return SGTD_ERR_INVALID;
-  const int64_t first = (int64_t)c->vr_host_soff[(size_t)pair] * c->vr_mode;
-  const int64_t need = (int64_t)c->vr_host_soff[(size_t)pair + 1] * c->vr_mode - first;
-  if (n) *n = need;
-  CopyOut out(e, c);
-  out.get(voxel, c->vr[sgtd_engine::VR_VID].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
-  CHK(out.finish());
-  return need > capacity && voxel ? SGTD_ERR_CAPACITY : SGTD_OK;
+  return vreg_matches_out(e, c, c->vr, c->vr_host_soff, c->vr_mode, c->vr_n, pair, voxel, capacity, n);
 }
 
 int sgtd_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  if (ms_cov) *ms_cov = c->vr_clock.ms[0];
-  if (ms_map) *ms_map = c->vr_clock.ms[1];
-  if (ms_corr) *ms_corr = c->vr_clock.ms[2];
-  if (ms_rest) *ms_rest = c->vr_clock.ms[3];
-  if (ms_total) *ms_total = c->vr_clock.ms[4];
+  vreg_ms_out(c->vr_clock, ms_cov, ms_map, ms_corr, ms_rest, ms_total);
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_register_stored_voxels: the voxel run over the cloud store's arena ----
+namespace {
+const char kNoStoredVoxel[] = "no stored voxel registration: sgtd_register_stored_voxels has not run";
+
+// the members of a run where sgtd_register_stored_local_loops formed them on the device (VregSite's d_* members)
+struct StoredMembers {
+  const int *slot, *map, *pt_off;
+  const double *pose;
+  long long pts;
+  const double *init;
+};
+
+// The stored voxel calls' run on the home engine, behind store_room: the call's clouds packed behind the slots, their
+// offsets, the voxel run over the arena (members = slots, given by the host or formed on the device).  Nothing reads the
+// call's covariances afterwards (the call has no covariance getter), so they stay where the run left them in the arena.
+int stored_voxels_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
+                      int device_ptrs, const int32_t *map_off, const int32_t *slot, const double *map_pose, int n_maps, const int32_t *src,
+                      const int32_t *tgt, const double *init, int n, const StoredMembers *formed = nullptr) {
+  CloudArena &A = c->st;
+  auto *B = c->sv;
+  const int n_members = n_maps ? map_off[n_maps] : 0;
+  std::vector<unsigned char> named((size_t)n_clouds, 0);
+  std::vector<int64_t> mem_n(formed ? 0 : (size_t)n_members);
+  for (size_t j = 0; j < mem_n.size(); j++) mem_n[j] = A.slots[(size_t)slot[j]].count;
+  for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
+  const int64_t total = pt_off[n_clouds];
+  const float *d_src = nullptr;
+  CHK(points_on_device(c, B[sgtd_engine::VR_PTS], points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(store_pack(c, A, d_src, stride, total, A.used));
+  std::vector<long long> rows;
+  CHK(store_tail_rows(c, A, pt_off, n_clouds, rows));
+  VregSite S{formed ? "sgtd_register_stored_local_loops" : "sgtd_register_stored_voxels", B, c->sv_mode, c->sv_host_soff, c->sv_host_up,
+             c->sv_host_map_vox, c->sv_clock, A.pts.as<float>(), 3, A.cov.as<double>(), A.off.as<long long>(), (int)A.slots.size()};
+  if (formed) {
+    S.d_mem_cloud = formed->slot; S.d_mem_map = formed->map; S.d_mem_pt_off = formed->pt_off; S.d_map_pose = formed->pose;
+    S.d_member_pts = formed->pts; S.d_init = formed->init;
+  }
+  return vreg_run(c, S, o, pt_off, n_clouds, named.data(), map_off, slot, mem_n.data(), map_pose, n_maps, src, tgt, init, n);      // (it ends waited for)
+}
+}  // namespace
+
+extern "C" {
+
+int sgtd_register_stored_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off,
+                                int n_clouds, const int32_t *map_off, const uint32_t *map_frame, const double *map_pose, int n_maps,
+                                const int32_t *src_cloud, const int32_t *tgt_map, const double *init_pose, int n_pairs, int device_ptrs) {
+  sgtd_voxel_register_options o;
+  CHK(vreg_check(e, "sgtd_register_stored_voxels", opt, &o, points, stride_floats, pt_off, n_clouds, map_off, map_frame, map_pose, n_maps, src_cloud, tgt_map,
+                 init_pose, n_pairs, [&](int j, int64_t *np) -> int {
+                   const sgtd_engine *c = home_engine(e);
+                   if (map_frame[j] >= c->st_slot_of.size() || c->st_slot_of[map_frame[j]] == SGTD_STORE_NONE) {
+                     e->err = "sgtd_register_stored_voxels: frame " + std::to_string(map_frame[j]) + " has no stored cloud (sgtd_set_frame_clouds)";
+                     return SGTD_ERR_INVALID;
+                   }
+                   *np = c->st.slots[(size_t)c->st_slot_of[map_frame[j]]].count;
+                   return SGTD_OK;
+                 }));
+  CHK(stored_settings(e, "sgtd_register_stored_voxels", o.k_neighbors, o.plane_eps));
+  const int64_t total = pt_off[n_clouds];
+  const int n_members = n_maps ? map_off[n_maps] : 0;
+  StageRun<int> run(e, &sgtd_engine::sv_n);
+  run.c->sv_local = false;
+  run.on_device([&](sgtd_engine *c) -> int {
+    CHK(store_room(c, total, n_clouds));      // (a rebuild renumbers the slots: the members are looked up behind it)
+    std::vector<int32_t> slot((size_t)n_members);
+    for (int j = 0; j < n_members; j++) slot[(size_t)j] = c->st_slot_of[map_frame[j]];
+    return stored_voxels_run(c, o, points, stride_floats, pt_off, n_clouds, device_ptrs, map_off, slot.data(), map_pose, n_maps, src_cloud, tgt_map,
+                             init_pose, n_pairs);
+  });
+  return run.end(n_pairs);
+}
+
+int sgtd_register_stored_local_loops(sgtd_handle e, const sgtd_voxel_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off,
+                                     int max_per_query, int start, double radius, int max_members, int device_ptrs) {
+  if (!e || max_per_query < 0 || start < SGTD_START_VERIFY || start > SGTD_START_ALIGNED) return SGTD_ERR_INVALID;
+  if (!(std::isfinite(radius) && radius >= 0.0) || max_members < 0) return SGTD_ERR_INVALID;
+  sgtd_voxel_register_options o;
+  CHK(vreg_options(opt, &o));
+  if (!pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  const char *call = "sgtd_register_stored_local_loops";
+  if (e->grp) {
+    e->err = std::string(call) + ": a multi-device handle's batch results live on several engines: form the maps and use sgtd_register_stored_voxels";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (!e->batch_valid || !e->verified) return needs(e, call, "sgtd_verify");
+  if (start == SGTD_START_REFINED && !e->refined) return needs(e, call, "sgtd_refine_poses");
+  if (start == SGTD_START_ALIGNED && !e->aligned) return needs(e, call, "sgtd_align_keypoints");
+  const int nq = e->nq, cn = e->dc.cand_num, mpq = std::min(max_per_query, cn);
+  if (!cloud_set_ok(pt_off, nq, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  if (!gicp_caps_ok(pt_off, nq, 0)) { e->err = gicp_caps_text(call); return SGTD_ERR_UNSUPPORTED; }
+  CHK(stored_settings(e, call, o.k_neighbors, o.plane_eps));
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  CHK(sync_batch(e));
+  const int64_t total = pt_off[nq];
+  const size_t upper = (size_t)nq * mpq;
+  int n = 0;
+  StageRun<int> run(e, &sgtd_engine::sv_n);
+  e->sv_local = true;
+  e->sv_rows.clear(); e->sv_map_frame.clear(); e->sv_mem_off.assign(1, 0);
+  run.on_device([&](sgtd_engine *c) -> int {
+    const size_t n_ids = std::min(c->st_slot_of.size(), c->has_pose.size());
+    CHK(store_room(c, total, nq));      // (a rebuild renumbers the slots: the table is made behind it)
+    if (upper == 0 || c->st_frames == 0 || n_ids == 0)      // (no row can form: a run without a pair and without a map)
+      return stored_voxels_run(c, o, points, stride_floats, pt_off, nq, device_ptrs, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+    CHK(store_table(c));
+    CHK(cons_upload_store(c, c));       // (the pose store's device copy is the consistency and consensus stages')
+    // one buffer: the per-id streams, the rows, the per-map records (a map per row at the most, and per id)
+    const size_t max_maps = std::min(upper, n_ids);
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t was = at; at += relax_up(bytes); return was; };
+    const size_t o_elig = take(n_ids), o_trans = take(3 * n_ids * sizeof(double)), o_flag = take((n_ids + 1) * sizeof(u32)),
+                 o_mapof = take((n_ids + 1) * sizeof(u32)), o_count = take(((size_t)nq + 1) * sizeof(u32)), o_first = take(((size_t)nq + 1) * sizeof(u32)),
+                 o_rows = take(upper * sizeof(int4)), o_init = take(upper * 12 * sizeof(double)), o_mframe = take(max_maps * sizeof(u32)),
+                 o_mcount = take(max_maps * sizeof(int)), o_mpts = take(max_maps * sizeof(long long)), o_mcut = take(max_maps * sizeof(int)),
+                 o_thr = take(max_maps * sizeof(u64)), o_thrid = take(max_maps * sizeof(u32)), o_moff = take((max_maps + 1) * sizeof(int));
+    CHK(ensure(c, c->sv_form, at));
+    char *fb = c->sv_form.as<char>();
+    c->sv_init_off = o_init;
+    StoredLocalParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.score = c->v_score.as<double>(); P.n_cand = c->n_cand.as<int>(); P.cand_frame = c->cand_frame.as<int>();
+    P.pose = start == SGTD_START_REFINED ? c->r_pose.as<double>() : start == SGTD_START_ALIGNED ? c->a_pose.as<double>() : c->v_pose.as<double>();
+    P.cand_num = cn; P.nq = nq; P.max_per_query = mpq;
+    P.slot_of = c->st_table.as<int>(); P.pose_store = c->ck_store.as<float>(); P.has_pose = c->ck_has.as<unsigned char>();
+    P.arena_off = c->st.off.as<long long>(); P.n_ids = (u32)n_ids;
+    P.elig = reinterpret_cast<unsigned char *>(fb + o_elig); P.trans = reinterpret_cast<double *>(fb + o_trans);
+    P.count = reinterpret_cast<u32 *>(fb + o_count); P.first = reinterpret_cast<const u32 *>(fb + o_first);
+    P.rows = reinterpret_cast<int4 *>(fb + o_rows); P.init = reinterpret_cast<double *>(fb + o_init);
+    P.flag = reinterpret_cast<u32 *>(fb + o_flag); P.map_of = reinterpret_cast<const u32 *>(fb + o_mapof);
+    P.map_frame = reinterpret_cast<u32 *>(fb + o_mframe);
+    P.rr = radius * radius; P.max_members = max_members;
+    P.mem_count = reinterpret_cast<int *>(fb + o_mcount); P.mem_pts = reinterpret_cast<long long *>(fb + o_mpts);
+    P.mem_cut = reinterpret_cast<int *>(fb + o_mcut); P.thr_d2 = reinterpret_cast<u64 *>(fb + o_thr); P.thr_id = reinterpret_cast<u32 *>(fb + o_thrid);
+    P.mem_off = reinterpret_cast<const int *>(fb + o_moff);
+    hipStream_t s = c->stream;
+    const int id_grid = grid_for((long long)n_ids + 1, SGTD_SL_THREADS), q_grid = grid_for(nq, SGTD_SL_THREADS / 64);
+    sl_eligible_kernel<<<id_grid, SGTD_SL_THREADS, 0, s>>>(P);
+    HIPCHK(hipMemsetAsync(P.count, 0, ((size_t)nq + 1) * sizeof(u32), s));
+    sl_rows_kernel<<<q_grid, SGTD_SL_THREADS, 0, s>>>(P, 0);
+    HIPCHK(hipGetLastError());
+    CHK(device_scan(c, P.count, reinterpret_cast<u32 *>(fb + o_first), (long long)nq + 1));
+    CHK(device_scan(c, P.flag, reinterpret_cast<u32 *>(fb + o_mapof), (long long)n_ids + 1));
+    sl_rows_kernel<<<q_grid, SGTD_SL_THREADS, 0, s>>>(P, 1);
+    sl_map_frames_kernel<<<id_grid, SGTD_SL_THREADS, 0, s>>>(P);
+    sl_members_kernel<<<(unsigned)max_maps, SGTD_SL_THREADS, 0, s>>>(P, 0);
+    HIPCHK(hipGetLastError());
+    // the one read-back: the rows, the maps' frames, the member counts and points
+    u32 found = 0, n_maps = 0;
+    std::vector<int32_t> rows(upper * 4);
+    std::vector<u32> map_frame(max_maps);
+    std::vector<int> mem_count(max_maps);
+    std::vector<long long> mem_pts(max_maps);
+    CHK(d2h(c, &found, P.first + nq, sizeof(u32)));
+    CHK(d2h(c, &n_maps, P.map_of + n_ids, sizeof(u32)));
+    CHK(d2h(c, rows.data(), P.rows, upper * sizeof(int4)));
+    CHK(d2h(c, map_frame.data(), P.map_frame, max_maps * sizeof(u32)));
+    CHK(d2h(c, mem_count.data(), P.mem_count, max_maps * sizeof(int)));
+    CHK(d2h(c, mem_pts.data(), P.mem_pts, max_maps * sizeof(long long)));
+    CHK(xfer_sync(c));
+    if (found == 0)
+      return stored_voxels_run(c, o, points, stride_floats, pt_off, nq, device_ptrs, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+    int64_t total_src = 0, member_pts = 0, members = 0;
+    for (u32 k = 0; k < found; k++) total_src += pt_off[rows[(size_t)k * 4] + 1] - pt_off[rows[(size_t)k * 4]];
+    for (u32 m = 0; m < n_maps; m++) { member_pts += mem_pts[m]; members += mem_count[m]; }
+    if (found > SGTD_REG_MAX_PAIRS || n_maps > SGTD_VREG_MAX_MAPS || member_pts > SGTD_VREG_MAX_MEMBER_POINTS || members > SGTD_VREG_MAX_MEMBER_POINTS ||
+        total_src * o.neighbor_mode > SGTD_VREG_MAX_CORR) {
+      c->err = std::string(call) + ": the rows and maps formed pass " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs, " + std::to_string(SGTD_VREG_MAX_MAPS) +
+               " maps, " + std::to_string(SGTD_VREG_MAX_MEMBER_POINTS) + " members or member points, or " + std::to_string(SGTD_VREG_MAX_CORR) +
+               " source points over the pairs times neighbor_mode";
+      return SGTD_ERR_UNSUPPORTED;
+    }
+    n = (int)found;
+    std::vector<int32_t> src, tgt, map_off((size_t)n_maps + 1, 0);
+    for (int k = 0; k < n; k++) {
+      const int32_t *r = rows.data() + (size_t)k * 4;
+      src.push_back(r[0]); tgt.push_back(r[3]);
+      c->sv_rows.insert(c->sv_rows.end(), r, r + 4);
+    }
+    for (u32 m = 0; m < n_maps; m++) map_off[(size_t)m + 1] = map_off[m] + mem_count[m];
+    c->sv_map_frame.assign(map_frame.begin(), map_frame.begin() + n_maps);
+    c->sv_mem_off.assign(map_off.begin(), map_off.end());
+    // the members: ids, slots, maps, sizes and their scan, poses
+    const size_t nm = (size_t)members;
+    at = 0;
+    const size_t o_member = take(nm * sizeof(int)), o_slot = take(nm * sizeof(int)), o_map = take(nm * sizeof(int)), o_size = take((nm + 1) * sizeof(u32)),
+                 o_ptoff = take((nm + 1) * sizeof(u32)), o_pose = take(nm * 12 * sizeof(double));
+    CHK(ensure(c, c->sv_members, at));
+    char *mb = c->sv_members.as<char>();
+    c->sv_member_off = o_member; c->sv_pose_off = o_pose;
+    P.member = reinterpret_cast<int *>(mb + o_member); P.mem_slot = reinterpret_cast<int *>(mb + o_slot); P.mem_map = reinterpret_cast<int *>(mb + o_map);
+    P.mem_size = reinterpret_cast<u32 *>(mb + o_size); P.mem_pose = reinterpret_cast<double *>(mb + o_pose);
+    CHK(h2d(c, fb + o_moff, map_off.data(), map_off.size() * sizeof(int)));
+    HIPCHK(hipMemsetAsync(P.mem_size + nm, 0, sizeof(u32), s));
+    sl_members_kernel<<<n_maps, SGTD_SL_THREADS, 0, s>>>(P, 1);
+    HIPCHK(hipGetLastError());
+    CHK(device_scan(c, P.mem_size, reinterpret_cast<u32 *>(mb + o_ptoff), (long long)nm + 1));
+    sl_poses_kernel<<<grid_for((long long)nm, SGTD_SL_THREADS), SGTD_SL_THREADS, 0, s>>>(P, (int)nm);
+    HIPCHK(hipGetLastError());
+    const StoredMembers formed{P.mem_slot, P.mem_map, reinterpret_cast<const int *>(mb + o_ptoff), P.mem_pose, member_pts, P.init};
+    return stored_voxels_run(c, o, points, stride_floats, pt_off, nq, device_ptrs, map_off.data(), nullptr, nullptr, (int)n_maps, src.data(), tgt.data(),
+                             nullptr, n, &formed);
+  });
+  return run.end(n);
+}
+
+int sgtd_result_stored_local_pairs(sgtd_handle e, int32_t *query, int32_t *cand, int32_t *frame, int32_t *tgt_map, double *init, int64_t capacity,
+                                   int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  if (!c->sv_local) { e->err = "no rows: sgtd_register_stored_local_loops has not run"; return SGTD_ERR_STATE; }
+  const int64_t need = c->sv_n;
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  for (size_t k = 0; k < m; k++) {
+    if (query) query[k] = c->sv_rows[k * 4];
+    if (cand) cand[k] = c->sv_rows[k * 4 + 1];
+    if (frame) frame[k] = c->sv_rows[k * 4 + 2];
+    if (tgt_map) tgt_map[k] = c->sv_rows[k * 4 + 3];
+  }
+  if (m) {
+    CopyOut out(e, c);
+    out.get(init, c->sv_form.as<char>() + c->sv_init_off, m * 12 * sizeof(double));
+    CHK(out.finish());
+  }
+  return need > capacity && (query || cand || frame || tgt_map || init) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_stored_local_maps(sgtd_handle e, uint32_t *map_frame, int64_t *mem_off, uint32_t *member, double *member_pose, int64_t cap_maps,
+                                  int64_t cap_members, int64_t *n_maps, int64_t *n_members) {
+  if (!e || cap_maps < 0 || cap_members < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  if (!c->sv_local) { e->err = "no maps: sgtd_register_stored_local_loops has not run"; return SGTD_ERR_STATE; }
+  const int64_t maps = (int64_t)c->sv_map_frame.size(), members = c->sv_mem_off.back();
+  if (n_maps) *n_maps = maps;
+  if (n_members) *n_members = members;
+  const size_t m = (size_t)std::min(maps, cap_maps), k = (size_t)std::min(members, cap_members);
+  if (map_frame) std::copy(c->sv_map_frame.begin(), c->sv_map_frame.begin() + m, map_frame);
+  if (mem_off && (maps <= cap_maps)) std::copy(c->sv_mem_off.begin(), c->sv_mem_off.end(), mem_off);
+  else if (mem_off) std::copy(c->sv_mem_off.begin(), c->sv_mem_off.begin() + m, mem_off);
+  if (k) {
+    CopyOut out(e, c);
+    out.get(member, c->sv_members.as<char>() + c->sv_member_off, k * sizeof(int));
+    out.get(member_pose, c->sv_members.as<char>() + c->sv_pose_off, k * 12 * sizeof(double));
+    CHK(out.finish());
+  }
+  const bool short_maps = maps > cap_maps && (map_frame || mem_off), short_members = members > cap_members && (member || member_pose);
+  return short_maps || short_members ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_result_stored_voxel_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *n_corr,
+                                        int32_t *iterations, int32_t *status) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  if (c->sv_n == 0) return SGTD_OK;
+  return reg_rows_out(e, c, RegOut((size_t)c->sv_n, true), c->sv[sgtd_engine::VR_OUT].p, pose, fitness, cost, n_matched, n_corr, iterations, status);
+}
+
+int sgtd_result_stored_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  return vreg_map_out(e, c, c->sv, c->sv_host_map_vox, map, coord, n_points, mean, cov, capacity, n);
+}
+
+int sgtd_result_stored_voxel_matches(sgtd_handle e, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  return vreg_matches_out(e, c, c->sv, c->sv_host_soff, c->sv_mode, c->sv_n, pair, voxel, capacity, n);
+}
+
+int sgtd_stored_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  vreg_ms_out(c->sv_clock, ms_cov, ms_map, ms_corr, ms_rest, ms_total);
   return SGTD_OK;
 }
 

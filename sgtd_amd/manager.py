@@ -1756,6 +1756,149 @@ class STDescManager:
         self._check(self._L.sgtd_voxel_register_stage_ms(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    # ---- voxel maps whose members are stored clouds (sgtd_register_stored_voxels) -------------------------------
+    def register_stored_voxels(self, points, pt_off, map_off, map_frame, map_pose, src, tgt_map, init=None, **options):
+        """sgtd_register_stored_voxels: register_voxels with the maps' members read from the cloud store.  points,
+        pt_off: the call's clouds (the sources), numpy or a torch.cuda tensor; map m has the members
+        map_frame[map_off[m]:map_off[m + 1]], frame ids that have a stored cloud (set_frame_clouds); map_pose, src,
+        tgt_map, init, options and the returned dict as register_voxels'.  The results are register_voxels' on the call's
+        clouds followed by the members' stored clouds, bit for bit; k_neighbors and plane_eps must be the store's."""
+        shape, pp, dev = self._points_arg(points)
+        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+        if off.size < 1:
+            raise ValueError("pt_off: n_clouds + 1 offsets")
+        if off[-1] > shape[0]:
+            raise ValueError("pt_off names more points than were given")
+        moff = np.ascontiguousarray(np.asarray(map_off).reshape(-1), np.int32)
+        if moff.size < 1:
+            raise ValueError("map_off: n_maps + 1 offsets")
+        mfr = self._frame_ids(map_frame)
+        if moff[-1] > mfr.size:
+            raise ValueError("map_off names more members than were given")
+        mp = None
+        if map_pose is not None:
+            mp = np.ascontiguousarray(map_pose, np.float64).reshape(-1, 12)
+            if mp.shape[0] != mfr.size:
+                raise ValueError("map_pose: (members, 12), one pose per member")
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        t = np.ascontiguousarray(tgt_map, np.int32).reshape(-1)
+        n = s.size
+        if t.size != n:
+            raise ValueError("src and tgt_map: one cloud and one map index per pair")
+        p0 = None
+        if init is not None:
+            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
+            if p0.shape[0] != n:
+                raise ValueError("init: (n, 12), one start pose per pair")
+        opt = VoxelRegisterOptions()
+        self._L.sgtd_default_voxel_register_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(VoxelRegisterOptions._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        self._check(self._L.sgtd_register_stored_voxels(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(moff), _p(mfr), _p(mp),
+                                                        moff.size - 1, _p(s), _p(t), _p(p0), n, dev))
+        self._svreg_n = n
+        return self.result_stored_voxel_registered()
+
+    def result_stored_voxel_registered(self):
+        """-> result_voxel_registered()'s dict of the last register_stored_voxels call"""
+        n = self._svreg_n
+        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
+               "n_matched": np.zeros(n, np.int32), "n_corr": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32),
+               "status": np.zeros(n, np.int32)}
+        self._check(self._L.sgtd_result_stored_voxel_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
+                                                                _p(out["n_corr"]), _p(out["iterations"]), _p(out["status"])))
+        return out
+
+    def stored_voxel_map(self, m):
+        """the voxels of map m of the last register_stored_voxels call -> voxel_map()'s dict"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_voxel_map(self._h, int(m), None, None, None, None, 0, C.byref(n)))
+        v = n.value
+        out = {"coord": np.zeros((v, 3), np.int32), "n_points": np.zeros(v, np.int32), "mean": np.zeros((v, 3), np.float64),
+               "cov": np.zeros((v, 3, 3), np.float64)}
+        self._check(self._L.sgtd_result_stored_voxel_map(self._h, int(m), _p(out["coord"]), _p(out["n_points"]), _p(out["mean"]), _p(out["cov"]), v,
+                                                         C.byref(n)))
+        return out
+
+    def stored_voxel_matches(self, pair):
+        """the correspondences of one pair of the last register_stored_voxels call, as voxel_matches()"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_voxel_matches(self._h, int(pair), None, 0, C.byref(n)))
+        v = np.zeros(n.value, np.int32)
+        self._check(self._L.sgtd_result_stored_voxel_matches(self._h, int(pair), _p(v), n.value, C.byref(n)))
+        return v
+
+    def register_loops_local_stored(self, query_points, query_pt_off, radius=15.0, max_members=0, max_per_query=5, start="verify", **options):
+        """sgtd_register_stored_local_loops, after verify(): register_loops_local with the map clouds read from the cloud
+        store (set_frame_clouds), the frames' poses from set_frame_poses, and the pairs, the local maps and the members'
+        relative poses formed on the device.  A candidate whose frame has no stored cloud, no stored pose or a pose that
+        is not finite is dropped.  With max_members = m > 0 a map keeps its frame and the m - 1 nearest others (ties to
+        the smaller id), not voxel_map_members' first m in id order.  query_points: (total, 3 or 4) f32, numpy or a
+        torch.cuda tensor, with the n_queries + 1 offsets query_pt_off.  -> register_loops_local's dict: query, cand, frame,
+        tgt_map [m] (int32), init [m, 12], register_voxels' fields per pair, map_frames, members (per map, the member frame
+        ids), map_off, map_frame, map_pose as register_stored_voxels takes them"""
+        starts = {"verify": 0, "refined": 1, "aligned": 2}
+        if start not in starts:
+            raise ValueError('start: "verify", "refined" or "aligned"')
+        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
+            raise ValueError("max_per_query: an integer, not negative")
+        if isinstance(max_members, bool) or not isinstance(max_members, (int, np.integer)) or max_members < 0:
+            raise ValueError("max_members: an integer, not negative (0 = no cap)")
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (np.isfinite(radius) and radius >= 0):
+            raise ValueError("radius: finite and not negative")
+        shape, pp, dev = self._points_arg(query_points, "query_points")
+        qoff = np.ascontiguousarray(np.asarray(query_pt_off).reshape(-1), np.int64)
+        if qoff.size != self._nq + 1:
+            raise ValueError("query_pt_off: n_queries + 1 offsets")
+        if qoff[-1] > shape[0]:
+            raise ValueError("query_pt_off names more points than were given")
+        opt = VoxelRegisterOptions()
+        self._L.sgtd_default_voxel_register_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(VoxelRegisterOptions._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        self._check(self._L.sgtd_register_stored_local_loops(self._h, C.byref(opt), pp, int(shape[1]), _p(qoff), int(max_per_query), starts[start],
+                                                             float(radius), int(max_members), dev))
+        q, c, f, tgt, init = self.stored_local_pairs()
+        self._svreg_n = len(q)
+        out = self.result_stored_voxel_registered()
+        maps = self.stored_local_maps()
+        out.update(query=q, cand=c, frame=f, tgt_map=tgt, init=init, src_cloud=q.copy(), map_frames=maps["map_frame"].tolist(),
+                   members=[maps["member"][a:b].astype(np.int32) for a, b in zip(maps["mem_off"][:-1], maps["mem_off"][1:])],
+                   map_off=maps["mem_off"].astype(np.int32), map_frame=maps["member"], map_pose=maps["member_pose"])
+        return out
+
+    def stored_local_pairs(self):
+        """the rows of the last register_loops_local_stored call -> (query, cand, frame, tgt_map [m] int32, init [m, 12])"""
+        n = C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_local_pairs(self._h, None, None, None, None, None, 0, C.byref(n)))
+        m = n.value
+        q, c, f, t, init = (np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 12), np.float64))
+        self._check(self._L.sgtd_result_stored_local_pairs(self._h, _p(q), _p(c), _p(f), _p(t), _p(init), m, C.byref(n)))
+        return q, c, f, t, init
+
+    def stored_local_maps(self):
+        """the maps of the last register_loops_local_stored call -> dict of map_frame [maps] (uint32, ascending), mem_off
+        [maps + 1] (int64), member [members] (uint32: a map's own frame first, the others in ascending id) and member_pose
+        [members, 12] (T_frame^-1 T_member; the identity for the frame itself)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.sgtd_result_stored_local_maps(self._h, None, None, None, None, 0, 0, C.byref(a), C.byref(b)))
+        out = {"map_frame": np.zeros(a.value, np.uint32), "mem_off": np.zeros(a.value + 1, np.int64), "member": np.zeros(b.value, np.uint32),
+               "member_pose": np.zeros((b.value, 12), np.float64)}
+        self._check(self._L.sgtd_result_stored_local_maps(self._h, _p(out["map_frame"]), _p(out["mem_off"]), _p(out["member"]), _p(out["member_pose"]),
+                                                          a.value, b.value, C.byref(a), C.byref(b)))
+        return out
+
+    def stored_voxel_register_stage_ms(self):
+        """device milliseconds of the last register_stored_voxels call: covariances (of the call's clouds alone), map
+        build, correspondence passes, the rest, the whole call (zeros unless set_timing(True))"""
+        v = [C.c_float(0) for _ in range(5)]
+        self._check(self._L.sgtd_stored_voxel_register_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     @staticmethod
     def voxel_map_members(frame, frame_poses, has_cloud, radius=15.0, max_members=0):
         """the members of the local map around `frame`: the frames that have a cloud and a pose whose position lies within
