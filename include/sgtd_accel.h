@@ -722,7 +722,9 @@ int sgtd_result_loop_edges(sgtd_handle h, double icp_threshold, int flags,
  * sgtd_consistent_loops; QUAT, UNIT and ROT those of sgtd_relax_poses.
  * Validity: candidate k is valid when k < n_cand, it has a result (score >= 0: neither rejected nor masked out), its frame
  *   has a stored pose B_k (an id beyond the stored range has none, which is no error) and all 24 numbers of B_k and of its
- *   relative pose T_k are finite.  P_k = mul(B_k, T_k).
+ *   relative pose T_k are finite.  P_k = mul(B_k, T_k).  k ranges over the cand_num slots only: an n_cand above cand_num
+ *   counts as cand_num, a negative one as 0.  The frame id is read as a uint32_t (a negative cand_frame names no stored
+ *   pose); a score of 0.0 or -0.0 is a result, a NaN score is none.
  * Agreement, for valid k < l: Z = mul(inv(P_k), P_l); d2 = (Zt[0]*Zt[0] + Zt[1]*Zt[1]) + Zt[2]*Zt[2];
  *   tr = (Z[0][0] + Z[1][1]) + Z[2][2]; the pair agrees iff d2 <= tt and tr >= min_trace, with tt = max_trans*max_trans and
  *   min_trace = 1.0 + 2.0*cos(max_rot) computed once on the host as sgtd_consistent_loops computes them and handed back

@@ -37,8 +37,8 @@ def candidates(store_ids, store_poses, n_cand, cand_frame, score, rel_pose):
 def adjacency(P, valid, tt, min_trace):
     """-> (adj, gap_d2, gap_tr) as _consistency_ref.adjacency gives them, with Z = mul(inv(P_k), P_l) for k < l"""
     n = valid.size
-    iP = cr.inv(P)
     with np.errstate(all="ignore"):
+        iP = cr.inv(P)
         Zr, Zt = cr.mul((iP[0][:, None], iP[1][:, None]), (P[0][None, :], P[1][None, :]))
         d2 = (Zt[..., 0] * Zt[..., 0] + Zt[..., 1] * Zt[..., 1]) + Zt[..., 2] * Zt[..., 2]
         tr = (Zr[..., 0, 0] + Zr[..., 1, 1]) + Zr[..., 2, 2]
