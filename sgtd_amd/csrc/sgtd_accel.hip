@@ -342,18 +342,21 @@ struct sgtd_engine {
   std::vector<int> rx_host_csr;
   std::vector<double> rx_host_w;
   std::vector<unsigned char> rx_host_held;
-  // sgtd_register_clouds (register_kernels.hip.h): independent of the batch.  rg_in: the call's index arrays, offsets and
-  // start poses; rg_pts: the points when the host gave them; rg_cov: a covariance per point; rg_part: the slices' minima;
-  // rg_match: the last pass's matches and M_i; rg_state: RegState per pair; rg_out: the result rows; rg_ctl: the count of
-  // unfinished pairs.  rg_n < 0: no results; rg_host_*: what the getters need of the call; rg_clock.ms: covariances,
-  // searches, the rest, the whole call (filled under sgtd_set_timing)
-  DevBuf rg_in, rg_pts, rg_cov, rg_part, rg_match, rg_state, rg_out, rg_ctl;
-  int rg_n = -1;
-  std::vector<int64_t> rg_host_off;
-  std::vector<int> rg_host_soff;         // src_off [n + 1]
-  std::vector<unsigned char> rg_host_named;
-  std::vector<int> rg_host_up;           // (the source of the index upload)
-  LapClock rg_clock;
+  // A dense GICP run (register_kernels.hip.h): independent of the batch.  in: the call's index arrays, offsets and start
+  // poses; pts: the points when the host gave them; cov: a covariance per point of the call's clouds; part: the slices'
+  // minima; match: the last pass's matches and M_i; state: RegState per pair; out: the result rows; ctl: the count of
+  // unfinished pairs.  n < 0: no results; host_*: what the getters need of the call; clock.ms: covariances, searches,
+  // the rest, the whole call (filled under sgtd_set_timing)
+  struct DenseRun {
+    DevBuf in, pts, cov, part, match, state, out, ctl;
+    int n = -1;
+    std::vector<int64_t> host_off;
+    std::vector<int> host_soff;         // src_off [n + 1]
+    std::vector<unsigned char> host_named;
+    std::vector<int> host_up;           // (the source of the index upload)
+    LapClock clock;
+  };
+  DenseRun dense;      // sgtd_register_clouds: every cloud is the call's
   // sgtd_set_frame_clouds (cloud_store_kernels.hip.h): the cloud store, settings of the handle.  st: the arena (points,
   // covariances and the clouds' offsets on the device: the stored clouds are its first clouds, "slots", in arrival
   // order, a call's own clouds follow for the length of the call) and what the host knows of it.  A slot whose frame was
@@ -372,46 +375,38 @@ struct sgtd_engine {
   double st_eps = 0.0;
   DevBuf st_stage, st_idx, st_table;
   u64 st_serial = 0, st_table_serial = ~0ull;
-  // sgtd_register_stored / sgtd_register_stored_loops: independent of the batch and of sgtd_register_clouds' and
-  // sgtd_register_voxels' buffers.  sr_in .. sr_ctl as rg_*; sr_pts: the call's points when the host gave them; sr_cov:
-  // the covariances of the call's clouds, copied out of the arena; sr_pairs: the loops form's counts, their scan, pair
-  // rows and start poses.  sr_n < 0: no results; sr_rows: the loops form's rows (query, candidate, frame) on the host,
-  // sr_loops: the results are that form's.
-  DevBuf sr_in, sr_pts, sr_cov, sr_part, sr_match, sr_state, sr_out, sr_ctl, sr_pairs;
-  int sr_n = -1;
+  // sgtd_register_stored / sgtd_register_stored_loops: the dense run over the cloud store's arena (RegSite), independent
+  // of the other registration calls' buffers.  stored.cov: the covariances of the call's clouds, copied out of the arena.
+  // sr_pairs: the loops form's counts, their scan, pair rows and start poses; sr_rows: the loops form's rows (query,
+  // candidate, frame) on the host, sr_loops: the results are that form's.
+  DenseRun stored;
+  DevBuf sr_pairs;
   bool sr_loops = false;
-  std::vector<int64_t> sr_host_off;
-  std::vector<int> sr_host_soff, sr_host_up;
-  std::vector<unsigned char> sr_host_named;
   std::vector<int32_t> sr_rows;
   size_t sr_init_off = 0;            // the rows' start poses within sr_pairs
-  LapClock sr_clock;
-  // sgtd_register_voxels (voxel_register_kernels.hip.h): independent of the batch and of sgtd_register_clouds' buffers.
-  // VR_IN: the call's index arrays, offsets and poses; VR_PTS: the points when the host gave them; VR_COV: a covariance per
-  // point; VR_KEY_* / VR_VAL_*: the sort's pairs; VR_FLAGS .. VR_MAP_VOX: the voxels' heads, keys, first points and the
-  // maps' ranges; VR_MEAN / VR_VCOV: the Gaussians; VR_VID / VR_MW: the per-correspondence streams; VR_STATE, VR_OUT,
-  // VR_CTL as rg_*.  vr_n < 0: no results; vr_host_*: what the getters need of the call; vr_clock.ms: covariances, map
-  // build, correspondence passes, the rest, the whole call (filled under sgtd_set_timing)
+  // A voxelised GICP run (voxel_register_kernels.hip.h): independent of the batch.  VR_IN: the call's index arrays,
+  // offsets and poses; VR_PTS: the points when the host gave them; VR_COV: a covariance per point; VR_KEY_* / VR_VAL_*:
+  // the sort's pairs; VR_FLAGS .. VR_MAP_VOX: the voxels' heads, keys, first points and the maps' ranges; VR_MEAN /
+  // VR_VCOV: the Gaussians; VR_VID / VR_MW: the per-correspondence streams; VR_STATE, VR_OUT, VR_CTL as DenseRun's.
+  // n < 0: no results; mode: the call's neighbor_mode; host_*: what the getters need of the call; clock.ms: covariances,
+  // map build, correspondence passes, the rest, the whole call (filled under sgtd_set_timing)
   enum { VR_IN = 0, VR_PTS, VR_COV, VR_KEY_A, VR_KEY_B, VR_VAL_A, VR_VAL_B, VR_FLAGS, VR_EXCL, VR_COUNTS, VR_VKEY, VR_VSTART, VR_MAP_VOX, VR_MEAN, VR_VCOV,
          VR_VID, VR_MW, VR_STATE, VR_OUT, VR_CTL, VR_BUFS };
-  DevBuf vr[VR_BUFS];
-  int vr_n = -1, vr_mode = 1;
-  std::vector<int> vr_host_soff;         // src_off [n + 1]
-  std::vector<u32> vr_host_map_vox;      // [n_maps + 1]
-  std::vector<int> vr_host_up;           // (the source of the index upload)
-  LapClock vr_clock;
-  // sgtd_register_stored_voxels: the same run over the cloud store's arena (VregSite), independent of the batch and of
-  // the other registration calls' buffers.  sv[VR_*] as vr[] (VR_PTS: the call's points when the host gave them, before
-  // they are packed behind the slots; VR_COV: unused, the covariances are the arena's).  sv_n < 0: no results; sv_host_*,
-  // sv_mode, sv_clock as vr_*
-  DevBuf sv[VR_BUFS];
-  int sv_n = -1, sv_mode = 1;
-  std::vector<int> sv_host_soff, sv_host_up;
-  std::vector<u32> sv_host_map_vox;
-  LapClock sv_clock;
+  struct VoxelRun {
+    DevBuf B[VR_BUFS];
+    int n = -1, mode = 1;
+    std::vector<int> host_soff;         // src_off [n + 1]
+    std::vector<int> host_up;           // (the source of the index upload)
+    std::vector<u32> host_map_vox;      // [n_maps + 1]
+    LapClock clock;
+  };
+  VoxelRun vox;        // sgtd_register_voxels: every cloud is the call's
+  // sgtd_register_stored_voxels: the same run over the cloud store's arena (VregSite).  VR_PTS: the call's points when
+  // the host gave them, before they are packed behind the slots; VR_COV: unused, the covariances are the arena's
+  VoxelRun svox;
   // sgtd_register_stored_local_loops (stored_local_kernels.hip.h): sv_form: the per-id streams, the rows and the per-map
   // records (StoredLocalParams); sv_members: the member lists, slots, sizes, point offsets and relative poses.  sv_local:
-  // the results are that form's; sv_rows: its rows (query, candidate, frame, map), sv_map_frame, sv_mem_off: the maps'
+  // svox's results are that form's; sv_rows: its rows (query, candidate, frame, map), sv_map_frame, sv_mem_off: the maps'
   // frames and member offsets, on the host; sv_init_off / sv_member_off / sv_pose_off: where the start poses (in sv_form),
   // the member ids and their poses (in sv_members) lie
   DevBuf sv_form, sv_members;
@@ -573,6 +568,17 @@ void free_store(DescStore &s) {
   free_buf(s.side); free_buf(s.angle); free_buf(s.center); free_buf(s.vertex);
   free_buf(s.label); free_buf(s.frame); free_buf(s.node_id); free_buf(s.qrec);
   s.cap = 0;
+}
+using DenseRun = sgtd_engine::DenseRun;
+using VoxelRun = sgtd_engine::VoxelRun;
+// a registration run's buffers and its clock's events
+void free_run(DenseRun &r) {
+  for (DevBuf *b : {&r.in, &r.pts, &r.cov, &r.part, &r.match, &r.state, &r.out, &r.ctl}) free_buf(*b);
+  r.clock.destroy();
+}
+void free_run(VoxelRun &r) {
+  for (DevBuf &b : r.B) free_buf(b);
+  r.clock.destroy();
 }
 
 // ---------------------------------------------------------------------------
@@ -2329,18 +2335,15 @@ int sgtd_destroy(sgtd_handle e) {
                     &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state,
                     &e->cs_in, &e->cs_out,
                     &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl,
-                    &e->rg_in, &e->rg_pts, &e->rg_cov, &e->rg_part, &e->rg_match, &e->rg_state, &e->rg_out, &e->rg_ctl,
-                    &e->st.pts, &e->st.cov, &e->st.off, &e->st_stage, &e->st_idx, &e->st_table,
-                    &e->sr_in, &e->sr_pts, &e->sr_cov, &e->sr_part, &e->sr_match, &e->sr_state, &e->sr_out, &e->sr_ctl, &e->sr_pairs,
-                    &e->sv_form, &e->sv_members};
+                    &e->st.pts, &e->st.cov, &e->st.off, &e->st_stage, &e->st_idx, &e->st_table, &e->sr_pairs, &e->sv_form, &e->sv_members};
   for (DevBuf *b : bufs) free_buf(*b);
   for (DevBuf &b : e->sk) free_buf(b);
   for (DevBuf &b : e->lm) free_buf(b);
-  for (DevBuf &b : e->vr) free_buf(b);
-  for (DevBuf &b : e->sv) free_buf(b);
+  free_run(e->dense); free_run(e->stored);
+  free_run(e->vox); free_run(e->svox);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
-  for (LapClock *k : {&e->rg_clock, &e->sr_clock, &e->vr_clock, &e->sv_clock, &e->lm_clock}) k->destroy();
+  e->lm_clock.destroy();
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
@@ -3738,12 +3741,18 @@ void keypoint_params(sgtd_engine *e, bool refined, double radius, size_t nb, Par
 // the engine a handle's batch-independent results live on: the handle itself, a group's first device
 sgtd_engine *home_engine(sgtd_engine *e) { return e->grp ? multi::device_handle(e, 0) : e; }
 
-// a getter's state check: *c is e's home engine, whose count `n` of results is negative while the stage has not run
-// (`missing` says so on the caller's handle)
-template <class N>
-int stage_ready(sgtd_engine *e, N sgtd_engine::*n, const char *missing, sgtd_engine **c) {
+// a stage's count of results, by the engine's member that stands for the stage: the count itself, or the registration
+// run that holds it
+template <class N> N &stage_count(N &n) { return n; }
+int &stage_count(DenseRun &r) { return r.n; }
+int &stage_count(VoxelRun &r) { return r.n; }
+
+// a getter's state check: *c is e's home engine, whose count of results (stage_count of `stage`) is negative while the
+// stage has not run (`missing` says so on the caller's handle)
+template <class S>
+int stage_ready(sgtd_engine *e, S sgtd_engine::*stage, const char *missing, sgtd_engine **c) {
   *c = home_engine(e);
-  if ((*c)->*n < 0) { e->err = missing; return SGTD_ERR_STATE; }
+  if (stage_count((*c)->*stage) < 0) { e->err = missing; return SGTD_ERR_STATE; }
   return SGTD_OK;
 }
 
@@ -3765,7 +3774,7 @@ struct CopyOut {
   }
 };
 
-// An entry point's run on the home engine c: from here on the stage has no results (its count `n` is negative; no
+// An entry point's run on the home engine c: from here on the stage has no results (its count, *n, is negative; no
 // device is touched yet), on_device() selects c's device and runs the stage's work at once (nothing may switch the
 // device in between: a group's getters do), and end() marks the results present unless that work failed, whose text
 // it hands a group handle.  A call with nothing to run ends without on_device().
@@ -3775,7 +3784,8 @@ struct StageRun {
   N *n;
   PinScope pin;
   int st = SGTD_OK;
-  StageRun(sgtd_engine *e_, N sgtd_engine::*n_) : e(e_), c(home_engine(e_)), n(&(c->*n_)), pin(c) { *n = -1; }
+  template <class S>
+  StageRun(sgtd_engine *e_, S sgtd_engine::*stage) : e(e_), c(home_engine(e_)), n(&stage_count(c->*stage)), pin(c) { *n = -1; }
   int select() {
     sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the stage)
     HIPCHK(hipSetDevice(c->cfg.device_id));
@@ -5216,13 +5226,10 @@ int gicp_rounds(sgtd_engine *c, const char *call, const RegParams &P, int unfini
 // over the cloud store's arena, whose stored clouds come before the call's.
 struct RegSite {
   const char *call;
-  DevBuf &in, &part, &match, &state, &out, &ctl;
-  std::vector<int> &up, &soff;      // the source of the index upload; src_off [n + 1]
-  LapClock &clock;
+  DenseRun &R;         // the run's buffers, host arrays and clock
   const float *pts;                 // the points of every cloud the kernels may name, on the device
   int stride;
-  DevBuf *cov_buf;                  // the call's own covariances, grown to its points; NULL: `cov` is where they go
-  double *cov;
+  double *cov;                      // where the covariances of those clouds go; NULL: R.cov, grown to the call's points
   const long long *d_off;           // the clouds' offsets where they are on the device already; NULL: pt_off is uploaded
   int first;                        // the index the kernels know the call's cloud 0 by
   const double *d_init;             // the start poses where they are on the device already (init is NULL then)
@@ -5234,16 +5241,17 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
             const int32_t *src, const int32_t *tgt, const int64_t *tgt_n, const double *init, int n) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
   const bool timed = c->timing;
-  LapClock &clock = S.clock;
+  DenseRun &R = S.R;
+  LapClock &clock = R.clock;
   CHK(clock.start(c, timed));
   const size_t total = (size_t)pt_off[n_clouds];
   // the tiles: of the pairs' sources, of the clouds that need covariances
   int64_t max_tgt = 0;
   for (int k = 0; k < n; k++) max_tgt = std::max<int64_t>(max_tgt, tgt_n[k]);
-  GicpIndex G(S.up);
-  G.tiles(pt_off, n_clouds, src, n, named, &S.soff);
+  GicpIndex G(R.host_up);
+  G.tiles(pt_off, n_clouds, src, n, named, &R.host_soff);
   if (n == 0) return SGTD_OK;      // (a run without a pair: no cloud is named, nothing comes back)
-  const int total_src = S.soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
+  const int total_src = R.host_soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
   long long slice = (long long)reg_slice_tiles() * SGTD_REG_TILE;
   auto slices_of = [&](long long len) { return (size_t)std::max<long long>((max_tgt + len - 1) / len, 1); };
   while ((size_t)total_src * slices_of(slice) > kRegPartMax) slice *= 2;
@@ -5252,9 +5260,9 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
   // the index upload: src, tgt, src_off, the tiles (clouds by the index the kernels know them by)
   G.u_src = G.put(src, (size_t)n);
   const size_t u_tgt = G.put(tgt, (size_t)n);
-  G.u_soff = G.put(S.soff.data(), (size_t)n + 1);
+  G.u_soff = G.put(R.host_soff.data(), (size_t)n + 1);
   if (S.first) {
-    for (int k = 0; k < n; k++) S.up[G.u_src + (size_t)k] += S.first;
+    for (int k = 0; k < n; k++) R.host_up[G.u_src + (size_t)k] += S.first;
     for (int &cl : G.ctile_cloud) cl += S.first;
   }
   G.put_tiles();
@@ -5262,14 +5270,14 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
                in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1);
   const RegOut out((size_t)n, false);
-  CHK(ensure(c, S.in, in_bytes));
-  if (S.cov_buf) CHK(ensure(c, *S.cov_buf, std::max<size_t>(total, 1) * 9 * sizeof(double)));
-  CHK(ensure(c, S.part, ts * n_slices * (sizeof(double) + sizeof(int))));
-  CHK(ensure(c, S.match, ts * (10 * sizeof(double) + sizeof(int))));
-  CHK(ensure(c, S.state, (size_t)n * sizeof(RegState)));
-  CHK(ensure(c, S.out, out.bytes()));
-  CHK(ensure(c, S.ctl, 64));
-  char *in = S.in.as<char>();
+  CHK(ensure(c, R.in, in_bytes));
+  if (!S.cov) CHK(ensure(c, R.cov, std::max<size_t>(total, 1) * 9 * sizeof(double)));
+  CHK(ensure(c, R.part, ts * n_slices * (sizeof(double) + sizeof(int))));
+  CHK(ensure(c, R.match, ts * (10 * sizeof(double) + sizeof(int))));
+  CHK(ensure(c, R.state, (size_t)n * sizeof(RegState)));
+  CHK(ensure(c, R.out, out.bytes()));
+  CHK(ensure(c, R.ctl, 64));
+  char *in = R.in.as<char>();
   if (!S.d_off) CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
   if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
   CHK(h2d(c, in + o_idx, G.up.data(), G.up.size() * sizeof(int)));
@@ -5277,13 +5285,13 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
 
   RegParams P;
   const int *di = reinterpret_cast<const int *>(in + o_idx);
-  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts, S.cov_buf ? S.cov_buf->as<double>() : S.cov,
-              S.state.p, S.ctl.p, out, S.out.p,
+  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts, S.cov ? S.cov : R.cov.as<double>(),
+              R.state.p, R.ctl.p, out, R.out.p,
               gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.max_corr_dist, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps,
                            o.plane_eps));
   P.tgt = di + u_tgt; P.slice = (int)slice;
-  P.part_d2 = S.part.as<double>(); P.part_j = reinterpret_cast<int *>(P.part_d2 + ts * n_slices);
-  P.md2 = S.match.as<double>(); P.M = P.md2 + ts; P.mj = reinterpret_cast<int *>(P.M + 9 * ts);
+  P.part_d2 = R.part.as<double>(); P.part_j = reinterpret_cast<int *>(P.part_d2 + ts * n_slices);
+  P.md2 = R.match.as<double>(); P.M = P.md2 + ts; P.mj = reinterpret_cast<int *>(P.M + 9 * ts);
 
   int unfinished = 0;
   for (int k = 0; k < n; k++)
@@ -5324,17 +5332,115 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
 // sgtd_register_clouds' run: every cloud is the call's, and a cloud some pair names needs covariances
 int reg_clouds_run(sgtd_engine *c, const sgtd_register_options &o, const float *points, int stride, const int64_t *pt_off, int n_clouds,
                    const int32_t *src, const int32_t *tgt, const double *init, int n) {
+  DenseRun &R = c->dense;
   // what the getters need
-  c->rg_host_off.assign(pt_off, pt_off + n_clouds + 1);
-  c->rg_host_named.assign((size_t)n_clouds, 0);
+  R.host_off.assign(pt_off, pt_off + n_clouds + 1);
+  R.host_named.assign((size_t)n_clouds, 0);
   std::vector<int64_t> tgt_n((size_t)n);
   for (int k = 0; k < n; k++) {
-    c->rg_host_named[(size_t)src[k]] = 1; c->rg_host_named[(size_t)tgt[k]] = 1;
+    R.host_named[(size_t)src[k]] = 1; R.host_named[(size_t)tgt[k]] = 1;
     tgt_n[(size_t)k] = pt_off[tgt[k] + 1] - pt_off[tgt[k]];
   }
-  const RegSite S{"sgtd_register_clouds", c->rg_in, c->rg_part, c->rg_match, c->rg_state, c->rg_out, c->rg_ctl, c->rg_host_up, c->rg_host_soff, c->rg_clock,
-                  points, stride, &c->rg_cov, nullptr, nullptr, 0, nullptr};
-  return reg_run(c, S, o, pt_off, n_clouds, c->rg_host_named.data(), src, tgt, tgt_n.data(), init, n);
+  const RegSite S{"sgtd_register_clouds", R, points, stride, nullptr, nullptr, 0, nullptr};
+  return reg_run(c, S, o, pt_off, n_clouds, R.host_named.data(), src, tgt, tgt_n.data(), init, n);
+}
+
+// the options of a dense call: the defaults or the caller's, checked
+int dense_options(const sgtd_register_options *opt, sgtd_register_options *o) {
+  sgtd_default_register_options(o);
+  if (opt) *o = *opt;
+  if (!gicp_options_ok(o->k_neighbors, o->max_iterations, o->lm_max_trials, o->reserved, o->lm_init_lambda_factor, o->rotation_eps, o->translation_eps,
+                       o->plane_eps) ||
+      !(o->max_corr_dist > 0.0))
+    return SGTD_ERR_INVALID;
+  return SGTD_OK;
+}
+
+// What both dense calls check of their arguments before the device is touched, in sgtd_register_clouds' order.
+// target_ok(k): whether pair k's target is one of the call's (sgtd_register_clouds: a cloud's index).  The frames of
+// sgtd_register_stored are looked up behind the caps and the store's settings, which come after this: that call checks
+// them itself.
+template <class TargetOk>
+int dense_check(sgtd_engine *e, const char *call, const sgtd_register_options *opt, sgtd_register_options *o, const float *points, int stride_floats,
+                const int64_t *pt_off, int n_clouds, const int32_t *src_cloud, const void *targets, const double *init_pose, int n_pairs,
+                TargetOk &&target_ok) {
+  if (!e || n_pairs < 0) return SGTD_ERR_INVALID;
+  if (n_pairs > 0 && (!src_cloud || !targets)) return SGTD_ERR_INVALID;
+  CHK(dense_options(opt, o));
+  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  int64_t total_src = 0;
+  for (int k = 0; k < n_pairs; k++) {
+    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || !target_ok(k)) return SGTD_ERR_INVALID;
+    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
+  }
+  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
+  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs) || total_src > SGTD_REG_MAX_SOURCE_POINTS) {
+    e->err = gicp_caps_text(call) + ", " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " + std::to_string(SGTD_REG_MAX_SOURCE_POINTS) +
+             " source points over the pairs";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  return SGTD_OK;
+}
+
+// The getters of a dense run, over the buffers and host arrays of the call that made it: `run` on e's home engine
+// (`missing`: what the handle is told where that call has not run)
+int dense_rows_out(sgtd_engine *e, DenseRun sgtd_engine::*run, const char *missing, double *pose, double *fitness, double *cost, int32_t *n_matched,
+                   int32_t *iterations, int32_t *status) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  const DenseRun &R = c->*run;
+  if (R.n == 0) return SGTD_OK;
+  return reg_rows_out(e, c, RegOut((size_t)R.n, false), R.out.p, pose, fitness, cost, n_matched, nullptr, iterations, status);
+}
+
+int dense_cov_out(sgtd_engine *e, DenseRun sgtd_engine::*run, const char *missing, int cloud, double *cov, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  const DenseRun &R = c->*run;
+  if (cloud < 0 || (size_t)cloud >= R.host_named.size()) return SGTD_ERR_INVALID;
+  const int64_t first = R.host_off[(size_t)cloud];
+  const int64_t need = R.host_named[(size_t)cloud] ? R.host_off[(size_t)cloud + 1] - first : 0;
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  CopyOut out(e, c);
+  out.get(cov, R.cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  CHK(out.finish());
+  return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int dense_matches_out(sgtd_engine *e, DenseRun sgtd_engine::*run, const char *missing, int pair, int32_t *tgt_index, double *d2, int64_t capacity,
+                      int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  const DenseRun &R = c->*run;
+  if (pair < 0 || pair >= R.n) return SGTD_ERR_INVALID;
+  const int *soff = R.host_soff.data();
+  const int64_t first = soff[pair], need = soff[pair + 1] - first;
+  const size_t ts = (size_t)std::max(soff[R.n], 1);
+  if (n) *n = need;
+  const size_t m = (size_t)std::min(need, capacity);
+  const double *md2 = R.match.as<double>();
+  const int *mj = reinterpret_cast<const int *>(md2 + 10 * ts);
+  CopyOut out(e, c);
+  out.get(tgt_index, mj + first, m * sizeof(int));
+  out.get(d2, md2 + first, m * sizeof(double));
+  CHK(out.finish());
+  return need > capacity && (tgt_index || d2) ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int dense_ms_out(sgtd_engine *e, DenseRun sgtd_engine::*run, const char *missing, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  const float *ms = (c->*run).clock.ms;
+  if (ms_cov) *ms_cov = ms[0];
+  if (ms_search) *ms_search = ms[1];
+  if (ms_rest) *ms_rest = ms[2];
+  if (ms_total) *ms_total = ms[3];
+  return SGTD_OK;
 }
 
 const char kNoRegistered[] = "no registered clouds: sgtd_register_clouds has not run";
@@ -5357,87 +5463,33 @@ void sgtd_register_tiles(int *src_tile, int *tgt_tile, int *slice) {
 
 int sgtd_register_clouds(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
                          const int32_t *src_cloud, const int32_t *tgt_cloud, const double *init_pose, int n_pairs, int device_ptrs) {
-  if (!e || n_pairs < 0) return SGTD_ERR_INVALID;
-  if (n_pairs > 0 && (!src_cloud || !tgt_cloud)) return SGTD_ERR_INVALID;
   sgtd_register_options o;
-  sgtd_default_register_options(&o);
-  if (opt) o = *opt;
-  if (!gicp_options_ok(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.reserved, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps, o.plane_eps) ||
-      !(o.max_corr_dist > 0.0))
-    return SGTD_ERR_INVALID;
-  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  CHK(dense_check(e, "sgtd_register_clouds", opt, &o, points, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs,
+                  [&](int k) { return tgt_cloud[k] >= 0 && tgt_cloud[k] < n_clouds; }));
   const int64_t total = pt_off[n_clouds];
-  int64_t total_src = 0;
-  for (int k = 0; k < n_pairs; k++) {
-    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds || tgt_cloud[k] < 0 || tgt_cloud[k] >= n_clouds) return SGTD_ERR_INVALID;
-    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
-  }
-  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
-  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs) || total_src > SGTD_REG_MAX_SOURCE_POINTS) {
-    e->err = gicp_caps_text("sgtd_register_clouds") + ", " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " + std::to_string(SGTD_REG_MAX_SOURCE_POINTS) +
-             " source points over the pairs";
-    return SGTD_ERR_UNSUPPORTED;
-  }
-  StageRun<int> run(e, &sgtd_engine::rg_n);
+  StageRun<int> run(e, &sgtd_engine::dense);
   run.on_device([&](sgtd_engine *c) -> int {
     const float *d_pts = nullptr;
-    CHK(points_on_device(c, c->rg_pts, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
+    CHK(points_on_device(c, c->dense.pts, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
     return reg_clouds_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
   });
   return run.end(n_pairs);
 }
 
 int sgtd_result_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *iterations, int32_t *status) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
-  if (c->rg_n == 0) return SGTD_OK;
-  return reg_rows_out(e, c, RegOut((size_t)c->rg_n, false), c->rg_out.p, pose, fitness, cost, n_matched, nullptr, iterations, status);
+  return dense_rows_out(e, &sgtd_engine::dense, kNoRegistered, pose, fitness, cost, n_matched, iterations, status);
 }
 
 int sgtd_result_register_covariances(sgtd_handle e, int cloud, double *cov, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
-  if (cloud < 0 || (size_t)cloud >= c->rg_host_named.size()) return SGTD_ERR_INVALID;
-  const int64_t first = c->rg_host_off[(size_t)cloud];
-  const int64_t need = c->rg_host_named[(size_t)cloud] ? c->rg_host_off[(size_t)cloud + 1] - first : 0;
-  if (n) *n = need;
-  const size_t m = (size_t)std::min(need, capacity);
-  CopyOut out(e, c);
-  out.get(cov, c->rg_cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
-  CHK(out.finish());
-  return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
+  return dense_cov_out(e, &sgtd_engine::dense, kNoRegistered, cloud, cov, capacity, n);
 }
 
 int sgtd_result_register_matches(sgtd_handle e, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
-  if (pair < 0 || pair >= c->rg_n) return SGTD_ERR_INVALID;
-  const int *soff = c->rg_host_soff.data();
-  const int64_t first = soff[pair], need = soff[pair + 1] - first;
-  const size_t ts = (size_t)std::max(soff[c->rg_n], 1);
-  if (n) *n = need;
-  const size_t m = (size_t)std::min(need, capacity);
-  const double *md2 = c->rg_match.as<double>();
-  const int *mj = reinterpret_cast<const int *>(md2 + 10 * ts);
-  CopyOut out(e, c);
-  out.get(tgt_index, mj + first, m * sizeof(int));
-  out.get(d2, md2 + first, m * sizeof(double));
-  CHK(out.finish());
-  return need > capacity && (tgt_index || d2) ? SGTD_ERR_CAPACITY : SGTD_OK;
+  return dense_matches_out(e, &sgtd_engine::dense, kNoRegistered, pair, tgt_index, d2, capacity, n);
 }
 
 int sgtd_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::rg_n, kNoRegistered, &c));
-  if (ms_cov) *ms_cov = c->rg_clock.ms[0];
-  if (ms_search) *ms_search = c->rg_clock.ms[1];
-  if (ms_rest) *ms_rest = c->rg_clock.ms[2];
-  if (ms_total) *ms_total = c->rg_clock.ms[3];
-  return SGTD_OK;
+  return dense_ms_out(e, &sgtd_engine::dense, kNoRegistered, ms_cov, ms_search, ms_rest, ms_total);
 }
 
 }  // extern "C"
@@ -5653,44 +5705,61 @@ int stored_run(sgtd_engine *c, const sgtd_register_options &o, const float *poin
                const int32_t *src, const int32_t *slot, const double *init, const double *d_init, int n) {
   sgtd_engine *e = c;
   CloudArena &A = c->st;
-  c->sr_host_off.assign(pt_off, pt_off + n_clouds + 1);
-  c->sr_host_named.assign((size_t)n_clouds, 0);
+  DenseRun &R = c->stored;
+  R.host_off.assign(pt_off, pt_off + n_clouds + 1);
+  R.host_named.assign((size_t)n_clouds, 0);
   std::vector<int64_t> tgt_n((size_t)n);
   for (int k = 0; k < n; k++) {
-    c->sr_host_named[(size_t)src[k]] = 1;
+    R.host_named[(size_t)src[k]] = 1;
     tgt_n[(size_t)k] = A.slots[(size_t)slot[k]].count;
   }
-  if (n == 0) { c->sr_host_soff.assign(1, 0); return SGTD_OK; }
+  if (n == 0) { R.host_soff.assign(1, 0); return SGTD_OK; }
   const int64_t total = pt_off[n_clouds];
   const float *d_src = nullptr;
-  CHK(points_on_device(c, c->sr_pts, points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(points_on_device(c, R.pts, points, (size_t)total * stride, device_ptrs, &d_src));
   CHK(store_pack(c, A, d_src, stride, total, A.used));
   std::vector<long long> rows;
   CHK(store_tail_rows(c, A, pt_off, n_clouds, rows));
-  const RegSite S{"sgtd_register_stored", c->sr_in, c->sr_part, c->sr_match, c->sr_state, c->sr_out, c->sr_ctl, c->sr_host_up, c->sr_host_soff, c->sr_clock,
-                  A.pts.as<float>(), 3, nullptr, A.cov.as<double>(), A.off.as<long long>(), (int)A.slots.size(), d_init};
-  CHK(reg_run(c, S, o, pt_off, n_clouds, c->sr_host_named.data(), src, slot, tgt_n.data(), init, n));
-  CHK(ensure(c, c->sr_cov, std::max<size_t>((size_t)total, 1) * 9 * sizeof(double)));
-  if (total) HIPCHK(hipMemcpyAsync(c->sr_cov.p, A.cov.as<double>() + (size_t)A.used * 9, (size_t)total * 9 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  const RegSite S{"sgtd_register_stored", R, A.pts.as<float>(), 3, A.cov.as<double>(), A.off.as<long long>(), (int)A.slots.size(), d_init};
+  CHK(reg_run(c, S, o, pt_off, n_clouds, R.host_named.data(), src, slot, tgt_n.data(), init, n));
+  CHK(ensure(c, R.cov, std::max<size_t>((size_t)total, 1) * 9 * sizeof(double)));
+  if (total) HIPCHK(hipMemcpyAsync(R.cov.p, A.cov.as<double>() + (size_t)A.used * 9, (size_t)total * 9 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   CHK(xfer_sync(c));
   return SGTD_OK;
 }
 
-// what both stored calls check of their options and of the store's settings
-int stored_options(const sgtd_register_options *opt, sgtd_register_options *o) {
-  sgtd_default_register_options(o);
-  if (opt) *o = *opt;
-  if (!gicp_options_ok(o->k_neighbors, o->max_iterations, o->lm_max_trials, o->reserved, o->lm_init_lambda_factor, o->rotation_eps, o->translation_eps,
-                       o->plane_eps) ||
-      !(o->max_corr_dist > 0.0))
-    return SGTD_ERR_INVALID;
-  return SGTD_OK;
-}
+// what the stored calls check of the store's settings
 int stored_settings(sgtd_engine *e, const char *call, int k_neighbors, double plane_eps) {
   const sgtd_engine *c = home_engine(e);
   if (c->st_k == 0 || (k_neighbors == c->st_k && plane_eps == c->st_eps)) return SGTD_OK;
   e->err = std::string(call) + ": k_neighbors and plane_eps must be the cloud store's (" + std::to_string(c->st_k) + ", " + std::to_string(c->st_eps) + ")";
   return SGTD_ERR_STATE;
+}
+
+// What both loops calls (sgtd_register_stored_loops, sgtd_register_stored_local_loops) check of the batch and of the
+// queries' clouds, behind their options (k_neighbors, plane_eps: the checked options'), and the batch waited for.
+// instead: what the refusal of a multi-device handle advises.
+int loops_begin(sgtd_engine *e, const char *call, const char *instead, const float *points, int stride_floats, const int64_t *pt_off, int max_per_query,
+                int start, int k_neighbors, double plane_eps) {
+  if (max_per_query < 0 || start < SGTD_START_VERIFY || start > SGTD_START_ALIGNED) return SGTD_ERR_INVALID;
+  if (!pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
+  if (e->grp) {
+    e->err = std::string(call) + ": a multi-device handle's batch results live on several engines: " + instead;
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  if (!e->batch_valid || !e->verified) return needs(e, call, "sgtd_verify");
+  if (start == SGTD_START_REFINED && !e->refined) return needs(e, call, "sgtd_refine_poses");
+  if (start == SGTD_START_ALIGNED && !e->aligned) return needs(e, call, "sgtd_align_keypoints");
+  if (!cloud_set_ok(pt_off, e->nq, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  if (!gicp_caps_ok(pt_off, e->nq, 0)) { e->err = gicp_caps_text(call); return SGTD_ERR_UNSUPPORTED; }
+  CHK(stored_settings(e, call, k_neighbors, plane_eps));
+  HIPCHK(hipSetDevice(e->cfg.device_id));
+  return sync_batch(e);
+}
+
+// the batch's poses a loops call starts from
+const double *start_pose(sgtd_engine *c, int start) {
+  return start == SGTD_START_REFINED ? c->r_pose.as<double>() : start == SGTD_START_ALIGNED ? c->a_pose.as<double>() : c->v_pose.as<double>();
 }
 }  // namespace
 
@@ -5778,23 +5847,10 @@ int sgtd_result_frame_cloud(sgtd_handle e, uint32_t frame, float *xyz, double *c
 
 int sgtd_register_stored(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
                          const int32_t *src_cloud, const uint32_t *tgt_frame, const double *init_pose, int n_pairs, int device_ptrs) {
-  if (!e || n_pairs < 0) return SGTD_ERR_INVALID;
-  if (n_pairs > 0 && (!src_cloud || !tgt_frame)) return SGTD_ERR_INVALID;
   sgtd_register_options o;
-  CHK(stored_options(opt, &o));
-  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  CHK(dense_check(e, "sgtd_register_stored", opt, &o, points, stride_floats, pt_off, n_clouds, src_cloud, tgt_frame, init_pose, n_pairs,
+                  [](int) { return true; }));
   const int64_t total = pt_off[n_clouds];
-  int64_t total_src = 0;
-  for (int k = 0; k < n_pairs; k++) {
-    if (src_cloud[k] < 0 || src_cloud[k] >= n_clouds) return SGTD_ERR_INVALID;
-    total_src += pt_off[src_cloud[k] + 1] - pt_off[src_cloud[k]];
-  }
-  if (init_pose && !relax_finite(init_pose, (size_t)n_pairs * 12)) return SGTD_ERR_INVALID;
-  if (!gicp_caps_ok(pt_off, n_clouds, n_pairs) || total_src > SGTD_REG_MAX_SOURCE_POINTS) {
-    e->err = gicp_caps_text("sgtd_register_stored") + ", " + std::to_string(SGTD_REG_MAX_PAIRS) + " pairs and " + std::to_string(SGTD_REG_MAX_SOURCE_POINTS) +
-             " source points over the pairs";
-    return SGTD_ERR_UNSUPPORTED;
-  }
   CHK(stored_settings(e, "sgtd_register_stored", o.k_neighbors, o.plane_eps));
   {
     const sgtd_engine *c = home_engine(e);
@@ -5804,7 +5860,7 @@ int sgtd_register_stored(sgtd_handle e, const sgtd_register_options *opt, const 
         return SGTD_ERR_INVALID;
       }
   }
-  StageRun<int> run(e, &sgtd_engine::sr_n);
+  StageRun<int> run(e, &sgtd_engine::stored);
   run.c->sr_loops = false;
   run.on_device([&](sgtd_engine *c) -> int {
     if (n_pairs > 0) CHK(store_room(c, total, n_clouds));
@@ -5817,27 +5873,16 @@ int sgtd_register_stored(sgtd_handle e, const sgtd_register_options *opt, const 
 
 int sgtd_register_stored_loops(sgtd_handle e, const sgtd_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off,
                                int max_per_query, int start, int device_ptrs) {
-  if (!e || max_per_query < 0 || start < SGTD_START_VERIFY || start > SGTD_START_ALIGNED) return SGTD_ERR_INVALID;
+  if (!e) return SGTD_ERR_INVALID;
   sgtd_register_options o;
-  CHK(stored_options(opt, &o));
-  if (!pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
-  if (e->grp) {
-    e->err = "sgtd_register_stored_loops: a multi-device handle's batch results live on several engines: form the pairs and use sgtd_register_stored";
-    return SGTD_ERR_UNSUPPORTED;
-  }
-  if (!e->batch_valid || !e->verified) return needs(e, "sgtd_register_stored_loops", "sgtd_verify");
-  if (start == SGTD_START_REFINED && !e->refined) return needs(e, "sgtd_register_stored_loops", "sgtd_refine_poses");
-  if (start == SGTD_START_ALIGNED && !e->aligned) return needs(e, "sgtd_register_stored_loops", "sgtd_align_keypoints");
+  CHK(dense_options(opt, &o));
+  CHK(loops_begin(e, "sgtd_register_stored_loops", "form the pairs and use sgtd_register_stored", points, stride_floats, pt_off, max_per_query, start,
+                  o.k_neighbors, o.plane_eps));
   const int nq = e->nq, cn = e->dc.cand_num, mpq = std::min(max_per_query, cn);
-  if (!cloud_set_ok(pt_off, nq, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
-  if (!gicp_caps_ok(pt_off, nq, 0)) { e->err = gicp_caps_text("sgtd_register_stored_loops"); return SGTD_ERR_UNSUPPORTED; }
-  CHK(stored_settings(e, "sgtd_register_stored_loops", o.k_neighbors, o.plane_eps));
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(sync_batch(e));
   const int64_t total = pt_off[nq];
   const size_t upper = (size_t)nq * mpq;
   int n = 0;
-  StageRun<int> run(e, &sgtd_engine::sr_n);
+  StageRun<int> run(e, &sgtd_engine::stored);
   e->sr_loops = true;
   e->sr_rows.clear();
   run.on_device([&](sgtd_engine *c) -> int {
@@ -5853,7 +5898,7 @@ int sgtd_register_stored_loops(sgtd_handle e, const sgtd_register_options *opt, 
       c->sr_init_off = o_init;
       StorePairParams P;
       P.score = c->v_score.as<double>(); P.n_cand = c->n_cand.as<int>(); P.cand_frame = c->cand_frame.as<int>();
-      P.pose = start == SGTD_START_REFINED ? c->r_pose.as<double>() : start == SGTD_START_ALIGNED ? c->a_pose.as<double>() : c->v_pose.as<double>();
+      P.pose = start_pose(c, start);
       P.slot_of = c->st_table.as<int>(); P.n_ids = (u32)c->st_slot_of.size();
       P.cand_num = cn; P.nq = nq; P.max_per_query = mpq;
       P.count = reinterpret_cast<u32 *>(pb + o_count); P.first = reinterpret_cast<const u32 *>(pb + o_first);
@@ -5893,9 +5938,9 @@ int sgtd_register_stored_loops(sgtd_handle e, const sgtd_register_options *opt, 
 int sgtd_result_stored_pairs(sgtd_handle e, int32_t *query, int32_t *cand, int32_t *frame, double *init, int64_t capacity, int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
+  CHK(stage_ready(e, &sgtd_engine::stored, kNoStored, &c));
   if (!c->sr_loops) { e->err = "no pair rows: sgtd_register_stored_loops has not run"; return SGTD_ERR_STATE; }
-  const int64_t need = c->sr_n;
+  const int64_t need = c->stored.n;
   if (n) *n = need;
   const size_t m = (size_t)std::min(need, capacity);
   for (size_t k = 0; k < m; k++) {
@@ -5912,56 +5957,19 @@ int sgtd_result_stored_pairs(sgtd_handle e, int32_t *query, int32_t *cand, int32
 }
 
 int sgtd_result_stored_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *iterations, int32_t *status) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
-  if (c->sr_n == 0) return SGTD_OK;
-  return reg_rows_out(e, c, RegOut((size_t)c->sr_n, false), c->sr_out.p, pose, fitness, cost, n_matched, nullptr, iterations, status);
+  return dense_rows_out(e, &sgtd_engine::stored, kNoStored, pose, fitness, cost, n_matched, iterations, status);
 }
 
 int sgtd_result_stored_covariances(sgtd_handle e, int cloud, double *cov, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
-  if (cloud < 0 || (size_t)cloud >= c->sr_host_named.size()) return SGTD_ERR_INVALID;
-  const int64_t first = c->sr_host_off[(size_t)cloud];
-  const int64_t need = c->sr_host_named[(size_t)cloud] ? c->sr_host_off[(size_t)cloud + 1] - first : 0;
-  if (n) *n = need;
-  const size_t m = (size_t)std::min(need, capacity);
-  CopyOut out(e, c);
-  out.get(cov, c->sr_cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
-  CHK(out.finish());
-  return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
+  return dense_cov_out(e, &sgtd_engine::stored, kNoStored, cloud, cov, capacity, n);
 }
 
 int sgtd_result_stored_matches(sgtd_handle e, int pair, int32_t *tgt_index, double *d2, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
-  if (pair < 0 || pair >= c->sr_n) return SGTD_ERR_INVALID;
-  const int *soff = c->sr_host_soff.data();
-  const int64_t first = soff[pair], need = soff[pair + 1] - first;
-  const size_t ts = (size_t)std::max(soff[c->sr_n], 1);
-  if (n) *n = need;
-  const size_t m = (size_t)std::min(need, capacity);
-  const double *md2 = c->sr_match.as<double>();
-  const int *mj = reinterpret_cast<const int *>(md2 + 10 * ts);
-  CopyOut out(e, c);
-  out.get(tgt_index, mj + first, m * sizeof(int));
-  out.get(d2, md2 + first, m * sizeof(double));
-  CHK(out.finish());
-  return need > capacity && (tgt_index || d2) ? SGTD_ERR_CAPACITY : SGTD_OK;
+  return dense_matches_out(e, &sgtd_engine::stored, kNoStored, pair, tgt_index, d2, capacity, n);
 }
 
 int sgtd_stored_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_search, float *ms_rest, float *ms_total) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sr_n, kNoStored, &c));
-  if (ms_cov) *ms_cov = c->sr_clock.ms[0];
-  if (ms_search) *ms_search = c->sr_clock.ms[1];
-  if (ms_rest) *ms_rest = c->sr_clock.ms[2];
-  if (ms_total) *ms_total = c->sr_clock.ms[3];
-  return SGTD_OK;
+  return dense_ms_out(e, &sgtd_engine::stored, kNoStored, ms_cov, ms_search, ms_rest, ms_total);
 }
 
 }  // extern "C"
@@ -5974,11 +5982,7 @@ static_assert(SGTD_VREG_W == SGTD_VREG_SUM_W, "the voxel kernels' sizes are the 
 // sgtd_register_stored_voxels' over the cloud store's arena, whose stored clouds come before the call's.
 struct VregSite {
   const char *call;
-  DevBuf *B;                        // the run's buffers (VR_*)
-  int &mode;
-  std::vector<int> &soff, &up;      // src_off [n + 1]; the source of the index upload
-  std::vector<u32> &map_vox;        // [n_maps + 1], read back for the getters
-  LapClock &clock;
+  VoxelRun &R;         // the run's buffers, mode, host arrays and clock
   const float *pts;                 // the points of every cloud the kernels may name, on the device
   int stride;
   double *cov;                      // the covariances of those clouds; NULL: VR_COV, grown to the call's points
@@ -6000,11 +6004,12 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
              const int32_t *tgt, const double *init, int n) {
   sgtd_engine *e = c;      // (HIPCHK reports on the engine that runs the pass)
   const bool timed = c->timing;
-  LapClock &clock = S.clock;
+  VoxelRun &R = S.R;
+  LapClock &clock = R.clock;
   CHK(clock.start(c, timed));
   const size_t total = (size_t)pt_off[n_clouds];
   const int mode = o.neighbor_mode, n_members = n_maps ? map_off[n_maps] : 0;
-  S.mode = mode;
+  R.mode = mode;
   // the members' points back to back, the tiles: of the pairs' sources, of the clouds that need covariances
   const bool on_device = S.d_mem_cloud != nullptr;
   std::vector<int> mem_map, mem_pt_off;
@@ -6018,8 +6023,8 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
       }
   }
   const long long MP = on_device ? S.d_member_pts : mem_pt_off[(size_t)n_members];
-  std::vector<int> &soff = S.soff;
-  GicpIndex G(S.up);
+  std::vector<int> &soff = R.host_soff;
+  GicpIndex G(R.host_up);
   G.tiles(pt_off, n_clouds, src, n, named, &soff);
   const int total_src = soff[(size_t)n], n_tiles = (int)G.tile_pair.size();
 
@@ -6031,7 +6036,7 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
   const size_t u_moff = n_maps ? G.put(map_off, (size_t)n_maps + 1) : G.up.size(), u_mcl = G.put(mem_cloud, on_device ? 0 : (size_t)n_members);
   const size_t u_mmap = G.put(mem_map.data(), mem_map.size()), u_mpo = G.put(mem_pt_off.data(), mem_pt_off.size());
   if (S.first) {
-    for (int k = 0; k < n; k++) S.up[G.u_src + (size_t)k] += S.first;
+    for (int k = 0; k < n; k++) R.host_up[G.u_src + (size_t)k] += S.first;
     for (int &cl : G.ctile_cloud) cl += S.first;
   }
   G.put_tiles();
@@ -6039,7 +6044,7 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
                o_idx = o_pose + relax_up((size_t)n_members * 12 * sizeof(double)), in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1), mp = (size_t)std::max<long long>(MP, 1), nn = (size_t)std::max(n, 1);
   const RegOut out((size_t)n, true);
-  auto *B = S.B;
+  DevBuf *B = R.B;
   auto buf = [&](int which, size_t bytes) { return ensure(c, B[which], std::max<size_t>(bytes, 16)); };
   CHK(buf(sgtd_engine::VR_IN, in_bytes));
   if (!S.cov) CHK(buf(sgtd_engine::VR_COV, std::max<size_t>(total, 1) * 9 * sizeof(double)));
@@ -6114,8 +6119,8 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
   }
   vreg_ranges_kernel<<<grid_for(n_maps + 1, 256), 256, 0, s>>>(V);
   HIPCHK(hipGetLastError());
-  S.map_vox.assign((size_t)n_maps + 1, 0);
-  CHK(d2h(c, S.map_vox.data(), V.map_vox, ((size_t)n_maps + 1) * sizeof(u32)));
+  R.host_map_vox.assign((size_t)n_maps + 1, 0);
+  CHK(d2h(c, R.host_map_vox.data(), V.map_vox, ((size_t)n_maps + 1) * sizeof(u32)));
   CHK(xfer_sync(c));
   if (timed) CHK(clock.lap(c, 1));
   if (n == 0) {
@@ -6123,7 +6128,7 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
     return SGTD_OK;
   }
 
-  const std::vector<u32> &mv = S.map_vox;
+  const std::vector<u32> &mv = R.host_map_vox;
   int unfinished = 0;
   for (int k = 0; k < n; k++)
     if (soff[(size_t)k + 1] > soff[(size_t)k] && mv[(size_t)tgt[k] + 1] > mv[(size_t)tgt[k]]) unfinished++;
@@ -6166,8 +6171,7 @@ int vreg_clouds_run(sgtd_engine *c, const sgtd_voxel_register_options &o, const 
     mem_n[(size_t)j] = pt_off[map_cloud[j] + 1] - pt_off[map_cloud[j]];
   }
   for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
-  const VregSite S{"sgtd_register_voxels", c->vr, c->vr_mode, c->vr_host_soff, c->vr_host_up, c->vr_host_map_vox, c->vr_clock,
-                   points, stride, nullptr, nullptr, 0};
+  const VregSite S{"sgtd_register_voxels", c->vox, points, stride, nullptr, nullptr, 0};
   return vreg_run(c, S, o, pt_off, n_clouds, named.data(), map_off, map_cloud, mem_n.data(), map_pose, n_maps, src, tgt, init, n);
 }
 
@@ -6230,9 +6234,25 @@ int vreg_check(sgtd_engine *e, const char *call, const sgtd_voxel_register_optio
   return SGTD_OK;
 }
 
-// The getters of a voxel run, over the buffers and host arrays of the call that made it (c: its home engine)
-int vreg_map_out(sgtd_engine *e, sgtd_engine *c, DevBuf *B, const std::vector<u32> &map_vox, int map, int32_t *coord, int32_t *n_points, double *mean,
-                 double *cov, int64_t capacity, int64_t *n) {
+// The getters of a voxel run, over the buffers and host arrays of the call that made it: `run` on e's home engine
+// (`missing`: what the handle is told where that call has not run)
+int vreg_rows_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing, double *pose, double *fitness, double *cost, int32_t *n_matched,
+                  int32_t *n_corr, int32_t *iterations, int32_t *status) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  VoxelRun &R = c->*run;
+  if (R.n == 0) return SGTD_OK;
+  return reg_rows_out(e, c, RegOut((size_t)R.n, true), R.B[sgtd_engine::VR_OUT].p, pose, fitness, cost, n_matched, n_corr, iterations, status);
+}
+
+int vreg_map_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov,
+                 int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  const std::vector<u32> &map_vox = (c->*run).host_map_vox;
+  DevBuf *B = (c->*run).B;
   if (map < 0 || (size_t)map + 1 >= map_vox.size()) return SGTD_ERR_INVALID;
   const int64_t first = map_vox[(size_t)map], need = (int64_t)map_vox[(size_t)map + 1] - first;
   if (n) *n = need;
@@ -6252,24 +6272,33 @@ int vreg_map_out(sgtd_engine *e, sgtd_engine *c, DevBuf *B, const std::vector<u3
   return need > capacity && any ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
-int vreg_matches_out(sgtd_engine *e, sgtd_engine *c, DevBuf *B, const std::vector<int> &soff, int mode, int n_pairs, int pair, int32_t *voxel,
-                     int64_t capacity, int64_t *n) {
-  if (pair < 0 || pair >= n_pairs) return SGTD_ERR_INVALID;
-  const int64_t first = (int64_t)soff[(size_t)pair] * mode;
-  const int64_t need = (int64_t)soff[(size_t)pair + 1] * mode - first;
+int vreg_matches_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  VoxelRun &R = c->*run;
+  if (pair < 0 || pair >= R.n) return SGTD_ERR_INVALID;
+  const int64_t first = (int64_t)R.host_soff[(size_t)pair] * R.mode;
+  const int64_t need = (int64_t)R.host_soff[(size_t)pair + 1] * R.mode - first;
   if (n) *n = need;
   CopyOut out(e, c);
-  out.get(voxel, B[sgtd_engine::VR_VID].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
+  out.get(voxel, R.B[sgtd_engine::VR_VID].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
   CHK(out.finish());
   return need > capacity && voxel ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
-void vreg_ms_out(const LapClock &clock, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
-  if (ms_cov) *ms_cov = clock.ms[0];
-  if (ms_map) *ms_map = clock.ms[1];
-  if (ms_corr) *ms_corr = clock.ms[2];
-  if (ms_rest) *ms_rest = clock.ms[3];
-  if (ms_total) *ms_total = clock.ms[4];
+int vreg_ms_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest,
+                float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, run, missing, &c));
+  const float *ms = (c->*run).clock.ms;
+  if (ms_cov) *ms_cov = ms[0];
+  if (ms_map) *ms_map = ms[1];
+  if (ms_corr) *ms_corr = ms[2];
+  if (ms_rest) *ms_rest = ms[3];
+  if (ms_total) *ms_total = ms[4];
+  return SGTD_OK;
 }
 
 const char kNoVoxelRegistered[] = "no voxel registration: sgtd_register_voxels has not run";
@@ -6296,10 +6325,10 @@ int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, 
                    return SGTD_OK;
                  }));
   const int64_t total = pt_off[n_clouds];
-  StageRun<int> run(e, &sgtd_engine::vr_n);
+  StageRun<int> run(e, &sgtd_engine::vox);
   run.on_device([&](sgtd_engine *c) -> int {
     const float *d_pts = nullptr;
-    CHK(points_on_device(c, c->vr[sgtd_engine::VR_PTS], points, (size_t)total * stride_floats, device_ptrs, &d_pts));
+    CHK(points_on_device(c, c->vox.B[sgtd_engine::VR_PTS], points, (size_t)total * stride_floats, device_ptrs, &d_pts));
     return vreg_clouds_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
   });
   return run.end(n_pairs);
@@ -6307,33 +6336,19 @@ int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, 
 
 int sgtd_result_voxel_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *n_corr, int32_t *iterations,
                                  int32_t *status) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  if (c->vr_n == 0) return SGTD_OK;
-  return reg_rows_out(e, c, RegOut((size_t)c->vr_n, true), c->vr[sgtd_engine::VR_OUT].p, pose, fitness, cost, n_matched, n_corr, iterations, status);
+  return vreg_rows_out(e, &sgtd_engine::vox, kNoVoxelRegistered, pose, fitness, cost, n_matched, n_corr, iterations, status);
 }
 
 int sgtd_result_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  return vreg_map_out(e, c, c->vr, c->vr_host_map_vox, map, coord, n_points, mean, cov, capacity, n);
+  return vreg_map_out(e, &sgtd_engine::vox, kNoVoxelRegistered, map, coord, n_points, mean, cov, capacity, n);
 }
 
 int sgtd_result_voxel_matches(sgtd_handle e, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  return vreg_matches_out(e, c, c->vr, c->vr_host_soff, c->vr_mode, c->vr_n, pair, voxel, capacity, n);
+  return vreg_matches_out(e, &sgtd_engine::vox, kNoVoxelRegistered, pair, voxel, capacity, n);
 }
 
 int sgtd_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::vr_n, kNoVoxelRegistered, &c));
-  vreg_ms_out(c->vr_clock, ms_cov, ms_map, ms_corr, ms_rest, ms_total);
-  return SGTD_OK;
+  return vreg_ms_out(e, &sgtd_engine::vox, kNoVoxelRegistered, ms_cov, ms_map, ms_corr, ms_rest, ms_total);
 }
 
 }  // extern "C"
@@ -6357,7 +6372,6 @@ int stored_voxels_run(sgtd_engine *c, const sgtd_voxel_register_options &o, cons
                       int device_ptrs, const int32_t *map_off, const int32_t *slot, const double *map_pose, int n_maps, const int32_t *src,
                       const int32_t *tgt, const double *init, int n, const StoredMembers *formed = nullptr) {
   CloudArena &A = c->st;
-  auto *B = c->sv;
   const int n_members = n_maps ? map_off[n_maps] : 0;
   std::vector<unsigned char> named((size_t)n_clouds, 0);
   std::vector<int64_t> mem_n(formed ? 0 : (size_t)n_members);
@@ -6365,12 +6379,12 @@ int stored_voxels_run(sgtd_engine *c, const sgtd_voxel_register_options &o, cons
   for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
   const int64_t total = pt_off[n_clouds];
   const float *d_src = nullptr;
-  CHK(points_on_device(c, B[sgtd_engine::VR_PTS], points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(points_on_device(c, c->svox.B[sgtd_engine::VR_PTS], points, (size_t)total * stride, device_ptrs, &d_src));
   CHK(store_pack(c, A, d_src, stride, total, A.used));
   std::vector<long long> rows;
   CHK(store_tail_rows(c, A, pt_off, n_clouds, rows));
-  VregSite S{formed ? "sgtd_register_stored_local_loops" : "sgtd_register_stored_voxels", B, c->sv_mode, c->sv_host_soff, c->sv_host_up,
-             c->sv_host_map_vox, c->sv_clock, A.pts.as<float>(), 3, A.cov.as<double>(), A.off.as<long long>(), (int)A.slots.size()};
+  VregSite S{formed ? "sgtd_register_stored_local_loops" : "sgtd_register_stored_voxels", c->svox, A.pts.as<float>(), 3, A.cov.as<double>(),
+             A.off.as<long long>(), (int)A.slots.size()};
   if (formed) {
     S.d_mem_cloud = formed->slot; S.d_mem_map = formed->map; S.d_mem_pt_off = formed->pt_off; S.d_map_pose = formed->pose;
     S.d_member_pts = formed->pts; S.d_init = formed->init;
@@ -6398,7 +6412,7 @@ int sgtd_register_stored_voxels(sgtd_handle e, const sgtd_voxel_register_options
   CHK(stored_settings(e, "sgtd_register_stored_voxels", o.k_neighbors, o.plane_eps));
   const int64_t total = pt_off[n_clouds];
   const int n_members = n_maps ? map_off[n_maps] : 0;
-  StageRun<int> run(e, &sgtd_engine::sv_n);
+  StageRun<int> run(e, &sgtd_engine::svox);
   run.c->sv_local = false;
   run.on_device([&](sgtd_engine *c) -> int {
     CHK(store_room(c, total, n_clouds));      // (a rebuild renumbers the slots: the members are looked up behind it)
@@ -6412,29 +6426,17 @@ int sgtd_register_stored_voxels(sgtd_handle e, const sgtd_voxel_register_options
 
 int sgtd_register_stored_local_loops(sgtd_handle e, const sgtd_voxel_register_options *opt, const float *points, int stride_floats, const int64_t *pt_off,
                                      int max_per_query, int start, double radius, int max_members, int device_ptrs) {
-  if (!e || max_per_query < 0 || start < SGTD_START_VERIFY || start > SGTD_START_ALIGNED) return SGTD_ERR_INVALID;
-  if (!(std::isfinite(radius) && radius >= 0.0) || max_members < 0) return SGTD_ERR_INVALID;
+  if (!e || !(std::isfinite(radius) && radius >= 0.0) || max_members < 0) return SGTD_ERR_INVALID;
   sgtd_voxel_register_options o;
   CHK(vreg_options(opt, &o));
-  if (!pt_off || (stride_floats != 3 && stride_floats != 4)) return SGTD_ERR_INVALID;
   const char *call = "sgtd_register_stored_local_loops";
-  if (e->grp) {
-    e->err = std::string(call) + ": a multi-device handle's batch results live on several engines: form the maps and use sgtd_register_stored_voxels";
-    return SGTD_ERR_UNSUPPORTED;
-  }
-  if (!e->batch_valid || !e->verified) return needs(e, call, "sgtd_verify");
-  if (start == SGTD_START_REFINED && !e->refined) return needs(e, call, "sgtd_refine_poses");
-  if (start == SGTD_START_ALIGNED && !e->aligned) return needs(e, call, "sgtd_align_keypoints");
+  CHK(loops_begin(e, call, "form the maps and use sgtd_register_stored_voxels", points, stride_floats, pt_off, max_per_query, start, o.k_neighbors,
+                  o.plane_eps));
   const int nq = e->nq, cn = e->dc.cand_num, mpq = std::min(max_per_query, cn);
-  if (!cloud_set_ok(pt_off, nq, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
-  if (!gicp_caps_ok(pt_off, nq, 0)) { e->err = gicp_caps_text(call); return SGTD_ERR_UNSUPPORTED; }
-  CHK(stored_settings(e, call, o.k_neighbors, o.plane_eps));
-  HIPCHK(hipSetDevice(e->cfg.device_id));
-  CHK(sync_batch(e));
   const int64_t total = pt_off[nq];
   const size_t upper = (size_t)nq * mpq;
   int n = 0;
-  StageRun<int> run(e, &sgtd_engine::sv_n);
+  StageRun<int> run(e, &sgtd_engine::svox);
   e->sv_local = true;
   e->sv_rows.clear(); e->sv_map_frame.clear(); e->sv_mem_off.assign(1, 0);
   run.on_device([&](sgtd_engine *c) -> int {
@@ -6459,7 +6461,7 @@ int sgtd_register_stored_local_loops(sgtd_handle e, const sgtd_voxel_register_op
     StoredLocalParams P;
     std::memset(&P, 0, sizeof(P));
     P.score = c->v_score.as<double>(); P.n_cand = c->n_cand.as<int>(); P.cand_frame = c->cand_frame.as<int>();
-    P.pose = start == SGTD_START_REFINED ? c->r_pose.as<double>() : start == SGTD_START_ALIGNED ? c->a_pose.as<double>() : c->v_pose.as<double>();
+    P.pose = start_pose(c, start);
     P.cand_num = cn; P.nq = nq; P.max_per_query = mpq;
     P.slot_of = c->st_table.as<int>(); P.pose_store = c->ck_store.as<float>(); P.has_pose = c->ck_has.as<unsigned char>();
     P.arena_off = c->st.off.as<long long>(); P.n_ids = (u32)n_ids;
@@ -6547,9 +6549,9 @@ int sgtd_result_stored_local_pairs(sgtd_handle e, int32_t *query, int32_t *cand,
                                    int64_t *n) {
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  CHK(stage_ready(e, &sgtd_engine::svox, kNoStoredVoxel, &c));
   if (!c->sv_local) { e->err = "no rows: sgtd_register_stored_local_loops has not run"; return SGTD_ERR_STATE; }
-  const int64_t need = c->sv_n;
+  const int64_t need = c->svox.n;
   if (n) *n = need;
   const size_t m = (size_t)std::min(need, capacity);
   for (size_t k = 0; k < m; k++) {
@@ -6570,7 +6572,7 @@ int sgtd_result_stored_local_maps(sgtd_handle e, uint32_t *map_frame, int64_t *m
                                   int64_t cap_members, int64_t *n_maps, int64_t *n_members) {
   if (!e || cap_maps < 0 || cap_members < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
+  CHK(stage_ready(e, &sgtd_engine::svox, kNoStoredVoxel, &c));
   if (!c->sv_local) { e->err = "no maps: sgtd_register_stored_local_loops has not run"; return SGTD_ERR_STATE; }
   const int64_t maps = (int64_t)c->sv_map_frame.size(), members = c->sv_mem_off.back();
   if (n_maps) *n_maps = maps;
@@ -6589,35 +6591,21 @@ int sgtd_result_stored_local_maps(sgtd_handle e, uint32_t *map_frame, int64_t *m
   return short_maps || short_members ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
-int sgtd_result_stored_voxel_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *n_corr,
-                                        int32_t *iterations, int32_t *status) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
-  if (c->sv_n == 0) return SGTD_OK;
-  return reg_rows_out(e, c, RegOut((size_t)c->sv_n, true), c->sv[sgtd_engine::VR_OUT].p, pose, fitness, cost, n_matched, n_corr, iterations, status);
+int sgtd_result_stored_voxel_registered(sgtd_handle e, double *pose, double *fitness, double *cost, int32_t *n_matched, int32_t *n_corr, int32_t *iterations,
+                                        int32_t *status) {
+  return vreg_rows_out(e, &sgtd_engine::svox, kNoStoredVoxel, pose, fitness, cost, n_matched, n_corr, iterations, status);
 }
 
 int sgtd_result_stored_voxel_map(sgtd_handle e, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
-  return vreg_map_out(e, c, c->sv, c->sv_host_map_vox, map, coord, n_points, mean, cov, capacity, n);
+  return vreg_map_out(e, &sgtd_engine::svox, kNoStoredVoxel, map, coord, n_points, mean, cov, capacity, n);
 }
 
 int sgtd_result_stored_voxel_matches(sgtd_handle e, int pair, int32_t *voxel, int64_t capacity, int64_t *n) {
-  if (!e || capacity < 0) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
-  return vreg_matches_out(e, c, c->sv, c->sv_host_soff, c->sv_mode, c->sv_n, pair, voxel, capacity, n);
+  return vreg_matches_out(e, &sgtd_engine::svox, kNoStoredVoxel, pair, voxel, capacity, n);
 }
 
 int sgtd_stored_voxel_register_stage_ms(sgtd_handle e, float *ms_cov, float *ms_map, float *ms_corr, float *ms_rest, float *ms_total) {
-  if (!e) return SGTD_ERR_INVALID;
-  sgtd_engine *c = nullptr;
-  CHK(stage_ready(e, &sgtd_engine::sv_n, kNoStoredVoxel, &c));
-  vreg_ms_out(c->sv_clock, ms_cov, ms_map, ms_corr, ms_rest, ms_total);
-  return SGTD_OK;
+  return vreg_ms_out(e, &sgtd_engine::svox, kNoStoredVoxel, ms_cov, ms_map, ms_corr, ms_rest, ms_total);
 }
 
 }  // extern "C"

@@ -1072,12 +1072,7 @@ class STDescManager:
             if w is not None and w.size != m:
                 raise ValueError("weights: one per edge")
             ws.append(w)
-        opt = RelaxOptions()
-        self._L.sgtd_default_relax_options(C.byref(opt))
-        for k, v in options.items():
-            if k not in dict(RelaxOptions._fields_):
-                raise TypeError("unknown option " + k)
-            setattr(opt, k, v)
+        opt = self._options(RelaxOptions, self._L.sgtd_default_relax_options, options)
         rep = RelaxReport()
         self._check(self._L.sgtd_relax_poses(self._h, n, _p(p0), _p(fx), m, _p(ni), _p(nj), _p(z), _p(ws[0]), _p(ws[1]),
                                              C.byref(opt), C.byref(rep)))
@@ -1336,6 +1331,109 @@ class STDescManager:
         self._check(self._L.sgtd_search_loop_aligned(self._h, float(min_overlap), float(max_rms), _p(bc), _p(bf), _p(br), _p(bo)))
         return bc, bf, br, bo
 
+    # ---- what the registration calls share: their arguments as the library takes them, checked, and their getters' bodies
+    def _points_arg(self, points, what="points"):
+        """(total, 3 or 4) f32, numpy or a torch.cuda tensor -> (shape, pointer, device_ptrs); the array is kept alive"""
+        if hasattr(points, "data_ptr"):
+            if not (points.is_cuda and points.is_contiguous()):
+                raise ValueError(what + ": a contiguous torch.cuda tensor")
+            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            shape, pp, dev = points.shape, _p(points), 0
+        self._keep = points
+        if len(shape) != 2 or shape[1] not in (3, 4):
+            raise ValueError(what + ": (total, 3 or 4)")
+        return shape, pp, dev
+
+    def _offsets(self, pt_off, shape, what="pt_off", per_query=False):
+        """the clouds' offsets within points of `shape` (int64): n_clouds + 1 of them, or one cloud per query of the batch"""
+        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+        if per_query and off.size != self._nq + 1:
+            raise ValueError(what + ": n_queries + 1 offsets")
+        if off.size < 1:
+            raise ValueError(what + ": n_clouds + 1 offsets")
+        if off[-1] > shape[0]:
+            raise ValueError(what + " names more points than were given")
+        return off
+
+    def _pairs_arg(self, src, tgt, init, what, tgt_ids=False):
+        """the pairs' sources, targets (cloud or map indices; tgt_ids: frame ids) and start poses -> (src, tgt, init, n)"""
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        t = self._frame_ids(tgt) if tgt_ids else np.ascontiguousarray(tgt, np.int32).reshape(-1)
+        if t.size != s.size:
+            raise ValueError(what)
+        p0 = None
+        if init is not None:
+            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
+            if p0.shape[0] != s.size:
+                raise ValueError("init: (n, 12), one start pose per pair")
+        return s, t, p0, s.size
+
+    def _maps_arg(self, map_off, members, map_pose, frame_ids=False):
+        """the maps' member offsets, members (cloud indices; frame_ids: frame ids) and member poses -> (map_off, members, map_pose)"""
+        moff = np.ascontiguousarray(np.asarray(map_off).reshape(-1), np.int32)
+        if moff.size < 1:
+            raise ValueError("map_off: n_maps + 1 offsets")
+        mem = self._frame_ids(members) if frame_ids else np.ascontiguousarray(members, np.int32).reshape(-1)
+        if moff[-1] > mem.size:
+            raise ValueError("map_off names more members than were given")
+        mp = None
+        if map_pose is not None:
+            mp = np.ascontiguousarray(map_pose, np.float64).reshape(-1, 12)
+            if mp.shape[0] != mem.size:
+                raise ValueError("map_pose: (members, 12), one pose per member")
+        return moff, mem, mp
+
+    @staticmethod
+    def _options(struct, default, options):
+        """an options struct of the library: `default` fills it, then the caller's fields"""
+        opt = struct()
+        default(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(struct._fields_):
+                raise TypeError("unknown option " + k)
+            setattr(opt, k, v)
+        return opt
+
+    @staticmethod
+    def _loops_args(start, max_per_query, max_members=0, radius=0.0):
+        """what the loops calls check of their choices -> the library's code of `start`"""
+        starts = {"verify": 0, "refined": 1, "aligned": 2}
+        if start not in starts:
+            raise ValueError('start: "verify", "refined" or "aligned"')
+        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
+            raise ValueError("max_per_query: an integer, not negative")
+        if isinstance(max_members, bool) or not isinstance(max_members, (int, np.integer)) or max_members < 0:
+            raise ValueError("max_members: an integer, not negative (0 = no cap)")
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (np.isfinite(radius) and radius >= 0):
+            raise ValueError("radius: finite and not negative")
+        return starts[start]
+
+    def _sized(self, fn, lead, kinds):
+        """a getter that is asked for its size first: fn(handle, *lead, arrays..., capacity, &n) -> the arrays, one per
+        (row shape, dtype) of `kinds`, n rows each"""
+        n = C.c_int64(0)
+        self._check(fn(self._h, *lead, *[None] * len(kinds), 0, C.byref(n)))
+        out = [np.zeros((n.value,) + row, dtype) for row, dtype in kinds]
+        self._check(fn(self._h, *lead, *[_p(a) for a in out], n.value, C.byref(n)))
+        return out
+
+    def _rows_dict(self, fn, n, with_corr):
+        """the result rows of a registration call of n pairs (n_corr: the voxel calls')"""
+        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64)}
+        for k in ("n_matched", "n_corr", "iterations", "status") if with_corr else ("n_matched", "iterations", "status"):
+            out[k] = np.zeros(n, np.int32)
+        self._check(fn(self._h, *[_p(a) for a in out.values()]))
+        return out
+
+    def _stage_ms(self, fn, k):
+        v = [C.c_float(0) for _ in range(k)]
+        self._check(fn(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    _VOXEL_KINDS = (((3,), np.int32), ((), np.int32), ((3,), np.float64), ((3, 3), np.float64))      # a voxel map's coord, n_points, mean, cov
+
     # ---- dense registration of raw clouds (sgtd_register_clouds) ---------------------------------------------
     def register_tiles(self):
         """source tile, target tile and slice length (points) of the register kernels"""
@@ -1349,71 +1447,30 @@ class STDescManager:
         the pairs; init: (n, 12) start poses in the rel_pose layout (rot row-major, t; x = R p + t takes a source point
         into the target's frame), None = the identity; options: fields of sgtd_register_options.  -> dict of pose [n, 12],
         fitness [n], cost [n, 2] (first and last linearisation), n_matched, iterations, status [n] (int32)"""
-        if hasattr(points, "data_ptr"):
-            assert points.is_cuda and points.is_contiguous()
-            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
-            self._keep = points
-        else:
-            points = np.ascontiguousarray(points, dtype=np.float32)
-            shape, pp, dev = points.shape, _p(points), 0
-        if len(shape) != 2 or shape[1] not in (3, 4):
-            raise ValueError("points: (total, 3 or 4)")
-        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
-        if off.size < 1:
-            raise ValueError("pt_off: n_clouds + 1 offsets")
-        if off[-1] > shape[0]:
-            raise ValueError("pt_off names more points than were given")
-        s = np.ascontiguousarray(src, np.int32).reshape(-1)
-        t = np.ascontiguousarray(tgt, np.int32).reshape(-1)
-        n = s.size
-        if t.size != n:
-            raise ValueError("src and tgt: one cloud index per pair")
-        p0 = None
-        if init is not None:
-            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
-            if p0.shape[0] != n:
-                raise ValueError("init: (n, 12), one start pose per pair")
-        opt = RegisterOptions()
-        self._L.sgtd_default_register_options(C.byref(opt))
-        for k, v in options.items():
-            if k not in dict(RegisterOptions._fields_):
-                raise TypeError("unknown option " + k)
-            setattr(opt, k, v)
+        shape, pp, dev = self._points_arg(points)
+        off = self._offsets(pt_off, shape)
+        s, t, p0, n = self._pairs_arg(src, tgt, init, "src and tgt: one cloud index per pair")
+        opt = self._options(RegisterOptions, self._L.sgtd_default_register_options, options)
         self._check(self._L.sgtd_register_clouds(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(s), _p(t), _p(p0), n, dev))
         self._reg_n = n
         return self.result_registered()
 
     def result_registered(self):
-        n = self._reg_n
-        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
-               "n_matched": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
-        self._check(self._L.sgtd_result_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
-                                                   _p(out["iterations"]), _p(out["status"])))
-        return out
+        return self._rows_dict(self._L.sgtd_result_registered, self._reg_n, False)
 
     def register_covariances(self, cloud):
         """the regularised covariances of one cloud of the last register_clouds call: (n, 3, 3) f64; 0 rows for a cloud no
         pair named"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_register_covariances(self._h, int(cloud), None, 0, C.byref(n)))
-        cov = np.zeros((n.value, 3, 3), np.float64)
-        self._check(self._L.sgtd_result_register_covariances(self._h, int(cloud), _p(cov), n.value, C.byref(n)))
-        return cov
+        return self._sized(self._L.sgtd_result_register_covariances, (int(cloud),), (((3, 3), np.float64),))[0]
 
     def register_matches(self, pair):
         """the correspondences of one pair under its final pose: (tgt_index (n,) int32, -1 where none; d2 (n,) f64)"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_register_matches(self._h, int(pair), None, None, 0, C.byref(n)))
-        j, d2 = np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
-        self._check(self._L.sgtd_result_register_matches(self._h, int(pair), _p(j), _p(d2), n.value, C.byref(n)))
-        return j, d2
+        return tuple(self._sized(self._L.sgtd_result_register_matches, (int(pair),), (((), np.int32), ((), np.float64))))
 
     def register_stage_ms(self):
         """device milliseconds of the last register_clouds call: covariances, searches, the rest, the whole call (zeros
         unless set_timing(True))"""
-        v = [C.c_float(0) for _ in range(4)]
-        self._check(self._L.sgtd_register_stage_ms(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._stage_ms(self._L.sgtd_register_stage_ms, 4)
 
     def register_pairs(self, max_per_query=5, start="verify"):
         """the (query, candidate) pairs register_loops forms, after verify(): per query its candidates with a verification
@@ -1421,10 +1478,7 @@ class STDescManager:
         of them -> (query [m], cand [m], frame [m] (int32), init [m, 12]) with the pose of the named stage: "verify",
         "refined" (refine_poses) or "aligned" (align_keypoints); a stage that has not run on this batch raises its state
         error"""
-        if start not in ("verify", "refined", "aligned"):
-            raise ValueError('start: "verify", "refined" or "aligned"')
-        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
-            raise ValueError("max_per_query: an integer, not negative")
+        self._loops_args(start, max_per_query)
         res = self.results()
         qs, cs, fs, init = [], [], [], []
         for q in range(self._nq):
@@ -1455,52 +1509,47 @@ class STDescManager:
         brute force.  The world pose of a pair is result_world_poses' composition (the frame's stored pose times the
         relative pose) with the registered pose in place of verify()'s; the node's :747 multiplies the GICP transform on
         the other side of the loop transform, which is not reproduced here."""
+        pack = self._loop_clouds(query_points, query_pt_off, map_clouds)
+        q, c, f, init = self.register_pairs(max_per_query, start)
+        has = np.array([self._by_frame(map_clouds, int(x)) is not None for x in f], bool)
+        q, c, f, init = q[has], c[has], f[has], init[has]
+        pts, off, slot = pack(sorted(set(int(x) for x in f)))
+        tgt = np.array([slot[int(x)] for x in f], np.int32)
+        out = self.register_clouds(pts, off, q, tgt, init if len(q) else None, **options)
+        out.update(query=q, cand=c, frame=f, init=init, src_cloud=q.copy(), tgt_cloud=tgt, points=pts, pt_off=off)
+        return out
+
+    @staticmethod
+    def _by_frame(table, frame):
+        """the entry of `frame` in a dict or sequence by frame id, None where it has none"""
+        if isinstance(table, dict):
+            return table.get(int(frame))
+        return table[frame] if 0 <= frame < len(table) else None
+
+    def _loop_clouds(self, query_points, query_pt_off, map_clouds):
+        """the queries' clouds of register_loops / register_loops_local, checked -> pack(frames): the query clouds followed
+        by the clouds of those map frames -> (points, pt_off, slot: frame id -> cloud index)"""
         qp = np.ascontiguousarray(query_points, dtype=np.float32)
         if qp.ndim != 2 or qp.shape[1] not in (3, 4):
             raise ValueError("query_points: (total, 3 or 4)")
         qoff = np.asarray(query_pt_off, np.int64).reshape(-1)
         if qoff.size != self._nq + 1:
             raise ValueError("query_pt_off: n_queries + 1 offsets")
-        q, c, f, init = self.register_pairs(max_per_query, start)
 
-        def cloud_of(frame):
-            if isinstance(map_clouds, dict):
-                return map_clouds.get(int(frame))
-            return map_clouds[frame] if 0 <= frame < len(map_clouds) else None
+        def pack(frames):
+            clouds = []
+            for x in frames:
+                a = np.ascontiguousarray(self._by_frame(map_clouds, x), dtype=np.float32)
+                if a.ndim != 2 or a.shape[1] != qp.shape[1]:
+                    raise ValueError("map_clouds: (n, %d) arrays, as the query points" % qp.shape[1])
+                clouds.append(a)
+            pts = np.concatenate([qp[:qoff[-1]]] + clouds) if clouds else qp[:qoff[-1]]
+            off = np.concatenate([qoff, qoff[-1] + np.cumsum([a.shape[0] for a in clouds], dtype=np.int64)]).astype(np.int64)
+            return pts, off, {x: self._nq + k for k, x in enumerate(frames)}
 
-        has = np.array([cloud_of(int(x)) is not None for x in f], bool)
-        q, c, f, init = q[has], c[has], f[has], init[has]
-        frames = sorted(set(int(x) for x in f))
-        stride = qp.shape[1]
-        clouds = []
-        for x in frames:
-            a = np.ascontiguousarray(cloud_of(x), dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != stride:
-                raise ValueError("map_clouds: (n, %d) arrays, as the query points" % stride)
-            clouds.append(a)
-        pts = np.concatenate([qp[:qoff[-1]]] + clouds) if clouds else qp[:qoff[-1]]
-        off = np.concatenate([qoff, qoff[-1] + np.cumsum([a.shape[0] for a in clouds], dtype=np.int64)]).astype(np.int64)
-        slot = {x: self._nq + k for k, x in enumerate(frames)}
-        tgt = np.array([slot[int(x)] for x in f], np.int32)
-        out = self.register_clouds(pts, off, q, tgt, init if len(q) else None, **options)
-        out.update(query=q, cand=c, frame=f, init=init, src_cloud=q.copy(), tgt_cloud=tgt, points=pts, pt_off=off)
-        return out
+        return pack
 
     # ---- map clouds kept on the device (sgtd_set_frame_clouds) and registration against them --------------------
-    def _points_arg(self, points, what="points"):
-        """(total, 3 or 4) f32, numpy or a torch.cuda tensor -> (shape, pointer, device_ptrs); the array is kept alive"""
-        if hasattr(points, "data_ptr"):
-            if not (points.is_cuda and points.is_contiguous()):
-                raise ValueError(what + ": a contiguous torch.cuda tensor")
-            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
-        else:
-            points = np.ascontiguousarray(points, dtype=np.float32)
-            shape, pp, dev = points.shape, _p(points), 0
-        self._keep = points
-        if len(shape) != 2 or shape[1] not in (3, 4):
-            raise ValueError(what + ": (total, 3 or 4)")
-        return shape, pp, dev
-
     @staticmethod
     def _frame_ids(frames):
         f = np.asarray(frames).reshape(-1)
@@ -1568,73 +1617,34 @@ class STDescManager:
         self._check(self._L.sgtd_result_frame_cloud(self._h, int(frame), _p(xyz), _p(cov), n.value, C.byref(n)))
         return xyz, cov
 
-    def _register_options(self, options):
-        opt = RegisterOptions()
-        self._L.sgtd_default_register_options(C.byref(opt))
-        for k, v in options.items():
-            if k not in dict(RegisterOptions._fields_):
-                raise TypeError("unknown option " + k)
-            setattr(opt, k, v)
-        return opt
-
     def register_stored(self, points, pt_off, src, tgt_frame, init=None, **options):
         """sgtd_register_stored: register_clouds with the targets read from the cloud store.  points, pt_off: the call's
         clouds as register_clouds takes them; src: (n,) cloud indices; tgt_frame: (n,) frame ids that have a stored cloud;
         init, options and the returned dict as register_clouds'.  The results are register_clouds' on the call's clouds
         followed by the frames' stored clouds, bit for bit."""
         shape, pp, dev = self._points_arg(points)
-        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
-        if off.size < 1:
-            raise ValueError("pt_off: n_clouds + 1 offsets")
-        if off[-1] > shape[0]:
-            raise ValueError("pt_off names more points than were given")
-        s = np.ascontiguousarray(src, np.int32).reshape(-1)
-        t = self._frame_ids(tgt_frame)
-        n = s.size
-        if t.size != n:
-            raise ValueError("src and tgt_frame: one cloud index and one frame id per pair")
-        p0 = None
-        if init is not None:
-            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
-            if p0.shape[0] != n:
-                raise ValueError("init: (n, 12), one start pose per pair")
-        opt = self._register_options(options)
+        off = self._offsets(pt_off, shape)
+        s, t, p0, n = self._pairs_arg(src, tgt_frame, init, "src and tgt_frame: one cloud index and one frame id per pair", tgt_ids=True)
+        opt = self._options(RegisterOptions, self._L.sgtd_default_register_options, options)
         self._check(self._L.sgtd_register_stored(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(s), _p(t), _p(p0), n, dev))
         self._stored_n = n
         return self.result_stored_registered()
 
     def result_stored_registered(self):
-        n = self._stored_n
-        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
-               "n_matched": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
-        self._check(self._L.sgtd_result_stored_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
-                                                          _p(out["iterations"]), _p(out["status"])))
-        return out
+        return self._rows_dict(self._L.sgtd_result_stored_registered, self._stored_n, False)
 
     def register_loops_stored(self, query_points, query_pt_off, max_per_query=5, start="verify", **options):
         """sgtd_register_stored_loops, after verify(): register_loops with the map clouds read from the cloud store and the
         pairs formed on the device (register_pairs' rule; a candidate whose frame has no stored cloud is dropped).
         query_points: (total, 3 or 4) f32, numpy or a torch.cuda tensor, with the n_queries + 1 offsets query_pt_off.
         -> register_loops' dict: query, cand, frame [m] (int32), init [m, 12] and register_clouds' fields per pair"""
-        starts = {"verify": 0, "refined": 1, "aligned": 2}
-        if start not in starts:
-            raise ValueError('start: "verify", "refined" or "aligned"')
-        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
-            raise ValueError("max_per_query: an integer, not negative")
+        code = self._loops_args(start, max_per_query)
         shape, pp, dev = self._points_arg(query_points, "query_points")
-        qoff = np.ascontiguousarray(np.asarray(query_pt_off).reshape(-1), np.int64)
-        if qoff.size != self._nq + 1:
-            raise ValueError("query_pt_off: n_queries + 1 offsets")
-        if qoff[-1] > shape[0]:
-            raise ValueError("query_pt_off names more points than were given")
-        opt = self._register_options(options)
-        self._check(self._L.sgtd_register_stored_loops(self._h, C.byref(opt), pp, int(shape[1]), _p(qoff), int(max_per_query), starts[start], dev))
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_stored_pairs(self._h, None, None, None, None, 0, C.byref(n)))
-        m = n.value
-        q, c, f, init = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 12), np.float64)
-        self._check(self._L.sgtd_result_stored_pairs(self._h, _p(q), _p(c), _p(f), _p(init), m, C.byref(n)))
-        self._stored_n = m
+        qoff = self._offsets(query_pt_off, shape, "query_pt_off", per_query=True)
+        opt = self._options(RegisterOptions, self._L.sgtd_default_register_options, options)
+        self._check(self._L.sgtd_register_stored_loops(self._h, C.byref(opt), pp, int(shape[1]), _p(qoff), int(max_per_query), code, dev))
+        q, c, f, init = self._sized(self._L.sgtd_result_stored_pairs, (), (((), np.int32),) * 3 + (((12,), np.float64),))
+        self._stored_n = len(q)
         out = self.result_stored_registered()
         out.update(query=q, cand=c, frame=f, init=init)
         return out
@@ -1642,27 +1652,17 @@ class STDescManager:
     def stored_covariances(self, cloud):
         """the regularised covariances of one of the call's clouds of the last register_stored / register_loops_stored
         call: (n, 3, 3) f64; 0 rows for a cloud no pair named"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_stored_covariances(self._h, int(cloud), None, 0, C.byref(n)))
-        cov = np.zeros((n.value, 3, 3), np.float64)
-        self._check(self._L.sgtd_result_stored_covariances(self._h, int(cloud), _p(cov), n.value, C.byref(n)))
-        return cov
+        return self._sized(self._L.sgtd_result_stored_covariances, (int(cloud),), (((3, 3), np.float64),))[0]
 
     def stored_matches(self, pair):
         """the correspondences of one pair under its final pose: (tgt_index (n,) int32 within the frame's stored cloud, -1
         where none; d2 (n,) f64)"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_stored_matches(self._h, int(pair), None, None, 0, C.byref(n)))
-        j, d2 = np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
-        self._check(self._L.sgtd_result_stored_matches(self._h, int(pair), _p(j), _p(d2), n.value, C.byref(n)))
-        return j, d2
+        return tuple(self._sized(self._L.sgtd_result_stored_matches, (int(pair),), (((), np.int32), ((), np.float64))))
 
     def stored_register_stage_ms(self):
         """device milliseconds of the last register_stored / register_loops_stored call: covariances, searches, the rest,
         the whole run (zeros unless set_timing(True))"""
-        v = [C.c_float(0) for _ in range(4)]
-        self._check(self._L.sgtd_stored_register_stage_ms(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._stage_ms(self._L.sgtd_stored_register_stage_ms, 4)
 
     # ---- voxelised registration against voxel maps (sgtd_register_voxels) -------------------------------------
     def register_voxels(self, points, pt_off, map_off, map_cloud, map_pose, src, tgt_map, init=None, **options):
@@ -1671,47 +1671,11 @@ class STDescManager:
         (members, 12) in the rel_pose layout (x = R p + t takes a member's point into the map's frame), None = the
         identity; src, tgt_map: (n,) the pairs' source clouds and target maps; init: (n, 12) start poses, None = the
         identity; options: fields of sgtd_voxel_register_options.  -> result_voxel_registered()"""
-        if hasattr(points, "data_ptr"):
-            assert points.is_cuda and points.is_contiguous()
-            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
-            self._keep = points
-        else:
-            points = np.ascontiguousarray(points, dtype=np.float32)
-            shape, pp, dev = points.shape, _p(points), 0
-        if len(shape) != 2 or shape[1] not in (3, 4):
-            raise ValueError("points: (total, 3 or 4)")
-        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
-        if off.size < 1:
-            raise ValueError("pt_off: n_clouds + 1 offsets")
-        if off[-1] > shape[0]:
-            raise ValueError("pt_off names more points than were given")
-        moff = np.ascontiguousarray(np.asarray(map_off).reshape(-1), np.int32)
-        if moff.size < 1:
-            raise ValueError("map_off: n_maps + 1 offsets")
-        mcl = np.ascontiguousarray(map_cloud, np.int32).reshape(-1)
-        if moff[-1] > mcl.size:
-            raise ValueError("map_off names more members than were given")
-        mp = None
-        if map_pose is not None:
-            mp = np.ascontiguousarray(map_pose, np.float64).reshape(-1, 12)
-            if mp.shape[0] != mcl.size:
-                raise ValueError("map_pose: (members, 12), one pose per member")
-        s = np.ascontiguousarray(src, np.int32).reshape(-1)
-        t = np.ascontiguousarray(tgt_map, np.int32).reshape(-1)
-        n = s.size
-        if t.size != n:
-            raise ValueError("src and tgt_map: one cloud and one map index per pair")
-        p0 = None
-        if init is not None:
-            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
-            if p0.shape[0] != n:
-                raise ValueError("init: (n, 12), one start pose per pair")
-        opt = VoxelRegisterOptions()
-        self._L.sgtd_default_voxel_register_options(C.byref(opt))
-        for k, v in options.items():
-            if k not in dict(VoxelRegisterOptions._fields_):
-                raise TypeError("unknown option " + k)
-            setattr(opt, k, v)
+        shape, pp, dev = self._points_arg(points)
+        off = self._offsets(pt_off, shape)
+        moff, mcl, mp = self._maps_arg(map_off, map_cloud, map_pose)
+        s, t, p0, n = self._pairs_arg(src, tgt_map, init, "src and tgt_map: one cloud and one map index per pair")
+        opt = self._options(VoxelRegisterOptions, self._L.sgtd_default_voxel_register_options, options)
         self._check(self._L.sgtd_register_voxels(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(moff), _p(mcl), _p(mp),
                                                  moff.size - 1, _p(s), _p(t), _p(p0), n, dev))
         self._vreg_n = n
@@ -1720,41 +1684,22 @@ class STDescManager:
     def result_voxel_registered(self):
         """-> dict of pose [n, 12], fitness [n], cost [n, 2] (first and last linearisation), n_matched, n_corr, iterations,
         status [n] (int32) of the last register_voxels call"""
-        n = self._vreg_n
-        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
-               "n_matched": np.zeros(n, np.int32), "n_corr": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32),
-               "status": np.zeros(n, np.int32)}
-        self._check(self._L.sgtd_result_voxel_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
-                                                         _p(out["n_corr"]), _p(out["iterations"]), _p(out["status"])))
-        return out
+        return self._rows_dict(self._L.sgtd_result_voxel_registered, self._vreg_n, True)
 
     def voxel_map(self, m):
         """the voxels of map m of the last register_voxels call, in their numbering -> dict of coord (v, 3) int32,
         n_points (v,) int32, mean (v, 3), cov (v, 3, 3) f64"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_voxel_map(self._h, int(m), None, None, None, None, 0, C.byref(n)))
-        v = n.value
-        out = {"coord": np.zeros((v, 3), np.int32), "n_points": np.zeros(v, np.int32), "mean": np.zeros((v, 3), np.float64),
-               "cov": np.zeros((v, 3, 3), np.float64)}
-        self._check(self._L.sgtd_result_voxel_map(self._h, int(m), _p(out["coord"]), _p(out["n_points"]), _p(out["mean"]), _p(out["cov"]), v,
-                                                  C.byref(n)))
-        return out
+        return dict(zip(("coord", "n_points", "mean", "cov"), self._sized(self._L.sgtd_result_voxel_map, (int(m),), self._VOXEL_KINDS)))
 
     def voxel_matches(self, pair):
         """the correspondences of one pair under its final pose: (n_src, mode) int32, the voxel's index within the map per
         offset, -1 where there is none"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_voxel_matches(self._h, int(pair), None, 0, C.byref(n)))
-        v = np.zeros(n.value, np.int32)
-        self._check(self._L.sgtd_result_voxel_matches(self._h, int(pair), _p(v), n.value, C.byref(n)))
-        return v
+        return self._sized(self._L.sgtd_result_voxel_matches, (int(pair),), (((), np.int32),))[0]
 
     def voxel_register_stage_ms(self):
         """device milliseconds of the last register_voxels call: covariances, map build, correspondence passes, the rest,
         the whole call (zeros unless set_timing(True))"""
-        v = [C.c_float(0) for _ in range(5)]
-        self._check(self._L.sgtd_voxel_register_stage_ms(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._stage_ms(self._L.sgtd_voxel_register_stage_ms, 5)
 
     # ---- voxel maps whose members are stored clouds (sgtd_register_stored_voxels) -------------------------------
     def register_stored_voxels(self, points, pt_off, map_off, map_frame, map_pose, src, tgt_map, init=None, **options):
@@ -1764,38 +1709,10 @@ class STDescManager:
         tgt_map, init, options and the returned dict as register_voxels'.  The results are register_voxels' on the call's
         clouds followed by the members' stored clouds, bit for bit; k_neighbors and plane_eps must be the store's."""
         shape, pp, dev = self._points_arg(points)
-        off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
-        if off.size < 1:
-            raise ValueError("pt_off: n_clouds + 1 offsets")
-        if off[-1] > shape[0]:
-            raise ValueError("pt_off names more points than were given")
-        moff = np.ascontiguousarray(np.asarray(map_off).reshape(-1), np.int32)
-        if moff.size < 1:
-            raise ValueError("map_off: n_maps + 1 offsets")
-        mfr = self._frame_ids(map_frame)
-        if moff[-1] > mfr.size:
-            raise ValueError("map_off names more members than were given")
-        mp = None
-        if map_pose is not None:
-            mp = np.ascontiguousarray(map_pose, np.float64).reshape(-1, 12)
-            if mp.shape[0] != mfr.size:
-                raise ValueError("map_pose: (members, 12), one pose per member")
-        s = np.ascontiguousarray(src, np.int32).reshape(-1)
-        t = np.ascontiguousarray(tgt_map, np.int32).reshape(-1)
-        n = s.size
-        if t.size != n:
-            raise ValueError("src and tgt_map: one cloud and one map index per pair")
-        p0 = None
-        if init is not None:
-            p0 = np.ascontiguousarray(init, np.float64).reshape(-1, 12)
-            if p0.shape[0] != n:
-                raise ValueError("init: (n, 12), one start pose per pair")
-        opt = VoxelRegisterOptions()
-        self._L.sgtd_default_voxel_register_options(C.byref(opt))
-        for k, v in options.items():
-            if k not in dict(VoxelRegisterOptions._fields_):
-                raise TypeError("unknown option " + k)
-            setattr(opt, k, v)
+        off = self._offsets(pt_off, shape)
+        moff, mfr, mp = self._maps_arg(map_off, map_frame, map_pose, frame_ids=True)
+        s, t, p0, n = self._pairs_arg(src, tgt_map, init, "src and tgt_map: one cloud and one map index per pair")
+        opt = self._options(VoxelRegisterOptions, self._L.sgtd_default_voxel_register_options, options)
         self._check(self._L.sgtd_register_stored_voxels(self._h, C.byref(opt), pp, int(shape[1]), _p(off), off.size - 1, _p(moff), _p(mfr), _p(mp),
                                                         moff.size - 1, _p(s), _p(t), _p(p0), n, dev))
         self._svreg_n = n
@@ -1803,32 +1720,15 @@ class STDescManager:
 
     def result_stored_voxel_registered(self):
         """-> result_voxel_registered()'s dict of the last register_stored_voxels call"""
-        n = self._svreg_n
-        out = {"pose": np.zeros((n, 12), np.float64), "fitness": np.zeros(n, np.float64), "cost": np.zeros((n, 2), np.float64),
-               "n_matched": np.zeros(n, np.int32), "n_corr": np.zeros(n, np.int32), "iterations": np.zeros(n, np.int32),
-               "status": np.zeros(n, np.int32)}
-        self._check(self._L.sgtd_result_stored_voxel_registered(self._h, _p(out["pose"]), _p(out["fitness"]), _p(out["cost"]), _p(out["n_matched"]),
-                                                                _p(out["n_corr"]), _p(out["iterations"]), _p(out["status"])))
-        return out
+        return self._rows_dict(self._L.sgtd_result_stored_voxel_registered, self._svreg_n, True)
 
     def stored_voxel_map(self, m):
         """the voxels of map m of the last register_stored_voxels call -> voxel_map()'s dict"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_stored_voxel_map(self._h, int(m), None, None, None, None, 0, C.byref(n)))
-        v = n.value
-        out = {"coord": np.zeros((v, 3), np.int32), "n_points": np.zeros(v, np.int32), "mean": np.zeros((v, 3), np.float64),
-               "cov": np.zeros((v, 3, 3), np.float64)}
-        self._check(self._L.sgtd_result_stored_voxel_map(self._h, int(m), _p(out["coord"]), _p(out["n_points"]), _p(out["mean"]), _p(out["cov"]), v,
-                                                         C.byref(n)))
-        return out
+        return dict(zip(("coord", "n_points", "mean", "cov"), self._sized(self._L.sgtd_result_stored_voxel_map, (int(m),), self._VOXEL_KINDS)))
 
     def stored_voxel_matches(self, pair):
         """the correspondences of one pair of the last register_stored_voxels call, as voxel_matches()"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_stored_voxel_matches(self._h, int(pair), None, 0, C.byref(n)))
-        v = np.zeros(n.value, np.int32)
-        self._check(self._L.sgtd_result_stored_voxel_matches(self._h, int(pair), _p(v), n.value, C.byref(n)))
-        return v
+        return self._sized(self._L.sgtd_result_stored_voxel_matches, (int(pair),), (((), np.int32),))[0]
 
     def register_loops_local_stored(self, query_points, query_pt_off, radius=15.0, max_members=0, max_per_query=5, start="verify", **options):
         """sgtd_register_stored_local_loops, after verify(): register_loops_local with the map clouds read from the cloud
@@ -1839,28 +1739,11 @@ class STDescManager:
         torch.cuda tensor, with the n_queries + 1 offsets query_pt_off.  -> register_loops_local's dict: query, cand, frame,
         tgt_map [m] (int32), init [m, 12], register_voxels' fields per pair, map_frames, members (per map, the member frame
         ids), map_off, map_frame, map_pose as register_stored_voxels takes them"""
-        starts = {"verify": 0, "refined": 1, "aligned": 2}
-        if start not in starts:
-            raise ValueError('start: "verify", "refined" or "aligned"')
-        if isinstance(max_per_query, bool) or not isinstance(max_per_query, (int, np.integer)) or max_per_query < 0:
-            raise ValueError("max_per_query: an integer, not negative")
-        if isinstance(max_members, bool) or not isinstance(max_members, (int, np.integer)) or max_members < 0:
-            raise ValueError("max_members: an integer, not negative (0 = no cap)")
-        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (np.isfinite(radius) and radius >= 0):
-            raise ValueError("radius: finite and not negative")
+        code = self._loops_args(start, max_per_query, max_members, radius)
         shape, pp, dev = self._points_arg(query_points, "query_points")
-        qoff = np.ascontiguousarray(np.asarray(query_pt_off).reshape(-1), np.int64)
-        if qoff.size != self._nq + 1:
-            raise ValueError("query_pt_off: n_queries + 1 offsets")
-        if qoff[-1] > shape[0]:
-            raise ValueError("query_pt_off names more points than were given")
-        opt = VoxelRegisterOptions()
-        self._L.sgtd_default_voxel_register_options(C.byref(opt))
-        for k, v in options.items():
-            if k not in dict(VoxelRegisterOptions._fields_):
-                raise TypeError("unknown option " + k)
-            setattr(opt, k, v)
-        self._check(self._L.sgtd_register_stored_local_loops(self._h, C.byref(opt), pp, int(shape[1]), _p(qoff), int(max_per_query), starts[start],
+        qoff = self._offsets(query_pt_off, shape, "query_pt_off", per_query=True)
+        opt = self._options(VoxelRegisterOptions, self._L.sgtd_default_voxel_register_options, options)
+        self._check(self._L.sgtd_register_stored_local_loops(self._h, C.byref(opt), pp, int(shape[1]), _p(qoff), int(max_per_query), code,
                                                              float(radius), int(max_members), dev))
         q, c, f, tgt, init = self.stored_local_pairs()
         self._svreg_n = len(q)
@@ -1873,12 +1756,7 @@ class STDescManager:
 
     def stored_local_pairs(self):
         """the rows of the last register_loops_local_stored call -> (query, cand, frame, tgt_map [m] int32, init [m, 12])"""
-        n = C.c_int64(0)
-        self._check(self._L.sgtd_result_stored_local_pairs(self._h, None, None, None, None, None, 0, C.byref(n)))
-        m = n.value
-        q, c, f, t, init = (np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 12), np.float64))
-        self._check(self._L.sgtd_result_stored_local_pairs(self._h, _p(q), _p(c), _p(f), _p(t), _p(init), m, C.byref(n)))
-        return q, c, f, t, init
+        return tuple(self._sized(self._L.sgtd_result_stored_local_pairs, (), (((), np.int32),) * 4 + (((12,), np.float64),)))
 
     def stored_local_maps(self):
         """the maps of the last register_loops_local_stored call -> dict of map_frame [maps] (uint32, ascending), mem_off
@@ -1895,9 +1773,7 @@ class STDescManager:
     def stored_voxel_register_stage_ms(self):
         """device milliseconds of the last register_stored_voxels call: covariances (of the call's clouds alone), map
         build, correspondence passes, the rest, the whole call (zeros unless set_timing(True))"""
-        v = [C.c_float(0) for _ in range(5)]
-        self._check(self._L.sgtd_stored_voxel_register_stage_ms(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._stage_ms(self._L.sgtd_stored_voxel_register_stage_ms, 5)
 
     @staticmethod
     def voxel_map_members(frame, frame_poses, has_cloud, radius=15.0, max_members=0):
@@ -1933,43 +1809,18 @@ class STDescManager:
         candidate without a cloud or a pose is skipped.  -> what register_loops returns (register_voxels' fields per
         pair) plus tgt_map [m], map_frames (the maps' candidate frames) and members (per map, the member frame ids),
         map_off, map_cloud, map_pose as given to the call.  evaluate.choose_registered works on its fitness."""
-        qp = np.ascontiguousarray(query_points, dtype=np.float32)
-        if qp.ndim != 2 or qp.shape[1] not in (3, 4):
-            raise ValueError("query_points: (total, 3 or 4)")
-        qoff = np.asarray(query_pt_off, np.int64).reshape(-1)
-        if qoff.size != self._nq + 1:
-            raise ValueError("query_pt_off: n_queries + 1 offsets")
+        pack = self._loop_clouds(query_points, query_pt_off, map_clouds)
         q, c, f, init = self.register_pairs(max_per_query, start)
-
-        def cloud_of(frame):
-            if isinstance(map_clouds, dict):
-                return map_clouds.get(int(frame))
-            return map_clouds[frame] if 0 <= frame < len(map_clouds) else None
-
-        def pose_of(frame):
-            if isinstance(frame_poses, dict):
-                return frame_poses.get(int(frame))
-            return frame_poses[frame] if 0 <= frame < len(frame_poses) else None
-
-        has = np.array([cloud_of(int(x)) is not None and pose_of(int(x)) is not None for x in f], bool)
+        has_cloud = lambda i: self._by_frame(map_clouds, i) is not None
+        has = np.array([has_cloud(int(x)) and self._by_frame(frame_poses, int(x)) is not None for x in f], bool)
         q, c, f, init = q[has], c[has], f[has], init[has]
         map_frames = sorted(set(int(x) for x in f))
         members, rels = [], []
         for x in map_frames:
-            m, rel = self.voxel_map_members(x, frame_poses, lambda i: cloud_of(i) is not None, radius, max_members)
+            m, rel = self.voxel_map_members(x, frame_poses, has_cloud, radius, max_members)
             members.append(m)
             rels.append(rel)
-        frames = sorted(set(int(i) for m in members for i in m))
-        stride = qp.shape[1]
-        clouds = []
-        for x in frames:
-            a = np.ascontiguousarray(cloud_of(x), dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != stride:
-                raise ValueError("map_clouds: (n, %d) arrays, as the query points" % stride)
-            clouds.append(a)
-        pts = np.concatenate([qp[:qoff[-1]]] + clouds) if clouds else qp[:qoff[-1]]
-        off = np.concatenate([qoff, qoff[-1] + np.cumsum([a.shape[0] for a in clouds], dtype=np.int64)]).astype(np.int64)
-        slot = {x: self._nq + k for k, x in enumerate(frames)}
+        pts, off, slot = pack(sorted(set(int(i) for m in members for i in m)))
         map_off = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.int32)
         map_cloud = np.array([slot[int(i)] for m in members for i in m], np.int32)
         map_pose = np.concatenate(rels).reshape(-1, 12) if rels else np.zeros((0, 12))
