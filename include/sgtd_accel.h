@@ -343,7 +343,12 @@ int sgtd_export_candidates_dev(sgtd_handle h, int32_t *d_cand_frame, int32_t *d_
  *                               and src (table << 8 | slot in the owner's local list, -1 unused), n_cand [n_queries], keep
  *                               u64 [n_queries] (bit s: slot s of table my_table's local list survived; my_table -1: none)
  *                               and flags[0] (bit 0: some table came from a batch that outgrew a work buffer — sgtd_sync
- *                               every rank and exchange again; bit 1: tables of different shapes)
+ *                               every rank and exchange again; bit 1: tables of different shapes).  Equal (frame, votes)
+ *                               pairs from different tables give ONE merged candidate; its src names one of their slots,
+ *                               which one is unspecified, and keep has its bit on that table only (frame-range shards
+ *                               never send such pairs).  The kernel holds the keys of a query in registers:
+ *                               n_tables * candidate_num <= 1024, beyond that SGTD_ERR_UNSUPPORTED and nothing is written;
+ *                               my_table outside [-1, n_tables) or n_tables < 1: SGTD_ERR_INVALID
  *   sgtd_set_deferred_lists /   a batch stops behind its candidate tables; sgtd_finish_lists writes the match lists — of the
  *   sgtd_finish_lists           candidates in d_keep only (NULL: all).  Repeatable (the match records stay intact).  Batches
  *                               whose lists come from the per-block passes (small batches, sgtd_stats.select_form 0) ignore

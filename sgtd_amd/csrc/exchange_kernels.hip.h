@@ -38,7 +38,11 @@ __global__ __launch_bounds__(256) void export_candidates_kernel(const int *cand_
 //                    the candidate's match list and its verification result
 //   out_keep[q]    = bit s: slot s of table `my_table`'s local list is in the merged list (the rank's winners: lists /
 //                    sgtd_verify_masked only run for them)
-// Frames of different tables must be disjoint (they are: frame-range shards); equal keys collapse into one candidate.
+// Frames of different tables must be disjoint (they are: frame-range shards).  Equal keys — the same (frame, votes) in two
+// slots — collapse into ONE candidate: every copy is cleared in the round that picks it.  Its source is the copy in the lowest
+// LANE (the first set bit of the ballot; within that lane the first register), which need not be the lowest item index: item 67
+// sits in lane 3 and wins over item 5 in lane 5.  Which copy is named is therefore unspecified; out_keep follows out_src, so
+// exactly one table has the bit (tests/test_gpu_exchange_edges.py::test_equal_keys).
 #define SGTD_MERGE_PER_LANE 16      // n_tables * cn <= 1024
 
 // PER: key registers per lane (the host picks the smallest of 1, 4, 8, 16 that holds n_tables * cn keys — a round costs
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void merge_candidates_kernel(const int *gather
     const u32 wlo = wave_max_u32((u32)(best >> 32) == whi ? (u32)best : 0u);
     const u64 wbest = ((u64)whi << 32) | (u64)wlo;
     const u64 holders = __ballot(best == wbest);
-    const int L = __builtin_ctzll(holders);                  // (equal keys: the lowest item index names the source)
+    const int L = __builtin_ctzll(holders);                  // (equal keys: the lowest LANE holding one names the source, see above)
     const int item = __builtin_amdgcn_readlane(bj * SGTD_WAVE + lane, L);
 #pragma unroll
     for (int j = 0; j < PER; j++) a[j] = (a[j] == wbest) ? 0ull : a[j];
