@@ -1203,7 +1203,8 @@ int sgtd_local_map_stage_ms(sgtd_handle h, float *ms_members, float *ms_gather, 
  * a workgroup per (tile of SGTD_REG_SRC_TILE source points, slice of the target), the slices' minima combined exactly;
  * every SUM one workgroup per pair; one lane per pair takes every decision, the host enqueues SGTD_REG_GROUP rounds
  * (search - match - linearise - trial; a pair in its trials skips the first three) and reads the number of unfinished
- * pairs once per group.  The search is brute force: n_source * n_target distances per pass, so thin raw scans first.
+ * pairs once per group.  The search is brute force: n_source * n_target distances per pass, so thin raw scans first
+ * (sgtd_thin_clouds below).
  * The call is a pure function of its arguments: independent of the pending batch, the table and the stored poses; it
  * uses buffers of its own on the handle's stream; a view runs it whatever state its owner is in; a multi-device handle
  * runs it on its first device.  The results last until the next sgtd_register_clouds call that passes its argument
@@ -1522,6 +1523,54 @@ int sgtd_result_stored_local_pairs(sgtd_handle h, int32_t *query, int32_t *cand,
                                    int64_t capacity, int64_t *n);
 int sgtd_result_stored_local_maps(sgtd_handle h, uint32_t *map_frame, int64_t *mem_off /* n_maps + 1 */, uint32_t *member,
                                   double *member_pose /*[members*12]*/, int64_t cap_maps, int64_t cap_members, int64_t *n_maps, int64_t *n_members);
+
+/* ---- voxel-grid thinning of raw clouds (thin_kernels.hip.h) ----
+ * What the node does to a scan with pcl's ApproximateVoxelGrid before GICP (semantic_graph_localization.cpp:357-358, 660),
+ * in the form of ingest.voxel_downsample, for a batch of clouds on the device.  The registration calls search by brute
+ * force: thin raw scans with this call first.  sgtd_thin_clouds is a pure function of its arguments.
+ *
+ * Input: n_clouds clouds back to back in points, stride_floats (3 or 4) floats a point, x y z first; with 4 the fourth
+ *   column is averaged like the others.  pt_off (n_clouds + 1 offsets, in points) is a host array; points is a host
+ *   array, or a device array with device_ptrs != 0 (not the view of an earlier call on the same handle: the call writes
+ *   there).  leaf: one per call, f64, finite and > 0.
+ * Per point: dropped when x, y or z is not finite.  Else its cell is c[a] = floor((double)p[a] / leaf) per axis: one f64
+ *   division, rounded once, then floor (-0.0 lies in cell 0).  A finite point with some c[a] outside
+ *   [-SGTD_THIN_MAX_CELL, SGTD_THIN_MAX_CELL) is dropped too (a departure: ingest.voxel_downsample has no such bound;
+ *   the two agree wherever no point is out of range).  Both kinds of drop are counted per cloud.
+ * Per occupied cell of a cloud: one output point.  Column a = (float)(s_a / (double)count), where s_a starts at +0.0 and
+ *   adds (double)p_i[a] over the cell's points in ascending point index: ONE sequential f64 sum, every addition rounded
+ *   once — what np.bincount(weights=) does, and so ingest.voxel_downsample's bits — not the 256-accumulator SUM of the
+ *   other stages.  A cell may hold a whole cloud: one lane walks it, which gives the same bits and is slow (the
+ *   additions of one cell are never spread over lanes: that would be a tree).
+ * Order: a cloud's cells in ascending order of their smallest point index; the clouds in order, cloud s at
+ *   out_off[s] .. out_off[s + 1].  Cells of different clouds never merge, and no result of a cloud depends on the other
+ *   clouds of the call or on how the work is tiled.
+ * On the device: a key per point (cloud; cx, cy, cz offset to unsigned 21 bits each), two stable radix sorts (the 63
+ *   cell bits, then the cloud; dropped points last), head flags and scans for the cells, a lane per cell for the sums.
+ *   No floating-point atomic; the one integer atomic adds the drop counts.  The host reads the output size back once.
+ *
+ * The call uses buffers of its own on the handle's stream; a view (sgtd_attach_table) runs it whatever state its owner
+ * is in; a multi-device handle runs it on its first device.  Results last until the next sgtd_thin_clouds call that
+ * passes its checks, or sgtd_destroy.  n_clouds == 0 is a valid run with empty results.  sgtd_thinned_device_view hands
+ * out the borrowed device pointer of the output (f32 [n_points * stride_floats]): with the host's out_off it is what
+ * sgtd_set_frame_clouds, sgtd_register_clouds, sgtd_register_stored, sgtd_register_stored_loops, sgtd_register_voxels,
+ * sgtd_register_stored_voxels and sgtd_register_stored_local_loops take with device_ptrs = 1, and it stays valid across
+ * those calls: none of them touches the thin buffers.  A thinned cloud may hold more than SGTD_REG_MAX_POINTS points;
+ * the registration call that receives it rejects it.  sgtd_thin_stage_ms: device milliseconds of the last call's two
+ * sorts, of the rest, of the whole call (zeros unless sgtd_set_timing).
+ *
+ * Errors, before the device is touched and with the earlier results kept: h == NULL, a negative count, a NULL array with
+ * a positive count, stride_floats neither 3 nor 4, pt_off[0] != 0 or offsets that decrease, leaf NaN, infinite or <= 0:
+ * SGTD_ERR_INVALID.  More than SGTD_REG_MAX_CLOUDS clouds or SGTD_SCAN_MAX_POINTS points in all: SGTD_ERR_UNSUPPORTED.
+ * The getters before a successful run: SGTD_ERR_STATE; more than capacity: SGTD_ERR_CAPACITY (*n = the size needed, the
+ * first `capacity` points written).  Any output may be NULL. */
+#define SGTD_THIN_MAX_CELL (1 << 20)   /* +-10 km at a 1 cm leaf */
+int sgtd_thin_clouds(sgtd_handle h, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds,
+                     double leaf, int device_ptrs);
+int sgtd_result_thinned(sgtd_handle h, int64_t *out_off /* n_clouds + 1 */, float *points /* [cap*stride] */,
+                        int32_t *n_dropped /* [n_clouds*2]: non-finite, out of range */, int64_t capacity, int64_t *n);
+int sgtd_thinned_device_view(sgtd_handle h, const float **d_points, int *stride_floats, int64_t *n_points);
+int sgtd_thin_stage_ms(sgtd_handle h, float *ms_sort, float *ms_rest, float *ms_total);
 
 /* Page-locked host memory for the destination buffers of the fetch calls (sgtd_fetch_entries,
  * sgtd_result_pairs, ...): a copy into it is one direct DMA transfer — pageable memory goes through the

@@ -52,6 +52,7 @@ SYMBOLS = [
     "sgtd_stored_register_stage_ms", "sgtd_register_stored_loops", "sgtd_result_stored_pairs",
     "sgtd_register_stored_voxels", "sgtd_result_stored_voxel_registered", "sgtd_result_stored_voxel_map", "sgtd_result_stored_voxel_matches",
     "sgtd_stored_voxel_register_stage_ms", "sgtd_register_stored_local_loops", "sgtd_result_stored_local_pairs", "sgtd_result_stored_local_maps",
+    "sgtd_thin_clouds", "sgtd_result_thinned", "sgtd_thinned_device_view", "sgtd_thin_stage_ms",
 ]
 
 
@@ -292,6 +293,10 @@ def lib():
     L.sgtd_register_stored_local_loops.argtypes = [vp, C.POINTER(VoxelRegisterOptions), vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
     L.sgtd_result_stored_local_pairs.argtypes = [vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.sgtd_result_stored_local_maps.argtypes = [vp, vp, vp, vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.sgtd_thin_clouds.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int]
+    L.sgtd_result_thinned.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.sgtd_thinned_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(i64)]
+    L.sgtd_thin_stage_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 3
     L.sgtd_query_frames.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.sgtd_loop_frames.argtypes = [vp, vp, vp, vp, C.c_int, i32, C.c_int]
     L.sgtd_query_descs.argtypes = [vp, C.POINTER(DescSoa), i64]

@@ -41,6 +41,7 @@
 #include "consensus_kernels.hip.h"
 #include "scan_kernels.hip.h"
 #include "local_map_kernels.hip.h"
+#include "thin_kernels.hip.h"
 #include "graph_ingest.hip.h"
 #include "table_file.h"
 
@@ -436,6 +437,18 @@ struct sgtd_engine {
   int64_t lm_kept = 0;
   std::vector<int64_t> lm_kp_off, lm_mem_off, lm_merged;
   LapClock lm_clock;
+  // sgtd_thin_clouds (thin_kernels.hip.h): independent of everything else on the handle, buffers of its own (TH_*:
+  // thin_run; no other call touches them, so TH_OUT, the device view, stays valid across the registration calls).
+  // th_n < 0: no results; th_stride / th_kept: floats a point and points of TH_OUT; th_out_off / th_dropped: per cloud,
+  // on the host; th_clock.ms: the sorts, the whole call (filled under sgtd_set_timing)
+  enum { TH_PTS = 0, TH_OFF, TH_KEY_PT, TH_CL_PT, TH_KEY_A, TH_KEY_B, TH_CKEY_A, TH_CKEY_B, TH_VAL_A, TH_VAL_B, TH_FLAGS, TH_EXCL, TH_FIRST, TH_FIRST_EXCL,
+         TH_COUNTS, TH_CSTART, TH_DROPPED, TH_OUT_OFF, TH_OUT, TH_BUFS };
+  DevBuf th[TH_BUFS];
+  int th_n = -1, th_stride = 3;
+  int64_t th_kept = 0;
+  std::vector<int64_t> th_out_off;
+  std::vector<int32_t> th_dropped;
+  LapClock th_clock;
   // ---- multi-GPU step (exchange_kernels.hip.h): the batch's local candidate tables are written, packed, into a caller
   // device buffer as soon as they are final (behind votes_topk_kernel / topk_kernel) and ev_cand is recorded; a side
   // stream waits for it (sgtd_export_wait), all-gathers and merges while the match lists are written, and records
@@ -2344,6 +2357,8 @@ int sgtd_destroy(sgtd_handle e) {
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
   e->lm_clock.destroy();
+  for (DevBuf &b : e->th) free_buf(b);
+  e->th_clock.destroy();
   for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
@@ -7159,6 +7174,158 @@ int sgtd_local_map_stage_ms(sgtd_handle e, float *ms_members, float *ms_gather, 
   if (ms_members) *ms_members = c->lm_clock.ms[0];
   if (ms_gather) *ms_gather = c->lm_clock.ms[1];
   if (ms_scan) *ms_scan = c->lm_clock.ms[2];
+  return SGTD_OK;
+}
+
+}  // extern "C"
+
+// ---- sgtd_thin_clouds: voxel-grid thinning of raw clouds on the device (thin_kernels.hip.h) ----
+namespace {
+
+int thin_run(sgtd_engine *e, const float *points, int stride, const int64_t *pt_off, int S, double leaf, int device_ptrs) {
+  const long long P = pt_off[S];
+  const size_t np = (size_t)P;
+  auto buf = [&](int k, size_t bytes) { return ensure(e, e->th[k], std::max<size_t>(bytes, 16)); };
+  auto *B = e->th;
+  const hipStream_t st = e->stream;
+  const bool timed = e->timing;
+  LapClock &clock = e->th_clock;      // (ms: the two sorts, the whole call)
+  CHK(clock.start(e, timed));
+  e->th_out_off.assign((size_t)S + 1, 0);
+  e->th_dropped.assign((size_t)S * 2, 0);
+  e->th_stride = stride; e->th_kept = 0;
+  CHK(buf(sgtd_engine::TH_OUT, 16));
+  if (S == 0 || P == 0) return xfer_sync(e);
+
+  const float *d_pts = nullptr;
+  CHK(points_on_device(e, B[sgtd_engine::TH_PTS], points, np * stride, device_ptrs, &d_pts));
+  CHK(buf(sgtd_engine::TH_OFF, ((size_t)S + 1) * sizeof(long long)));
+  CHK(h2d(e, B[sgtd_engine::TH_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(buf(sgtd_engine::TH_KEY_PT, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::TH_CL_PT, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_KEY_A, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::TH_KEY_B, np * sizeof(u64)));
+  CHK(buf(sgtd_engine::TH_CKEY_A, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_CKEY_B, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_VAL_A, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_VAL_B, np * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_FLAGS, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_EXCL, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_FIRST, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_FIRST_EXCL, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_COUNTS, 4 * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_CSTART, (np + 1) * sizeof(u32)));
+  CHK(buf(sgtd_engine::TH_DROPPED, (size_t)S * 2 * sizeof(int)));
+  CHK(buf(sgtd_engine::TH_OUT_OFF, ((size_t)S + 1) * sizeof(long long)));
+  const int gp = grid_for(P, 256);
+  const long long *d_off = B[sgtd_engine::TH_OFF].as<long long>();
+  u64 *key_pt = B[sgtd_engine::TH_KEY_PT].as<u64>();
+  u32 *cl_pt = B[sgtd_engine::TH_CL_PT].as<u32>();
+  u64 *kin = B[sgtd_engine::TH_KEY_A].as<u64>(), *kout = B[sgtd_engine::TH_KEY_B].as<u64>();
+  u32 *ckin = B[sgtd_engine::TH_CKEY_A].as<u32>(), *ckout = B[sgtd_engine::TH_CKEY_B].as<u32>();
+  u32 *vin = B[sgtd_engine::TH_VAL_A].as<u32>(), *vout = B[sgtd_engine::TH_VAL_B].as<u32>();
+  u32 *flags = B[sgtd_engine::TH_FLAGS].as<u32>(), *excl = B[sgtd_engine::TH_EXCL].as<u32>();
+  u32 *first = B[sgtd_engine::TH_FIRST].as<u32>(), *first_excl = B[sgtd_engine::TH_FIRST_EXCL].as<u32>();
+  u32 *counts = B[sgtd_engine::TH_COUNTS].as<u32>(), *cstart = B[sgtd_engine::TH_CSTART].as<u32>();
+  int *dropped = B[sgtd_engine::TH_DROPPED].as<int>();
+  long long *d_out_off = B[sgtd_engine::TH_OUT_OFF].as<long long>();
+
+  // keys, the two sorts
+  if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
+  HIPCHK(hipMemsetAsync(dropped, 0, (size_t)S * 2 * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(u32), st));
+  HIPCHK(hipMemsetAsync(first, 0, (np + 1) * sizeof(u32), st));
+  thin_keys_kernel<<<gp, 256, 0, st>>>(d_pts, stride, d_off, S, P, leaf, key_pt, cl_pt, kin, vin, dropped);
+  HIPCHK(hipGetLastError());
+  if (timed) HIPCHK(hipEventRecord(clock.ev[1], st));
+  CHK(radix_sort_pairs<u64>(e, kin, kout, vin, vout, P, 3 * SGTD_THIN_CELL_BITS, false));
+  thin_cloud_keys_kernel<<<gp, 256, 0, st>>>(vin, cl_pt, P, ckin);
+  HIPCHK(hipGetLastError());
+  CHK(radix_sort_pairs<u32>(e, ckin, ckout, vin, vout, P, key_bits((u64)S), false));
+  if (timed) HIPCHK(hipEventRecord(clock.ev[2], st));
+
+  // cells in key order, their places by smallest point index, the clouds' offsets
+  thin_heads_kernel<<<grid_for(P + 1, 256), 256, 0, st>>>(vin, key_pt, cl_pt, P, (u32)S, flags, first, counts);
+  HIPCHK(hipGetLastError());
+  CHK(device_scan(e, flags, excl, P + 1));
+  CHK(device_scan(e, first, first_excl, P + 1));
+  thin_cells_kernel<<<gp, 256, 0, st>>>(flags, excl, P, counts, cstart);
+  thin_offsets_kernel<<<grid_for(S + 1, 256), 256, 0, st>>>(first_excl, d_off, S, d_out_off);
+  HIPCHK(hipGetLastError());
+  CHK(d2h(e, e->th_out_off.data(), d_out_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(d2h(e, e->th_dropped.data(), dropped, (size_t)S * 2 * sizeof(int)));
+  CHK(xfer_sync(e));
+  if (timed) CHK(clock.span(e, 1, 2, 0, true));
+  const long long K = e->th_out_off[(size_t)S];
+  e->th_kept = K;
+
+  // the sums
+  CHK(buf(sgtd_engine::TH_OUT, (size_t)std::max<long long>(K, 1) * stride * sizeof(float)));
+  if (K > 0) {
+    float *out = B[sgtd_engine::TH_OUT].as<float>();
+    if (stride == 3) thin_sum_kernel<3><<<grid_for(K, 256), 256, 0, st>>>(d_pts, vin, cstart, first_excl, excl + P, out);
+    else thin_sum_kernel<4><<<grid_for(K, 256), 256, 0, st>>>(d_pts, vin, cstart, first_excl, excl + P, out);
+    HIPCHK(hipGetLastError());
+  }
+  if (timed) {
+    HIPCHK(hipEventRecord(clock.ev[1], st));
+    CHK(clock.span(e, 0, 1, 1, true));
+  }
+  // (the caller's array is read for the last time by the sums: the call returns when they are done)
+  return xfer_sync(e);
+}
+
+const char kNoThin[] = "no thinned clouds: sgtd_thin_clouds has not run";
+
+}  // namespace
+
+extern "C" {
+
+int sgtd_thin_clouds(sgtd_handle e, const float *points, int stride_floats, const int64_t *pt_off, int n_clouds, double leaf, int device_ptrs) {
+  if (!e) return SGTD_ERR_INVALID;
+  if (!cloud_set_ok(pt_off, n_clouds, stride_floats, points, false, nullptr)) return SGTD_ERR_INVALID;
+  if (!(std::isfinite(leaf) && leaf > 0.0)) return SGTD_ERR_INVALID;
+  if (n_clouds > SGTD_REG_MAX_CLOUDS || pt_off[n_clouds] > SGTD_SCAN_MAX_POINTS) {
+    e->err = "sgtd_thin_clouds takes at most " + std::to_string(SGTD_REG_MAX_CLOUDS) + " clouds and " + std::to_string(SGTD_SCAN_MAX_POINTS) +
+             " points in one call";
+    return SGTD_ERR_UNSUPPORTED;
+  }
+  StageRun<int> run(e, &sgtd_engine::th_n);
+  run.on_device([&](sgtd_engine *k) { return thin_run(k, points, stride_floats, pt_off, n_clouds, leaf, device_ptrs); });
+  return run.end(n_clouds);
+}
+
+int sgtd_result_thinned(sgtd_handle e, int64_t *out_off, float *points, int32_t *n_dropped, int64_t capacity, int64_t *n) {
+  if (!e || capacity < 0) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::th_n, kNoThin, &c));
+  const int64_t K = c->th_kept;
+  if (n) *n = K;
+  if (out_off) std::memcpy(out_off, c->th_out_off.data(), c->th_out_off.size() * sizeof(int64_t));
+  if (n_dropped && !c->th_dropped.empty()) std::memcpy(n_dropped, c->th_dropped.data(), c->th_dropped.size() * sizeof(int32_t));
+  CopyOut out(e, c);
+  out.get(points, c->th[sgtd_engine::TH_OUT].p, (size_t)std::min(K, capacity) * c->th_stride * sizeof(float));
+  CHK(out.finish());
+  return K > capacity && points ? SGTD_ERR_CAPACITY : SGTD_OK;
+}
+
+int sgtd_thinned_device_view(sgtd_handle e, const float **d_points, int *stride_floats, int64_t *n_points) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::th_n, kNoThin, &c));
+  if (d_points) *d_points = c->th[sgtd_engine::TH_OUT].as<float>();
+  if (stride_floats) *stride_floats = c->th_stride;
+  if (n_points) *n_points = c->th_kept;
+  return SGTD_OK;
+}
+
+int sgtd_thin_stage_ms(sgtd_handle e, float *ms_sort, float *ms_rest, float *ms_total) {
+  if (!e) return SGTD_ERR_INVALID;
+  sgtd_engine *c = nullptr;
+  CHK(stage_ready(e, &sgtd_engine::th_n, kNoThin, &c));
+  if (ms_sort) *ms_sort = c->th_clock.ms[0];
+  if (ms_rest) *ms_rest = c->th_clock.ms[1] - c->th_clock.ms[0];
+  if (ms_total) *ms_total = c->th_clock.ms[1];
   return SGTD_OK;
 }
 

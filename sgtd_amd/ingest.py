@@ -146,7 +146,8 @@ def voxel_downsample(points, leaf):
     comes out is the centroid of the cell's points (f64 mean of every column, rounded to f32), and the cells come out in
     the order of their smallest point index.  points: (n, 3 or 4) f32; rows with a non-finite coordinate are dropped.
     The node thins the query scan with pcl's ApproximateVoxelGrid (semantic_graph_localization.cpp:660) before GICP;
-    STDescManager.register_clouds searches by brute force and needs the same thinning."""
+    STDescManager.register_clouds searches by brute force and needs the same thinning.  On the device, with the same bits:
+    STDescManager.thin_clouds (sgtd_thin_clouds)."""
     p = np.asarray(points, np.float32)
     if p.ndim != 2 or p.shape[1] not in (3, 4):
         raise ValueError("points: (n, 3 or 4)")

@@ -226,6 +226,27 @@ class BatchResult:
         return np.where(self.n_cand > 0, self.cand_frame[:, 0], -1)
 
 
+class DevicePoints:
+    """borrowed device memory of the library holding (count, stride) f32 points, in the form the manager's
+    device-pointer paths take a torch.cuda tensor: thin_clouds(fetch=False) returns one.  Valid until the manager's next
+    thin_clouds call (or one of the leaf= forms, or set_frame_scans) or close()."""
+    is_cuda = True
+    ndim = 2
+
+    def __init__(self, ptr, stride, count):
+        self.ptr, self.stride, self.count = int(ptr or 0), int(stride), int(count)
+        self.shape = (self.count, self.stride)
+
+    def data_ptr(self):
+        return self.ptr
+
+    def is_contiguous(self):
+        return True
+
+    def __len__(self):
+        return self.count
+
+
 class STDescManager:
     def __init__(self, **kw):
         """devices=[ids]: one handle over several GPUs of this process (sgtd_create_multi: the
@@ -1600,6 +1621,92 @@ class STDescManager:
             raise ValueError("pt_off: from 0, not decreasing, within the points given")
         self._check(self._L.sgtd_set_frame_clouds(self._h, _p(ids), _p(off), pp, int(shape[1]), ids.size, int(k_neighbors), float(plane_eps), dev))
 
+    # ---- voxel-grid thinning of raw clouds on the device (sgtd_thin_clouds) -------------------------------------
+    def _thin_args(self, points, pt_off, leaf, what="points", per_query=False):
+        """thin_clouds' arguments, checked before the library is called -> (pointer, stride, offsets, device_ptrs)"""
+        if isinstance(leaf, bool) or not isinstance(leaf, (int, float, np.integer, np.floating)) or not (np.isfinite(leaf) and leaf > 0):
+            raise ValueError("leaf: finite and > 0")
+        if hasattr(points, "data_ptr"):
+            if not (points.is_cuda and points.is_contiguous()):
+                raise ValueError(what + ": a contiguous torch.cuda tensor")
+            shape, pp, dev = tuple(points.shape), C.c_void_p(points.data_ptr()), 1
+        else:
+            points = np.ascontiguousarray(points, dtype=np.float32)
+            shape, pp, dev = points.shape, _p(points), 0
+        self._keep = points
+        if len(shape) not in (2, 3) or shape[-1] not in (3, 4) or (len(shape) == 3 and pt_off is not None):
+            raise ValueError(what + ": (total, 3 or 4), or (S, N, 3 or 4) without offsets")
+        total = int(np.prod(shape[:-1]))
+        if pt_off is None:
+            off = np.arange(shape[0] + 1, dtype=np.int64) * shape[1] if len(shape) == 3 else np.array([0, total], np.int64)
+        else:
+            off = np.ascontiguousarray(np.asarray(pt_off).reshape(-1), np.int64)
+        if per_query and off.size != self._nq + 1:
+            raise ValueError("pt_off: n_queries + 1 offsets")
+        if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] > total:
+            raise ValueError("pt_off: n_clouds + 1 offsets from 0, not decreasing, within the points given")
+        return pp, int(shape[-1]), off, dev
+
+    def thin_clouds(self, points, pt_off=None, leaf=0.25, fetch=True):
+        """sgtd_thin_clouds: ingest.voxel_downsample of a batch of clouds on the device, bit for bit (but points whose cell
+        lies outside +-2^20 cells are dropped and counted).  points: (total, 3 or 4) f32 with the n_clouds + 1 offsets
+        pt_off (None: one cloud), or (S, N, 3 or 4) without offsets; numpy or a torch.cuda tensor.  -> dict of points
+        (n, 3 or 4) f32, pt_off (n_clouds + 1,) i64 and n_dropped (n_clouds, 2) i32: non-finite, out of range.  fetch=False
+        leaves the points on the device: the dict holds pt_off and points as a DevicePoints (pointer, stride, count), which
+        set_frame_clouds((points, pt_off)) and the register calls take like a torch.cuda tensor."""
+        pp, stride, off, dev = self._thin_args(points, pt_off, leaf)
+        self._check(self._L.sgtd_thin_clouds(self._h, pp, stride, _p(off), off.size - 1, float(leaf), dev))
+        self._thin_n = off.size - 1      # (after the call: one that is refused leaves the earlier results, and their count)
+        return self.thin_results(fetch)
+
+    def thin_results(self, fetch=True):
+        """the results of the last thin_clouds call, as it returns them"""
+        out_off, n = np.zeros(self._thin_n + 1, np.int64), C.c_int64(0)
+        if not fetch:
+            ptr, stride = C.c_void_p(), C.c_int(0)
+            self._check(self._L.sgtd_thinned_device_view(self._h, C.byref(ptr), C.byref(stride), C.byref(n)))
+            self._check(self._L.sgtd_result_thinned(self._h, _p(out_off), None, None, 0, None))
+            return {"points": DevicePoints(ptr.value, stride.value, n.value), "pt_off": out_off}
+        stride = C.c_int(0)
+        self._check(self._L.sgtd_thinned_device_view(self._h, None, C.byref(stride), C.byref(n)))
+        pts, dropped = np.zeros((n.value, stride.value), np.float32), np.zeros((self._thin_n, 2), np.int32)
+        self._check(self._L.sgtd_result_thinned(self._h, _p(out_off), _p(pts), _p(dropped), n.value, C.byref(n)))
+        return {"points": pts, "pt_off": out_off, "n_dropped": dropped}
+
+    def thin_stage_ms(self):
+        """device milliseconds of the last thin_clouds call: the sorts, the rest, the whole call (zeros unless
+        set_timing(True))"""
+        return self._stage_ms(self._L.sgtd_thin_stage_ms, 3)
+
+    def _thin_first(self, points, pt_off, leaf, what, per_query=False):
+        """the leaf= forms: the call's clouds thinned on the device -> (points, pt_off) as the register calls take them"""
+        pp, stride, off, dev = self._thin_args(points, pt_off, leaf, what, per_query)
+        self._check(self._L.sgtd_thin_clouds(self._h, pp, stride, _p(off), off.size - 1, float(leaf), dev))
+        self._thin_n = off.size - 1
+        view = self.thin_results(fetch=False)
+        return view["points"], view["pt_off"]
+
+    def set_frame_scans(self, frames, scans, leaf, k_neighbors=20, plane_eps=1e-3):
+        """thin_clouds, then set_frame_clouds on the thinned clouds where they lie on the device: no point crosses back.
+        frames: the frame ids; scans: the raw scans as set_frame_clouds takes clouds (a list of (n, 3 or 4) f32 arrays, or
+        (points, pt_off)); leaf: the voxel size.  Returns the thinned clouds' offsets."""
+        ids = self._frame_ids(frames)
+        if isinstance(scans, tuple) and len(scans) == 2 and not isinstance(scans[0], (list, tuple)) and np.ndim(scans[1]) == 1 \
+                and getattr(scans[0], "ndim", 0) == 2:
+            points, off = scans
+        else:
+            arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in scans]
+            strides = {a.shape[1] for a in arrs if a.ndim == 2}
+            if any(a.ndim != 2 for a in arrs) or len(strides) != 1 or not strides <= {3, 4}:
+                raise ValueError("scans: (n, 3) or (n, 4) arrays of one width")
+            off = np.concatenate([[0], np.cumsum([a.shape[0] for a in arrs])]).astype(np.int64)
+            points = np.concatenate(arrs)
+        if np.size(off) != ids.size + 1:
+            raise ValueError("scans: one scan (len(frames) + 1 offsets) per frame id")
+        d_points, out_off = self._thin_first(points, off, leaf, "scans")
+        self.set_frame_clouds(ids, (d_points, out_off), k_neighbors, plane_eps)
+        return out_off
+
     def frame_clouds_info(self):
         """-> dict of n_frames, n_points (live), device_bytes (the arena's arrays), k_neighbors and plane_eps (0 while the
         store has no settings)"""
@@ -1617,11 +1724,14 @@ class STDescManager:
         self._check(self._L.sgtd_result_frame_cloud(self._h, int(frame), _p(xyz), _p(cov), n.value, C.byref(n)))
         return xyz, cov
 
-    def register_stored(self, points, pt_off, src, tgt_frame, init=None, **options):
+    def register_stored(self, points, pt_off, src, tgt_frame, init=None, leaf=None, **options):
         """sgtd_register_stored: register_clouds with the targets read from the cloud store.  points, pt_off: the call's
         clouds as register_clouds takes them; src: (n,) cloud indices; tgt_frame: (n,) frame ids that have a stored cloud;
         init, options and the returned dict as register_clouds'.  The results are register_clouds' on the call's clouds
-        followed by the frames' stored clouds, bit for bit."""
+        followed by the frames' stored clouds, bit for bit.  leaf: a number thins the call's clouds on the device first
+        (thin_clouds) and registers them from there; None takes them as they are."""
+        if leaf is not None:
+            points, pt_off = self._thin_first(points, pt_off, leaf, "points")
         shape, pp, dev = self._points_arg(points)
         off = self._offsets(pt_off, shape)
         s, t, p0, n = self._pairs_arg(src, tgt_frame, init, "src and tgt_frame: one cloud index and one frame id per pair", tgt_ids=True)
@@ -1633,12 +1743,15 @@ class STDescManager:
     def result_stored_registered(self):
         return self._rows_dict(self._L.sgtd_result_stored_registered, self._stored_n, False)
 
-    def register_loops_stored(self, query_points, query_pt_off, max_per_query=5, start="verify", **options):
+    def register_loops_stored(self, query_points, query_pt_off, max_per_query=5, start="verify", leaf=None, **options):
         """sgtd_register_stored_loops, after verify(): register_loops with the map clouds read from the cloud store and the
         pairs formed on the device (register_pairs' rule; a candidate whose frame has no stored cloud is dropped).
         query_points: (total, 3 or 4) f32, numpy or a torch.cuda tensor, with the n_queries + 1 offsets query_pt_off.
+        leaf: a number thins the query clouds on the device first (thin_clouds); None takes them as they are.
         -> register_loops' dict: query, cand, frame [m] (int32), init [m, 12] and register_clouds' fields per pair"""
         code = self._loops_args(start, max_per_query)
+        if leaf is not None:
+            query_points, query_pt_off = self._thin_first(query_points, query_pt_off, leaf, "query_points", per_query=True)
         shape, pp, dev = self._points_arg(query_points, "query_points")
         qoff = self._offsets(query_pt_off, shape, "query_pt_off", per_query=True)
         opt = self._options(RegisterOptions, self._L.sgtd_default_register_options, options)
@@ -1702,12 +1815,15 @@ class STDescManager:
         return self._stage_ms(self._L.sgtd_voxel_register_stage_ms, 5)
 
     # ---- voxel maps whose members are stored clouds (sgtd_register_stored_voxels) -------------------------------
-    def register_stored_voxels(self, points, pt_off, map_off, map_frame, map_pose, src, tgt_map, init=None, **options):
+    def register_stored_voxels(self, points, pt_off, map_off, map_frame, map_pose, src, tgt_map, init=None, leaf=None, **options):
         """sgtd_register_stored_voxels: register_voxels with the maps' members read from the cloud store.  points,
         pt_off: the call's clouds (the sources), numpy or a torch.cuda tensor; map m has the members
         map_frame[map_off[m]:map_off[m + 1]], frame ids that have a stored cloud (set_frame_clouds); map_pose, src,
         tgt_map, init, options and the returned dict as register_voxels'.  The results are register_voxels' on the call's
-        clouds followed by the members' stored clouds, bit for bit; k_neighbors and plane_eps must be the store's."""
+        clouds followed by the members' stored clouds, bit for bit; k_neighbors and plane_eps must be the store's.
+        leaf: a number thins the call's clouds on the device first (thin_clouds); None takes them as they are."""
+        if leaf is not None:
+            points, pt_off = self._thin_first(points, pt_off, leaf, "points")
         shape, pp, dev = self._points_arg(points)
         off = self._offsets(pt_off, shape)
         moff, mfr, mp = self._maps_arg(map_off, map_frame, map_pose, frame_ids=True)
@@ -1730,7 +1846,8 @@ class STDescManager:
         """the correspondences of one pair of the last register_stored_voxels call, as voxel_matches()"""
         return self._sized(self._L.sgtd_result_stored_voxel_matches, (int(pair),), (((), np.int32),))[0]
 
-    def register_loops_local_stored(self, query_points, query_pt_off, radius=15.0, max_members=0, max_per_query=5, start="verify", **options):
+    def register_loops_local_stored(self, query_points, query_pt_off, radius=15.0, max_members=0, max_per_query=5, start="verify", leaf=None,
+                                    **options):
         """sgtd_register_stored_local_loops, after verify(): register_loops_local with the map clouds read from the cloud
         store (set_frame_clouds), the frames' poses from set_frame_poses, and the pairs, the local maps and the members'
         relative poses formed on the device.  A candidate whose frame has no stored cloud, no stored pose or a pose that
@@ -1738,8 +1855,11 @@ class STDescManager:
         the smaller id), not voxel_map_members' first m in id order.  query_points: (total, 3 or 4) f32, numpy or a
         torch.cuda tensor, with the n_queries + 1 offsets query_pt_off.  -> register_loops_local's dict: query, cand, frame,
         tgt_map [m] (int32), init [m, 12], register_voxels' fields per pair, map_frames, members (per map, the member frame
-        ids), map_off, map_frame, map_pose as register_stored_voxels takes them"""
+        ids), map_off, map_frame, map_pose as register_stored_voxels takes them.  leaf: a number thins the query clouds on
+        the device first (thin_clouds); None takes them as they are."""
         code = self._loops_args(start, max_per_query, max_members, radius)
+        if leaf is not None:
+            query_points, query_pt_off = self._thin_first(query_points, query_pt_off, leaf, "query_points", per_query=True)
         shape, pp, dev = self._points_arg(query_points, "query_points")
         qoff = self._offsets(query_pt_off, shape, "query_pt_off", per_query=True)
         opt = self._options(VoxelRegisterOptions, self._L.sgtd_default_voxel_register_options, options)
