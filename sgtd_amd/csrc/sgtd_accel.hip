@@ -47,11 +47,38 @@
 
 namespace {
 
+// A device array and its owner: freed with whatever holds it (the handle's device is current whenever one goes: sgtd_destroy
+// selects it, every other place is inside a call that did).  Move-only; the moved-from buffer is empty.
 struct DevBuf {
   void *p = nullptr;
   size_t bytes = 0;
   bool borrowed = false;     // the memory belongs to another handle (sgtd_attach_table): never freed or regrown here
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes), borrowed(o.borrowed) { o.p = nullptr; o.bytes = 0; o.borrowed = false; }
+  DevBuf &operator=(DevBuf &&o) noexcept {      // (this buffer's own memory goes; hipFree waits for the kernels that use it)
+    if (this != &o) {
+      if (p && !borrowed) (void)hipFree(p);
+      p = o.p; bytes = o.bytes; borrowed = o.borrowed;
+      o.p = nullptr; o.bytes = 0; o.borrowed = false;
+    }
+    return *this;
+  }
+  ~DevBuf() { if (p && !borrowed) (void)hipFree(p); }
+  // the other handle's array in place of this buffer's own
+  void borrow_from(const DevBuf &src) {
+    *this = DevBuf();
+    p = src.p; bytes = src.bytes; borrowed = true;
+  }
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// A device array of T.  need() (below) is where one is sized: in elements, so the size and the pointer's type cannot disagree.
+template <class T>
+struct DevArr {
+  DevBuf buf;
+  T *p() const { return buf.as<T>(); }
 };
 
 struct DescStore {
@@ -148,6 +175,10 @@ struct SelectPlan {
 struct LapClock {
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  LapClock() = default;
+  LapClock(const LapClock &) = delete;
+  LapClock &operator=(const LapClock &) = delete;
+  ~LapClock() { destroy(); }
   int start(sgtd_engine *e, bool timed);                       // a call begins: no milliseconds yet, the events exist if it is timed
   int lap(sgtd_engine *e, int kind);                           // ms[kind] += the work since ev[0] (waited for); ev[0] is recorded anew
   int span(sgtd_engine *e, int a, int b, int kind, bool wait); // ms[kind] += the time from ev[a] to ev[b], recorded both (wait: ev[b] is waited for)
@@ -346,10 +377,13 @@ struct sgtd_engine {
   // A dense GICP run (register_kernels.hip.h): independent of the batch.  in: the call's index arrays, offsets and start
   // poses; pts: the points when the host gave them; cov: a covariance per point of the call's clouds; part: the slices'
   // minima; match: the last pass's matches and M_i; state: RegState per pair; out: the result rows; ctl: the count of
-  // unfinished pairs.  n < 0: no results; host_*: what the getters need of the call; clock.ms: covariances, searches,
-  // the rest, the whole call (filled under sgtd_set_timing)
+  // unfinished pairs (in, part, match, out: packed, several types each).  n < 0: no results; host_*: what the getters
+  // need of the call; clock.ms: covariances, searches, the rest, the whole call (filled under sgtd_set_timing)
   struct DenseRun {
-    DevBuf in, pts, cov, part, match, state, out, ctl;
+    DevBuf in;
+    DevArr<float> pts;
+    DevArr<double> cov;
+    DevBuf part, match, state, out, ctl;
     int n = -1;
     std::vector<int64_t> host_off;
     std::vector<int> host_soff;         // src_off [n + 1]
@@ -385,16 +419,29 @@ struct sgtd_engine {
   bool sr_loops = false;
   std::vector<int32_t> sr_rows;
   size_t sr_init_off = 0;            // the rows' start poses within sr_pairs
-  // A voxelised GICP run (voxel_register_kernels.hip.h): independent of the batch.  VR_IN: the call's index arrays,
-  // offsets and poses; VR_PTS: the points when the host gave them; VR_COV: a covariance per point; VR_KEY_* / VR_VAL_*:
-  // the sort's pairs; VR_FLAGS .. VR_MAP_VOX: the voxels' heads, keys, first points and the maps' ranges; VR_MEAN /
-  // VR_VCOV: the Gaussians; VR_VID / VR_MW: the per-correspondence streams; VR_STATE, VR_OUT, VR_CTL as DenseRun's.
-  // n < 0: no results; mode: the call's neighbor_mode; host_*: what the getters need of the call; clock.ms: covariances,
-  // map build, correspondence passes, the rest, the whole call (filled under sgtd_set_timing)
-  enum { VR_IN = 0, VR_PTS, VR_COV, VR_KEY_A, VR_KEY_B, VR_VAL_A, VR_VAL_B, VR_FLAGS, VR_EXCL, VR_COUNTS, VR_VKEY, VR_VSTART, VR_MAP_VOX, VR_MEAN, VR_VCOV,
-         VR_VID, VR_MW, VR_STATE, VR_OUT, VR_CTL, VR_BUFS };
+  // The runs of equal keys among sorted (key, value) pairs, as the stages that put points into voxels need them
+  // (sorted_runs): the sort's pairs, the runs' head flags and their exclusive scan (excl[n]: the count of runs), the
+  // counters of the head kernels, the runs' keys and first positions [runs + 1]
+  struct RunScratch {
+    DevArr<u64> key_a, key_b;
+    DevArr<u32> val_a, val_b, flags, excl, counts;
+    DevArr<u64> vkey;
+    DevArr<u32> vstart;
+  };
+  // A voxelised GICP run (voxel_register_kernels.hip.h): independent of the batch.  n < 0: no results; mode: the call's
+  // neighbor_mode; host_*: what the getters need of the call; clock.ms: covariances, map build, correspondence passes,
+  // the rest, the whole call (filled under sgtd_set_timing)
   struct VoxelRun {
-    DevBuf B[VR_BUFS];
+    DevArr<char> in;               // the call's index arrays, offsets and poses
+    DevArr<float> pts;             // the points when the host gave them
+    DevArr<double> cov;            // a covariance per point
+    RunScratch runs;               // the members' points by voxel: the voxels' heads, keys and first points
+    DevArr<u32> map_vox;           // the maps' ranges of voxels [n_maps + 1]
+    DevArr<double> mean, vcov;     // the voxels' Gaussians
+    DevArr<int> vid;               // the per-correspondence streams: the voxel,
+    DevArr<double> mw;             // ... its weight matrix
+    DevArr<RegState> state;        // as DenseRun's
+    DevArr<char> out, ctl;
     int n = -1, mode = 1;
     std::vector<int> host_soff;         // src_off [n + 1]
     std::vector<int> host_up;           // (the source of the index upload)
@@ -402,8 +449,8 @@ struct sgtd_engine {
     LapClock clock;
   };
   VoxelRun vox;        // sgtd_register_voxels: every cloud is the call's
-  // sgtd_register_stored_voxels: the same run over the cloud store's arena (VregSite).  VR_PTS: the call's points when
-  // the host gave them, before they are packed behind the slots; VR_COV: unused, the covariances are the arena's
+  // sgtd_register_stored_voxels: the same run over the cloud store's arena (VregSite).  pts: the call's points when
+  // the host gave them, before they are packed behind the slots; cov: unused, the covariances are the arena's
   VoxelRun svox;
   // sgtd_register_stored_local_loops (stored_local_kernels.hip.h): sv_form: the per-id streams, the rows and the per-map
   // records (StoredLocalParams); sv_members: the member lists, slots, sizes, point offsets and relative poses.  sv_local:
@@ -416,34 +463,75 @@ struct sgtd_engine {
   std::vector<u32> sv_map_frame;
   std::vector<int64_t> sv_mem_off;
   size_t sv_init_off = 0, sv_member_off = 0, sv_pose_off = 0;
-  // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (SK_*: scan_run).  sk_n < 0:
-  // no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets on the host
-  enum { SK_PTS = 0, SK_LAB, SK_OFF, SK_SC, SK_R, SK_PITCH, SK_AZI, SK_MM, SK_VOTE, SK_GRID, SK_RANGE, SK_BOUNDS, SK_KEY_A, SK_KEY_B, SK_VAL_A, SK_VAL_B,
-         SK_FLAGS, SK_EXCL, SK_COUNTS, SK_VKEY, SK_VSTART, SK_NBR, SK_NBR_CNT, SK_PARENT, SK_CHANGED, SK_CCOUNT, SK_CMIN, SK_CKEY_A, SK_CKEY_B, SK_CVAL_A,
-         SK_CVAL_B, SK_KP_OFF, SK_CL_OF_ROOT, SK_KCOUNT, SK_CSTART, SK_PKEY_A, SK_PKEY_B, SK_PVAL_A, SK_PVAL_B, SK_CLUSTER, SK_XYZ, SK_LABEL, SK_NPOINTS,
-         SK_BUFS };
-  DevBuf sk[SK_BUFS];
+  // sgtd_scan_keypoints (scan_kernels.hip.h): independent of the batch, buffers of its own (scan_run, scan_device).
+  // sk_n < 0: no results; sk_points / sk_kept: points and keypoints of the run; sk_off / sk_kp_off: the scans' offsets
+  // on the host
+  struct ScanBufs {
+    DevArr<float> pts;                        // the host's points and labels (scan_run's staging),
+    DevArr<u32> lab;
+    DevArr<long long> off;                    // ... the scans' offsets [S + 1]
+    DevArr<u32> sc;                           // per point: (scan, class), range, pitch, azimuth
+    DevArr<double> r, pitch, azi;
+    DevArr<u64> mm;                           // per (scan, class): the extrema, the votes, the grid's sizes, ranges and ring bounds
+    DevArr<u32> vote;
+    DevArr<int> grid;
+    DevArr<double> range, bounds;
+    RunScratch runs;                          // the points by voxel
+    DevArr<u32> nbr, nbr_cnt, parent;         // per voxel: its links and its component's root
+    DevArr<u32> changed;                      // per round of the components: did anything move
+    DevArr<u32> ccount, cmin;                 // per component: its points, its smallest point
+    DevArr<u64> ckey_a, ckey_b;               // the clusters' sort into keypoint order
+    DevArr<u32> cval_a, cval_b;
+    DevArr<long long> kp_off;                 // the scans' keypoint offsets [S + 1]
+    DevArr<u32> cl_of_root, kcount, cstart;   // root -> keypoint; per keypoint: its points, their first place
+    DevArr<u32> pkey_a, pkey_b, pval_a, pval_b;   // the points' sort by keypoint
+    DevArr<int> cluster;                      // per point: its keypoint or -1
+    DevArr<float> xyz;                        // the keypoints: centres, labels, point counts
+    DevArr<u32> label;
+    DevArr<int> npoints;
+  } sk;
   int sk_n = -1;
   int64_t sk_points = 0, sk_kept = 0;
   std::vector<int64_t> sk_off, sk_kp_off;
-  // sgtd_local_map_keypoints (local_map_kernels.hip.h): the member lists, the pass's segments and merged cloud, and the
-  // appended keypoints of all passes (LM_XYZ / LM_LABEL / LM_NPOINTS); the clustering runs in the sk buffers above.
-  // lm_n < 0: no results; lm_kp_off / lm_mem_off / lm_merged: per anchor, on the host; lm_clock.ms: members, gather,
-  // scan passes of the last call (filled under sgtd_set_timing)
-  enum { LM_POSE = 0, LM_OFF, LM_ANCH, LM_COUNT, LM_MERGED, LM_MEM_OFF, LM_MEMBER, LM_SEG, LM_CNT, LM_START, LM_MPTS, LM_MLAB, LM_XYZ, LM_LABEL,
-         LM_NPOINTS, LM_BUFS };
-  DevBuf lm[LM_BUFS];
+  // sgtd_local_map_keypoints (local_map_kernels.hip.h); the clustering runs in the sk buffers above.  lm_n < 0: no
+  // results; lm_kp_off / lm_mem_off / lm_merged: per anchor, on the host; lm_clock.ms: members, gather, scan passes of
+  // the last call (filled under sgtd_set_timing)
+  struct LocalMapBufs {
+    DevArr<float> pose;                       // the scans' poses, offsets [S + 1], the anchors
+    DevArr<long long> off;
+    DevArr<int> anch, count;                  // per anchor: its members,
+    DevArr<long long> merged, mem_off;        // ... its merged cloud's points, its members' offset [A + 1]
+    DevArr<int> member;                       // the member lists
+    DevArr<LmSeg> seg;                        // a pass's segments, their sizes and first places [n_seg + 1]
+    DevArr<u32> cnt, start;
+    DevArr<float> mpts;                       // ... and its merged cloud
+    DevArr<u32> mlab;
+    DevArr<float> xyz;                        // the appended keypoints of all passes
+    DevArr<u32> label;
+    DevArr<int> npoints;
+  } lm;
   int lm_n = -1, lm_passes = 0;
   int64_t lm_kept = 0;
   std::vector<int64_t> lm_kp_off, lm_mem_off, lm_merged;
   LapClock lm_clock;
-  // sgtd_thin_clouds (thin_kernels.hip.h): independent of everything else on the handle, buffers of its own (TH_*:
-  // thin_run; no other call touches them, so TH_OUT, the device view, stays valid across the registration calls).
-  // th_n < 0: no results; th_stride / th_kept: floats a point and points of TH_OUT; th_out_off / th_dropped: per cloud,
+  // sgtd_thin_clouds (thin_kernels.hip.h): independent of everything else on the handle, buffers of its own (thin_run;
+  // no other call touches them, so th.out, the device view, stays valid across the registration calls).
+  // th_n < 0: no results; th_stride / th_kept: floats a point and points of th.out; th_out_off / th_dropped: per cloud,
   // on the host; th_clock.ms: the sorts, the whole call (filled under sgtd_set_timing)
-  enum { TH_PTS = 0, TH_OFF, TH_KEY_PT, TH_CL_PT, TH_KEY_A, TH_KEY_B, TH_CKEY_A, TH_CKEY_B, TH_VAL_A, TH_VAL_B, TH_FLAGS, TH_EXCL, TH_FIRST, TH_FIRST_EXCL,
-         TH_COUNTS, TH_CSTART, TH_DROPPED, TH_OUT_OFF, TH_OUT, TH_BUFS };
-  DevBuf th[TH_BUFS];
+  struct ThinBufs {
+    DevArr<float> pts;                        // the host's points (staging), the clouds' offsets [S + 1]
+    DevArr<long long> off;
+    DevArr<u64> key_pt;                       // per point: its cell key, its cloud
+    DevArr<u32> cl_pt;
+    DevArr<u64> key_a, key_b;                 // the sort by cell, then (stable) by cloud: keys, cloud keys, the points' order
+    DevArr<u32> ckey_a, ckey_b, val_a, val_b;
+    DevArr<u32> flags, excl;                  // the cells' heads and their scan (excl[P]: the cells),
+    DevArr<u32> first, first_excl;            // ... the cells by smallest point index and their scan
+    DevArr<u32> counts, cstart;               // the head kernel's counters; the cells' first places [cells + 1]
+    DevArr<int> dropped;                      // per cloud: its non-finite and its out-of-range points [S * 2]
+    DevArr<long long> out_off;                // the thinned clouds' offsets [S + 1]
+    DevArr<float> out;                        // the thinned points
+  } th;
   int th_n = -1, th_stride = 3;
   int64_t th_kept = 0;
   std::vector<int64_t> th_out_off;
@@ -571,28 +659,23 @@ int ensure_store(sgtd_engine *e, DescStore &s, size_t cap, bool keep = false) {
   return SGTD_OK;
 }
 
-void free_buf(DevBuf &b) {
-  if (b.p && !b.borrowed) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  b.borrowed = false;
+// the one place a typed array is sized (16 bytes at the least: an empty call's kernels still get a pointer)
+template <class T>
+int need(sgtd_engine *e, DevArr<T> &a, size_t n_elems, bool keep = false) {
+  return ensure(e, a.buf, std::max<size_t>(n_elems * sizeof(T), 16), keep);
 }
-void free_store(DescStore &s) {
-  free_buf(s.side); free_buf(s.angle); free_buf(s.center); free_buf(s.vertex);
-  free_buf(s.label); free_buf(s.frame); free_buf(s.node_id); free_buf(s.qrec);
-  s.cap = 0;
+// ... several arrays of n elements each, in the order given
+template <class... A>
+int need_each(sgtd_engine *e, size_t n, A &...a) {
+  int r = SGTD_OK;
+  (void)(((r = need(e, a, n)) == SGTD_OK) && ...);
+  return r;
 }
+
+// a buffer released in the middle of a handle's life (whatever is left at the end goes with the handle)
+void free_buf(DevBuf &b) { b = DevBuf(); }
 using DenseRun = sgtd_engine::DenseRun;
 using VoxelRun = sgtd_engine::VoxelRun;
-// a registration run's buffers and its clock's events
-void free_run(DenseRun &r) {
-  for (DevBuf *b : {&r.in, &r.pts, &r.cov, &r.part, &r.match, &r.state, &r.out, &r.ctl}) free_buf(*b);
-  r.clock.destroy();
-}
-void free_run(VoxelRun &r) {
-  for (DevBuf &b : r.B) free_buf(b);
-  r.clock.destroy();
-}
 
 // ---------------------------------------------------------------------------
 // Small host <-> device transfers go through ONE pinned staging buffer per handle: a
@@ -2299,9 +2382,9 @@ int sgtd_create(const sgtd_config *cfg, sgtd_handle *out) {
   // test hook: the undecided queue's floor, so that a small record buffer gives a queue of rec_cap / 64 entries that overflows
   if (const char *o = getenv("SGTD_AMB_MIN")) e->amb_min = (size_t)std::max(1ll, atoll(o));
   for (int i = 0; i < EV_COUNT; i++)
-    if (hipEventCreate(&e->ev[i]) != hipSuccess) { delete e; return SGTD_ERR_HIP; }
+    if (hipEventCreate(&e->ev[i]) != hipSuccess) { sgtd_destroy(e); return SGTD_ERR_HIP; }      // (the events made so far go too)
   if (hipEventCreateWithFlags(&e->ev_cand, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_export_free, hipEventDisableTiming) != hipSuccess) { delete e; return SGTD_ERR_HIP; }
+      hipEventCreateWithFlags(&e->ev_export_free, hipEventDisableTiming) != hipSuccess) { sgtd_destroy(e); return SGTD_ERR_HIP; }
   *out = e;
   return SGTD_OK;
 }
@@ -2330,36 +2413,8 @@ int sgtd_destroy(sgtd_handle e) {
   (void)hipSetDevice(e->cfg.device_id);
   (void)hipStreamSynchronize(e->stream);
   if (e->attached_to) { e->attached_to->n_views--; e->attached_to = nullptr; }
-  free_store(e->tab); free_store(e->tmp); free_store(e->qd); free_store(e->fetch); free_buf(e->fetch_idx);
-  DevBuf *bufs[] = {&e->seg[0].hot, &e->seg[0].perm, &e->seg[0].hash, &e->seg[0].bucket_start, &e->seg[0].bucket_key, &e->seg[0].dir,
-                    &e->seg[1].hot, &e->seg[1].perm, &e->seg[1].hash, &e->seg[1].bucket_start, &e->seg[1].bucket_key, &e->seg[1].dir, &e->slice_of, &e->sq_sum,
-                    &e->keyA, &e->keyB, &e->valA, &e->valB, &e->hist, &e->digit_tot, &e->flags, &e->bad_flag, &e->order_work,
-                    &e->kp_off_dev, &e->xyz_dev, &e->label_dev, &e->b_kp_off_dev, &e->b_xyz_dev, &e->b_label_dev, &e->ws_keys, &e->ws_slots, &e->cnt_scan,
-                    &e->tmp_count, &e->q_count, &e->n_valid, &e->cell_rows, &e->gid, &e->q_prefix, &e->group_first, &e->n_groups, &e->pos_of_slot, &e->rec_off, &e->pass_pool, &e->v_score, &e->v_pose, &e->v_inlier, &e->v_best, &e->r_pose, &e->r_rmse, &e->r_rmse_v, &e->r_npairs, &e->r_moments, &e->r_flag, &e->kp_dev, &e->kp_word, &e->o_cnt, &e->o_val, &e->o_qxyz, &e->o_qlabel, &e->o_qoff, &e->a_pose, &e->a_fit, &e->a_cnt, &e->a_val, &e->a_mom, &e->a_assign, &e->inl_pairs, &e->inl_off, &e->v_hyp64, &e->v_hyp32, &e->v_bound, &e->v_hypB, &e->v_tau, &e->v_words, &e->v_okey[0], &e->v_okey[1], &e->v_oval[0], &e->v_oval[1], &e->cursors, &e->list, &e->n_visit,
-                    &e->votes, &e->slot_of, &e->q_M, &e->q_P, &e->q_pairs, &e->q_pair_base,
-                    &e->blk_count, &e->c_pair, &e->c_blk, &e->amb_queue, &e->rec, &e->rec_cell, &e->rec_dis, &e->rough_qi,
-                    &e->rough_entry, &e->rough_frame, &e->rough_cell, &e->rough_dis, &e->n_cand, &e->cand_frame,
-                    &e->cand_votes, &e->pair_off, &e->pairs, &e->totals, &e->inl_counts, &e->in_block, &e->b_in, &e->b_out,
-                    // (the entry-id map: missing from this list until the engine's host code ran under the sanitizers — every destroyed
-                    // handle kept them, 8 bytes per map frame and, with frame ids out of insertion order, 8 bytes per entry)
-                    &e->frame_first, &e->by_frame, &e->id_of_g, &e->longest,
-                    &e->rm_bits, &e->rm_present, &e->rm_mask, &e->rm_count, &e->rm_scratch, &e->filt_rows,
-                    &e->pos_dev, &e->prior_dev, &e->filt_base,
-                    &e->ck_store, &e->ck_has, &e->ck_in, &e->ck_soa, &e->ck_valid, &e->ck_rows, &e->ck_pmask, &e->ck_out, &e->ck_state,
-                    &e->cs_in, &e->cs_out,
-                    &e->rx_in, &e->rx_state, &e->rx_edge, &e->rx_node, &e->rx_ctl,
-                    &e->st.pts, &e->st.cov, &e->st.off, &e->st_stage, &e->st_idx, &e->st_table, &e->sr_pairs, &e->sv_form, &e->sv_members};
-  for (DevBuf *b : bufs) free_buf(*b);
-  for (DevBuf &b : e->sk) free_buf(b);
-  for (DevBuf &b : e->lm) free_buf(b);
-  free_run(e->dense); free_run(e->stored);
-  free_run(e->vox); free_run(e->svox);
   for (hipEvent_t ev : e->ck_ev)
     if (ev) (void)hipEventDestroy(ev);
-  e->lm_clock.destroy();
-  for (DevBuf &b : e->th) free_buf(b);
-  e->th_clock.destroy();
-  for (auto &b : e->scan_lvl) free_buf(b);
   if (e->pin) (void)hipHostFree(e->pin);
   if (e->frame_host) (void)hipHostFree(e->frame_host);
   if (e->pin_build) (void)hipHostFree(e->pin_build);
@@ -2367,7 +2422,7 @@ int sgtd_destroy(sgtd_handle e) {
     if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
   if (e->ev_cand) (void)hipEventDestroy(e->ev_cand);
   if (e->ev_export_free) (void)hipEventDestroy(e->ev_export_free);
-  delete e;
+  delete e;      // (every device buffer and the stages' clocks go here, with the device selected above)
   return SGTD_OK;
 }
 
@@ -2582,24 +2637,19 @@ int sgtd_attach_table(sgtd_handle v, sgtd_handle o) {
     if (st != SGTD_OK) { e->err = "sgtd_attach_table: the owner's table could not be finalized"; return st; }
     if (hipStreamSynchronize(o->stream) != hipSuccess) return SGTD_ERR_HIP;
   }
-  auto borrow = [](DevBuf &dst, const DevBuf &src) {
-    if (dst.p && !dst.borrowed) (void)hipFree(dst.p);
-    dst = src;
-    dst.borrowed = true;
-  };
-  borrow(v->tab.side, o->tab.side); borrow(v->tab.angle, o->tab.angle); borrow(v->tab.center, o->tab.center);
-  borrow(v->tab.vertex, o->tab.vertex); borrow(v->tab.label, o->tab.label); borrow(v->tab.frame, o->tab.frame);
-  borrow(v->tab.node_id, o->tab.node_id);
+  v->tab.side.borrow_from(o->tab.side); v->tab.angle.borrow_from(o->tab.angle); v->tab.center.borrow_from(o->tab.center);
+  v->tab.vertex.borrow_from(o->tab.vertex); v->tab.label.borrow_from(o->tab.label); v->tab.frame.borrow_from(o->tab.frame);
+  v->tab.node_id.borrow_from(o->tab.node_id);
   v->tab.cap = o->tab.cap;
   for (int k = 0; k < 2; k++) {
     sgtd_engine::Segment &d = v->seg[k];
     const sgtd_engine::Segment &s = o->seg[k];
-    borrow(d.hot, s.hot); borrow(d.perm, s.perm); borrow(d.hash, s.hash); borrow(d.bucket_start, s.bucket_start);
-    borrow(d.bucket_key, s.bucket_key); borrow(d.dir, s.dir);
+    d.hot.borrow_from(s.hot); d.perm.borrow_from(s.perm); d.hash.borrow_from(s.hash); d.bucket_start.borrow_from(s.bucket_start);
+    d.bucket_key.borrow_from(s.bucket_key); d.dir.borrow_from(s.dir);
     d.hash_mask = s.hash_mask; d.n_buckets = s.n_buckets; d.g0 = s.g0; d.g1 = s.g1; d.sum_len_sq = s.sum_len_sq;
     d.frame_hi = s.frame_hi; d.built = s.built;
   }
-  borrow(v->frame_first, o->frame_first); borrow(v->by_frame, o->by_frame); borrow(v->id_of_g, o->id_of_g);
+  v->frame_first.borrow_from(o->frame_first); v->by_frame.borrow_from(o->by_frame); v->id_of_g.borrow_from(o->id_of_g);
   v->n_seg = o->n_seg; v->id_bits = o->id_bits; v->id_by_frame = o->id_by_frame;
   v->n_entries = o->n_entries; v->n_add_calls = o->n_add_calls; v->have_frames = o->have_frames;
   v->frame_lo = o->frame_lo; v->frame_hi = o->frame_hi; v->current_frame_id = o->current_frame_id;
@@ -3850,6 +3900,27 @@ int voxel_runs(sgtd_engine *e, const u64 *keys, long long n, u64 drop, u32 *flag
   CHK(device_scan(e, flags, excl, n + 1));
   scan_voxels_kernel<<<grid_for(n, 256), 256, 0, e->stream>>>(keys, flags, excl, n, counts, vkey, vstart);
   return SGTD_OK;      // (the caller asks for the launches' error, behind what it launches next)
+}
+
+using RunScratch = sgtd_engine::RunScratch;
+// room for the runs among n pairs
+int need_runs(sgtd_engine *e, RunScratch &R, size_t n) {
+  CHK(need_each(e, n, R.key_a, R.key_b, R.val_a, R.val_b));
+  CHK(need_each(e, n + 1, R.flags, R.excl));
+  CHK(need(e, R.counts, 4));
+  CHK(need(e, R.vkey, n));
+  return need(e, R.vstart, n + 1);
+}
+// The n pairs a kernel left in key_a / val_a, sorted by the low `bits` of the key (stable), and their runs (voxel_runs;
+// keys from `drop` on belong to none).  *keys / *vals: where the sort left the pairs.
+int sorted_runs(sgtd_engine *e, RunScratch &R, long long n, int bits, bool skip_const, u64 drop, u64 **keys, u32 **vals) {
+  u64 *kin = R.key_a.p(), *kout = R.key_b.p();
+  u32 *vin = R.val_a.p(), *vout = R.val_b.p();
+  CHK(radix_sort_pairs<u64>(e, kin, kout, vin, vout, n, bits, skip_const));
+  HIPCHK(hipMemsetAsync(R.counts.p(), 0, 4 * sizeof(u32), e->stream));
+  CHK(voxel_runs(e, kin, n, drop, R.flags.p(), R.excl.p(), R.counts.p(), R.vkey.p(), R.vstart.p()));
+  *keys = kin; *vals = vin;
+  return SGTD_OK;
 }
 
 int LapClock::start(sgtd_engine *e, bool timed) {
@@ -5286,7 +5357,7 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
   const size_t ts = (size_t)std::max(total_src, 1);
   const RegOut out((size_t)n, false);
   CHK(ensure(c, R.in, in_bytes));
-  if (!S.cov) CHK(ensure(c, R.cov, std::max<size_t>(total, 1) * 9 * sizeof(double)));
+  if (!S.cov) CHK(need(c, R.cov, std::max<size_t>(total, 1) * 9));
   CHK(ensure(c, R.part, ts * n_slices * (sizeof(double) + sizeof(int))));
   CHK(ensure(c, R.match, ts * (10 * sizeof(double) + sizeof(int))));
   CHK(ensure(c, R.state, (size_t)n * sizeof(RegState)));
@@ -5300,7 +5371,7 @@ int reg_run(sgtd_engine *c, const RegSite &S, const sgtd_register_options &o, co
 
   RegParams P;
   const int *di = reinterpret_cast<const int *>(in + o_idx);
-  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts, S.cov ? S.cov : R.cov.as<double>(),
+  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts, S.cov ? S.cov : R.cov.p(),
               R.state.p, R.ctl.p, out, R.out.p,
               gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, o.max_corr_dist, o.lm_init_lambda_factor, o.rotation_eps, o.translation_eps,
                            o.plane_eps));
@@ -5420,7 +5491,7 @@ int dense_cov_out(sgtd_engine *e, DenseRun sgtd_engine::*run, const char *missin
   if (n) *n = need;
   const size_t m = (size_t)std::min(need, capacity);
   CopyOut out(e, c);
-  out.get(cov, R.cov.as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  out.get(cov, R.cov.p() + (size_t)first * 9, m * 9 * sizeof(double));
   CHK(out.finish());
   return need > capacity && cov ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
@@ -5485,7 +5556,7 @@ int sgtd_register_clouds(sgtd_handle e, const sgtd_register_options *opt, const 
   StageRun<int> run(e, &sgtd_engine::dense);
   run.on_device([&](sgtd_engine *c) -> int {
     const float *d_pts = nullptr;
-    CHK(points_on_device(c, c->dense.pts, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
+    CHK(points_on_device(c, c->dense.pts.buf, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
     return reg_clouds_run(c, o, d_pts, stride_floats, pt_off, n_clouds, src_cloud, tgt_cloud, init_pose, n_pairs);
   });
   return run.end(n_pairs);
@@ -5533,7 +5604,6 @@ int store_alloc(sgtd_engine *e, DevBuf &b, size_t bytes) {
   b.p = p; b.bytes = bytes;
   return SGTD_OK;
 }
-void store_free(CloudArena &A) { free_buf(A.pts); free_buf(A.cov); free_buf(A.off); }
 
 // A change of the arena that is not the store's until store_commit: the slots that die (`dies`, indices into the
 // current arena), and `next` where the change needs new arrays (the live slots, in order, copied into them).  Leaving
@@ -5542,7 +5612,6 @@ struct StoreChange {
   std::vector<int> dies;
   CloudArena next;
   bool rebuilt = false;
-  ~StoreChange() { store_free(next); }
 };
 
 // Room behind the slots for `pts` points and `clouds` clouds.  *A = the arena to write to: the store's own where they
@@ -5731,14 +5800,14 @@ int stored_run(sgtd_engine *c, const sgtd_register_options &o, const float *poin
   if (n == 0) { R.host_soff.assign(1, 0); return SGTD_OK; }
   const int64_t total = pt_off[n_clouds];
   const float *d_src = nullptr;
-  CHK(points_on_device(c, R.pts, points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(points_on_device(c, R.pts.buf, points, (size_t)total * stride, device_ptrs, &d_src));
   CHK(store_pack(c, A, d_src, stride, total, A.used));
   std::vector<long long> rows;
   CHK(store_tail_rows(c, A, pt_off, n_clouds, rows));
   const RegSite S{"sgtd_register_stored", R, A.pts.as<float>(), 3, A.cov.as<double>(), A.off.as<long long>(), (int)A.slots.size(), d_init};
   CHK(reg_run(c, S, o, pt_off, n_clouds, R.host_named.data(), src, slot, tgt_n.data(), init, n));
-  CHK(ensure(c, R.cov, std::max<size_t>((size_t)total, 1) * 9 * sizeof(double)));
-  if (total) HIPCHK(hipMemcpyAsync(R.cov.p, A.cov.as<double>() + (size_t)A.used * 9, (size_t)total * 9 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  CHK(need(c, R.cov, std::max<size_t>((size_t)total, 1) * 9));
+  if (total) HIPCHK(hipMemcpyAsync(R.cov.p(), A.cov.as<double>() + (size_t)A.used * 9, (size_t)total * 9 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   CHK(xfer_sync(c));
   return SGTD_OK;
 }
@@ -5795,7 +5864,6 @@ int sgtd_set_frame_clouds(sgtd_handle e, const uint32_t *frame_ids, const int64_
     if (frame_ids) return SGTD_OK;
     (void)hipSetDevice(c->cfg.device_id);
     (void)hipStreamSynchronize(c->stream);
-    store_free(c->st);
     c->st = CloudArena();
     for (DevBuf *b : {&c->st_stage, &c->st_idx, &c->st_table}) free_buf(*b);
     c->st_slot_of.clear(); c->st_frames = 0; c->st_k = 0; c->st_eps = 0.0;
@@ -6000,7 +6068,7 @@ struct VregSite {
   VoxelRun &R;         // the run's buffers, mode, host arrays and clock
   const float *pts;                 // the points of every cloud the kernels may name, on the device
   int stride;
-  double *cov;                      // the covariances of those clouds; NULL: VR_COV, grown to the call's points
+  double *cov;                      // the covariances of those clouds; NULL: the run's cov, grown to the call's points
   const long long *d_off;           // the clouds' offsets where they are on the device already; NULL: pt_off is uploaded
   int first;                        // the index the kernels know the call's cloud 0 by
   // the members where they were formed on the device (sgtd_register_stored_local_loops): their clouds, maps, first points
@@ -6059,26 +6127,16 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
                o_idx = o_pose + relax_up((size_t)n_members * 12 * sizeof(double)), in_bytes = o_idx + relax_up(G.up.size() * sizeof(int));
   const size_t ts = (size_t)std::max(total_src, 1), mp = (size_t)std::max<long long>(MP, 1), nn = (size_t)std::max(n, 1);
   const RegOut out((size_t)n, true);
-  DevBuf *B = R.B;
-  auto buf = [&](int which, size_t bytes) { return ensure(c, B[which], std::max<size_t>(bytes, 16)); };
-  CHK(buf(sgtd_engine::VR_IN, in_bytes));
-  if (!S.cov) CHK(buf(sgtd_engine::VR_COV, std::max<size_t>(total, 1) * 9 * sizeof(double)));
-  CHK(buf(sgtd_engine::VR_KEY_A, mp * sizeof(u64)));
-  CHK(buf(sgtd_engine::VR_KEY_B, mp * sizeof(u64)));
-  CHK(buf(sgtd_engine::VR_VAL_A, mp * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_VAL_B, mp * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_FLAGS, (mp + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_EXCL, (mp + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_COUNTS, 4 * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_VKEY, mp * sizeof(u64)));
-  CHK(buf(sgtd_engine::VR_VSTART, (mp + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_MAP_VOX, ((size_t)n_maps + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::VR_VID, ts * mode * sizeof(int)));
-  CHK(buf(sgtd_engine::VR_MW, ts * mode * 9 * sizeof(double)));
-  CHK(buf(sgtd_engine::VR_STATE, nn * sizeof(RegState)));
-  CHK(buf(sgtd_engine::VR_OUT, out.bytes()));
-  CHK(buf(sgtd_engine::VR_CTL, 64));
-  char *in = B[sgtd_engine::VR_IN].as<char>();
+  CHK(need(c, R.in, in_bytes));
+  if (!S.cov) CHK(need(c, R.cov, std::max<size_t>(total, 1) * 9));
+  CHK(need_runs(c, R.runs, mp));
+  CHK(need(c, R.map_vox, (size_t)n_maps + 1));
+  CHK(need(c, R.vid, ts * mode));
+  CHK(need(c, R.mw, ts * mode * 9));
+  CHK(need(c, R.state, nn));
+  CHK(need(c, R.out, out.bytes()));
+  CHK(need(c, R.ctl, 64));
+  char *in = R.in.p();
   if (!S.d_off) CHK(h2d(c, in + o_off, pt_off, (size_t)(n_clouds + 1) * sizeof(int64_t)));
   if (init) CHK(h2d(c, in + o_init, init, (size_t)n * 12 * sizeof(double)));
   if (map_pose) CHK(h2d(c, in + o_pose, map_pose, (size_t)n_members * 12 * sizeof(double)));
@@ -6086,9 +6144,9 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
 
   RegParams P;
   const int *di = reinterpret_cast<const int *>(in + o_idx);
-  void *ob = B[sgtd_engine::VR_OUT].p;
-  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts,
-              S.cov ? S.cov : B[sgtd_engine::VR_COV].as<double>(), B[sgtd_engine::VR_STATE].p, B[sgtd_engine::VR_CTL].p, out, ob,
+  void *ob = R.out.p();
+  gicp_params(P, G, S.pts, S.stride, S.d_off ? static_cast<const void *>(S.d_off) : in + o_off, di, n, ts, S.cov ? S.cov : R.cov.p(), R.state.p(),
+              R.ctl.p(), out, ob,
               gicp_options(o.k_neighbors, o.max_iterations, o.lm_max_trials, std::numeric_limits<double>::infinity(), o.lm_init_lambda_factor, o.rotation_eps,
                            o.translation_eps, o.plane_eps));
   VregParams V;
@@ -6098,8 +6156,8 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
   if (on_device) { V.map_cloud = S.d_mem_cloud; V.mem_map = S.d_mem_map; V.mem_pt_off = S.d_mem_pt_off; V.map_pose = S.d_map_pose; }
   V.tgt_map = di + u_tgt;
   V.n_maps = n_maps; V.n_members = n_members; V.n_member_pts = (int)MP; V.mode = mode; V.res = o.voxel_resolution;
-  V.map_vox = B[sgtd_engine::VR_MAP_VOX].as<u32>();
-  V.vid = B[sgtd_engine::VR_VID].as<int>(); V.Mw = B[sgtd_engine::VR_MW].as<double>();
+  V.map_vox = R.map_vox.p();
+  V.vid = R.vid.p(); V.Mw = R.mw.p();
   V.out_corr = out.corr(ob);
 
   hipStream_t s = c->stream;
@@ -6111,25 +6169,19 @@ int vreg_run(sgtd_engine *c, const VregSite &S, const sgtd_voxel_register_option
   // the maps: keys, the stable sort, the voxels' heads, the Gaussians, the maps' ranges
   u32 n_vox = 0;
   if (MP > 0) {
-    u64 *kin = B[sgtd_engine::VR_KEY_A].as<u64>(), *kout = B[sgtd_engine::VR_KEY_B].as<u64>();
-    u32 *vin = B[sgtd_engine::VR_VAL_A].as<u32>(), *vout = B[sgtd_engine::VR_VAL_B].as<u32>();
-    u32 *flags = B[sgtd_engine::VR_FLAGS].as<u32>(), *excl = B[sgtd_engine::VR_EXCL].as<u32>(), *counts = B[sgtd_engine::VR_COUNTS].as<u32>();
-    u64 *vkey = B[sgtd_engine::VR_VKEY].as<u64>();
-    u32 *vstart = B[sgtd_engine::VR_VSTART].as<u32>();
-    const int gp = grid_for(MP, 256);
-    vreg_keys_kernel<<<gp, 256, 0, s>>>(P, V, kin, vin);
+    u64 *keys = nullptr;
+    u32 *order = nullptr;
+    vreg_keys_kernel<<<grid_for(MP, 256), 256, 0, s>>>(P, V, R.runs.key_a.p(), R.runs.val_a.p());
     HIPCHK(hipGetLastError());
-    CHK(radix_sort_pairs<u64>(c, kin, kout, vin, vout, MP, 48 + key_bits((u64)n_maps), true));
-    HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(u32), s));
-    CHK(voxel_runs(c, kin, MP, (u64)n_maps << 48, flags, excl, counts, vkey, vstart));
+    CHK(sorted_runs(c, R.runs, MP, 48 + key_bits((u64)n_maps), true, (u64)n_maps << 48, &keys, &order));
     HIPCHK(hipGetLastError());
-    CHK(d2h(c, &n_vox, excl + MP, sizeof(u32)));
+    CHK(d2h(c, &n_vox, R.runs.excl.p() + MP, sizeof(u32)));
     CHK(xfer_sync(c));
-    V.vkey = vkey; V.vstart = vstart; V.order = vin; V.n_vox = n_vox;
+    V.vkey = R.runs.vkey.p(); V.vstart = R.runs.vstart.p(); V.order = order; V.n_vox = n_vox;
     const size_t nv = std::max<size_t>(n_vox, 1);
-    CHK(buf(sgtd_engine::VR_MEAN, nv * 3 * sizeof(double)));
-    CHK(buf(sgtd_engine::VR_VCOV, nv * 9 * sizeof(double)));
-    V.vmean = B[sgtd_engine::VR_MEAN].as<double>(); V.vcov = B[sgtd_engine::VR_VCOV].as<double>();
+    CHK(need(c, R.mean, nv * 3));
+    CHK(need(c, R.vcov, nv * 9));
+    V.vmean = R.mean.p(); V.vcov = R.vcov.p();
     if (n_vox) vreg_voxel_kernel<<<grid_for(n_vox, 4), 256, 0, s>>>(P, V);
   }
   vreg_ranges_kernel<<<grid_for(n_maps + 1, 256), 256, 0, s>>>(V);
@@ -6258,7 +6310,7 @@ int vreg_rows_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missin
   CHK(stage_ready(e, run, missing, &c));
   VoxelRun &R = c->*run;
   if (R.n == 0) return SGTD_OK;
-  return reg_rows_out(e, c, RegOut((size_t)R.n, true), R.B[sgtd_engine::VR_OUT].p, pose, fitness, cost, n_matched, n_corr, iterations, status);
+  return reg_rows_out(e, c, RegOut((size_t)R.n, true), R.out.p(), pose, fitness, cost, n_matched, n_corr, iterations, status);
 }
 
 int vreg_map_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing, int map, int32_t *coord, int32_t *n_points, double *mean, double *cov,
@@ -6266,8 +6318,8 @@ int vreg_map_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing
   if (!e || capacity < 0) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, run, missing, &c));
-  const std::vector<u32> &map_vox = (c->*run).host_map_vox;
-  DevBuf *B = (c->*run).B;
+  const VoxelRun &R = c->*run;
+  const std::vector<u32> &map_vox = R.host_map_vox;
   if (map < 0 || (size_t)map + 1 >= map_vox.size()) return SGTD_ERR_INVALID;
   const int64_t first = map_vox[(size_t)map], need = (int64_t)map_vox[(size_t)map + 1] - first;
   if (n) *n = need;
@@ -6276,10 +6328,10 @@ int vreg_map_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *missing
   std::vector<u64> keys(coord ? m : 0);
   std::vector<u32> starts(n_points && m ? m + 1 : 0);
   CopyOut out(e, c);
-  out.get(keys.data(), B[sgtd_engine::VR_VKEY].as<u64>() + first, keys.size() * sizeof(u64));
-  out.get(starts.data(), B[sgtd_engine::VR_VSTART].as<u32>() + first, starts.size() * sizeof(u32));
-  out.get(mean, B[sgtd_engine::VR_MEAN].as<double>() + (size_t)first * 3, m * 3 * sizeof(double));
-  out.get(cov, B[sgtd_engine::VR_VCOV].as<double>() + (size_t)first * 9, m * 9 * sizeof(double));
+  out.get(keys.data(), R.runs.vkey.p() + first, keys.size() * sizeof(u64));
+  out.get(starts.data(), R.runs.vstart.p() + first, starts.size() * sizeof(u32));
+  out.get(mean, R.mean.p() + (size_t)first * 3, m * 3 * sizeof(double));
+  out.get(cov, R.vcov.p() + (size_t)first * 9, m * 9 * sizeof(double));
   CHK(out.finish());
   for (size_t v = 0; v < keys.size(); v++)
     for (int a = 0; a < 3; a++) coord[v * 3 + a] = (int32_t)((keys[v] >> (32 - 16 * a)) & 0xFFFFu) - 32768;
@@ -6297,7 +6349,7 @@ int vreg_matches_out(sgtd_engine *e, VoxelRun sgtd_engine::*run, const char *mis
   const int64_t need = (int64_t)R.host_soff[(size_t)pair + 1] * R.mode - first;
   if (n) *n = need;
   CopyOut out(e, c);
-  out.get(voxel, R.B[sgtd_engine::VR_VID].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
+  out.get(voxel, R.vid.p() + first, (size_t)std::min(need, capacity) * sizeof(int));
   CHK(out.finish());
   return need > capacity && voxel ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
@@ -6343,7 +6395,7 @@ int sgtd_register_voxels(sgtd_handle e, const sgtd_voxel_register_options *opt, 
   StageRun<int> run(e, &sgtd_engine::vox);
   run.on_device([&](sgtd_engine *c) -> int {
     const float *d_pts = nullptr;
-    CHK(points_on_device(c, c->vox.B[sgtd_engine::VR_PTS], points, (size_t)total * stride_floats, device_ptrs, &d_pts));
+    CHK(points_on_device(c, c->vox.pts.buf, points, (size_t)total * stride_floats, device_ptrs, &d_pts));
     return vreg_clouds_run(c, o, d_pts, stride_floats, pt_off, n_clouds, map_off, map_cloud, map_pose, n_maps, src_cloud, tgt_map, init_pose, n_pairs);
   });
   return run.end(n_pairs);
@@ -6394,7 +6446,7 @@ int stored_voxels_run(sgtd_engine *c, const sgtd_voxel_register_options &o, cons
   for (int k = 0; k < n; k++) named[(size_t)src[k]] = 1;
   const int64_t total = pt_off[n_clouds];
   const float *d_src = nullptr;
-  CHK(points_on_device(c, c->svox.B[sgtd_engine::VR_PTS], points, (size_t)total * stride, device_ptrs, &d_src));
+  CHK(points_on_device(c, c->svox.pts.buf, points, (size_t)total * stride, device_ptrs, &d_src));
   CHK(store_pack(c, A, d_src, stride, total, A.used));
   std::vector<long long> rows;
   CHK(store_tail_rows(c, A, pt_off, n_clouds, rows));
@@ -6641,113 +6693,86 @@ bool scan_rings_fit(const sgtd_scan_config &c) {
 }
 
 // the pipeline from "points on the device" onward: d_pts / d_lab are device arrays (nullptr: scan_run's own staging
-// buffers SK_PTS / SK_LAB, which it has filled), pt_off is the host's.  sgtd_local_map_keypoints calls it once per pass.
+// buffers sk.pts / sk.lab, which it has filled), pt_off is the host's.  sgtd_local_map_keypoints calls it once per pass.
 int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int stride, const u32 *d_lab, const int64_t *pt_off, int S);
 
 int scan_run(sgtd_engine *e, const ScanCfgDev &C, const float *points, int stride, const uint32_t *labels, const int64_t *pt_off, int S,
              int device_ptrs) {
   const long long P = pt_off[S];
   if (device_ptrs || S == 0 || P == 0) return scan_device(e, C, points, stride, labels, pt_off, S);
-  auto buf = [&](int k, size_t bytes) { return ensure(e, e->sk[k], std::max<size_t>(bytes, 16)); };
   const size_t np = (size_t)P;
-  CHK(buf(sgtd_engine::SK_PTS, np * stride * sizeof(float)));
-  CHK(buf(sgtd_engine::SK_LAB, np * sizeof(u32)));
-  CHK(h2d(e, e->sk[sgtd_engine::SK_PTS].p, points, np * stride * sizeof(float)));
-  CHK(h2d(e, e->sk[sgtd_engine::SK_LAB].p, labels, np * sizeof(u32)));
+  CHK(need(e, e->sk.pts, np * stride));
+  CHK(need(e, e->sk.lab, np));
+  CHK(h2d(e, e->sk.pts.p(), points, np * stride * sizeof(float)));
+  CHK(h2d(e, e->sk.lab.p(), labels, np * sizeof(u32)));
   return scan_device(e, C, nullptr, stride, nullptr, pt_off, S);
 }
 
 int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int stride, const u32 *d_lab, const int64_t *pt_off, int S) {
   const long long P = pt_off[S];
   const int n_sc = S * 32;
-  auto buf = [&](int k, size_t bytes) { return ensure(e, e->sk[k], std::max<size_t>(bytes, 16)); };
+  sgtd_engine::ScanBufs &B = e->sk;
   const size_t np = (size_t)P;
   e->sk_off.assign(pt_off, pt_off + S + 1);
   e->sk_kp_off.assign((size_t)S + 1, 0);
   e->sk_points = P; e->sk_kept = 0;
-  CHK(buf(sgtd_engine::SK_GRID, (size_t)std::max(n_sc, 1) * 4 * sizeof(int)));
-  CHK(buf(sgtd_engine::SK_RANGE, (size_t)std::max(n_sc, 1) * 4 * sizeof(double)));
-  CHK(buf(sgtd_engine::SK_XYZ, 16));
-  CHK(buf(sgtd_engine::SK_LABEL, 16));
+  CHK(need(e, B.grid, (size_t)std::max(n_sc, 1) * 4));
+  CHK(need(e, B.range, (size_t)std::max(n_sc, 1) * 4));
+  CHK(need_each(e, 0, B.xyz, B.label));      // (a run without keypoints still has results to point to)
   if (S == 0 || P == 0) {
     if (n_sc > 0) {
-      HIPCHK(hipMemsetAsync(e->sk[sgtd_engine::SK_GRID].p, 0, (size_t)n_sc * 4 * sizeof(int), e->stream));
-      HIPCHK(hipMemsetAsync(e->sk[sgtd_engine::SK_RANGE].p, 0, (size_t)n_sc * 4 * sizeof(double), e->stream));
+      HIPCHK(hipMemsetAsync(B.grid.p(), 0, (size_t)n_sc * 4 * sizeof(int), e->stream));
+      HIPCHK(hipMemsetAsync(B.range.p(), 0, (size_t)n_sc * 4 * sizeof(double), e->stream));
     }
     return xfer_sync(e);
   }
-  if (!d_pts) d_pts = e->sk[sgtd_engine::SK_PTS].as<float>();
-  if (!d_lab) d_lab = e->sk[sgtd_engine::SK_LAB].as<u32>();
-  CHK(buf(sgtd_engine::SK_OFF, ((size_t)S + 1) * sizeof(long long)));
-  CHK(h2d(e, e->sk[sgtd_engine::SK_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
-  CHK(buf(sgtd_engine::SK_SC, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_R, np * sizeof(double)));
-  CHK(buf(sgtd_engine::SK_PITCH, np * sizeof(double)));
-  CHK(buf(sgtd_engine::SK_AZI, np * sizeof(double)));
-  CHK(buf(sgtd_engine::SK_MM, (size_t)n_sc * 4 * sizeof(u64)));
-  CHK(buf(sgtd_engine::SK_VOTE, (size_t)n_sc * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_BOUNDS, (size_t)n_sc * SGTD_SCAN_CELLS * sizeof(double)));
-  CHK(buf(sgtd_engine::SK_KEY_A, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::SK_KEY_B, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::SK_VAL_A, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_VAL_B, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_FLAGS, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_EXCL, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_COUNTS, 4 * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_VKEY, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::SK_VSTART, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_NBR, np * SGTD_SCAN_NBR * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_NBR_CNT, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_PARENT, np * sizeof(u32)));
+  if (!d_pts) d_pts = B.pts.p();
+  if (!d_lab) d_lab = B.lab.p();
+  CHK(need(e, B.off, (size_t)S + 1));
+  CHK(h2d(e, B.off.p(), pt_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(need_each(e, np, B.sc, B.r, B.pitch, B.azi));
+  CHK(need(e, B.mm, (size_t)n_sc * 4));
+  CHK(need(e, B.vote, (size_t)n_sc));
+  CHK(need(e, B.bounds, (size_t)n_sc * SGTD_SCAN_CELLS));
+  CHK(need_runs(e, B.runs, np));
+  CHK(need(e, B.nbr, np * SGTD_SCAN_NBR));
+  CHK(need_each(e, np, B.nbr_cnt, B.parent));
   constexpr int kMaxRounds = 4096, kGroup = 8;
-  CHK(buf(sgtd_engine::SK_CHANGED, kMaxRounds * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_CCOUNT, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_CMIN, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_CKEY_A, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::SK_CKEY_B, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::SK_CVAL_A, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_CVAL_B, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_KP_OFF, ((size_t)S + 1) * sizeof(long long)));
-  CHK(buf(sgtd_engine::SK_CL_OF_ROOT, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_PKEY_A, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_PKEY_B, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_PVAL_A, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_PVAL_B, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_CLUSTER, np * sizeof(int)));
-  auto *B = e->sk;
+  CHK(need(e, B.changed, kMaxRounds));
+  CHK(need_each(e, np, B.ccount, B.cmin, B.ckey_a, B.ckey_b, B.cval_a, B.cval_b));
+  CHK(need(e, B.kp_off, (size_t)S + 1));
+  CHK(need_each(e, np, B.cl_of_root, B.pkey_a, B.pkey_b, B.pval_a, B.pval_b, B.cluster));
   const hipStream_t st = e->stream;
   const int gp = grid_for(P, 256);
-  const long long *d_off = B[sgtd_engine::SK_OFF].as<long long>();
-  int *grid = B[sgtd_engine::SK_GRID].as<int>();
-  double *range = B[sgtd_engine::SK_RANGE].as<double>(), *bounds = B[sgtd_engine::SK_BOUNDS].as<double>();
+  const long long *d_off = B.off.p();
+  int *grid = B.grid.p();
+  double *range = B.range.p(), *bounds = B.bounds.p();
 
   // per point, per (scan, class), keys
-  scan_init_kernel<<<grid_for(n_sc, 256), 256, 0, st>>>(B[sgtd_engine::SK_MM].as<u64>(), B[sgtd_engine::SK_VOTE].as<u32>(), n_sc);
+  scan_init_kernel<<<grid_for(n_sc, 256), 256, 0, st>>>(B.mm.p(), B.vote.p(), n_sc);
   ScanPointParams PP;
   PP.pts = d_pts; PP.stride = stride; PP.labels = d_lab; PP.pt_off = d_off; PP.n = P;
-  PP.sc_of = B[sgtd_engine::SK_SC].as<u32>(); PP.r = B[sgtd_engine::SK_R].as<double>(); PP.pitch = B[sgtd_engine::SK_PITCH].as<double>();
-  PP.azimuth = B[sgtd_engine::SK_AZI].as<double>(); PP.mm = B[sgtd_engine::SK_MM].as<u64>(); PP.vote = B[sgtd_engine::SK_VOTE].as<u32>();
+  PP.sc_of = B.sc.p(); PP.r = B.r.p(); PP.pitch = B.pitch.p();
+  PP.azimuth = B.azi.p(); PP.mm = B.mm.p(); PP.vote = B.vote.p();
   scan_point_kernel<<<grid_for(P, SGTD_SCAN_TILE), 256, 0, st>>>(PP, C);
   scan_rings_kernel<<<grid_for(n_sc, 64), 64, 0, st>>>(PP.mm, PP.vote, n_sc, C, grid, range, bounds);
-  u64 *kin = B[sgtd_engine::SK_KEY_A].as<u64>(), *kout = B[sgtd_engine::SK_KEY_B].as<u64>();
-  u32 *vin = B[sgtd_engine::SK_VAL_A].as<u32>(), *vout = B[sgtd_engine::SK_VAL_B].as<u32>();
-  scan_keys_kernel<<<gp, 256, 0, st>>>(PP.sc_of, d_lab, PP.r, PP.pitch, PP.azimuth, grid, range, bounds, C, P, kin, vin);
+  scan_keys_kernel<<<gp, 256, 0, st>>>(PP.sc_of, d_lab, PP.r, PP.pitch, PP.azimuth, grid, range, bounds, C, P, B.runs.key_a.p(), B.runs.val_a.p());
   HIPCHK(hipGetLastError());
-  CHK(radix_sort_pairs<u64>(e, kin, kout, vin, vout, P, 38 + key_bits((u64)S), false));
 
   // voxels, links, components
-  u32 *flags = B[sgtd_engine::SK_FLAGS].as<u32>(), *excl = B[sgtd_engine::SK_EXCL].as<u32>(), *counts = B[sgtd_engine::SK_COUNTS].as<u32>();
+  u64 *kin = nullptr;
+  u32 *vin = nullptr;
+  CHK(sorted_runs(e, B.runs, P, 38 + key_bits((u64)S), false, (u64)S << 38, &kin, &vin));
+  u32 *flags = B.runs.flags.p(), *excl = B.runs.excl.p(), *counts = B.runs.counts.p();
   const u32 *n_vox_p = excl + P;
-  u64 *vkey = B[sgtd_engine::SK_VKEY].as<u64>();
-  u32 *vstart = B[sgtd_engine::SK_VSTART].as<u32>(), *nbr = B[sgtd_engine::SK_NBR].as<u32>(), *nbr_cnt = B[sgtd_engine::SK_NBR_CNT].as<u32>();
-  u32 *parent = B[sgtd_engine::SK_PARENT].as<u32>(), *changed = B[sgtd_engine::SK_CHANGED].as<u32>();
-  u32 *ccount = B[sgtd_engine::SK_CCOUNT].as<u32>(), *cmin = B[sgtd_engine::SK_CMIN].as<u32>();
-  HIPCHK(hipMemsetAsync(counts, 0, 4 * sizeof(u32), st));
+  u64 *vkey = B.runs.vkey.p();
+  u32 *vstart = B.runs.vstart.p(), *nbr = B.nbr.p(), *nbr_cnt = B.nbr_cnt.p();
+  u32 *parent = B.parent.p(), *changed = B.changed.p();
+  u32 *ccount = B.ccount.p(), *cmin = B.cmin.p();
   HIPCHK(hipMemsetAsync(changed, 0, kMaxRounds * sizeof(u32), st));
   HIPCHK(hipMemsetAsync(ccount, 0, np * sizeof(u32), st));
   HIPCHK(hipMemsetAsync(cmin, 0xFF, np * sizeof(u32), st));
-  HIPCHK(hipMemsetAsync(B[sgtd_engine::SK_CL_OF_ROOT].p, 0xFF, np * sizeof(u32), st));
-  CHK(voxel_runs(e, kin, P, (u64)S << 38, flags, excl, counts, vkey, vstart));
+  HIPCHK(hipMemsetAsync(B.cl_of_root.p(), 0xFF, np * sizeof(u32), st));
   scan_links_kernel<<<gp, 256, 0, st>>>(vkey, n_vox_p, grid, nbr, nbr_cnt, parent);
   HIPCHK(hipGetLastError());
   bool settled = false;
@@ -6766,12 +6791,12 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
   scan_component_kernel<<<gp, 256, 0, st>>>(n_vox_p, parent, vstart, vin, ccount, cmin);
 
   // kept clusters in keypoint order, the offsets
-  u64 *ckin = B[sgtd_engine::SK_CKEY_A].as<u64>(), *ckout = B[sgtd_engine::SK_CKEY_B].as<u64>();
-  u32 *cvin = B[sgtd_engine::SK_CVAL_A].as<u32>(), *cvout = B[sgtd_engine::SK_CVAL_B].as<u32>();
+  u64 *ckin = B.ckey_a.p(), *ckout = B.ckey_b.p();
+  u32 *cvin = B.cval_a.p(), *cvout = B.cval_b.p();
   scan_cluster_keys_kernel<<<gp, 256, 0, st>>>(n_vox_p, vkey, parent, ccount, cmin, grid, C, ckin, cvin);
   HIPCHK(hipGetLastError());
   CHK(radix_sort_pairs<u64>(e, ckin, ckout, cvin, cvout, P, 37 + key_bits((u64)S), false, n_vox_p));
-  long long *d_kp_off = B[sgtd_engine::SK_KP_OFF].as<long long>();
+  long long *d_kp_off = B.kp_off.p();
   scan_offsets_kernel<<<grid_for(S + 1, 256), 256, 0, st>>>(ckin, n_vox_p, S, d_kp_off);
   HIPCHK(hipGetLastError());
   CHK(d2h(e, e->sk_kp_off.data(), d_kp_off, ((size_t)S + 1) * sizeof(long long)));
@@ -6780,25 +6805,21 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
   e->sk_kept = K;
 
   // the points by keypoint, the centres
-  CHK(buf(sgtd_engine::SK_KCOUNT, (size_t)std::max<long long>(K, 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_CSTART, (size_t)std::max<long long>(K, 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_XYZ, (size_t)std::max<long long>(K, 1) * 3 * sizeof(float)));
-  CHK(buf(sgtd_engine::SK_LABEL, (size_t)std::max<long long>(K, 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::SK_NPOINTS, (size_t)std::max<long long>(K, 1) * sizeof(int)));
-  u32 *kcount = B[sgtd_engine::SK_KCOUNT].as<u32>(), *cstart = B[sgtd_engine::SK_CSTART].as<u32>();
-  u32 *cl_of_root = B[sgtd_engine::SK_CL_OF_ROOT].as<u32>();
-  if (K > 0)
-    scan_cluster_ids_kernel<<<grid_for(K, 256), 256, 0, st>>>(ckin, cvin, (u32)K, ccount, C, cl_of_root, kcount, B[sgtd_engine::SK_NPOINTS].as<int>(),
-                                                             B[sgtd_engine::SK_LABEL].as<u32>());
-  u32 *pkin = B[sgtd_engine::SK_PKEY_A].as<u32>(), *pkout = B[sgtd_engine::SK_PKEY_B].as<u32>();
-  u32 *pvin = B[sgtd_engine::SK_PVAL_A].as<u32>(), *pvout = B[sgtd_engine::SK_PVAL_B].as<u32>();
-  scan_point_clusters_kernel<<<gp, 256, 0, st>>>(kin, vin, flags, excl, counts, parent, cl_of_root, d_kp_off, P, (u32)K, pkin, pvin,
-                                                 B[sgtd_engine::SK_CLUSTER].as<int>());
+  const size_t nk = (size_t)std::max<long long>(K, 1);
+  CHK(need_each(e, nk, B.kcount, B.cstart));
+  CHK(need(e, B.xyz, nk * 3));
+  CHK(need_each(e, nk, B.label, B.npoints));
+  u32 *kcount = B.kcount.p(), *cstart = B.cstart.p();
+  u32 *cl_of_root = B.cl_of_root.p();
+  if (K > 0) scan_cluster_ids_kernel<<<grid_for(K, 256), 256, 0, st>>>(ckin, cvin, (u32)K, ccount, C, cl_of_root, kcount, B.npoints.p(), B.label.p());
+  u32 *pkin = B.pkey_a.p(), *pkout = B.pkey_b.p();
+  u32 *pvin = B.pval_a.p(), *pvout = B.pval_b.p();
+  scan_point_clusters_kernel<<<gp, 256, 0, st>>>(kin, vin, flags, excl, counts, parent, cl_of_root, d_kp_off, P, (u32)K, pkin, pvin, B.cluster.p());
   HIPCHK(hipGetLastError());
   if (K > 0) {
     CHK(radix_sort_pairs<u32>(e, pkin, pkout, pvin, pvout, P, key_bits((u64)K), false));
     CHK(device_scan(e, kcount, cstart, K));
-    float *xyz = B[sgtd_engine::SK_XYZ].as<float>();
+    float *xyz = B.xyz.p();
     scan_sum_wave_kernel<<<grid_for(K, 4), 256, 0, st>>>(d_pts, stride, pvin, cstart, kcount, (u32)K, xyz);
     scan_sum_block_kernel<<<(unsigned)K, 256, 0, st>>>(d_pts, stride, pvin, cstart, kcount, xyz);
     HIPCHK(hipGetLastError());
@@ -6808,12 +6829,12 @@ int scan_device(sgtd_engine *e, const ScanCfgDev &C, const float *d_pts, int str
 }
 
 // the first m keypoints a stage left on its home engine c, to those of the caller's arrays that are given
-int keypoints_out(sgtd_engine *e, sgtd_engine *c, const DevBuf &xyz_dev, const DevBuf &label_dev, const DevBuf &n_points_dev, size_t m, float *xyz,
-                  uint32_t *label, int32_t *n_points) {
+int keypoints_out(sgtd_engine *e, sgtd_engine *c, const DevArr<float> &xyz_dev, const DevArr<u32> &label_dev, const DevArr<int> &n_points_dev, size_t m,
+                  float *xyz, uint32_t *label, int32_t *n_points) {
   CopyOut out(e, c);
-  out.get(xyz, xyz_dev.p, m * 3 * sizeof(float));
-  out.get(label, label_dev.p, m * sizeof(u32));
-  out.get(n_points, n_points_dev.p, m * sizeof(int));
+  out.get(xyz, xyz_dev.p(), m * 3 * sizeof(float));
+  out.get(label, label_dev.p(), m * sizeof(u32));
+  out.get(n_points, n_points_dev.p(), m * sizeof(int));
   return out.finish();
 }
 
@@ -6832,8 +6853,7 @@ ScanCfgDev scan_cfg_dev(const sgtd_scan_config &c, int n_scans) {
 
 int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_map_options &opt, const float *points, int stride,
                   const uint32_t *labels, const int64_t *pt_off, const float *pose12, int S, const int32_t *anchors, int A, int device_ptrs) {
-  auto buf = [&](int k, size_t bytes, bool keep = false) { return ensure(e, e->lm[k], std::max<size_t>(bytes, 16), keep); };
-  auto *B = e->lm;
+  sgtd_engine::LocalMapBufs &B = e->lm;
   const hipStream_t st = e->stream;
   const bool timed = e->timing;
   LapClock &clock = e->lm_clock;      // (ms: members, gather, scan passes; the events bracket the work they measure)
@@ -6842,36 +6862,30 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
   e->lm_mem_off.assign((size_t)A + 1, 0);
   e->lm_merged.assign((size_t)A, 0);
   e->lm_kept = 0; e->lm_passes = 0;
-  CHK(buf(sgtd_engine::LM_XYZ, 16));
-  CHK(buf(sgtd_engine::LM_LABEL, 16));
-  CHK(buf(sgtd_engine::LM_NPOINTS, 16));
-  CHK(buf(sgtd_engine::LM_MEMBER, 16));
+  CHK(need_each(e, 0, B.xyz, B.label, B.npoints, B.member));      // (a call without anchors or keypoints still has results to point to)
   if (A == 0) return SGTD_OK;
 
   // members: counts and merged sizes, the host's plan, then the lists
   std::vector<int32_t> anch((size_t)A);
   for (int a = 0; a < A; a++) anch[(size_t)a] = anchors ? anchors[a] : a;
-  CHK(buf(sgtd_engine::LM_POSE, (size_t)S * 12 * sizeof(float)));
-  CHK(buf(sgtd_engine::LM_OFF, ((size_t)S + 1) * sizeof(long long)));
-  CHK(buf(sgtd_engine::LM_ANCH, (size_t)A * sizeof(int)));
-  CHK(buf(sgtd_engine::LM_COUNT, (size_t)A * sizeof(int)));
-  CHK(buf(sgtd_engine::LM_MERGED, (size_t)A * sizeof(long long)));
-  CHK(buf(sgtd_engine::LM_MEM_OFF, ((size_t)A + 1) * sizeof(long long)));
-  CHK(h2d(e, B[sgtd_engine::LM_POSE].p, pose12, (size_t)S * 12 * sizeof(float)));
-  CHK(h2d(e, B[sgtd_engine::LM_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
-  CHK(h2d(e, B[sgtd_engine::LM_ANCH].p, anch.data(), (size_t)A * sizeof(int)));
-  const float *d_pose = B[sgtd_engine::LM_POSE].as<float>();
-  const long long *d_off = B[sgtd_engine::LM_OFF].as<long long>();
-  const int *d_anch = B[sgtd_engine::LM_ANCH].as<int>();
+  CHK(need(e, B.pose, (size_t)S * 12));
+  CHK(need(e, B.off, (size_t)S + 1));
+  CHK(need_each(e, (size_t)A, B.anch, B.count, B.merged));
+  CHK(need(e, B.mem_off, (size_t)A + 1));
+  CHK(h2d(e, B.pose.p(), pose12, (size_t)S * 12 * sizeof(float)));
+  CHK(h2d(e, B.off.p(), pt_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(h2d(e, B.anch.p(), anch.data(), (size_t)A * sizeof(int)));
+  const float *d_pose = B.pose.p();
+  const long long *d_off = B.off.p();
+  const int *d_anch = B.anch.p();
   const double rr = opt.radius * opt.radius;
   if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
-  lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, nullptr, nullptr, B[sgtd_engine::LM_COUNT].as<int>(),
-                                                   B[sgtd_engine::LM_MERGED].as<long long>());
+  lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, nullptr, nullptr, B.count.p(), B.merged.p());
   HIPCHK(hipGetLastError());
   if (timed) HIPCHK(hipEventRecord(clock.ev[1], st));
   std::vector<int32_t> count((size_t)A);
-  CHK(d2h(e, count.data(), B[sgtd_engine::LM_COUNT].p, (size_t)A * sizeof(int)));
-  CHK(d2h(e, e->lm_merged.data(), B[sgtd_engine::LM_MERGED].p, (size_t)A * sizeof(long long)));
+  CHK(d2h(e, count.data(), B.count.p(), (size_t)A * sizeof(int)));
+  CHK(d2h(e, e->lm_merged.data(), B.merged.p(), (size_t)A * sizeof(long long)));
   CHK(xfer_sync(e));
   if (timed) CHK(clock.span(e, 0, 1, 0, true));
   const int64_t cap = opt.max_pass_points > 0 ? opt.max_pass_points : (int64_t)1 << 26;
@@ -6885,13 +6899,12 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
     }
   }
   const int64_t M = e->lm_mem_off[(size_t)A];
-  CHK(buf(sgtd_engine::LM_MEMBER, (size_t)M * sizeof(int)));
-  CHK(h2d(e, B[sgtd_engine::LM_MEM_OFF].p, e->lm_mem_off.data(), ((size_t)A + 1) * sizeof(long long)));
-  const long long *d_mem_off = B[sgtd_engine::LM_MEM_OFF].as<long long>();
-  int *d_member = B[sgtd_engine::LM_MEMBER].as<int>();
+  CHK(need(e, B.member, (size_t)M));
+  CHK(h2d(e, B.mem_off.p(), e->lm_mem_off.data(), ((size_t)A + 1) * sizeof(long long)));
+  const long long *d_mem_off = B.mem_off.p();
+  int *d_member = B.member.p();
   if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
-  lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, d_mem_off, d_member, B[sgtd_engine::LM_COUNT].as<int>(),
-                                                   B[sgtd_engine::LM_MERGED].as<long long>());
+  lm_members_kernel<<<A, SGTD_LM_THREADS, 0, st>>>(d_pose, d_off, S, d_anch, rr, opt.max_members, d_mem_off, d_member, B.count.p(), B.merged.p());
   HIPCHK(hipGetLastError());
   if (timed) {
     HIPCHK(hipEventRecord(clock.ev[1], st));
@@ -6904,12 +6917,12 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
   const size_t np = (size_t)pt_off[S];
   e->sk_n = -1;
   if (!device_ptrs && np) {
-    CHK(ensure(e, e->sk[sgtd_engine::SK_PTS], np * stride * sizeof(float)));
-    CHK(ensure(e, e->sk[sgtd_engine::SK_LAB], np * sizeof(u32)));
-    CHK(h2d(e, e->sk[sgtd_engine::SK_PTS].p, points, np * stride * sizeof(float)));
-    CHK(h2d(e, e->sk[sgtd_engine::SK_LAB].p, labels, np * sizeof(u32)));
-    d_pts = e->sk[sgtd_engine::SK_PTS].as<float>();
-    d_lab = e->sk[sgtd_engine::SK_LAB].as<u32>();
+    CHK(ensure(e, e->sk.pts.buf, np * stride * sizeof(float)));      // (as they always were here: to the byte, no floor of 16)
+    CHK(ensure(e, e->sk.lab.buf, np * sizeof(u32)));
+    CHK(h2d(e, e->sk.pts.p(), points, np * stride * sizeof(float)));
+    CHK(h2d(e, e->sk.lab.p(), labels, np * sizeof(u32)));
+    d_pts = e->sk.pts.p();
+    d_lab = e->sk.lab.p();
   }
   const bool vec = stride == 4 && ((uintptr_t)d_pts & 15) == 0;
 
@@ -6925,15 +6938,14 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
     const int n_seg = (int)n_seg64;
     pass_off.assign((size_t)na + 1, 0);
     for (int a = 0; a < na; a++) pass_off[(size_t)a + 1] = pass_off[(size_t)a] + e->lm_merged[(size_t)(a0 + a)];
-    CHK(buf(sgtd_engine::LM_SEG, (size_t)n_seg * sizeof(LmSeg)));
-    CHK(buf(sgtd_engine::LM_CNT, ((size_t)n_seg + 1) * sizeof(u32)));
-    CHK(buf(sgtd_engine::LM_START, ((size_t)n_seg + 1) * sizeof(u32)));
-    CHK(buf(sgtd_engine::LM_MPTS, (size_t)Pp * 3 * sizeof(float)));
-    CHK(buf(sgtd_engine::LM_MLAB, (size_t)Pp * sizeof(u32)));
-    LmSeg *seg = B[sgtd_engine::LM_SEG].as<LmSeg>();
-    u32 *cnt = B[sgtd_engine::LM_CNT].as<u32>(), *start = B[sgtd_engine::LM_START].as<u32>();
-    float *m_pts = B[sgtd_engine::LM_MPTS].as<float>();
-    u32 *m_lab = B[sgtd_engine::LM_MLAB].as<u32>();
+    CHK(need(e, B.seg, (size_t)n_seg));
+    CHK(need_each(e, (size_t)n_seg + 1, B.cnt, B.start));
+    CHK(need(e, B.mpts, (size_t)Pp * 3));
+    CHK(need(e, B.mlab, (size_t)Pp));
+    LmSeg *seg = B.seg.p();
+    u32 *cnt = B.cnt.p(), *start = B.start.p();
+    float *m_pts = B.mpts.p();
+    u32 *m_lab = B.mlab.p();
     if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
     if (Pp > 0) {
       lm_segments_kernel<<<grid_for((long long)n_seg + 1, 256), 256, 0, st>>>(d_pose, d_off, d_anch, d_mem_off, d_member, a0, na, n_seg, seg, cnt);
@@ -6957,15 +6969,12 @@ int local_map_run(sgtd_engine *e, const sgtd_scan_config &cfg, const sgtd_local_
     const int64_t K = e->sk_kept, K0 = e->lm_kept;
     for (int a = 0; a <= na; a++) e->lm_kp_off[(size_t)(a0 + a)] = K0 + e->sk_kp_off[(size_t)a];
     if (K > 0) {
-      CHK(buf(sgtd_engine::LM_XYZ, (size_t)(K0 + K) * 3 * sizeof(float), true));
-      CHK(buf(sgtd_engine::LM_LABEL, (size_t)(K0 + K) * sizeof(u32), true));
-      CHK(buf(sgtd_engine::LM_NPOINTS, (size_t)(K0 + K) * sizeof(int), true));
-      HIPCHK(hipMemcpyAsync(B[sgtd_engine::LM_XYZ].as<float>() + (size_t)K0 * 3, e->sk[sgtd_engine::SK_XYZ].p, (size_t)K * 3 * sizeof(float),
-                            hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipMemcpyAsync(B[sgtd_engine::LM_LABEL].as<u32>() + (size_t)K0, e->sk[sgtd_engine::SK_LABEL].p, (size_t)K * sizeof(u32),
-                            hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipMemcpyAsync(B[sgtd_engine::LM_NPOINTS].as<int>() + (size_t)K0, e->sk[sgtd_engine::SK_NPOINTS].p, (size_t)K * sizeof(int),
-                            hipMemcpyDeviceToDevice, st));
+      CHK(need(e, B.xyz, (size_t)(K0 + K) * 3, true));
+      CHK(need(e, B.label, (size_t)(K0 + K), true));
+      CHK(need(e, B.npoints, (size_t)(K0 + K), true));
+      HIPCHK(hipMemcpyAsync(B.xyz.p() + (size_t)K0 * 3, e->sk.xyz.p(), (size_t)K * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(B.label.p() + (size_t)K0, e->sk.label.p(), (size_t)K * sizeof(u32), hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(B.npoints.p() + (size_t)K0, e->sk.npoints.p(), (size_t)K * sizeof(int), hipMemcpyDeviceToDevice, st));
     }
     e->lm_kept = K0 + K;
     e->lm_passes++;
@@ -7050,7 +7059,7 @@ int sgtd_result_scan_keypoints(sgtd_handle e, int64_t *kp_off, float *xyz, uint3
   const int64_t K = c->sk_kept;
   if (n_keypoints) *n_keypoints = K;
   if (kp_off) std::memcpy(kp_off, c->sk_kp_off.data(), c->sk_kp_off.size() * sizeof(int64_t));
-  CHK(keypoints_out(e, c, c->sk[sgtd_engine::SK_XYZ], c->sk[sgtd_engine::SK_LABEL], c->sk[sgtd_engine::SK_NPOINTS], (size_t)std::min(K, capacity), xyz, label, n_points));
+  CHK(keypoints_out(e, c, c->sk.xyz, c->sk.label, c->sk.npoints, (size_t)std::min(K, capacity), xyz, label, n_points));
   return K > capacity && (xyz || label || n_points) ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
@@ -7062,7 +7071,7 @@ int sgtd_result_scan_point_clusters(sgtd_handle e, int scan, int32_t *cluster, i
   const int64_t first = c->sk_off[(size_t)scan], need = c->sk_off[(size_t)scan + 1] - first;
   if (n) *n = need;
   CopyOut out(e, c);
-  out.get(cluster, c->sk[sgtd_engine::SK_CLUSTER].as<int>() + first, (size_t)std::min(need, capacity) * sizeof(int));
+  out.get(cluster, c->sk.cluster.p() + first, (size_t)std::min(need, capacity) * sizeof(int));
   CHK(out.finish());
   return need > capacity && cluster ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
@@ -7073,8 +7082,8 @@ int sgtd_result_scan_grids(sgtd_handle e, int scan, int32_t *grid, double *range
   CHK(stage_ready(e, &sgtd_engine::sk_n, kNoScan, &c));
   if (scan < 0 || scan >= c->sk_n) return SGTD_ERR_INVALID;
   CopyOut out(e, c);
-  out.get(grid, c->sk[sgtd_engine::SK_GRID].as<int>() + (size_t)scan * 128, 128 * sizeof(int));
-  out.get(range, c->sk[sgtd_engine::SK_RANGE].as<double>() + (size_t)scan * 128, 128 * sizeof(double));
+  out.get(grid, c->sk.grid.p() + (size_t)scan * 128, 128 * sizeof(int));
+  out.get(range, c->sk.range.p() + (size_t)scan * 128, 128 * sizeof(double));
   return out.finish();
 }
 
@@ -7082,8 +7091,8 @@ int sgtd_scan_device_view(sgtd_handle e, const float **d_xyz, const uint32_t **d
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, &sgtd_engine::sk_n, kNoScan, &c));
-  if (d_xyz) *d_xyz = c->sk[sgtd_engine::SK_XYZ].as<float>();
-  if (d_label) *d_label = c->sk[sgtd_engine::SK_LABEL].as<u32>();
+  if (d_xyz) *d_xyz = c->sk.xyz.p();
+  if (d_label) *d_label = c->sk.label.p();
   return SGTD_OK;
 }
 
@@ -7138,7 +7147,7 @@ int sgtd_result_local_map_keypoints(sgtd_handle e, int64_t *kp_off, float *xyz, 
   const int64_t K = c->lm_kept;
   if (n_keypoints) *n_keypoints = K;
   if (kp_off) std::memcpy(kp_off, c->lm_kp_off.data(), c->lm_kp_off.size() * sizeof(int64_t));
-  CHK(keypoints_out(e, c, c->lm[sgtd_engine::LM_XYZ], c->lm[sgtd_engine::LM_LABEL], c->lm[sgtd_engine::LM_NPOINTS], (size_t)std::min(K, capacity), xyz, label, n_points));
+  CHK(keypoints_out(e, c, c->lm.xyz, c->lm.label, c->lm.npoints, (size_t)std::min(K, capacity), xyz, label, n_points));
   return K > capacity && (xyz || label || n_points) ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
 
@@ -7153,7 +7162,7 @@ int sgtd_result_local_map_members(sgtd_handle e, int64_t *mem_off, int32_t *memb
   if (mem_off) std::memcpy(mem_off, c->lm_mem_off.data(), c->lm_mem_off.size() * sizeof(int64_t));
   if (merged_points && !c->lm_merged.empty()) std::memcpy(merged_points, c->lm_merged.data(), c->lm_merged.size() * sizeof(int64_t));
   CopyOut out(e, c);
-  out.get(member, c->lm[sgtd_engine::LM_MEMBER].p, (size_t)std::min(M, capacity) * sizeof(int));
+  out.get(member, c->lm.member.p(), (size_t)std::min(M, capacity) * sizeof(int));
   CHK(out.finish());
   return M > capacity && member ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
@@ -7162,8 +7171,8 @@ int sgtd_local_map_device_view(sgtd_handle e, const float **d_xyz, const uint32_
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, &sgtd_engine::lm_n, kNoLocalMap, &c));
-  if (d_xyz) *d_xyz = c->lm[sgtd_engine::LM_XYZ].as<float>();
-  if (d_label) *d_label = c->lm[sgtd_engine::LM_LABEL].as<u32>();
+  if (d_xyz) *d_xyz = c->lm.xyz.p();
+  if (d_label) *d_label = c->lm.label.p();
   return SGTD_OK;
 }
 
@@ -7185,8 +7194,7 @@ namespace {
 int thin_run(sgtd_engine *e, const float *points, int stride, const int64_t *pt_off, int S, double leaf, int device_ptrs) {
   const long long P = pt_off[S];
   const size_t np = (size_t)P;
-  auto buf = [&](int k, size_t bytes) { return ensure(e, e->th[k], std::max<size_t>(bytes, 16)); };
-  auto *B = e->th;
+  sgtd_engine::ThinBufs &B = e->th;
   const hipStream_t st = e->stream;
   const bool timed = e->timing;
   LapClock &clock = e->th_clock;      // (ms: the two sorts, the whole call)
@@ -7194,41 +7202,31 @@ int thin_run(sgtd_engine *e, const float *points, int stride, const int64_t *pt_
   e->th_out_off.assign((size_t)S + 1, 0);
   e->th_dropped.assign((size_t)S * 2, 0);
   e->th_stride = stride; e->th_kept = 0;
-  CHK(buf(sgtd_engine::TH_OUT, 16));
+  CHK(need(e, B.out, 0));      // (a call that keeps nothing still has results to point to)
   if (S == 0 || P == 0) return xfer_sync(e);
 
   const float *d_pts = nullptr;
-  CHK(points_on_device(e, B[sgtd_engine::TH_PTS], points, np * stride, device_ptrs, &d_pts));
-  CHK(buf(sgtd_engine::TH_OFF, ((size_t)S + 1) * sizeof(long long)));
-  CHK(h2d(e, B[sgtd_engine::TH_OFF].p, pt_off, ((size_t)S + 1) * sizeof(long long)));
-  CHK(buf(sgtd_engine::TH_KEY_PT, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::TH_CL_PT, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_KEY_A, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::TH_KEY_B, np * sizeof(u64)));
-  CHK(buf(sgtd_engine::TH_CKEY_A, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_CKEY_B, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_VAL_A, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_VAL_B, np * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_FLAGS, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_EXCL, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_FIRST, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_FIRST_EXCL, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_COUNTS, 4 * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_CSTART, (np + 1) * sizeof(u32)));
-  CHK(buf(sgtd_engine::TH_DROPPED, (size_t)S * 2 * sizeof(int)));
-  CHK(buf(sgtd_engine::TH_OUT_OFF, ((size_t)S + 1) * sizeof(long long)));
+  CHK(points_on_device(e, B.pts.buf, points, np * stride, device_ptrs, &d_pts));
+  CHK(need(e, B.off, (size_t)S + 1));
+  CHK(h2d(e, B.off.p(), pt_off, ((size_t)S + 1) * sizeof(long long)));
+  CHK(need_each(e, np, B.key_pt, B.cl_pt, B.key_a, B.key_b, B.ckey_a, B.ckey_b, B.val_a, B.val_b));
+  CHK(need_each(e, np + 1, B.flags, B.excl, B.first, B.first_excl));
+  CHK(need(e, B.counts, 4));
+  CHK(need(e, B.cstart, np + 1));
+  CHK(need(e, B.dropped, (size_t)S * 2));
+  CHK(need(e, B.out_off, (size_t)S + 1));
   const int gp = grid_for(P, 256);
-  const long long *d_off = B[sgtd_engine::TH_OFF].as<long long>();
-  u64 *key_pt = B[sgtd_engine::TH_KEY_PT].as<u64>();
-  u32 *cl_pt = B[sgtd_engine::TH_CL_PT].as<u32>();
-  u64 *kin = B[sgtd_engine::TH_KEY_A].as<u64>(), *kout = B[sgtd_engine::TH_KEY_B].as<u64>();
-  u32 *ckin = B[sgtd_engine::TH_CKEY_A].as<u32>(), *ckout = B[sgtd_engine::TH_CKEY_B].as<u32>();
-  u32 *vin = B[sgtd_engine::TH_VAL_A].as<u32>(), *vout = B[sgtd_engine::TH_VAL_B].as<u32>();
-  u32 *flags = B[sgtd_engine::TH_FLAGS].as<u32>(), *excl = B[sgtd_engine::TH_EXCL].as<u32>();
-  u32 *first = B[sgtd_engine::TH_FIRST].as<u32>(), *first_excl = B[sgtd_engine::TH_FIRST_EXCL].as<u32>();
-  u32 *counts = B[sgtd_engine::TH_COUNTS].as<u32>(), *cstart = B[sgtd_engine::TH_CSTART].as<u32>();
-  int *dropped = B[sgtd_engine::TH_DROPPED].as<int>();
-  long long *d_out_off = B[sgtd_engine::TH_OUT_OFF].as<long long>();
+  const long long *d_off = B.off.p();
+  u64 *key_pt = B.key_pt.p();
+  u32 *cl_pt = B.cl_pt.p();
+  u64 *kin = B.key_a.p(), *kout = B.key_b.p();
+  u32 *ckin = B.ckey_a.p(), *ckout = B.ckey_b.p();
+  u32 *vin = B.val_a.p(), *vout = B.val_b.p();
+  u32 *flags = B.flags.p(), *excl = B.excl.p();
+  u32 *first = B.first.p(), *first_excl = B.first_excl.p();
+  u32 *counts = B.counts.p(), *cstart = B.cstart.p();
+  int *dropped = B.dropped.p();
+  long long *d_out_off = B.out_off.p();
 
   // keys, the two sorts
   if (timed) HIPCHK(hipEventRecord(clock.ev[0], st));
@@ -7260,9 +7258,9 @@ int thin_run(sgtd_engine *e, const float *points, int stride, const int64_t *pt_
   e->th_kept = K;
 
   // the sums
-  CHK(buf(sgtd_engine::TH_OUT, (size_t)std::max<long long>(K, 1) * stride * sizeof(float)));
+  CHK(need(e, B.out, (size_t)std::max<long long>(K, 1) * stride));
   if (K > 0) {
-    float *out = B[sgtd_engine::TH_OUT].as<float>();
+    float *out = B.out.p();
     if (stride == 3) thin_sum_kernel<3><<<grid_for(K, 256), 256, 0, st>>>(d_pts, vin, cstart, first_excl, excl + P, out);
     else thin_sum_kernel<4><<<grid_for(K, 256), 256, 0, st>>>(d_pts, vin, cstart, first_excl, excl + P, out);
     HIPCHK(hipGetLastError());
@@ -7304,7 +7302,7 @@ int sgtd_result_thinned(sgtd_handle e, int64_t *out_off, float *points, int32_t 
   if (out_off) std::memcpy(out_off, c->th_out_off.data(), c->th_out_off.size() * sizeof(int64_t));
   if (n_dropped && !c->th_dropped.empty()) std::memcpy(n_dropped, c->th_dropped.data(), c->th_dropped.size() * sizeof(int32_t));
   CopyOut out(e, c);
-  out.get(points, c->th[sgtd_engine::TH_OUT].p, (size_t)std::min(K, capacity) * c->th_stride * sizeof(float));
+  out.get(points, c->th.out.p(), (size_t)std::min(K, capacity) * c->th_stride * sizeof(float));
   CHK(out.finish());
   return K > capacity && points ? SGTD_ERR_CAPACITY : SGTD_OK;
 }
@@ -7313,7 +7311,7 @@ int sgtd_thinned_device_view(sgtd_handle e, const float **d_points, int *stride_
   if (!e) return SGTD_ERR_INVALID;
   sgtd_engine *c = nullptr;
   CHK(stage_ready(e, &sgtd_engine::th_n, kNoThin, &c));
-  if (d_points) *d_points = c->th[sgtd_engine::TH_OUT].as<float>();
+  if (d_points) *d_points = c->th.out.p();
   if (stride_floats) *stride_floats = c->th_stride;
   if (n_points) *n_points = c->th_kept;
   return SGTD_OK;

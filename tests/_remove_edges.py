@@ -18,8 +18,8 @@ Constants restated from the sources:
   TILE 1024, THREADS 256, ROUNDS 4     SGTD_RM_TILE, SGTD_RM_THREADS, SGTD_RM_ROUNDS   remove_kernels.hip.h:16-18
   MASKS 16                             SGTD_RM_MASKS (one 64-bit keep mask per wave and round)   remove_kernels.hip.h:19
   SCAN_BLOCK 2048                      SGTD_SCAN_THREADS x SGTD_SCAN_ITEMS   table_kernels.hip.h:21-22
-  LDS_SWITCH 65536 bytes of bitmap     remove_entries, `if (lds <= 65536)`: 524 288 frames   sgtd_accel.hip:1864
-  FLAG_GRID 4 x CU count               remove_entries, `e->n_cus * 4`   sgtd_accel.hip:1862
+  LDS_SWITCH 65536 bytes of bitmap     remove_entries, `if (lds <= 65536)`: 524 288 frames   sgtd_accel.hip
+  FLAG_GRID 4 x CU count               remove_entries, `e->n_cus * 4`   sgtd_accel.hip
   SHARD_BLOCK 64                       SGTD_SHARD_BLOCK   multi.hip.h
 
 The model's switches (test_remove_edges.py asserts each on the workload named here, and that the plain model equals

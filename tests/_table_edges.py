@@ -13,9 +13,9 @@ Constants restated from the sources (the reach assertions of test_table_edges.py
   RS_ROUND 256, RS_TILE 4096   SGTD_RS_THREADS, SGTD_RS_TILE   table_kernels.hip.h:123-125
   SCAN_BLOCK 2048              SGTD_SCAN_THREADS x SGTD_SCAN_ITEMS   table_kernels.hip.h:21-22
   RUN_MAX 48                   SGTD_RUN_MAX   table_kernels.hip.h:290
-  HASH_MIN 1024                build_segment, `u32 cap = 1024; while (cap < 2ull * U)`   sgtd_accel.hip:810
-  BLOCK_MAX 4 MiB              copy_in, `bo.total <= (4u << 20)`   sgtd_accel.hip:622
-  RANK_BITS 13                 build_idmap   sgtd_accel.hip:834
+  HASH_MIN 1024                build_segment, `u32 cap = 1024; while (cap < 2ull * U)`   sgtd_accel.hip
+  BLOCK_MAX 4 MiB              copy_in, `bo.total <= (4u << 20)`   sgtd_accel.hip
+  RANK_BITS 13                 build_idmap   sgtd_accel.hip
   REMOVE_TILE 1024             remove_kernels.hip.h
 """
 import numpy as np

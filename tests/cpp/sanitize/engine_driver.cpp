@@ -363,6 +363,16 @@ void hook(const char *name, void **args, void *user) {
     } else {
       *B.rec_cursor() = B.rec_cap / 2;
     }
+  } else if (strstr(name, "remove_flag_kernel")) {
+    // the survivors = (count of the last tile) + (exclusive scan at the last tile): with no scan running both reads see this word —
+    // a quarter of the entries, so half of them "survive"; every frame of the span has entries
+    const long long E = *static_cast<long long *>(args[1]);
+    const u32 span = *static_cast<u32 *>(args[4]);
+    u32 *count = *static_cast<u32 **>(args[6]), *present = *static_cast<u32 **>(args[7]);
+    const size_t tiles = ((size_t)E + 1023) / 1024, words = ((size_t)span + 31) / 32;
+    REQUIRE(sgtd_stub_block_size(count) >= tiles * sizeof(u32) && sgtd_stub_block_size(present) >= words * sizeof(u32));
+    count[tiles - 1] = (u32)(E / 4);
+    memset(present, 0xFF, words * sizeof(u32));
   } else if (strstr(name, "small_order_kernel")) {
     // a one-frame batch clears its counters inside this kernel (the general form: a memset, which the stand-in performs)
     const kernels_of_the_engine::SmallOrder &O = *static_cast<const kernels_of_the_engine::SmallOrder *>(args[1]);
@@ -2221,6 +2231,22 @@ int main(int argc, char **argv) {
   }
   OK(sgtd_destroy(l));
   remove(path.c_str());
+
+  // ---- sgtd_remove_frames: every field compacted into a scratch buffer that takes the field's place; the old buffers, the keep
+  // masks and the tile counts are freed by the call, the two bitmaps stay with the handle
+  {
+    sgtd_handle t = nullptr;
+    OK(sgtd_create(&cfg, &t));
+    for (int f = 0; f < 4; f++) { Descs d = random_descs(rng, 300, (uint32_t)f); sgtd_desc_soa s = d.soa(); OK(sgtd_add(t, &s, 300)); }
+    const size_t blocks = sgtd_stub_device_blocks();
+    const uint32_t gone[2] = {1, 900};          // (900: outside the table's frames)
+    int64_t removed = -1;
+    OK(sgtd_remove_frames(t, gone, 2, &removed));
+    REQUIRE(removed == 1200 - 2 * (1200 / 4) && sgtd_stub_device_blocks() == blocks + 2);
+    OK(sgtd_get_stats(t, &st));
+    REQUIRE(st.n_entries == 1200 - removed);
+    OK(sgtd_destroy(t));
+  }
 
   // ---- two "devices" behind one handle (both shards on the stand-in's device 0): add, finalize, a batch, the verification
   {

@@ -66,7 +66,7 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason="needs the ROCm compilers (host-only compile of the engine)")
 def test_engine_host_code_under_asan_and_ubsan(tmp_path):
-    """sgtd_accel.hip + multi_impl.hip.h — the engine's ~3 200 lines of host orchestration — compiled for the host only with the
+    """sgtd_accel.hip + multi_impl.hip.h — the engine's host orchestration — compiled for the host only with the
     sanitizers on and linked against tests/cpp/sanitize/hip_stub.cpp (device memory = zeroed host memory, kernels = a hook that
     leaves behind what a scenario needs): tables frame by frame with tail segments and their merge, batches whose sweep / whose
     reservations / whose candidate pairs outgrow the work buffers (re-runs, growth), the verification on a batch of 4e7 stand-in
