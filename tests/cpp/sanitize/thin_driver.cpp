@@ -1,12 +1,14 @@
 // thin_driver.cpp — the host code of sgtd_thin_clouds and its getters (sgtd_accel.hip) under ASan + UBSan, against
 // hip_stub.cpp.  "Device" memory is host memory there and no kernel runs, so the launch hook below does on the host what
-// the call's last two kernels would if every finite point were a cell of its own (thin_offsets_kernel: out_off = pt_off;
-// thin_sum_kernel: the points as they are): enough for the call to size, fill and hand out its output, so that every copy
-// the host code makes is checked by the sanitizer against the real size of the allocation.  Covered: the getters before a
-// run, every argument error with the earlier results intact, both caps, an empty batch, empty clouds, host and "device"
+// the call's kernels would if every finite point were a cell of its own and every other point were dropped
+// (thin_keys_kernel: the drop counts; thin_offsets_kernel: out_off = the finite points before pt_off; thin_sum_kernel: the
+// finite points as they are): enough for the call to size, fill and hand out its output, so that every copy the host
+// code makes is checked by the sanitizer against the real size of the allocation.  Covered: the getters before a run,
+// every argument error with the earlier results intact, both caps, an empty batch, empty clouds, host and "device"
 // input, stride 3 and 4, a larger call after a smaller one, capacity one short, every output NULL, the timed form, a
-// view, destroy with no device block left.  Compiled for the host only and run by hand, the way
-// tests/test_store_sanitize.py builds store_driver.cpp; no test builds it.
+// view, and one handle through a shrinking size, a batch with every point dropped (K = 0), a growing size, a change of
+// stride and 256 clouds; destroy with no device block left.  Compiled for the host only, the way
+// tests/test_store_sanitize.py builds store_driver.cpp; tests/test_thin_sanitize.py builds and runs it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,7 +33,12 @@ static sgtd_handle g_h = nullptr;
 
 namespace {
 int g_sums = 0;
-long long g_total = 0;      // the points of the call being run
+// the call being run, as thin_keys_kernel was handed it
+const float *g_pts = nullptr;
+const long long *g_off = nullptr;
+int g_stride = 0, g_clouds = 0;
+
+bool finite_point(const float *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
 
 // `kernel` is the function the (mangled) name names
 bool names(const char *name, const char *kernel) {
@@ -40,17 +47,35 @@ bool names(const char *name, const char *kernel) {
 }
 
 void hook(const char *name, void **args, void *) {
-  if (names(name, "thin_offsets_kernel")) {
+  if (names(name, "thin_keys_kernel")) {
+    g_pts = *static_cast<const float **>(args[0]);
+    g_stride = *static_cast<int *>(args[1]);
+    g_off = *static_cast<const long long **>(args[2]);
+    g_clouds = *static_cast<int *>(args[3]);
+    int *dropped = *static_cast<int **>(args[10]);
+    for (int s = 0; s < g_clouds; s++)
+      for (long long i = g_off[s]; i < g_off[s + 1]; i++)
+        if (!finite_point(g_pts + i * g_stride)) dropped[s * 2]++;
+  } else if (names(name, "thin_offsets_kernel")) {
     const long long *pt_off = *static_cast<const long long **>(args[1]);
     const int n_clouds = *static_cast<int *>(args[2]);
     long long *out_off = *static_cast<long long **>(args[3]);
-    for (int s = 0; s <= n_clouds; s++) out_off[s] = pt_off[s];
-    g_total = pt_off[n_clouds];
+    REQUIRE(pt_off == g_off && n_clouds == g_clouds);
+    long long kept = 0;
+    for (int s = 0; s <= n_clouds; s++) {
+      out_off[s] = kept;
+      for (long long i = pt_off[s]; s < n_clouds && i < pt_off[s + 1]; i++) kept += finite_point(g_pts + i * g_stride);
+    }
   } else if (names(name, "thin_sum_kernel")) {
     const float *pts = *static_cast<const float **>(args[0]);
     float *out = *static_cast<float **>(args[5]);
     const int stride = strstr(name, "Li4E") ? 4 : 3;
-    for (long long i = 0; i < g_total * stride; i++) out[i] = pts[i];
+    REQUIRE(pts == g_pts && stride == g_stride);
+    for (long long i = 0; i < g_off[g_clouds]; i++)
+      if (finite_point(pts + i * stride)) {
+        std::memcpy(out, pts + i * stride, stride * sizeof(float));
+        out += stride;
+      }
     g_sums++;
   }
 }
@@ -61,14 +86,40 @@ std::vector<float> cloud(int tag, long long n, int stride) {
   return v;
 }
 
-void expect(sgtd_handle h, const std::vector<float> &pts, const std::vector<int64_t> &off, int stride) {
+// what the hook makes of a call: the finite points, their offsets, the drop counts
+struct Want {
+  std::vector<float> pts;
+  std::vector<int64_t> off;
+  std::vector<int32_t> dropped;
+};
+
+Want want_of(const std::vector<float> &pts, const std::vector<int64_t> &off, int stride) {
+  Want w;
+  const int S = (int)off.size() - 1;
+  w.off.assign((size_t)S + 1, 0);
+  w.dropped.assign((size_t)S * 2, 0);
+  for (int s = 0; s < S; s++) {
+    for (int64_t i = off[(size_t)s]; i < off[(size_t)s + 1]; i++) {
+      const float *p = pts.data() + (size_t)i * stride;
+      if (finite_point(p)) w.pts.insert(w.pts.end(), p, p + stride);
+      else w.dropped[(size_t)s * 2]++;
+    }
+    w.off[(size_t)s + 1] = (int64_t)(w.pts.size() / (size_t)stride);
+  }
+  return w;
+}
+
+void expect(sgtd_handle h, const std::vector<float> &raw, const std::vector<int64_t> &raw_off, int stride) {
+  const Want w = want_of(raw, raw_off, stride);
+  const std::vector<float> &pts = w.pts;
+  const std::vector<int64_t> &off = w.off;
   const int S = (int)off.size() - 1;
   int64_t n = -1;
   std::vector<int64_t> got_off((size_t)S + 1, -1);
   std::vector<int32_t> dropped((size_t)S * 2 + 1, -1);
   OK(sgtd_result_thinned(h, got_off.data(), nullptr, dropped.data(), 0, &n));
   REQUIRE(n == off.back() && got_off == off);
-  for (int s = 0; s < S * 2; s++) REQUIRE(dropped[(size_t)s] == 0);
+  for (int s = 0; s < S * 2; s++) REQUIRE(dropped[(size_t)s] == w.dropped[(size_t)s]);
   REQUIRE(dropped[(size_t)S * 2] == -1);
   std::vector<float> out((size_t)n * stride + 1, -7.f);
   OK(sgtd_result_thinned(h, nullptr, out.data(), nullptr, n, nullptr));
@@ -152,6 +203,36 @@ int main() {
   g_h = h;
   expect(h, a, off_a, 3);
   REQUIRE(g_sums == 4);
+  // one handle, call after call: a small call after a large one, every point dropped (nothing kept: no sum runs), a
+  // larger call than any before, another stride, 256 clouds
+  const std::vector<int64_t> off_c = {0, 4, 10};
+  const std::vector<float> c = cloud(3, 10, 3);
+  OK(sgtd_thin_clouds(h, b.data(), 4, off_b.data(), 2, 0.5, 0));
+  expect(h, b, off_b, 4);
+  OK(sgtd_thin_clouds(h, c.data(), 3, off_c.data(), 2, 0.25, 0));
+  expect(h, c, off_c, 3);
+  const std::vector<int64_t> off_d = {0, 100, 100, 250};
+  std::vector<float> d = cloud(4, 250, 3);
+  for (size_t i = 0; i < 250; i++) d[i * 3 + i % 3] = i % 2 ? NAN : INFINITY;
+  OK(sgtd_thin_clouds(h, d.data(), 3, off_d.data(), 3, 0.25, 0));
+  expect(h, d, off_d, 3);
+  REQUIRE(g_sums == 6);
+  OK(sgtd_result_thinned(h, nullptr, nullptr, nullptr, 0, &n));
+  REQUIRE(n == 0);
+  const std::vector<int64_t> off_e = {0, 1, 29999, 30000};
+  std::vector<float> e = cloud(5, 30000, 3);
+  e[0] = NAN;                                // the first point dropped
+  e[(size_t)29999 * 3 + 2] = -INFINITY;      // and the last
+  OK(sgtd_thin_clouds(h, e.data(), 3, off_e.data(), 3, 0.25, 1));
+  expect(h, e, off_e, 3);
+  std::vector<int64_t> off_f(257);
+  for (size_t s = 0; s <= 256; s++) off_f[s] = (int64_t)(s * 3 - (s > 100 ? 3 : 0) + (s == 256 ? 3 : 0));      // cloud 100 empty, cloud 255 of six points
+  std::vector<float> f = cloud(6, off_f[256], 4);
+  for (int64_t i = 0; i < off_f[256]; i += 7) f[(size_t)i * 4 + 1] = NAN;
+  f[(size_t)(off_f[256] - 1) * 4] = INFINITY;
+  OK(sgtd_thin_clouds(h, f.data(), 4, off_f.data(), 256, 0.5, 0));
+  expect(h, f, off_f, 4);
+  REQUIRE(g_sums == 8);
   OK(sgtd_destroy(view));
   OK(sgtd_destroy(h));
   REQUIRE(sgtd_stub_device_blocks() == 0);
